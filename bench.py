@@ -2,10 +2,17 @@
 """bench.py — Mpixels/s of the gfx950 sphere-tracer on BASELINE.json's configs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|orbit]
-                    [--transport dist|cabi] [--emulate-root-of N]
+                    [--transport dist|cabi] [--emulate-root-of N] [--full] [--dump-outputs DIR]
 
 A step = one frame of the hot path (camera ray → march → normal → shadows/Phong → gamma →
 XRGB8888) rendered from the scene already resident on the device, into a device framebuffer.
+K timed steps (default 20; the orbit: one pass, 256 frames), `ms_per_step` = wall time of the K steps / K.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds, on one GPU, the legs that
+measure or check more than the headline figure, each with runs of its own: the cold start-up leg (`startup`),
+the other kernel (`kernels`), the fixed tile orders (`scheduling`, `value_new_view`), frames in flight, the
+host surface, and the CPU oracle (`cpu_baseline`, `valu`, `orbit_parity`; --no-cpu-baseline drops it).
+--dump-outputs DIR writes the frame of the last timed step as DIR/frame_rgb.npy (see dump_outputs).
 
   N = 1   workload "c3": tests/golden/scenes/scene4.lol, 3840x2160, 256 march steps — the config
           BASELINE.json's metric is quoted on.
@@ -24,7 +31,7 @@ XRGB8888) rendered from the scene already resident on the device, into a device 
                          1-rank RCCL group, assembles the whole frame — the root's cadence and host cost per frame.
 
 The JSON line carries `roofline` (HBM-write roofline named by BASELINE.json: 4 B per pixel over the
-render kernel's average launch duration measured with HIP events on the launch stream) and
+render kernel's average launch duration measured with HIP events on the launch stream) and, with --full,
 `cpu_baseline` (the CPU oracle — a bit-faithful port of naive_renderer.c — on the host cores, on a
 bounded row sample of the same frame).  This path is VALU-bound, not HBM-bound; `valu` describes the
 MACHINE: the share of the SIMDs' raw issue rate the kernel reaches (2 cycles per wave64 VALU instruction
@@ -71,6 +78,29 @@ WORKLOADS = {
     "c4": dict(scene="scene4", w=7680, h=4320, max_steps=256),
     "orbit": dict(scene="scene4", w=3840, h=2160, max_steps=256, frames=256),
 }
+DEFAULT_STEPS = 20              # timed steps when --steps is not given (the orbit: one pass over its frames)
+
+# --dump-outputs: at most this many pixels of the frame, 3 float32 channels each (48 MiB; a C3 frame has 8,294,400 pixels)
+DUMP_PIXELS = 1 << 22
+
+
+def dump_pixel_index(h: int, w: int) -> np.ndarray:
+    """The pixels --dump-outputs writes, as row-major indices in increasing order: every pixel of a frame of at most
+    DUMP_PIXELS, else a fixed sample of DUMP_PIXELS of them (seed 0), the same in every run of the same size."""
+    n = h * w
+    if n <= DUMP_PIXELS:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, DUMP_PIXELS, replace=False))
+
+
+def dump_outputs(out_dir: str, frame) -> None:
+    """--dump-outputs: the XRGB8888 frame the last timed step rendered (what a caller of the render path receives) as
+    out_dir/frame_rgb.npy — float32 [n, 3], the R, G, B channel values 0 ... 255 of the pixels dump_pixel_index names."""
+    h, w = frame.shape
+    px = frame.reshape(-1).cpu().numpy().view(np.uint32)[dump_pixel_index(h, w)]
+    rgb = np.stack([(px >> 16) & 0xFF, (px >> 8) & 0xFF, px & 0xFF], axis=1).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_rgb.npy"), rgb)
 
 
 def orbit_camera(i: int, n: int = 256) -> S.Camera:
@@ -764,6 +794,8 @@ def run_cabi(args, record_fd):
     run(args.steps)
     dt = time.perf_counter() - t0
     watchdog.stage("checks")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, frames[(args.steps - 1) % 2])
     # outside the timed region, by default (LOL_BENCH_CHECK=0 skips it): the frame assembled from every device's bands must
     # equal ONE launch of the whole frame on device 0
     check = None
@@ -802,14 +834,27 @@ def run_cabi(args, record_fd):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None,
+                    help=f"timed steps (default {DEFAULT_STEPS}; the orbit: one pass over its {WORKLOADS['orbit']['frames']} frames)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None, choices=list(WORKLOADS))
     ap.add_argument("--band-rows", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--transport", default="dist", choices=["dist", "cabi"])
     ap.add_argument("--emulate-root-of", type=int, default=0, metavar="N")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the timed steps, the legs that measure or check more than the headline figure")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame of the last timed step as DIR/frame_rgb.npy")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.emulate_root_of:
+        ap.error("--dump-outputs: --emulate-root-of renders the root's share of a frame, not a whole frame")
+    if args.steps is None and (args.workload != "orbit" or args.transport == "cabi"):
+        args.steps = DEFAULT_STEPS
 
     if args.transport == "cabi":
         sys.stdout.flush()
@@ -862,7 +907,7 @@ def main():
     w, h, max_steps = cfg["w"], cfg["h"], cfg["max_steps"]
     sc = S.Scene.parse_file(os.path.join(ROOT, "tests", "golden", "scenes", cfg["scene"] + ".lol"))
     startup = None
-    if world == 1 and not emulate and os.environ.get("LOL_BENCH_STARTUP", "1") != "0":
+    if args.full and world == 1 and not emulate and os.environ.get("LOL_BENCH_STARTUP", "1") != "0":
         try:
             startup = startup_times(sc, w, h, max_steps, local_rank)  # before this process has compiled the scene
         except Exception as e:                                    # noqa: BLE001 — an extra of the record must not cost the line
@@ -922,9 +967,12 @@ def main():
                                              assembler=assembler, kernel_streams=kstreams)
 
     if orbit:
-        frames_total = cfg["frames"]
+        # K frames of the orbit (default: one pass), striped over the ranks; frame i has camera i of the orbit, modulo its length
+        frames_total = args.steps or cfg["frames"]
+        if frames_total < world:
+            raise SystemExit(f"--workload orbit --steps {frames_total}: fewer frames than the {world} ranks")
         my_frames = list(range(rank, frames_total, world))
-        cams = [sc.frame_camera(w, h, orbit_camera(i, frames_total)) for i in my_frames]
+        cams = [sc.frame_camera(w, h, orbit_camera(i % cfg["frames"], cfg["frames"])) for i in my_frames]
     else:
         cams = [sc.frame_camera(w, h)]
     # The orbit's frames are independent (BASELINE.json config 5: "frames striped", no per-frame collective): a rank keeps
@@ -1045,6 +1093,11 @@ def main():
         print("[force-pipe] 1-rank nccl gather path completed", file=sys.stderr, flush=True)
     # ---- everything below is outside the timed region ----
     watchdog.stage("checks")
+    if args.dump_outputs:
+        last = ring[(steps - 1) % fif] if not piped else pipe.drain()      # (piped: the frame assembled on rank 0, None elsewhere)
+        if last is not None:
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, last)
     if fif > 1:
         r.set_frames_in_flight(1)
     # Correctness of what was just timed, by default (LOL_BENCH_CHECK=0 skips it; the driver's plain `bench.py --gpus N` gets it):
@@ -1056,7 +1109,7 @@ def main():
     # there (frame i in ring[i % fif]) — the frames that were TIMED, not renders made again afterwards (round-5 advisor)
     orbit_timed = None
     if orbit and ring is not None and steps >= fif:
-        orbit_timed = [(my_frames[i], ring[i % fif].clone()) for i in range(steps - fif, steps)]
+        orbit_timed = [(my_frames[i] % cfg["frames"], ring[i % fif].clone()) for i in range(steps - fif, steps)]
     if check_on and pipe is not None and not pipe.single and not emulate:
         final = pipe.drain()
         if rank == 0:
@@ -1076,10 +1129,10 @@ def main():
         if rank == 0:
             frames_equal, compared = True, 0
             for rk in range(world):
-                theirs = list(range(rk, cfg["frames"], world))
+                theirs = list(range(rk, frames_total, world))
                 for k, got in zip((theirs[0], theirs[-1]), sums[rk]):
                     r.render_into(probe.data_ptr(), w, h, max_steps, stream=stream,
-                                  frame_camera=sc.frame_camera(w, h, orbit_camera(k, cfg["frames"])))
+                                  frame_camera=sc.frame_camera(w, h, orbit_camera(k % cfg["frames"], cfg["frames"])))
                     torch.cuda.synchronize()
                     frames_equal = frames_equal and frame_checksum(probe) == got
                     compared += 1
@@ -1111,8 +1164,8 @@ def main():
         "tile_order_code": {"rows": 0, "cols": 1, "auto": 2, "lpt": 3}[tile["order"]], "tile_rows_ms": tile["trial_ms"]["rows"],
         "tile_cols_ms": tile["trial_ms"]["cols"], "tile_deciding": tile["deciding"]}, dev)
     if orbit:
-        total_px = cfg["frames"] * w * h              # all ranks together render each frame once
-        steps_reported = cfg["frames"]
+        total_px = frames_total * w * h               # all ranks together render each frame once
+        steps_reported = frames_total
     else:
         total_px = steps * w * h
         steps_reported = steps
@@ -1130,7 +1183,8 @@ def main():
             "warmup": args.warmup, "ms_per_step": round(dt / steps_reported * 1e3, 4), "higher_is_better": True,
             "scaling": "weak" if orbit else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{name}: tests/golden/scenes/{cfg['scene']}.lol {w}x{h}, {max_steps} march steps"
-                                   + (f", {cfg['frames']}-frame orbit striped over ranks, a new camera every frame, {fif} frame(s) in flight per rank" if orbit else
+                                   + (f", {cfg['frames']}-frame orbit" + (f" ({frames_total} frames timed)" if frames_total != cfg["frames"] else "")
+                                      + f" striped over ranks, a new camera every frame, {fif} frame(s) in flight per rank" if orbit else
                                       (f", rows in bands of {band} ({P.root_band or band} for rank 0) over {P.world} ranks + RCCL gather to rank 0"
                                        if P is not None else ", one kernel launch per frame")
                                       + ", STILL CAMERA: the same view frame after frame (every pixel computed again in every frame; the "
@@ -1197,21 +1251,22 @@ def main():
                 out[key] = {"error": f"{type(e).__name__}: {e}"}
                 print(f"[bench] the `{key}` leg failed: {type(e).__name__}: {e}", file=sys.stderr, flush=True)
 
-        if world == 1 and not orbit and local is not None:       # (local is None in the 1-rank gather rehearsal)
+        full = args.full and world == 1                          # the legs below run with --full only
+        if full and not orbit and local is not None:             # (local is None in the 1-rank gather rehearsal)
             leg("kernels", lambda: out.__setitem__("kernels", both_kernels(r, sc, local, w, h, max_steps, cams[0], stream, k_avg, px_per_launch)))
         # `value` is the rate of a view that REPEATS (the workload BASELINE.json names: one camera); the rate of a frame whose camera
         # has just moved stands beside it at the top level: the same frame in the better fixed tile order, same context, same run
         out["value_new_view"] = None
         if orbit:
             out["value_new_view"] = out["value"]          # every frame of the orbit has a new camera
-        if world == 1 and not orbit and local is not None and tile["mode"] == "lpt" and os.environ.get("LOL_BENCH_SCHEDULING", "1") != "0":
+        if full and not orbit and local is not None and tile["mode"] == "lpt" and os.environ.get("LOL_BENCH_SCHEDULING", "1") != "0":
             def sched_leg():
                 out["scheduling"] = scheduling_rates(r, local, w, h, max_steps, cams[0], stream, k_avg, px_per_launch)
                 out["value_new_view"] = out["scheduling"]["new_view_mpixels_per_s"]
                 out["value_new_view_note"] = ("Mpixels/s of the same frame when its camera has just moved: no costs of a frame before, the better "
                                               "of the two fixed tile orders (`scheduling`); `value` is the repeated view")
             leg("scheduling", sched_leg)
-        if world == 1 and not orbit and local is not None and os.environ.get("LOL_BENCH_FRAMES_IN_FLIGHT_LEG", "1") != "0":
+        if full and not orbit and local is not None and os.environ.get("LOL_BENCH_FRAMES_IN_FLIGHT_LEG", "1") != "0":
             def fif_leg():
                 out["frames_in_flight"] = frames_in_flight_rates(r, sc, cfg)
                 mv = out["frames_in_flight"].get("moving_camera")
@@ -1220,11 +1275,11 @@ def main():
                     # a camera that moves EVERY frame, two frames in flight on the library's own streams
                     out["value_moving_camera_2_in_flight"] = mv["2_in_flight_mpixels_per_s"]
             leg("frames_in_flight", fif_leg)
-        if world == 1 and not args.no_cpu_baseline and orbit and orbit_timed:
+        if full and not args.no_cpu_baseline and orbit and orbit_timed:
             def orbit_parity_leg():
                 out["orbit_parity"] = orbit_parity(r, sc, cfg, orbit_timed, stream)
             leg("orbit_parity", orbit_parity_leg)
-        if world == 1 and not args.no_cpu_baseline and not orbit and local is not None:
+        if full and not args.no_cpu_baseline and not orbit and local is not None:
             def cpu_leg():
                 base, ctr = cpu_baseline(sc, cfg, gpu_frame=local.cpu().numpy().view(np.uint32))
                 out["cpu_baseline"] = base
@@ -1233,7 +1288,7 @@ def main():
             leg("cpu_baseline", cpu_leg)
         if startup is not None:
             out["startup"] = startup
-        if world == 1 and local is not None and os.environ.get("LOL_BENCH_HOST_SURFACE", "1") != "0":
+        if full and local is not None and os.environ.get("LOL_BENCH_HOST_SURFACE", "1") != "0":
             def host_leg():
                 torch.cuda.synchronize()
                 hs_cams = [orbit_camera(i, 256) for i in range(0, 256, 16)] if orbit else None

@@ -37,6 +37,9 @@ Outputs (all DATA — inputs and expected outputs, no reference source text):
                         held together), stepped the way main.c's update_camera does (main.c:70-112) with every vector
                         operation a call into the reference's compiled vec.h (v3cross, v3normalize, v3add, v3scale) —
                         pins the host-side keyboard → camera step of integration/lol_host_input.h.
+  ref_scene_programs.json  the four example scenes as the REFERENCE's scene.c builds them, converted by our
+                        integration/lol_refscene.c and flattened: the program's tables and the camera, as hex
+                        (tests/test_refscene.py holds the build's own .lol reader against them).
   oracle_frames.npz     XRGB8888 frames + float RGB of the CPU ORACLE (not of the reference:
                         naive_renderer.c cannot be built here) — regression fixtures that
                         pin the oracle's output across toolchains / on the GPU box.
@@ -533,6 +536,38 @@ def gen_camera_path(ref, cam7):
     return out
 
 
+def converted_program(ref, name):
+    """scene `name` built by the reference's scene.c (Walker), converted by integration/lol_refscene.c and flattened:
+    (Program.tables() bytes, lol_camera bytes).  The caller frees nothing: the program and both scenes are freed here."""
+    from loltracer_amd import scene as S
+    ref.lol_scene_from_reference.argtypes = [C.c_void_p]
+    ref.lol_scene_from_reference.restype = C.POINTER(S.SceneStruct)
+    ref.lol_scene_flatten.argtypes = [C.POINTER(S.SceneStruct), C.POINTER(S.Program)]
+    ref.lol_scene_flatten.restype = C.c_int
+    ref.lol_scene_free.argtypes = [C.POINTER(S.SceneStruct)]
+    ref.lol_program_free.argtypes = [C.POINTER(S.Program)]
+    rsc = Walker(ref, open(os.path.join(HERE, "scenes", name + ".lol")).read()).run()
+    conv = ref.lol_scene_from_reference(rsc)
+    assert conv, name
+    prog = S.Program()
+    assert ref.lol_scene_flatten(conv, C.byref(prog)) == S.LOL_OK, name
+    tables, camera = prog.tables(), bytes(conv.contents.camera)
+    ref.lol_program_free(C.byref(prog))
+    ref.lol_scene_free(conv)
+    ref.ref_scene_free(rsc)
+    return tables, camera
+
+
+def write_converted_programs(ref):
+    with open(os.path.join(HERE, "ref_scene_programs.json"), "w") as f:
+        progs = {n: dict(zip(("tables", "camera"), (b.hex() for b in converted_program(ref, n))))
+                 for n in ("scene", "scene2", "scene3", "scene4")}
+        json.dump({"source": "the reference's scene.c builders via oracle/_ref/liblol_ref.so, converted by integration/lol_refscene.c "
+                             "(lol_scene_from_reference) and flattened (lol_scene_flatten)",
+                   "format": "tables = loltracer_amd.scene.Program.tables(), camera = the lol_camera struct; both as hex",
+                   "programs": progs}, f, indent=1)
+
+
 def main():
     if not os.path.exists(REF_SO):
         raise SystemExit("oracle/_ref/liblol_ref.so missing: run `make -C oracle ref` where /root/reference exists")
@@ -588,6 +623,7 @@ def main():
     with open(os.path.join(HERE, "ref_scenes.json"), "w") as f:
         json.dump({"source": "reference scene.c builders via oracle/_ref/liblol_ref.so", "abi_sizes": sizes,
                    "scenes": scenes}, f, indent=1)
+    write_converted_programs(ref)
 
     import oracle_lib as O
     from loltracer_amd import scene as S
@@ -600,7 +636,8 @@ def main():
         if w == 64:
             frames[f"{name}_{w}x{h}_rgb"] = rgb
     np.savez_compressed(os.path.join(HERE, "oracle_frames.npz"), **frames)
-    print("wrote ref_primitives.json, ref_scenes.json, ref_sdf_points.json, ref_pixels.json, ref_frames.npz, ref_camera_path.json, oracle_frames.npz")
+    print("wrote ref_primitives.json, ref_scenes.json, ref_sdf_points.json, ref_pixels.json, ref_frames.npz, ref_camera_path.json, "
+          "ref_scene_programs.json, oracle_frames.npz")
 
 
 if __name__ == "__main__":

@@ -191,6 +191,26 @@ def test_frame_checksum_sees_single_pixels_and_their_position():
     assert bench.frame_checksum(neg) == bench.frame_checksum(neg.clone())
 
 
+def test_dump_outputs_writes_the_channels_of_a_fixed_sample_within_64_mb(tmp_path):
+    """--dump-outputs: float32 R, G, B of every pixel of a small frame; of the same seeded sample of a C3 / C4 frame every run."""
+    import numpy as np
+    small = torch.arange(1080 * 1920, dtype=torch.int32).reshape(1080, 1920) * 0x010203
+    bench.dump_outputs(str(tmp_path / "c2"), small)
+    rgb = np.load(tmp_path / "c2" / "frame_rgb.npy")
+    px = small.reshape(-1).numpy().view(np.uint32)
+    assert rgb.dtype == np.float32 and rgb.shape == (1080 * 1920, 3)
+    assert np.array_equal(rgb, np.stack([px >> 16 & 255, px >> 8 & 255, px & 255], axis=1).astype(np.float32))
+    for h, w in ((2160, 3840), (4320, 7680)):
+        idx = bench.dump_pixel_index(h, w)
+        assert len(idx) * 3 * 4 <= 64 * 10 ** 6 and np.all(np.diff(idx) > 0) and idx[-1] < h * w
+        assert np.array_equal(idx, bench.dump_pixel_index(h, w))
+    big = torch.randint(0, 1 << 24, (2160, 3840), dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "c3"), big)
+    rgb = np.load(tmp_path / "c3" / "frame_rgb.npy")
+    px = big.reshape(-1).numpy().view(np.uint32)[bench.dump_pixel_index(2160, 3840)]
+    assert rgb.shape == (bench.DUMP_PIXELS, 3) and np.array_equal(rgb[:, 1], (px >> 8 & 255).astype(np.float32))
+
+
 def test_valu_record_describes_the_machine_and_has_no_fraction_above_one():
     import json
     rec = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))["kernels"]["lol_render_spec"]

@@ -57,8 +57,47 @@ def test_orbit_over_two_ranks_checks_frames_against_rank_0():
     assert out["config"]["frames_in_flight"] == 2 and out["value_new_view"] == out["value"] and out["config"]["camera"].startswith("moving")
 
 
+def _dumped_rows_equal_the_oracle(dump_dir, w, h, camera=None, rows=(1000, 1016)):
+    """The pixels of frame_rgb.npy that lie in `rows` against the CPU oracle's render of those rows (scene4, 256 steps)."""
+    import numpy as np
+
+    import bench
+    import oracle_lib as O
+    from loltracer_amd import scene as S
+    rgb = np.load(os.path.join(dump_dir, "frame_rgb.npy"))
+    idx = bench.dump_pixel_index(h, w)
+    assert rgb.dtype == np.float32 and rgb.shape == (len(idx), 3) and rgb.nbytes <= 64 * 10 ** 6
+    sc = S.Scene.parse_file(os.path.join(ROOT, "tests", "golden", "scenes", "scene4.lol"))
+    ox, _, _ = O.render_rows(sc, w, h, rows[0], rows[1], 256, camera=camera)
+    sel = (idx // w >= rows[0]) & (idx // w < rows[1])
+    px = ox.reshape(-1)[idx[sel]]
+    want = np.stack([(px >> 16) & 0xFF, (px >> 8) & 0xFF, px & 0xFF], axis=1).astype(np.float32)
+    assert sel.sum() > 1000 and np.array_equal(rgb[sel], want)
+
+
+def test_plain_line_times_its_steps_and_dumps_the_last_frame(tmp_path):
+    """A plain run (no --full) is set-up, warm-up, the K timed steps and the line — none of the legs that take runs of their
+    own — and --dump-outputs writes the frame its last timed step rendered."""
+    out, _ = _bench(["--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 7 and out["warmup"] == 2 and out["unit"] == "Mpixels/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["config"]["workload"].startswith("c3:")
+    assert abs(out["value"] - 3840 * 2160 / (out["ms_per_step"] * 1e-3) / 1e6) <= 1e-2 * out["value"]
+    for leg in ("startup", "kernels", "scheduling", "frames_in_flight", "host_surface", "cpu_baseline", "valu"):
+        assert leg not in out, leg
+    _dumped_rows_equal_the_oracle(str(tmp_path), 3840, 2160)
+
+
+def test_orbit_times_the_frames_it_is_given(tmp_path):
+    """--steps K on the orbit: K frames of it (cameras 0 ... K-1), and the dump is frame K-1."""
+    import bench
+    out, _ = _bench(["--workload", "orbit", "--steps", "5", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 5 and out["scaling"] == "weak" and out["config"]["camera"].startswith("moving")
+    _dumped_rows_equal_the_oracle(str(tmp_path), 3840, 2160, camera=bench.orbit_camera(4, 256))
+
+
 def test_default_line_carries_roofline_cpu_baseline_and_both_kernels():
-    out, _ = _bench(["--steps", "5", "--warmup", "2"])
+    """The C3 line with --full: every leg beside the headline figure."""
+    out, _ = _bench(["--steps", "5", "--warmup", "2", "--full"])
     assert out["n_gpus"] == 1 and out["unit"] == "Mpixels/s" and out["dtype"] == "f32"
     assert out["config"]["workload"].startswith("c3:")
     rf = out["roofline"]

@@ -7,7 +7,7 @@ export TMPDIR=/tmp; R=${GRAFT_REPO_ROOT:?run on the GPU box (gpurun sets GRAFT_R
 rm -rf "$O"; mkdir -p "$O"; cd /tmp
 export LOL_BENCH_HOST_SURFACE=0                     # the PMC passes time kernels; the host-surface leg has its own record
 export LOL_BENCH_FRAMES_IN_FLIGHT_LEG=0             # ... and so has the frames-in-flight leg (round 5): its frames are other frames (moving camera, fixed order)
-B="python3 $R/bench.py --steps 20 --warmup 5"
+B="python3 $R/bench.py --full --steps 20 --warmup 5"
 # The scene kernels are compiled by whichever hipRTC the process has loaded, and the one a process gets under rocprofv3 is not the
 # one a plain `python bench.py` gets (torch brings its own; the profiler preloads the system's): the same source gave three
 # different code objects that way (keys a9cd… / f6c3… / 254a…).  So the kernels the profiler times are the ones a plain run
@@ -51,7 +51,7 @@ python3 $R/tools/pmc_summary.py --merge --kernel render_interp --kernel-key $2 -
 # the counter summary of THIS run is what the records below quote (`roofline.traffic`, `valu.issue_frac`): bench.py reads
 # profiles/pmc_traffic.json, so it goes there now — on the box; the same file is copied into the repository afterwards
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
-LOL_BENCH_SCHEDULING=1 python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline 2> /dev/null | grep -o '^{.*' > $O/${TAG}_interp_c3_bench.json
+LOL_BENCH_SCHEDULING=1 python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2> /dev/null | grep -o '^{.*' > $O/${TAG}_interp_c3_bench.json
 unset LOL_GPU_SPECIALIZE
 # kernel-trace statistics of the bench's own frames only (no `scheduling` / host-surface legs: their frames are other frames),
 # so that the average can be held against the HIP-event average in the record
@@ -65,6 +65,6 @@ for n in write fetch sq sq2 sq3; do
 done
 cd $R
 unset LOL_BENCH_STARTUP LOL_BENCH_SCHEDULING LOL_BENCH_HOST_SURFACE LOL_BENCH_FRAMES_IN_FLIGHT_LEG
-python3 bench.py 2> /dev/null | grep -o '^{.*' > $O/${TAG}_spec_c3_plain_bench.json
-for w in c2 c4 orbit; do python3 bench.py --workload $w 2> /dev/null | grep -o '^{.*' > $O/${TAG}_spec_${w}_1gpu_bench.json; done
+python3 bench.py --full 2> /dev/null | grep -o '^{.*' > $O/${TAG}_spec_c3_plain_bench.json
+for w in c2 c4 orbit; do python3 bench.py --full --workload $w 2> /dev/null | grep -o '^{.*' > $O/${TAG}_spec_${w}_1gpu_bench.json; done
 ls $O | grep -v "^spec_\|^interp_\|^stats$"

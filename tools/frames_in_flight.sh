@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:?run on the GPU box (gpurun sets GRAFT_REPO_ROOT)}
 O=$R/gpurun_out/r5_fif; mkdir -p $O; cd $R
 rec() { grep -o '^{.*' | tail -1; }
 for w in c3 c2; do
-	LOL_BENCH_HOST_SURFACE=0 LOL_BENCH_STARTUP=0 timeout -k 10 300 python3 bench.py --no-cpu-baseline --workload $w 2> $O/bench_$w.err | rec > $O/bench_$w.json || exit 1
+	LOL_BENCH_HOST_SURFACE=0 LOL_BENCH_STARTUP=0 timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --workload $w 2> $O/bench_$w.err | rec > $O/bench_$w.json || exit 1
 	python3 -c "import json; d=json.load(open('$O/bench_$w.json')); print('$w value', d['value'], 'new_view', d['value_new_view'], json.dumps(d['frames_in_flight']))"
 done
 for rep in 1 2; do for n in 1 2 3 4; do
