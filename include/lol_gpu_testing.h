@@ -18,7 +18,7 @@ extern "C" {
 int lol_gpu_testing_fail_uploads(lol_gpu* ctx, int n);
 
 /* The next `n` FIRST runs of the scene compiler for a scene of the middle sizes (257 ... 1024 ops: out-of-line form first, inlined
- * form behind it) count as failed: exercises "the inlined form is compiled all the same" (lol_gpu.hip, finish_specialise). */
+ * form behind it) count as failed: exercises "the inlined form is compiled all the same" (lol_tiers.hip, apply). */
 int lol_gpu_testing_fail_first_tier(lol_gpu* ctx, int n);
 
 /* Every `stride`-th PART gets the root's band height (lol_gpu_multi_set_root_band_rows) even on ONE device, so that a

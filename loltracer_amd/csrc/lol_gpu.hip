@@ -263,224 +263,7 @@ struct Roctx {
 	}
 } g_roctx;
 
-
-/* the compiler runs of programs this context has since replaced: the finished ones are joined; `all` (lol_gpu_destroy): every
- * one is waited for.  A run cannot be left behind: hipRTC cannot be interrupted, and a thread still inside it when the process
- * exits crashes in the compiler's own teardown (comgr is loaded on first use, so its statics go BEFORE this library's — tried in
- * round 5 with a process-lifetime reaper: the C host segfaulted at exit).  What bounds the wait instead is LOL_SPEC_MAX_OPS. */
-void reap(lol_gpu* ctx, bool all) {
-	for (size_t i = 0; i < ctx->old_jobs.size();) {
-		SpecJob* j = ctx->old_jobs[i];
-		bool done;
-		{ std::lock_guard<std::mutex> lock(j->mu); done = j->done; }
-		if (done || all) {
-			if (j->th.joinable()) j->th.join();
-			delete j;
-			ctx->old_jobs.erase(ctx->old_jobs.begin() + (long)i);
-		} else i++;
-	}
-}
-
-void launch_job(SpecJob* job);
-
-/* Start compiling the specialised kernel of ctx's (just committed) program.  The previous scene's module is gone already
- * (the caller has drained the device); until finish_specialise() swaps the new one in, the interpreter renders. */
-void start_specialise(lol_gpu* ctx, const FastPaths& fast) {
-	if (ctx->spec_module) { (void)hipModuleUnload(ctx->spec_module); ctx->spec_module = nullptr; }
-	if (ctx->spec_module_old) { (void)hipModuleUnload(ctx->spec_module_old); ctx->spec_module_old = nullptr; }
-	ctx->second_tier_pending = ctx->second_tier_running = false;
-	ctx->kernel_epoch++;                                /* the interpreter renders the new scene until its kernel is there */
-	ctx->spec_fn = ctx->spec_steps_fn = nullptr;
-	ctx->spec_sdf_fn = nullptr;
-	snprintf(ctx->kernel_name, sizeof ctx->kernel_name, "render_interp");
-	ctx->spec_log.clear();
-	ctx->spec_state = 0;
-	if (ctx->job) { ctx->old_jobs.push_back(ctx->job); ctx->job = nullptr; }      /* a compile of the scene before: its result is not wanted any more */
-	reap(ctx, false);
-	const char* env = tuning_env("LOL_GPU_SPECIALIZE");
-	if (!ctx->want_spec || (env && env[0] == '0')) return;
-	/* every program up to LOL_SPEC_MAX_OPS is specialised, large ones with their SDF out of line (emit_sdf).  Beyond that the
-	 * straight-line source (two SDF bodies of ~150 bytes per op) takes hipRTC minutes, and programs no longer have a
-	 * capacity (lol_scene.h): such a scene renders on the interpreter, which reads it as data.  Not a failure: no complaint. */
-	{
-		uint32_t limit = ctx->spec_max_ops ? ctx->spec_max_ops : LOL_SPEC_MAX_OPS;
-		if (const char* e = tuning_env("LOL_GPU_SPEC_MAX_OPS")) limit = (uint32_t)strtoul(e, nullptr, 10);
-		if (ctx->h_prog.n_ops > limit) {
-			char b[160];
-			snprintf(b, sizeof b, "%u ops: above the %u the scene compiler takes on (lol_gpu_set_specialize_max_ops / LOL_GPU_SPEC_MAX_OPS); rendered by the interpreter", ctx->h_prog.n_ops, limit);
-			ctx->spec_log = b;
-			return;
-		}
-	}
-	hipDeviceProp_t prop;
-	std::string arch = "gfx950";
-	if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.gcnArchName[0]) {
-		std::string name = prop.gcnArchName;             /* e.g. "gfx950:sramecc+:xnack-" */
-		arch = name.substr(0, name.find(':'));
-	}
-	SpecJob* job = nullptr;
-	try {
-		job = new SpecJob;
-		job->prog = std::make_shared<OwnedProgram>();    /* the thread's own copy: the context may take another scene meanwhile */
-		job->prog->assign(ctx->h_prog);
-		job->fast = std::make_shared<FastPaths>(fast);
-		job->arch = arch;
-	} catch (...) { delete job; ctx->spec_log = "out of host memory"; return; }
-	{
-		char b[160];
-		snprintf(b, sizeof b, "fast paths proven on device: sqrt=%d, smin divisors=%zu (without div_fixup: %zu)\n", fast.sqrt_kind,
-		         fast.div_ok.size(), fast.div_nf_ok.size());
-		job->note = b;
-		const std::string sw = lol_gpu_tuning_switches();
-		if (!sw.empty()) job->note += "tuning switches in effect (LOL_GPU_TUNING=1): " + sw + "\n";
-	}
-	job->cull = culling_enabled(ctx->want_cull);
-	/* Two tiers for mid-size scenes (round 5).  With its SDF inlined into the three loops a scene of 257 ... 1024 ops renders
-	 * 14 - 88 % faster than with the one out-of-line function (profiles/r5_large_scene_ab.jsonl, r5_field_inline_ab.jsonl) —
-	 * and takes hipRTC 3 - 18 s instead of 0.4 - 3 s.  So such a scene gets the out-of-line kernel first and the inlined one
-	 * when that is ready: interpreter -> out-of-line kernel -> inlined kernel, each swap at a frame boundary, same pixels on
-	 * all three.  (LOL_GPU_SPEC_INLINE_MAX, a tuning switch, pins ONE form by size as before.) */
-	ctx->second_tier_pending = ctx->want_second_tier && !tuning_env("LOL_GPU_SPEC_INLINE_MAX") && ctx->h_prog.n_ops > LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS &&
-	                           ctx->h_prog.n_ops <= LOL_SPEC_INLINE_MAX_OPS;
-	ctx->second_tier_running = false;
-	job->form = ctx->second_tier_pending ? SPEC_OUT_OF_LINE : SPEC_BY_SIZE;
-	ctx->job = job;
-	ctx->spec_state = 1;
-	launch_job(job);
-}
-
-/* start the run on its own (large-stack) thread; without a thread to be had, or with LOL_GPU_ASYNC_COMPILE=0, it runs / is waited
- * for here */
-void launch_job(SpecJob* job) {
-	job->started = std::chrono::steady_clock::now();
-	auto work = [job]() {
-		bool ok = false;
-		std::vector<char> code;
-		std::string log;
-		try {
-			std::lock_guard<std::mutex> rtc(g_rtc_mutex);
-			ok = compile_spec(job->prog->p, job->fast.get(), job->arch, code, log, nullptr, job->cull, job->form);
-		} catch (...) { ok = false; log = "the scene compiler ran out of memory"; }
-		std::lock_guard<std::mutex> lock(job->mu);
-		job->compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - job->started).count();
-		job->code = std::move(code);
-		job->log = std::move(log);
-		job->ok = ok;
-		job->done = true;
-		job->cv.notify_all();
-	};
-	const char* async = tuning_env("LOL_GPU_ASYNC_COMPILE");
-	bool threaded = !(async && async[0] == '0');
-	/* LOL_GPU_ASYNC_COMPILE=0: the upload itself waits for the compiler (still on the large-stack thread) */
-	bool started = false;
-	try { started = job->th.start(work); } catch (...) { started = false; }
-	if (!started) work();                                  /* no thread to be had: compile here */
-	else if (!threaded) job->th.join();
-}
-
-/* The frame boundary: when the compiler has finished (or `wait`), load the module and switch the context over to it; a
- * scene of the middle sizes then has its second run started (the inlined form), which takes over the same way when IT is
- * done — `wait` waits for both.  Returns true when the state changed.  The device of the context is current. */
-bool finish_specialise(lol_gpu* ctx, bool wait) {
-	bool changed = false;
-	for (;;) {
-		SpecJob* job = ctx->job;
-		if (!job) return changed;
-		{
-			std::unique_lock<std::mutex> lock(job->mu);
-			if (!job->done) {
-				if (!wait) return changed;
-				job->cv.wait(lock, [job] { return job->done; });
-			}
-		}
-		if (job->th.joinable()) job->th.join();
-		ctx->job = nullptr;
-		ctx->spec_compile_ms = job->compile_ms;
-		const bool second = ctx->second_tier_running;
-		ctx->second_tier_running = false;
-		changed = true;
-		/* the scene's second run (the form with the SDF inlined) behind the first: same program and proofs */
-		auto start_second_tier = [&]() {
-			ctx->second_tier_pending = false;
-			SpecJob* next = nullptr;
-			try {
-				next = new SpecJob;
-				next->prog = job->prog; next->fast = job->fast; next->arch = job->arch; next->cull = job->cull;
-				next->form = SPEC_INLINE;
-			} catch (...) { delete next; next = nullptr; }
-			if (!next) return false;
-			ctx->job = next;
-			ctx->second_tier_running = true;
-			try { launch_job(next); } catch (...) { ctx->job = nullptr; ctx->second_tier_running = false; delete next; return false; }
-			return true;
-		};
-		/* an unexpected failure is reported once on stderr: frames still render, through the (slower) interpreter — or, when it
-		 * is the second run that failed, through the first run's kernel, which stays.  A FIRST run that fails where a second was
-		 * to follow (257 ... 1024 ops: the out-of-line form, the one the long-branch trip-wire and the dropped-options refusal of
-		 * compile_spec are about) does not cost the scene its kernel: the inlined form, which has no out-of-line function to
-		 * trip them, is compiled all the same while the interpreter renders (round-5 advisor). */
-		auto complain = [&](const std::string& why) {
-			if (second) {
-				if (ctx->spec_fn) {
-					ctx->spec_log += "(the inlined form of the kernel was not to be had: " + why + "; the out-of-line form stays)\n";
-					ctx->spec_state = 2;
-				} else {
-					ctx->spec_log += "(nor was the inlined form: " + why + ")\n";
-					ctx->spec_state = -1;
-					fprintf(stderr, "lol_gpu: scene specialisation failed, using the interpreter kernel: %s\n", ctx->spec_log.c_str());
-				}
-			} else if (ctx->second_tier_pending && start_second_tier()) {
-				ctx->spec_log = "(the out-of-line form of the kernel was not to be had: " + why + "; compiling the inlined form)\n";
-				ctx->spec_state = 1;
-			} else {
-				ctx->spec_log = why;
-				ctx->spec_state = -1;
-				ctx->second_tier_pending = false;
-				fprintf(stderr, "lol_gpu: scene specialisation failed, using the interpreter kernel: %s\n", ctx->spec_log.c_str());
-			}
-			delete job;
-		};
-		if (!second && ctx->second_tier_pending && ctx->fail_first_tier > 0) {      /* lol_gpu_testing_fail_first_tier */
-			ctx->fail_first_tier--;
-			job->ok = false;
-			job->log = "injected failure of the first run (lol_gpu_testing_fail_first_tier)";
-		}
-		if (!job->ok) { complain(job->log); if (!wait || !ctx->job) return true; continue; }
-		hipModule_t mod = nullptr;
-		hipFunction_t fn = nullptr, steps_fn = nullptr, sdf_fn = nullptr;
-		if (hipModuleLoadData(&mod, job->code.data()) != hipSuccess) { complain("hipModuleLoadData failed"); if (!wait || !ctx->job) return true; continue; }
-		if (hipModuleGetFunction(&fn, mod, "lol_render_spec") != hipSuccess) {
-			(void)hipModuleUnload(mod);
-			complain("lol_render_spec not found in the compiled module");
-			if (!wait || !ctx->job) return true;
-			continue;
-		}
-		/* (a module with one kernel: that one counts.  Asked for only where it was generated — a failed look-up leaves
-		 * hipErrorNotFound behind as the thread's last error, which the host's next HIP call would trip over — and cleared anyway) */
-		if (job->prog->p.n_ops > LOL_SPEC_TWO_KERNELS_MAX_OPS || hipModuleGetFunction(&steps_fn, mod, "lol_render_spec_steps") != hipSuccess) steps_fn = nullptr;
-		if (hipModuleGetFunction(&sdf_fn, mod, "lol_sdf_spec") != hipSuccess) sdf_fn = nullptr;
-		(void)hipGetLastError();
-		if (ctx->spec_module) {
-			/* the first tier's module: frames launched through it may still be in flight, so it is only unloaded by the next
-			 * upload (which drains the device first) or with the context */
-			if (ctx->spec_module_old) (void)hipModuleUnload(ctx->spec_module_old);      /* (cannot happen: one second tier per upload) */
-			ctx->spec_module_old = ctx->spec_module;
-		}
-		ctx->spec_module = mod;
-		ctx->spec_fn = fn;
-		ctx->spec_steps_fn = steps_fn;
-		ctx->spec_sdf_fn = sdf_fn;
-		ctx->spec_log = (second ? ctx->spec_log + "second tier (SDF inlined): " : job->note) + job->log + (job->log.empty() || job->log.back() == '\n' ? "" : "\n");
-		snprintf(ctx->kernel_name, sizeof ctx->kernel_name, "lol_render_spec");
-		ctx->spec_key = fnv_hex(job->code.data(), job->code.size());
-		ctx->spec_state = 2;
-		ctx->kernel_epoch++;
-		/* the out-of-line kernel renders from now on; the inlined form is compiled behind it */
-		if (ctx->second_tier_pending && start_second_tier()) ctx->spec_state = 5;
-		delete job;
-		if (!wait) return true;
-	}
-}
+const char* kernel_name(const lol_gpu* ctx) { return scene_kernel(ctx) ? "lol_render_spec" : "render_interp"; }
 
 }  // namespace
 
@@ -521,10 +304,6 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 		hipStream_t fs = i ? ctx->frame_streams[i] : ctx->stream;
 		if (fs) { (void)hipStreamSynchronize(fs); (void)hipStreamDestroy(fs); }
 	}
-	if (ctx->job) { ctx->old_jobs.push_back(ctx->job); ctx->job = nullptr; }
-	reap(ctx, true);                         /* a compiler thread still running is waited for: it must not outlive the library */
-	if (ctx->spec_module) (void)hipModuleUnload(ctx->spec_module);
-	if (ctx->spec_module_old) (void)hipModuleUnload(ctx->spec_module_old);
 	for (int i = 0; i < 2; i++) {
 		if (ctx->d_tables[i]) (void)hipFree(ctx->d_tables[i]);
 		if (ctx->d_mops[i]) (void)hipFree(ctx->d_mops[i]);
@@ -541,29 +320,12 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 	if (ctx->d_gamma) (void)hipFree(ctx->d_gamma);
 	if (ctx->tiles.have_events) for (hipEvent_t e : ctx->tiles.ev) (void)hipEventDestroy(e);
 	lpt_release(ctx);
-	delete ctx;
+	delete ctx;                              /* ~SpecTiers: a compiler run still going is waited for, the scene kernels unloaded */
 }
 
 const char* lol_gpu_error(const lol_gpu* ctx) { return ctx ? ctx->err : "null context"; }
 
 int lol_gpu_device(const lol_gpu* ctx) { return ctx ? ctx->device : -1; }
-
-int lol_gpu_set_specialize(lol_gpu* ctx, int enable) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	/* 0 interpreter, plain | 1 specialised + proven fast paths (default) | 3 specialised, plain | 4 interpreter + fast paths |
-	 * 5 = 1 without the second tier of a mid-size scene (the out-of-line kernel stays: nothing compiles behind it) */
-	if (enable < 0 || enable == 2 || enable > 5) return LOL_GPU_ERR_ARG;
-	ctx->want_spec = (enable == 1 || enable == 3 || enable == 5) ? 1 : 0;
-	ctx->want_fast = (enable == 1 || enable == 4 || enable == 5) ? 1 : 0;
-	ctx->want_second_tier = enable != 5;
-	return LOL_GPU_OK;
-}
-
-int lol_gpu_set_specialize_max_ops(lol_gpu* ctx, unsigned max_ops) {
-	if (!ctx || max_ops > LOL_MAX_OPS) return LOL_GPU_ERR_ARG;
-	ctx->spec_max_ops = max_ops;             /* takes effect at the next lol_gpu_upload_program */
-	return LOL_GPU_OK;
-}
 
 /* which of the wanted skips the uploaded program (and the environment) allows */
 static void resolve_skips(lol_gpu* ctx) {
@@ -591,26 +353,6 @@ int lol_gpu_set_cull(lol_gpu* ctx, int enable) {
 int lol_gpu_miss_skip_active(const lol_gpu* ctx) {
 	return ctx ? (ctx->miss_skip ? 1 : 0) | (ctx->dark_skip ? 2 : 0) | (ctx->shadow_settle ? 4 : 0) : 0;
 }
-int lol_gpu_specialize_wait(lol_gpu* ctx) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	finish_specialise(ctx, true);
-	return LOL_GPU_OK;
-}
-
-int lol_gpu_specialize_state(lol_gpu* ctx, double* compile_ms) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	if (ctx->job) {                                    /* has the compiler finished?  (the swap itself happens at a frame or a wait) */
-		std::lock_guard<std::mutex> lock(ctx->job->mu);
-		/* (while the second run is at work: what the first one took) */
-		if (compile_ms) *compile_ms = ctx->job->done ? ctx->job->compile_ms : ctx->second_tier_running ? ctx->spec_compile_ms : 0.0;
-		if (ctx->second_tier_running) return ctx->job->done ? 6 : 5;
-		return ctx->job->done ? 3 : 1;
-	}
-	if (compile_ms) *compile_ms = ctx->spec_compile_ms;
-	return ctx->spec_state;
-}
-
 static int upload_program(lol_gpu* ctx, const lol_program* prog);
 
 /* No exception crosses the C boundary: programs may have 2^20 ops, and the analysis of a scene (culling plan, the interpreter's
@@ -720,7 +462,7 @@ static int upload_program(lol_gpu* ctx, const lol_program* prog) {
 	/* the scene compiler starts on its own thread; the new scene renders on the interpreter until its kernel is there
 	 * (a failed specialisation is not an error either: the interpreter goes on rendering) */
 	try { start_specialise(ctx, fast); }
-	catch (...) { ctx->spec_state = 0; }              /* (no memory for a compiler run: the interpreter renders the scene) */
+	catch (...) {}                                    /* (no memory for a compiler run: the interpreter renders the scene) */
 	return LOL_GPU_OK;
 }
 
@@ -813,15 +555,15 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	g_roctx.init();
 	if (g_roctx.push) {
 		char label[96];
-		snprintf(label, sizeof label, "lol frame %dx%d rows=%d band=%d@%d/%d %s", w, h, n_rows, R->band_rows, R->offset_rows, R->cycle_rows, ctx->kernel_name);
+		snprintf(label, sizeof label, "lol frame %dx%d rows=%d band=%d@%d/%d %s", w, h, n_rows, R->band_rows, R->offset_rows, R->cycle_rows, kernel_name(ctx));
 		g_roctx.push(label);
 		g_roctx.ranges++;
 	}
-	if (ctx->spec_fn) {
+	if (const SceneKernel* k = scene_kernel(ctx)) {
 		void* args[] = { &L };
-		/* the step counters are compiled into lol_render_spec_steps alone (generate_source): who reads them gets that kernel */
+		/* the step counters are compiled into render_counting alone (generate_source): who reads them gets that kernel */
 		const bool counts = (dbg && dbg->steps) || L.pixel_cost;
-		e = hipModuleLaunchKernel(counts && ctx->spec_steps_fn ? ctx->spec_steps_fn : ctx->spec_fn, grid.x, grid.y, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
+		e = hipModuleLaunchKernel(counts ? k->render_counting : k->render, grid.x, grid.y, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
 	} else {
 		const int kind = ctx->interp_sqrt_kind;
 		const int cls = interp_stack_class(P.max_stack);
@@ -1075,7 +817,7 @@ int lol_gpu_memcpy_d2h(lol_gpu* ctx, void* host, const void* dev, size_t bytes) 
 	return LOL_GPU_OK;
 }
 
-const char* lol_gpu_kernel_name(const lol_gpu* ctx) { return ctx ? ctx->kernel_name : ""; }
+const char* lol_gpu_kernel_name(const lol_gpu* ctx) { return ctx ? kernel_name(ctx) : ""; }
 
 long lol_gpu_roctx_ranges(void) {
 	g_roctx.init();
@@ -1084,16 +826,11 @@ long lol_gpu_roctx_ranges(void) {
 
 const char* lol_gpu_kernel_key(const lol_gpu* ctx) {
 	if (!ctx) return "";
-	return ctx->spec_fn ? ctx->spec_key.c_str() : ctx->interp_key.c_str();
+	const SceneKernel* k = scene_kernel(ctx);
+	return k ? k->key.c_str() : ctx->interp_key.c_str();
 }
 
 int lol_gpu_abi_version(void) { return LOL_GPU_ABI_VERSION; }
-
-int lol_gpu_testing_fail_first_tier(lol_gpu* ctx, int n) {
-	if (!ctx || n < 0) return LOL_GPU_ERR_ARG;
-	ctx->fail_first_tier = n;
-	return LOL_GPU_OK;
-}
 
 int lol_gpu_testing_fail_uploads(lol_gpu* ctx, int n) {
 	if (!ctx || n < 0) return LOL_GPU_ERR_ARG;
@@ -1109,9 +846,9 @@ int lol_gpu_sdf_batch(lol_gpu* ctx, const float* pts_dev, float* dist_dev, uint3
 	uint32_t n32 = (uint32_t)n;
 	hipError_t e;
 	finish_specialise(ctx, false);
-	if (ctx->spec_fn && ctx->spec_sdf_fn) {
+	if (const SceneKernel* k = scene_kernel(ctx)) {
 		void* args[] = { &pts_dev, &dist_dev, &id_dev, &n32 };
-		e = hipModuleLaunchKernel(ctx->spec_sdf_fn, (n32 + 63) / 64, 1, 1, 64, 1, 1, 0, s, args, nullptr);
+		e = hipModuleLaunchKernel(k->sdf, (n32 + 63) / 64, 1, 1, 64, 1, 1, 0, s, args, nullptr);
 	} else {
 		const int kind = ctx->interp_sqrt_kind;
 		const int cls = interp_stack_class(ctx->h_prog.max_stack);

@@ -3,8 +3,10 @@
  * the proven shortcuts (FastPaths), and the few functions that cross from one unit to another.  Nothing here is part of the
  * C ABI (include/lol_gpu.h); everything declared between the visibility pragmas stays inside the library.
  *
- *   lol_gpu.hip      the context and the C ABI around it: upload, the tiers of the scene compiler, frames (device and host
- *                    surfaces, frames in flight), the first march step, diagnostics
+ *   lol_gpu.hip      the context and the C ABI around it: upload, frames (device and host surfaces, frames in flight), the
+ *                    first march step, diagnostics
+ *   lol_tiers.hip    the tiers of the scene compiler: its runs on their own threads, the kernels they load, the swaps at frame
+ *                    boundaries, lol_gpu_specialize_*
  *   lol_proofs.hip   the exhaustive on-device proofs of the fast paths, the gamma table, lol_gpu_verify_*
  *   lol_codegen.hip  exact culling (bounds, plan), the interpreter's macro-op lists, the scene -> HIP source generator,
  *                    hipRTC + the code-object cache + the long-branch trip-wire, lol_gpu_compile_offline
@@ -94,25 +96,6 @@ struct FastPaths {
 	}
 };
 
-struct OwnedProgram;
-/* One run of the scene compiler on a host thread (tiered start-up: start_specialise / finish_specialise below). */
-struct SpecJob {
-	std::mutex mu;
-	std::condition_variable cv;
-	bool done = false, ok = false;
-	std::vector<char> code;
-	std::string log, note;
-	std::chrono::steady_clock::time_point started;
-	double compile_ms = 0;
-	/* what the run compiles — its own copies: the context may take another scene meanwhile */
-	std::shared_ptr<OwnedProgram> prog;
-	std::shared_ptr<FastPaths> fast;
-	std::string arch;
-	bool cull = true;
-	int form = 0;                        /* SpecForm: by size, or the form a tier asks for */
-	BigStackThread th;
-};
-
 /* A program and the memory behind its four tables (lol_program itself only points: include/lol_scene.h). */
 struct OwnedProgram {
 	lol_program p{};
@@ -134,6 +117,46 @@ struct OwnedProgram {
 	OwnedProgram() = default;
 	OwnedProgram(const OwnedProgram&) = delete;
 	OwnedProgram& operator=(const OwnedProgram&) = delete;
+};
+
+/* One code object of the scene compiler, loaded with every kernel generate_source put in it or not at all (load_scene_kernel,
+ * lol_tiers.hip).  A plain value: whoever holds it calls unload(). */
+struct SceneKernel {
+	hipModule_t   module = nullptr;
+	hipFunction_t render = nullptr;            /* lol_render_spec */
+	hipFunction_t render_counting = nullptr;   /* lol_render_spec_steps — or lol_render_spec where the module holds that one alone: it counts */
+	hipFunction_t sdf = nullptr;               /* lol_sdf_spec (lol_gpu_sdf_batch) */
+	std::string   key;                         /* FNV-1a of the code object (lol_gpu_kernel_key) */
+	explicit operator bool() const { return module != nullptr; }
+	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
+};
+
+struct SpecJob;
+/* The tiers of the scene compiler: interpreter -> [out-of-line kernel ->] scene kernel (lol_tiers.hip) */
+struct SpecTiers {
+	enum Tier {
+		OFF,          /* no scene kernel wanted or possible: the interpreter renders */
+		FIRST,        /* `job` is the scene's first run */
+		SECOND,       /* `job` compiles the inlined form */
+		SETTLED,      /* nothing behind `kernel` */
+		FAILED,       /* no scene kernel to be had: the interpreter renders */
+	};
+	Tier         tier = OFF;
+	std::unique_ptr<SpecJob> job;             /* the run of tier FIRST or SECOND, until the frame boundary that takes its outcome */
+	bool         second_wanted = false;       /* the inlined form follows the first tier's kernel */
+	SceneKernel  kernel;                      /* the kernel frames run; empty: the interpreter */
+	SceneKernel  retired;                     /* the first tier's once the second has taken over: frames in flight may still run it, so it
+	                                           * stays loaded until the next upload (which drains the device) or the end of the context */
+	std::vector<std::unique_ptr<SpecJob>> old_jobs;   /* runs for programs since replaced: dropped when they have finished */
+	std::string  log;                         /* lol_gpu_specialize_log */
+	double       compile_ms = 0;              /* how long the last finished run took (wall clock of its thread) */
+	/* what the next upload asks for */
+	bool         want = true;                 /* lol_gpu_set_specialize */
+	bool         want_second = true;          /* ... (ctx, 5) says no */
+	uint32_t     max_ops = 0;                 /* lol_gpu_set_specialize_max_ops: 0 = LOL_SPEC_MAX_OPS */
+	int          fail_first = 0;              /* lol_gpu_testing_fail_first_tier: that many out-of-line first runs "fail" */
+	SpecTiers();
+	~SpecTiers();                             /* waits for every run (a thread must not outlive the library) and unloads both kernels */
 };
 
 struct lol_gpu {
@@ -171,27 +194,9 @@ struct lol_gpu {
 	hipStream_t  pipe_last_stream = nullptr;     /* ... a frame under the view of the frame before it follows that frame on its stream */
 	lol_frame_camera pipe_last_cam{};
 	int          pipe_last_geom[3] = { 0, 0, 0 };
-	int          want_spec = 1;
-	bool         want_second_tier = true; /* lol_gpu_set_specialize(ctx, 5) says no */
-	uint32_t     spec_max_ops = 0;       /* lol_gpu_set_specialize_max_ops: 0 = LOL_SPEC_MAX_OPS */
-	hipModule_t  spec_module = nullptr;
-	hipFunction_t spec_fn = nullptr;
-	hipFunction_t spec_steps_fn = nullptr;   /* lol_render_spec_steps, the same pipeline with the per-lane step counters (generate_source);
-	                                          * nullptr where the module holds one kernel only: spec_fn counts then */
-	hipFunction_t spec_sdf_fn = nullptr; /* lol_sdf_spec of the same module (lol_gpu_sdf_batch) */
-	std::string  spec_log;
-	hipModule_t  spec_module_old = nullptr;   /* the first tier's module once the second has taken over: frames in flight may still run it, so it
-	                                           * stays loaded until the next upload (which drains the device) or the end of the context */
-	bool         second_tier_pending = false; /* when the running job's kernel is in use, the INLINED form is compiled next (start_specialise) */
-	bool         second_tier_running = false; /* `job` is that second run */
-	SpecJob*     job = nullptr;       /* the scene compiler's run for the CURRENT program, until its module is swapped in */
-	std::vector<SpecJob*> old_jobs;   /* runs for programs since replaced: joined when they have finished */
-	int          spec_state = 0;         /* 0 no specialised kernel wanted / possible, 1 compiling, 2 in use, -1 failed */
-	double       spec_compile_ms = 0;    /* how long the last finished run took (wall clock of its thread) */
-	std::string  spec_key;               /* FNV-1a of the code object the frames run (lol_gpu_kernel_key) */
-	std::string  interp_key;             /* ... and of {this build, the uploaded macro-op lists} for the interpreter */
+	SpecTiers    tiers;                  /* the scene compiler's: the kernel frames run, or none (the interpreter) */
+	std::string  interp_key;             /* FNV-1a of {this build, the uploaded macro-op lists}: lol_gpu_kernel_key of the interpreter */
 	int          fail_uploads = 0;       /* lol_gpu_testing_fail_uploads: that many uploads still fail at the copy */
-	int          fail_first_tier = 0;    /* lol_gpu_testing_fail_first_tier: that many out-of-line first runs of the scene compiler "fail" */
 	int          want_fast = 1;          /* allow the proven-exact shortcuts in the specialised kernel */
 	unsigned     want_skips = 7;         /* exact skips allowed when the program qualifies: bit 0 escaped waves, 1 zero incidence, 2 settled shadows */
 	int          want_cull = 1;          /* allow the exact culling of top-level objects (plan_culling) */
@@ -281,7 +286,6 @@ struct lol_gpu {
 	int          n_frame_streams = 1;
 	unsigned     frame_rr = 0;
 	char         err[512] = { 0 };
-	char         kernel_name[64] = "render_interp";
 };
 
 /* an A/B switch from the environment, honoured only beside LOL_GPU_TUNING=1 and recorded when it is (lol_gpu.hip) */
@@ -317,7 +321,7 @@ constexpr int interp_stack_class(uint32_t max_stack) {
  * LOL_GPU_SPEC_INLINE_MAX (a tuning switch) overrides. */
 constexpr uint32_t LOL_SPEC_INLINE_MAX_OPS = 1024;
 /* ... and above THIS many ops the inlined form is the scene's SECOND kernel: the out-of-line form, which hipRTC delivers 3 - 6
- * times sooner, renders until it is there (start_specialise) */
+ * times sooner, renders until it is there (lol_tiers.hip) */
 constexpr uint32_t LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS = 256;
 /* ... and up to THIS many ops the module holds the pipeline twice: with and without the per-lane step counters (generate_source) */
 constexpr uint32_t LOL_SPEC_TWO_KERNELS_MAX_OPS = 256;
@@ -344,6 +348,16 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, std::vector<uint32_t>& lists, uint32_t& n_mops);
 std::string fnv_hex(const void* data, size_t n);
 extern std::mutex g_rtc_mutex;               /* one run of the scene compiler at a time (lol_gpu.hip) */
+
+/* ---- lol_tiers.hip */
+/* the scene compiler's first run for the program the context has just committed (the previous scene's kernels go: the caller has
+ * drained the device) */
+void start_specialise(lol_gpu* ctx, const FastPaths& fast);
+/* the frame boundary: a finished run's outcome takes effect, one per call; `wait`: every run is waited for.  True when the state
+ * changed.  The device of the context is current. */
+bool finish_specialise(lol_gpu* ctx, bool wait);
+/* the scene kernel frames run, or nullptr: the interpreter */
+inline const SceneKernel* scene_kernel(const lol_gpu* ctx) { return ctx->tiers.kernel ? &ctx->tiers.kernel : nullptr; }
 
 /* ---- lol_sched.hip */
 struct FrameTables { const uint32_t* order; uint32_t* cost; const uint32_t* lanes; unsigned short* pixel_cost; uint32_t n_waves; };

@@ -263,8 +263,6 @@ int lol_gpu_verify_gamma_table(lol_gpu* ctx, unsigned long long* mismatches, flo
 	return LOL_GPU_OK;
 }
 
-const char* lol_gpu_specialize_log(const lol_gpu* ctx) { return ctx ? ctx->spec_log.c_str() : ""; }
-
 int lol_gpu_powf_batch(lol_gpu* ctx, const float* x_dev, const float* y_dev, float* out_dev, size_t n, void* stream) {
 	if (!ctx || !x_dev || !y_dev || !out_dev) return LOL_GPU_ERR_ARG;
 	if (n == 0) return LOL_GPU_OK;

@@ -52,7 +52,7 @@ def test_abi_version_of_the_library_is_the_headers():
 
 def test_no_test_switch_is_read_from_the_environment():
     """Fault injection and test geometry are per-context setters (include/lol_gpu_testing.h), never ambient variables."""
-    for f in ("lol_gpu.hip", "lol_multi.hip"):
+    for f in ("lol_gpu.hip", "lol_tiers.hip", "lol_multi.hip"):
         src = open(os.path.join(ROOT, "loltracer_amd", "csrc", f)).read()
         assert not re.search(r'getenv\("LOL_GPU[A-Z_]*TEST', src), f
 

@@ -369,7 +369,7 @@ def test_very_large_scenes_stay_on_the_interpreter(torch_cuda, monkeypatch):
 
 
 def test_both_tiers_of_mid_size_scenes_match_the_oracle(torch_cuda, monkeypatch):
-    """Scenes of 257 ... 1024 ops get two kernels (lol_gpu.hip, start_specialise): the SDF as one out-of-line function first, the
+    """Scenes of 257 ... 1024 ops get two kernels (lol_tiers.hip, start_specialise): the SDF as one out-of-line function first, the
     SDF inlined into the three loops behind it.  Chains, fields (the culling plan's nested tests in both forms) and a union tree:
     every pixel, id, distance and step count of a frame rendered on EACH tier equals the oracle's."""
     import time
