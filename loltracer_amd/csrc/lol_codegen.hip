@@ -192,6 +192,41 @@ CullTest make_test(const Sphere& b) {
 	return t;
 }
 
+/* The culling bound carried along a ray (fast SDF, outermost run; emit_sdf).  The march and shadow loops evaluate points
+ * p(t) = fl(ro + fl(rd t)) componentwise, at t that never decrease within a loop.  With e = 2^-24, eta = 2^-150 and, for one
+ * test (centre C, float; radius rm; factor k), D(t) = |p(t) - C| in real arithmetic:
+ *   |p(t) - (ro + rd t)| <= e |rd| t + e |p(t)| + sqrt(3) eta,   |p(t)| <= D(t) + |C|
+ *   D(t) (1 + e) >= D(T) (1 - e) - |rd| ((1 + e) t - (1 - e) T) - 2 e |C| - 2 sqrt(3) eta          for t >= T >= 0.
+ * The loop checks, per wave, len2(rd) <= 1 + 2^-20 in binary32, which gives |rd| <= rho = 1 + 2^-20.  The skip is allowed when
+ * D(t) > (|best| + rm) k: that implies the premise of make_test's proof for best >= 0 and, for best < 0, the premise for
+ * best = 0 (value > 0 > best).  Divided by k (1 + e) that is
+ *   g(T) + cT T > |best| + ct t,   g(T) = (D(T)(1 - e) - 2e|C| - 2 sqrt(3) eta) / (k (1 + e)) - rm,
+ *   cT = rho (1 - e) / (k (1 + e)),  ct = rho / k.
+ * At a test the wave passed, D(T) >= s (1 - 2^-20) - 2^-74 for s = v_sqrt_f32(cl) (cl: the test's own binary32 squared length,
+ * within (1 + e)^6 and 3 eta of D^2; v_sqrt within 4 ulps), so g(T) >= s A + B per test, and the kernel keeps
+ *   lb = G - |G| 2^-20,   G = fma(T, ctt, min_j fma(s_j, A_j, B_j))
+ * with ctt = cT (1 - 2^-20): the last factor and the 2^-20 in lb cover the roundings of the three fmas.  At a later t the run is
+ * skipped where every lane has fl(fma(t, ctc, |best|)) < lb, ctc = ct (1 + 2^-20).  Constants are rounded towards the safe
+ * side.  tests/test_cull_carry_bound.py re-derives them in rational arithmetic and checks the implication there. */
+struct CarryConsts { std::vector<float> a, b; float ctt = 0.f, ctc = 0.f; };
+static float f_down(double v) { v -= fabs(v) * 0x1p-40; float f = (float)v; if ((double)f > v) f = nextafterf(f, -INFINITY); return f; }
+static float f_up(double v) { v += fabs(v) * 0x1p-40; float f = (float)v; if ((double)f < v) f = nextafterf(f, INFINITY); return f; }
+CarryConsts carry_constants(const std::vector<CullTest>& tests) {
+	const double e = 0x1p-24, rho = 1.0 + 0x1p-20;
+	CarryConsts c;
+	double ctt = INFINITY, ctc = 0.0;
+	for (const CullTest& t : tests) {
+		const double k = t.k, cn = sqrt((double)t.c[0] * t.c[0] + (double)t.c[1] * t.c[1] + (double)t.c[2] * t.c[2]) * (1.0 + 0x1p-40);
+		c.a.push_back(f_down((1.0 - 0x1p-20) * (1.0 - e) / (k * (1.0 + e))));
+		c.b.push_back(f_down(-(double)t.rm - (0x1p-73 + 2.0 * e * cn) / k));
+		ctt = fmin(ctt, rho * (1.0 - e) / (k * (1.0 + e)) * (1.0 - 0x1p-20));
+		ctc = fmax(ctc, rho / k * (1.0 + 0x1p-20));
+	}
+	c.ctt = f_down(ctt);
+	c.ctc = f_up(ctc);
+	return c;
+}
+
 std::vector<CullTest> cluster_tests(const RootBound& r) {
 	std::vector<CullTest> t;
 	for (const Sphere& c : r.clusters) t.push_back(make_test(c));
@@ -422,6 +457,20 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 	/* only the outermost test keeps a cool-down counter (wave-uniform state in the Sdf struct) */
 	char cool_decl[64] = "";
 	if (!plan.intervals.empty()) snprintf(cool_decl, sizeof cool_decl, "\tu32 cool[1] = {};\n");
+	/* ... and, in the inlined fast SDF, the culling bound carried along the ray (carry_constants): `lb` per lane, `rt` the t of the
+	 * point being evaluated, `carry` whether this loop's ray may set lb (ray_begin; lol_kernel.h, march / soft_shadow).  Out of
+	 * line the body keeps today's test: its state would be per call.  By default only where the outermost run is ONE object behind
+	 * its two cluster spheres: measured on one box, six alternating repetitions (profiles/r7_ab_cull_carry.txt), scene4 C3
+	 * +5.5 %, orbit +2.7 %, but scene.lol's group of three objects (C2) -2.7 %: its rays keep failing the group test, and the
+	 * carried check is one fma, a compare and a branch more on every test.  LOL_GPU_CULL_CARRY=0 / 1: off / on wherever inlined. */
+	bool carry = fast && !out_of_line && !plan.intervals.empty();
+	if (const char* e = tuning_env("LOL_GPU_CULL_CARRY")) carry = carry && atoi(e) != 0;
+	else carry = carry && !plan.intervals[0].both.empty();
+	std::string carry_decl;
+	if (carry)
+		carry_decl = "\tfloat lb = -__builtin_inff(), rt = 0.f;\n\tbool carry = false;\n"
+		             "\t__device__ __forceinline__ void ray_begin(V3 rd) { carry = vote(!(len2(rd) <= 0x1.00001p+0f)) == 0; }\n"
+		             "\t__device__ __forceinline__ void ray_at(float t) { rt = t; }\n";
 	if (out_of_line) {
 		/* out of line the cool-down state is per call (always 0: every evaluation tests) */
 		/* (amdgpu_waves_per_eu applies to kernels only: the function is scheduled with the default register budget) */
@@ -436,9 +485,9 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 		/* ASK_ID_ONCE: the primary march evaluates the distance alone and asks for the id of its last step once (lol_kernel.h,
 		 * march) — from three top-level objects on, where a v_min per object and step outweighs the one evaluation more per pixel
 		 * (measured: scene.lol's four objects +3.6 %, scene4's two -0.8 %; profiles/r6_ab_id_asked_once.txt) */
-		snprintf(line, sizeof line, "struct %s {\n\tstatic constexpr bool ASSUME_SETTLED = %s;\n\tstatic constexpr bool ASK_ID_ONCE = %s;\n\tRange rg;\n\tfloat nanacc = 0.f;\n%s"
-		         "\t__device__ __forceinline__ void loop_done() { %s }\n", name, fast ? "true" : "false", P.n_roots >= 3 ? "true" : "false", cool_decl,
-		         plan.intervals.empty() ? "" : "cool[0] = 0u;");
+		snprintf(line, sizeof line, "struct %s {\n\tstatic constexpr bool ASSUME_SETTLED = %s;\n\tstatic constexpr bool ASK_ID_ONCE = %s;\n\tRange rg;\n\tfloat nanacc = 0.f;\n%s%s"
+		         "\t__device__ __forceinline__ void loop_done() { %s%s }\n", name, fast ? "true" : "false", P.n_roots >= 3 ? "true" : "false", cool_decl,
+		         carry_decl.c_str(), plan.intervals.empty() ? "" : "cool[0] = 0u;", carry ? " lb = -__builtin_inff(); carry = false;" : "");
 		s += line;
 	}
 	/* The body twice where it is inlined: eval() — distance and object id — for the primary march and the normal taps, and
@@ -488,7 +537,31 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 			snprintf(line, sizeof line, "%svote(!(cl%d > cu%d * cu%d)) | vote(!(cu%d > 0.f))", votes.empty() ? "" : " | ", k, k, k, k);
 			votes += line;
 		}
-		if (with_cooldown) {
+		if (with_cooldown && carry) {
+			/* the carried bound first (one fma and one compare); where a lane fails it, the full test — which, passed by the whole
+			 * wave on a ray that may carry, sets lb anew (one v_sqrt per sphere).  A failed full test leaves lb as it is: still a
+			 * bound, only an older one. */
+			const CarryConsts cc = carry_constants(tests);
+			snprintf(line, sizeof line, "\t\t{ bool need%d = true;\n\t\t  if (cool[0] == 0u) {\n"
+			         "\t\t  if (vote(!(__builtin_fmaf(rt, %s, __builtin_fabsf(best)) < lb)) == 0) need%d = false; else {\n",
+			         k0, fbits(cc.ctc).c_str(), k0);
+			s += line;
+			s += decl;
+			snprintf(line, sizeof line, "\t\t  need%d = ((", k0);
+			s += line;
+			s += votes;
+			snprintf(line, sizeof line, ")) != 0;\n\t\t  if (need%d) cool[0] = %du;\n\t\t  else if (carry) {\n", k0, cooldown);
+			s += line;
+			for (size_t j = 0; j < tests.size(); j++) {
+				snprintf(line, sizeof line, j ? "\t\t    lm = vmin_(__builtin_fmaf(__builtin_amdgcn_sqrtf(cl%d), %s, %s), lm);\n"
+				                              : "\t\t    float lm = __builtin_fmaf(__builtin_amdgcn_sqrtf(cl%d), %s, %s);\n",
+				         k0 + (int)j, fbits(cc.a[j]).c_str(), fbits(cc.b[j]).c_str());
+				s += line;
+			}
+			snprintf(line, sizeof line, "\t\t    const float lg = __builtin_fmaf(rt, %s, lm);\n\t\t    lb = __builtin_fmaf(__builtin_fabsf(lg), -0x1p-20f, lg);\n"
+			         "\t\t  }\n\t\t  } } else cool[0]--;\n\t\t  if (need%d) {\n", fbits(cc.ctt).c_str(), k0);
+			s += line;
+		} else if (with_cooldown) {
 			snprintf(line, sizeof line, "\t\t{ bool need%d = true;\n\t\t  if (cool[0] == 0u) {\n", k0);
 			s += line;
 			s += decl;

@@ -834,6 +834,16 @@ __device__ __forceinline__ bool unproven(const Sdf& sdf) { return (vote(sdf.rg.o
 
 /* --------------------------------------------------------------- the pipeline */
 
+/* The points of a march or shadow loop lie on one ray, at t that never decrease within the loop: the march's steps are >= EPSILON
+ * or end it, and under FLAG_SHADOW_SETTLED a shadow step s < 0 makes 50 s / t < 0 and ends that march (soft_shadow).  An Sdf that
+ * carries a culling bound along the ray (lol_codegen.hip, carry_constants: the specialised kernel's fast SDF) is told where a loop's
+ * ray begins (its direction) and the t of every point it evaluates; every other Sdf ignores both.  loop_done() forgets the ray, so
+ * the normal taps and the id asked for in normal_and_id() — points that are not on a ray — use the plain test. */
+template <class S> __device__ __forceinline__ auto ray_begin(S& s, V3 rd, int) -> decltype(s.ray_begin(rd)) { s.ray_begin(rd); }
+template <class S> __device__ __forceinline__ void ray_begin(S&, V3, long) {}
+template <class S> __device__ __forceinline__ auto ray_at(S& s, float t, int) -> decltype(s.ray_at(t)) { s.ray_at(t); }
+template <class S> __device__ __forceinline__ void ray_at(S&, float, long) {}
+
 struct Hit { float dist; u32 id; u32 steps; };
 /* what march() hands on: the distance marched, the distance BEFORE its last step (the point that step evaluated), the step count,
  * and the object id as far as it is known without asking — `ask`: this lane's id is that of the object nearest to the point of
@@ -878,8 +888,10 @@ __device__ __forceinline__ Marched march(Sdf& sdf, V3 ro, V3 rd, int max_steps, 
 	float dist = skip_first ? first_dist : 0.f, prev = 0.f;
 	u32 id = skip_first ? first_id : 0u, steps = skip_first ? 1u : 0u;
 	const int first_turn = skip_first ? 1 : 0;
+	ray_begin(sdf, rd, 0);
 	for (int i = first_turn; i < max_steps; i++) {
 		V3 p = add(ro, scale(rd, dist));
+		ray_at(sdf, dist, 0);
 		float d;
 		if constexpr (Sdf::ASK_ID_ONCE) {
 			sdf.eval_dist(p, d);
@@ -934,8 +946,10 @@ __device__ __forceinline__ float soft_shadow(Sdf& sdf, V3 p, V3 dir, float max_d
 	/* res < -1 (naive_renderer.c:85) is res <= the float below -1 for every res that is not NaN (and NaN fails both) */
 	const float stop = (VMIN || settled) ? 0.f : -0x1.000002p+0f;
 	if (needed) {
+		ray_begin(sdf, dir, 0);
 		for (int i = 0; i < 128; i++) {
 			V3 q = add(ro, scale(dir, t));
+			ray_at(sdf, t, 0);
 			float s;
 			sdf.eval_dist(q, s);                         /* (the distance alone: see Interp::eval_dist / lol_codegen.hip, emit_sdf) */
 			/* The quotient 50 s / t (11 instructions, one of them v_rcp) is only needed where it can lower the minimum.  In the fast
