@@ -204,8 +204,33 @@ int lol_gpu_malloc(lol_gpu* ctx, size_t bytes, void** out);
 int lol_gpu_free(lol_gpu* ctx, void* ptr);
 int lol_gpu_memcpy_d2h(lol_gpu* ctx, void* host, const void* dev, size_t bytes);
 
+/*
+ * Supersampling: s x s samples per pixel on an ordered grid, s in {1, 2, 4} (default 1: one ray per pixel, today's frames byte
+ * for byte).  Any other s returns LOL_GPU_ERR_ARG and leaves the setting as it was (LOL_GPU_ERR_UNSUPPORTED: a library built
+ * with an experimental wave patch whose sides s does not divide).  Takes effect at the next frame of
+ * lol_gpu_render_device, lol_gpu_render_host and lol_gpu_render_host_begin; a frame already begun keeps the s it was begun with.
+ * With s samples per axis, pixel (x, y) of a w x h frame is computed exactly so:
+ *   1. sample (i, j), 0 <= i, j < s, is pixel (s x + i, s y + j) of the reference's frame of s w x s h pixels
+ *      (naive_renderer.c:217-229 at view_pos = ((s x + i) + .5f) / (float)(s w) * 2 - 1, the same for y with s h): the clamped
+ *      LINEAR colour get_light() returns, before gamma.  The camera is unchanged (lol_frame_camera_init with w, h: the aspect
+ *      ratio of s w x s h is the same rational);
+ *   2. the samples are averaged in linear space, in float32, in a fixed order: in order k = j s + i, each channel summed as a
+ *      balanced binary tree ((v0 + v1) + (v2 + v3) for s = 2; the same nested four levels deep for s = 4), the sum multiplied
+ *      by 1 / s^2;
+ *   3. the mean goes through gamma and packing like a single sample's colour (lol_gpu_set_pixel_format).
+ * Diagnostics: lol_gpu_debug.rgb is the mean after gamma; hit_dist, hit_id and steps have no single value for such a pixel, and
+ * a frame that asks for them with s > 1 returns LOL_GPU_ERR_UNSUPPORTED, with nothing launched and nothing written.  Supersampled
+ * frames launch in a fixed tile order (columns under LOL_GPU_TILES_COLS, rows otherwise) and neither use nor change the state of
+ * LOL_GPU_TILES_LPT / _AUTO.  The scene's own kernel renders them when s > 1 was set BEFORE lol_gpu_upload_program (its module
+ * then also carries lol_render_spec_aa); otherwise they render on the interpreter's render_interp_aa until the next upload —
+ * same pixels either way.
+ */
+int         lol_gpu_set_samples(lol_gpu* ctx, int samples);
+int         lol_gpu_samples(const lol_gpu* ctx);
+
 /* Name of the kernel a launch uses (for matching rocprofv3 kernel-trace rows):
- * "lol_render_spec" (scene-specialised, compiled by hipRTC at upload) or "render_interp". */
+ * "lol_render_spec" (scene-specialised, compiled by hipRTC at upload) or "render_interp"; with supersampling
+ * (lol_gpu_set_samples) "lol_render_spec_aa" or "render_interp_aa". */
 const char* lol_gpu_kernel_name(const lol_gpu* ctx);
 /* Identity of the code that kernel is: 16 hex digits — FNV-1a of the hipRTC code object for "lol_render_spec"; for
  * "render_interp" of {this library's build id (a digest of its sources and compiler flags), the uploaded macro-op lists,
@@ -377,6 +402,7 @@ int  lol_gpu_multi_render_host(lol_gpu_multi* m, const lol_frame_camera* cam, in
 int  lol_gpu_multi_set_host_via_root(lol_gpu_multi* m, int enable);
 int  lol_gpu_multi_set_pixel_format(lol_gpu_multi* m, const lol_gpu_pixel_format* fmt);
 int  lol_gpu_multi_set_tile_order(lol_gpu_multi* m, int order);         /* lol_gpu_set_tile_order on every device (each decides for itself under AUTO) */
+int  lol_gpu_multi_set_samples(lol_gpu_multi* m, int samples);          /* lol_gpu_set_samples on every device (bands are output rows) */
 /* Parts per device (default 1): the frame is cut into n * parts parts, part p belonging to device p % n, each part one
  * launch.  Finer interleaving of the rows, and the way a single-GPU machine exercises the multi-part code paths.
  * n * parts <= 64. */

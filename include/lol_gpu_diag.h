@@ -69,6 +69,14 @@ int         lol_gpu_powf_batch(lol_gpu* ctx, const float* x_dev, const float* y_
  * (tests/golden/ref_sdf_points.json) without a march in between.
  */
 int         lol_gpu_sdf_batch(lol_gpu* ctx, const float* pts_dev, float* dist_dev, uint32_t* id_dev, size_t n, void* stream);
+/*
+ * lol_gpu_compile_offline (lol_gpu.h) for a context that asked for supersampling (lol_gpu_set_samples) before its upload:
+ * samples = 1 writes exactly what lol_gpu_compile_offline writes; 2 and 4 the same source with the kernel lol_render_spec_aa
+ * appended, and its code object — so that the supersampling kernel's ISA can be inspected without a device.  LOL_GPU_ERR_ARG
+ * for any other number of samples.
+ */
+int         lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                            int samples, char* log, size_t logcap);
 
 #ifdef __cplusplus
 }

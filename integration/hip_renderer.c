@@ -20,7 +20,10 @@
  *                   these GPUs, each writing its bands into the surface,
  *                   include/lol_gpu.h lol_gpu_multi_*), --parts-per-device N,
  *                   --root-band-rows N (the first device's smaller share),
- *                   --max-steps N, --tile-columns / --tile-rows (pin the order in
+ *                   --max-steps N, --samples N (N x N samples per pixel, 1, 2 or 4:
+ *                   supersampling, lol_gpu_set_samples; set before the upload, so the
+ *                   scene's own kernel carries it),
+ *                   --tile-columns / --tile-rows (pin the order in
  *                   which a launch hands out its tiles, lol_gpu_set_tile_order;
  *                   without either the library's default applies: a frame under the
  *                   camera of the frame before it is scheduled by what that frame
@@ -93,6 +96,7 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 	int device = 0;
 	int devices[LOL_GPU_MULTI_MAX_DEVICES], n_devices = 0;
 	int parts_per_device = 0, root_band = -1, tile_order = -1 /* the library's default: LOL_GPU_TILES_LPT */, wait_kernel = 0;
+	int samples = 1;                        /* --samples N: N x N samples per pixel (lol_gpu_set_samples) */
 	const char* dump = NULL;
 	HOST_PRIVATE(data) = r;
 	if (!r) { fprintf(stderr, "hip_renderer: out of memory\n"); return; }
@@ -107,6 +111,7 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 		const int is_device = !strcmp(argv[i], "--device"), is_devices = !strcmp(argv[i], "--devices");
 		const int is_steps = !strcmp(argv[i], "--max-steps"), is_dump = !strcmp(argv[i], "--dump-kernel");
 		const int is_ppd = !strcmp(argv[i], "--parts-per-device"), is_root = !strcmp(argv[i], "--root-band-rows");
+		const int is_samples = !strcmp(argv[i], "--samples");
 		if (!strcmp(argv[i], "--pipeline")) { if (r->pipeline < 2) r->pipeline = 2; continue; }
 		if (!strcmp(argv[i], "--pipeline-depth") && i + 1 < argc) {
 			const int d = atoi(argv[++i]);
@@ -117,7 +122,7 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 		if (!strcmp(argv[i], "--tile-rows")) { tile_order = LOL_GPU_TILES_ROWS; continue; }
 		if (!strcmp(argv[i], "--report")) { r->report = 1; continue; }
 		if (!strcmp(argv[i], "--wait-kernel")) { wait_kernel = 1; continue; }      /* render_prepare returns with the scene's own kernel in place (benchmarks) */
-		if (!(is_device || is_devices || is_steps || is_dump || is_ppd || is_root)) continue;      /* the host's own flags */
+		if (!(is_device || is_devices || is_steps || is_dump || is_ppd || is_root || is_samples)) continue;      /* the host's own flags */
 		if (i + 1 >= argc) { fprintf(stderr, "hip_renderer: %s needs a value, ignored\n", argv[i]); break; }
 		const char* v = argv[++i];
 		if (is_device) device = atoi(v);
@@ -125,6 +130,7 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 		else if (is_dump) dump = v;
 		else if (is_ppd) parts_per_device = atoi(v);
 		else if (is_root) root_band = atoi(v);
+		else if (is_samples) samples = atoi(v);
 		else {
 			n_devices = 0;
 			for (const char* p = v; *p && n_devices < LOL_GPU_MULTI_MAX_DEVICES;) {
@@ -160,12 +166,16 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 		if (root_band >= 0 && lol_gpu_multi_set_root_band_rows(r->multi, root_band) != LOL_GPU_OK)
 			fprintf(stderr, "hip_renderer: --root-band-rows %d refused\n", root_band);
 		if (tile_order >= 0) (void)lol_gpu_multi_set_tile_order(r->multi, tile_order);
+		if (samples != 1 && lol_gpu_multi_set_samples(r->multi, samples) != LOL_GPU_OK)
+			fprintf(stderr, "hip_renderer: --samples %d refused (1, 2 or 4)\n", samples);
 		st = lol_gpu_multi_upload_program(r->multi, &r->program);
 		if (st != LOL_GPU_OK) { fprintf(stderr, "hip_renderer: %s\n", lol_gpu_multi_error(r->multi)); return; }
 		if (wait_kernel) (void)lol_gpu_multi_specialize_wait(r->multi);
 	} else {
 		st = lol_gpu_create(device, &r->gpu);
 		if (st != LOL_GPU_OK) { fprintf(stderr, "hip_renderer: no usable HIP device %d (status %d)\n", device, st); return; }
+		if (samples != 1 && lol_gpu_set_samples(r->gpu, samples) != LOL_GPU_OK)      /* before the upload: the scene's own kernel carries it */
+			fprintf(stderr, "hip_renderer: --samples %d refused (1, 2 or 4)\n", samples);
 		st = lol_gpu_upload_program(r->gpu, &r->program);
 		if (st != LOL_GPU_OK) { fprintf(stderr, "hip_renderer: %s\n", lol_gpu_error(r->gpu)); return; }
 		if (tile_order >= 0) (void)lol_gpu_set_tile_order(r->gpu, tile_order);

@@ -1,4 +1,4 @@
-"""python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N]
+"""python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N] [--samples N]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  There is no CPU rendering path."""
@@ -21,6 +21,7 @@ def main(argv=None) -> int:
     ap.add_argument("--max-steps", type=int, default=256)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--frames", type=int, default=1)
+    ap.add_argument("--samples", type=int, default=1, choices=(1, 2, 4), help="N x N samples per pixel (supersampling)")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     try:
@@ -32,6 +33,7 @@ def main(argv=None) -> int:
         print("scene_validate_materials failed", file=sys.stderr)
         return 1
     r = gpu.Renderer(args.device)
+    r.set_samples(args.samples)          # before prepare(): the scene's own kernel then carries the supersampling form
     r.prepare(sc)
     surf = np.zeros((h, w), dtype=np.uint32)
     for f in range(args.frames):

@@ -6,7 +6,7 @@
  */
 #include "lol_gpu_internal.h"
 
-/* lol_kernel.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
+/* lol_kernel.h's and lol_kernel_aa.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
 #include "lol_kernel_src.inc"
 
 #pragma GCC visibility push(hidden)
@@ -745,7 +745,7 @@ bool spec_out_of_line(const lol_program& P, int form) {
 	return P.n_ops > limit;
 }
 
-std::string generate_source(const lol_program& P, const FastPaths* fast, bool cull, int form = SPEC_BY_SIZE) {
+std::string generate_source(const lol_program& P, const FastPaths* fast, bool cull, int form = SPEC_BY_SIZE, bool aa = false) {
 	std::string s;
 	const bool ool = spec_out_of_line(P, form);
 	const std::vector<RootBound> roots = analyse_roots(P);
@@ -810,6 +810,37 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	if (any_fast) s += "\tlol::SpecSdfFast fast;\n\tlol::sdf_points(fast, exact, true, pts, dist, id, n);\n";
 	else          s += "\tlol::sdf_points(exact, exact, false, pts, dist, id, n);\n";
 	s += "}\n";
+	/* Supersampling (lol_gpu_set_samples before the upload): the same pipeline with one lane per sample and the mean of each pixel's
+	 * samples stored (lol_kernel.h, store_pixel_aa), s read at run time.  Appended, so that a module without it is the same source
+	 * — and the same code object and kernel_key — as before supersampling existed.  No step counters: hit_dist, hit_id and steps
+	 * have no single value for a pixel of several samples (lol_gpu_render_device refuses them). */
+	if (aa) {
+		s += "#include \"lol_kernel_aa.h\"\n";
+		s += head + "lol_render_spec_aa(const lol::Launch L) {\n\textern __shared__ lol::u32 lds[];\n";
+		if (!tables_global) {
+			s += "\tlol::stage_common(L, lds);\n";
+			s += "\t__syncthreads();\n";
+		}
+		s += "\tconst lol::Launch S = lol::sample_launch(L);\n";
+		s += "\tlol::Pixel P;\n";
+		if (any_fast) {
+			s += "\tbool plain = !(L.flags & lol::FLAG_SHADOW_SETTLED);\n";
+			s += "\tif (!plain) {\n";
+			s += "\t\tlol::SpecSdfFast fast;\n";
+			s += "\t\tP = lol::shade_pixel<lol::SpecSdfFast, " + tg + ", false>(S, fast, lds);\n";
+			s += "\t\tplain = lol::unproven(fast);\n";
+			s += "\t}\n";
+			s += "\tif (plain) {\n";
+			s += "\t\tlol::SpecSdfExact exact;\n";
+			s += "\t\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
+			s += "\t}\n";
+		} else {
+			s += "\tlol::SpecSdfExact exact;\n";
+			s += "\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
+		}
+		s += "\tlol::store_pixel_aa<" + tg + ">(L, P.rgb);\n";
+		s += "}\n";
+	}
 	return s;
 }
 
@@ -927,8 +958,8 @@ bool has_return_clobbering_branch(const std::vector<char>& code) { return has_re
 
 /* hipRTC: generated source + lol_kernel.h → code object for `arch`.  Needs no device. */
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
-                  std::string& log, std::string* src_out, bool cull, int form) {
-	std::string src = generate_source(P, fast, cull, form);
+                  std::string& log, std::string* src_out, bool cull, int form, bool aa) {
+	std::string src = generate_source(P, fast, cull, form, aa);
 	if (src_out) *src_out = src;
 	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
 		if (FILE* f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
@@ -990,17 +1021,19 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	}
 	/* on disk the pipeline source (lol_kernel.h, embedded in this library) is part of the key: another build of the
 	 * library must not pick up this one's kernels */
-	const std::string disk_key = key + "|" + LOL_KERNEL_H_TEXT;
+	const std::string disk_key = key + "|" + LOL_KERNEL_H_TEXT + (aa ? std::string("|") + LOL_KERNEL_AA_H_TEXT : std::string());
 	if (disk_cache_load(disk_key, code)) {
 		std::lock_guard<std::mutex> lock(g_cache_mutex);
 		g_code_cache[key] = code;
 		log = "(code object from the disk cache)";
 		return true;
 	}
-	const char* hdr_src[] = { LOL_KERNEL_H_TEXT };
-	const char* hdr_name[] = { "lol_kernel.h" };
+	/* lol_kernel_aa.h only where the source includes it: hipRTC's compilation-unit id — bytes of the code object — follows the headers */
+	const char* hdr_src[] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT };
+	const char* hdr_name[] = { "lol_kernel.h", "lol_kernel_aa.h" };
+	const int n_hdr = aa ? 2 : 1;
 	hiprtcProgram prog = nullptr;
-	if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", 1, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
+	if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_hdr, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
 		log = "hiprtcCreateProgram failed";
 		return false;
 	}
@@ -1021,7 +1054,7 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 			options_dropped = true;
 			hiprtcDestroyProgram(&prog);
 			prog = nullptr;
-			if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", 1, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
+			if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_hdr, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
 				log = "hiprtcCreateProgram failed";
 				return false;
 			}
@@ -1109,7 +1142,14 @@ int lol_gpu_testing_has_return_clobbering_branch(const void* code, size_t n_byte
  * `arch` and write `<out_base>.hip` (generated source) and `<out_base>.co` (code object). */
 int lol_gpu_compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                             char* log, size_t logcap) {
-	if (!prog || !arch) return LOL_GPU_ERR_ARG;
+	return lol_gpu_compile_offline_samples(prog, arch, out_base, assume_fast, 1, log, logcap);
+}
+
+/* ... the module a context with lol_gpu_set_samples(ctx, samples) compiles at its upload: with samples > 1 it also carries
+ * lol_render_spec_aa (lol_gpu_diag.h) */
+int lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples,
+                                    char* log, size_t logcap) {
+	if (!prog || !arch || (samples != 1 && samples != 2 && samples != 4)) return LOL_GPU_ERR_ARG;
 	std::vector<char> code;
 	std::string lg, src;
 	FastPaths fast;
@@ -1125,7 +1165,7 @@ int lol_gpu_compile_offline(const lol_program* prog, const char* arch, const cha
 		/* on the large-stack thread, like every run of the scene compiler (BigStackThread) */
 		BigStackThread th;
 		auto work = [&]() {
-			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1)); }
+			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), SPEC_BY_SIZE, samples > 1); }
 			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
 		};
 		bool started = false;

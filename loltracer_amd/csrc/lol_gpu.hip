@@ -88,7 +88,12 @@ hipError_t launch_sdf_interp(const uint32_t* mops, uint32_t n_mops, const float*
 }
 
 template <int SSIZE, bool TABLES_GLOBAL = false>
-hipError_t launch_interp(const lol::Launch& L, dim3 grid, size_t lds, hipStream_t s, int sqrt_kind) {
+hipError_t launch_interp(const lol::Launch& L, dim3 grid, size_t lds, hipStream_t s, int sqrt_kind, bool aa) {
+	if (aa) {                  /* supersampled frames (lol_gpu_set_samples): one instantiation per variant, s read at run time */
+		if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_aa<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
+		else                hipLaunchKernelGGL((lol::render_interp_aa<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
+		return hipGetLastError();
+	}
 	if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
 	else                hipLaunchKernelGGL((lol::render_interp<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
 	return hipGetLastError();
@@ -263,7 +268,16 @@ struct Roctx {
 	}
 } g_roctx;
 
-const char* kernel_name(const lol_gpu* ctx) { return scene_kernel(ctx) ? "lol_render_spec" : "render_interp"; }
+/* the scene kernel a frame of the context's current settings runs, or nullptr: the interpreter.  A supersampled frame needs a module
+ * compiled with lol_render_spec_aa (samples > 1 at the upload); else it renders on render_interp_aa, same pixels. */
+const SceneKernel* frame_kernel(const lol_gpu* ctx) {
+	const SceneKernel* k = scene_kernel(ctx);
+	return k && (ctx->samples == 1 || k->render_aa) ? k : nullptr;
+}
+const char* kernel_name(const lol_gpu* ctx) {
+	if (ctx->samples > 1) return frame_kernel(ctx) ? "lol_render_spec_aa" : "render_interp_aa";
+	return scene_kernel(ctx) ? "lol_render_spec" : "render_interp";
+}
 
 }  // namespace
 
@@ -441,12 +455,14 @@ static int upload_program(lol_gpu* ctx, const lol_program* prog) {
 		e = hipMemcpy(ctx->d_mops[next], mops.data(), mops.size() * 4, hipMemcpyHostToDevice);
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "upload of the scene tables", e);
 	const int interp_sqrt_kind = fast.sqrt_kind == 3 ? 3 : 0;
-	std::string interp_key;
+	std::string interp_key, interp_aa_key;
 	{
 		/* what render_interp executes = this build's code (lol_kernel.h AND this file: record layout, flags) + the lists */
 		std::string id = std::string(LOL_BUILD_ID) + "|" + fnv_hex(mops.data(), mops.size() * 4) + "|" + std::to_string(interp_sqrt_kind) +
 		                 (fast.gamma_ok ? "|gamma" : "");
 		interp_key = fnv_hex(id.data(), id.size());
+		id += "|render_interp_aa";
+		interp_aa_key = fnv_hex(id.data(), id.size());
 	}
 	ctx->h_own.assign(*prog);                         /* the last fallible step (host memory; all or nothing itself): the old scene is intact until here */
 	/* commit (nothing below allocates on the way to the new scene being in place) */
@@ -458,6 +474,7 @@ static int upload_program(lol_gpu* ctx, const lol_program* prog) {
 	ctx->interp_sqrt_kind = interp_sqrt_kind;
 	ctx->gamma_table = fast.gamma_ok;
 	ctx->interp_key.swap(interp_key);
+	ctx->interp_aa_key.swap(interp_aa_key);
 	resolve_skips(ctx);
 	/* the scene compiler starts on its own thread; the new scene renders on the interpreter until its kernel is there
 	 * (a failed specialisation is not an error either: the interpreter goes on rendering) */
@@ -492,6 +509,15 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	const lol_gpu_rows* R = rows ? rows : &whole;
 	int n_rows = lol_gpu_part_rows(h, R);
 	if (n_rows < 0) return fail(ctx, LOL_GPU_ERR_ARG, "bad row partition");
+	/* supersampling (lol_gpu_set_samples): s x s samples per pixel, one lane each — the kernel's grid covers the s w x s n_rows
+	 * samples, and a pixel of several samples has no single hit distance, object or step count */
+	const int ss = ctx->samples;
+	const bool aa = ss > 1;
+	if (aa && dbg && (dbg->hit_dist || dbg->hit_id || dbg->steps))
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "hit_dist, hit_id and steps have no single value for a supersampled pixel (lol_gpu_set_samples)");
+	if (aa && ((long long)ss * w > (1 << 24) || (long long)ss * h > (1 << 24) ||
+	           ((long long)ss * n_rows + lol::TILE_H - 1) / lol::TILE_H > 65535 || ((long long)ss * w + lol::TILE_W - 1) / lol::TILE_W > 65535))
+		return fail(ctx, LOL_GPU_ERR_ARG, "frame too large for its samples per pixel");
 	if (n_rows == 0) return LOL_GPU_OK;
 	/* h need not be a multiple of cycle_rows: a part's band in the last, partial cycle is cut or absent, and it is the
 	 * part's last, so every part's local rows stay dense (lol_gpu_part_frame_row is the mapping) */
@@ -499,7 +525,7 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	lol::Launch L;
 	memset(&L, 0, sizeof L);
 	memcpy(&L.cam, cam, sizeof L.cam);
-	L.fw = (float)w; L.fh = (float)h;
+	L.fw = (float)(ss * w); L.fh = (float)(ss * h);      /* AA: the size of the sample grid (the camera's aspect ratio is the same rational) */
 	L.w = w; L.h = h; L.max_steps = max_steps;
 	L.n_rows = n_rows;
 	L.band_rows = R->band_rows; L.cycle_rows = R->cycle_rows; L.offset_rows = R->offset_rows;
@@ -513,6 +539,7 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	L.flags = (ctx->miss_skip ? lol::FLAG_MISS_SKIP : 0u) | (ctx->dark_skip ? lol::FLAG_DARK_SKIP : 0u) |
 	          (ctx->shadow_settle && camera_sane(*cam) ? lol::FLAG_SHADOW_SETTLED : 0u);
 	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+	if (aa) L.flags |= ss == 4 ? lol::FLAG_SAMPLES_4 : lol::FLAG_SAMPLES_2;
 	if (first_step(ctx, *cam, max_steps)) { L.flags |= lol::FLAG_FIRST_STEP; L.first_dist = ctx->first_dist; L.first_id = ctx->first_id; }
 	L.dst = static_cast<uint32_t*>(dst);
 	L.pitch_px = (uint32_t)(pitch_bytes / 4);
@@ -528,11 +555,18 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	finish_specialise(ctx, false);           /* the frame boundary at which a finished scene kernel takes over */
 	const int tile_w = lol::TILE_W, tile_h = lol::TILE_H;      /* both kernels: one 16 x 4 wave per block (lol_kernel.h) */
 	const int block = tile_w * tile_h;
-	dim3 grid((w + tile_w - 1) / tile_w, (n_rows + tile_h - 1) / tile_h);
+	dim3 grid((ss * w + tile_w - 1) / tile_w, (ss * n_rows + tile_h - 1) / tile_h);
 	const size_t common = (size_t)(lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) - lol::TILE_W * lol::TILE_H + block) * 4;
 	int trial = -1;
 	bool table = false;
-	if (ctx->tiles.mode == LOL_GPU_TILES_LPT) {
+	if (aa) {
+		/* Supersampled frames go in a fixed order — columns where the host asked for them, rows otherwise — and leave the longest-first
+		 * tables and AUTO's trials alone: a plain frame after them is scheduled as if they had not been there. */
+		if (ctx->tiles.mode == LOL_GPU_TILES_COLS) {
+			L.flags |= lol::FLAG_TILE_COLS;
+			const unsigned t = grid.x; grid.x = grid.y; grid.y = t;
+		}
+	} else if (ctx->tiles.mode == LOL_GPU_TILES_LPT) {
 		FrameTables F;
 		if ((table = lpt_table_for_frame(ctx, cam, w, h, max_steps, R, n_rows, block, s, &F))) {
 			L.flags |= lol::FLAG_TILE_TABLE;
@@ -544,9 +578,9 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 			grid = dim3(F.n_waves, 1);
 		}
 	}
-	if (!table) ctx->lpt_last_set = -1;
+	if (!table && !aa) ctx->lpt_last_set = -1;
 	/* (longest-first without a table — the camera moves, or another stream —: the better of the two fixed orders, like AUTO) */
-	if (!table && tile_order_for_frame(ctx, w, h, max_steps, R, dbg != nullptr, &trial) == LOL_GPU_TILES_COLS) {
+	if (!table && !aa && tile_order_for_frame(ctx, w, h, max_steps, R, dbg != nullptr, &trial) == LOL_GPU_TILES_COLS) {
 		L.flags |= lol::FLAG_TILE_COLS;
 		const unsigned t = grid.x; grid.x = grid.y; grid.y = t;      /* (both stay far below the 65535 blocks a grid may have in y) */
 	}
@@ -559,24 +593,24 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 		g_roctx.push(label);
 		g_roctx.ranges++;
 	}
-	if (const SceneKernel* k = scene_kernel(ctx)) {
+	if (const SceneKernel* k = frame_kernel(ctx)) {
 		void* args[] = { &L };
 		/* the step counters are compiled into render_counting alone (generate_source): who reads them gets that kernel */
 		const bool counts = (dbg && dbg->steps) || L.pixel_cost;
-		e = hipModuleLaunchKernel(counts ? k->render_counting : k->render, grid.x, grid.y, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
+		e = hipModuleLaunchKernel(aa ? k->render_aa : counts ? k->render_counting : k->render, grid.x, grid.y, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
 	} else {
 		const int kind = ctx->interp_sqrt_kind;
 		const int cls = interp_stack_class(P.max_stack);
 		if (lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots)) {
-			if (cls == 1)      e = launch_interp<1>(L, grid, common, s, kind);
-			else if (cls == 3) e = launch_interp<3>(L, grid, common, s, kind);
-			else if (cls == 7) e = launch_interp<7>(L, grid, common, s, kind);
-			else if (cls == lol::MOP_DEEP_FROM - 1) e = launch_interp<lol::MOP_DEEP_FROM - 1>(L, grid, common, s, kind);
-			else               e = launch_interp<lol::MOP_DEEP_SLOTS>(L, grid, common, s, kind);
+			if (cls == 1)      e = launch_interp<1>(L, grid, common, s, kind, aa);
+			else if (cls == 3) e = launch_interp<3>(L, grid, common, s, kind, aa);
+			else if (cls == 7) e = launch_interp<7>(L, grid, common, s, kind, aa);
+			else if (cls == lol::MOP_DEEP_FROM - 1) e = launch_interp<lol::MOP_DEEP_FROM - 1>(L, grid, common, s, kind, aa);
+			else               e = launch_interp<lol::MOP_DEEP_SLOTS>(L, grid, common, s, kind, aa);
 		} else {               /* large tables, read from global memory (lol_kernel.h, TABLES_LDS_MAX_DWORDS): three stack classes */
-			if (cls <= 3)      e = launch_interp<3, true>(L, grid, common, s, kind);
-			else if (cls <= lol::MOP_DEEP_FROM - 1) e = launch_interp<lol::MOP_DEEP_FROM - 1, true>(L, grid, common, s, kind);
-			else               e = launch_interp<lol::MOP_DEEP_SLOTS, true>(L, grid, common, s, kind);
+			if (cls <= 3)      e = launch_interp<3, true>(L, grid, common, s, kind, aa);
+			else if (cls <= lol::MOP_DEEP_FROM - 1) e = launch_interp<lol::MOP_DEEP_FROM - 1, true>(L, grid, common, s, kind, aa);
+			else               e = launch_interp<lol::MOP_DEEP_SLOTS, true>(L, grid, common, s, kind, aa);
 		}
 	}
 	if (g_roctx.pop) g_roctx.pop();
@@ -819,6 +853,17 @@ int lol_gpu_memcpy_d2h(lol_gpu* ctx, void* host, const void* dev, size_t bytes) 
 
 const char* lol_gpu_kernel_name(const lol_gpu* ctx) { return ctx ? kernel_name(ctx) : ""; }
 
+int lol_gpu_set_samples(lol_gpu* ctx, int samples) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (samples != 1 && samples != 2 && samples != 4) return fail(ctx, LOL_GPU_ERR_ARG, "samples per axis must be 1, 2 or 4");
+	if (!lol::samples_fit_wave(samples))
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "this build's wave patch (LOL_WAVE_W x LOL_WAVE_H) does not divide into that many samples per axis");
+	ctx->samples = samples;                 /* the next frame's; a frame already queued keeps its own */
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_samples(const lol_gpu* ctx) { return ctx ? ctx->samples : LOL_GPU_ERR_ARG; }
+
 long lol_gpu_roctx_ranges(void) {
 	g_roctx.init();
 	return g_roctx.asked && !g_roctx.push ? -1 : g_roctx.ranges.load();
@@ -826,8 +871,8 @@ long lol_gpu_roctx_ranges(void) {
 
 const char* lol_gpu_kernel_key(const lol_gpu* ctx) {
 	if (!ctx) return "";
-	const SceneKernel* k = scene_kernel(ctx);
-	return k ? k->key.c_str() : ctx->interp_key.c_str();
+	const SceneKernel* k = frame_kernel(ctx);
+	return k ? k->key.c_str() : ctx->samples > 1 ? ctx->interp_aa_key.c_str() : ctx->interp_key.c_str();
 }
 
 int lol_gpu_abi_version(void) { return LOL_GPU_ABI_VERSION; }

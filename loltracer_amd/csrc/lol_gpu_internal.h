@@ -19,6 +19,7 @@
 #include "lol_gpu_diag.h"
 #include "lol_gpu_testing.h"
 #include "lol_kernel.h"
+#include "lol_kernel_aa.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -126,6 +127,7 @@ struct SceneKernel {
 	hipFunction_t render = nullptr;            /* lol_render_spec */
 	hipFunction_t render_counting = nullptr;   /* lol_render_spec_steps — or lol_render_spec where the module holds that one alone: it counts */
 	hipFunction_t sdf = nullptr;               /* lol_sdf_spec (lol_gpu_sdf_batch) */
+	hipFunction_t render_aa = nullptr;         /* lol_render_spec_aa, where the module was compiled with it (lol_gpu_set_samples) */
 	std::string   key;                         /* FNV-1a of the code object (lol_gpu_kernel_key) */
 	explicit operator bool() const { return module != nullptr; }
 	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
@@ -196,6 +198,8 @@ struct lol_gpu {
 	int          pipe_last_geom[3] = { 0, 0, 0 };
 	SpecTiers    tiers;                  /* the scene compiler's: the kernel frames run, or none (the interpreter) */
 	std::string  interp_key;             /* FNV-1a of {this build, the uploaded macro-op lists}: lol_gpu_kernel_key of the interpreter */
+	std::string  interp_aa_key;          /* ... and of its supersampling kernel (render_interp_aa) */
+	int          samples = 1;            /* lol_gpu_set_samples: samples per pixel along each axis of the frames launched from now on */
 	int          fail_uploads = 0;       /* lol_gpu_testing_fail_uploads: that many uploads still fail at the copy */
 	int          want_fast = 1;          /* allow the proven-exact shortcuts in the specialised kernel */
 	unsigned     want_skips = 7;         /* exact skips allowed when the program qualifies: bit 0 escaped waves, 1 zero incidence, 2 settled shadows */
@@ -341,8 +345,10 @@ float smooth_sat_threshold(float k);
 /* ---- lol_codegen.hip */
 inline bool culling_enabled(int want) { return want != 0; }      /* (lol_gpu_set_cull) */
 bool spec_out_of_line(const lol_program& P, int form = SPEC_BY_SIZE);
+/* aa: the module also carries lol_render_spec_aa (the context asked for supersampling before the upload); without it the source
+ * is exactly what it was before supersampling existed */
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
-                  std::string& log, std::string* src_out = nullptr, bool cull = true, int form = SPEC_BY_SIZE);
+                  std::string& log, std::string* src_out = nullptr, bool cull = true, int form = SPEC_BY_SIZE, bool aa = false);
 /* the interpreter's two macro-op lists for `P`, one after the other (with / without v_div_fixup in the proven blend factors);
  * false: the two differ in length (cannot happen: same records by construction) */
 bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, std::vector<uint32_t>& lists, uint32_t& n_mops);

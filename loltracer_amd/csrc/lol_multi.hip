@@ -508,6 +508,17 @@ int lol_gpu_multi_set_pixel_format(lol_gpu_multi* m, const lol_gpu_pixel_format*
 	return LOL_GPU_OK;
 }
 
+/* bands are output rows: every device supersamples its own rows, and the exchange moves pixels as before */
+int lol_gpu_multi_set_samples(lol_gpu_multi* m, int samples) {
+	if (!m) return LOL_GPU_ERR_ARG;
+	if (samples != 1 && samples != 2 && samples != 4) return mfail(m, LOL_GPU_ERR_ARG, "lol_gpu_set_samples", "samples per axis must be 1, 2 or 4");
+	for (int i = 0; i < m->n; i++) {
+		int st = lol_gpu_set_samples(m->dev[i].ctx, samples);
+		if (st != LOL_GPU_OK) return mfail(m, st, "lol_gpu_set_samples", lol_gpu_error(m->dev[i].ctx));
+	}
+	return LOL_GPU_OK;
+}
+
 int lol_gpu_multi_set_tile_order(lol_gpu_multi* m, int columns) {
 	if (!m) return LOL_GPU_ERR_ARG;
 	for (int i = 0; i < m->n; i++) {

@@ -172,6 +172,14 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_multi_specialize_wait.restype = C.c_int
         lib.lol_gpu_compile_offline.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
         lib.lol_gpu_compile_offline.restype = C.c_int
+        lib.lol_gpu_compile_offline_samples.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+        lib.lol_gpu_compile_offline_samples.restype = C.c_int
+        lib.lol_gpu_set_samples.argtypes = [vp, C.c_int]
+        lib.lol_gpu_set_samples.restype = C.c_int
+        lib.lol_gpu_samples.argtypes = [vp]
+        lib.lol_gpu_samples.restype = C.c_int
+        lib.lol_gpu_multi_set_samples.argtypes = [vp, C.c_int]
+        lib.lol_gpu_multi_set_samples.restype = C.c_int
         lib.lol_gpu_verify_fast_paths.argtypes = [vp, C.c_float, P(C.c_ulonglong), P(C.c_ulonglong)]
         lib.lol_gpu_verify_fast_paths.restype = C.c_int
         lib.lol_gpu_verify_smin_no_fixup.argtypes = [vp, C.c_float, P(C.c_ulonglong)]
@@ -280,12 +288,13 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_render_host_pending_size", "lol_gpu_render_host_discard", "lol_gpu_kernel_key", "lol_gpu_assemble_parts_at",
     "lol_gpu_split_rows", "lol_gpu_multi_set_root_band_rows", "lol_gpu_multi_set_pixel_format", "lol_gpu_multi_set_tile_order",
     "lol_gpu_set_frames_in_flight", "lol_gpu_frames_in_flight", "lol_gpu_next_stream", "lol_gpu_set_specialize_max_ops",
+    "lol_gpu_set_samples", "lol_gpu_samples", "lol_gpu_multi_set_samples",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
     "lol_gpu_tuning_switches", "lol_gpu_roctx_ranges", "lol_gpu_verify_fast_paths", "lol_gpu_verify_smin_no_fixup",
     "lol_gpu_verify_gamma_table", "lol_gpu_cull_bounds", "lol_gpu_cull_bounds_clusters", "lol_gpu_powf_batch",
-    "lol_gpu_sdf_batch",
+    "lol_gpu_sdf_batch", "lol_gpu_compile_offline_samples",
 ]
 
 
@@ -299,6 +308,17 @@ def compile_offline(program: S.Program, out_base: str, arch: str = "gfx950", ass
     log = C.create_string_buffer(1 << 16)
     st = gpu_lib().lol_gpu_compile_offline(C.byref(program), arch.encode(), os.fsencode(out_base),
                                            int(assume_fast), log, len(log))
+    if st != LOL_GPU_OK:
+        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
+    return log.value.decode(errors="replace")
+
+
+def compile_offline_samples(program: S.Program, out_base: str, samples: int, arch: str = "gfx950",
+                            assume_fast: bool = False) -> str:
+    """compile_offline for a context with set_samples(samples) before its upload: samples > 1 adds lol_render_spec_aa."""
+    log = C.create_string_buffer(1 << 16)
+    st = gpu_lib().lol_gpu_compile_offline_samples(C.byref(program), arch.encode(), os.fsencode(out_base),
+                                                   int(assume_fast), int(samples), log, len(log))
     if st != LOL_GPU_OK:
         raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
     return log.value.decode(errors="replace")
@@ -452,6 +472,16 @@ class Renderer:
     def kernel_name(self) -> str:
         return self._lib.lol_gpu_kernel_name(self._ctx).decode()
 
+    def set_samples(self, s: int):
+        """s x s samples per pixel (1, 2 or 4; 1 = one ray per pixel, the default) from the next frame on: the mean of the
+        reference's s w x s h frame's linear colours, in a fixed order (lol_gpu.h).  Set it before prepare() for the scene's own
+        kernel to carry the supersampling form; otherwise such frames render on the interpreter (same pixels)."""
+        self._check(self._lib.lol_gpu_set_samples(self._ctx, int(s)))
+
+    @property
+    def samples(self) -> int:
+        return int(self._lib.lol_gpu_samples(self._ctx))
+
     def verify_fast_paths(self, k: float = 3.0):
         """([sqrt_pm, sqrt_gs, sqrt_r2], x/k) mismatch counts over all 2^32 float inputs; 0 means proven exact."""
         sq, dv = (C.c_ulonglong * 3)(), C.c_ulonglong()
@@ -583,6 +613,10 @@ class MultiRenderer:
 
     def set_tile_order(self, order):
         self._check(self._lib.lol_gpu_multi_set_tile_order(self._m, _tile_order_arg(order)))
+
+    def set_samples(self, s: int):
+        """Renderer.set_samples on every device (bands are output rows: the exchange is unchanged)."""
+        self._check(self._lib.lol_gpu_multi_set_samples(self._m, int(s)))
 
     def tile_order(self, i: int = 0) -> dict:
         """lol_gpu_tile_order of device index i's context."""
