@@ -228,9 +228,31 @@ int lol_gpu_memcpy_d2h(lol_gpu* ctx, void* host, const void* dev, size_t bytes);
 int         lol_gpu_set_samples(lol_gpu* ctx, int samples);
 int         lol_gpu_samples(const lol_gpu* ctx);
 
+/*
+ * Adaptive supersampling: s x s samples only where the plain frame has an edge.  contrast = -1 is off (the default: frames are
+ * those of lol_gpu_set_samples); 0 <= contrast <= 255 turns it on; any other value returns LOL_GPU_ERR_ARG and leaves the setting
+ * as it was.  It matters only with samples > 1 (with s = 1 a frame is the plain frame whatever contrast says) and takes effect at
+ * the next frame, like lol_gpu_set_samples; a frame already begun keeps the setting it was begun with.
+ * For a w x h frame with s samples per axis and contrast T, pixel (x, y) is:
+ *   1. P = the plain frame (what s = 1 renders), with id(x, y) = get_intersection().id (naive_renderer.c:225; 0 for an escaped ray)
+ *      and c8(x, y) = the three 8-bit channels (Uint8)(c * 255) after gamma, before any pixel-format loss or shift;
+ *   2. the pixel is REFINED if one of its 8 neighbours q inside the frame has id(q) != id(x, y), or |c8(q)[ch] - c8(x, y)[ch]| > T
+ *      for a channel ch (neighbours outside the frame are ignored);
+ *   3. a refined pixel is the s x s pixel of lol_gpu_set_samples, exactly as defined there;
+ *   4. any other pixel is P's pixel, packed in the context's pixel format.
+ * lol_gpu_debug.rgb is the colour after gamma of whichever of the two the pixel is; hit_dist, hit_id and steps are refused as for
+ * any s > 1 frame.  A frame is three launches on its stream (the plain frame, the mask, the refined pixels) with no host wait.
+ * Whole frames only: a `rows` argument that is not the whole frame returns LOL_GPU_ERR_UNSUPPORTED, nothing launched — a pixel's
+ * mask reads rows another part renders.  The sample grid must fit s w <= 65536 and s h <= 32768 (else LOL_GPU_ERR_ARG).
+ * lol_gpu_multi_* has no adaptive setter: multi-device adaptive frames would need halo rows, and are not built.
+ */
+int         lol_gpu_set_adaptive_samples(lol_gpu* ctx, int contrast);
+int         lol_gpu_adaptive_samples(const lol_gpu* ctx);
+
 /* Name of the kernel a launch uses (for matching rocprofv3 kernel-trace rows):
  * "lol_render_spec" (scene-specialised, compiled by hipRTC at upload) or "render_interp"; with supersampling
- * (lol_gpu_set_samples) "lol_render_spec_aa" or "render_interp_aa". */
+ * (lol_gpu_set_samples) "lol_render_spec_aa" or "render_interp_aa"; for adaptive frames (lol_gpu_set_adaptive_samples) the
+ * kernel of their refine pass, "lol_render_spec_aa_list" or "render_interp_aa_list". */
 const char* lol_gpu_kernel_name(const lol_gpu* ctx);
 /* Identity of the code that kernel is: 16 hex digits — FNV-1a of the hipRTC code object for "lol_render_spec"; for
  * "render_interp" of {this library's build id (a digest of its sources and compiler flags), the uploaded macro-op lists,

@@ -71,12 +71,20 @@ int         lol_gpu_powf_batch(lol_gpu* ctx, const float* x_dev, const float* y_
 int         lol_gpu_sdf_batch(lol_gpu* ctx, const float* pts_dev, float* dist_dev, uint32_t* id_dev, size_t n, void* stream);
 /*
  * lol_gpu_compile_offline (lol_gpu.h) for a context that asked for supersampling (lol_gpu_set_samples) before its upload:
- * samples = 1 writes exactly what lol_gpu_compile_offline writes; 2 and 4 the same source with the kernel lol_render_spec_aa
- * appended, and its code object — so that the supersampling kernel's ISA can be inspected without a device.  LOL_GPU_ERR_ARG
- * for any other number of samples.
+ * samples = 1 writes exactly what lol_gpu_compile_offline writes; 2 and 4 the same source with the kernels lol_render_spec_aa
+ * and lol_render_spec_aa_list appended, and its code object — so that the supersampling kernels' ISA can be inspected without a
+ * device.  LOL_GPU_ERR_ARG for any other number of samples.
  */
 int         lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                             int samples, char* log, size_t logcap);
+/*
+ * Adaptive frames (lol_gpu_set_adaptive_samples): waits for the context's last adaptive frame and gives how many of its pixels
+ * were refined (*n), or the time its three passes took on the device, in milliseconds between events on its stream (ms[0] the
+ * plain frame, ms[1] the mask and the list, ms[2] the refined pixels).  LOL_GPU_ERR_ARG when no adaptive frame was launched.
+ * For tests and rate tools; frames never need them.
+ */
+int         lol_gpu_adaptive_refined(lol_gpu* ctx, int64_t* n);
+int         lol_gpu_adaptive_pass_ms(lol_gpu* ctx, float ms[3]);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,9 @@
  *                   --root-band-rows N (the first device's smaller share),
  *                   --max-steps N, --samples N (N x N samples per pixel, 1, 2 or 4:
  *                   supersampling, lol_gpu_set_samples; set before the upload, so the
- *                   scene's own kernel carries it),
+ *                   scene's own kernel carries it), --adaptive T (with --samples N:
+ *                   N x N samples only on pixels at an edge of the plain frame, contrast
+ *                   T in 0 ... 255, lol_gpu_set_adaptive_samples; refused with --devices),
  *                   --tile-columns / --tile-rows (pin the order in
  *                   which a launch hands out its tiles, lol_gpu_set_tile_order;
  *                   without either the library's default applies: a frame under the
@@ -97,6 +99,7 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 	int devices[LOL_GPU_MULTI_MAX_DEVICES], n_devices = 0;
 	int parts_per_device = 0, root_band = -1, tile_order = -1 /* the library's default: LOL_GPU_TILES_LPT */, wait_kernel = 0;
 	int samples = 1;                        /* --samples N: N x N samples per pixel (lol_gpu_set_samples) */
+	int adaptive = -1;                      /* --adaptive T: ... only at edges of the plain frame (lol_gpu_set_adaptive_samples) */
 	const char* dump = NULL;
 	HOST_PRIVATE(data) = r;
 	if (!r) { fprintf(stderr, "hip_renderer: out of memory\n"); return; }
@@ -111,7 +114,7 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 		const int is_device = !strcmp(argv[i], "--device"), is_devices = !strcmp(argv[i], "--devices");
 		const int is_steps = !strcmp(argv[i], "--max-steps"), is_dump = !strcmp(argv[i], "--dump-kernel");
 		const int is_ppd = !strcmp(argv[i], "--parts-per-device"), is_root = !strcmp(argv[i], "--root-band-rows");
-		const int is_samples = !strcmp(argv[i], "--samples");
+		const int is_samples = !strcmp(argv[i], "--samples"), is_adaptive = !strcmp(argv[i], "--adaptive");
 		if (!strcmp(argv[i], "--pipeline")) { if (r->pipeline < 2) r->pipeline = 2; continue; }
 		if (!strcmp(argv[i], "--pipeline-depth") && i + 1 < argc) {
 			const int d = atoi(argv[++i]);
@@ -122,7 +125,7 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 		if (!strcmp(argv[i], "--tile-rows")) { tile_order = LOL_GPU_TILES_ROWS; continue; }
 		if (!strcmp(argv[i], "--report")) { r->report = 1; continue; }
 		if (!strcmp(argv[i], "--wait-kernel")) { wait_kernel = 1; continue; }      /* render_prepare returns with the scene's own kernel in place (benchmarks) */
-		if (!(is_device || is_devices || is_steps || is_dump || is_ppd || is_root || is_samples)) continue;      /* the host's own flags */
+		if (!(is_device || is_devices || is_steps || is_dump || is_ppd || is_root || is_samples || is_adaptive)) continue;      /* the host's own flags */
 		if (i + 1 >= argc) { fprintf(stderr, "hip_renderer: %s needs a value, ignored\n", argv[i]); break; }
 		const char* v = argv[++i];
 		if (is_device) device = atoi(v);
@@ -131,6 +134,7 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 		else if (is_ppd) parts_per_device = atoi(v);
 		else if (is_root) root_band = atoi(v);
 		else if (is_samples) samples = atoi(v);
+		else if (is_adaptive) adaptive = atoi(v);
 		else {
 			n_devices = 0;
 			for (const char* p = v; *p && n_devices < LOL_GPU_MULTI_MAX_DEVICES;) {
@@ -158,6 +162,11 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 			fprintf(stderr, "hip_renderer: --dump-kernel failed: %s\n", log);
 	}
 
+	if (n_devices > 0 && adaptive >= 0) {
+		/* a pixel's mask reads its neighbours' rows, which other devices render: that would need halo rows, not built */
+		fprintf(stderr, "hip_renderer: --adaptive is refused with --devices (multi-device adaptive frames are not supported): not rendering\n");
+		return;
+	}
 	if (n_devices > 0) {
 		st = lol_gpu_multi_create(devices, n_devices, &r->multi);
 		if (st != LOL_GPU_OK) { fprintf(stderr, "hip_renderer: cannot set up %d device(s) (status %d)\n", n_devices, st); return; }
@@ -176,6 +185,8 @@ void render_prepare(struct render_data* data, int argc, const char* argv[]) {
 		if (st != LOL_GPU_OK) { fprintf(stderr, "hip_renderer: no usable HIP device %d (status %d)\n", device, st); return; }
 		if (samples != 1 && lol_gpu_set_samples(r->gpu, samples) != LOL_GPU_OK)      /* before the upload: the scene's own kernel carries it */
 			fprintf(stderr, "hip_renderer: --samples %d refused (1, 2 or 4)\n", samples);
+		if (adaptive != -1 && lol_gpu_set_adaptive_samples(r->gpu, adaptive) != LOL_GPU_OK)
+			fprintf(stderr, "hip_renderer: --adaptive %d refused (0 ... 255)\n", adaptive);
 		st = lol_gpu_upload_program(r->gpu, &r->program);
 		if (st != LOL_GPU_OK) { fprintf(stderr, "hip_renderer: %s\n", lol_gpu_error(r->gpu)); return; }
 		if (tile_order >= 0) (void)lol_gpu_set_tile_order(r->gpu, tile_order);

@@ -1,4 +1,5 @@
 """python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N] [--samples N]
+                          [--adaptive T]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  There is no CPU rendering path."""
@@ -22,6 +23,8 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--frames", type=int, default=1)
     ap.add_argument("--samples", type=int, default=1, choices=(1, 2, 4), help="N x N samples per pixel (supersampling)")
+    ap.add_argument("--adaptive", type=int, default=-1, metavar="T",
+                    help="with --samples N: N x N samples only at edges of the plain frame (contrast T, 0 ... 255)")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     try:
@@ -34,6 +37,8 @@ def main(argv=None) -> int:
         return 1
     r = gpu.Renderer(args.device)
     r.set_samples(args.samples)          # before prepare(): the scene's own kernel then carries the supersampling form
+    if args.adaptive != -1:
+        r.set_adaptive_samples(args.adaptive)
     r.prepare(sc)
     surf = np.zeros((h, w), dtype=np.uint32)
     for f in range(args.frames):

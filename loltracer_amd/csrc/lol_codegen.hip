@@ -815,30 +815,40 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * — and the same code object and kernel_key — as before supersampling existed.  No step counters: hit_dist, hit_id and steps
 	 * have no single value for a pixel of several samples (lol_gpu_render_device refuses them). */
 	if (aa) {
+		/* P = the lane's sample of launch S, the fast SDF's exact fallback done (`in`: indentation) */
+		auto shade = [&](const std::string& in) {
+			std::string b = in + "lol::Pixel P;\n";
+			if (any_fast) {
+				b += in + "bool plain = !(L.flags & lol::FLAG_SHADOW_SETTLED);\n";
+				b += in + "if (!plain) {\n";
+				b += in + "\tlol::SpecSdfFast fast;\n";
+				b += in + "\tP = lol::shade_pixel<lol::SpecSdfFast, " + tg + ", false>(S, fast, lds);\n";
+				b += in + "\tplain = lol::unproven(fast);\n";
+				b += in + "}\n";
+				b += in + "if (plain) {\n";
+				b += in + "\tlol::SpecSdfExact exact;\n";
+				b += in + "\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
+				b += in + "}\n";
+			} else {
+				b += in + "lol::SpecSdfExact exact;\n";
+				b += in + "P = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
+			}
+			return b;
+		};
+		const std::string stage = tables_global ? "" : "\tlol::stage_common(L, lds);\n\t__syncthreads();\n";
 		s += "#include \"lol_kernel_aa.h\"\n";
-		s += head + "lol_render_spec_aa(const lol::Launch L) {\n\textern __shared__ lol::u32 lds[];\n";
-		if (!tables_global) {
-			s += "\tlol::stage_common(L, lds);\n";
-			s += "\t__syncthreads();\n";
-		}
+		s += head + "lol_render_spec_aa(const lol::Launch L) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tconst lol::Launch S = lol::sample_launch(L);\n";
-		s += "\tlol::Pixel P;\n";
-		if (any_fast) {
-			s += "\tbool plain = !(L.flags & lol::FLAG_SHADOW_SETTLED);\n";
-			s += "\tif (!plain) {\n";
-			s += "\t\tlol::SpecSdfFast fast;\n";
-			s += "\t\tP = lol::shade_pixel<lol::SpecSdfFast, " + tg + ", false>(S, fast, lds);\n";
-			s += "\t\tplain = lol::unproven(fast);\n";
-			s += "\t}\n";
-			s += "\tif (plain) {\n";
-			s += "\t\tlol::SpecSdfExact exact;\n";
-			s += "\t\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
-			s += "\t}\n";
-		} else {
-			s += "\tlol::SpecSdfExact exact;\n";
-			s += "\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
-		}
+		s += shade("\t");
 		s += "\tlol::store_pixel_aa<" + tg + ">(L, P.rgb);\n";
+		s += "}\n";
+		/* the refine pass of adaptive frames (lol_gpu_set_adaptive_samples): the same pixel for a list of pixels */
+		s += head + "lol_render_spec_aa_list(const lol::Launch L, const lol::u32* list, const lol::u32* count) {\n";
+		s += "\textern __shared__ lol::u32 lds[];\n" + stage;
+		s += "\tlol::render_aa_list<" + tg + ">(L, list, count, [&](const lol::Launch& S) {\n";
+		s += shade("\t\t");
+		s += "\t\treturn P;\n";
+		s += "\t});\n";
 		s += "}\n";
 	}
 	return s;

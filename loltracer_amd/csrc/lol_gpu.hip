@@ -88,7 +88,13 @@ hipError_t launch_sdf_interp(const uint32_t* mops, uint32_t n_mops, const float*
 }
 
 template <int SSIZE, bool TABLES_GLOBAL = false>
-hipError_t launch_interp(const lol::Launch& L, dim3 grid, size_t lds, hipStream_t s, int sqrt_kind, bool aa) {
+hipError_t launch_interp(const lol::Launch& L, dim3 grid, size_t lds, hipStream_t s, int sqrt_kind, bool aa,
+                         const uint32_t* list, const uint32_t* count) {
+	if (list) {                /* the refine pass of adaptive frames (lol_gpu_set_adaptive_samples) */
+		if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_aa_list<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, list, count);
+		else                hipLaunchKernelGGL((lol::render_interp_aa_list<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, list, count);
+		return hipGetLastError();
+	}
 	if (aa) {                  /* supersampled frames (lol_gpu_set_samples): one instantiation per variant, s read at run time */
 		if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_aa<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
 		else                hipLaunchKernelGGL((lol::render_interp_aa<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
@@ -275,8 +281,76 @@ const SceneKernel* frame_kernel(const lol_gpu* ctx) {
 	return k && (ctx->samples == 1 || k->render_aa) ? k : nullptr;
 }
 const char* kernel_name(const lol_gpu* ctx) {
+	if (ctx->samples > 1 && ctx->adaptive >= 0) return frame_kernel(ctx) ? "lol_render_spec_aa_list" : "render_interp_aa_list";
 	if (ctx->samples > 1) return frame_kernel(ctx) ? "lol_render_spec_aa" : "render_interp_aa";
 	return scene_kernel(ctx) ? "lol_render_spec" : "render_interp";
+}
+
+/* a frame (or pass) on the interpreter: the instantiation for the program's stack class and table placement; `list`, `count`: the
+ * refine pass of an adaptive frame */
+hipError_t interp_frame(const lol_gpu* ctx, const lol::Launch& L, dim3 grid, size_t common, hipStream_t s, bool aa,
+                        const uint32_t* list = nullptr, const uint32_t* count = nullptr) {
+	const lol_program& P = ctx->h_prog;
+	const int kind = ctx->interp_sqrt_kind;
+	const int cls = interp_stack_class(P.max_stack);
+	if (lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots)) {
+		if (cls == 1)      return launch_interp<1>(L, grid, common, s, kind, aa, list, count);
+		else if (cls == 3) return launch_interp<3>(L, grid, common, s, kind, aa, list, count);
+		else if (cls == 7) return launch_interp<7>(L, grid, common, s, kind, aa, list, count);
+		else if (cls == lol::MOP_DEEP_FROM - 1) return launch_interp<lol::MOP_DEEP_FROM - 1>(L, grid, common, s, kind, aa, list, count);
+		else               return launch_interp<lol::MOP_DEEP_SLOTS>(L, grid, common, s, kind, aa, list, count);
+	}
+	/* large tables, read from global memory (lol_kernel.h, TABLES_LDS_MAX_DWORDS): three stack classes */
+	if (cls <= 3)      return launch_interp<3, true>(L, grid, common, s, kind, aa, list, count);
+	else if (cls <= lol::MOP_DEEP_FROM - 1) return launch_interp<lol::MOP_DEEP_FROM - 1, true>(L, grid, common, s, kind, aa, list, count);
+	else               return launch_interp<lol::MOP_DEEP_SLOTS, true>(L, grid, common, s, kind, aa, list, count);
+}
+
+/*
+ * Adaptive frames (lol_gpu_set_adaptive_samples), pass 2: classify and compact.  One lane per pixel, a 16 x 4 tile per wave, tiles
+ * row by row.  A pixel is refined when one of its (up to 8) neighbours inside the frame has another object id, or differs from it
+ * by more than `contrast` in one of the 8-bit channels of the plain frame (`xrgb`, XRGB8888).  An unrefined pixel is the plain
+ * pixel: written here, in the surface's format.  A refined one is appended to `list` (x | y << 16): one ballot and one atomic add
+ * per wave, so a wave's pixels stay together in tile order — the refine pass's waves take consecutive entries.  Which wave gets
+ * which part of the list depends on the order of the atomics; no pixel's value does.
+ */
+constexpr int CLASSIFY_W = 16, CLASSIFY_H = 4;
+__global__ __launch_bounds__(64) void adaptive_classify(const uint32_t* xrgb, const uint32_t* ids, int w, int h, int contrast,
+                                                        uint32_t* dst, uint32_t pitch_px, uint32_t fmt_shift, uint32_t fmt_loss,
+                                                        uint32_t fmt_amask, uint32_t* list, uint32_t* count) {
+	const int lane = threadIdx.x;
+	const int x = blockIdx.x * CLASSIFY_W + lane % CLASSIFY_W, y = blockIdx.y * CLASSIFY_H + lane / CLASSIFY_W;
+	const bool in = x < w && y < h;
+	bool refined = false;
+	uint32_t c = 0;
+	if (in) {
+		const size_t o = (size_t)y * w + x;
+		c = xrgb[o];
+		const uint32_t id = ids[o];
+		for (int dy = -1; dy <= 1; dy++) {
+			for (int dx = -1; dx <= 1; dx++) {
+				const int qx = x + dx, qy = y + dy;
+				if ((dx == 0 && dy == 0) || qx < 0 || qy < 0 || qx >= w || qy >= h) continue;
+				const size_t q = (size_t)qy * w + qx;
+				const uint32_t cq = xrgb[q];
+				bool differs = ids[q] != id;
+				for (int sh = 0; sh <= 16; sh += 8)
+					differs |= abs((int)(c >> sh & 0xFFu) - (int)(cq >> sh & 0xFFu)) > contrast;
+				refined |= differs;
+			}
+		}
+	}
+	if (in && !refined) {                    /* SDL_MapRGB's packing of the plain pixel's 8-bit channels (store_pixel) */
+		const uint32_t r8 = c >> 16 & 0xFFu, g8 = c >> 8 & 0xFFu, b8 = c & 0xFFu;
+		dst[(size_t)y * pitch_px + x] = (r8 >> (fmt_loss & 0xFFu)) << (fmt_shift & 0xFFu) | (g8 >> (fmt_loss >> 8 & 0xFFu)) << (fmt_shift >> 8 & 0xFFu) |
+		                                (b8 >> (fmt_loss >> 16 & 0xFFu)) << (fmt_shift >> 16 & 0xFFu) | fmt_amask;
+	}
+	const unsigned long long m = __ballot(refined);
+	if (!m) return;
+	uint32_t base = 0;
+	if (lane == 0) base = atomicAdd(count, (uint32_t)__popcll(m));
+	base = __shfl(base, 0, 64);
+	if (refined) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)x | (uint32_t)y << 16;
 }
 
 }  // namespace
@@ -330,6 +404,11 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 		if (ctx->pipe_copied[i]) (void)hipEventDestroy(ctx->pipe_copied[i]);
 	}
 
+	for (lol_gpu::AdaptiveSet& S : ctx->adaptive_sets) {
+		if (S.d_buf) (void)hipFree(S.d_buf);
+		for (hipEvent_t ev : S.ev) if (ev) (void)hipEventDestroy(ev);
+	}
+	if (ctx->d_adaptive_order) (void)hipFree(ctx->d_adaptive_order);
 	if (ctx->d_bad) (void)hipFree(ctx->d_bad);
 	if (ctx->d_gamma) (void)hipFree(ctx->d_gamma);
 	if (ctx->tiles.have_events) for (hipEvent_t e : ctx->tiles.ev) (void)hipEventDestroy(e);
@@ -498,6 +577,115 @@ int lol_gpu_part_rows(int h, const lol_gpu_rows* rows) {
 	return (int)n;
 }
 
+/*
+ * An adaptive frame (lol_gpu_set_adaptive_samples): three launches on `s`, no host wait between them.  `A` = the launch of the
+ * whole supersampled frame (lol_gpu_render_device).
+ *  1. the plain frame P into the scratch set: XRGB8888 pixels and object ids, by the non-counting kernel (the diagnostic colour
+ *     straight into the caller's buffer), in a fixed tile order — the longest-first tables and AUTO's trials are left alone;
+ *  2. adaptive_classify: the mask; unrefined pixels go to `dst`, refined ones to the list;
+ *  3. the refine pass (lol_kernel_aa.h, render_aa_list) over the list, on a grid that fills the device — the list's length stays
+ *     on the device.
+ * Scratch: the next set of the ring, after the frame that used it last (hipStreamWaitEvent: frames on other streams, frames in
+ * flight); the host waits for that frame only where the set has to grow, or where this frame goes to one of HIP's special stream
+ * handles and that frame has not finished.
+ */
+static int render_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_gpu_debug* dbg, hipStream_t s, size_t common) {
+	const int w = A.w, h = A.h, ss = ctx->samples;
+	const size_t px = (size_t)w * h;
+	if (!ctx->adaptive_blocks) {
+		/* the refine grid: enough one-wave blocks to fill the device (8 waves per SIMD, 4 SIMDs per CU), each with a slot of its own
+		 * in the lane table; the order table maps block b to slot b */
+		int cus = 0;
+		LOL_HIP(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+		const uint32_t blocks = (uint32_t)std::max(1, cus) * 32u, stride = (blocks + 7u) / 8u;
+		std::vector<uint32_t> order;
+		try { order.assign((size_t)stride * 8u, 0u); } catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory"); }
+		for (uint32_t b = 0; b < blocks; b++) order[(b & 7u) * stride + (b >> 3)] = b;      /* (lol_kernel.h, tile_slot) */
+		if (!ctx->d_adaptive_order) LOL_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_adaptive_order), order.size() * 4));
+		LOL_HIP(ctx, hipMemcpy(ctx->d_adaptive_order, order.data(), order.size() * 4, hipMemcpyHostToDevice));
+		ctx->adaptive_blocks = blocks; ctx->adaptive_stride = stride;
+	}
+	const uint32_t per_wave = 64u / (uint32_t)(ss * ss);
+	const uint32_t blocks = (uint32_t)std::min<size_t>(ctx->adaptive_blocks, (px + per_wave - 1) / per_wave);
+	const int si = (int)(ctx->adaptive_rr++ % lol_gpu::ADAPTIVE_SETS);
+	lol_gpu::AdaptiveSet& S = ctx->adaptive_sets[si];
+	for (hipEvent_t& ev : S.ev) if (!ev) LOL_HIP(ctx, hipEventCreate(&ev));
+	const size_t need = (3 * px + 64 + (size_t)ctx->adaptive_blocks * 64) * 4;
+	if (need > S.bytes) {
+		if (S.used) LOL_HIP(ctx, hipEventSynchronize(S.ev[3]));
+		if (S.d_buf) (void)hipFree(S.d_buf);
+		S.d_buf = nullptr; S.bytes = 0; S.d_count = nullptr; S.used = false;
+		if (ctx->adaptive_last == si) ctx->adaptive_last = -1;
+		LOL_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&S.d_buf), need));
+		S.bytes = need;
+	}
+	uint32_t* xrgb = S.d_buf;
+	uint32_t* ids = xrgb + px;
+	uint32_t* list = ids + px;
+	uint32_t* count = list + px;
+	uint32_t* lanes = count + 64;
+	if (S.used) {
+		/* behind the set's last frame, whatever stream it ran on.  Not by hipStreamWaitEvent on HIP's special handles (the legacy
+		 * default stream, the per-thread one): this HIP's hipStreamWaitEvent dereferences the handle it is given and crashes
+		 * (lol_sched.hip says the same) — there the host waits for that frame, where it has not finished yet. */
+		const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
+		if (!special) LOL_HIP(ctx, hipStreamWaitEvent(s, S.ev[3], 0));
+		else LOL_HIP(ctx, hipEventSynchronize(S.ev[3]));
+	}
+	LOL_HIP(ctx, hipEventRecord(S.ev[0], s));
+	LOL_HIP(ctx, hipMemsetAsync(count, 0, 4, s));
+	const int block = lol::TILE_W * lol::TILE_H;
+
+	/* 1. the plain frame */
+	lol::Launch L = A;
+	L.fw = (float)w; L.fh = (float)h;
+	L.flags &= ~(lol::FLAG_SAMPLES_2 | lol::FLAG_SAMPLES_4);
+	L.n_rows = h; L.band_rows = h; L.cycle_rows = h; L.offset_rows = 0;
+	L.dst = xrgb; L.pitch_px = (uint32_t)w;
+	L.fmt_shift = 16u | 8u << 8; L.fmt_loss = 0; L.fmt_amask = 0;
+	L.dbg_rgb = dbg ? dbg->rgb : nullptr; L.dbg_hit_dist = nullptr; L.dbg_hit_id = ids; L.dbg_steps = nullptr;
+	dim3 grid((w + lol::TILE_W - 1) / lol::TILE_W, (h + lol::TILE_H - 1) / lol::TILE_H);
+	if (ctx->tiles.mode == LOL_GPU_TILES_COLS) {
+		L.flags |= lol::FLAG_TILE_COLS;
+		const unsigned t = grid.x; grid.x = grid.y; grid.y = t;
+	}
+	hipError_t e;
+	if (const SceneKernel* k = scene_kernel(ctx)) {
+		void* args[] = { &L };
+		e = hipModuleLaunchKernel(k->render, grid.x, grid.y, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
+	} else {
+		e = interp_frame(ctx, L, grid, common, s, false);
+	}
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (adaptive frame, plain pass)", e);
+	LOL_HIP(ctx, hipEventRecord(S.ev[1], s));
+
+	/* 2. classify and compact */
+	hipLaunchKernelGGL(adaptive_classify, dim3((w + CLASSIFY_W - 1) / CLASSIFY_W, (h + CLASSIFY_H - 1) / CLASSIFY_H), dim3(64), 0, s,
+	                   xrgb, ids, w, h, ctx->adaptive, A.dst, A.pitch_px, A.fmt_shift, A.fmt_loss, A.fmt_amask, list, count);
+	e = hipGetLastError();
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (adaptive frame, classify pass)", e);
+	LOL_HIP(ctx, hipEventRecord(S.ev[2], s));
+
+	/* 3. the s x s pixels of the list */
+	lol::Launch R = A;
+	R.n_rows = h; R.band_rows = h; R.cycle_rows = h; R.offset_rows = 0;
+	R.tile_order = ctx->d_adaptive_order; R.tile_stride = ctx->adaptive_stride; R.lane_pixels = lanes;
+	if (const SceneKernel* k = frame_kernel(ctx)) {
+		const uint32_t* list_arg = list;
+		const uint32_t* count_arg = count;
+		void* args[] = { &R, &list_arg, &count_arg };
+		e = hipModuleLaunchKernel(k->render_aa_list, blocks, 1, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
+	} else {
+		e = interp_frame(ctx, R, dim3(blocks), common, s, true, list, count);
+	}
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (adaptive frame, refine pass)", e);
+	LOL_HIP(ctx, hipEventRecord(S.ev[3], s));
+	S.used = true;
+	S.d_count = count;
+	ctx->adaptive_last = si;
+	return LOL_GPU_OK;
+}
+
 int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
                           const lol_gpu_rows* rows, void* dst, size_t pitch_bytes,
                           const lol_gpu_debug* dbg, void* stream) {
@@ -518,6 +706,13 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	if (aa && ((long long)ss * w > (1 << 24) || (long long)ss * h > (1 << 24) ||
 	           ((long long)ss * n_rows + lol::TILE_H - 1) / lol::TILE_H > 65535 || ((long long)ss * w + lol::TILE_W - 1) / lol::TILE_W > 65535))
 		return fail(ctx, LOL_GPU_ERR_ARG, "frame too large for its samples per pixel");
+	/* adaptive supersampling (lol_gpu_set_adaptive_samples): a pixel's mask reads its neighbours' rows, so whole frames only; the
+	 * refine pass finds its samples through shade_pixel's pixel table (lol_kernel_aa.h, render_aa_list): 16-bit columns, 15-bit rows */
+	const bool adaptive = aa && ctx->adaptive >= 0;
+	if (adaptive && n_rows != h)
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "adaptive frames are whole frames: a row partition needs halo rows (lol_gpu_set_adaptive_samples)");
+	if (adaptive && ((long long)ss * w > 65536 || (long long)ss * h > 32768))
+		return fail(ctx, LOL_GPU_ERR_ARG, "frame too large for adaptive supersampling (s w <= 65536, s h <= 32768)");
 	if (n_rows == 0) return LOL_GPU_OK;
 	/* h need not be a multiple of cycle_rows: a part's band in the last, partial cycle is cut or absent, and it is the
 	 * part's last, so every part's local rows stay dense (lol_gpu_part_frame_row is the mapping) */
@@ -557,6 +752,7 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	const int block = tile_w * tile_h;
 	dim3 grid((ss * w + tile_w - 1) / tile_w, (ss * n_rows + tile_h - 1) / tile_h);
 	const size_t common = (size_t)(lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) - lol::TILE_W * lol::TILE_H + block) * 4;
+	if (adaptive) return render_adaptive(ctx, L, dbg, s, common);
 	int trial = -1;
 	bool table = false;
 	if (aa) {
@@ -599,19 +795,7 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 		const bool counts = (dbg && dbg->steps) || L.pixel_cost;
 		e = hipModuleLaunchKernel(aa ? k->render_aa : counts ? k->render_counting : k->render, grid.x, grid.y, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
 	} else {
-		const int kind = ctx->interp_sqrt_kind;
-		const int cls = interp_stack_class(P.max_stack);
-		if (lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots)) {
-			if (cls == 1)      e = launch_interp<1>(L, grid, common, s, kind, aa);
-			else if (cls == 3) e = launch_interp<3>(L, grid, common, s, kind, aa);
-			else if (cls == 7) e = launch_interp<7>(L, grid, common, s, kind, aa);
-			else if (cls == lol::MOP_DEEP_FROM - 1) e = launch_interp<lol::MOP_DEEP_FROM - 1>(L, grid, common, s, kind, aa);
-			else               e = launch_interp<lol::MOP_DEEP_SLOTS>(L, grid, common, s, kind, aa);
-		} else {               /* large tables, read from global memory (lol_kernel.h, TABLES_LDS_MAX_DWORDS): three stack classes */
-			if (cls <= 3)      e = launch_interp<3, true>(L, grid, common, s, kind, aa);
-			else if (cls <= lol::MOP_DEEP_FROM - 1) e = launch_interp<lol::MOP_DEEP_FROM - 1, true>(L, grid, common, s, kind, aa);
-			else               e = launch_interp<lol::MOP_DEEP_SLOTS, true>(L, grid, common, s, kind, aa);
-		}
+		e = interp_frame(ctx, L, grid, common, s, aa);
 	}
 	if (g_roctx.pop) g_roctx.pop();
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch", e);
@@ -863,6 +1047,48 @@ int lol_gpu_set_samples(lol_gpu* ctx, int samples) {
 }
 
 int lol_gpu_samples(const lol_gpu* ctx) { return ctx ? ctx->samples : LOL_GPU_ERR_ARG; }
+
+int lol_gpu_set_adaptive_samples(lol_gpu* ctx, int contrast) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (contrast < -1 || contrast > 255) return fail(ctx, LOL_GPU_ERR_ARG, "adaptive contrast must be -1 (off) or 0 ... 255");
+	if (contrast >= 0 && lol::BLOCK != 64)
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "adaptive frames need one-wave blocks (this build's LOL_WAVES_X is not 1)");
+	ctx->adaptive = contrast;               /* the next frame's; a frame already queued keeps its own */
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_adaptive_samples(const lol_gpu* ctx) { return ctx ? ctx->adaptive : LOL_GPU_ERR_ARG; }
+
+/* the set of the context's last adaptive frame, waited for */
+static int last_adaptive_set(lol_gpu* ctx, lol_gpu::AdaptiveSet** out) {
+	if (ctx->adaptive_last < 0 || !ctx->adaptive_sets[ctx->adaptive_last].d_count)
+		return fail(ctx, LOL_GPU_ERR_ARG, "no adaptive frame has been launched");
+	lol_gpu::AdaptiveSet& S = ctx->adaptive_sets[ctx->adaptive_last];
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	LOL_HIP(ctx, hipEventSynchronize(S.ev[3]));
+	*out = &S;
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_adaptive_refined(lol_gpu* ctx, int64_t* n) {
+	if (!ctx || !n) return LOL_GPU_ERR_ARG;
+	lol_gpu::AdaptiveSet* S = nullptr;
+	const int st = last_adaptive_set(ctx, &S);
+	if (st != LOL_GPU_OK) return st;
+	uint32_t c = 0;
+	LOL_HIP(ctx, hipMemcpy(&c, S->d_count, 4, hipMemcpyDeviceToHost));
+	*n = c;
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_adaptive_pass_ms(lol_gpu* ctx, float ms[3]) {
+	if (!ctx || !ms) return LOL_GPU_ERR_ARG;
+	lol_gpu::AdaptiveSet* S = nullptr;
+	const int st = last_adaptive_set(ctx, &S);
+	if (st != LOL_GPU_OK) return st;
+	for (int i = 0; i < 3; i++) LOL_HIP(ctx, hipEventElapsedTime(&ms[i], S->ev[i], S->ev[i + 1]));
+	return LOL_GPU_OK;
+}
 
 long lol_gpu_roctx_ranges(void) {
 	g_roctx.init();

@@ -128,6 +128,7 @@ struct SceneKernel {
 	hipFunction_t render_counting = nullptr;   /* lol_render_spec_steps — or lol_render_spec where the module holds that one alone: it counts */
 	hipFunction_t sdf = nullptr;               /* lol_sdf_spec (lol_gpu_sdf_batch) */
 	hipFunction_t render_aa = nullptr;         /* lol_render_spec_aa, where the module was compiled with it (lol_gpu_set_samples) */
+	hipFunction_t render_aa_list = nullptr;    /* ... and lol_render_spec_aa_list beside it (the refine pass of adaptive frames) */
 	std::string   key;                         /* FNV-1a of the code object (lol_gpu_kernel_key) */
 	explicit operator bool() const { return module != nullptr; }
 	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
@@ -200,6 +201,24 @@ struct lol_gpu {
 	std::string  interp_key;             /* FNV-1a of {this build, the uploaded macro-op lists}: lol_gpu_kernel_key of the interpreter */
 	std::string  interp_aa_key;          /* ... and of its supersampling kernel (render_interp_aa) */
 	int          samples = 1;            /* lol_gpu_set_samples: samples per pixel along each axis of the frames launched from now on */
+	int          adaptive = -1;          /* lol_gpu_set_adaptive_samples: the contrast T, or -1 (off) */
+	/* Scratch of adaptive frames (render_adaptive, lol_gpu.hip): a ring of sets, one per frame, whatever its stream.  A frame waits
+	 * on its set's `ev[3]` (behind the last frame that used it) with hipStreamWaitEvent and records it again at its end; ev[0] marks
+	 * its start, ev[1] and ev[2] the ends of its first two passes (lol_gpu_adaptive_pass_ms).  Sets grow with the frame, freed in
+	 * lol_gpu_destroy. */
+	struct AdaptiveSet {
+		uint32_t*  d_buf = nullptr;          /* plain xrgb [w h] | ids [w h] | list [w h] | count [64] | lane table [64 per refine block] */
+		size_t     bytes = 0;
+		uint32_t*  d_count = nullptr;        /* the list's length of the set's last frame */
+		hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+		bool       used = false;             /* ev[] have been recorded */
+	};
+	static constexpr int ADAPTIVE_SETS = 4;
+	AdaptiveSet  adaptive_sets[ADAPTIVE_SETS];
+	unsigned     adaptive_rr = 0;
+	int          adaptive_last = -1;     /* the set of the last adaptive frame (lol_gpu_adaptive_refined) */
+	uint32_t*    d_adaptive_order = nullptr;   /* the refine pass's block -> lane-table slot table: slot b at tile_slot(b, stride) */
+	uint32_t     adaptive_blocks = 0, adaptive_stride = 0;      /* its size in blocks (the most a refine grid has); ceil(blocks / 8) */
 	int          fail_uploads = 0;       /* lol_gpu_testing_fail_uploads: that many uploads still fail at the copy */
 	int          want_fast = 1;          /* allow the proven-exact shortcuts in the specialised kernel */
 	unsigned     want_skips = 7;         /* exact skips allowed when the program qualifies: bit 0 escaped waves, 1 zero incidence, 2 settled shadows */

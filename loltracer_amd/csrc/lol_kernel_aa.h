@@ -117,4 +117,76 @@ void render_interp_aa(const Launch L) {
 	store_pixel_aa<TABLES_GLOBAL>(L, P.rgb);
 }
 
+/*
+ * Adaptive supersampling (lol_gpu_set_adaptive_samples): the s x s pixel of a LIST of pixels, the refine pass of an adaptive frame
+ * (lol_gpu.hip, render_adaptive).  `list` holds *count entries x | y << 16, whole-frame pixels, written in tile order by
+ * adaptive_classify.  A grid-stride loop over the list: group g of 64 / s^2 consecutive entries goes to wave g mod (waves in the
+ * grid), so a grid sized to fill the device serves any length read from device memory.
+ *
+ * Lane = e s^2 + k, k = j s + i: entry e of the group, sample (i, j) of its pixel.  An xor butterfly over the bits of k, lowest
+ * first, is the tree of the contract (store_pixel_aa's, over other lane bits).  shade_pixel (lol_kernel.h, unchanged) finds its
+ * sample through its pixel-table path (FLAG_TILE_TABLE): the wave writes the 64 sample coordinates of the group into its own slot
+ * of Launch::lane_pixels, slot Launch::tile_order[tile_slot(blockIdx.x, tile_stride)] (the host makes that blockIdx.x), and
+ * shade_pixel reads them back in the same lanes.  The sample grid must therefore fit that table's fields: s w <= 65536, s h <=
+ * 32768 (checked by the host).  Launch::band_rows / cycle_rows / offset_rows describe the whole frame.
+ *
+ * `shade(S)` = the lane's Pixel for sample launch S, the fast SDF's exact fallback included: every wave reshades before anything is
+ * reduced.  One wave per block (the host refuses adaptive frames where BLOCK != 64).
+ */
+template <bool TABLES_GLOBAL, class Shade>
+__device__ __forceinline__ void render_aa_list(const Launch& L, const u32* list, const u32* count, Shade&& shade) {
+	const int s = samples_of(L.flags), ss = s * s;
+	const u32 per_wave = 64u / (u32)ss;
+	const u32 n = __builtin_amdgcn_readfirstlane(*count);
+	Launch S = sample_launch(L);
+	S.flags |= FLAG_TILE_TABLE;
+	/* (the lane's entry and pixel are read again after shading rather than held across it: registers are what the march needs) */
+	for (u32 g = blockIdx.x; g * per_wave < n; g += gridDim.x) {
+		{
+			const int lane = threadIdx.x & 63, k = lane & (ss - 1);
+			const u32 e = g * per_wave + (u32)(lane / ss);
+			const u32 px = list[e < n ? e : n - 1u];                 /* (lanes past the end shade the last entry again, store nothing) */
+			const u32 slot = L.tile_order[tile_slot(blockIdx.x, L.tile_stride)];
+			const_cast<u32*>(L.lane_pixels)[(unsigned long long)slot * 64u + (u32)lane] =
+				(u32)(s * (int)(px & 0xFFFFu) + (k & (s - 1))) | (u32)(s * (int)(px >> 16) + k / s) << 16;
+		}
+		const Pixel P = shade(S);
+		V3 c = P.rgb;
+		for (int m = 1; m < ss; m <<= 1) c = aa_add_xor(c, m);
+		c = scale(c, s == 4 ? 1.f / 16.f : 1.f / 4.f);             /* 1 / s^2 */
+		const LaunchTail T = launch_tail(L);
+		V3 post;
+		const u32 out = pack_pixel(L, T, c, post);
+		const int lane = threadIdx.x & 63, k = lane & (ss - 1);
+		const u32 e = g * per_wave + (u32)(lane / ss);
+		if (k == 0 && e < n) {
+			const u32 px = list[e];
+			const int x = (int)(px & 0xFFFFu), y = (int)(px >> 16);
+			const unsigned long long o = (unsigned long long)y * L.w + x;
+			if (T.dbg_rgb) { T.dbg_rgb[o * 3 + 0] = post.x; T.dbg_rgb[o * 3 + 1] = post.y; T.dbg_rgb[o * 3 + 2] = post.z; }
+			T.dst[(unsigned long long)y * T.pitch_px + x] = out;
+		}
+	}
+}
+
+/* The interpreter's refine pass: one instantiation per render_interp_aa */
+template <int SSIZE, int KIND, bool TABLES_GLOBAL = false>
+__global__ __launch_bounds__(BLOCK)
+void render_interp_aa_list(const Launch L, const u32* list, const u32* count) {
+	extern __shared__ u32 lds[];
+	if constexpr (!TABLES_GLOBAL) {
+		stage_common(L, lds);
+		__syncthreads();
+	}
+	render_aa_list<TABLES_GLOBAL>(L, list, count, [&](const Launch& S) {
+		Interp<SSIZE, KIND> sdf{ L.ops, L.n_ops, {}, 0u };
+		Pixel P = shade_pixel<Interp<SSIZE, KIND>, TABLES_GLOBAL, false>(S, sdf, lds);
+		if (KIND != 0 && unproven(sdf)) {
+			Interp<SSIZE, 0> exact{ L.ops, L.n_ops, {}, 0u };
+			P = shade_pixel<Interp<SSIZE, 0>, TABLES_GLOBAL, false>(S, exact, lds);
+		}
+		return P;
+	});
+}
+
 }  // namespace lol

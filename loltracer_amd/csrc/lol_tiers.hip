@@ -90,7 +90,7 @@ bool load_scene_kernel(const std::vector<char>& code, uint32_t n_ops, bool aa, S
 	k.key = fnv_hex(code.data(), code.size());
 	if (hipModuleLoadData(&k.module, code.data()) != hipSuccess) why = "hipModuleLoadData failed";
 	else if (get(k.render, "lol_render_spec") && (!two || get(k.render_counting, "lol_render_spec_steps")) && get(k.sdf, "lol_sdf_spec") &&
-	         (!aa || get(k.render_aa, "lol_render_spec_aa"))) {
+	         (!aa || (get(k.render_aa, "lol_render_spec_aa") && get(k.render_aa_list, "lol_render_spec_aa_list")))) {
 		if (!two) k.render_counting = k.render;
 		return true;
 	}

@@ -178,6 +178,14 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_set_samples.restype = C.c_int
         lib.lol_gpu_samples.argtypes = [vp]
         lib.lol_gpu_samples.restype = C.c_int
+        lib.lol_gpu_set_adaptive_samples.argtypes = [vp, C.c_int]
+        lib.lol_gpu_set_adaptive_samples.restype = C.c_int
+        lib.lol_gpu_adaptive_samples.argtypes = [vp]
+        lib.lol_gpu_adaptive_samples.restype = C.c_int
+        lib.lol_gpu_adaptive_refined.argtypes = [vp, P(C.c_int64)]
+        lib.lol_gpu_adaptive_refined.restype = C.c_int
+        lib.lol_gpu_adaptive_pass_ms.argtypes = [vp, P(C.c_float)]
+        lib.lol_gpu_adaptive_pass_ms.restype = C.c_int
         lib.lol_gpu_multi_set_samples.argtypes = [vp, C.c_int]
         lib.lol_gpu_multi_set_samples.restype = C.c_int
         lib.lol_gpu_verify_fast_paths.argtypes = [vp, C.c_float, P(C.c_ulonglong), P(C.c_ulonglong)]
@@ -288,13 +296,14 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_render_host_pending_size", "lol_gpu_render_host_discard", "lol_gpu_kernel_key", "lol_gpu_assemble_parts_at",
     "lol_gpu_split_rows", "lol_gpu_multi_set_root_band_rows", "lol_gpu_multi_set_pixel_format", "lol_gpu_multi_set_tile_order",
     "lol_gpu_set_frames_in_flight", "lol_gpu_frames_in_flight", "lol_gpu_next_stream", "lol_gpu_set_specialize_max_ops",
-    "lol_gpu_set_samples", "lol_gpu_samples", "lol_gpu_multi_set_samples",
+    "lol_gpu_set_samples", "lol_gpu_samples", "lol_gpu_multi_set_samples", "lol_gpu_set_adaptive_samples",
+    "lol_gpu_adaptive_samples",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
     "lol_gpu_tuning_switches", "lol_gpu_roctx_ranges", "lol_gpu_verify_fast_paths", "lol_gpu_verify_smin_no_fixup",
     "lol_gpu_verify_gamma_table", "lol_gpu_cull_bounds", "lol_gpu_cull_bounds_clusters", "lol_gpu_powf_batch",
-    "lol_gpu_sdf_batch", "lol_gpu_compile_offline_samples",
+    "lol_gpu_sdf_batch", "lol_gpu_compile_offline_samples", "lol_gpu_adaptive_refined", "lol_gpu_adaptive_pass_ms",
 ]
 
 
@@ -481,6 +490,29 @@ class Renderer:
     @property
     def samples(self) -> int:
         return int(self._lib.lol_gpu_samples(self._ctx))
+
+    def set_adaptive_samples(self, contrast: int):
+        """Adaptive supersampling from the next frame on: with set_samples(s > 1), only pixels on an edge of the plain frame (an
+        object id, or an 8-bit channel more than `contrast` away, among the 8 neighbours) get s x s samples; the others are the
+        plain pixel (lol_gpu.h).  0 <= contrast <= 255; -1 turns it off (the default).  Whole frames only."""
+        self._check(self._lib.lol_gpu_set_adaptive_samples(self._ctx, int(contrast)))
+
+    @property
+    def adaptive_samples(self) -> int:
+        """the contrast of adaptive supersampling, or -1 (off)"""
+        return int(self._lib.lol_gpu_adaptive_samples(self._ctx))
+
+    def adaptive_refined(self) -> int:
+        """how many pixels of the last adaptive frame were refined (waits for that frame)"""
+        n = C.c_int64()
+        self._check(self._lib.lol_gpu_adaptive_refined(self._ctx, C.byref(n)))
+        return int(n.value)
+
+    def adaptive_pass_ms(self) -> tuple:
+        """(plain frame, mask and list, refined pixels): milliseconds each pass of the last adaptive frame took on the device"""
+        ms = (C.c_float * 3)()
+        self._check(self._lib.lol_gpu_adaptive_pass_ms(self._ctx, ms))
+        return tuple(float(v) for v in ms)
 
     def verify_fast_paths(self, k: float = 3.0):
         """([sqrt_pm, sqrt_gs, sqrt_r2], x/k) mismatch counts over all 2^32 float inputs; 0 means proven exact."""
