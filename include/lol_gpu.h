@@ -249,10 +249,50 @@ int         lol_gpu_samples(const lol_gpu* ctx);
 int         lol_gpu_set_adaptive_samples(lol_gpu* ctx, int contrast);
 int         lol_gpu_adaptive_samples(const lol_gpu* ctx);
 
+/*
+ * A batch of views: n_views frames of the same size, scene and settings under n_views cameras, in ONE launch.  For hosts that have
+ * all their cameras in hand and want small frames — a contact sheet of an orbit, thumbnails from a ring of viewpoints, a few
+ * thousand 128 x 128 views with depth and object ids — where a launch, a launch tail and a first-step evaluation per view cost
+ * more than the view itself.
+ * View v (0 <= v < n_views) is EXACTLY the frame lol_gpu_render_device(ctx, &cams[v], w, h, max_steps, NULL, ...) renders with one
+ * sample per pixel in a fixed tile order: the same pixels in the context's pixel format, the same rgb, hit_dist, hit_id and steps
+ * (lol_gpu_set_exact_skips and lol_gpu_set_miss_skip apply to every view as they do to a frame).  Row y of view v starts at
+ * dst + v * view_stride_bytes + y * pitch_bytes; pitch_bytes >= 4 w and a multiple of 4; view_stride_bytes >= h * pitch_bytes and
+ * a multiple of 4; bytes between rows and between views are not written.  The diagnostics of `dbg` (NULL = none), each optional,
+ * are dense: element (v, y, x) at index (v * h + y) * w + x (three floats each for rgb).
+ * `cams` is HOST memory and is copied before the call returns.  The call is asynchronous on `stream` like lol_gpu_render_device
+ * (NULL = the context's streams in turn, lol_gpu_set_frames_in_flight): one small copy of the per-view records and one render
+ * launch, no wait for any render.  Batches on different streams may be in flight together; the records go through a ring of 8
+ * sets, so a host that queues batches faster than the device renders them is held 8 batches ahead of it (and a batch on one of
+ * HIP's special stream handles — LOL_GPU_STREAM_DEFAULT — waits on the host for the batch that used its set 8 calls before).
+ * Everything lol_gpu_render_device decides per frame from the camera is decided per view — the primary march's first step, and
+ * what a camera beyond the sane range (a coordinate that is not finite, or at least 10^15 in magnitude) switches off — so a batch
+ * may mix any cameras.  The views are rendered in order of v in a fixed tile order (columns under LOL_GPU_TILES_COLS, rows
+ * otherwise), view v + 1's first waves filling view v's tail; a batch neither uses nor changes the state of LOL_GPU_TILES_LPT /
+ * _AUTO: a plain frame after it is scheduled as if the batch had not been there.
+ * Refused, with nothing launched and nothing written: n_views < 1 or > LOL_GPU_MAX_VIEWS, bad geometry, a frame of more than
+ * 65535 tiles (16 x 4 pixels) along an axis, or more than 2^32 - 1 lanes in the whole launch (fewer views per call) —
+ * LOL_GPU_ERR_ARG; lol_gpu_samples() > 1 — LOL_GPU_ERR_UNSUPPORTED: supersampled and adaptive batches are not built; no program —
+ * LOL_GPU_ERR_NO_PROGRAM.  There are no row partitions and no lol_gpu_multi_* form: a host with several devices stripes its VIEWS
+ * over them, one context each.
+ * Which kernel: after lol_gpu_set_view_batches(ctx, 1) BEFORE lol_gpu_upload_program the scene's own module also carries
+ * lol_render_spec_batch (both kernels of a 257 ... 1024-op scene do), and batches run on it once it is ready; otherwise, and until
+ * then, they run on the interpreter's render_interp_batch — same pixels either way.  A module compiled without the switch is the
+ * module it was before batches existed (same code object, same lol_gpu_kernel_key).
+ */
+#define LOL_GPU_MAX_VIEWS 4096
+int         lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
+                                 void* dst, size_t pitch_bytes, size_t view_stride_bytes,
+                                 const lol_gpu_debug* dbg, void* stream);
+int         lol_gpu_set_view_batches(lol_gpu* ctx, int enable);
+int         lol_gpu_view_batches(const lol_gpu* ctx);
+
 /* Name of the kernel a launch uses (for matching rocprofv3 kernel-trace rows):
  * "lol_render_spec" (scene-specialised, compiled by hipRTC at upload) or "render_interp"; with supersampling
  * (lol_gpu_set_samples) "lol_render_spec_aa" or "render_interp_aa"; for adaptive frames (lol_gpu_set_adaptive_samples) the
- * kernel of their refine pass, "lol_render_spec_aa_list" or "render_interp_aa_list". */
+ * kernel of their refine pass, "lol_render_spec_aa_list" or "render_interp_aa_list".  It describes FRAMES: batches of views
+ * (lol_gpu_render_views) run "lol_render_spec_batch" ("lol_render_spec_batch_steps" with lol_gpu_debug.steps) or
+ * "render_interp_batch". */
 const char* lol_gpu_kernel_name(const lol_gpu* ctx);
 /* Identity of the code that kernel is: 16 hex digits — FNV-1a of the hipRTC code object for "lol_render_spec"; for
  * "render_interp" of {this library's build id (a digest of its sources and compiler flags), the uploaded macro-op lists,

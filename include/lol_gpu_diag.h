@@ -78,6 +78,15 @@ int         lol_gpu_sdf_batch(lol_gpu* ctx, const float* pts_dev, float* dist_de
 int         lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                             int samples, char* log, size_t logcap);
 /*
+ * ... and for a context that asked for batches of views (lol_gpu_set_view_batches) before its upload: enable = 0 writes exactly
+ * what lol_gpu_compile_offline writes; otherwise the same source with lol_render_spec_batch (and, up to 256 ops,
+ * lol_render_spec_batch_steps) appended, and its code object.  form: 0 = the form a scene of this size ends up with, 1 = the SDF as
+ * one out-of-line function, 2 = inlined — the two kernels a scene of 257 ... 1024 ops gets one after the other.  LOL_GPU_ERR_ARG
+ * for any other form.
+ */
+int         lol_gpu_compile_offline_views(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                          int enable, int form, char* log, size_t logcap);
+/*
  * Adaptive frames (lol_gpu_set_adaptive_samples): waits for the context's last adaptive frame and gives how many of its pixels
  * were refined (*n), or the time its three passes took on the device, in milliseconds between events on its stream (ms[0] the
  * plain frame, ms[1] the mask and the list, ms[2] the refined pixels).  LOL_GPU_ERR_ARG when no adaptive frame was launched.

@@ -1,17 +1,52 @@
 """python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N] [--samples N]
-                          [--adaptive T]
+                          [--adaptive T] [--orbit K -o DIR]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
-`loltracer_amd/lib/lol_headless`.  There is no CPU rendering path."""
+`loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
+(Renderer.render_views_into) and writes DIR/view_0000.ppm ...  There is no CPU rendering path."""
 from __future__ import annotations
 
 import argparse
+import os
 import sys
 import time
 
 import numpy as np
 
 from . import gpu, scene as S
+
+
+def write_ppm(path, surf):
+    rgb = np.stack([(surf >> 16) & 0xFF, (surf >> 8) & 0xFF, surf & 0xFF], axis=-1).astype(np.uint8)
+    with open(path, "wb") as fp:
+        fp.write(b"P6\n%d %d\n255\n" % (surf.shape[1], surf.shape[0]))
+        fp.write(rgb.tobytes())
+
+
+def orbit(sc, args, w, h) -> int:
+    """K views of one batch into K PPMs"""
+    k = args.orbit
+    r = gpu.Renderer(args.device)
+    try:
+        r.set_view_batches(True)             # before prepare(): the scene's own kernel then carries the batch form
+        r.prepare(sc)
+        views = np.zeros((k, h, w), dtype=np.uint32)
+        dev = r.malloc(views.nbytes)
+        try:
+            t0 = time.perf_counter()
+            r.render_views_into(dev, S.orbit_cameras(sc, k), w, h, args.max_steps)
+            r.sync()
+            dt = (time.perf_counter() - t0) * 1e3
+            r.memcpy_d2h(views.ctypes.data, dev, views.nbytes)
+        finally:
+            r.free(dev)
+    finally:
+        r.close()
+    print(f"{k} views of {w}x{h}: {dt:.3f}ms  {k * w * h / dt / 1e3:.1f} Mpixels/s")
+    os.makedirs(args.out, exist_ok=True)
+    for v in range(k):
+        write_ppm(os.path.join(args.out, f"view_{v:04d}.ppm"), views[v])
+    return 0
 
 
 def main(argv=None) -> int:
@@ -25,6 +60,8 @@ def main(argv=None) -> int:
     ap.add_argument("--samples", type=int, default=1, choices=(1, 2, 4), help="N x N samples per pixel (supersampling)")
     ap.add_argument("--adaptive", type=int, default=-1, metavar="T",
                     help="with --samples N: N x N samples only at edges of the plain frame (contrast T, 0 ... 255)")
+    ap.add_argument("--orbit", type=int, default=0, metavar="K",
+                    help="K views from a circle round the scene in one batch; -o names the directory the PPMs go to")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     try:
@@ -35,6 +72,12 @@ def main(argv=None) -> int:
     if not sc.validate_materials():
         print("scene_validate_materials failed", file=sys.stderr)
         return 1
+    if args.orbit:
+        if (args.orbit < 1 or args.orbit > gpu.MAX_VIEWS or args.samples != 1 or args.adaptive != -1 or args.frames != 1
+                or not args.out):
+            print(f"--orbit takes 1 ... {gpu.MAX_VIEWS} views and -o DIR; not with --samples, --adaptive or --frames", file=sys.stderr)
+            return 1
+        return orbit(sc, args, w, h)
     r = gpu.Renderer(args.device)
     r.set_samples(args.samples)          # before prepare(): the scene's own kernel then carries the supersampling form
     if args.adaptive != -1:
@@ -47,10 +90,7 @@ def main(argv=None) -> int:
         dt = (time.perf_counter() - t0) * 1e3
         print(f"Frame {f + 1}: {dt:.3f}ms  {w * h / dt / 1e3:.1f} Mpixels/s  [{r.kernel_name()}]")
     if args.out:
-        rgb = np.stack([(surf >> 16) & 0xFF, (surf >> 8) & 0xFF, surf & 0xFF], axis=-1).astype(np.uint8)
-        with open(args.out, "wb") as fp:
-            fp.write(b"P6\n%d %d\n255\n" % (w, h))
-            fp.write(rgb.tobytes())
+        write_ppm(args.out, surf)
     r.close()
     return 0
 

@@ -6,7 +6,7 @@
  */
 #include "lol_gpu_internal.h"
 
-/* lol_kernel.h's and lol_kernel_aa.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
+/* lol_kernel.h's, lol_kernel_aa.h's and lol_kernel_batch.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
 #include "lol_kernel_src.inc"
 
 #pragma GCC visibility push(hidden)
@@ -745,7 +745,7 @@ bool spec_out_of_line(const lol_program& P, int form) {
 	return P.n_ops > limit;
 }
 
-std::string generate_source(const lol_program& P, const FastPaths* fast, bool cull, int form = SPEC_BY_SIZE, bool aa = false) {
+std::string generate_source(const lol_program& P, const FastPaths* fast, bool cull, int form = SPEC_BY_SIZE, bool aa = false, bool batch = false) {
 	std::string s;
 	const bool ool = spec_out_of_line(P, form);
 	const std::vector<RootBound> roots = analyse_roots(P);
@@ -850,6 +850,37 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 		s += "\t\treturn P;\n";
 		s += "\t});\n";
 		s += "}\n";
+	}
+	/* Batches of views (lol_gpu_set_view_batches before the upload): the same pipeline on the launch of the block's view
+	 * (lol_kernel_batch.h), stored at that view's address.  Appended after everything else, for the reason above.  With and without
+	 * the step counters like lol_render_spec: a batch with lol_gpu_debug::steps runs lol_render_spec_batch_steps. */
+	if (batch) {
+		s += "#include \"lol_kernel_batch.h\"\n";
+		s += "template <bool COUNT> __device__ __forceinline__ void lol_spec_batch_body(const lol::Launch& L, const lol::BatchTail& B, lol::u32* lds) {\n";
+		if (!tables_global) s += "\tlol::stage_common(L, lds);\n\t__syncthreads();\n";
+		s += "\tconst lol::Launch S = lol::view_launch(L, B.views);\n";
+		if (any_fast) {
+			/* (the VIEW's FLAG_SHADOW_SETTLED: a camera beyond the sane range in the middle of a batch takes the plain pipeline) */
+			s += "\tlol::Pixel P;\n";
+			s += "\tbool plain = !(S.flags & lol::FLAG_SHADOW_SETTLED);\n";
+			s += "\tif (!plain) {\n";
+			s += "\t\tlol::SpecSdfFast fast;\n";
+			s += "\t\tP = lol::shade_pixel<lol::SpecSdfFast, " + tg + ", COUNT>(S, fast, lds);\n";
+			s += "\t\tplain = lol::unproven(fast);\n";
+			s += "\t}\n";
+			s += "\tif (plain) {\n";
+			s += "\t\tlol::SpecSdfExact exact;\n";
+			s += "\t\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", COUNT>(S, exact, lds);\n";
+			s += "\t}\n";
+		} else {
+			s += "\tlol::SpecSdfExact exact;\n";
+			s += "\tconst lol::Pixel P = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", COUNT>(S, exact, lds);\n";
+		}
+		s += "\tlol::store_pixel_view(L, B, P);\n";
+		s += "}\n";
+		const std::string btail = "(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n\tlol_spec_batch_body<";
+		if (two) s += head + "lol_render_spec_batch_steps" + btail + "true>(L, B, lds);\n}\n";
+		s += head + "lol_render_spec_batch" + btail + (two ? "false" : "true") + ">(L, B, lds);\n}\n";
 	}
 	return s;
 }
@@ -968,8 +999,8 @@ bool has_return_clobbering_branch(const std::vector<char>& code) { return has_re
 
 /* hipRTC: generated source + lol_kernel.h → code object for `arch`.  Needs no device. */
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
-                  std::string& log, std::string* src_out, bool cull, int form, bool aa) {
-	std::string src = generate_source(P, fast, cull, form, aa);
+                  std::string& log, std::string* src_out, bool cull, int form, bool aa, bool batch) {
+	std::string src = generate_source(P, fast, cull, form, aa, batch);
 	if (src_out) *src_out = src;
 	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
 		if (FILE* f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
@@ -1031,7 +1062,8 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	}
 	/* on disk the pipeline source (lol_kernel.h, embedded in this library) is part of the key: another build of the
 	 * library must not pick up this one's kernels */
-	const std::string disk_key = key + "|" + LOL_KERNEL_H_TEXT + (aa ? std::string("|") + LOL_KERNEL_AA_H_TEXT : std::string());
+	const std::string disk_key = key + "|" + LOL_KERNEL_H_TEXT + (aa ? std::string("|") + LOL_KERNEL_AA_H_TEXT : std::string()) +
+	                             (batch ? std::string("|batch|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT : std::string());
 	if (disk_cache_load(disk_key, code)) {
 		std::lock_guard<std::mutex> lock(g_cache_mutex);
 		g_code_cache[key] = code;
@@ -1039,9 +1071,10 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 		return true;
 	}
 	/* lol_kernel_aa.h only where the source includes it: hipRTC's compilation-unit id — bytes of the code object — follows the headers */
-	const char* hdr_src[] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT };
-	const char* hdr_name[] = { "lol_kernel.h", "lol_kernel_aa.h" };
-	const int n_hdr = aa ? 2 : 1;
+	/* ... and lol_kernel_batch.h (which includes lol_kernel_aa.h for pack_pixel) only where the module carries the batch kernel */
+	const char* hdr_src[] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT };
+	const char* hdr_name[] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h" };
+	const int n_hdr = batch ? 3 : aa ? 2 : 1;
 	hiprtcProgram prog = nullptr;
 	if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_hdr, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
 		log = "hiprtcCreateProgram failed";
@@ -1157,8 +1190,24 @@ int lol_gpu_compile_offline(const lol_program* prog, const char* arch, const cha
 
 /* ... the module a context with lol_gpu_set_samples(ctx, samples) compiles at its upload: with samples > 1 it also carries
  * lol_render_spec_aa (lol_gpu_diag.h) */
+static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples, bool batch,
+                           int form, char* log, size_t logcap);
+
 int lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples,
                                     char* log, size_t logcap) {
+	return compile_offline(prog, arch, out_base, assume_fast, samples, false, SPEC_BY_SIZE, log, logcap);
+}
+
+/* ... the module a context with lol_gpu_set_view_batches(ctx, 1) compiles at its upload, in the form of one of its tiers
+ * (lol_gpu_diag.h) */
+int lol_gpu_compile_offline_views(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable, int form,
+                                  char* log, size_t logcap) {
+	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
+	return compile_offline(prog, arch, out_base, assume_fast, 1, enable != 0, form, log, logcap);
+}
+
+static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples, bool batch,
+                           int form, char* log, size_t logcap) {
 	if (!prog || !arch || (samples != 1 && samples != 2 && samples != 4)) return LOL_GPU_ERR_ARG;
 	std::vector<char> code;
 	std::string lg, src;
@@ -1175,7 +1224,7 @@ int lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, c
 		/* on the large-stack thread, like every run of the scene compiler (BigStackThread) */
 		BigStackThread th;
 		auto work = [&]() {
-			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), SPEC_BY_SIZE, samples > 1); }
+			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), form, samples > 1, batch); }
 			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
 		};
 		bool started = false;

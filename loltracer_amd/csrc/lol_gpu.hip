@@ -106,6 +106,14 @@ hipError_t launch_interp(const lol::Launch& L, dim3 grid, size_t lds, hipStream_
 }
 
 
+/* a batch of views on the interpreter (lol_kernel_batch.h): the instantiation beside launch_interp's */
+template <int SSIZE, bool TABLES_GLOBAL = false>
+hipError_t launch_interp_batch(const lol::Launch& L, const lol::BatchTail& B, dim3 grid, size_t lds, hipStream_t s, int sqrt_kind) {
+	if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_batch<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B);
+	else                hipLaunchKernelGGL((lol::render_interp_batch<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B);
+	return hipGetLastError();
+}
+
 /* Conditions under which an escaped ray's colour is exactly clamp(ambient * materials[0].ambient), so
  * that waves of escaped rays may skip normal + lights (lol_kernel.h, FLAG_MISS_SKIP): material #0 has
  * diffuse == specular == 0 (either sign), shininess >= 0 and not NaN (powf(c in [0,1], s >= 0) is finite),
@@ -286,24 +294,41 @@ const char* kernel_name(const lol_gpu* ctx) {
 	return scene_kernel(ctx) ? "lol_render_spec" : "render_interp";
 }
 
-/* a frame (or pass) on the interpreter: the instantiation for the program's stack class and table placement; `list`, `count`: the
- * refine pass of an adaptive frame */
-hipError_t interp_frame(const lol_gpu* ctx, const lol::Launch& L, dim3 grid, size_t common, hipStream_t s, bool aa,
-                        const uint32_t* list = nullptr, const uint32_t* count = nullptr) {
+/* The interpreter's instantiation for the program's stack class and table placement — THE ladder, for every kernel the interpreter
+ * has (frames, supersampled frames, refine passes, batches of views): launch(ssize, tables_global) is called with the two as
+ * compile-time constants. */
+template <int SSIZE, bool TABLES_GLOBAL = false> struct InterpVariant {
+	static constexpr int ssize = SSIZE;
+	static constexpr bool tables_global = TABLES_GLOBAL;
+};
+template <class Launcher>
+hipError_t interp_dispatch(const lol_gpu* ctx, Launcher&& launch) {
 	const lol_program& P = ctx->h_prog;
-	const int kind = ctx->interp_sqrt_kind;
 	const int cls = interp_stack_class(P.max_stack);
 	if (lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots)) {
-		if (cls == 1)      return launch_interp<1>(L, grid, common, s, kind, aa, list, count);
-		else if (cls == 3) return launch_interp<3>(L, grid, common, s, kind, aa, list, count);
-		else if (cls == 7) return launch_interp<7>(L, grid, common, s, kind, aa, list, count);
-		else if (cls == lol::MOP_DEEP_FROM - 1) return launch_interp<lol::MOP_DEEP_FROM - 1>(L, grid, common, s, kind, aa, list, count);
-		else               return launch_interp<lol::MOP_DEEP_SLOTS>(L, grid, common, s, kind, aa, list, count);
+		if (cls == 1)      return launch(InterpVariant<1>());
+		else if (cls == 3) return launch(InterpVariant<3>());
+		else if (cls == 7) return launch(InterpVariant<7>());
+		else if (cls == lol::MOP_DEEP_FROM - 1) return launch(InterpVariant<lol::MOP_DEEP_FROM - 1>());
+		else               return launch(InterpVariant<lol::MOP_DEEP_SLOTS>());
 	}
 	/* large tables, read from global memory (lol_kernel.h, TABLES_LDS_MAX_DWORDS): three stack classes */
-	if (cls <= 3)      return launch_interp<3, true>(L, grid, common, s, kind, aa, list, count);
-	else if (cls <= lol::MOP_DEEP_FROM - 1) return launch_interp<lol::MOP_DEEP_FROM - 1, true>(L, grid, common, s, kind, aa, list, count);
-	else               return launch_interp<lol::MOP_DEEP_SLOTS, true>(L, grid, common, s, kind, aa, list, count);
+	if (cls <= 3)      return launch(InterpVariant<3, true>());
+	else if (cls <= lol::MOP_DEEP_FROM - 1) return launch(InterpVariant<lol::MOP_DEEP_FROM - 1, true>());
+	else               return launch(InterpVariant<lol::MOP_DEEP_SLOTS, true>());
+}
+
+/* a frame (or pass) on the interpreter; `list`, `count`: the refine pass of an adaptive frame */
+hipError_t interp_frame(const lol_gpu* ctx, const lol::Launch& L, dim3 grid, size_t common, hipStream_t s, bool aa,
+                        const uint32_t* list = nullptr, const uint32_t* count = nullptr) {
+	const int kind = ctx->interp_sqrt_kind;
+	return interp_dispatch(ctx, [&](auto v) { return launch_interp<decltype(v)::ssize, decltype(v)::tables_global>(L, grid, common, s, kind, aa, list, count); });
+}
+
+/* ... and a batch of views on it: through the same ladder */
+hipError_t interp_batch(const lol_gpu* ctx, const lol::Launch& L, const lol::BatchTail& B, dim3 grid, size_t common, hipStream_t s) {
+	const int kind = ctx->interp_sqrt_kind;
+	return interp_dispatch(ctx, [&](auto v) { return launch_interp_batch<decltype(v)::ssize, decltype(v)::tables_global>(L, B, grid, common, s, kind); });
 }
 
 /*
@@ -407,6 +432,12 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 	for (lol_gpu::AdaptiveSet& S : ctx->adaptive_sets) {
 		if (S.d_buf) (void)hipFree(S.d_buf);
 		for (hipEvent_t ev : S.ev) if (ev) (void)hipEventDestroy(ev);
+	}
+	for (lol_gpu::ViewSet& S : ctx->view_sets) {
+		if (S.d_views) (void)hipFree(S.d_views);
+		if (S.h_views) (void)hipHostFree(S.h_views);
+		if (S.copied) (void)hipEventDestroy(S.copied);
+		if (S.done) (void)hipEventDestroy(S.done);
 	}
 	if (ctx->d_adaptive_order) (void)hipFree(ctx->d_adaptive_order);
 	if (ctx->d_bad) (void)hipFree(ctx->d_bad);
@@ -803,6 +834,131 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	if (trial >= 0) LOL_HIP(ctx, hipEventRecord(ctx->tiles.ev[2 * trial + 1], s));
 	return LOL_GPU_OK;
 }
+
+/*
+ * A batch of views: ONE render launch whose grid has the view as its z coordinate (lol_kernel_batch.h), behind one copy of the view
+ * records on the same stream.  Everything lol_gpu_render_device decides per frame from the camera is decided here per view and
+ * goes into the view's record: which copy of the macro-op list, FLAG_SHADOW_SETTLED (camera_sane), FLAG_FIRST_STEP and its value
+ * (first_step).  Fixed tile order; the longest-first tables, AUTO's trials and what they remember of the last frame are neither
+ * read nor written.  Records: the next set of the ring (lol_gpu_internal.h, ViewSet).
+ */
+int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
+                         void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
+	if (!ctx || !cams || !dst) return LOL_GPU_ERR_ARG;
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	if (n_views < 1 || n_views > LOL_GPU_MAX_VIEWS) return fail(ctx, LOL_GPU_ERR_ARG, "a batch holds 1 ... LOL_GPU_MAX_VIEWS views");
+	if (w <= 0 || h <= 0 || max_steps < 0 || pitch_bytes % 4 || pitch_bytes < (size_t)w * 4 ||
+	    view_stride_bytes % 4 || view_stride_bytes / pitch_bytes < (size_t)h)
+		return fail(ctx, LOL_GPU_ERR_ARG, "bad batch geometry");
+	if (ctx->samples > 1)
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "batches of views are one sample per pixel (lol_gpu_set_samples)");
+	const int tile_w = lol::TILE_W, tile_h = lol::TILE_H, block = tile_w * tile_h;
+	dim3 grid((w + tile_w - 1) / tile_w, (h + tile_h - 1) / tile_h, (unsigned)n_views);
+	/* (a grid has at most 65535 blocks in y and z, and HIP takes at most 2^32 - 1 threads per launch) */
+	if (grid.x > 65535u || grid.y > 65535u || (unsigned long long)grid.x * grid.y * grid.z * (unsigned)block > 0xFFFFFFFFull)
+		return fail(ctx, LOL_GPU_ERR_ARG, "batch too large for one launch: fewer views per call");
+
+	lol::Launch L;
+	memset(&L, 0, sizeof L);
+	L.fw = (float)w; L.fh = (float)h;
+	L.w = w; L.h = h; L.max_steps = max_steps;
+	L.n_rows = h; L.band_rows = h; L.cycle_rows = h; L.offset_rows = 0;
+	const lol_program& P = ctx->h_prog;
+	L.n_ops = ctx->n_mops; L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
+	L.ops           = ctx->d_mops[ctx->cur];                 /* (+ View::ops_offset) */
+	L.lights        = ctx->d_tables[ctx->cur];
+	L.materials     = L.lights + (size_t)P.n_lights * lol::LIGHT_DWORDS;
+	L.root_material = L.materials + (size_t)P.n_materials * lol::MATERIAL_DWORDS;
+	L.ambient[0] = P.ambient_color.x; L.ambient[1] = P.ambient_color.y; L.ambient[2] = P.ambient_color.z;
+	L.flags = (ctx->miss_skip ? lol::FLAG_MISS_SKIP : 0u) | (ctx->dark_skip ? lol::FLAG_DARK_SKIP : 0u);
+	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+	L.dst = static_cast<uint32_t*>(dst);
+	L.pitch_px = (uint32_t)(pitch_bytes / 4);
+	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
+	if (dbg) {
+		L.dbg_rgb = dbg->rgb; L.dbg_hit_dist = dbg->hit_dist;
+		L.dbg_hit_id = dbg->hit_id; L.dbg_steps = dbg->steps;
+	}
+	if (ctx->tiles.mode == LOL_GPU_TILES_COLS) {
+		L.flags |= lol::FLAG_TILE_COLS;
+		const unsigned t = grid.x; grid.x = grid.y; grid.y = t;
+	}
+
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->frame_streams[ctx->frame_rr++ % (unsigned)ctx->n_frame_streams];
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	finish_specialise(ctx, false);           /* the frame boundary at which a finished scene kernel takes over */
+	const size_t common = (size_t)(lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) - lol::TILE_W * lol::TILE_H + block) * 4;
+
+	/* the view records */
+	lol_gpu::ViewSet& S = ctx->view_sets[ctx->view_rr++ % lol_gpu::VIEW_SETS];
+	if (!S.copied) LOL_HIP(ctx, hipEventCreateWithFlags(&S.copied, hipEventDisableTiming));
+	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+	if ((size_t)n_views > S.cap) {
+		if (S.used) LOL_HIP(ctx, hipEventSynchronize(S.done));
+		if (S.d_views) (void)hipFree(S.d_views);
+		if (S.h_views) (void)hipHostFree(S.h_views);
+		S.d_views = nullptr; S.h_views = nullptr; S.cap = 0; S.used = false;
+		const size_t want = std::max<size_t>(64, (size_t)n_views);
+		LOL_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&S.d_views), want * sizeof(lol::View)));
+		LOL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&S.h_views), want * sizeof(lol::View), hipHostMallocDefault));
+		S.cap = want;
+	}
+	if (S.used) {
+		/* The pinned copy is the host's to write once the set's last COPY has run (VIEW_SETS batches ago: in practice long done; a host
+		 * that queues faster than the device renders is held VIEW_SETS batches ahead of it here).  The device copy is this batch's once
+		 * the set's last LAUNCH has finished, whatever stream it ran on — not by hipStreamWaitEvent on HIP's special handles, which
+		 * this HIP dereferences (render_adaptive): there the host waits. */
+		LOL_HIP(ctx, hipEventSynchronize(S.copied));
+		const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
+		if (!special) LOL_HIP(ctx, hipStreamWaitEvent(s, S.done, 0));
+		else LOL_HIP(ctx, hipEventSynchronize(S.done));
+	}
+	const bool settle = ctx->shadow_settle, finite = ctx->finite_scene;
+	for (int v = 0; v < n_views; v++) {
+		lol::View& V = S.h_views[v];
+		memcpy(&V.cam, &cams[v], sizeof V.cam);
+		const bool sane = camera_sane(cams[v]);
+		V.flags = settle && sane ? lol::FLAG_SHADOW_SETTLED : 0u;
+		V.ops_offset = finite && sane ? ctx->n_mops * (uint32_t)lol::MOP_DWORDS : 0u;
+		V.first_dist = 0.f; V.first_id = 0u;
+		if (first_step(ctx, cams[v], max_steps)) { V.flags |= lol::FLAG_FIRST_STEP; V.first_dist = ctx->first_dist; V.first_id = ctx->first_id; }
+	}
+	LOL_HIP(ctx, hipMemcpyAsync(S.d_views, S.h_views, (size_t)n_views * sizeof(lol::View), hipMemcpyHostToDevice, s));
+	LOL_HIP(ctx, hipEventRecord(S.copied, s));
+
+	lol::BatchTail B = { S.d_views, (unsigned long long)(view_stride_bytes / 4) };
+	g_roctx.init();
+	if (g_roctx.push) {
+		char label[96];
+		snprintf(label, sizeof label, "lol batch %d x %dx%d", n_views, w, h);
+		g_roctx.push(label);
+		g_roctx.ranges++;
+	}
+	hipError_t e;
+	const SceneKernel* k = scene_kernel(ctx);
+	if (k && k->render_batch) {
+		void* args[] = { &L, &B };
+		e = hipModuleLaunchKernel(dbg && dbg->steps ? k->render_batch_counting : k->render_batch, grid.x, grid.y, grid.z, block, 1, 1,
+		                          (unsigned)common, s, args, nullptr);
+	} else {
+		e = interp_batch(ctx, L, B, grid, common, s);
+	}
+	if (g_roctx.pop) g_roctx.pop();
+	/* (recorded even behind a failed launch: the copy above is queued, and the set's next user must find both events recorded) */
+	const hipError_t e2 = hipEventRecord(S.done, s);
+	S.used = true;
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (batch of views)", e);
+	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (batch of views)", e2);
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_set_view_batches(lol_gpu* ctx, int enable) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	ctx->view_batches = enable ? 1 : 0;      /* takes effect at the next lol_gpu_upload_program */
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_view_batches(const lol_gpu* ctx) { return ctx ? ctx->view_batches : LOL_GPU_ERR_ARG; }
 
 int lol_gpu_set_pixel_format(lol_gpu* ctx, const lol_gpu_pixel_format* fmt) {
 	if (!ctx) return LOL_GPU_ERR_ARG;

@@ -20,6 +20,7 @@
 #include "lol_gpu_testing.h"
 #include "lol_kernel.h"
 #include "lol_kernel_aa.h"
+#include "lol_kernel_batch.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -50,6 +51,11 @@
 static_assert(sizeof(lol_light) == lol::LIGHT_DWORDS * 4, "lol_light layout");
 static_assert(sizeof(lol_material) == lol::MATERIAL_DWORDS * 4, "lol_material layout");
 static_assert(sizeof(lol_frame_camera) == sizeof(lol::Cam), "lol_frame_camera layout");
+/* the batch kernels' argument segment is a Launch and a BatchTail behind it at the next multiple of 8 (lol_kernel_batch.h,
+ * view_stride_px reads the tail there) */
+static_assert(sizeof(lol::Launch) % 8 == 0 && offsetof(lol::BatchArgs, B) == sizeof(lol::Launch) &&
+              sizeof(lol::BatchArgs) == sizeof(lol::Launch) + sizeof(lol::BatchTail) && sizeof(lol::View) == 18 * 4,
+              "kernel-argument layout of the batch kernels");
 
 #pragma GCC visibility push(hidden)
 
@@ -129,6 +135,8 @@ struct SceneKernel {
 	hipFunction_t sdf = nullptr;               /* lol_sdf_spec (lol_gpu_sdf_batch) */
 	hipFunction_t render_aa = nullptr;         /* lol_render_spec_aa, where the module was compiled with it (lol_gpu_set_samples) */
 	hipFunction_t render_aa_list = nullptr;    /* ... and lol_render_spec_aa_list beside it (the refine pass of adaptive frames) */
+	hipFunction_t render_batch = nullptr;      /* lol_render_spec_batch, where the module was compiled with it (lol_gpu_set_view_batches) */
+	hipFunction_t render_batch_counting = nullptr;   /* ... and lol_render_spec_batch_steps — or the former, where the module holds that one alone */
 	std::string   key;                         /* FNV-1a of the code object (lol_gpu_kernel_key) */
 	explicit operator bool() const { return module != nullptr; }
 	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
@@ -202,6 +210,21 @@ struct lol_gpu {
 	std::string  interp_aa_key;          /* ... and of its supersampling kernel (render_interp_aa) */
 	int          samples = 1;            /* lol_gpu_set_samples: samples per pixel along each axis of the frames launched from now on */
 	int          adaptive = -1;          /* lol_gpu_set_adaptive_samples: the contrast T, or -1 (off) */
+	int          view_batches = 0;       /* lol_gpu_set_view_batches: the next upload's module carries lol_render_spec_batch */
+	/* The view records of batches (lol_gpu_render_views, lol_gpu.hip): a ring of sets, one per batch, whatever its stream.  A batch
+	 * fills its set's pinned host copy, queues the copy to the device and the launch behind it on its stream, and records `done`;
+	 * the next batch through the set waits for `copied` on the host (the pinned copy is the host's to write again) and for `done`
+	 * on its stream.  Sets grow with the batch, freed in lol_gpu_destroy. */
+	struct ViewSet {
+		lol::View* h_views = nullptr;        /* pinned */
+		lol::View* d_views = nullptr;
+		size_t     cap = 0;                  /* views both hold */
+		hipEvent_t copied = nullptr, done = nullptr;
+		bool       used = false;             /* both events have been recorded */
+	};
+	static constexpr int VIEW_SETS = 8;
+	ViewSet      view_sets[VIEW_SETS];
+	unsigned     view_rr = 0;
 	/* Scratch of adaptive frames (render_adaptive, lol_gpu.hip): a ring of sets, one per frame, whatever its stream.  A frame waits
 	 * on its set's `ev[3]` (behind the last frame that used it) with hipStreamWaitEvent and records it again at its end; ev[0] marks
 	 * its start, ev[1] and ev[2] the ends of its first two passes (lol_gpu_adaptive_pass_ms).  Sets grow with the frame, freed in
@@ -365,9 +388,10 @@ float smooth_sat_threshold(float k);
 inline bool culling_enabled(int want) { return want != 0; }      /* (lol_gpu_set_cull) */
 bool spec_out_of_line(const lol_program& P, int form = SPEC_BY_SIZE);
 /* aa: the module also carries lol_render_spec_aa (the context asked for supersampling before the upload); without it the source
- * is exactly what it was before supersampling existed */
+ * is exactly what it was before supersampling existed; batch: ... and lol_render_spec_batch (lol_gpu_set_view_batches), likewise */
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
-                  std::string& log, std::string* src_out = nullptr, bool cull = true, int form = SPEC_BY_SIZE, bool aa = false);
+                  std::string& log, std::string* src_out = nullptr, bool cull = true, int form = SPEC_BY_SIZE, bool aa = false,
+                  bool batch = false);
 /* the interpreter's two macro-op lists for `P`, one after the other (with / without v_div_fixup in the proven blend factors);
  * false: the two differ in length (cannot happen: same records by construction) */
 bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, std::vector<uint32_t>& lists, uint32_t& n_mops);

@@ -186,6 +186,15 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_adaptive_refined.restype = C.c_int
         lib.lol_gpu_adaptive_pass_ms.argtypes = [vp, P(C.c_float)]
         lib.lol_gpu_adaptive_pass_ms.restype = C.c_int
+        lib.lol_gpu_render_views.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t,
+                                             P(Debug), vp]
+        lib.lol_gpu_render_views.restype = C.c_int
+        lib.lol_gpu_set_view_batches.argtypes = [vp, C.c_int]
+        lib.lol_gpu_set_view_batches.restype = C.c_int
+        lib.lol_gpu_view_batches.argtypes = [vp]
+        lib.lol_gpu_view_batches.restype = C.c_int
+        lib.lol_gpu_compile_offline_views.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+        lib.lol_gpu_compile_offline_views.restype = C.c_int
         lib.lol_gpu_multi_set_samples.argtypes = [vp, C.c_int]
         lib.lol_gpu_multi_set_samples.restype = C.c_int
         lib.lol_gpu_verify_fast_paths.argtypes = [vp, C.c_float, P(C.c_ulonglong), P(C.c_ulonglong)]
@@ -297,13 +306,14 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_split_rows", "lol_gpu_multi_set_root_band_rows", "lol_gpu_multi_set_pixel_format", "lol_gpu_multi_set_tile_order",
     "lol_gpu_set_frames_in_flight", "lol_gpu_frames_in_flight", "lol_gpu_next_stream", "lol_gpu_set_specialize_max_ops",
     "lol_gpu_set_samples", "lol_gpu_samples", "lol_gpu_multi_set_samples", "lol_gpu_set_adaptive_samples",
-    "lol_gpu_adaptive_samples",
+    "lol_gpu_adaptive_samples", "lol_gpu_render_views", "lol_gpu_set_view_batches", "lol_gpu_view_batches",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
     "lol_gpu_tuning_switches", "lol_gpu_roctx_ranges", "lol_gpu_verify_fast_paths", "lol_gpu_verify_smin_no_fixup",
     "lol_gpu_verify_gamma_table", "lol_gpu_cull_bounds", "lol_gpu_cull_bounds_clusters", "lol_gpu_powf_batch",
     "lol_gpu_sdf_batch", "lol_gpu_compile_offline_samples", "lol_gpu_adaptive_refined", "lol_gpu_adaptive_pass_ms",
+    "lol_gpu_compile_offline_views",
 ]
 
 
@@ -331,6 +341,21 @@ def compile_offline_samples(program: S.Program, out_base: str, samples: int, arc
     if st != LOL_GPU_OK:
         raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
     return log.value.decode(errors="replace")
+
+
+def compile_offline_views(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
+                          assume_fast: bool = False) -> str:
+    """compile_offline for a context with set_view_batches(enable) before its upload: adds lol_render_spec_batch.  form: 0 by the
+    scene's size, 1 the SDF out of line, 2 inlined (the two kernels of a 257 ... 1024-op scene)."""
+    log = C.create_string_buffer(1 << 16)
+    st = gpu_lib().lol_gpu_compile_offline_views(C.byref(program), arch.encode(), os.fsencode(out_base),
+                                                 int(assume_fast), int(bool(enable)), int(form), log, len(log))
+    if st != LOL_GPU_OK:
+        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
+    return log.value.decode(errors="replace")
+
+
+MAX_VIEWS = 4096                     # LOL_GPU_MAX_VIEWS
 
 
 def part_rows(h: int, rows: Rows | None) -> int:
@@ -417,6 +442,32 @@ class Renderer:
             C.byref(debug) if debug is not None else None,
             _stream_arg(stream)))
 
+    def set_view_batches(self, enable: bool):
+        """Before prepare(): the scene's own module also carries the batch kernel (lol_render_spec_batch); without it — and until
+        that kernel is ready — render_views_into runs on the interpreter's render_interp_batch.  Same pixels either way."""
+        self._check(self._lib.lol_gpu_set_view_batches(self._ctx, 1 if enable else 0))
+
+    @property
+    def view_batches(self) -> bool:
+        return bool(self._lib.lol_gpu_view_batches(self._ctx))
+
+    def render_views_into(self, dst_ptr: int, cameras, w: int, h: int, max_steps: int = 256, pitch_bytes: int | None = None,
+                          view_stride_bytes: int | None = None, debug: Debug | None = None, stream: int | None = None):
+        """Asynchronously render len(cameras) views of w x h in ONE launch (lol_gpu_render_views): view v is exactly the frame
+        render_into renders under cameras[v] in a fixed tile order, its row y at dst_ptr + v * view_stride_bytes + y * pitch_bytes;
+        the diagnostics of `debug` are dense [view, y, x] arrays.  cameras: scene.Camera or ready scene.FrameCamera objects (the
+        array is copied before the call returns)."""
+        cams = list(cameras)
+        arr = (S.FrameCamera * max(1, len(cams)))()
+        for i, c in enumerate(cams):
+            fc = c if isinstance(c, S.FrameCamera) else self.scene.frame_camera(w, h, c)
+            C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
+        pitch = pitch_bytes if pitch_bytes is not None else w * 4
+        stride = view_stride_bytes if view_stride_bytes is not None else h * pitch
+        self._check(self._lib.lol_gpu_render_views(
+            self._ctx, arr, len(cams), w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride,
+            C.byref(debug) if debug is not None else None, _stream_arg(stream)))
+
     def render_host(self, host_ptr: int, w: int, h: int, max_steps: int = 256, camera: S.Camera | None = None,
                     pitch_bytes: int | None = None):
         """What render_thread does with surf->pixels: whole frame into a host surface, synchronous."""
@@ -465,6 +516,19 @@ class Renderer:
 
     def sync(self):
         self._check(self._lib.lol_gpu_sync(self._ctx))
+
+    def malloc(self, nbytes: int) -> int:
+        """lol_gpu_malloc: device memory on the renderer's device, for hosts without torch (free() it)."""
+        ptr = C.c_void_p()
+        self._check(self._lib.lol_gpu_malloc(self._ctx, nbytes, C.byref(ptr)))
+        return int(ptr.value or 0)
+
+    def free(self, dev_ptr: int):
+        self._check(self._lib.lol_gpu_free(self._ctx, C.c_void_p(dev_ptr)))
+
+    def memcpy_d2h(self, host_ptr: int, dev_ptr: int, nbytes: int):
+        """lol_gpu_memcpy_d2h: waits for the renderer's own streams, then copies device memory to the host."""
+        self._check(self._lib.lol_gpu_memcpy_d2h(self._ctx, C.c_void_p(host_ptr), C.c_void_p(dev_ptr), nbytes))
 
     def set_frames_in_flight(self, n: int):
         """Frames launched with stream=None go to n streams of the context in turn (1 = sequential, the default; <= 4):

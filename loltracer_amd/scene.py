@@ -9,6 +9,7 @@ scene_validate_materials → Scene.validate_materials).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -215,3 +216,45 @@ class Scene:
             self.close()
         except Exception:
             pass
+
+
+def orbit_cameras(scene: "Scene", n: int) -> list:
+    """n cameras on a circle round the scene: what a contact sheet or a ring of thumbnails wants (Renderer.render_views_into).
+
+    The circle is horizontal (constant y), at the scene camera's height, about the vertical axis through the PIVOT: the point on
+    the scene camera's axis nearest to the mean of the centres of the scene's spheres and boxes (one unit ahead of the camera when
+    the scene has none, or when that point lies behind it).  Camera i stands at angle 2 pi i / n from the scene camera's own
+    position — camera 0 is there — and looks at the pivot with the scene's field of view.  A camera straight above or below the
+    pivot has no circle to go round: every camera is then the scene's own.  Positions are computed in doubles and rounded to float."""
+    if n < 1:
+        raise ValueError("orbit_cameras: n must be at least 1")
+    cam = scene.camera
+    p = [float(v) for v in cam.point.tuple()]
+    d = [float(v) for v in cam.direction.tuple()]
+    norm = math.sqrt(sum(v * v for v in d)) or 1.0
+    d = [v / norm for v in d]
+    centres = [nd.point.tuple() for nd in scene.nodes() if nd.type in (0, 1)]      # LOL_NODE_SPHERE, LOL_NODE_BOX
+    t = 1.0
+    if centres:
+        mean = [sum(c[k] for c in centres) / len(centres) for k in range(3)]
+        along = sum((mean[k] - p[k]) * d[k] for k in range(3))
+        if along > 0.0 and math.isfinite(along):
+            t = along
+    pivot = [p[k] + t * d[k] for k in range(3)]
+    rx, rz = p[0] - pivot[0], p[2] - pivot[2]
+    radius, phase = math.hypot(rx, rz), math.atan2(rx, rz)
+    out = []
+    for i in range(n):
+        c = Camera()
+        if radius > 0.0:
+            th = phase + 2.0 * math.pi * i / n
+            pos = [pivot[0] + radius * math.sin(th), p[1], pivot[2] + radius * math.cos(th)]
+        else:
+            pos = list(p)
+        look = [pivot[k] - pos[k] for k in range(3)]
+        ln = math.sqrt(sum(v * v for v in look))
+        c.point = V3(*pos)
+        c.direction = V3(*([v / ln for v in look] if ln > 0.0 else d))
+        c.fov = cam.fov
+        out.append(c)
+    return out
