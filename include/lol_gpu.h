@@ -272,7 +272,8 @@ int         lol_gpu_adaptive_samples(const lol_gpu* ctx);
  * _AUTO: a plain frame after it is scheduled as if the batch had not been there.
  * Refused, with nothing launched and nothing written: n_views < 1 or > LOL_GPU_MAX_VIEWS, bad geometry, a frame of more than
  * 65535 tiles (16 x 4 pixels) along an axis, or more than 2^32 - 1 lanes in the whole launch (fewer views per call) —
- * LOL_GPU_ERR_ARG; lol_gpu_samples() > 1 — LOL_GPU_ERR_UNSUPPORTED: supersampled and adaptive batches are not built; no program —
+ * LOL_GPU_ERR_ARG; lol_gpu_samples() > 1 — LOL_GPU_ERR_UNSUPPORTED: supersampled and adaptive batches take their samples as arguments
+ * (lol_gpu_render_views_samples below); no program —
  * LOL_GPU_ERR_NO_PROGRAM.  There are no row partitions and no lol_gpu_multi_* form: a host with several devices stripes its VIEWS
  * over them, one context each.
  * Which kernel: after lol_gpu_set_view_batches(ctx, 1) BEFORE lol_gpu_upload_program the scene's own module also carries
@@ -287,12 +288,47 @@ int         lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int
 int         lol_gpu_set_view_batches(lol_gpu* ctx, int enable);
 int         lol_gpu_view_batches(const lol_gpu* ctx);
 
+/*
+ * A supersampled batch of views: lol_gpu_render_views with s x s samples per pixel, on every pixel or edge-adaptively.  The samples
+ * are ARGUMENTS of the call: it neither reads nor changes lol_gpu_set_samples / lol_gpu_set_adaptive_samples.
+ * View v is EXACTLY the frame lol_gpu_render_device(ctx, &cams[v], w, h, max_steps, NULL, ...) renders on a context with
+ * lol_gpu_set_samples(samples) and lol_gpu_set_adaptive_samples(contrast): the same packed pixels in the context's pixel format and
+ * the same lol_gpu_debug.rgb, bit for bit.  samples in {1, 2, 4}; contrast = -1 (every pixel gets its s x s samples) or 0 ... 255
+ * (only the pixels the adaptive definition refines; a view's mask reads that view's pixels alone: views are not neighbours).
+ * samples == 1 is lol_gpu_render_views whatever contrast says (with all its diagnostics, and whatever lol_gpu_samples() is).
+ * Addressing, `cams` (host memory, copied before the call returns), `stream`, the ring of 8 record sets, what is decided per view
+ * from its camera, the fixed tile order and "neither uses nor changes LOL_GPU_TILES_LPT / _AUTO": all as lol_gpu_render_views.
+ * With samples > 1 lol_gpu_debug.rgb is dense [v][y][x]; hit_dist, hit_id and steps are refused (LOL_GPU_ERR_UNSUPPORTED) as for
+ * any supersampled frame.
+ * A batch with contrast = -1 is one launch over the sample grids of all views.  An adaptive batch is four launches on its stream
+ * with no host wait (the plain batch, every view's mask, the numbering of the lists' groups, the refined pixels) and takes its
+ * scratch — 12 bytes per pixel of the batch — from a ring of 4 sets: a fifth adaptive batch in flight queues behind the first (on
+ * one of HIP's special stream handles the host waits for it instead).  A scratch allocation that fails returns LOL_GPU_ERR_HIP,
+ * nothing launched, and the context stays usable.
+ * Refused, with nothing launched and nothing written: samples not in {1, 2, 4} or contrast outside -1 ... 255 — LOL_GPU_ERR_ARG;
+ * everything lol_gpu_render_views refuses except lol_gpu_samples() > 1; a sample grid (s w x s h) of more than 65535 tiles along
+ * an axis, or more than 2^32 - 1 lanes in a launch over all its samples — LOL_GPU_ERR_ARG; for adaptive batches also s w > 65536
+ * or s h > 32768 — LOL_GPU_ERR_ARG — and a library whose block is not one wave — LOL_GPU_ERR_UNSUPPORTED.
+ * Which kernel: after lol_gpu_set_view_samples(ctx, 1) BEFORE lol_gpu_upload_program the scene's own module also carries
+ * lol_render_spec_batch_aa and lol_render_spec_batch_aa_list (both kernels of a 257 ... 1024-op scene do) and, for an adaptive
+ * batch's first pass, the kernels of lol_gpu_set_view_batches; otherwise, and until that module is ready, the interpreter's
+ * render_interp_batch_aa / render_interp_batch_aa_list render — same pixels either way.  A module compiled without the switch is
+ * the module it was before (same code object, same lol_gpu_kernel_key).
+ */
+int         lol_gpu_render_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
+                                         int samples, int contrast,
+                                         void* dst, size_t pitch_bytes, size_t view_stride_bytes,
+                                         const lol_gpu_debug* dbg, void* stream);
+int         lol_gpu_set_view_samples(lol_gpu* ctx, int enable);
+int         lol_gpu_view_samples(const lol_gpu* ctx);
+
 /* Name of the kernel a launch uses (for matching rocprofv3 kernel-trace rows):
  * "lol_render_spec" (scene-specialised, compiled by hipRTC at upload) or "render_interp"; with supersampling
  * (lol_gpu_set_samples) "lol_render_spec_aa" or "render_interp_aa"; for adaptive frames (lol_gpu_set_adaptive_samples) the
  * kernel of their refine pass, "lol_render_spec_aa_list" or "render_interp_aa_list".  It describes FRAMES: batches of views
  * (lol_gpu_render_views) run "lol_render_spec_batch" ("lol_render_spec_batch_steps" with lol_gpu_debug.steps) or
- * "render_interp_batch". */
+ * "render_interp_batch"; supersampled batches (lol_gpu_render_views_samples) what lol_gpu_view_samples_kernel_name (lol_gpu_diag.h)
+ * says. */
 const char* lol_gpu_kernel_name(const lol_gpu* ctx);
 /* Identity of the code that kernel is: 16 hex digits — FNV-1a of the hipRTC code object for "lol_render_spec"; for
  * "render_interp" of {this library's build id (a digest of its sources and compiler flags), the uploaded macro-op lists,

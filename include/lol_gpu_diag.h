@@ -87,6 +87,21 @@ int         lol_gpu_compile_offline_samples(const lol_program* prog, const char*
 int         lol_gpu_compile_offline_views(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                           int enable, int form, char* log, size_t logcap);
 /*
+ * ... and for a context that asked for supersampled batches (lol_gpu_set_view_samples) before its upload: enable = 0 writes exactly
+ * what lol_gpu_compile_offline writes; otherwise what lol_gpu_compile_offline_views writes with lol_render_spec_batch_aa and
+ * lol_render_spec_batch_aa_list appended, and its code object.  form as above.
+ */
+int         lol_gpu_compile_offline_view_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                                 int enable, int form, char* log, size_t logcap);
+/* The kernel the NEXT lol_gpu_render_views_samples(..., samples, contrast, ...) of this context launches, decided by the test the
+ * launch itself makes: "lol_render_spec_batch_aa" / "render_interp_batch_aa" for contrast = -1, the refine pass's
+ * "lol_render_spec_batch_aa_list" / "render_interp_batch_aa_list" for an adaptive batch, lol_gpu_render_views' for samples = 1.
+ * (A scene kernel that has finished compiling takes over at the next frame, batch or lol_gpu_specialize_wait.) */
+const char* lol_gpu_view_samples_kernel_name(const lol_gpu* ctx, int samples, int contrast);
+/* Waits for the context's last adaptive batch and gives how many pixels of all its views were refined.  LOL_GPU_ERR_ARG when no
+ * adaptive batch was launched.  For tests and rate tools. */
+int         lol_gpu_views_refined(lol_gpu* ctx, int64_t* n);
+/*
  * Adaptive frames (lol_gpu_set_adaptive_samples): waits for the context's last adaptive frame and gives how many of its pixels
  * were refined (*n), or the time its three passes took on the device, in milliseconds between events on its stream (ms[0] the
  * plain frame, ms[1] the mask and the list, ms[2] the refined pixels).  LOL_GPU_ERR_ARG when no adaptive frame was launched.

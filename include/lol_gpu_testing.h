@@ -17,6 +17,10 @@ extern "C" {
  * every check has passed: exercises the all-or-nothing upload. */
 int lol_gpu_testing_fail_uploads(lol_gpu* ctx, int n);
 
+/* The next `n` scratch allocations of adaptive batches (lol_gpu_render_views_samples with contrast >= 0) on this context fail as a
+ * hipMalloc without memory would: the batch returns LOL_GPU_ERR_HIP with nothing launched, and the context stays usable. */
+int lol_gpu_testing_fail_view_scratch(lol_gpu* ctx, int n);
+
 /* The next `n` FIRST runs of the scene compiler for a scene of the middle sizes (257 ... 1024 ops: out-of-line form first, inlined
  * form behind it) count as failed: exercises "the inlined form is compiled all the same" (lol_tiers.hip, apply). */
 int lol_gpu_testing_fail_first_tier(lol_gpu* ctx, int n);

@@ -1,9 +1,10 @@
 """python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N] [--samples N]
-                          [--adaptive T] [--orbit K -o DIR]
+                          [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]]]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
-(Renderer.render_views_into) and writes DIR/view_0000.ppm ...  There is no CPU rendering path."""
+(Renderer.render_views_into) and writes DIR/view_0000.ppm ...; --orbit-samples N supersamples the views of that batch (N x N samples
+per pixel; with --orbit-adaptive T only at the edges of each view).  There is no CPU rendering path."""
 from __future__ import annotations
 
 import argparse
@@ -29,12 +30,15 @@ def orbit(sc, args, w, h) -> int:
     r = gpu.Renderer(args.device)
     try:
         r.set_view_batches(True)             # before prepare(): the scene's own kernel then carries the batch form
+        if args.orbit_samples > 1:
+            r.set_view_samples(True)         # ... and the supersampled batch forms
         r.prepare(sc)
         views = np.zeros((k, h, w), dtype=np.uint32)
         dev = r.malloc(views.nbytes)
         try:
             t0 = time.perf_counter()
-            r.render_views_into(dev, S.orbit_cameras(sc, k), w, h, args.max_steps)
+            r.render_views_into(dev, S.orbit_cameras(sc, k), w, h, args.max_steps, samples=args.orbit_samples,
+                                adaptive=args.orbit_adaptive if args.orbit_samples > 1 else -1)
             r.sync()
             dt = (time.perf_counter() - t0) * 1e3
             r.memcpy_d2h(views.ctypes.data, dev, views.nbytes)
@@ -62,6 +66,10 @@ def main(argv=None) -> int:
                     help="with --samples N: N x N samples only at edges of the plain frame (contrast T, 0 ... 255)")
     ap.add_argument("--orbit", type=int, default=0, metavar="K",
                     help="K views from a circle round the scene in one batch; -o names the directory the PPMs go to")
+    ap.add_argument("--orbit-samples", type=int, default=1, choices=(1, 2, 4), metavar="N",
+                    help="with --orbit: N x N samples per pixel in every view of the batch")
+    ap.add_argument("--orbit-adaptive", type=int, default=-1, metavar="T",
+                    help="with --orbit-samples N: N x N samples only at edges of each view (contrast T, 0 ... 255)")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     try:
@@ -77,7 +85,13 @@ def main(argv=None) -> int:
                 or not args.out):
             print(f"--orbit takes 1 ... {gpu.MAX_VIEWS} views and -o DIR; not with --samples, --adaptive or --frames", file=sys.stderr)
             return 1
+        if args.orbit_adaptive < -1 or args.orbit_adaptive > 255:
+            print("--orbit-adaptive takes a contrast 0 ... 255", file=sys.stderr)
+            return 1
         return orbit(sc, args, w, h)
+    if args.orbit_samples != 1 or args.orbit_adaptive != -1:
+        print("--orbit-samples and --orbit-adaptive go with --orbit K", file=sys.stderr)
+        return 1
     r = gpu.Renderer(args.device)
     r.set_samples(args.samples)          # before prepare(): the scene's own kernel then carries the supersampling form
     if args.adaptive != -1:

@@ -6,7 +6,7 @@
  */
 #include "lol_gpu_internal.h"
 
-/* lol_kernel.h's, lol_kernel_aa.h's and lol_kernel_batch.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
+/* lol_kernel.h's, lol_kernel_aa.h's, lol_kernel_batch.h's and lol_kernel_batch_aa.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
 #include "lol_kernel_src.inc"
 
 #pragma GCC visibility push(hidden)
@@ -745,7 +745,8 @@ bool spec_out_of_line(const lol_program& P, int form) {
 	return P.n_ops > limit;
 }
 
-std::string generate_source(const lol_program& P, const FastPaths* fast, bool cull, int form = SPEC_BY_SIZE, bool aa = false, bool batch = false) {
+std::string generate_source(const lol_program& P, const FastPaths* fast, bool cull, int form = SPEC_BY_SIZE, bool aa = false, bool batch = false,
+                            bool batch_aa = false) {
 	std::string s;
 	const bool ool = spec_out_of_line(P, form);
 	const std::vector<RootBound> roots = analyse_roots(P);
@@ -882,6 +883,47 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 		if (two) s += head + "lol_render_spec_batch_steps" + btail + "true>(L, B, lds);\n}\n";
 		s += head + "lol_render_spec_batch" + btail + (two ? "false" : "true") + ">(L, B, lds);\n}\n";
 	}
+	/* Supersampled batches (lol_gpu_set_view_samples before the upload; the batch kernels above come with it: the first pass of an
+	 * adaptive batch is theirs): the pipeline on the sample grid of the block's view, every pixel's samples reduced before the
+	 * store (lol_kernel_batch_aa.h), and the same for the per-view lists of an adaptive batch.  Appended after everything else,
+	 * for the reason above.  No step counters. */
+	if (batch_aa) {
+		/* P = the lane's sample of launch S — the VIEW's launch, whose FLAG_SHADOW_SETTLED chooses the pipeline — with the fast SDF's
+		 * exact fallback done (`in`: indentation) */
+		auto shade = [&](const std::string& in) {
+			std::string b = in + "lol::Pixel P;\n";
+			if (any_fast) {
+				b += in + "bool plain = !(S.flags & lol::FLAG_SHADOW_SETTLED);\n";
+				b += in + "if (!plain) {\n";
+				b += in + "\tlol::SpecSdfFast fast;\n";
+				b += in + "\tP = lol::shade_pixel<lol::SpecSdfFast, " + tg + ", false>(S, fast, lds);\n";
+				b += in + "\tplain = lol::unproven(fast);\n";
+				b += in + "}\n";
+				b += in + "if (plain) {\n";
+				b += in + "\tlol::SpecSdfExact exact;\n";
+				b += in + "\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
+				b += in + "}\n";
+			} else {
+				b += in + "lol::SpecSdfExact exact;\n";
+				b += in + "P = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
+			}
+			return b;
+		};
+		const std::string stage = tables_global ? "" : "\tlol::stage_common(L, lds);\n\t__syncthreads();\n";
+		s += "#include \"lol_kernel_batch_aa.h\"\n";
+		s += head + "lol_render_spec_batch_aa(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
+		s += "\tconst lol::Launch S = lol::sample_launch(lol::view_launch(L, B.views));\n";
+		s += shade("\t");
+		s += "\tlol::store_pixel_view_aa(L, B, P.rgb);\n";
+		s += "}\n";
+		s += head + "lol_render_spec_batch_aa_list(const lol::Launch L, const lol::BatchTail B, const lol::BatchLists Q) {\n";
+		s += "\textern __shared__ lol::u32 lds[];\n" + stage;
+		s += "\tlol::render_aa_view_lists<" + tg + ">(L, B, Q, [&](const lol::Launch& S) {\n";
+		s += shade("\t\t");
+		s += "\t\treturn P;\n";
+		s += "\t});\n";
+		s += "}\n";
+	}
 	return s;
 }
 
@@ -999,8 +1041,9 @@ bool has_return_clobbering_branch(const std::vector<char>& code) { return has_re
 
 /* hipRTC: generated source + lol_kernel.h → code object for `arch`.  Needs no device. */
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
-                  std::string& log, std::string* src_out, bool cull, int form, bool aa, bool batch) {
-	std::string src = generate_source(P, fast, cull, form, aa, batch);
+                  std::string& log, std::string* src_out, bool cull, int form, bool aa, bool batch, bool batch_aa) {
+	if (batch_aa) batch = true;                 /* (a module with the supersampled batch kernels carries the plain ones) */
+	std::string src = generate_source(P, fast, cull, form, aa, batch, batch_aa);
 	if (src_out) *src_out = src;
 	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
 		if (FILE* f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
@@ -1063,7 +1106,8 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	/* on disk the pipeline source (lol_kernel.h, embedded in this library) is part of the key: another build of the
 	 * library must not pick up this one's kernels */
 	const std::string disk_key = key + "|" + LOL_KERNEL_H_TEXT + (aa ? std::string("|") + LOL_KERNEL_AA_H_TEXT : std::string()) +
-	                             (batch ? std::string("|batch|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT : std::string());
+	                             (batch ? std::string("|batch|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT : std::string()) +
+	                             (batch_aa ? std::string("|batch_aa|") + LOL_KERNEL_BATCH_AA_H_TEXT : std::string());
 	if (disk_cache_load(disk_key, code)) {
 		std::lock_guard<std::mutex> lock(g_cache_mutex);
 		g_code_cache[key] = code;
@@ -1072,9 +1116,10 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	}
 	/* lol_kernel_aa.h only where the source includes it: hipRTC's compilation-unit id — bytes of the code object — follows the headers */
 	/* ... and lol_kernel_batch.h (which includes lol_kernel_aa.h for pack_pixel) only where the module carries the batch kernel */
-	const char* hdr_src[] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT };
-	const char* hdr_name[] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h" };
-	const int n_hdr = batch ? 3 : aa ? 2 : 1;
+	/* ... and lol_kernel_batch_aa.h (which includes lol_kernel_batch.h) only where it carries the supersampled batch kernels */
+	const char* hdr_src[] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT };
+	const char* hdr_name[] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h" };
+	const int n_hdr = batch_aa ? 4 : batch ? 3 : aa ? 2 : 1;
 	hiprtcProgram prog = nullptr;
 	if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_hdr, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
 		log = "hiprtcCreateProgram failed";
@@ -1191,7 +1236,7 @@ int lol_gpu_compile_offline(const lol_program* prog, const char* arch, const cha
 /* ... the module a context with lol_gpu_set_samples(ctx, samples) compiles at its upload: with samples > 1 it also carries
  * lol_render_spec_aa (lol_gpu_diag.h) */
 static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples, bool batch,
-                           int form, char* log, size_t logcap);
+                           int form, char* log, size_t logcap, bool batch_aa = false);
 
 int lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples,
                                     char* log, size_t logcap) {
@@ -1206,8 +1251,15 @@ int lol_gpu_compile_offline_views(const lol_program* prog, const char* arch, con
 	return compile_offline(prog, arch, out_base, assume_fast, 1, enable != 0, form, log, logcap);
 }
 
+/* ... and the module a context with lol_gpu_set_view_samples(ctx, 1) compiles at its upload (lol_gpu_diag.h) */
+int lol_gpu_compile_offline_view_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                         int form, char* log, size_t logcap) {
+	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
+	return compile_offline(prog, arch, out_base, assume_fast, 1, false, form, log, logcap, enable != 0);
+}
+
 static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples, bool batch,
-                           int form, char* log, size_t logcap) {
+                           int form, char* log, size_t logcap, bool batch_aa) {
 	if (!prog || !arch || (samples != 1 && samples != 2 && samples != 4)) return LOL_GPU_ERR_ARG;
 	std::vector<char> code;
 	std::string lg, src;
@@ -1224,7 +1276,7 @@ static int compile_offline(const lol_program* prog, const char* arch, const char
 		/* on the large-stack thread, like every run of the scene compiler (BigStackThread) */
 		BigStackThread th;
 		auto work = [&]() {
-			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), form, samples > 1, batch); }
+			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), form, samples > 1, batch, batch_aa); }
 			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
 		};
 		bool started = false;

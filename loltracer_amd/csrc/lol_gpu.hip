@@ -114,6 +114,20 @@ hipError_t launch_interp_batch(const lol::Launch& L, const lol::BatchTail& B, di
 	return hipGetLastError();
 }
 
+/* ... and a supersampled batch (lol_kernel_batch_aa.h): every pixel, or — `Q` — the lists of an adaptive batch */
+template <int SSIZE, bool TABLES_GLOBAL = false>
+hipError_t launch_interp_batch_aa(const lol::Launch& L, const lol::BatchTail& B, const lol::BatchLists* Q, dim3 grid, size_t lds, hipStream_t s,
+                                  int sqrt_kind) {
+	if (Q) {
+		if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_batch_aa_list<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B, *Q);
+		else                hipLaunchKernelGGL((lol::render_interp_batch_aa_list<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B, *Q);
+		return hipGetLastError();
+	}
+	if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_batch_aa<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B);
+	else                hipLaunchKernelGGL((lol::render_interp_batch_aa<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B);
+	return hipGetLastError();
+}
+
 /* Conditions under which an escaped ray's colour is exactly clamp(ambient * materials[0].ambient), so
  * that waves of escaped rays may skip normal + lights (lol_kernel.h, FLAG_MISS_SKIP): material #0 has
  * diffuse == specular == 0 (either sign), shininess >= 0 and not NaN (powf(c in [0,1], s >= 0) is finite),
@@ -331,6 +345,13 @@ hipError_t interp_batch(const lol_gpu* ctx, const lol::Launch& L, const lol::Bat
 	return interp_dispatch(ctx, [&](auto v) { return launch_interp_batch<decltype(v)::ssize, decltype(v)::tables_global>(L, B, grid, common, s, kind); });
 }
 
+/* ... and a supersampled one (`Q`: the refine pass of an adaptive batch) */
+hipError_t interp_batch_aa(const lol_gpu* ctx, const lol::Launch& L, const lol::BatchTail& B, const lol::BatchLists* Q, dim3 grid, size_t common,
+                           hipStream_t s) {
+	const int kind = ctx->interp_sqrt_kind;
+	return interp_dispatch(ctx, [&](auto v) { return launch_interp_batch_aa<decltype(v)::ssize, decltype(v)::tables_global>(L, B, Q, grid, common, s, kind); });
+}
+
 /*
  * Adaptive frames (lol_gpu_set_adaptive_samples), pass 2: classify and compact.  One lane per pixel, a 16 x 4 tile per wave, tiles
  * row by row.  A pixel is refined when one of its (up to 8) neighbours inside the frame has another object id, or differs from it
@@ -340,9 +361,9 @@ hipError_t interp_batch(const lol_gpu* ctx, const lol::Launch& L, const lol::Bat
  * which part of the list depends on the order of the atomics; no pixel's value does.
  */
 constexpr int CLASSIFY_W = 16, CLASSIFY_H = 4;
-__global__ __launch_bounds__(64) void adaptive_classify(const uint32_t* xrgb, const uint32_t* ids, int w, int h, int contrast,
-                                                        uint32_t* dst, uint32_t pitch_px, uint32_t fmt_shift, uint32_t fmt_loss,
-                                                        uint32_t fmt_amask, uint32_t* list, uint32_t* count) {
+__device__ __forceinline__ void classify_tile(const uint32_t* xrgb, const uint32_t* ids, int w, int h, int contrast,
+                                              uint32_t* dst, uint32_t pitch_px, uint32_t fmt_shift, uint32_t fmt_loss,
+                                              uint32_t fmt_amask, uint32_t* list, uint32_t* count) {
 	const int lane = threadIdx.x;
 	const int x = blockIdx.x * CLASSIFY_W + lane % CLASSIFY_W, y = blockIdx.y * CLASSIFY_H + lane / CLASSIFY_W;
 	const bool in = x < w && y < h;
@@ -376,6 +397,43 @@ __global__ __launch_bounds__(64) void adaptive_classify(const uint32_t* xrgb, co
 	if (lane == 0) base = atomicAdd(count, (uint32_t)__popcll(m));
 	base = __shfl(base, 0, 64);
 	if (refined) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)x | (uint32_t)y << 16;
+}
+__global__ __launch_bounds__(64) void adaptive_classify(const uint32_t* xrgb, const uint32_t* ids, int w, int h, int contrast,
+                                                        uint32_t* dst, uint32_t pitch_px, uint32_t fmt_shift, uint32_t fmt_loss,
+                                                        uint32_t fmt_amask, uint32_t* list, uint32_t* count) {
+	classify_tile(xrgb, ids, w, h, contrast, dst, pitch_px, fmt_shift, fmt_loss, fmt_amask, list, count);
+}
+
+/*
+ * Adaptive batches (lol_gpu_render_views_samples), pass 2: the same for every view of a batch, the view in the grid's z.  The plain
+ * batch is dense (view v's pixels and ids at v w h); a view's mask reads that view's pixels alone — classify_tile's frame is the
+ * view, so neighbours outside it are ignored —, its unrefined pixels go to the view's address in `dst`, and its refined ones to
+ * a list segment of its own (w h entries at v w h) with a count of its own.
+ */
+__global__ __launch_bounds__(64) void adaptive_classify_views(const uint32_t* xrgb, const uint32_t* ids, int w, int h, int contrast,
+                                                              uint32_t* dst, uint32_t pitch_px, unsigned long long view_stride_px,
+                                                              uint32_t fmt_shift, uint32_t fmt_loss, uint32_t fmt_amask,
+                                                              uint32_t* lists, uint32_t* counts) {
+	const unsigned long long v = blockIdx.z, o = v * (unsigned long long)w * (unsigned long long)h;
+	classify_tile(xrgb + o, ids + o, w, h, contrast, dst + v * view_stride_px, pitch_px, fmt_shift, fmt_loss, fmt_amask, lists + o, counts + v);
+}
+
+/* ... and between pass 2 and 3: the lists' lengths into the numbering of their groups of `per_wave` entries (lol_kernel_batch_aa.h,
+ * render_aa_view_lists): prefix[v] = the groups of the views before v, prefix[n_views] = all of them.  One wave: lane l sums
+ * the views [l c, (l + 1) c), c = ceil(n_views / 64), and a scan over the lanes gives each its start. */
+__global__ __launch_bounds__(64) void view_group_prefix(const uint32_t* counts, uint32_t n_views, uint32_t per_wave, uint32_t* prefix) {
+	const uint32_t lane = threadIdx.x, chunk = (n_views + 63u) / 64u;
+	const uint32_t v0 = min(lane * chunk, n_views), v1 = min(v0 + chunk, n_views);
+	uint32_t sum = 0;
+	for (uint32_t v = v0; v < v1; v++) sum += (counts[v] + per_wave - 1u) / per_wave;
+	uint32_t upto = sum;                                   /* inclusive scan over the lanes */
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t below = __shfl_up(upto, d, 64);
+		if (lane >= (uint32_t)d) upto += below;
+	}
+	uint32_t run = upto - sum;
+	for (uint32_t v = v0; v < v1; v++) { prefix[v] = run; run += (counts[v] + per_wave - 1u) / per_wave; }
+	if (lane == 63u) prefix[n_views] = upto;
 }
 
 }  // namespace
@@ -432,6 +490,10 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 	for (lol_gpu::AdaptiveSet& S : ctx->adaptive_sets) {
 		if (S.d_buf) (void)hipFree(S.d_buf);
 		for (hipEvent_t ev : S.ev) if (ev) (void)hipEventDestroy(ev);
+	}
+	for (lol_gpu::ViewAdaptiveSet& S : ctx->view_adaptive_sets) {
+		if (S.d_buf) (void)hipFree(S.d_buf);
+		if (S.done) (void)hipEventDestroy(S.done);
 	}
 	for (lol_gpu::ViewSet& S : ctx->view_sets) {
 		if (S.d_views) (void)hipFree(S.d_views);
@@ -620,9 +682,7 @@ int lol_gpu_part_rows(int h, const lol_gpu_rows* rows) {
  * flight); the host waits for that frame only where the set has to grow, or where this frame goes to one of HIP's special stream
  * handles and that frame has not finished.
  */
-static int render_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_gpu_debug* dbg, hipStream_t s, size_t common) {
-	const int w = A.w, h = A.h, ss = ctx->samples;
-	const size_t px = (size_t)w * h;
+static int ensure_refine_grid(lol_gpu* ctx) {
 	if (!ctx->adaptive_blocks) {
 		/* the refine grid: enough one-wave blocks to fill the device (8 waves per SIMD, 4 SIMDs per CU), each with a slot of its own
 		 * in the lane table; the order table maps block b to slot b */
@@ -635,6 +695,16 @@ static int render_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_gpu_deb
 		if (!ctx->d_adaptive_order) LOL_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_adaptive_order), order.size() * 4));
 		LOL_HIP(ctx, hipMemcpy(ctx->d_adaptive_order, order.data(), order.size() * 4, hipMemcpyHostToDevice));
 		ctx->adaptive_blocks = blocks; ctx->adaptive_stride = stride;
+	}
+	return LOL_GPU_OK;
+}
+
+static int render_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_gpu_debug* dbg, hipStream_t s, size_t common) {
+	const int w = A.w, h = A.h, ss = ctx->samples;
+	const size_t px = (size_t)w * h;
+	{
+		const int st = ensure_refine_grid(ctx);
+		if (st != LOL_GPU_OK) return st;
 	}
 	const uint32_t per_wave = 64u / (uint32_t)(ss * ss);
 	const uint32_t blocks = (uint32_t)std::min<size_t>(ctx->adaptive_blocks, (px + per_wave - 1) / per_wave);
@@ -841,24 +911,33 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
  * goes into the view's record: which copy of the macro-op list, FLAG_SHADOW_SETTLED (camera_sane), FLAG_FIRST_STEP and its value
  * (first_step).  Fixed tile order; the longest-first tables, AUTO's trials and what they remember of the last frame are neither
  * read nor written.  Records: the next set of the ring (lol_gpu_internal.h, ViewSet).
+ *
+ * The pieces, shared by lol_gpu_render_views and lol_gpu_render_views_samples: what both refuse (batch_refused), the launch of a
+ * whole frame of the batch's size with one sample per pixel (batch_launch), the view records queued on the batch's stream
+ * (queue_view_records) and the event behind the batch's last launch (view_records_done).
  */
-int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
-                         void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
+static int batch_refused(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps, const void* dst, size_t pitch_bytes,
+                         size_t view_stride_bytes) {
 	if (!ctx || !cams || !dst) return LOL_GPU_ERR_ARG;
 	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
 	if (n_views < 1 || n_views > LOL_GPU_MAX_VIEWS) return fail(ctx, LOL_GPU_ERR_ARG, "a batch holds 1 ... LOL_GPU_MAX_VIEWS views");
 	if (w <= 0 || h <= 0 || max_steps < 0 || pitch_bytes % 4 || pitch_bytes < (size_t)w * 4 ||
 	    view_stride_bytes % 4 || view_stride_bytes / pitch_bytes < (size_t)h)
 		return fail(ctx, LOL_GPU_ERR_ARG, "bad batch geometry");
-	if (ctx->samples > 1)
-		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "batches of views are one sample per pixel (lol_gpu_set_samples)");
-	const int tile_w = lol::TILE_W, tile_h = lol::TILE_H, block = tile_w * tile_h;
-	dim3 grid((w + tile_w - 1) / tile_w, (h + tile_h - 1) / tile_h, (unsigned)n_views);
-	/* (a grid has at most 65535 blocks in y and z, and HIP takes at most 2^32 - 1 threads per launch) */
-	if (grid.x > 65535u || grid.y > 65535u || (unsigned long long)grid.x * grid.y * grid.z * (unsigned)block > 0xFFFFFFFFull)
-		return fail(ctx, LOL_GPU_ERR_ARG, "batch too large for one launch: fewer views per call");
+	return LOL_GPU_OK;
+}
 
-	lol::Launch L;
+/* the grid of a batch over a grid of gw x gh pixels or samples per view (transposed under LOL_GPU_TILES_COLS: batch_launch sets the
+ * flag), or false: a grid has at most 65535 blocks in y and z, and HIP takes at most 2^32 - 1 threads per launch */
+static bool batch_grid(const lol_gpu* ctx, long long gw, long long gh, int n_views, dim3* grid) {
+	const long long tx = (gw + lol::TILE_W - 1) / lol::TILE_W, ty = (gh + lol::TILE_H - 1) / lol::TILE_H;
+	if (tx > 65535 || ty > 65535 || (unsigned long long)tx * (unsigned long long)ty * (unsigned)n_views * (unsigned)lol::BLOCK > 0xFFFFFFFFull) return false;
+	const bool cols = ctx->tiles.mode == LOL_GPU_TILES_COLS;
+	*grid = dim3((unsigned)(cols ? ty : tx), (unsigned)(cols ? tx : ty), (unsigned)n_views);
+	return true;
+}
+
+static void batch_launch(const lol_gpu* ctx, int w, int h, int max_steps, void* dst, size_t pitch_bytes, const lol_gpu_debug* dbg, lol::Launch& L) {
 	memset(&L, 0, sizeof L);
 	L.fw = (float)w; L.fh = (float)h;
 	L.w = w; L.h = h; L.max_steps = max_steps;
@@ -872,6 +951,7 @@ int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views
 	L.ambient[0] = P.ambient_color.x; L.ambient[1] = P.ambient_color.y; L.ambient[2] = P.ambient_color.z;
 	L.flags = (ctx->miss_skip ? lol::FLAG_MISS_SKIP : 0u) | (ctx->dark_skip ? lol::FLAG_DARK_SKIP : 0u);
 	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+	if (ctx->tiles.mode == LOL_GPU_TILES_COLS) L.flags |= lol::FLAG_TILE_COLS;
 	L.dst = static_cast<uint32_t*>(dst);
 	L.pitch_px = (uint32_t)(pitch_bytes / 4);
 	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
@@ -879,17 +959,33 @@ int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views
 		L.dbg_rgb = dbg->rgb; L.dbg_hit_dist = dbg->hit_dist;
 		L.dbg_hit_id = dbg->hit_id; L.dbg_steps = dbg->steps;
 	}
-	if (ctx->tiles.mode == LOL_GPU_TILES_COLS) {
-		L.flags |= lol::FLAG_TILE_COLS;
-		const unsigned t = grid.x; grid.x = grid.y; grid.y = t;
-	}
+}
 
-	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->frame_streams[ctx->frame_rr++ % (unsigned)ctx->n_frame_streams];
+/* LOL_GPU_STREAM_DEFAULT == hipStreamLegacy; NULL = the context's own stream(s), in turn.  Makes the context's device current and
+ * takes a finished scene kernel over: the frame boundary. */
+static int batch_stream(lol_gpu* ctx, void* stream, hipStream_t* s) {
+	*s = stream ? static_cast<hipStream_t>(stream) : ctx->frame_streams[ctx->frame_rr++ % (unsigned)ctx->n_frame_streams];
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	finish_specialise(ctx, false);           /* the frame boundary at which a finished scene kernel takes over */
-	const size_t common = (size_t)(lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) - lol::TILE_W * lol::TILE_H + block) * 4;
+	finish_specialise(ctx, false);
+	return LOL_GPU_OK;
+}
 
-	/* the view records */
+static size_t batch_common_lds(const lol_gpu* ctx) {
+	const lol_program& P = ctx->h_prog;
+	return (size_t)lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) * 4;
+}
+
+/* not by hipStreamWaitEvent on HIP's special handles (the legacy default stream, the per-thread one), which this HIP dereferences
+ * (render_adaptive): there the host waits */
+static int wait_on_stream(lol_gpu* ctx, hipStream_t s, hipEvent_t ev) {
+	const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
+	if (!special) LOL_HIP(ctx, hipStreamWaitEvent(s, ev, 0));
+	else LOL_HIP(ctx, hipEventSynchronize(ev));
+	return LOL_GPU_OK;
+}
+
+/* the view records of a batch: the next set of the ring filled, and its copy to the device queued on `s` */
+static int queue_view_records(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int max_steps, hipStream_t s, lol_gpu::ViewSet** out) {
 	lol_gpu::ViewSet& S = ctx->view_sets[ctx->view_rr++ % lol_gpu::VIEW_SETS];
 	if (!S.copied) LOL_HIP(ctx, hipEventCreateWithFlags(&S.copied, hipEventDisableTiming));
 	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
@@ -906,12 +1002,10 @@ int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views
 	if (S.used) {
 		/* The pinned copy is the host's to write once the set's last COPY has run (VIEW_SETS batches ago: in practice long done; a host
 		 * that queues faster than the device renders is held VIEW_SETS batches ahead of it here).  The device copy is this batch's once
-		 * the set's last LAUNCH has finished, whatever stream it ran on — not by hipStreamWaitEvent on HIP's special handles, which
-		 * this HIP dereferences (render_adaptive): there the host waits. */
+		 * the set's last LAUNCH has finished, whatever stream it ran on. */
 		LOL_HIP(ctx, hipEventSynchronize(S.copied));
-		const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
-		if (!special) LOL_HIP(ctx, hipStreamWaitEvent(s, S.done, 0));
-		else LOL_HIP(ctx, hipEventSynchronize(S.done));
+		const int st = wait_on_stream(ctx, s, S.done);
+		if (st != LOL_GPU_OK) return st;
 	}
 	const bool settle = ctx->shadow_settle, finite = ctx->finite_scene;
 	for (int v = 0; v < n_views; v++) {
@@ -925,30 +1019,294 @@ int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views
 	}
 	LOL_HIP(ctx, hipMemcpyAsync(S.d_views, S.h_views, (size_t)n_views * sizeof(lol::View), hipMemcpyHostToDevice, s));
 	LOL_HIP(ctx, hipEventRecord(S.copied, s));
+	*out = &S;
+	return LOL_GPU_OK;
+}
 
-	lol::BatchTail B = { S.d_views, (unsigned long long)(view_stride_bytes / 4) };
+/* behind the batch's last launch (`e`: what it returned).  Recorded even behind a failed launch: the copy is queued, and the set's
+ * next user must find both events recorded. */
+static int view_records_done(lol_gpu* ctx, lol_gpu::ViewSet& S, hipStream_t s, hipError_t e, const char* what) {
+	const hipError_t e2 = hipEventRecord(S.done, s);
+	S.used = true;
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, what, e);
+	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (batch of views)", e2);
+	return LOL_GPU_OK;
+}
+
+static void batch_range(const char* what, int n_views, int w, int h) {
 	g_roctx.init();
 	if (g_roctx.push) {
 		char label[96];
-		snprintf(label, sizeof label, "lol batch %d x %dx%d", n_views, w, h);
+		snprintf(label, sizeof label, "lol %s %d x %dx%d", what, n_views, w, h);
 		g_roctx.push(label);
 		g_roctx.ranges++;
 	}
-	hipError_t e;
+}
+
+/* one launch of the plain batch kernel for `L` / `B`: the scene's own where its module carries one, else the interpreter's */
+static hipError_t launch_plain_batch(const lol_gpu* ctx, const lol::Launch& L, const lol::BatchTail& B, dim3 grid, bool counts, hipStream_t s) {
+	const size_t common = batch_common_lds(ctx);
 	const SceneKernel* k = scene_kernel(ctx);
 	if (k && k->render_batch) {
-		void* args[] = { &L, &B };
-		e = hipModuleLaunchKernel(dbg && dbg->steps ? k->render_batch_counting : k->render_batch, grid.x, grid.y, grid.z, block, 1, 1,
-		                          (unsigned)common, s, args, nullptr);
-	} else {
-		e = interp_batch(ctx, L, B, grid, common, s);
+		lol::Launch La = L; lol::BatchTail Ba = B;
+		void* args[] = { &La, &Ba };
+		return hipModuleLaunchKernel(counts ? k->render_batch_counting : k->render_batch, grid.x, grid.y, grid.z, lol::BLOCK, 1, 1,
+		                             (unsigned)common, s, args, nullptr);
 	}
+	return interp_batch(ctx, L, B, grid, common, s);
+}
+
+/* lol_gpu_render_views without its look at lol_gpu_set_samples */
+static int render_views_plain(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
+                              void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
+	dim3 grid;
+	if (!batch_grid(ctx, w, h, n_views, &grid))
+		return fail(ctx, LOL_GPU_ERR_ARG, "batch too large for one launch: fewer views per call");
+	lol::Launch L;
+	batch_launch(ctx, w, h, max_steps, dst, pitch_bytes, dbg, L);
+	hipStream_t s;
+	{
+		const int st = batch_stream(ctx, stream, &s);
+		if (st != LOL_GPU_OK) return st;
+	}
+	lol_gpu::ViewSet* S = nullptr;
+	{
+		const int st = queue_view_records(ctx, cams, n_views, max_steps, s, &S);
+		if (st != LOL_GPU_OK) return st;
+	}
+	const lol::BatchTail B = { S->d_views, (unsigned long long)(view_stride_bytes / 4) };
+	batch_range("batch", n_views, w, h);
+	const hipError_t e = launch_plain_batch(ctx, L, B, grid, dbg && dbg->steps, s);
 	if (g_roctx.pop) g_roctx.pop();
-	/* (recorded even behind a failed launch: the copy above is queued, and the set's next user must find both events recorded) */
+	return view_records_done(ctx, *S, s, e, "kernel launch (batch of views)");
+}
+
+int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
+                         void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
+	{
+		const int st = batch_refused(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes);
+		if (st != LOL_GPU_OK) return st;
+	}
+	if (ctx->samples > 1)
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "batches of views are one sample per pixel (lol_gpu_set_samples): lol_gpu_render_views_samples");
+	return render_views_plain(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+}
+
+/* the scene kernel a supersampled batch runs, or nullptr: the interpreter (a module compiled without lol_gpu_set_view_samples, or
+ * none yet) */
+static const SceneKernel* batch_aa_kernel(const lol_gpu* ctx) {
+	const SceneKernel* k = scene_kernel(ctx);
+	return k && k->render_batch_aa ? k : nullptr;
+}
+
+/*
+ * An adaptive batch: what render_adaptive does for a frame, for every view of a batch — four launches on `s` behind the copy of
+ * the view records, no host wait between them.  `A` = the launch of the whole supersampled batch.
+ *  1. the plain batch P into the scratch set, dense: XRGB8888 pixels and object ids (the diagnostic colour straight into the
+ *     caller's buffer), by the batch kernel as lol_gpu_render_views runs it;
+ *  2. adaptive_classify_views: every view's mask from its own pixels; unrefined pixels go to `dst`, refined ones to the view's list;
+ *  3. view_group_prefix: the lists' lengths into the numbering of their groups;
+ *  4. the refine pass (lol_kernel_batch_aa.h, render_aa_view_lists) on a grid that fills the device.
+ * Scratch: the next set of a ring of its own (lol_gpu_internal.h, ViewAdaptiveSet), behind the batch that used it last; the host
+ * waits for that batch only where the set has to grow, or on one of HIP's special stream handles.
+ */
+static int render_views_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_frame_camera* cams, int n_views, int samples, int contrast,
+                                 size_t view_stride_bytes, const lol_gpu_debug* dbg, hipStream_t s) {
+	const int w = A.w, h = A.h;
+	const size_t px = (size_t)w * h, all = px * (size_t)n_views;
+	{
+		const int st = ensure_refine_grid(ctx);
+		if (st != LOL_GPU_OK) return st;
+	}
+	const uint32_t per_wave = 64u / (uint32_t)(samples * samples);
+	/* (every view's list ends with a group that may be partly filled: at most n_views groups more than the entries need) */
+	const uint32_t blocks = (uint32_t)std::min<size_t>(ctx->adaptive_blocks, (px + per_wave - 1) / per_wave * (size_t)n_views);
+	const int si = (int)(ctx->view_adaptive_rr++ % lol_gpu::VIEW_ADAPTIVE_SETS);
+	lol_gpu::ViewAdaptiveSet& S = ctx->view_adaptive_sets[si];
+	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+	const size_t tables = 2 * ((size_t)n_views + 1);
+	const size_t need = (3 * all + tables + (size_t)ctx->adaptive_blocks * 64) * 4;
+	if (need > S.bytes) {
+		if (S.used) LOL_HIP(ctx, hipEventSynchronize(S.done));
+		if (S.d_buf) (void)hipFree(S.d_buf);
+		S.d_buf = nullptr; S.bytes = 0; S.d_counts = nullptr; S.n_views = 0; S.used = false;
+		if (ctx->view_adaptive_last == si) ctx->view_adaptive_last = -1;
+		const bool injected = ctx->fail_view_scratch > 0;      /* lol_gpu_testing_fail_view_scratch */
+		if (injected) ctx->fail_view_scratch--;
+		const hipError_t me = injected ? hipErrorOutOfMemory : hipMalloc(reinterpret_cast<void**>(&S.d_buf), need);
+		if (me != hipSuccess) {
+			S.d_buf = nullptr;
+			(void)hipGetLastError();             /* (the thread's last error: the host's next HIP call must not trip over it) */
+			return fail(ctx, LOL_GPU_ERR_HIP, "scratch of an adaptive batch", me);
+		}
+		S.bytes = need;
+	}
+	uint32_t* xrgb = S.d_buf;
+	uint32_t* ids = xrgb + all;
+	uint32_t* lists = ids + all;
+	uint32_t* counts = lists + all;
+	uint32_t* prefix = counts + n_views + 1;
+	uint32_t* lanes = prefix + n_views + 1;
+	if (S.used) {
+		const int st = wait_on_stream(ctx, s, S.done);
+		if (st != LOL_GPU_OK) return st;
+	}
+	lol_gpu::ViewSet* V = nullptr;
+	{
+		const int st = queue_view_records(ctx, cams, n_views, A.max_steps, s, &V);
+		if (st != LOL_GPU_OK) return st;
+	}
+	const char* what = "hipMemsetAsync (adaptive batch)";
+	hipError_t e = hipMemsetAsync(counts, 0, ((size_t)n_views + 1) * 4, s);
+
+	/* 1. the plain batch */
+	if (e == hipSuccess) {
+		lol::Launch L = A;
+		L.fw = (float)w; L.fh = (float)h;
+		L.flags &= ~(lol::FLAG_SAMPLES_2 | lol::FLAG_SAMPLES_4);
+		L.dst = xrgb; L.pitch_px = (uint32_t)w;
+		L.fmt_shift = 16u | 8u << 8; L.fmt_loss = 0; L.fmt_amask = 0;
+		L.dbg_rgb = dbg ? dbg->rgb : nullptr; L.dbg_hit_dist = nullptr; L.dbg_hit_id = ids; L.dbg_steps = nullptr;
+		const lol::BatchTail B = { V->d_views, (unsigned long long)px };
+		dim3 grid;
+		(void)batch_grid(ctx, w, h, n_views, &grid);      /* (a part of the sample grid the caller has checked) */
+		what = "kernel launch (adaptive batch, plain pass)";
+		e = launch_plain_batch(ctx, L, B, grid, false, s);
+	}
+	/* 2. classify and compact, view by view */
+	if (e == hipSuccess) {
+		what = "kernel launch (adaptive batch, classify pass)";
+		hipLaunchKernelGGL(adaptive_classify_views, dim3((w + CLASSIFY_W - 1) / CLASSIFY_W, (h + CLASSIFY_H - 1) / CLASSIFY_H, n_views), dim3(64), 0, s,
+		                   xrgb, ids, w, h, contrast, A.dst, A.pitch_px, (unsigned long long)(view_stride_bytes / 4), A.fmt_shift, A.fmt_loss,
+		                   A.fmt_amask, lists, counts);
+		e = hipGetLastError();
+	}
+	/* 3. the groups' numbering */
+	if (e == hipSuccess) {
+		what = "kernel launch (adaptive batch, group prefix)";
+		hipLaunchKernelGGL(view_group_prefix, dim3(1), dim3(64), 0, s, counts, (uint32_t)n_views, per_wave, prefix);
+		e = hipGetLastError();
+	}
+	/* 4. the s x s pixels of the lists */
+	if (e == hipSuccess) {
+		lol::Launch R = A;
+		R.flags &= ~lol::FLAG_TILE_COLS;                  /* (a one-dimensional grid) */
+		R.tile_order = ctx->d_adaptive_order; R.tile_stride = ctx->adaptive_stride; R.lane_pixels = lanes;
+		lol::BatchTail B = { V->d_views, (unsigned long long)(view_stride_bytes / 4) };
+		lol::BatchLists Q = { lists, counts, prefix, (uint32_t)n_views };
+		const size_t common = batch_common_lds(ctx);
+		what = "kernel launch (adaptive batch, refine pass)";
+		if (const SceneKernel* k = batch_aa_kernel(ctx)) {
+			void* args[] = { &R, &B, &Q };
+			e = hipModuleLaunchKernel(k->render_batch_aa_list, blocks, 1, 1, lol::BLOCK, 1, 1, (unsigned)common, s, args, nullptr);
+		} else {
+			e = interp_batch_aa(ctx, R, B, &Q, dim3(blocks), common, s);
+		}
+	}
+	/* (recorded even behind a failed launch, like the view records' event and for the same reason) */
 	const hipError_t e2 = hipEventRecord(S.done, s);
 	S.used = true;
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (batch of views)", e);
-	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (batch of views)", e2);
+	S.d_counts = counts; S.n_views = n_views;
+	ctx->view_adaptive_last = si;
+	const int st = view_records_done(ctx, *V, s, e, what);
+	if (st != LOL_GPU_OK) return st;
+	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (adaptive batch)", e2);
+	return LOL_GPU_OK;
+}
+
+/*
+ * A supersampled batch of views: lol_gpu_render_views with s x s samples per pixel — on every pixel (contrast -1: ONE launch over
+ * the sample grids of all views, lol_kernel_batch_aa.h) or on the pixels the adaptive definition refines (render_views_adaptive).
+ * The samples are arguments: lol_gpu_set_samples / lol_gpu_set_adaptive_samples are neither read nor changed.
+ */
+int lol_gpu_render_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
+                                 int samples, int contrast, void* dst, size_t pitch_bytes, size_t view_stride_bytes,
+                                 const lol_gpu_debug* dbg, void* stream) {
+	if (!ctx || !cams || !dst) return LOL_GPU_ERR_ARG;
+	if (samples != 1 && samples != 2 && samples != 4) return fail(ctx, LOL_GPU_ERR_ARG, "samples per axis must be 1, 2 or 4");
+	if (contrast < -1 || contrast > 255) return fail(ctx, LOL_GPU_ERR_ARG, "adaptive contrast must be -1 (off) or 0 ... 255");
+	{
+		const int st = batch_refused(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes);
+		if (st != LOL_GPU_OK) return st;
+	}
+	if (samples == 1) return render_views_plain(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+	const bool adaptive = contrast >= 0;
+	if (!lol::samples_fit_wave(samples))
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "this build's wave patch (LOL_WAVE_W x LOL_WAVE_H) does not divide into that many samples per axis");
+	if (adaptive && lol::BLOCK != 64)
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "adaptive batches need one-wave blocks (this build's LOL_WAVES_X is not 1)");
+	if (dbg && (dbg->hit_dist || dbg->hit_id || dbg->steps))
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "hit_dist, hit_id and steps have no single value for a supersampled pixel");
+	/* the launch is counted in SAMPLES: the grid of the kernel that shades every pixel's (an adaptive batch shades a part of it) */
+	dim3 grid;
+	if (!batch_grid(ctx, (long long)samples * w, (long long)samples * h, n_views, &grid))
+		return fail(ctx, LOL_GPU_ERR_ARG, "batch too large for one launch in samples: fewer views per call");
+	/* ... and the refine pass finds its samples through shade_pixel's pixel table (lol_kernel_aa.h, render_aa_list) */
+	if (adaptive && ((long long)samples * w > 65536 || (long long)samples * h > 32768))
+		return fail(ctx, LOL_GPU_ERR_ARG, "views too large for adaptive supersampling (s w <= 65536, s h <= 32768)");
+
+	lol::Launch L;
+	batch_launch(ctx, w, h, max_steps, dst, pitch_bytes, dbg, L);
+	L.fw = (float)(samples * w); L.fh = (float)(samples * h);      /* the size of the sample grid */
+	L.flags |= samples == 4 ? lol::FLAG_SAMPLES_4 : lol::FLAG_SAMPLES_2;
+	hipStream_t s;
+	{
+		const int st = batch_stream(ctx, stream, &s);
+		if (st != LOL_GPU_OK) return st;
+	}
+	if (adaptive) return render_views_adaptive(ctx, L, cams, n_views, samples, contrast, view_stride_bytes, dbg, s);
+	lol_gpu::ViewSet* S = nullptr;
+	{
+		const int st = queue_view_records(ctx, cams, n_views, max_steps, s, &S);
+		if (st != LOL_GPU_OK) return st;
+	}
+	lol::BatchTail B = { S->d_views, (unsigned long long)(view_stride_bytes / 4) };
+	const size_t common = batch_common_lds(ctx);
+	batch_range("supersampled batch", n_views, w, h);
+	hipError_t e;
+	if (const SceneKernel* k = batch_aa_kernel(ctx)) {
+		void* args[] = { &L, &B };
+		e = hipModuleLaunchKernel(k->render_batch_aa, grid.x, grid.y, grid.z, lol::BLOCK, 1, 1, (unsigned)common, s, args, nullptr);
+	} else {
+		e = interp_batch_aa(ctx, L, B, nullptr, grid, common, s);
+	}
+	if (g_roctx.pop) g_roctx.pop();
+	return view_records_done(ctx, *S, s, e, "kernel launch (supersampled batch of views)");
+}
+
+int lol_gpu_set_view_samples(lol_gpu* ctx, int enable) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	ctx->view_samples = enable ? 1 : 0;      /* takes effect at the next lol_gpu_upload_program */
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_view_samples(const lol_gpu* ctx) { return ctx ? ctx->view_samples : LOL_GPU_ERR_ARG; }
+
+const char* lol_gpu_view_samples_kernel_name(const lol_gpu* ctx, int samples, int contrast) {
+	if (!ctx) return "";
+	if (samples <= 1) return scene_kernel(ctx) && scene_kernel(ctx)->render_batch ? "lol_render_spec_batch" : "render_interp_batch";
+	if (contrast >= 0) return batch_aa_kernel(ctx) ? "lol_render_spec_batch_aa_list" : "render_interp_batch_aa_list";
+	return batch_aa_kernel(ctx) ? "lol_render_spec_batch_aa" : "render_interp_batch_aa";
+}
+
+int lol_gpu_views_refined(lol_gpu* ctx, int64_t* n) {
+	if (!ctx || !n) return LOL_GPU_ERR_ARG;
+	if (ctx->view_adaptive_last < 0 || !ctx->view_adaptive_sets[ctx->view_adaptive_last].d_counts)
+		return fail(ctx, LOL_GPU_ERR_ARG, "no adaptive batch has been launched");
+	lol_gpu::ViewAdaptiveSet& S = ctx->view_adaptive_sets[ctx->view_adaptive_last];
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	LOL_HIP(ctx, hipEventSynchronize(S.done));
+	std::vector<uint32_t> c;
+	try { c.resize((size_t)S.n_views); } catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory"); }
+	LOL_HIP(ctx, hipMemcpy(c.data(), S.d_counts, c.size() * 4, hipMemcpyDeviceToHost));
+	*n = 0;
+	for (uint32_t v : c) *n += v;
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_testing_fail_view_scratch(lol_gpu* ctx, int n) {
+	if (!ctx || n < 0) return LOL_GPU_ERR_ARG;
+	ctx->fail_view_scratch = n;
 	return LOL_GPU_OK;
 }
 

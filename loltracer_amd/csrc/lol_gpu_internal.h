@@ -21,6 +21,7 @@
 #include "lol_kernel.h"
 #include "lol_kernel_aa.h"
 #include "lol_kernel_batch.h"
+#include "lol_kernel_batch_aa.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -137,6 +138,8 @@ struct SceneKernel {
 	hipFunction_t render_aa_list = nullptr;    /* ... and lol_render_spec_aa_list beside it (the refine pass of adaptive frames) */
 	hipFunction_t render_batch = nullptr;      /* lol_render_spec_batch, where the module was compiled with it (lol_gpu_set_view_batches) */
 	hipFunction_t render_batch_counting = nullptr;   /* ... and lol_render_spec_batch_steps — or the former, where the module holds that one alone */
+	hipFunction_t render_batch_aa = nullptr;   /* lol_render_spec_batch_aa, where the module was compiled with it (lol_gpu_set_view_samples) */
+	hipFunction_t render_batch_aa_list = nullptr;    /* ... and lol_render_spec_batch_aa_list beside it (the refine pass of adaptive batches) */
 	std::string   key;                         /* FNV-1a of the code object (lol_gpu_kernel_key) */
 	explicit operator bool() const { return module != nullptr; }
 	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
@@ -211,6 +214,7 @@ struct lol_gpu {
 	int          samples = 1;            /* lol_gpu_set_samples: samples per pixel along each axis of the frames launched from now on */
 	int          adaptive = -1;          /* lol_gpu_set_adaptive_samples: the contrast T, or -1 (off) */
 	int          view_batches = 0;       /* lol_gpu_set_view_batches: the next upload's module carries lol_render_spec_batch */
+	int          view_samples = 0;       /* lol_gpu_set_view_samples: ... and lol_render_spec_batch_aa / _aa_list (and the batch kernels) */
 	/* The view records of batches (lol_gpu_render_views, lol_gpu.hip): a ring of sets, one per batch, whatever its stream.  A batch
 	 * fills its set's pinned host copy, queues the copy to the device and the launch behind it on its stream, and records `done`;
 	 * the next batch through the set waits for `copied` on the host (the pinned copy is the host's to write again) and for `done`
@@ -238,6 +242,23 @@ struct lol_gpu {
 	};
 	static constexpr int ADAPTIVE_SETS = 4;
 	AdaptiveSet  adaptive_sets[ADAPTIVE_SETS];
+	/* Scratch of adaptive batches (render_views_adaptive, lol_gpu.hip): a ring of its own, one set per batch, whatever its stream;
+	 * a batch waits on its set's `done` (behind the last batch that used it) and records it again at its end.  For n views of
+	 * w x h: 12 n w h bytes (plain pixels, ids, lists) + 8 (n + 1) (counts, group prefix) + 256 per refine block (the lane table).
+	 * Sets grow with the batch, freed in lol_gpu_destroy. */
+	struct ViewAdaptiveSet {
+		uint32_t*  d_buf = nullptr;          /* xrgb [n w h] | ids [n w h] | lists [n w h] | counts [n + 1] | prefix [n + 1] | lane table */
+		size_t     bytes = 0;
+		uint32_t*  d_counts = nullptr;       /* the lists' lengths of the set's last batch, and how many views it had */
+		int        n_views = 0;
+		hipEvent_t done = nullptr;
+		bool       used = false;             /* `done` has been recorded */
+	};
+	static constexpr int VIEW_ADAPTIVE_SETS = 4;
+	ViewAdaptiveSet view_adaptive_sets[VIEW_ADAPTIVE_SETS];
+	unsigned     view_adaptive_rr = 0;
+	int          view_adaptive_last = -1;      /* the set of the last adaptive batch (lol_gpu_views_refined) */
+	int          fail_view_scratch = 0;        /* lol_gpu_testing_fail_view_scratch: that many scratch allocations of adaptive batches still fail */
 	unsigned     adaptive_rr = 0;
 	int          adaptive_last = -1;     /* the set of the last adaptive frame (lol_gpu_adaptive_refined) */
 	uint32_t*    d_adaptive_order = nullptr;   /* the refine pass's block -> lane-table slot table: slot b at tile_slot(b, stride) */
@@ -388,10 +409,11 @@ float smooth_sat_threshold(float k);
 inline bool culling_enabled(int want) { return want != 0; }      /* (lol_gpu_set_cull) */
 bool spec_out_of_line(const lol_program& P, int form = SPEC_BY_SIZE);
 /* aa: the module also carries lol_render_spec_aa (the context asked for supersampling before the upload); without it the source
- * is exactly what it was before supersampling existed; batch: ... and lol_render_spec_batch (lol_gpu_set_view_batches), likewise */
+ * is exactly what it was before supersampling existed; batch: ... and lol_render_spec_batch (lol_gpu_set_view_batches), likewise;
+ * batch_aa: ... and lol_render_spec_batch_aa / _aa_list (lol_gpu_set_view_samples; implies batch), likewise */
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
                   std::string& log, std::string* src_out = nullptr, bool cull = true, int form = SPEC_BY_SIZE, bool aa = false,
-                  bool batch = false);
+                  bool batch = false, bool batch_aa = false);
 /* the interpreter's two macro-op lists for `P`, one after the other (with / without v_div_fixup in the proven blend factors);
  * false: the two differ in length (cannot happen: same records by construction) */
 bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, std::vector<uint32_t>& lists, uint32_t& n_mops);

@@ -195,6 +195,22 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_view_batches.restype = C.c_int
         lib.lol_gpu_compile_offline_views.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
         lib.lol_gpu_compile_offline_views.restype = C.c_int
+        lib.lol_gpu_render_views_samples.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                                     C.c_size_t, C.c_size_t, P(Debug), vp]
+        lib.lol_gpu_render_views_samples.restype = C.c_int
+        lib.lol_gpu_set_view_samples.argtypes = [vp, C.c_int]
+        lib.lol_gpu_set_view_samples.restype = C.c_int
+        lib.lol_gpu_view_samples.argtypes = [vp]
+        lib.lol_gpu_view_samples.restype = C.c_int
+        lib.lol_gpu_compile_offline_view_samples.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p,
+                                                             C.c_size_t]
+        lib.lol_gpu_compile_offline_view_samples.restype = C.c_int
+        lib.lol_gpu_view_samples_kernel_name.argtypes = [vp, C.c_int, C.c_int]
+        lib.lol_gpu_view_samples_kernel_name.restype = C.c_char_p
+        lib.lol_gpu_views_refined.argtypes = [vp, P(C.c_int64)]
+        lib.lol_gpu_views_refined.restype = C.c_int
+        lib.lol_gpu_testing_fail_view_scratch.argtypes = [vp, C.c_int]
+        lib.lol_gpu_testing_fail_view_scratch.restype = C.c_int
         lib.lol_gpu_multi_set_samples.argtypes = [vp, C.c_int]
         lib.lol_gpu_multi_set_samples.restype = C.c_int
         lib.lol_gpu_verify_fast_paths.argtypes = [vp, C.c_float, P(C.c_ulonglong), P(C.c_ulonglong)]
@@ -288,7 +304,7 @@ def gpu_lib() -> C.CDLL:
 
 
 TESTING_SYMBOLS = ["lol_gpu_testing_fail_uploads", "lol_gpu_testing_fail_first_tier", "lol_gpu_testing_has_return_clobbering_branch", "lol_gpu_multi_testing_root_stride",
-                   "lol_gpu_multi_testing_force_copier_threads"]          # include/lol_gpu_testing.h
+                   "lol_gpu_multi_testing_force_copier_threads", "lol_gpu_testing_fail_view_scratch"]      # include/lol_gpu_testing.h
 
 EXPORTED_SYMBOLS = [                                                    # include/lol_gpu.h
     "lol_gpu_abi_version", "lol_gpu_device_count", "lol_gpu_create", "lol_gpu_destroy", "lol_gpu_error",
@@ -307,13 +323,15 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_set_frames_in_flight", "lol_gpu_frames_in_flight", "lol_gpu_next_stream", "lol_gpu_set_specialize_max_ops",
     "lol_gpu_set_samples", "lol_gpu_samples", "lol_gpu_multi_set_samples", "lol_gpu_set_adaptive_samples",
     "lol_gpu_adaptive_samples", "lol_gpu_render_views", "lol_gpu_set_view_batches", "lol_gpu_view_batches",
+    "lol_gpu_render_views_samples", "lol_gpu_set_view_samples", "lol_gpu_view_samples",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
     "lol_gpu_tuning_switches", "lol_gpu_roctx_ranges", "lol_gpu_verify_fast_paths", "lol_gpu_verify_smin_no_fixup",
     "lol_gpu_verify_gamma_table", "lol_gpu_cull_bounds", "lol_gpu_cull_bounds_clusters", "lol_gpu_powf_batch",
     "lol_gpu_sdf_batch", "lol_gpu_compile_offline_samples", "lol_gpu_adaptive_refined", "lol_gpu_adaptive_pass_ms",
-    "lol_gpu_compile_offline_views",
+    "lol_gpu_compile_offline_views", "lol_gpu_compile_offline_view_samples", "lol_gpu_view_samples_kernel_name",
+    "lol_gpu_views_refined",
 ]
 
 
@@ -350,6 +368,18 @@ def compile_offline_views(program: S.Program, out_base: str, enable: bool = True
     log = C.create_string_buffer(1 << 16)
     st = gpu_lib().lol_gpu_compile_offline_views(C.byref(program), arch.encode(), os.fsencode(out_base),
                                                  int(assume_fast), int(bool(enable)), int(form), log, len(log))
+    if st != LOL_GPU_OK:
+        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
+    return log.value.decode(errors="replace")
+
+
+def compile_offline_view_samples(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
+                                 assume_fast: bool = False) -> str:
+    """compile_offline for a context with set_view_samples(enable) before its upload: what compile_offline_views writes, with
+    lol_render_spec_batch_aa and lol_render_spec_batch_aa_list appended.  form as for compile_offline_views."""
+    log = C.create_string_buffer(1 << 16)
+    st = gpu_lib().lol_gpu_compile_offline_view_samples(C.byref(program), arch.encode(), os.fsencode(out_base),
+                                                        int(assume_fast), int(bool(enable)), int(form), log, len(log))
     if st != LOL_GPU_OK:
         raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
     return log.value.decode(errors="replace")
@@ -451,12 +481,39 @@ class Renderer:
     def view_batches(self) -> bool:
         return bool(self._lib.lol_gpu_view_batches(self._ctx))
 
+    def set_view_samples(self, enable: bool):
+        """Before prepare(): the scene's own module also carries the supersampled batch kernels (lol_render_spec_batch_aa,
+        lol_render_spec_batch_aa_list, and the batch kernels of set_view_batches); without it — and until that module is ready —
+        render_views_into(samples=2 or 4) runs on the interpreter's instantiations.  Same pixels either way."""
+        self._check(self._lib.lol_gpu_set_view_samples(self._ctx, 1 if enable else 0))
+
+    @property
+    def view_samples(self) -> bool:
+        return bool(self._lib.lol_gpu_view_samples(self._ctx))
+
+    def view_samples_kernel_name(self, samples: int, adaptive: int = -1) -> str:
+        """the kernel the next render_views_into(..., samples, adaptive) launches (an adaptive batch: its refine pass)"""
+        return self._lib.lol_gpu_view_samples_kernel_name(self._ctx, int(samples), int(adaptive)).decode()
+
+    def views_refined(self) -> int:
+        """how many pixels of the last adaptive batch, all views together, were refined (waits for that batch)"""
+        n = C.c_int64(0)
+        self._check(self._lib.lol_gpu_views_refined(self._ctx, C.byref(n)))
+        return int(n.value)
+
+    def testing_fail_view_scratch(self, n: int):
+        """lol_gpu_testing.h: the next n scratch allocations of adaptive batches fail"""
+        self._check(self._lib.lol_gpu_testing_fail_view_scratch(self._ctx, int(n)))
+
     def render_views_into(self, dst_ptr: int, cameras, w: int, h: int, max_steps: int = 256, pitch_bytes: int | None = None,
-                          view_stride_bytes: int | None = None, debug: Debug | None = None, stream: int | None = None):
+                          view_stride_bytes: int | None = None, debug: Debug | None = None, stream: int | None = None,
+                          samples: int = 1, adaptive: int = -1):
         """Asynchronously render len(cameras) views of w x h in ONE launch (lol_gpu_render_views): view v is exactly the frame
         render_into renders under cameras[v] in a fixed tile order, its row y at dst_ptr + v * view_stride_bytes + y * pitch_bytes;
         the diagnostics of `debug` are dense [view, y, x] arrays.  cameras: scene.Camera or ready scene.FrameCamera objects (the
-        array is copied before the call returns)."""
+        array is copied before the call returns).
+        samples = 2 or 4 (and adaptive = a contrast 0 ... 255): the supersampled batch of lol_gpu_render_views_samples — view v is the
+        frame of set_samples(samples) / set_adaptive_samples(adaptive), whatever this renderer's own set_samples says."""
         cams = list(cameras)
         arr = (S.FrameCamera * max(1, len(cams)))()
         for i, c in enumerate(cams):
@@ -464,9 +521,14 @@ class Renderer:
             C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
         pitch = pitch_bytes if pitch_bytes is not None else w * 4
         stride = view_stride_bytes if view_stride_bytes is not None else h * pitch
-        self._check(self._lib.lol_gpu_render_views(
-            self._ctx, arr, len(cams), w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride,
-            C.byref(debug) if debug is not None else None, _stream_arg(stream)))
+        dbg = C.byref(debug) if debug is not None else None
+        if samples == 1 and adaptive == -1:
+            self._check(self._lib.lol_gpu_render_views(
+                self._ctx, arr, len(cams), w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride, dbg, _stream_arg(stream)))
+        else:
+            self._check(self._lib.lol_gpu_render_views_samples(
+                self._ctx, arr, len(cams), w, h, max_steps, int(samples), int(adaptive), C.c_void_p(dst_ptr), pitch, stride, dbg,
+                _stream_arg(stream)))
 
     def render_host(self, host_ptr: int, w: int, h: int, max_steps: int = 256, camera: S.Camera | None = None,
                     pitch_bytes: int | None = None):
