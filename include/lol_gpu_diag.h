@@ -98,6 +98,11 @@ int         lol_gpu_compile_offline_view_samples(const lol_program* prog, const 
  * "lol_render_spec_batch_aa_list" / "render_interp_batch_aa_list" for an adaptive batch, lol_gpu_render_views' for samples = 1.
  * (A scene kernel that has finished compiling takes over at the next frame, batch or lol_gpu_specialize_wait.) */
 const char* lol_gpu_view_samples_kernel_name(const lol_gpu* ctx, int samples, int contrast);
+/* The interpreter's instantiation for the uploaded program: *ssize = the operand-stack entries of its template argument (1, 3, 7,
+ * 11 or 63), *tables_global = 1 when lights, materials and root materials are read from global memory instead of LDS (then ssize is
+ * 3, 11 or 63).  The answer of the very function the interpreter's launches go through — frames, supersampled frames, refine passes
+ * and every kind of batch alike.  LOL_GPU_ERR_NO_PROGRAM before an upload.  For tests. */
+int         lol_gpu_interp_variant(lol_gpu* ctx, int* ssize, int* tables_global);
 /* Waits for the context's last adaptive batch and gives how many pixels of all its views were refined.  LOL_GPU_ERR_ARG when no
  * adaptive batch was launched.  For tests and rate tools. */
 int         lol_gpu_views_refined(lol_gpu* ctx, int64_t* n);

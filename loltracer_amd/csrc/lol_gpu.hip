@@ -315,21 +315,34 @@ template <int SSIZE, bool TABLES_GLOBAL = false> struct InterpVariant {
 	static constexpr int ssize = SSIZE;
 	static constexpr bool tables_global = TABLES_GLOBAL;
 };
+/* which rung: the stack class the program needs (lol_gpu_internal.h, interp_stack_class) on the LDS ladder; with large tables, read
+ * from global memory (lol_kernel.h, TABLES_LDS_MAX_DWORDS), the next of three stack classes.  interp_dispatch launches what this
+ * says and lol_gpu_interp_variant (lol_gpu_diag.h) reports it: one choice, made here. */
+struct InterpRung { int ssize; bool tables_global; };
+InterpRung interp_rung(const lol_program& P) {
+	const int cls = interp_stack_class(P.max_stack);
+	if (lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots)) return { cls, false };
+	return { cls <= 3 ? 3 : cls <= lol::MOP_DEEP_FROM - 1 ? lol::MOP_DEEP_FROM - 1 : lol::MOP_DEEP_SLOTS, true };
+}
 template <class Launcher>
 hipError_t interp_dispatch(const lol_gpu* ctx, Launcher&& launch) {
-	const lol_program& P = ctx->h_prog;
-	const int cls = interp_stack_class(P.max_stack);
-	if (lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots)) {
-		if (cls == 1)      return launch(InterpVariant<1>());
-		else if (cls == 3) return launch(InterpVariant<3>());
-		else if (cls == 7) return launch(InterpVariant<7>());
-		else if (cls == lol::MOP_DEEP_FROM - 1) return launch(InterpVariant<lol::MOP_DEEP_FROM - 1>());
-		else               return launch(InterpVariant<lol::MOP_DEEP_SLOTS>());
+	const InterpRung r = interp_rung(ctx->h_prog);
+	if (!r.tables_global) {
+		switch (r.ssize) {
+		case 1:  return launch(InterpVariant<1>());
+		case 3:  return launch(InterpVariant<3>());
+		case 7:  return launch(InterpVariant<7>());
+		case lol::MOP_DEEP_FROM - 1: return launch(InterpVariant<lol::MOP_DEEP_FROM - 1>());
+		case lol::MOP_DEEP_SLOTS:    return launch(InterpVariant<lol::MOP_DEEP_SLOTS>());
+		}
+	} else {
+		switch (r.ssize) {
+		case 3:  return launch(InterpVariant<3, true>());
+		case lol::MOP_DEEP_FROM - 1: return launch(InterpVariant<lol::MOP_DEEP_FROM - 1, true>());
+		case lol::MOP_DEEP_SLOTS:    return launch(InterpVariant<lol::MOP_DEEP_SLOTS, true>());
+		}
 	}
-	/* large tables, read from global memory (lol_kernel.h, TABLES_LDS_MAX_DWORDS): three stack classes */
-	if (cls <= 3)      return launch(InterpVariant<3, true>());
-	else if (cls <= lol::MOP_DEEP_FROM - 1) return launch(InterpVariant<lol::MOP_DEEP_FROM - 1, true>());
-	else               return launch(InterpVariant<lol::MOP_DEEP_SLOTS, true>());
+	return hipErrorInvalidValue;           /* a rung without an instantiation: never a silent substitute */
 }
 
 /* a frame (or pass) on the interpreter; `list`, `count`: the refine pass of an adaptive frame */
@@ -1287,6 +1300,15 @@ const char* lol_gpu_view_samples_kernel_name(const lol_gpu* ctx, int samples, in
 	if (samples <= 1) return scene_kernel(ctx) && scene_kernel(ctx)->render_batch ? "lol_render_spec_batch" : "render_interp_batch";
 	if (contrast >= 0) return batch_aa_kernel(ctx) ? "lol_render_spec_batch_aa_list" : "render_interp_batch_aa_list";
 	return batch_aa_kernel(ctx) ? "lol_render_spec_batch_aa" : "render_interp_batch_aa";
+}
+
+int lol_gpu_interp_variant(lol_gpu* ctx, int* ssize, int* tables_global) {
+	if (!ctx || !ssize || !tables_global) return LOL_GPU_ERR_ARG;
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	const InterpRung r = interp_rung(ctx->h_prog);
+	*ssize = r.ssize;
+	*tables_global = r.tables_global ? 1 : 0;
+	return LOL_GPU_OK;
 }
 
 int lol_gpu_views_refined(lol_gpu* ctx, int64_t* n) {

@@ -221,9 +221,13 @@ void start_specialise(lol_gpu* ctx, const FastPaths& fast) {
 	job->batch = ctx->view_batches != 0;             /* (batches asked for after the upload render on render_interp_batch) */
 	job->batch_aa = ctx->view_samples != 0;          /* (... supersampled ones on render_interp_batch_aa / _aa_list) */
 	/* (LOL_GPU_SPEC_INLINE_MAX, a tuning switch, pins ONE form by size) */
-	T.second_wanted = T.want_second && !tuning_env("LOL_GPU_SPEC_INLINE_MAX") && ctx->h_prog.n_ops > LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS &&
-	                  ctx->h_prog.n_ops <= LOL_SPEC_INLINE_MAX_OPS;
-	job->form = T.second_wanted ? SPEC_OUT_OF_LINE : SPEC_BY_SIZE;
+	const bool first_tier = !tuning_env("LOL_GPU_SPEC_INLINE_MAX") && ctx->h_prog.n_ops > LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS &&
+	                        ctx->h_prog.n_ops <= LOL_SPEC_INLINE_MAX_OPS;
+	T.second_wanted = first_tier && T.want_second;
+	/* a mid-size scene's first kernel is the out-of-line form whether or not the inlined one follows: lol_gpu_set_specialize(ctx, 5)
+	 * declines the SECOND run, it does not ask for the slow compile in place of the first */
+	job->form = first_tier ? SPEC_OUT_OF_LINE : SPEC_BY_SIZE;
+	try { job->note += spec_out_of_line(ctx->h_prog, job->form) ? "form: SDF out of line\n" : "form: SDF inlined\n"; } catch (...) {}
 	T.job = std::move(job);
 	T.tier = SpecTiers::FIRST;
 	launch_job(T.job.get());

@@ -209,6 +209,8 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_view_samples_kernel_name.restype = C.c_char_p
         lib.lol_gpu_views_refined.argtypes = [vp, P(C.c_int64)]
         lib.lol_gpu_views_refined.restype = C.c_int
+        lib.lol_gpu_interp_variant.argtypes = [vp, P(C.c_int), P(C.c_int)]
+        lib.lol_gpu_interp_variant.restype = C.c_int
         lib.lol_gpu_testing_fail_view_scratch.argtypes = [vp, C.c_int]
         lib.lol_gpu_testing_fail_view_scratch.restype = C.c_int
         lib.lol_gpu_multi_set_samples.argtypes = [vp, C.c_int]
@@ -331,7 +333,7 @@ DIAG_SYMBOLS = [                                                        # includ
     "lol_gpu_verify_gamma_table", "lol_gpu_cull_bounds", "lol_gpu_cull_bounds_clusters", "lol_gpu_powf_batch",
     "lol_gpu_sdf_batch", "lol_gpu_compile_offline_samples", "lol_gpu_adaptive_refined", "lol_gpu_adaptive_pass_ms",
     "lol_gpu_compile_offline_views", "lol_gpu_compile_offline_view_samples", "lol_gpu_view_samples_kernel_name",
-    "lol_gpu_views_refined",
+    "lol_gpu_views_refined", "lol_gpu_interp_variant",
 ]
 
 
@@ -500,6 +502,13 @@ class Renderer:
         n = C.c_int64(0)
         self._check(self._lib.lol_gpu_views_refined(self._ctx, C.byref(n)))
         return int(n.value)
+
+    def interp_variant(self) -> tuple:
+        """(ssize, tables_global) of the interpreter instantiation the uploaded program runs on, as the launches themselves choose it
+        (lol_gpu_interp_variant): ssize 1, 3, 7, 11 or 63; tables_global True = tables read from global memory (ssize 3, 11 or 63)"""
+        ssize, tg = C.c_int(), C.c_int()
+        self._check(self._lib.lol_gpu_interp_variant(self._ctx, C.byref(ssize), C.byref(tg)))
+        return int(ssize.value), bool(tg.value)
 
     def testing_fail_view_scratch(self, n: int):
         """lol_gpu_testing.h: the next n scratch allocations of adaptive batches fail"""

@@ -31,6 +31,7 @@ def test_lol_gpu_diag_header_is_exported_too():
     assert set(names) == set(gpu.DIAG_SYMBOLS)
     for n in names:
         assert getattr(lib, n) is not None
+    assert gpu.gpu_lib().lol_gpu_interp_variant(None, C.byref(C.c_int()), C.byref(C.c_int())) == -3      # (no context: LOL_GPU_ERR_ARG)
     for host in ("hip_renderer.c", "lol_headless.c"):
         text = open(os.path.join(ROOT, "integration", host)).read()
         assert "lol_gpu_diag.h" not in text and not any(n + "(" in text for n in names), host

@@ -92,26 +92,30 @@ def test_random_scenes(torch_cuda, mode):
     r.close()
 
 
-def test_degenerate_inputs(torch_cuda):
-    """No lights, no objects, camera inside a sphere / on a plane, negative shininess (powf → inf → NaN → 1.0)."""
-    cases = [
-        "materials { { shininess = 2, diffuse = (1,1,1), specular = (1,1,1), ambient = (.5,.25,.125) } } scene { ambient { color = (1,1,1) } }",
-        "materials { { shininess = 2, diffuse = (1,1,1), specular = (1,1,1), ambient = (.5,.5,.5) } } scene { ambient { color = (.3,.3,.3) }, sphere { radius = 5 }, point_light { point = (0,9,0), diffuse_intensity = (1,1,1), specular_intensity = (1,1,1) } }",
-        "materials { { shininess = -1.5, diffuse = (.2,.2,.2), specular = (.3,.3,.3), ambient = (0,0,0) } } scene { camera { point = (0,1,0), direction = (0,-.2,-1), fov = 90 }, plane { y = 0 }, point_light { point = (2,5,-3), diffuse_intensity = (2,2,2), specular_intensity = (2,2,2) } }",
-        "materials { { shininess = 4, diffuse = (.2,.2,.2), specular = (.3,.3,.3), ambient = (.1,.1,.1) } } scene { camera { point = (0,0,0), direction = (0,0,-1), fov = 120 }, plane { y = 0 }, box { point = (0,0,-4), point2 = (1,1,1), radius = 0 }, point_light { point = (0,0,0), diffuse_intensity = (2,2,2), specular_intensity = (2,2,2) } }",
-    ]
+# No lights, no objects, camera inside a sphere / on a plane, negative shininess (powf → inf → NaN → 1.0) ...
+DEGENERATE_CASES = [
+    "materials { { shininess = 2, diffuse = (1,1,1), specular = (1,1,1), ambient = (.5,.25,.125) } } scene { ambient { color = (1,1,1) } }",
+    "materials { { shininess = 2, diffuse = (1,1,1), specular = (1,1,1), ambient = (.5,.5,.5) } } scene { ambient { color = (.3,.3,.3) }, sphere { radius = 5 }, point_light { point = (0,9,0), diffuse_intensity = (1,1,1), specular_intensity = (1,1,1) } }",
+    "materials { { shininess = -1.5, diffuse = (.2,.2,.2), specular = (.3,.3,.3), ambient = (0,0,0) } } scene { camera { point = (0,1,0), direction = (0,-.2,-1), fov = 90 }, plane { y = 0 }, point_light { point = (2,5,-3), diffuse_intensity = (2,2,2), specular_intensity = (2,2,2) } }",
+    "materials { { shininess = 4, diffuse = (.2,.2,.2), specular = (.3,.3,.3), ambient = (.1,.1,.1) } } scene { camera { point = (0,0,0), direction = (0,0,-1), fov = 120 }, plane { y = 0 }, box { point = (0,0,-4), point2 = (1,1,1), radius = 0 }, point_light { point = (0,0,0), diffuse_intensity = (2,2,2), specular_intensity = (2,2,2) } }",
     # a sphere so far away that |p - c|^2 overflows to +inf: sqrt(inf) = inf in the reference; the fast roots are not
     # proven there, so lol::Range must flag it and the wave re-shades through the plain path
-    cases.append("materials { { shininess = 4, diffuse = (.2,.2,.2), specular = (.3,.3,.3), ambient = (.1,.1,.1) } } scene {"
-                 " camera { point = (0,1,0), direction = (0,0,-1), fov = 90 }, sphere { point = (100000000000000000000, 0, 0), radius = 1 },"
-                 " sphere { point = (0,1,-4), radius = 1 }, point_light { point = (3,5,0), diffuse_intensity = (2,2,2), specular_intensity = (1,1,1) } }")
+    "materials { { shininess = 4, diffuse = (.2,.2,.2), specular = (.3,.3,.3), ambient = (.1,.1,.1) } } scene {"
+    " camera { point = (0,1,0), direction = (0,0,-1), fov = 90 }, sphere { point = (100000000000000000000, 0, 0), radius = 1 },"
+    " sphere { point = (0,1,-4), radius = 1 }, point_light { point = (3,5,0), diffuse_intensity = (2,2,2), specular_intensity = (1,1,1) } }",
     # the camera sits exactly on a sphere's centre (squared length 0: the fast root gives NaN there), next to a sphere
     # too small for the NaN flag (radius 2^-21: keeps the range tracker), inside a smooth union and on its own
-    cases.append("materials { { shininess = 4, diffuse = (.2,.2,.2), specular = (.3,.3,.3), ambient = (.1,.1,.1) } } scene {"
-                 " camera { point = (0,1,0), direction = (0,0,-1), fov = 90 }, sphere { point = (0,1,0), radius = 0.25 },"
-                 " smooth_union { smoothness = 0.5, a = sphere { point = (0,1,0), radius = 0.125 }, b = sphere { point = (1,1,-3), radius = 1 } },"
-                 " sphere { point = (0,1,0), radius = 0.000000476837158203125 }, plane { y = -1 },"
-                 " point_light { point = (0,1,0), diffuse_intensity = (2,2,2), specular_intensity = (1,1,1) } }")
+    "materials { { shininess = 4, diffuse = (.2,.2,.2), specular = (.3,.3,.3), ambient = (.1,.1,.1) } } scene {"
+    " camera { point = (0,1,0), direction = (0,0,-1), fov = 90 }, sphere { point = (0,1,0), radius = 0.25 },"
+    " smooth_union { smoothness = 0.5, a = sphere { point = (0,1,0), radius = 0.125 }, b = sphere { point = (1,1,-3), radius = 1 } },"
+    " sphere { point = (0,1,0), radius = 0.000000476837158203125 }, plane { y = -1 },"
+    " point_light { point = (0,1,0), diffuse_intensity = (2,2,2), specular_intensity = (1,1,1) } }",
+]
+
+
+def test_degenerate_inputs(torch_cuda):
+    """DEGENERATE_CASES on the scene kernel and on the interpreter."""
+    cases = DEGENERATE_CASES
     for mode in (1, 4):
         r = gpu.Renderer(0, specialize=mode)
         for text in cases:
@@ -235,20 +239,37 @@ def test_unions_of_unions_with_one_smoothness(torch_cuda, monkeypatch):
         assert np.array_equal(frames[0], frames[1]), "scene %d" % n
 
 
-def test_deep_tree_needs_the_big_operand_stack(torch_cuda):
-    """A perfectly balanced smooth-union tree of 512 spheres (1024 ops): operand stack depth 10 — the interpreter's
-    largest instantiation and the out-of-line specialised SDF; both against the oracle."""
-    rng = np.random.default_rng(11)
+def balanced_tree_text(depth, seed, spread, centre, radii, smoothness, materials=None, extra=""):
+    """One object: a perfectly balanced smooth-union tree of 2^depth spheres (2^(depth+1) ops, operand stack depth + 1), material
+    #1, under one light.  materials: the whole `materials { ... }` block (default: the two the trees have always had); extra:
+    further scene components (", plane { ... }", more lights), appended after the tree."""
+    rng = np.random.default_rng(seed)
 
     def tree(d):
         if d == 0:
-            return "sphere { point = %s, radius = %s }" % (fmt(rng.normal(size=3) * [4, 2, 3] + [0, 0, -9]), num(rng.uniform(0.2, 0.8)))
-        return "smooth_union { smoothness = 0.5, a = %s, b = %s }" % (tree(d - 1), tree(d - 1))
-    text = ("materials { { shininess = 2, diffuse = (0,0,0), specular = (0,0,0), ambient = (.02,.02,.02) },"
-            " { shininess = 8, diffuse = (.5,.5,.5), specular = (.2,.2,.2), ambient = (.1,.1,.1) } }\n"
-            "scene { camera { point = (0, 1, 4), direction = (0, -0.1, -1), fov = 100 },"
+            return "sphere { point = %s, radius = %s }" % (fmt(rng.normal(size=3) * list(spread) + list(centre)), num(rng.uniform(*radii)))
+        return "smooth_union { smoothness = %s, a = %s, b = %s }" % (num(smoothness), tree(d - 1), tree(d - 1))
+    mats = materials or ("materials { { shininess = 2, diffuse = (0,0,0), specular = (0,0,0), ambient = (.02,.02,.02) },"
+                         " { shininess = 8, diffuse = (.5,.5,.5), specular = (.2,.2,.2), ambient = (.1,.1,.1) } }\n")
+    return (mats + "scene { camera { point = (0, 1, 4), direction = (0, -0.1, -1), fov = 100 },"
             " point_light { point = (0,9,0), diffuse_intensity = (2,2,2), specular_intensity = (2,2,2) }, "
-            + tree(9).replace("{", "{ material = #1,", 1) + " }")
+            + tree(depth).replace("{", "{ material = #1,", 1) + extra + " }")
+
+
+def deep_tree_text(depth=9, **kw):
+    """the tree of test_deep_tree_needs_the_big_operand_stack: 512 spheres, 1024 ops, operand stack 10 at depth 9"""
+    return balanced_tree_text(depth, 11, (4, 2, 3), (0, 0, -9), (0.2, 0.8), 0.5, **kw)
+
+
+def deeper_tree_text(depth=12, **kw):
+    """the tree of test_operand_stack_deeper_than_the_slot_fields: 4096 small spheres, 8192 ops, operand stack 13 at depth 12"""
+    return balanced_tree_text(depth, 3, (5, 2, 4), (0, 0, -10), (0.1, 0.5), 0.25, **kw)
+
+
+def test_deep_tree_needs_the_big_operand_stack(torch_cuda):
+    """A perfectly balanced smooth-union tree of 512 spheres (1024 ops): operand stack depth 10 — the interpreter's
+    largest instantiation and the out-of-line specialised SDF; both against the oracle."""
+    text = deep_tree_text()
     sc = S.Scene.parse_string(text)
     prog = sc.flatten()
     assert prog.n_ops == 1024 and prog.max_stack == 10
@@ -326,17 +347,7 @@ def test_operand_stack_deeper_than_the_slot_fields(torch_cuda):
     """A balanced smooth-union tree of 4096 spheres in ONE object: operand stack 13 — one more than the interpreter's register
     stacks hold; the deep instantiation (slots in words of their own, lol_kernel.h MOP_DEEP_FROM) renders it like the oracle, and
     so does the specialised kernel, whose straight-line SDF needs no stack at all."""
-    rng = np.random.default_rng(3)
-
-    def tree(d):
-        if d == 0:
-            return "sphere { point = %s, radius = %s }" % (fmt(rng.normal(size=3) * [5, 2, 4] + [0, 0, -10]), num(rng.uniform(0.1, 0.5)))
-        return "smooth_union { smoothness = 0.25, a = %s, b = %s }" % (tree(d - 1), tree(d - 1))
-    text = ("materials { { shininess = 2, diffuse = (0,0,0), specular = (0,0,0), ambient = (.02,.02,.02) },"
-            " { shininess = 8, diffuse = (.5,.5,.5), specular = (.2,.2,.2), ambient = (.1,.1,.1) } }\n"
-            "scene { camera { point = (0, 1, 4), direction = (0, -0.1, -1), fov = 100 },"
-            " point_light { point = (0,9,0), diffuse_intensity = (2,2,2), specular_intensity = (2,2,2) }, "
-            + tree(12).replace("{", "{ material = #1,", 1) + " }")
+    text = deeper_tree_text()
     sc = S.Scene.parse_string(text)
     prog = sc.flatten()
     assert prog.n_ops == 8192 and prog.max_stack == 13

@@ -65,7 +65,7 @@ def renderer(torch_cuda, request):
     r.close()
 
 
-def render_aa(torch, r, sc, w, h, s, rows=None, pitch_px=None, want_rgb=True, prepare=True):
+def render_aa(torch, r, sc, w, h, s, rows=None, pitch_px=None, want_rgb=True, prepare=True, max_steps=256):
     if prepare:
         r.set_samples(s)
         r.prepare(sc)
@@ -76,7 +76,7 @@ def render_aa(torch, r, sc, w, h, s, rows=None, pitch_px=None, want_rgb=True, pr
     rgb = torch.zeros((n_rows, w, 3), dtype=torch.float32, device="cuda:0") if want_rgb else None
     dbg = gpu.Debug(rgb.data_ptr(), None, None, None) if want_rgb else None
     torch.cuda.synchronize()
-    r.render_into(frame.data_ptr(), w, h, rows=rows, pitch_bytes=pitch_px * 4, debug=dbg,
+    r.render_into(frame.data_ptr(), w, h, max_steps, rows=rows, pitch_bytes=pitch_px * 4, debug=dbg,
                   stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     x = frame.cpu().numpy().view(np.uint32)

@@ -95,15 +95,15 @@ def collect(out):
     return out
 
 
-def render_batch(torch, r, cams, w, h, s, T, pitch_px=None, stride_px=None, rgb=True, stream=None):
+def render_batch(torch, r, cams, w, h, s, T, pitch_px=None, stride_px=None, rgb=True, stream=None, max_steps=256):
     out = alloc(torch, len(cams), w, h, pitch_px, stride_px, rgb)
     torch.cuda.synchronize()                 # torch's fills run on ITS stream; the batch on the renderer's own
-    queue(r, out, cams, s, T, stream)
+    queue(r, out, cams, s, T, stream, max_steps)
     r.sync()
     return collect(out)
 
 
-def render_single(torch, r2, cam, w, h, s, T):
+def render_single(torch, r2, cam, w, h, s, T, max_steps=256):
     """the frame of set_samples(s) / set_adaptive_samples(T) under `cam`, by lol_gpu_render_device"""
     r2.set_samples(s)
     r2.set_adaptive_samples(T)
@@ -111,7 +111,7 @@ def render_single(torch, r2, cam, w, h, s, T):
     frame = torch.full((h, w), SENTINEL, dtype=torch.int32, device=dev)
     rgb = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
     torch.cuda.synchronize()
-    r2.render_into(frame.data_ptr(), w, h, 256, camera=cam, debug=gpu.Debug(rgb.data_ptr(), None, None, None))
+    r2.render_into(frame.data_ptr(), w, h, max_steps, camera=cam, debug=gpu.Debug(rgb.data_ptr(), None, None, None))
     r2.sync()
     return dict(xrgb=frame.cpu().numpy().view(np.uint32), rgb=rgb.cpu().numpy())
 
