@@ -745,9 +745,9 @@ bool spec_out_of_line(const lol_program& P, int form) {
 	return P.n_ops > limit;
 }
 
-std::string generate_source(const lol_program& P, const FastPaths* fast, bool cull, int form = SPEC_BY_SIZE, bool aa = false, bool batch = false,
-                            bool batch_aa = false) {
+std::string generate_source(const lol_program& P, const FastPaths* fast, bool cull, int form = SPEC_BY_SIZE, ModuleKernels carries = {}) {
 	std::string s;
+	const FamilyRow* K = KERNEL_FAMILIES;
 	const bool ool = spec_out_of_line(P, form);
 	const std::vector<RootBound> roots = analyse_roots(P);
 	const CullPlan plan = plan_culling(roots, cull);
@@ -776,35 +776,43 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * A scene above LOL_SPEC_TWO_KERNELS_MAX_OPS gets the counting kernel alone, under the name lol_render_spec: a second copy of
 	 * its pipeline would nearly double what the compiler takes for it. */
 	const bool two = P.n_ops <= LOL_SPEC_TWO_KERNELS_MAX_OPS;
-	s += "template <bool COUNT> __device__ __forceinline__ void lol_spec_body(const lol::Launch& L, lol::u32* lds) {\n";
-	if (!tables_global) {
-		s += "\tlol::stage_common(L, lds);\n";
-		s += "\t__syncthreads();\n";
-	}
+	/* what every kernel begins with: lights, materials and root materials staged in LDS, where the scene keeps them there */
+	const std::string stage = tables_global ? "" : "\tlol::stage_common(L, lds);\n\t__syncthreads();\n";
+	/* P = the lane's pixel or sample of launch `of`: shaded with the fast SDF, and again with the exact one where the wave left what
+	 * was proven.  The fast pipeline takes FLAG_SHADOW_SETTLED for granted (lol_kernel.h, soft_shadow): a launch without it — `flags`
+	 * names the one that says; for a batch the VIEW's, so that a camera beyond the sane range in the middle of a batch takes the plain
+	 * pipeline — is the plain pipeline's.  `in`: indentation; `count`: shade_pixel's COUNT; `decl`: how a scene without a fast SDF
+	 * declares P in the statement that shades it, or "": on a line of its own first, as the fast form always does. */
+	auto shade = [&](const std::string& in, const std::string& flags, const std::string& of, const std::string& count, const std::string& decl) {
+		const std::string args = tg + ", " + count + ">(" + of + ", ";
+		std::string b;
+		if (any_fast || decl.empty()) b += in + "lol::Pixel P;\n";
+		if (any_fast) {
+			b += in + "bool plain = !(" + flags + ".flags & lol::FLAG_SHADOW_SETTLED);\n";
+			b += in + "if (!plain) {\n";
+			b += in + "\tlol::SpecSdfFast fast;\n";
+			b += in + "\tP = lol::shade_pixel<lol::SpecSdfFast, " + args + "fast, lds);\n";
+			b += in + "\tplain = lol::unproven(fast);\n";
+			b += in + "}\n";
+			b += in + "if (plain) {\n";
+			b += in + "\tlol::SpecSdfExact exact;\n";
+			b += in + "\tP = lol::shade_pixel<lol::SpecSdfExact, " + args + "exact, lds);\n";
+			b += in + "}\n";
+		} else {
+			b += in + "lol::SpecSdfExact exact;\n";
+			b += in + (decl.empty() ? "P = " : decl) + "lol::shade_pixel<lol::SpecSdfExact, " + args + "exact, lds);\n";
+		}
+		return b;
+	};
+	s += "template <bool COUNT> __device__ __forceinline__ void lol_spec_body(const lol::Launch& L, lol::u32* lds) {\n" + stage;
 	s += "\tif (!lol::start_tile_clock<" + tg + ">(L, lds)) return;\n";
-	if (any_fast) {
-		/* the fast pipeline takes FLAG_SHADOW_SETTLED for granted (lol_kernel.h, soft_shadow): a launch without it is the plain pipeline's */
-		s += "\tlol::Pixel P;\n";
-		s += "\tbool plain = !(L.flags & lol::FLAG_SHADOW_SETTLED);\n";
-		s += "\tif (!plain) {\n";
-		s += "\t\tlol::SpecSdfFast fast;\n";
-		s += "\t\tP = lol::shade_pixel<lol::SpecSdfFast, " + tg + ", COUNT>(L, fast, lds);\n";
-		s += "\t\tplain = lol::unproven(fast);\n";
-		s += "\t}\n";
-		s += "\tif (plain) {\n";
-		s += "\t\tlol::SpecSdfExact exact;\n";
-		s += "\t\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", COUNT>(L, exact, lds);\n";
-		s += "\t}\n";
-	} else {
-		s += "\tlol::SpecSdfExact exact;\n";
-		s += "\tlol::Pixel P = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", COUNT>(L, exact, lds);\n";
-	}
+	s += shade("\t", "L", "L", "COUNT", "lol::Pixel P = ");
 	s += "\tlol::store_pixel<" + tg + ">(L, P, lds);\n";
 	s += "}\n";
 	const std::string head = "extern \"C\" __global__ __launch_bounds__(lol::BLOCK)" + occupancy + " void ";
 	const std::string tail = "(const lol::Launch L) {\n\textern __shared__ lol::u32 lds[];\n\tlol_spec_body<";
-	if (two) s += head + "lol_render_spec_steps" + tail + "true>(L, lds);\n}\n";
-	s += head + "lol_render_spec" + tail + (two ? "false" : "true") + ">(L, lds);\n}\n";
+	if (two) s += head + K[FAM_FRAME].counting + tail + "true>(L, lds);\n}\n";
+	s += head + K[FAM_FRAME].symbol + tail + (two ? "false" : "true") + ">(L, lds);\n}\n";
 	/* the SDF alone at arbitrary points (lol_gpu_sdf_batch) */
 	s += "extern \"C\" __global__ __launch_bounds__(64) void lol_sdf_spec(const float* pts, float* dist, lol::u32* id, lol::u32 n) {\n";
 	s += "\tlol::SpecSdfExact exact;\n";
@@ -815,111 +823,51 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * samples stored (lol_kernel.h, store_pixel_aa), s read at run time.  Appended, so that a module without it is the same source
 	 * — and the same code object and kernel_key — as before supersampling existed.  No step counters: hit_dist, hit_id and steps
 	 * have no single value for a pixel of several samples (lol_gpu_render_device refuses them). */
-	if (aa) {
-		/* P = the lane's sample of launch S, the fast SDF's exact fallback done (`in`: indentation) */
-		auto shade = [&](const std::string& in) {
-			std::string b = in + "lol::Pixel P;\n";
-			if (any_fast) {
-				b += in + "bool plain = !(L.flags & lol::FLAG_SHADOW_SETTLED);\n";
-				b += in + "if (!plain) {\n";
-				b += in + "\tlol::SpecSdfFast fast;\n";
-				b += in + "\tP = lol::shade_pixel<lol::SpecSdfFast, " + tg + ", false>(S, fast, lds);\n";
-				b += in + "\tplain = lol::unproven(fast);\n";
-				b += in + "}\n";
-				b += in + "if (plain) {\n";
-				b += in + "\tlol::SpecSdfExact exact;\n";
-				b += in + "\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
-				b += in + "}\n";
-			} else {
-				b += in + "lol::SpecSdfExact exact;\n";
-				b += in + "P = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
-			}
-			return b;
-		};
-		const std::string stage = tables_global ? "" : "\tlol::stage_common(L, lds);\n\t__syncthreads();\n";
+	if (carries.carries(SWITCH_AA)) {
 		s += "#include \"lol_kernel_aa.h\"\n";
-		s += head + "lol_render_spec_aa(const lol::Launch L) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
+		s += head + K[FAM_FRAME_AA].symbol + "(const lol::Launch L) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tconst lol::Launch S = lol::sample_launch(L);\n";
-		s += shade("\t");
+		s += shade("\t", "L", "S", "false", "");
 		s += "\tlol::store_pixel_aa<" + tg + ">(L, P.rgb);\n";
 		s += "}\n";
 		/* the refine pass of adaptive frames (lol_gpu_set_adaptive_samples): the same pixel for a list of pixels */
-		s += head + "lol_render_spec_aa_list(const lol::Launch L, const lol::u32* list, const lol::u32* count) {\n";
+		s += head + K[FAM_FRAME_AA_LIST].symbol + "(const lol::Launch L, const lol::u32* list, const lol::u32* count) {\n";
 		s += "\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tlol::render_aa_list<" + tg + ">(L, list, count, [&](const lol::Launch& S) {\n";
-		s += shade("\t\t");
+		s += shade("\t\t", "L", "S", "false", "");
 		s += "\t\treturn P;\n";
 		s += "\t});\n";
 		s += "}\n";
 	}
 	/* Batches of views (lol_gpu_set_view_batches before the upload): the same pipeline on the launch of the block's view
 	 * (lol_kernel_batch.h), stored at that view's address.  Appended after everything else, for the reason above.  With and without
-	 * the step counters like lol_render_spec: a batch with lol_gpu_debug::steps runs lol_render_spec_batch_steps. */
-	if (batch) {
+	 * the step counters like the frame kernel: a batch with lol_gpu_debug::steps runs the counting twin. */
+	if (carries.carries(SWITCH_BATCH)) {
 		s += "#include \"lol_kernel_batch.h\"\n";
-		s += "template <bool COUNT> __device__ __forceinline__ void lol_spec_batch_body(const lol::Launch& L, const lol::BatchTail& B, lol::u32* lds) {\n";
-		if (!tables_global) s += "\tlol::stage_common(L, lds);\n\t__syncthreads();\n";
+		s += "template <bool COUNT> __device__ __forceinline__ void lol_spec_batch_body(const lol::Launch& L, const lol::BatchTail& B, lol::u32* lds) {\n" + stage;
 		s += "\tconst lol::Launch S = lol::view_launch(L, B.views);\n";
-		if (any_fast) {
-			/* (the VIEW's FLAG_SHADOW_SETTLED: a camera beyond the sane range in the middle of a batch takes the plain pipeline) */
-			s += "\tlol::Pixel P;\n";
-			s += "\tbool plain = !(S.flags & lol::FLAG_SHADOW_SETTLED);\n";
-			s += "\tif (!plain) {\n";
-			s += "\t\tlol::SpecSdfFast fast;\n";
-			s += "\t\tP = lol::shade_pixel<lol::SpecSdfFast, " + tg + ", COUNT>(S, fast, lds);\n";
-			s += "\t\tplain = lol::unproven(fast);\n";
-			s += "\t}\n";
-			s += "\tif (plain) {\n";
-			s += "\t\tlol::SpecSdfExact exact;\n";
-			s += "\t\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", COUNT>(S, exact, lds);\n";
-			s += "\t}\n";
-		} else {
-			s += "\tlol::SpecSdfExact exact;\n";
-			s += "\tconst lol::Pixel P = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", COUNT>(S, exact, lds);\n";
-		}
+		s += shade("\t", "S", "S", "COUNT", "const lol::Pixel P = ");
 		s += "\tlol::store_pixel_view(L, B, P);\n";
 		s += "}\n";
 		const std::string btail = "(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n\tlol_spec_batch_body<";
-		if (two) s += head + "lol_render_spec_batch_steps" + btail + "true>(L, B, lds);\n}\n";
-		s += head + "lol_render_spec_batch" + btail + (two ? "false" : "true") + ">(L, B, lds);\n}\n";
+		if (two) s += head + K[FAM_BATCH].counting + btail + "true>(L, B, lds);\n}\n";
+		s += head + K[FAM_BATCH].symbol + btail + (two ? "false" : "true") + ">(L, B, lds);\n}\n";
 	}
 	/* Supersampled batches (lol_gpu_set_view_samples before the upload; the batch kernels above come with it: the first pass of an
 	 * adaptive batch is theirs): the pipeline on the sample grid of the block's view, every pixel's samples reduced before the
 	 * store (lol_kernel_batch_aa.h), and the same for the per-view lists of an adaptive batch.  Appended after everything else,
 	 * for the reason above.  No step counters. */
-	if (batch_aa) {
-		/* P = the lane's sample of launch S — the VIEW's launch, whose FLAG_SHADOW_SETTLED chooses the pipeline — with the fast SDF's
-		 * exact fallback done (`in`: indentation) */
-		auto shade = [&](const std::string& in) {
-			std::string b = in + "lol::Pixel P;\n";
-			if (any_fast) {
-				b += in + "bool plain = !(S.flags & lol::FLAG_SHADOW_SETTLED);\n";
-				b += in + "if (!plain) {\n";
-				b += in + "\tlol::SpecSdfFast fast;\n";
-				b += in + "\tP = lol::shade_pixel<lol::SpecSdfFast, " + tg + ", false>(S, fast, lds);\n";
-				b += in + "\tplain = lol::unproven(fast);\n";
-				b += in + "}\n";
-				b += in + "if (plain) {\n";
-				b += in + "\tlol::SpecSdfExact exact;\n";
-				b += in + "\tP = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
-				b += in + "}\n";
-			} else {
-				b += in + "lol::SpecSdfExact exact;\n";
-				b += in + "P = lol::shade_pixel<lol::SpecSdfExact, " + tg + ", false>(S, exact, lds);\n";
-			}
-			return b;
-		};
-		const std::string stage = tables_global ? "" : "\tlol::stage_common(L, lds);\n\t__syncthreads();\n";
+	if (carries.carries(SWITCH_BATCH_AA)) {
 		s += "#include \"lol_kernel_batch_aa.h\"\n";
-		s += head + "lol_render_spec_batch_aa(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
+		s += head + K[FAM_BATCH_AA].symbol + "(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tconst lol::Launch S = lol::sample_launch(lol::view_launch(L, B.views));\n";
-		s += shade("\t");
+		s += shade("\t", "S", "S", "false", "");
 		s += "\tlol::store_pixel_view_aa(L, B, P.rgb);\n";
 		s += "}\n";
-		s += head + "lol_render_spec_batch_aa_list(const lol::Launch L, const lol::BatchTail B, const lol::BatchLists Q) {\n";
+		s += head + K[FAM_BATCH_AA_LIST].symbol + "(const lol::Launch L, const lol::BatchTail B, const lol::BatchLists Q) {\n";
 		s += "\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tlol::render_aa_view_lists<" + tg + ">(L, B, Q, [&](const lol::Launch& S) {\n";
-		s += shade("\t\t");
+		s += shade("\t\t", "S", "S", "false", "");
 		s += "\t\treturn P;\n";
 		s += "\t});\n";
 		s += "}\n";
@@ -1041,9 +989,9 @@ bool has_return_clobbering_branch(const std::vector<char>& code) { return has_re
 
 /* hipRTC: generated source + lol_kernel.h → code object for `arch`.  Needs no device. */
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
-                  std::string& log, std::string* src_out, bool cull, int form, bool aa, bool batch, bool batch_aa) {
-	if (batch_aa) batch = true;                 /* (a module with the supersampled batch kernels carries the plain ones) */
-	std::string src = generate_source(P, fast, cull, form, aa, batch, batch_aa);
+                  std::string& log, std::string* src_out, bool cull, int form, ModuleKernels carries) {
+	const bool aa = carries.carries(SWITCH_AA), batch = carries.carries(SWITCH_BATCH), batch_aa = carries.carries(SWITCH_BATCH_AA);
+	std::string src = generate_source(P, fast, cull, form, carries);
 	if (src_out) *src_out = src;
 	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
 		if (FILE* f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
@@ -1235,12 +1183,13 @@ int lol_gpu_compile_offline(const lol_program* prog, const char* arch, const cha
 
 /* ... the module a context with lol_gpu_set_samples(ctx, samples) compiles at its upload: with samples > 1 it also carries
  * lol_render_spec_aa (lol_gpu_diag.h) */
-static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples, bool batch,
-                           int form, char* log, size_t logcap, bool batch_aa = false);
+static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, ModuleKernels carries,
+                           int form, char* log, size_t logcap);
 
 int lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples,
                                     char* log, size_t logcap) {
-	return compile_offline(prog, arch, out_base, assume_fast, samples, false, SPEC_BY_SIZE, log, logcap);
+	if (samples != 1 && samples != 2 && samples != 4) return LOL_GPU_ERR_ARG;
+	return compile_offline(prog, arch, out_base, assume_fast, { samples > 1, false, false }, SPEC_BY_SIZE, log, logcap);
 }
 
 /* ... the module a context with lol_gpu_set_view_batches(ctx, 1) compiles at its upload, in the form of one of its tiers
@@ -1248,19 +1197,19 @@ int lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, c
 int lol_gpu_compile_offline_views(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable, int form,
                                   char* log, size_t logcap) {
 	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
-	return compile_offline(prog, arch, out_base, assume_fast, 1, enable != 0, form, log, logcap);
+	return compile_offline(prog, arch, out_base, assume_fast, { false, enable != 0, false }, form, log, logcap);
 }
 
 /* ... and the module a context with lol_gpu_set_view_samples(ctx, 1) compiles at its upload (lol_gpu_diag.h) */
 int lol_gpu_compile_offline_view_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
                                          int form, char* log, size_t logcap) {
 	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
-	return compile_offline(prog, arch, out_base, assume_fast, 1, false, form, log, logcap, enable != 0);
+	return compile_offline(prog, arch, out_base, assume_fast, { false, false, enable != 0 }, form, log, logcap);
 }
 
-static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples, bool batch,
-                           int form, char* log, size_t logcap, bool batch_aa) {
-	if (!prog || !arch || (samples != 1 && samples != 2 && samples != 4)) return LOL_GPU_ERR_ARG;
+static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, ModuleKernels carries,
+                           int form, char* log, size_t logcap) {
+	if (!prog || !arch) return LOL_GPU_ERR_ARG;
 	std::vector<char> code;
 	std::string lg, src;
 	FastPaths fast;
@@ -1276,7 +1225,7 @@ static int compile_offline(const lol_program* prog, const char* arch, const char
 		/* on the large-stack thread, like every run of the scene compiler (BigStackThread) */
 		BigStackThread th;
 		auto work = [&]() {
-			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), form, samples > 1, batch, batch_aa); }
+			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), form, carries); }
 			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
 		};
 		bool started = false;

@@ -87,45 +87,19 @@ hipError_t launch_sdf_interp(const uint32_t* mops, uint32_t n_mops, const float*
 	return hipGetLastError();
 }
 
-template <int SSIZE, bool TABLES_GLOBAL = false>
-hipError_t launch_interp(const lol::Launch& L, dim3 grid, size_t lds, hipStream_t s, int sqrt_kind, bool aa,
-                         const uint32_t* list, const uint32_t* count) {
-	if (list) {                /* the refine pass of adaptive frames (lol_gpu_set_adaptive_samples) */
-		if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_aa_list<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, list, count);
-		else                hipLaunchKernelGGL((lol::render_interp_aa_list<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, list, count);
-		return hipGetLastError();
+/* the interpreter's kernel of a family (lol_gpu_internal.h, KERNEL_FAMILIES) for one stack class, sqrt kind and table placement: its
+ * address, for hipLaunchKernel */
+template <int SSIZE, int KIND, bool TABLES_GLOBAL>
+const void* interp_kernel(KernelFamily f) {
+	switch (f) {
+	case FAM_FRAME:         return reinterpret_cast<const void*>(&lol::render_interp<SSIZE, KIND, TABLES_GLOBAL>);
+	case FAM_FRAME_AA:      return reinterpret_cast<const void*>(&lol::render_interp_aa<SSIZE, KIND, TABLES_GLOBAL>);
+	case FAM_FRAME_AA_LIST: return reinterpret_cast<const void*>(&lol::render_interp_aa_list<SSIZE, KIND, TABLES_GLOBAL>);
+	case FAM_BATCH:         return reinterpret_cast<const void*>(&lol::render_interp_batch<SSIZE, KIND, TABLES_GLOBAL>);
+	case FAM_BATCH_AA:      return reinterpret_cast<const void*>(&lol::render_interp_batch_aa<SSIZE, KIND, TABLES_GLOBAL>);
+	case FAM_BATCH_AA_LIST: return reinterpret_cast<const void*>(&lol::render_interp_batch_aa_list<SSIZE, KIND, TABLES_GLOBAL>);
+	default:                return nullptr;
 	}
-	if (aa) {                  /* supersampled frames (lol_gpu_set_samples): one instantiation per variant, s read at run time */
-		if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_aa<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
-		else                hipLaunchKernelGGL((lol::render_interp_aa<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
-		return hipGetLastError();
-	}
-	if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
-	else                hipLaunchKernelGGL((lol::render_interp<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L);
-	return hipGetLastError();
-}
-
-
-/* a batch of views on the interpreter (lol_kernel_batch.h): the instantiation beside launch_interp's */
-template <int SSIZE, bool TABLES_GLOBAL = false>
-hipError_t launch_interp_batch(const lol::Launch& L, const lol::BatchTail& B, dim3 grid, size_t lds, hipStream_t s, int sqrt_kind) {
-	if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_batch<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B);
-	else                hipLaunchKernelGGL((lol::render_interp_batch<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B);
-	return hipGetLastError();
-}
-
-/* ... and a supersampled batch (lol_kernel_batch_aa.h): every pixel, or — `Q` — the lists of an adaptive batch */
-template <int SSIZE, bool TABLES_GLOBAL = false>
-hipError_t launch_interp_batch_aa(const lol::Launch& L, const lol::BatchTail& B, const lol::BatchLists* Q, dim3 grid, size_t lds, hipStream_t s,
-                                  int sqrt_kind) {
-	if (Q) {
-		if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_batch_aa_list<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B, *Q);
-		else                hipLaunchKernelGGL((lol::render_interp_batch_aa_list<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B, *Q);
-		return hipGetLastError();
-	}
-	if (sqrt_kind == 3) hipLaunchKernelGGL((lol::render_interp_batch_aa<SSIZE, 3, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B);
-	else                hipLaunchKernelGGL((lol::render_interp_batch_aa<SSIZE, 0, TABLES_GLOBAL>), grid, dim3(lol::BLOCK), lds, s, L, B);
-	return hipGetLastError();
 }
 
 /* Conditions under which an escaped ray's colour is exactly clamp(ambient * materials[0].ambient), so
@@ -296,21 +270,19 @@ struct Roctx {
 	}
 } g_roctx;
 
-/* the scene kernel a frame of the context's current settings runs, or nullptr: the interpreter.  A supersampled frame needs a module
- * compiled with lol_render_spec_aa (samples > 1 at the upload); else it renders on render_interp_aa, same pixels. */
-const SceneKernel* frame_kernel(const lol_gpu* ctx) {
+/* the scene kernel that runs family `f`, or nullptr: the interpreter does — there is no module yet, or it was compiled without that
+ * family (a switch set after the upload).  Same pixels either way. */
+const SceneKernel* family_kernel(const lol_gpu* ctx, KernelFamily f) {
 	const SceneKernel* k = scene_kernel(ctx);
-	return k && (ctx->samples == 1 || k->render_aa) ? k : nullptr;
+	return k && k->fn[f] ? k : nullptr;
 }
-const char* kernel_name(const lol_gpu* ctx) {
-	if (ctx->samples > 1 && ctx->adaptive >= 0) return frame_kernel(ctx) ? "lol_render_spec_aa_list" : "render_interp_aa_list";
-	if (ctx->samples > 1) return frame_kernel(ctx) ? "lol_render_spec_aa" : "render_interp_aa";
-	return scene_kernel(ctx) ? "lol_render_spec" : "render_interp";
-}
+const char* family_name(const lol_gpu* ctx, KernelFamily f) { return family_kernel(ctx, f) ? KERNEL_FAMILIES[f].symbol : KERNEL_FAMILIES[f].interp; }
+/* the family of a frame under the context's current settings (of an adaptive frame: its refine pass) */
+KernelFamily frame_family(const lol_gpu* ctx) { return ctx->samples == 1 ? FAM_FRAME : ctx->adaptive >= 0 ? FAM_FRAME_AA_LIST : FAM_FRAME_AA; }
+const char* kernel_name(const lol_gpu* ctx) { return family_name(ctx, frame_family(ctx)); }
 
 /* The interpreter's instantiation for the program's stack class and table placement — THE ladder, for every kernel the interpreter
- * has (frames, supersampled frames, refine passes, batches of views): launch(ssize, tables_global) is called with the two as
- * compile-time constants. */
+ * has (launch_family): launch(ssize, tables_global) is called with the two as compile-time constants. */
 template <int SSIZE, bool TABLES_GLOBAL = false> struct InterpVariant {
 	static constexpr int ssize = SSIZE;
 	static constexpr bool tables_global = TABLES_GLOBAL;
@@ -345,24 +317,24 @@ hipError_t interp_dispatch(const lol_gpu* ctx, Launcher&& launch) {
 	return hipErrorInvalidValue;           /* a rung without an instantiation: never a silent substitute */
 }
 
-/* a frame (or pass) on the interpreter; `list`, `count`: the refine pass of an adaptive frame */
-hipError_t interp_frame(const lol_gpu* ctx, const lol::Launch& L, dim3 grid, size_t common, hipStream_t s, bool aa,
-                        const uint32_t* list = nullptr, const uint32_t* count = nullptr) {
+/* ONE launch of a kernel of family `f`: the scene module's where the module carries the family, else the interpreter's instantiation
+ * for the program's rung (interp_dispatch: a rung without one is an error, never a substitute).  `args`: the addresses of the
+ * kernel's arguments — (L), (L, list, count), (L, B) or (L, B, Q), the same for both kernels of a family, so one array serves
+ * hipModuleLaunchKernel and hipLaunchKernel.  `counts`: somebody reads the per-lane step counters — a module compiles them into the
+ * family's counting twin alone (generate_source); the interpreter's kernels always count, the supersampling families never. */
+hipError_t launch_family(const lol_gpu* ctx, KernelFamily f, bool counts, void** args, dim3 grid, hipStream_t s) {
+	/* dynamic LDS, of frames and batches alike: the scene's tables and a dword per lane of the block (lol_kernel.h, common_lds_dwords) */
+	const lol_program& P = ctx->h_prog;
+	const unsigned lds = lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u;
+	if (const SceneKernel* k = family_kernel(ctx, f))
+		return hipModuleLaunchKernel(counts ? k->counting[f] : k->fn[f], grid.x, grid.y, grid.z, lol::BLOCK, 1, 1, lds, s, args, nullptr);
 	const int kind = ctx->interp_sqrt_kind;
-	return interp_dispatch(ctx, [&](auto v) { return launch_interp<decltype(v)::ssize, decltype(v)::tables_global>(L, grid, common, s, kind, aa, list, count); });
-}
-
-/* ... and a batch of views on it: through the same ladder */
-hipError_t interp_batch(const lol_gpu* ctx, const lol::Launch& L, const lol::BatchTail& B, dim3 grid, size_t common, hipStream_t s) {
-	const int kind = ctx->interp_sqrt_kind;
-	return interp_dispatch(ctx, [&](auto v) { return launch_interp_batch<decltype(v)::ssize, decltype(v)::tables_global>(L, B, grid, common, s, kind); });
-}
-
-/* ... and a supersampled one (`Q`: the refine pass of an adaptive batch) */
-hipError_t interp_batch_aa(const lol_gpu* ctx, const lol::Launch& L, const lol::BatchTail& B, const lol::BatchLists* Q, dim3 grid, size_t common,
-                           hipStream_t s) {
-	const int kind = ctx->interp_sqrt_kind;
-	return interp_dispatch(ctx, [&](auto v) { return launch_interp_batch_aa<decltype(v)::ssize, decltype(v)::tables_global>(L, B, Q, grid, common, s, kind); });
+	return interp_dispatch(ctx, [&](auto v) {
+		constexpr int ssize = decltype(v)::ssize;
+		constexpr bool tables_global = decltype(v)::tables_global;
+		const void* fn = kind == 3 ? interp_kernel<ssize, 3, tables_global>(f) : interp_kernel<ssize, 0, tables_global>(f);
+		return hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	});
 }
 
 /*
@@ -683,18 +655,6 @@ int lol_gpu_part_rows(int h, const lol_gpu_rows* rows) {
 	return (int)n;
 }
 
-/*
- * An adaptive frame (lol_gpu_set_adaptive_samples): three launches on `s`, no host wait between them.  `A` = the launch of the
- * whole supersampled frame (lol_gpu_render_device).
- *  1. the plain frame P into the scratch set: XRGB8888 pixels and object ids, by the non-counting kernel (the diagnostic colour
- *     straight into the caller's buffer), in a fixed tile order — the longest-first tables and AUTO's trials are left alone;
- *  2. adaptive_classify: the mask; unrefined pixels go to `dst`, refined ones to the list;
- *  3. the refine pass (lol_kernel_aa.h, render_aa_list) over the list, on a grid that fills the device — the list's length stays
- *     on the device.
- * Scratch: the next set of the ring, after the frame that used it last (hipStreamWaitEvent: frames on other streams, frames in
- * flight); the host waits for that frame only where the set has to grow, or where this frame goes to one of HIP's special stream
- * handles and that frame has not finished.
- */
 static int ensure_refine_grid(lol_gpu* ctx) {
 	if (!ctx->adaptive_blocks) {
 		/* the refine grid: enough one-wave blocks to fill the device (8 waves per SIMD, 4 SIMDs per CU), each with a slot of its own
@@ -712,64 +672,110 @@ static int ensure_refine_grid(lol_gpu* ctx) {
 	return LOL_GPU_OK;
 }
 
-static int render_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_gpu_debug* dbg, hipStream_t s, size_t common) {
+/* not by hipStreamWaitEvent on HIP's special handles (the legacy default stream, the per-thread one): this HIP's hipStreamWaitEvent
+ * dereferences the handle it is given and crashes (lol_sched.hip says the same) — there the host waits for the event */
+static int wait_on_stream(lol_gpu* ctx, hipStream_t s, hipEvent_t ev) {
+	const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
+	if (!special) LOL_HIP(ctx, hipStreamWaitEvent(s, ev, 0));
+	else LOL_HIP(ctx, hipEventSynchronize(ev));
+	return LOL_GPU_OK;
+}
+
+/* The scratch of set `si` of a ring (lol_gpu_internal.h, ScratchSet) grows to `need` bytes: the host waits for `behind`, the event of
+ * the set's last user, and the old buffer goes with what pointed into it (`last`: the ring's set that lol_gpu_*_refined reads).
+ * `inject`: lol_gpu_testing_fail_view_scratch's counter, for the ring it is about. */
+static int grow_scratch(lol_gpu* ctx, lol_gpu::ScratchSet& S, hipEvent_t behind, size_t need, int si, int& last, int* inject, const char* what) {
+	if (need <= S.bytes) return LOL_GPU_OK;
+	if (S.used) LOL_HIP(ctx, hipEventSynchronize(behind));
+	if (S.d_buf) (void)hipFree(S.d_buf);
+	S.d_buf = nullptr; S.bytes = 0; S.d_counts = nullptr; S.used = false;
+	if (last == si) last = -1;
+	const bool injected = inject && *inject > 0;
+	if (injected) --*inject;
+	const hipError_t me = injected ? hipErrorOutOfMemory : hipMalloc(reinterpret_cast<void**>(&S.d_buf), need);
+	if (me != hipSuccess) {
+		S.d_buf = nullptr;
+		(void)hipGetLastError();             /* (the thread's last error: the host's next HIP call must not trip over it) */
+		return fail(ctx, LOL_GPU_ERR_HIP, what, me);
+	}
+	S.bytes = need;
+	return LOL_GPU_OK;
+}
+
+/* The part of a launch that is the uploaded scene's and the context's: program and tables, ambient, the exact skips that hold for
+ * every camera, the gamma table, the surface's pixel format, the diagnostics' buffers.  What depends on the camera (which copy of the
+ * macro-op list, FLAG_SHADOW_SETTLED, the first step) is the caller's: per frame, or per view of a batch. */
+static void scene_launch_fields(const lol_gpu* ctx, const lol_gpu_debug* dbg, lol::Launch& L) {
+	const lol_program& P = ctx->h_prog;
+	L.n_ops = ctx->n_mops; L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
+	L.ops           = ctx->d_mops[ctx->cur];
+	L.lights        = ctx->d_tables[ctx->cur];
+	L.materials     = L.lights + (size_t)P.n_lights * lol::LIGHT_DWORDS;
+	L.root_material = L.materials + (size_t)P.n_materials * lol::MATERIAL_DWORDS;
+	L.ambient[0] = P.ambient_color.x; L.ambient[1] = P.ambient_color.y; L.ambient[2] = P.ambient_color.z;
+	L.flags = (ctx->miss_skip ? lol::FLAG_MISS_SKIP : 0u) | (ctx->dark_skip ? lol::FLAG_DARK_SKIP : 0u);
+	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
+	if (dbg) {
+		L.dbg_rgb = dbg->rgb; L.dbg_hit_dist = dbg->hit_dist;
+		L.dbg_hit_id = dbg->hit_id; L.dbg_steps = dbg->steps;
+	}
+}
+
+/* Pass 1 of an adaptive frame or batch, from `A`, the launch of the whole supersampled one: one sample per pixel, whole frames,
+ * dense XRGB8888 into `xrgb` and the object ids into `ids` (the diagnostic colour straight into the caller's buffer) */
+static lol::Launch plain_pass_of(const lol::Launch& A, uint32_t* xrgb, uint32_t* ids, const lol_gpu_debug* dbg) {
+	lol::Launch L = A;
+	L.fw = (float)A.w; L.fh = (float)A.h;
+	L.flags &= ~(lol::FLAG_SAMPLES_2 | lol::FLAG_SAMPLES_4);
+	L.n_rows = A.h; L.band_rows = A.h; L.cycle_rows = A.h; L.offset_rows = 0;
+	L.dst = xrgb; L.pitch_px = (uint32_t)A.w;
+	L.fmt_shift = 16u | 8u << 8; L.fmt_loss = 0; L.fmt_amask = 0;
+	L.dbg_rgb = dbg ? dbg->rgb : nullptr; L.dbg_hit_dist = nullptr; L.dbg_hit_id = ids; L.dbg_steps = nullptr;
+	return L;
+}
+
+/*
+ * An adaptive frame (lol_gpu_set_adaptive_samples): three launches on `s`, no host wait between them.  `A` = the launch of the
+ * whole supersampled frame (lol_gpu_render_device).
+ *  1. the plain frame P into the scratch set: XRGB8888 pixels and object ids, by the non-counting kernel (the diagnostic colour
+ *     straight into the caller's buffer), in a fixed tile order — the longest-first tables and AUTO's trials are left alone;
+ *  2. adaptive_classify: the mask; unrefined pixels go to `dst`, refined ones to the list;
+ *  3. the refine pass (lol_kernel_aa.h, render_aa_list) over the list, on a grid that fills the device — the list's length stays
+ *     on the device.
+ * Scratch: the next set of the ring, after the frame that used it last (hipStreamWaitEvent: frames on other streams, frames in
+ * flight); the host waits for that frame only where the set has to grow, or where this frame goes to one of HIP's special stream
+ * handles and that frame has not finished.
+ */
+static int render_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_gpu_debug* dbg, hipStream_t s) {
 	const int w = A.w, h = A.h, ss = ctx->samples;
 	const size_t px = (size_t)w * h;
-	{
-		const int st = ensure_refine_grid(ctx);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(ensure_refine_grid(ctx));
 	const uint32_t per_wave = 64u / (uint32_t)(ss * ss);
 	const uint32_t blocks = (uint32_t)std::min<size_t>(ctx->adaptive_blocks, (px + per_wave - 1) / per_wave);
 	const int si = (int)(ctx->adaptive_rr++ % lol_gpu::ADAPTIVE_SETS);
 	lol_gpu::AdaptiveSet& S = ctx->adaptive_sets[si];
 	for (hipEvent_t& ev : S.ev) if (!ev) LOL_HIP(ctx, hipEventCreate(&ev));
-	const size_t need = (3 * px + 64 + (size_t)ctx->adaptive_blocks * 64) * 4;
-	if (need > S.bytes) {
-		if (S.used) LOL_HIP(ctx, hipEventSynchronize(S.ev[3]));
-		if (S.d_buf) (void)hipFree(S.d_buf);
-		S.d_buf = nullptr; S.bytes = 0; S.d_count = nullptr; S.used = false;
-		if (ctx->adaptive_last == si) ctx->adaptive_last = -1;
-		LOL_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&S.d_buf), need));
-		S.bytes = need;
-	}
+	LOL_TRY(grow_scratch(ctx, S, S.ev[3], (3 * px + 64 + (size_t)ctx->adaptive_blocks * 64) * 4, si, ctx->adaptive_last, nullptr,
+	                     "scratch of an adaptive frame"));
 	uint32_t* xrgb = S.d_buf;
 	uint32_t* ids = xrgb + px;
 	uint32_t* list = ids + px;
 	uint32_t* count = list + px;
 	uint32_t* lanes = count + 64;
-	if (S.used) {
-		/* behind the set's last frame, whatever stream it ran on.  Not by hipStreamWaitEvent on HIP's special handles (the legacy
-		 * default stream, the per-thread one): this HIP's hipStreamWaitEvent dereferences the handle it is given and crashes
-		 * (lol_sched.hip says the same) — there the host waits for that frame, where it has not finished yet. */
-		const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
-		if (!special) LOL_HIP(ctx, hipStreamWaitEvent(s, S.ev[3], 0));
-		else LOL_HIP(ctx, hipEventSynchronize(S.ev[3]));
-	}
+	if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.ev[3]));      /* behind the set's last frame, whatever stream it ran on */
 	LOL_HIP(ctx, hipEventRecord(S.ev[0], s));
 	LOL_HIP(ctx, hipMemsetAsync(count, 0, 4, s));
-	const int block = lol::TILE_W * lol::TILE_H;
 
 	/* 1. the plain frame */
-	lol::Launch L = A;
-	L.fw = (float)w; L.fh = (float)h;
-	L.flags &= ~(lol::FLAG_SAMPLES_2 | lol::FLAG_SAMPLES_4);
-	L.n_rows = h; L.band_rows = h; L.cycle_rows = h; L.offset_rows = 0;
-	L.dst = xrgb; L.pitch_px = (uint32_t)w;
-	L.fmt_shift = 16u | 8u << 8; L.fmt_loss = 0; L.fmt_amask = 0;
-	L.dbg_rgb = dbg ? dbg->rgb : nullptr; L.dbg_hit_dist = nullptr; L.dbg_hit_id = ids; L.dbg_steps = nullptr;
+	lol::Launch L = plain_pass_of(A, xrgb, ids, dbg);
 	dim3 grid((w + lol::TILE_W - 1) / lol::TILE_W, (h + lol::TILE_H - 1) / lol::TILE_H);
 	if (ctx->tiles.mode == LOL_GPU_TILES_COLS) {
 		L.flags |= lol::FLAG_TILE_COLS;
 		const unsigned t = grid.x; grid.x = grid.y; grid.y = t;
 	}
-	hipError_t e;
-	if (const SceneKernel* k = scene_kernel(ctx)) {
-		void* args[] = { &L };
-		e = hipModuleLaunchKernel(k->render, grid.x, grid.y, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
-	} else {
-		e = interp_frame(ctx, L, grid, common, s, false);
-	}
+	void* plain_args[] = { &L };
+	hipError_t e = launch_family(ctx, FAM_FRAME, false, plain_args, grid, s);
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (adaptive frame, plain pass)", e);
 	LOL_HIP(ctx, hipEventRecord(S.ev[1], s));
 
@@ -784,18 +790,12 @@ static int render_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_gpu_deb
 	lol::Launch R = A;
 	R.n_rows = h; R.band_rows = h; R.cycle_rows = h; R.offset_rows = 0;
 	R.tile_order = ctx->d_adaptive_order; R.tile_stride = ctx->adaptive_stride; R.lane_pixels = lanes;
-	if (const SceneKernel* k = frame_kernel(ctx)) {
-		const uint32_t* list_arg = list;
-		const uint32_t* count_arg = count;
-		void* args[] = { &R, &list_arg, &count_arg };
-		e = hipModuleLaunchKernel(k->render_aa_list, blocks, 1, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
-	} else {
-		e = interp_frame(ctx, R, dim3(blocks), common, s, true, list, count);
-	}
+	void* refine_args[] = { &R, &list, &count };
+	e = launch_family(ctx, FAM_FRAME_AA_LIST, false, refine_args, dim3(blocks), s);
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (adaptive frame, refine pass)", e);
 	LOL_HIP(ctx, hipEventRecord(S.ev[3], s));
 	S.used = true;
-	S.d_count = count;
+	S.d_counts = count;
 	ctx->adaptive_last = si;
 	return LOL_GPU_OK;
 }
@@ -838,25 +838,13 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	L.w = w; L.h = h; L.max_steps = max_steps;
 	L.n_rows = n_rows;
 	L.band_rows = R->band_rows; L.cycle_rows = R->cycle_rows; L.offset_rows = R->offset_rows;
-	const lol_program& P = ctx->h_prog;
-	L.n_ops = ctx->n_mops; L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
-	L.ops           = ctx->d_mops[ctx->cur] + (ctx->finite_scene && camera_sane(*cam) ? (size_t)ctx->n_mops * lol::MOP_DWORDS : 0u);
-	L.lights        = ctx->d_tables[ctx->cur];
-	L.materials     = L.lights + (size_t)P.n_lights * lol::LIGHT_DWORDS;
-	L.root_material = L.materials + (size_t)P.n_materials * lol::MATERIAL_DWORDS;
-	L.ambient[0] = P.ambient_color.x; L.ambient[1] = P.ambient_color.y; L.ambient[2] = P.ambient_color.z;
-	L.flags = (ctx->miss_skip ? lol::FLAG_MISS_SKIP : 0u) | (ctx->dark_skip ? lol::FLAG_DARK_SKIP : 0u) |
-	          (ctx->shadow_settle && camera_sane(*cam) ? lol::FLAG_SHADOW_SETTLED : 0u);
-	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+	scene_launch_fields(ctx, dbg, L);
+	if (ctx->finite_scene && camera_sane(*cam)) L.ops += (size_t)ctx->n_mops * lol::MOP_DWORDS;
+	if (ctx->shadow_settle && camera_sane(*cam)) L.flags |= lol::FLAG_SHADOW_SETTLED;
 	if (aa) L.flags |= ss == 4 ? lol::FLAG_SAMPLES_4 : lol::FLAG_SAMPLES_2;
 	if (first_step(ctx, *cam, max_steps)) { L.flags |= lol::FLAG_FIRST_STEP; L.first_dist = ctx->first_dist; L.first_id = ctx->first_id; }
 	L.dst = static_cast<uint32_t*>(dst);
 	L.pitch_px = (uint32_t)(pitch_bytes / 4);
-	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
-	if (dbg) {
-		L.dbg_rgb = dbg->rgb; L.dbg_hit_dist = dbg->hit_dist;
-		L.dbg_hit_id = dbg->hit_id; L.dbg_steps = dbg->steps;
-	}
 
 	/* LOL_GPU_STREAM_DEFAULT == hipStreamLegacy; NULL = the context's own stream(s), in turn (lol_gpu_set_frames_in_flight) */
 	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->frame_streams[ctx->frame_rr++ % (unsigned)ctx->n_frame_streams];
@@ -865,8 +853,7 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	const int tile_w = lol::TILE_W, tile_h = lol::TILE_H;      /* both kernels: one 16 x 4 wave per block (lol_kernel.h) */
 	const int block = tile_w * tile_h;
 	dim3 grid((ss * w + tile_w - 1) / tile_w, (ss * n_rows + tile_h - 1) / tile_h);
-	const size_t common = (size_t)(lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) - lol::TILE_W * lol::TILE_H + block) * 4;
-	if (adaptive) return render_adaptive(ctx, L, dbg, s, common);
+	if (adaptive) return render_adaptive(ctx, L, dbg, s);
 	int trial = -1;
 	bool table = false;
 	if (aa) {
@@ -894,7 +881,6 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 		L.flags |= lol::FLAG_TILE_COLS;
 		const unsigned t = grid.x; grid.x = grid.y; grid.y = t;      /* (both stay far below the 65535 blocks a grid may have in y) */
 	}
-	hipError_t e;
 	if (trial >= 0) LOL_HIP(ctx, hipEventRecord(ctx->tiles.ev[2 * trial], s));
 	g_roctx.init();
 	if (g_roctx.push) {
@@ -903,14 +889,8 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 		g_roctx.push(label);
 		g_roctx.ranges++;
 	}
-	if (const SceneKernel* k = frame_kernel(ctx)) {
-		void* args[] = { &L };
-		/* the step counters are compiled into render_counting alone (generate_source): who reads them gets that kernel */
-		const bool counts = (dbg && dbg->steps) || L.pixel_cost;
-		e = hipModuleLaunchKernel(aa ? k->render_aa : counts ? k->render_counting : k->render, grid.x, grid.y, 1, block, 1, 1, (unsigned)common, s, args, nullptr);
-	} else {
-		e = interp_frame(ctx, L, grid, common, s, aa);
-	}
+	void* args[] = { &L };
+	const hipError_t e = launch_family(ctx, aa ? FAM_FRAME_AA : FAM_FRAME, (dbg && dbg->steps) || L.pixel_cost, args, grid, s);
 	if (g_roctx.pop) g_roctx.pop();
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch", e);
 	if (table) lpt_frame_queued(ctx, s);
@@ -955,23 +935,10 @@ static void batch_launch(const lol_gpu* ctx, int w, int h, int max_steps, void* 
 	L.fw = (float)w; L.fh = (float)h;
 	L.w = w; L.h = h; L.max_steps = max_steps;
 	L.n_rows = h; L.band_rows = h; L.cycle_rows = h; L.offset_rows = 0;
-	const lol_program& P = ctx->h_prog;
-	L.n_ops = ctx->n_mops; L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
-	L.ops           = ctx->d_mops[ctx->cur];                 /* (+ View::ops_offset) */
-	L.lights        = ctx->d_tables[ctx->cur];
-	L.materials     = L.lights + (size_t)P.n_lights * lol::LIGHT_DWORDS;
-	L.root_material = L.materials + (size_t)P.n_materials * lol::MATERIAL_DWORDS;
-	L.ambient[0] = P.ambient_color.x; L.ambient[1] = P.ambient_color.y; L.ambient[2] = P.ambient_color.z;
-	L.flags = (ctx->miss_skip ? lol::FLAG_MISS_SKIP : 0u) | (ctx->dark_skip ? lol::FLAG_DARK_SKIP : 0u);
-	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+	scene_launch_fields(ctx, dbg, L);                        /* (ops: + View::ops_offset) */
 	if (ctx->tiles.mode == LOL_GPU_TILES_COLS) L.flags |= lol::FLAG_TILE_COLS;
 	L.dst = static_cast<uint32_t*>(dst);
 	L.pitch_px = (uint32_t)(pitch_bytes / 4);
-	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
-	if (dbg) {
-		L.dbg_rgb = dbg->rgb; L.dbg_hit_dist = dbg->hit_dist;
-		L.dbg_hit_id = dbg->hit_id; L.dbg_steps = dbg->steps;
-	}
 }
 
 /* LOL_GPU_STREAM_DEFAULT == hipStreamLegacy; NULL = the context's own stream(s), in turn.  Makes the context's device current and
@@ -980,20 +947,6 @@ static int batch_stream(lol_gpu* ctx, void* stream, hipStream_t* s) {
 	*s = stream ? static_cast<hipStream_t>(stream) : ctx->frame_streams[ctx->frame_rr++ % (unsigned)ctx->n_frame_streams];
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
 	finish_specialise(ctx, false);
-	return LOL_GPU_OK;
-}
-
-static size_t batch_common_lds(const lol_gpu* ctx) {
-	const lol_program& P = ctx->h_prog;
-	return (size_t)lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) * 4;
-}
-
-/* not by hipStreamWaitEvent on HIP's special handles (the legacy default stream, the per-thread one), which this HIP dereferences
- * (render_adaptive): there the host waits */
-static int wait_on_stream(lol_gpu* ctx, hipStream_t s, hipEvent_t ev) {
-	const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
-	if (!special) LOL_HIP(ctx, hipStreamWaitEvent(s, ev, 0));
-	else LOL_HIP(ctx, hipEventSynchronize(ev));
 	return LOL_GPU_OK;
 }
 
@@ -1017,8 +970,7 @@ static int queue_view_records(lol_gpu* ctx, const lol_frame_camera* cams, int n_
 		 * that queues faster than the device renders is held VIEW_SETS batches ahead of it here).  The device copy is this batch's once
 		 * the set's last LAUNCH has finished, whatever stream it ran on. */
 		LOL_HIP(ctx, hipEventSynchronize(S.copied));
-		const int st = wait_on_stream(ctx, s, S.done);
-		if (st != LOL_GPU_OK) return st;
+		LOL_TRY(wait_on_stream(ctx, s, S.done));
 	}
 	const bool settle = ctx->shadow_settle, finite = ctx->finite_scene;
 	for (int v = 0; v < n_views; v++) {
@@ -1056,19 +1008,6 @@ static void batch_range(const char* what, int n_views, int w, int h) {
 	}
 }
 
-/* one launch of the plain batch kernel for `L` / `B`: the scene's own where its module carries one, else the interpreter's */
-static hipError_t launch_plain_batch(const lol_gpu* ctx, const lol::Launch& L, const lol::BatchTail& B, dim3 grid, bool counts, hipStream_t s) {
-	const size_t common = batch_common_lds(ctx);
-	const SceneKernel* k = scene_kernel(ctx);
-	if (k && k->render_batch) {
-		lol::Launch La = L; lol::BatchTail Ba = B;
-		void* args[] = { &La, &Ba };
-		return hipModuleLaunchKernel(counts ? k->render_batch_counting : k->render_batch, grid.x, grid.y, grid.z, lol::BLOCK, 1, 1,
-		                             (unsigned)common, s, args, nullptr);
-	}
-	return interp_batch(ctx, L, B, grid, common, s);
-}
-
 /* lol_gpu_render_views without its look at lol_gpu_set_samples */
 static int render_views_plain(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
                               void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
@@ -1078,38 +1017,23 @@ static int render_views_plain(lol_gpu* ctx, const lol_frame_camera* cams, int n_
 	lol::Launch L;
 	batch_launch(ctx, w, h, max_steps, dst, pitch_bytes, dbg, L);
 	hipStream_t s;
-	{
-		const int st = batch_stream(ctx, stream, &s);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(batch_stream(ctx, stream, &s));
 	lol_gpu::ViewSet* S = nullptr;
-	{
-		const int st = queue_view_records(ctx, cams, n_views, max_steps, s, &S);
-		if (st != LOL_GPU_OK) return st;
-	}
-	const lol::BatchTail B = { S->d_views, (unsigned long long)(view_stride_bytes / 4) };
+	LOL_TRY(queue_view_records(ctx, cams, n_views, max_steps, s, &S));
+	lol::BatchTail B = { S->d_views, (unsigned long long)(view_stride_bytes / 4) };
 	batch_range("batch", n_views, w, h);
-	const hipError_t e = launch_plain_batch(ctx, L, B, grid, dbg && dbg->steps, s);
+	void* args[] = { &L, &B };
+	const hipError_t e = launch_family(ctx, FAM_BATCH, dbg && dbg->steps, args, grid, s);
 	if (g_roctx.pop) g_roctx.pop();
 	return view_records_done(ctx, *S, s, e, "kernel launch (batch of views)");
 }
 
 int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
                          void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
-	{
-		const int st = batch_refused(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(batch_refused(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
 	if (ctx->samples > 1)
 		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "batches of views are one sample per pixel (lol_gpu_set_samples): lol_gpu_render_views_samples");
 	return render_views_plain(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
-}
-
-/* the scene kernel a supersampled batch runs, or nullptr: the interpreter (a module compiled without lol_gpu_set_view_samples, or
- * none yet) */
-static const SceneKernel* batch_aa_kernel(const lol_gpu* ctx) {
-	const SceneKernel* k = scene_kernel(ctx);
-	return k && k->render_batch_aa ? k : nullptr;
 }
 
 /*
@@ -1127,10 +1051,7 @@ static int render_views_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_f
                                  size_t view_stride_bytes, const lol_gpu_debug* dbg, hipStream_t s) {
 	const int w = A.w, h = A.h;
 	const size_t px = (size_t)w * h, all = px * (size_t)n_views;
-	{
-		const int st = ensure_refine_grid(ctx);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(ensure_refine_grid(ctx));
 	const uint32_t per_wave = 64u / (uint32_t)(samples * samples);
 	/* (every view's list ends with a group that may be partly filled: at most n_views groups more than the entries need) */
 	const uint32_t blocks = (uint32_t)std::min<size_t>(ctx->adaptive_blocks, (px + per_wave - 1) / per_wave * (size_t)n_views);
@@ -1138,53 +1059,29 @@ static int render_views_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_f
 	lol_gpu::ViewAdaptiveSet& S = ctx->view_adaptive_sets[si];
 	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
 	const size_t tables = 2 * ((size_t)n_views + 1);
-	const size_t need = (3 * all + tables + (size_t)ctx->adaptive_blocks * 64) * 4;
-	if (need > S.bytes) {
-		if (S.used) LOL_HIP(ctx, hipEventSynchronize(S.done));
-		if (S.d_buf) (void)hipFree(S.d_buf);
-		S.d_buf = nullptr; S.bytes = 0; S.d_counts = nullptr; S.n_views = 0; S.used = false;
-		if (ctx->view_adaptive_last == si) ctx->view_adaptive_last = -1;
-		const bool injected = ctx->fail_view_scratch > 0;      /* lol_gpu_testing_fail_view_scratch */
-		if (injected) ctx->fail_view_scratch--;
-		const hipError_t me = injected ? hipErrorOutOfMemory : hipMalloc(reinterpret_cast<void**>(&S.d_buf), need);
-		if (me != hipSuccess) {
-			S.d_buf = nullptr;
-			(void)hipGetLastError();             /* (the thread's last error: the host's next HIP call must not trip over it) */
-			return fail(ctx, LOL_GPU_ERR_HIP, "scratch of an adaptive batch", me);
-		}
-		S.bytes = need;
-	}
+	LOL_TRY(grow_scratch(ctx, S, S.done, (3 * all + tables + (size_t)ctx->adaptive_blocks * 64) * 4, si, ctx->view_adaptive_last,
+	                     &ctx->fail_view_scratch, "scratch of an adaptive batch"));
 	uint32_t* xrgb = S.d_buf;
 	uint32_t* ids = xrgb + all;
 	uint32_t* lists = ids + all;
 	uint32_t* counts = lists + all;
 	uint32_t* prefix = counts + n_views + 1;
 	uint32_t* lanes = prefix + n_views + 1;
-	if (S.used) {
-		const int st = wait_on_stream(ctx, s, S.done);
-		if (st != LOL_GPU_OK) return st;
-	}
+	if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.done));
 	lol_gpu::ViewSet* V = nullptr;
-	{
-		const int st = queue_view_records(ctx, cams, n_views, A.max_steps, s, &V);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(queue_view_records(ctx, cams, n_views, A.max_steps, s, &V));
 	const char* what = "hipMemsetAsync (adaptive batch)";
 	hipError_t e = hipMemsetAsync(counts, 0, ((size_t)n_views + 1) * 4, s);
 
 	/* 1. the plain batch */
 	if (e == hipSuccess) {
-		lol::Launch L = A;
-		L.fw = (float)w; L.fh = (float)h;
-		L.flags &= ~(lol::FLAG_SAMPLES_2 | lol::FLAG_SAMPLES_4);
-		L.dst = xrgb; L.pitch_px = (uint32_t)w;
-		L.fmt_shift = 16u | 8u << 8; L.fmt_loss = 0; L.fmt_amask = 0;
-		L.dbg_rgb = dbg ? dbg->rgb : nullptr; L.dbg_hit_dist = nullptr; L.dbg_hit_id = ids; L.dbg_steps = nullptr;
-		const lol::BatchTail B = { V->d_views, (unsigned long long)px };
+		lol::Launch L = plain_pass_of(A, xrgb, ids, dbg);
+		lol::BatchTail B = { V->d_views, (unsigned long long)px };
 		dim3 grid;
 		(void)batch_grid(ctx, w, h, n_views, &grid);      /* (a part of the sample grid the caller has checked) */
 		what = "kernel launch (adaptive batch, plain pass)";
-		e = launch_plain_batch(ctx, L, B, grid, false, s);
+		void* args[] = { &L, &B };
+		e = launch_family(ctx, FAM_BATCH, false, args, grid, s);
 	}
 	/* 2. classify and compact, view by view */
 	if (e == hipSuccess) {
@@ -1207,22 +1104,16 @@ static int render_views_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_f
 		R.tile_order = ctx->d_adaptive_order; R.tile_stride = ctx->adaptive_stride; R.lane_pixels = lanes;
 		lol::BatchTail B = { V->d_views, (unsigned long long)(view_stride_bytes / 4) };
 		lol::BatchLists Q = { lists, counts, prefix, (uint32_t)n_views };
-		const size_t common = batch_common_lds(ctx);
 		what = "kernel launch (adaptive batch, refine pass)";
-		if (const SceneKernel* k = batch_aa_kernel(ctx)) {
-			void* args[] = { &R, &B, &Q };
-			e = hipModuleLaunchKernel(k->render_batch_aa_list, blocks, 1, 1, lol::BLOCK, 1, 1, (unsigned)common, s, args, nullptr);
-		} else {
-			e = interp_batch_aa(ctx, R, B, &Q, dim3(blocks), common, s);
-		}
+		void* args[] = { &R, &B, &Q };
+		e = launch_family(ctx, FAM_BATCH_AA_LIST, false, args, dim3(blocks), s);
 	}
 	/* (recorded even behind a failed launch, like the view records' event and for the same reason) */
 	const hipError_t e2 = hipEventRecord(S.done, s);
 	S.used = true;
 	S.d_counts = counts; S.n_views = n_views;
 	ctx->view_adaptive_last = si;
-	const int st = view_records_done(ctx, *V, s, e, what);
-	if (st != LOL_GPU_OK) return st;
+	LOL_TRY(view_records_done(ctx, *V, s, e, what));
 	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (adaptive batch)", e2);
 	return LOL_GPU_OK;
 }
@@ -1238,10 +1129,7 @@ int lol_gpu_render_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, int
 	if (!ctx || !cams || !dst) return LOL_GPU_ERR_ARG;
 	if (samples != 1 && samples != 2 && samples != 4) return fail(ctx, LOL_GPU_ERR_ARG, "samples per axis must be 1, 2 or 4");
 	if (contrast < -1 || contrast > 255) return fail(ctx, LOL_GPU_ERR_ARG, "adaptive contrast must be -1 (off) or 0 ... 255");
-	{
-		const int st = batch_refused(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(batch_refused(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
 	if (samples == 1) return render_views_plain(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
 	const bool adaptive = contrast >= 0;
 	if (!lol::samples_fit_wave(samples))
@@ -1263,26 +1151,14 @@ int lol_gpu_render_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, int
 	L.fw = (float)(samples * w); L.fh = (float)(samples * h);      /* the size of the sample grid */
 	L.flags |= samples == 4 ? lol::FLAG_SAMPLES_4 : lol::FLAG_SAMPLES_2;
 	hipStream_t s;
-	{
-		const int st = batch_stream(ctx, stream, &s);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(batch_stream(ctx, stream, &s));
 	if (adaptive) return render_views_adaptive(ctx, L, cams, n_views, samples, contrast, view_stride_bytes, dbg, s);
 	lol_gpu::ViewSet* S = nullptr;
-	{
-		const int st = queue_view_records(ctx, cams, n_views, max_steps, s, &S);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(queue_view_records(ctx, cams, n_views, max_steps, s, &S));
 	lol::BatchTail B = { S->d_views, (unsigned long long)(view_stride_bytes / 4) };
-	const size_t common = batch_common_lds(ctx);
 	batch_range("supersampled batch", n_views, w, h);
-	hipError_t e;
-	if (const SceneKernel* k = batch_aa_kernel(ctx)) {
-		void* args[] = { &L, &B };
-		e = hipModuleLaunchKernel(k->render_batch_aa, grid.x, grid.y, grid.z, lol::BLOCK, 1, 1, (unsigned)common, s, args, nullptr);
-	} else {
-		e = interp_batch_aa(ctx, L, B, nullptr, grid, common, s);
-	}
+	void* args[] = { &L, &B };
+	const hipError_t e = launch_family(ctx, FAM_BATCH_AA, false, args, grid, s);
 	if (g_roctx.pop) g_roctx.pop();
 	return view_records_done(ctx, *S, s, e, "kernel launch (supersampled batch of views)");
 }
@@ -1297,9 +1173,7 @@ int lol_gpu_view_samples(const lol_gpu* ctx) { return ctx ? ctx->view_samples : 
 
 const char* lol_gpu_view_samples_kernel_name(const lol_gpu* ctx, int samples, int contrast) {
 	if (!ctx) return "";
-	if (samples <= 1) return scene_kernel(ctx) && scene_kernel(ctx)->render_batch ? "lol_render_spec_batch" : "render_interp_batch";
-	if (contrast >= 0) return batch_aa_kernel(ctx) ? "lol_render_spec_batch_aa_list" : "render_interp_batch_aa_list";
-	return batch_aa_kernel(ctx) ? "lol_render_spec_batch_aa" : "render_interp_batch_aa";
+	return family_name(ctx, samples <= 1 ? FAM_BATCH : contrast >= 0 ? FAM_BATCH_AA_LIST : FAM_BATCH_AA);
 }
 
 int lol_gpu_interp_variant(lol_gpu* ctx, int* ssize, int* tables_global) {
@@ -1399,8 +1273,7 @@ int lol_gpu_render_host(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h,
 		LOL_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_frame), need));
 		ctx->frame_bytes = need;
 	}
-	int st = lol_gpu_render_device(ctx, cam, w, h, max_steps, nullptr, ctx->d_frame, (size_t)w * 4, nullptr, ctx->stream);
-	if (st != LOL_GPU_OK) return st;
+	LOL_TRY(lol_gpu_render_device(ctx, cam, w, h, max_steps, nullptr, ctx->d_frame, (size_t)w * 4, nullptr, ctx->stream));
 	LOL_HIP(ctx, hipMemcpy2DAsync(host_pixels, pitch_bytes, ctx->d_frame, (size_t)w * 4, (size_t)w * 4, h,
 	                              hipMemcpyDeviceToHost, ctx->stream));
 	LOL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1430,11 +1303,8 @@ int lol_gpu_render_host_begin(lol_gpu* ctx, const lol_frame_camera* cam, int w, 
 		return fail(ctx, LOL_GPU_ERR_ARG, depth == 2 ? "two frames already in flight: call lol_gpu_render_host_end first"
 		                                             : "every frame slot is in flight (lol_gpu_set_frames_in_flight): call lol_gpu_render_host_end first");
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	{
-		int st = ensure_copy_stream(ctx);
-		if (st == LOL_GPU_OK) st = ensure_frame_streams(ctx, (int)depth);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(ensure_copy_stream(ctx));
+	LOL_TRY(ensure_frame_streams(ctx, (int)depth));
 	const int slot = (int)(ctx->pipe_begun % lol_gpu::PIPE_SLOTS);
 	/* Which stream.  A frame whose view is NEW goes to the next stream of the rotation: it runs in a fixed tile order, its launch
 	 * has a long tail, and the frame after it fills that tail (the orbit through the C host: 9170 -> 11,000 Mpixels/s).  A frame
@@ -1462,8 +1332,7 @@ int lol_gpu_render_host_begin(lol_gpu* ctx, const lol_frame_camera* cam, int w, 
 	 * last wrote it, where that one ran on another stream (a frame that was discarded; a changed number of streams) */
 	LOL_HIP(ctx, hipStreamWaitEvent(ks, ctx->pipe_copied[slot], 0));
 	if (ctx->pipe_stream[slot] && ctx->pipe_stream[slot] != ks) LOL_HIP(ctx, hipStreamWaitEvent(ks, ctx->pipe_rendered[slot], 0));
-	int st = lol_gpu_render_device(ctx, cam, w, h, max_steps, nullptr, ctx->d_pipe[slot], (size_t)w * 4, nullptr, ks);
-	if (st != LOL_GPU_OK) return st;
+	LOL_TRY(lol_gpu_render_device(ctx, cam, w, h, max_steps, nullptr, ctx->d_pipe[slot], (size_t)w * 4, nullptr, ks));
 	LOL_HIP(ctx, hipEventRecord(ctx->pipe_rendered[slot], ks));
 	ctx->pipe_stream[slot] = ks;
 	ctx->pipe_last_stream = ks;
@@ -1526,15 +1395,9 @@ int lol_gpu_sync(lol_gpu* ctx) {
 int lol_gpu_set_frames_in_flight(lol_gpu* ctx, int n) {
 	if (!ctx || n < 1 || n > lol_gpu::MAX_FRAME_STREAMS) return LOL_GPU_ERR_ARG;
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	{
-		const int st = ensure_frame_streams(ctx, n);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(ensure_frame_streams(ctx, n));
 	/* a frame queued on a stream that is about to fall out of the rotation stays ordered before whatever comes next */
-	{
-		const int st = sync_own_streams(ctx);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(sync_own_streams(ctx));
 	ctx->n_frame_streams = n;
 	ctx->frame_rr = 0;
 	return LOL_GPU_OK;
@@ -1563,10 +1426,7 @@ int lol_gpu_free(lol_gpu* ctx, void* ptr) {
 int lol_gpu_memcpy_d2h(lol_gpu* ctx, void* host, const void* dev, size_t bytes) {
 	if (!ctx || !host || !dev) return LOL_GPU_ERR_ARG;
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	{
-		const int st = sync_own_streams(ctx);
-		if (st != LOL_GPU_OK) return st;
-	}
+	LOL_TRY(sync_own_streams(ctx));
 	LOL_HIP(ctx, hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
 	return LOL_GPU_OK;
 }
@@ -1597,7 +1457,7 @@ int lol_gpu_adaptive_samples(const lol_gpu* ctx) { return ctx ? ctx->adaptive : 
 
 /* the set of the context's last adaptive frame, waited for */
 static int last_adaptive_set(lol_gpu* ctx, lol_gpu::AdaptiveSet** out) {
-	if (ctx->adaptive_last < 0 || !ctx->adaptive_sets[ctx->adaptive_last].d_count)
+	if (ctx->adaptive_last < 0 || !ctx->adaptive_sets[ctx->adaptive_last].d_counts)
 		return fail(ctx, LOL_GPU_ERR_ARG, "no adaptive frame has been launched");
 	lol_gpu::AdaptiveSet& S = ctx->adaptive_sets[ctx->adaptive_last];
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
@@ -1609,10 +1469,9 @@ static int last_adaptive_set(lol_gpu* ctx, lol_gpu::AdaptiveSet** out) {
 int lol_gpu_adaptive_refined(lol_gpu* ctx, int64_t* n) {
 	if (!ctx || !n) return LOL_GPU_ERR_ARG;
 	lol_gpu::AdaptiveSet* S = nullptr;
-	const int st = last_adaptive_set(ctx, &S);
-	if (st != LOL_GPU_OK) return st;
+	LOL_TRY(last_adaptive_set(ctx, &S));
 	uint32_t c = 0;
-	LOL_HIP(ctx, hipMemcpy(&c, S->d_count, 4, hipMemcpyDeviceToHost));
+	LOL_HIP(ctx, hipMemcpy(&c, S->d_counts, 4, hipMemcpyDeviceToHost));
 	*n = c;
 	return LOL_GPU_OK;
 }
@@ -1620,8 +1479,7 @@ int lol_gpu_adaptive_refined(lol_gpu* ctx, int64_t* n) {
 int lol_gpu_adaptive_pass_ms(lol_gpu* ctx, float ms[3]) {
 	if (!ctx || !ms) return LOL_GPU_ERR_ARG;
 	lol_gpu::AdaptiveSet* S = nullptr;
-	const int st = last_adaptive_set(ctx, &S);
-	if (st != LOL_GPU_OK) return st;
+	LOL_TRY(last_adaptive_set(ctx, &S));
 	for (int i = 0; i < 3; i++) LOL_HIP(ctx, hipEventElapsedTime(&ms[i], S->ev[i], S->ev[i + 1]));
 	return LOL_GPU_OK;
 }
@@ -1633,7 +1491,7 @@ long lol_gpu_roctx_ranges(void) {
 
 const char* lol_gpu_kernel_key(const lol_gpu* ctx) {
 	if (!ctx) return "";
-	const SceneKernel* k = frame_kernel(ctx);
+	const SceneKernel* k = family_kernel(ctx, frame_family(ctx));
 	return k ? k->key.c_str() : ctx->samples > 1 ? ctx->interp_aa_key.c_str() : ctx->interp_key.c_str();
 }
 

@@ -127,19 +127,44 @@ struct OwnedProgram {
 	OwnedProgram& operator=(const OwnedProgram&) = delete;
 };
 
+/* The families of render kernels, each of which exists twice: as an instantiation of the interpreter (lol_kernel*.h) and as a symbol
+ * of the scene module (generate_source).  THE list: generate_source emits the symbols, load_scene_kernel looks them up, launch_family
+ * (lol_gpu.hip) launches one or the other and the reported kernel names come from here.  A new family is one row plus its kernel. */
+enum KernelFamily { FAM_FRAME, FAM_FRAME_AA, FAM_FRAME_AA_LIST, FAM_BATCH, FAM_BATCH_AA, FAM_BATCH_AA_LIST, N_FAMILIES };
+/* the switch of the context that puts a family into the module of the next upload */
+enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA };
+struct FamilyRow {
+	const char*  symbol;        /* in the scene module */
+	const char*  counting;      /* its twin with the per-lane step counters (modules up to LOL_SPEC_TWO_KERNELS_MAX_OPS ops), or none */
+	const char*  interp;        /* the interpreter's kernel, as lol_gpu_kernel_name reports it */
+	ModuleSwitch needs;
+};
+constexpr FamilyRow KERNEL_FAMILIES[N_FAMILIES] = {
+	/* FAM_FRAME         (L)              */ { "lol_render_spec",               "lol_render_spec_steps",       "render_interp",               SWITCH_NONE },
+	/* FAM_FRAME_AA      (L)              */ { "lol_render_spec_aa",            nullptr,                       "render_interp_aa",            SWITCH_AA },
+	/* FAM_FRAME_AA_LIST (L, list, count) */ { "lol_render_spec_aa_list",       nullptr,                       "render_interp_aa_list",       SWITCH_AA },
+	/* FAM_BATCH         (L, B)           */ { "lol_render_spec_batch",         "lol_render_spec_batch_steps", "render_interp_batch",         SWITCH_BATCH },
+	/* FAM_BATCH_AA      (L, B)           */ { "lol_render_spec_batch_aa",      nullptr,                       "render_interp_batch_aa",      SWITCH_BATCH_AA },
+	/* FAM_BATCH_AA_LIST (L, B, Q)        */ { "lol_render_spec_batch_aa_list", nullptr,                       "render_interp_batch_aa_list", SWITCH_BATCH_AA },
+};
+
+/* What a scene module carries beside lol_render_spec and lol_sdf_spec.  Without any of it the source is exactly what it was before
+ * these kernels existed.  aa: lol_gpu_set_samples > 1 at the upload; batch: lol_gpu_set_view_batches; batch_aa:
+ * lol_gpu_set_view_samples, which brings the plain batch kernels with it (the first pass of an adaptive batch is theirs). */
+struct ModuleKernels {
+	bool aa = false, batch = false, batch_aa = false;
+	bool carries(ModuleSwitch sw) const {
+		return sw == SWITCH_NONE || (sw == SWITCH_AA && aa) || (sw == SWITCH_BATCH && (batch || batch_aa)) || (sw == SWITCH_BATCH_AA && batch_aa);
+	}
+};
+
 /* One code object of the scene compiler, loaded with every kernel generate_source put in it or not at all (load_scene_kernel,
  * lol_tiers.hip).  A plain value: whoever holds it calls unload(). */
 struct SceneKernel {
 	hipModule_t   module = nullptr;
-	hipFunction_t render = nullptr;            /* lol_render_spec */
-	hipFunction_t render_counting = nullptr;   /* lol_render_spec_steps — or lol_render_spec where the module holds that one alone: it counts */
+	hipFunction_t fn[N_FAMILIES] = {};         /* by family; nullptr: the module was compiled without it, the interpreter renders that family */
+	hipFunction_t counting[N_FAMILIES] = {};   /* the family's counting twin — or fn[] again, where the module holds no twin of it: that one counts */
 	hipFunction_t sdf = nullptr;               /* lol_sdf_spec (lol_gpu_sdf_batch) */
-	hipFunction_t render_aa = nullptr;         /* lol_render_spec_aa, where the module was compiled with it (lol_gpu_set_samples) */
-	hipFunction_t render_aa_list = nullptr;    /* ... and lol_render_spec_aa_list beside it (the refine pass of adaptive frames) */
-	hipFunction_t render_batch = nullptr;      /* lol_render_spec_batch, where the module was compiled with it (lol_gpu_set_view_batches) */
-	hipFunction_t render_batch_counting = nullptr;   /* ... and lol_render_spec_batch_steps — or the former, where the module holds that one alone */
-	hipFunction_t render_batch_aa = nullptr;   /* lol_render_spec_batch_aa, where the module was compiled with it (lol_gpu_set_view_samples) */
-	hipFunction_t render_batch_aa_list = nullptr;    /* ... and lol_render_spec_batch_aa_list beside it (the refine pass of adaptive batches) */
 	std::string   key;                         /* FNV-1a of the code object (lol_gpu_kernel_key) */
 	explicit operator bool() const { return module != nullptr; }
 	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
@@ -229,30 +254,28 @@ struct lol_gpu {
 	static constexpr int VIEW_SETS = 8;
 	ViewSet      view_sets[VIEW_SETS];
 	unsigned     view_rr = 0;
-	/* Scratch of adaptive frames (render_adaptive, lol_gpu.hip): a ring of sets, one per frame, whatever its stream.  A frame waits
-	 * on its set's `ev[3]` (behind the last frame that used it) with hipStreamWaitEvent and records it again at its end; ev[0] marks
-	 * its start, ev[1] and ev[2] the ends of its first two passes (lol_gpu_adaptive_pass_ms).  Sets grow with the frame, freed in
-	 * lol_gpu_destroy. */
-	struct AdaptiveSet {
-		uint32_t*  d_buf = nullptr;          /* plain xrgb [w h] | ids [w h] | list [w h] | count [64] | lane table [64 per refine block] */
+	/* Scratch of adaptive frames and batches: two rings of sets, one set per frame or batch, whatever its stream; sets grow with what
+	 * they serve (grow_scratch, lol_gpu.hip), freed in lol_gpu_destroy */
+	struct ScratchSet {
+		uint32_t*  d_buf = nullptr;
 		size_t     bytes = 0;
-		uint32_t*  d_count = nullptr;        /* the list's length of the set's last frame */
+		uint32_t*  d_counts = nullptr;       /* in d_buf: the length(s) of the list(s) of the set's last frame or batch */
+		bool       used = false;             /* the event that ends the set's last use has been recorded */
+	};
+	/* ... of frames (render_adaptive): xrgb [w h] | ids [w h] | list [w h] | count [64] | lane table [64 per refine block].  A frame
+	 * waits on its set's `ev[3]` (behind the last frame that used it) with hipStreamWaitEvent and records it again at its end; ev[0]
+	 * marks its start, ev[1] and ev[2] the ends of its first two passes (lol_gpu_adaptive_pass_ms). */
+	struct AdaptiveSet : ScratchSet {
 		hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-		bool       used = false;             /* ev[] have been recorded */
 	};
 	static constexpr int ADAPTIVE_SETS = 4;
 	AdaptiveSet  adaptive_sets[ADAPTIVE_SETS];
-	/* Scratch of adaptive batches (render_views_adaptive, lol_gpu.hip): a ring of its own, one set per batch, whatever its stream;
-	 * a batch waits on its set's `done` (behind the last batch that used it) and records it again at its end.  For n views of
-	 * w x h: 12 n w h bytes (plain pixels, ids, lists) + 8 (n + 1) (counts, group prefix) + 256 per refine block (the lane table).
-	 * Sets grow with the batch, freed in lol_gpu_destroy. */
-	struct ViewAdaptiveSet {
-		uint32_t*  d_buf = nullptr;          /* xrgb [n w h] | ids [n w h] | lists [n w h] | counts [n + 1] | prefix [n + 1] | lane table */
-		size_t     bytes = 0;
-		uint32_t*  d_counts = nullptr;       /* the lists' lengths of the set's last batch, and how many views it had */
-		int        n_views = 0;
+	/* ... of batches (render_views_adaptive), a ring of its own: xrgb [n w h] | ids [n w h] | lists [n w h] | counts [n + 1] |
+	 * prefix [n + 1] | lane table — for n views of w x h: 12 n w h bytes + 8 (n + 1) + 256 per refine block.  A batch waits on its
+	 * set's `done` (behind the last batch that used it) and records it again at its end. */
+	struct ViewAdaptiveSet : ScratchSet {
+		int        n_views = 0;              /* how many views the set's last batch had: d_counts holds that many */
 		hipEvent_t done = nullptr;
-		bool       used = false;             /* `done` has been recorded */
 	};
 	static constexpr int VIEW_ADAPTIVE_SETS = 4;
 	ViewAdaptiveSet view_adaptive_sets[VIEW_ADAPTIVE_SETS];
@@ -365,6 +388,12 @@ int fail(lol_gpu* ctx, int status, const char* what, hipError_t e = hipSuccess);
 		hipError_t e_ = (call);                                                   \
 		if (e_ != hipSuccess) return fail((ctx), LOL_GPU_ERR_HIP, #call, e_);     \
 	} while (0)
+/* ... and for a step that reports a status of its own */
+#define LOL_TRY(expr)                                                             \
+	do {                                                                          \
+		const int st_ = (expr);                                                   \
+		if (st_ != LOL_GPU_OK) return st_;                                        \
+	} while (0)
 
 /* operand-stack entries under the accumulator a program needs → the instantiation that has them */
 constexpr int interp_stack_class(uint32_t max_stack) {
@@ -408,12 +437,8 @@ float smooth_sat_threshold(float k);
 /* ---- lol_codegen.hip */
 inline bool culling_enabled(int want) { return want != 0; }      /* (lol_gpu_set_cull) */
 bool spec_out_of_line(const lol_program& P, int form = SPEC_BY_SIZE);
-/* aa: the module also carries lol_render_spec_aa (the context asked for supersampling before the upload); without it the source
- * is exactly what it was before supersampling existed; batch: ... and lol_render_spec_batch (lol_gpu_set_view_batches), likewise;
- * batch_aa: ... and lol_render_spec_batch_aa / _aa_list (lol_gpu_set_view_samples; implies batch), likewise */
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
-                  std::string& log, std::string* src_out = nullptr, bool cull = true, int form = SPEC_BY_SIZE, bool aa = false,
-                  bool batch = false, bool batch_aa = false);
+                  std::string& log, std::string* src_out = nullptr, bool cull = true, int form = SPEC_BY_SIZE, ModuleKernels carries = {});
 /* the interpreter's two macro-op lists for `P`, one after the other (with / without v_div_fixup in the proven blend factors);
  * false: the two differ in length (cannot happen: same records by construction) */
 bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, std::vector<uint32_t>& lists, uint32_t& n_mops);

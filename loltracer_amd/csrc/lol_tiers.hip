@@ -24,9 +24,7 @@ struct SpecJob {
 	std::string arch;
 	bool cull = true;
 	int form = SPEC_BY_SIZE;
-	bool aa = false;                   /* the module carries lol_render_spec_aa as well */
-	bool batch = false;                /* ... and lol_render_spec_batch (lol_gpu_set_view_batches) */
-	bool batch_aa = false;             /* ... and lol_render_spec_batch_aa / _aa_list, and the former with them (lol_gpu_set_view_samples) */
+	ModuleKernels carries;             /* what the module holds beside the frame kernel */
 	BigStackThread th;
 	/* A run is never left behind: hipRTC cannot be interrupted, and a thread still inside it when the process exits crashes in the
 	 * compiler's own teardown (comgr is loaded on first use, so its statics go BEFORE this library's: with a process-lifetime
@@ -62,7 +60,7 @@ void launch_job(SpecJob* job) {
 		std::string log;
 		try {
 			std::lock_guard<std::mutex> rtc(g_rtc_mutex);
-			ok = compile_spec(job->prog->p, job->fast.get(), job->arch, code, log, nullptr, job->cull, job->form, job->aa, job->batch, job->batch_aa);
+			ok = compile_spec(job->prog->p, job->fast.get(), job->arch, code, log, nullptr, job->cull, job->form, job->carries);
 		} catch (...) { ok = false; log = "the scene compiler ran out of memory"; }
 		std::lock_guard<std::mutex> lock(job->mu);
 		job->compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - job->started).count();
@@ -80,9 +78,9 @@ void launch_job(SpecJob* job) {
 	else if (!threaded) job->th.join();
 }
 
-/* All or nothing: the module with every kernel generate_source emits for a program of n_ops ops, or `why` not.  A failed call
- * leaves its error behind as the thread's last error, which the host's next HIP call would trip over: cleared. */
-bool load_scene_kernel(const std::vector<char>& code, uint32_t n_ops, bool aa, bool batch, bool batch_aa, SceneKernel& k, std::string& why) {
+/* All or nothing: the module with every kernel generate_source emits for a program of n_ops ops and those switches, or `why` not.
+ * A failed call leaves its error behind as the thread's last error, which the host's next HIP call would trip over: cleared. */
+bool load_scene_kernel(const std::vector<char>& code, uint32_t n_ops, ModuleKernels carries, SceneKernel& k, std::string& why) {
 	auto get = [&](hipFunction_t& fn, const char* name) {
 		if (hipModuleGetFunction(&fn, k.module, name) == hipSuccess) return true;
 		why = std::string(name) + " not found in the compiled module";
@@ -90,14 +88,17 @@ bool load_scene_kernel(const std::vector<char>& code, uint32_t n_ops, bool aa, b
 	};
 	const bool two = n_ops <= LOL_SPEC_TWO_KERNELS_MAX_OPS;
 	k.key = fnv_hex(code.data(), code.size());
-	if (hipModuleLoadData(&k.module, code.data()) != hipSuccess) why = "hipModuleLoadData failed";
-	else if (get(k.render, "lol_render_spec") && (!two || get(k.render_counting, "lol_render_spec_steps")) && get(k.sdf, "lol_sdf_spec") &&
-	         (!aa || (get(k.render_aa, "lol_render_spec_aa") && get(k.render_aa_list, "lol_render_spec_aa_list"))) &&
-	         (!batch || (get(k.render_batch, "lol_render_spec_batch") && (!two || get(k.render_batch_counting, "lol_render_spec_batch_steps")))) &&
-	         (!batch_aa || (get(k.render_batch_aa, "lol_render_spec_batch_aa") && get(k.render_batch_aa_list, "lol_render_spec_batch_aa_list")))) {
-		if (!two) { k.render_counting = k.render; k.render_batch_counting = k.render_batch; }
-		return true;
+	bool ok = hipModuleLoadData(&k.module, code.data()) == hipSuccess;
+	if (!ok) why = "hipModuleLoadData failed";
+	ok = ok && get(k.sdf, "lol_sdf_spec");
+	for (int f = 0; ok && f < N_FAMILIES; f++) {
+		const FamilyRow& row = KERNEL_FAMILIES[f];
+		if (!carries.carries(row.needs)) continue;
+		ok = get(k.fn[f], row.symbol);
+		if (ok && two && row.counting) ok = get(k.counting[f], row.counting);
+		else k.counting[f] = k.fn[f];                  /* (no twin in the module: the kernel itself counts, or nobody asks it to) */
 	}
+	if (ok) return true;
 	k.unload();
 	(void)hipGetLastError();
 	return false;
@@ -112,7 +113,7 @@ Outcome outcome_of(SpecTiers& T, const SpecJob& job) {
 		T.fail_first--;
 		o.why = "injected failure of the first run (lol_gpu_testing_fail_first_tier)";
 	} else if (!job.ok) o.why = job.log;
-	else load_scene_kernel(job.code, job.prog->p.n_ops, job.aa, job.batch || job.batch_aa, job.batch_aa, o.kernel, o.why);
+	else load_scene_kernel(job.code, job.prog->p.n_ops, job.carries, o.kernel, o.why);
 	return o;
 }
 
@@ -122,7 +123,7 @@ bool start_second_tier(SpecTiers& T, const SpecJob& first) {
 	std::unique_ptr<SpecJob> next;
 	try {
 		next = std::make_unique<SpecJob>();
-		next->prog = first.prog; next->fast = first.fast; next->arch = first.arch; next->cull = first.cull; next->aa = first.aa; next->batch = first.batch; next->batch_aa = first.batch_aa;
+		next->prog = first.prog; next->fast = first.fast; next->arch = first.arch; next->cull = first.cull; next->carries = first.carries;
 		next->form = SPEC_INLINE;
 	} catch (...) { return false; }
 	T.job = std::move(next);
@@ -217,9 +218,8 @@ void start_specialise(lol_gpu* ctx, const FastPaths& fast) {
 		if (!sw.empty()) job->note += "tuning switches in effect (LOL_GPU_TUNING=1): " + sw + "\n";
 	} catch (...) { T.log = "out of host memory"; return; }
 	job->cull = culling_enabled(ctx->want_cull);
-	job->aa = ctx->samples > 1;                      /* (samples asked for after the upload render on render_interp_aa) */
-	job->batch = ctx->view_batches != 0;             /* (batches asked for after the upload render on render_interp_batch) */
-	job->batch_aa = ctx->view_samples != 0;          /* (... supersampled ones on render_interp_batch_aa / _aa_list) */
+	/* (what is asked for after the upload renders on the interpreter's kernel of that family) */
+	job->carries = { ctx->samples > 1, ctx->view_batches != 0, ctx->view_samples != 0 };
 	/* (LOL_GPU_SPEC_INLINE_MAX, a tuning switch, pins ONE form by size) */
 	const bool first_tier = !tuning_env("LOL_GPU_SPEC_INLINE_MAX") && ctx->h_prog.n_ops > LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS &&
 	                        ctx->h_prog.n_ops <= LOL_SPEC_INLINE_MAX_OPS;

@@ -172,3 +172,29 @@ def test_the_new_kernels_have_no_scalar_stores_and_the_scratch_stated(tmp_path, 
             k = notes[kernel]
             assert int(k["private_segment_fixed_size"]) <= SCRATCH_STATED[kernel] <= int(ref["private_segment_fixed_size"]), (name, kernel, k)
             assert int(k["vgpr_count"]) <= 64, (name, kernel, k)
+
+
+def test_every_kernel_of_the_module_has_its_own_argument_list_and_body(tmp_path, scenes):
+    """The symbols come from one table of kernel families (lol_gpu_internal.h, KERNEL_FAMILIES), which the host also launches by: a
+    row with another row's symbol would hand a kernel the wrong arguments.  Each symbol heads the argument list of its family, and
+    what tells its body from its neighbours' follows before the next kernel."""
+    prog = scenes["scene4"].flatten()
+    both, aa = str(tmp_path / "both"), str(tmp_path / "aa")
+    gpu.compile_offline_view_samples(prog, both)
+    gpu.compile_offline_samples(prog, aa, 2)
+    src = read(both + ".hip") + read(aa + ".hip")
+    L, B = "const lol::Launch L", "const lol::BatchTail B"
+    expect = {
+        "lol_render_spec_steps": ("(%s)" % L, "lol_spec_body<true>(L, lds)"),
+        "lol_render_spec": ("(%s)" % L, "lol_spec_body<false>(L, lds)"),
+        "lol_render_spec_aa": ("(%s)" % L, "lol::store_pixel_aa<"),
+        "lol_render_spec_aa_list": ("(%s, const lol::u32* list, const lol::u32* count)" % L, "lol::render_aa_list<"),
+        "lol_render_spec_batch_steps": ("(%s, %s)" % (L, B), "lol_spec_batch_body<true>(L, B, lds)"),
+        "lol_render_spec_batch": ("(%s, %s)" % (L, B), "lol_spec_batch_body<false>(L, B, lds)"),
+        "lol_render_spec_batch_aa": ("(%s, %s)" % (L, B), "lol::store_pixel_view_aa("),
+        "lol_render_spec_batch_aa_list": ("(%s, %s, const lol::BatchLists Q)" % (L, B), "lol::render_aa_view_lists<"),
+    }
+    for symbol, (args, mark) in expect.items():
+        at = src.index("void %s%s {" % (symbol, args))
+        body = src[at:src.find('extern "C"', at + 1) if src.find('extern "C"', at + 1) > 0 else len(src)]
+        assert mark in body, symbol
