@@ -322,6 +322,48 @@ int         lol_gpu_render_views_samples(lol_gpu* ctx, const lol_frame_camera* c
 int         lol_gpu_set_view_samples(lol_gpu* ctx, int enable);
 int         lol_gpu_view_samples(const lol_gpu* ctx);
 
+/*
+ * Views averaged over CAMERAS: motion blur (the cameras of a frame's exposure) and depth of field (cameras on a lens).  The modes
+ * above average over the pixel's area; this one averages K = cams_per_view frames of the same size under K cameras, in linear
+ * light.  `cams` holds n_views * K cameras; view v uses cams[v * K + k], k = 0 ... K - 1; K in {1, 2, 4, 8, 16}.
+ * Pixel (x, y) of view v:
+ *   1. sample k is pixel (x, y) of the reference's w x h frame under cams[v * K + k]: the clamped LINEAR colour get_light() returns,
+ *      before gamma (what lol_gpu_set_samples calls a sample);
+ *   2. the K samples, in order of k, are summed per channel in binary32 as a balanced binary tree — K = 2: (v0 + v1); K = 4:
+ *      (v0 + v1) + (v2 + v3); ... up to four levels deep — and the sum is multiplied by 1 / K;
+ *   3. the mean goes through gamma and the context's pixel format exactly as one sample's colour does.
+ * So K = 1 IS lol_gpu_render_views, with all its diagnostics, and K equal cameras give that camera's plain view bit for bit
+ * (doubling and a power-of-two scale are exact on [0, 1]).  Averaging the packed 8-bit pixels of K views on the host is NOT this:
+ * that mean is taken after gamma and after quantisation.
+ * Addressing, `cams` (host memory, copied before the call returns), `stream`, the ring of 8 record sets, the fixed tile order and
+ * "neither uses nor changes LOL_GPU_TILES_LPT / _AUTO": all as lol_gpu_render_views.  What lol_gpu_render_views decides per view
+ * from its camera — the primary march's first step, what a camera beyond the sane range switches off — is decided per RECORD: a
+ * group may mix sane and insane cameras.  The call neither reads nor changes lol_gpu_set_samples / lol_gpu_set_adaptive_samples.
+ * With K > 1 lol_gpu_debug.rgb is the mean after gamma, dense [v][y][x]; hit_dist, hit_id and steps are refused
+ * (LOL_GPU_ERR_UNSUPPORTED), as for any averaged pixel.
+ * A blend with K > 1 is one copy of the n_views * K records and two launches on its stream with no host wait: every camera's linear
+ * colours (the K cameras of a view are K times as many independent blocks, which is what fills the device for one or a few small
+ * views), then the means.  The colours go through scratch — 16 bytes per ray, 16 * n_views * K * w * h bytes per call (12 of colour
+ * and 4 of padding: one 16-byte store per lane) — from a ring of 4 sets that grow on demand and live as long as the context: a fifth
+ * blend in flight queues behind the first (on one of HIP's special stream handles the host waits for it instead).  A scratch
+ * allocation that fails returns LOL_GPU_ERR_HIP, nothing launched, and the context stays usable.
+ * Refused with LOL_GPU_ERR_ARG, nothing launched and nothing written: K outside {1, 2, 4, 8, 16}; n_views * K > LOL_GPU_MAX_VIEWS;
+ * everything lol_gpu_render_views refuses (except lol_gpu_samples() > 1), its limit of 2^32 - 1 lanes applied to all n_views * K frames.
+ * Which kernel: after lol_gpu_set_view_blends(ctx, 1) BEFORE lol_gpu_upload_program the scene's own module also carries
+ * lol_render_spec_batch_lin (both kernels of a 257 ... 1024-op scene do); otherwise, and until that module is ready, the
+ * interpreter's render_interp_batch_lin renders — same pixels either way (lol_gpu_view_blend_kernel_name, lol_gpu_diag.h).  A
+ * module compiled without the switch is the module it was before (same code object, same lol_gpu_kernel_key).
+ * Not built: supersampled blends (samples per pixel AND cameras per view), row partitions, a lol_gpu_multi_* form (stripe the
+ * views over the devices, one context each), host surfaces, and the renderer.h protocol, which has one camera per frame.
+ */
+#define LOL_GPU_MAX_BLEND 16
+int         lol_gpu_render_views_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view,
+                                       int w, int h, int max_steps,
+                                       void* dst, size_t pitch_bytes, size_t view_stride_bytes,
+                                       const lol_gpu_debug* dbg, void* stream);
+int         lol_gpu_set_view_blends(lol_gpu* ctx, int enable);
+int         lol_gpu_view_blends(const lol_gpu* ctx);
+
 /* Name of the kernel a launch uses (for matching rocprofv3 kernel-trace rows):
  * "lol_render_spec" (scene-specialised, compiled by hipRTC at upload) or "render_interp"; with supersampling
  * (lol_gpu_set_samples) "lol_render_spec_aa" or "render_interp_aa"; for adaptive frames (lol_gpu_set_adaptive_samples) the

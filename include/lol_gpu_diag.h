@@ -93,6 +93,19 @@ int         lol_gpu_compile_offline_views(const lol_program* prog, const char* a
  */
 int         lol_gpu_compile_offline_view_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                                  int enable, int form, char* log, size_t logcap);
+/*
+ * ... and for a context that asked for blends of views (lol_gpu_set_view_blends) before its upload: enable = 0 writes exactly what
+ * lol_gpu_compile_offline writes; 1 the same source with lol_render_spec_batch_lin appended, and its code object.  form as above.
+ * `enable` is a mask, so that the module of a context with several switches set can be inspected too: 1 = lol_gpu_set_view_blends,
+ * 2 = lol_gpu_set_samples > 1, 4 = lol_gpu_set_view_batches, 8 = lol_gpu_set_view_samples — the kernels of each, in the order the
+ * scene compiler appends them, the linear kernel last.  LOL_GPU_ERR_ARG outside 0 ... 15.  Needs no device.
+ */
+int         lol_gpu_compile_offline_view_blends(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                                int enable, int form, char* log, size_t logcap);
+/* The kernel the first pass of the NEXT lol_gpu_render_views_blend(..., cams_per_view, ...) of this context launches, decided by
+ * the test the launch itself makes: "lol_render_spec_batch_lin" / "render_interp_batch_lin"; lol_gpu_render_views' for
+ * cams_per_view = 1.  (The second pass is always the library's own blend_resolve.) */
+const char* lol_gpu_view_blend_kernel_name(const lol_gpu* ctx, int cams_per_view);
 /* The kernel the NEXT lol_gpu_render_views_samples(..., samples, contrast, ...) of this context launches, decided by the test the
  * launch itself makes: "lol_render_spec_batch_aa" / "render_interp_batch_aa" for contrast = -1, the refine pass's
  * "lol_render_spec_batch_aa_list" / "render_interp_batch_aa_list" for an adaptive batch, lol_gpu_render_views' for samples = 1.

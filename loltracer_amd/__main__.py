@@ -1,10 +1,14 @@
 """python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N] [--samples N]
-                          [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]]]
+                          [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]] [--orbit-shutter K]]
+                          [--lens R --focus D --lens-samples K]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
 (Renderer.render_views_into) and writes DIR/view_0000.ppm ...; --orbit-samples N supersamples the views of that batch (N x N samples
-per pixel; with --orbit-adaptive T only at the edges of each view).  There is no CPU rendering path."""
+per pixel; with --orbit-adaptive T only at the edges of each view); --orbit N --orbit-shutter K blurs each of the N views by the motion
+inside its own exposure: view v is the mean in linear light of cameras v K ... v K + K - 1 of scene.orbit_cameras(scene, N K)
+(Renderer.render_blended_views_into).  --lens R --focus D --lens-samples K renders ONE frame with depth of field: the mean over the K
+cameras of scene.lens_cameras on a lens of radius R focused at distance D.  There is no CPU rendering path."""
 from __future__ import annotations
 
 import argparse
@@ -26,19 +30,24 @@ def write_ppm(path, surf):
 
 def orbit(sc, args, w, h) -> int:
     """K views of one batch into K PPMs"""
-    k = args.orbit
+    k, shutter = args.orbit, args.orbit_shutter
     r = gpu.Renderer(args.device)
     try:
         r.set_view_batches(True)             # before prepare(): the scene's own kernel then carries the batch form
         if args.orbit_samples > 1:
             r.set_view_samples(True)         # ... and the supersampled batch forms
+        if shutter > 1:
+            r.set_view_blends(True)          # ... and the linear-colour form of blends
         r.prepare(sc)
         views = np.zeros((k, h, w), dtype=np.uint32)
         dev = r.malloc(views.nbytes)
         try:
             t0 = time.perf_counter()
-            r.render_views_into(dev, S.orbit_cameras(sc, k), w, h, args.max_steps, samples=args.orbit_samples,
-                                adaptive=args.orbit_adaptive if args.orbit_samples > 1 else -1)
+            if shutter > 1:
+                r.render_blended_views_into(dev, S.orbit_cameras(sc, k * shutter), shutter, w, h, args.max_steps)
+            else:
+                r.render_views_into(dev, S.orbit_cameras(sc, k), w, h, args.max_steps, samples=args.orbit_samples,
+                                    adaptive=args.orbit_adaptive if args.orbit_samples > 1 else -1)
             r.sync()
             dt = (time.perf_counter() - t0) * 1e3
             r.memcpy_d2h(views.ctypes.data, dev, views.nbytes)
@@ -50,6 +59,31 @@ def orbit(sc, args, w, h) -> int:
     os.makedirs(args.out, exist_ok=True)
     for v in range(k):
         write_ppm(os.path.join(args.out, f"view_{v:04d}.ppm"), views[v])
+    return 0
+
+
+def lens(sc, args, w, h) -> int:
+    """one frame averaged over the cameras of a lens into one PPM"""
+    r = gpu.Renderer(args.device)
+    try:
+        r.set_view_blends(True)
+        r.prepare(sc)
+        surf = np.zeros((h, w), dtype=np.uint32)
+        dev = r.malloc(surf.nbytes)
+        try:
+            t0 = time.perf_counter()
+            r.render_blended_views_into(dev, S.lens_cameras(sc.camera, args.focus, args.lens, args.lens_samples), args.lens_samples,
+                                        w, h, args.max_steps)
+            r.sync()
+            dt = (time.perf_counter() - t0) * 1e3
+            r.memcpy_d2h(surf.ctypes.data, dev, surf.nbytes)
+        finally:
+            r.free(dev)
+    finally:
+        r.close()
+    print(f"{w}x{h} over {args.lens_samples} lens cameras: {dt:.3f}ms")
+    if args.out:
+        write_ppm(args.out, surf)
     return 0
 
 
@@ -70,6 +104,12 @@ def main(argv=None) -> int:
                     help="with --orbit: N x N samples per pixel in every view of the batch")
     ap.add_argument("--orbit-adaptive", type=int, default=-1, metavar="T",
                     help="with --orbit-samples N: N x N samples only at edges of each view (contrast T, 0 ... 255)")
+    ap.add_argument("--orbit-shutter", type=int, default=1, choices=(1, 2, 4, 8, 16), metavar="K",
+                    help="with --orbit N: every view is the mean of K cameras of its own exposure (motion blur)")
+    ap.add_argument("--lens", type=float, default=0.0, metavar="R", help="depth of field: the radius of the lens (with --focus)")
+    ap.add_argument("--focus", type=float, default=0.0, metavar="D", help="with --lens: the distance that stays sharp")
+    ap.add_argument("--lens-samples", type=int, default=16, choices=(1, 2, 4, 8, 16), metavar="K",
+                    help="with --lens: cameras on the lens")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     try:
@@ -88,10 +128,21 @@ def main(argv=None) -> int:
         if args.orbit_adaptive < -1 or args.orbit_adaptive > 255:
             print("--orbit-adaptive takes a contrast 0 ... 255", file=sys.stderr)
             return 1
+        if args.lens:
+            print("--orbit does not go with --lens: the lens mode renders one frame", file=sys.stderr)
+            return 1
+        if args.orbit_shutter > 1 and (args.orbit_samples != 1 or args.orbit * args.orbit_shutter > gpu.MAX_VIEWS):
+            print(f"--orbit N --orbit-shutter K takes N K <= {gpu.MAX_VIEWS} cameras; not with --orbit-samples", file=sys.stderr)
+            return 1
         return orbit(sc, args, w, h)
-    if args.orbit_samples != 1 or args.orbit_adaptive != -1:
-        print("--orbit-samples and --orbit-adaptive go with --orbit K", file=sys.stderr)
+    if args.orbit_samples != 1 or args.orbit_adaptive != -1 or args.orbit_shutter != 1:
+        print("--orbit-samples, --orbit-adaptive and --orbit-shutter go with --orbit K", file=sys.stderr)
         return 1
+    if args.lens:
+        if args.lens < 0 or not args.focus > 0 or args.samples != 1 or args.adaptive != -1 or args.frames != 1:
+            print("--lens R takes a radius > 0 and --focus D > 0; not with --samples, --adaptive or --frames", file=sys.stderr)
+            return 1
+        return lens(sc, args, w, h)
     r = gpu.Renderer(args.device)
     r.set_samples(args.samples)          # before prepare(): the scene's own kernel then carries the supersampling form
     if args.adaptive != -1:

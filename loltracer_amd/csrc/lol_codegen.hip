@@ -6,7 +6,7 @@
  */
 #include "lol_gpu_internal.h"
 
-/* lol_kernel.h's, lol_kernel_aa.h's, lol_kernel_batch.h's and lol_kernel_batch_aa.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
+/* lol_kernel.h's, lol_kernel_aa.h's, lol_kernel_batch.h's, lol_kernel_batch_aa.h's and lol_kernel_blend.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
 #include "lol_kernel_src.inc"
 
 #pragma GCC visibility push(hidden)
@@ -872,6 +872,17 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 		s += "\t});\n";
 		s += "}\n";
 	}
+	/* Views averaged over K cameras (lol_gpu_set_view_blends before the upload): the batch pipeline on the launch of the block's
+	 * record, the clamped LINEAR colour stored into the blend's scratch instead of a packed pixel (lol_kernel_blend.h).  Appended
+	 * after everything else, for the reason above.  No step counters. */
+	if (carries.carries(SWITCH_BATCH_BLEND)) {
+		s += "#include \"lol_kernel_blend.h\"\n";
+		s += head + K[FAM_BATCH_LIN].symbol + "(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
+		s += "\tconst lol::Launch S = lol::view_launch(L, B.views);\n";
+		s += shade("\t", "S", "S", "false", "");
+		s += "\tlol::store_linear_view(L, P.rgb);\n";
+		s += "}\n";
+	}
 	return s;
 }
 
@@ -991,6 +1002,7 @@ bool has_return_clobbering_branch(const std::vector<char>& code) { return has_re
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
                   std::string& log, std::string* src_out, bool cull, int form, ModuleKernels carries) {
 	const bool aa = carries.carries(SWITCH_AA), batch = carries.carries(SWITCH_BATCH), batch_aa = carries.carries(SWITCH_BATCH_AA);
+	const bool blend = carries.carries(SWITCH_BATCH_BLEND);
 	std::string src = generate_source(P, fast, cull, form, carries);
 	if (src_out) *src_out = src;
 	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
@@ -1055,7 +1067,8 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	 * library must not pick up this one's kernels */
 	const std::string disk_key = key + "|" + LOL_KERNEL_H_TEXT + (aa ? std::string("|") + LOL_KERNEL_AA_H_TEXT : std::string()) +
 	                             (batch ? std::string("|batch|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT : std::string()) +
-	                             (batch_aa ? std::string("|batch_aa|") + LOL_KERNEL_BATCH_AA_H_TEXT : std::string());
+	                             (batch_aa ? std::string("|batch_aa|") + LOL_KERNEL_BATCH_AA_H_TEXT : std::string()) +
+	                             (blend ? std::string("|blend|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT + "|" + LOL_KERNEL_BLEND_H_TEXT : std::string());
 	if (disk_cache_load(disk_key, code)) {
 		std::lock_guard<std::mutex> lock(g_cache_mutex);
 		g_code_cache[key] = code;
@@ -1065,9 +1078,16 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	/* lol_kernel_aa.h only where the source includes it: hipRTC's compilation-unit id — bytes of the code object — follows the headers */
 	/* ... and lol_kernel_batch.h (which includes lol_kernel_aa.h for pack_pixel) only where the module carries the batch kernel */
 	/* ... and lol_kernel_batch_aa.h (which includes lol_kernel_batch.h) only where it carries the supersampled batch kernels */
-	const char* hdr_src[] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT };
-	const char* hdr_name[] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h" };
-	const int n_hdr = batch_aa ? 4 : batch ? 3 : aa ? 2 : 1;
+	/* ... and lol_kernel_blend.h (which includes lol_kernel_batch.h) only where it carries the linear-colour batch kernel: last, so
+	 * that a module without it is handed the very list it was handed before that file existed */
+	const char* hdr_src[5] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT, nullptr };
+	const char* hdr_name[5] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h", nullptr };
+	int n_hdr = batch_aa ? 4 : batch ? 3 : aa ? 2 : 1;
+	if (blend) {
+		n_hdr = std::max(n_hdr, 3);
+		hdr_src[n_hdr] = LOL_KERNEL_BLEND_H_TEXT; hdr_name[n_hdr] = "lol_kernel_blend.h";
+		n_hdr++;
+	}
 	hiprtcProgram prog = nullptr;
 	if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_hdr, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
 		log = "hiprtcCreateProgram failed";
@@ -1205,6 +1225,16 @@ int lol_gpu_compile_offline_view_samples(const lol_program* prog, const char* ar
                                          int form, char* log, size_t logcap) {
 	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
 	return compile_offline(prog, arch, out_base, assume_fast, { false, false, enable != 0 }, form, log, logcap);
+}
+
+/* ... and the module a context with lol_gpu_set_view_blends(ctx, 1) compiles at its upload (lol_gpu_diag.h) */
+int lol_gpu_compile_offline_view_blends(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                        int form, char* log, size_t logcap) {
+	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
+	if (enable < 0 || enable > 15) return LOL_GPU_ERR_ARG;
+	/* bit 0: lol_gpu_set_view_blends; bits 1 - 3: the context's other switches beside it (samples > 1, view batches, view samples) */
+	return compile_offline(prog, arch, out_base, assume_fast, { (enable & 2) != 0, (enable & 4) != 0, (enable & 8) != 0, (enable & 1) != 0 },
+	                       form, log, logcap);
 }
 
 static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, ModuleKernels carries,

@@ -98,6 +98,7 @@ const void* interp_kernel(KernelFamily f) {
 	case FAM_BATCH:         return reinterpret_cast<const void*>(&lol::render_interp_batch<SSIZE, KIND, TABLES_GLOBAL>);
 	case FAM_BATCH_AA:      return reinterpret_cast<const void*>(&lol::render_interp_batch_aa<SSIZE, KIND, TABLES_GLOBAL>);
 	case FAM_BATCH_AA_LIST: return reinterpret_cast<const void*>(&lol::render_interp_batch_aa_list<SSIZE, KIND, TABLES_GLOBAL>);
+	case FAM_BATCH_LIN:     return reinterpret_cast<const void*>(&lol::render_interp_batch_lin<SSIZE, KIND, TABLES_GLOBAL>);
 	default:                return nullptr;
 	}
 }
@@ -421,6 +422,47 @@ __global__ __launch_bounds__(64) void view_group_prefix(const uint32_t* counts, 
 	if (lane == 63u) prefix[n_views] = upto;
 }
 
+/*
+ * Views averaged over K cameras (lol_gpu_render_views_blend), pass 2: one lane per output pixel, a 16 x 4 tile per wave, the view in
+ * the grid's z.  `lin`: pass 1's linear colours, dense [v K + k][y][x] (lol_kernel_blend.h).  The pixel's K colours are summed per
+ * channel in binary32 as a balanced binary tree in order of k — (c0 + c1) + (c2 + c3) ... — and the sum is multiplied by 1 / K; the
+ * mean goes through gamma and the pixel format as one sample's colour does (pack_pixel), to the view's address, and after gamma
+ * to the dense diagnostic.  Bytes between rows and between views are not written.
+ */
+struct BlendOut {
+	uint32_t* dst; uint32_t pitch_px; unsigned long long view_stride_px;
+	uint32_t fmt_shift, fmt_loss, fmt_amask, flags;       /* flags: FLAG_GAMMA_TABLE or 0 */
+	float* dbg_rgb; const float* gamma_table;
+};
+template <int K>
+__global__ __launch_bounds__(64) void blend_resolve(const lol::LinearColour* lin, int w, int h, const BlendOut O) {
+	const int lane = threadIdx.x;
+	const int x = blockIdx.x * CLASSIFY_W + lane % CLASSIFY_W, y = blockIdx.y * CLASSIFY_H + lane / CLASSIFY_W;
+	if (x >= w || y >= h) return;
+	const unsigned long long v = blockIdx.z, frame = (unsigned long long)w * (unsigned long long)h;
+	const unsigned long long at = (unsigned long long)y * (unsigned long long)w + (unsigned long long)x;
+	lol::V3 c[K];                            /* (K is a template argument: every loop below unrolls, c[] stays in registers) */
+#pragma unroll
+	for (int k = 0; k < K; k++) {
+		const lol::LinearColour e = lin[(v * K + k) * frame + at];
+		c[k] = { e.r, e.g, e.b };
+	}
+#pragma unroll
+	for (int m = 1; m < K; m <<= 1)
+#pragma unroll
+		for (int i = 0; i < K; i += 2 * m) c[i] = { c[i].x + c[i + m].x, c[i].y + c[i + m].y, c[i].z + c[i + m].z };
+	const float inv = 1.f / (float)K;
+	const lol::V3 mean = { c[0].x * inv, c[0].y * inv, c[0].z * inv };
+	lol::Launch L{};
+	L.flags = O.flags;
+	const lol::LaunchTail T = { O.dst, O.pitch_px, O.fmt_shift, O.fmt_loss, O.fmt_amask, O.dbg_rgb, nullptr, nullptr, nullptr, O.gamma_table };
+	lol::V3 post;
+	const uint32_t px = lol::pack_pixel(L, T, mean, post);
+	const unsigned long long o = v * frame + at;
+	if (O.dbg_rgb) { O.dbg_rgb[o * 3 + 0] = post.x; O.dbg_rgb[o * 3 + 1] = post.y; O.dbg_rgb[o * 3 + 2] = post.z; }
+	O.dst[v * O.view_stride_px + (unsigned long long)y * O.pitch_px + (unsigned long long)x] = px;
+}
+
 }  // namespace
 
 extern "C" {
@@ -477,6 +519,10 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 		for (hipEvent_t ev : S.ev) if (ev) (void)hipEventDestroy(ev);
 	}
 	for (lol_gpu::ViewAdaptiveSet& S : ctx->view_adaptive_sets) {
+		if (S.d_buf) (void)hipFree(S.d_buf);
+		if (S.done) (void)hipEventDestroy(S.done);
+	}
+	for (lol_gpu::BlendSet& S : ctx->blend_sets) {
 		if (S.d_buf) (void)hipFree(S.d_buf);
 		if (S.done) (void)hipEventDestroy(S.done);
 	}
@@ -1161,6 +1207,84 @@ int lol_gpu_render_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, int
 	const hipError_t e = launch_family(ctx, FAM_BATCH_AA, false, args, grid, s);
 	if (g_roctx.pop) g_roctx.pop();
 	return view_records_done(ctx, *S, s, e, "kernel launch (supersampled batch of views)");
+}
+
+/*
+ * Views averaged over K cameras: two launches on `s` behind ONE copy of the n K records, no host wait between them.
+ *  1. the linear-colour batch kernel (lol_kernel_blend.h) over z = v K + k, into the scratch set: everything a batch decides per
+ *     view is decided per RECORD (queue_view_records), so a group may mix sane and insane cameras;
+ *  2. blend_resolve: each pixel's tree over its K colours, gamma, packing, the stores.
+ * Scratch: the next set of a ring of its own (lol_gpu_internal.h, BlendSet), behind the blend that used it last; the host waits for
+ * that blend only where the set has to grow, or on one of HIP's special stream handles.  Fixed tile order, like any batch.
+ */
+int lol_gpu_render_views_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view, int w, int h, int max_steps,
+                               void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
+	/* (everything lol_gpu_render_views refuses first, in its order: no program before any word about K) */
+	LOL_TRY(batch_refused(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
+	const int K = cams_per_view;
+	if (K != 1 && K != 2 && K != 4 && K != 8 && K != 16) return fail(ctx, LOL_GPU_ERR_ARG, "cameras per view must be 1, 2, 4, 8 or 16");
+	if ((long long)n_views * K > LOL_GPU_MAX_VIEWS) return fail(ctx, LOL_GPU_ERR_ARG, "a blend holds at most LOL_GPU_MAX_VIEWS cameras in all");
+	if (K == 1) return render_views_plain(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+	if (dbg && (dbg->hit_dist || dbg->hit_id || dbg->steps))
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "hit_dist, hit_id and steps have no single value for a pixel averaged over cameras");
+	const int n_rays = n_views * K;
+	dim3 grid;
+	if (!batch_grid(ctx, w, h, n_rays, &grid))
+		return fail(ctx, LOL_GPU_ERR_ARG, "blend too large for one launch over all its cameras: fewer views per call");
+	hipStream_t s;
+	LOL_TRY(batch_stream(ctx, stream, &s));
+	const int si = (int)(ctx->blend_rr++ % lol_gpu::BLEND_SETS);
+	lol_gpu::BlendSet& S = ctx->blend_sets[si];
+	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+	LOL_TRY(grow_scratch(ctx, S, S.done, (size_t)n_rays * (size_t)w * (size_t)h * sizeof(lol::LinearColour), si, ctx->blend_last,
+	                     &ctx->fail_view_scratch, "scratch of a blend of views"));
+	if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.done));
+	lol_gpu::ViewSet* V = nullptr;
+	LOL_TRY(queue_view_records(ctx, cams, n_rays, max_steps, s, &V));
+	batch_range("blend", n_rays, w, h);
+	/* 1. the linear colours: the launch's destination is the scratch (no diagnostics: they are the resolve's) */
+	lol::Launch L;
+	batch_launch(ctx, w, h, max_steps, S.d_buf, (size_t)w * 4, nullptr, L);
+	lol::BatchTail B = { V->d_views, 0ull };
+	const char* what = "kernel launch (blend of views, linear pass)";
+	void* args[] = { &L, &B };
+	hipError_t e = launch_family(ctx, FAM_BATCH_LIN, false, args, grid, s);
+	/* 2. the means */
+	if (e == hipSuccess) {
+		what = "kernel launch (blend of views, resolve pass)";
+		const BlendOut O = { static_cast<uint32_t*>(dst), (uint32_t)(pitch_bytes / 4), (unsigned long long)(view_stride_bytes / 4),
+		                     ctx->fmt_shift, ctx->fmt_loss, ctx->fmt_amask, L.flags & lol::FLAG_GAMMA_TABLE,
+		                     dbg ? dbg->rgb : nullptr, L.gamma_table };
+		const lol::LinearColour* lin = reinterpret_cast<const lol::LinearColour*>(S.d_buf);
+		const dim3 rgrid((w + CLASSIFY_W - 1) / CLASSIFY_W, (h + CLASSIFY_H - 1) / CLASSIFY_H, n_views);
+		switch (K) {
+		case 2:  hipLaunchKernelGGL(blend_resolve<2>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
+		case 4:  hipLaunchKernelGGL(blend_resolve<4>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
+		case 8:  hipLaunchKernelGGL(blend_resolve<8>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
+		default: hipLaunchKernelGGL(blend_resolve<16>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
+		}
+		e = hipGetLastError();
+	}
+	if (g_roctx.pop) g_roctx.pop();
+	/* (recorded even behind a failed launch, like the view records' event and for the same reason) */
+	const hipError_t e2 = hipEventRecord(S.done, s);
+	S.used = true;
+	LOL_TRY(view_records_done(ctx, *V, s, e, what));
+	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (blend of views)", e2);
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_set_view_blends(lol_gpu* ctx, int enable) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	ctx->view_blends = enable ? 1 : 0;       /* takes effect at the next lol_gpu_upload_program */
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_view_blends(const lol_gpu* ctx) { return ctx ? ctx->view_blends : LOL_GPU_ERR_ARG; }
+
+const char* lol_gpu_view_blend_kernel_name(const lol_gpu* ctx, int cams_per_view) {
+	if (!ctx) return "";
+	return family_name(ctx, cams_per_view <= 1 ? FAM_BATCH : FAM_BATCH_LIN);
 }
 
 int lol_gpu_set_view_samples(lol_gpu* ctx, int enable) {

@@ -22,6 +22,7 @@
 #include "lol_kernel_aa.h"
 #include "lol_kernel_batch.h"
 #include "lol_kernel_batch_aa.h"
+#include "lol_kernel_blend.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -130,9 +131,9 @@ struct OwnedProgram {
 /* The families of render kernels, each of which exists twice: as an instantiation of the interpreter (lol_kernel*.h) and as a symbol
  * of the scene module (generate_source).  THE list: generate_source emits the symbols, load_scene_kernel looks them up, launch_family
  * (lol_gpu.hip) launches one or the other and the reported kernel names come from here.  A new family is one row plus its kernel. */
-enum KernelFamily { FAM_FRAME, FAM_FRAME_AA, FAM_FRAME_AA_LIST, FAM_BATCH, FAM_BATCH_AA, FAM_BATCH_AA_LIST, N_FAMILIES };
+enum KernelFamily { FAM_FRAME, FAM_FRAME_AA, FAM_FRAME_AA_LIST, FAM_BATCH, FAM_BATCH_AA, FAM_BATCH_AA_LIST, FAM_BATCH_LIN, N_FAMILIES };
 /* the switch of the context that puts a family into the module of the next upload */
-enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA };
+enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA, SWITCH_BATCH_BLEND };
 struct FamilyRow {
 	const char*  symbol;        /* in the scene module */
 	const char*  counting;      /* its twin with the per-lane step counters (modules up to LOL_SPEC_TWO_KERNELS_MAX_OPS ops), or none */
@@ -146,15 +147,18 @@ constexpr FamilyRow KERNEL_FAMILIES[N_FAMILIES] = {
 	/* FAM_BATCH         (L, B)           */ { "lol_render_spec_batch",         "lol_render_spec_batch_steps", "render_interp_batch",         SWITCH_BATCH },
 	/* FAM_BATCH_AA      (L, B)           */ { "lol_render_spec_batch_aa",      nullptr,                       "render_interp_batch_aa",      SWITCH_BATCH_AA },
 	/* FAM_BATCH_AA_LIST (L, B, Q)        */ { "lol_render_spec_batch_aa_list", nullptr,                       "render_interp_batch_aa_list", SWITCH_BATCH_AA },
+	/* FAM_BATCH_LIN     (L, B)           */ { "lol_render_spec_batch_lin",     nullptr,                       "render_interp_batch_lin",     SWITCH_BATCH_BLEND },
 };
 
 /* What a scene module carries beside lol_render_spec and lol_sdf_spec.  Without any of it the source is exactly what it was before
  * these kernels existed.  aa: lol_gpu_set_samples > 1 at the upload; batch: lol_gpu_set_view_batches; batch_aa:
- * lol_gpu_set_view_samples, which brings the plain batch kernels with it (the first pass of an adaptive batch is theirs). */
+ * lol_gpu_set_view_samples, which brings the plain batch kernels with it (the first pass of an adaptive batch is theirs); blend:
+ * lol_gpu_set_view_blends, the linear-colour batch kernel alone (lol_kernel_blend.h). */
 struct ModuleKernels {
-	bool aa = false, batch = false, batch_aa = false;
+	bool aa = false, batch = false, batch_aa = false, blend = false;
 	bool carries(ModuleSwitch sw) const {
-		return sw == SWITCH_NONE || (sw == SWITCH_AA && aa) || (sw == SWITCH_BATCH && (batch || batch_aa)) || (sw == SWITCH_BATCH_AA && batch_aa);
+		return sw == SWITCH_NONE || (sw == SWITCH_AA && aa) || (sw == SWITCH_BATCH && (batch || batch_aa)) || (sw == SWITCH_BATCH_AA && batch_aa) ||
+		       (sw == SWITCH_BATCH_BLEND && blend);
 	}
 };
 
@@ -240,6 +244,7 @@ struct lol_gpu {
 	int          adaptive = -1;          /* lol_gpu_set_adaptive_samples: the contrast T, or -1 (off) */
 	int          view_batches = 0;       /* lol_gpu_set_view_batches: the next upload's module carries lol_render_spec_batch */
 	int          view_samples = 0;       /* lol_gpu_set_view_samples: ... and lol_render_spec_batch_aa / _aa_list (and the batch kernels) */
+	int          view_blends = 0;        /* lol_gpu_set_view_blends: ... and lol_render_spec_batch_lin */
 	/* The view records of batches (lol_gpu_render_views, lol_gpu.hip): a ring of sets, one per batch, whatever its stream.  A batch
 	 * fills its set's pinned host copy, queues the copy to the device and the launch behind it on its stream, and records `done`;
 	 * the next batch through the set waits for `copied` on the host (the pinned copy is the host's to write again) and for `done`
@@ -281,7 +286,16 @@ struct lol_gpu {
 	ViewAdaptiveSet view_adaptive_sets[VIEW_ADAPTIVE_SETS];
 	unsigned     view_adaptive_rr = 0;
 	int          view_adaptive_last = -1;      /* the set of the last adaptive batch (lol_gpu_views_refined) */
-	int          fail_view_scratch = 0;        /* lol_gpu_testing_fail_view_scratch: that many scratch allocations of adaptive batches still fail */
+	int          fail_view_scratch = 0;        /* lol_gpu_testing_fail_view_scratch: that many scratch allocations of adaptive batches and blends still fail */
+	/* ... of blends (lol_gpu_render_views_blend), a ring of its own: the linear colours [n K][h][w] of pass 1, a lol::LinearColour of
+	 * 16 bytes each.  A blend waits on its set's `done` (behind the last blend that used it) and records it again at its end. */
+	struct BlendSet : ScratchSet {
+		hipEvent_t done = nullptr;
+	};
+	static constexpr int BLEND_SETS = 4;
+	BlendSet     blend_sets[BLEND_SETS];
+	unsigned     blend_rr = 0;
+	int          blend_last = -1;              /* (grow_scratch's `last`: nothing reads a blend's set afterwards) */
 	unsigned     adaptive_rr = 0;
 	int          adaptive_last = -1;     /* the set of the last adaptive frame (lol_gpu_adaptive_refined) */
 	uint32_t*    d_adaptive_order = nullptr;   /* the refine pass's block -> lane-table slot table: slot b at tile_slot(b, stride) */

@@ -258,3 +258,85 @@ def orbit_cameras(scene: "Scene", n: int) -> list:
         c.fov = cam.fov
         out.append(c)
     return out
+
+
+def _copy_camera(cam: Camera) -> Camera:
+    out = Camera()
+    C.memmove(C.byref(out), C.byref(cam), C.sizeof(Camera))
+    return out
+
+
+def shutter_cameras(a: Camera, b: Camera, k: int) -> list:
+    """k cameras of one exposure, for motion blur (Renderer.render_blended_views_into): the shutter opens at camera a and closes at
+    camera b, and camera i (0 <= i < k) stands at the midpoint t = (i + 1/2) / k of the i-th of k equal parts of that interval.
+
+    Position and direction are a + t (b - a), interpolated in doubles; the direction is then normalised and everything rounded to
+    float.  Where a and b look the same way the direction is a's, as it is (nothing to interpolate, nothing to normalise), so
+    shutter_cameras(a, a, k) is a, k times over.  Two directions that cancel at some t leave a's direction there.  The fov is a's."""
+    if k < 1:
+        raise ValueError("shutter_cameras: k must be at least 1")
+    pa, pb = [float(v) for v in a.point.tuple()], [float(v) for v in b.point.tuple()]
+    da, db = [float(v) for v in a.direction.tuple()], [float(v) for v in b.direction.tuple()]
+    out = []
+    for i in range(k):
+        t = (i + 0.5) / k
+        c = _copy_camera(a)
+        c.point = V3(*[pa[j] + t * (pb[j] - pa[j]) for j in range(3)])
+        if da != db:
+            d = [da[j] + t * (db[j] - da[j]) for j in range(3)]
+            ln = math.sqrt(sum(v * v for v in d))
+            if ln > 0.0 and math.isfinite(ln):
+                c.direction = V3(*[v / ln for v in d])
+        out.append(c)
+    return out
+
+
+GOLDEN_ANGLE = math.pi * (3.0 - math.sqrt(5.0))
+
+
+def lens_cameras(camera: Camera, focus_distance: float, aperture_radius: float, k: int) -> list:
+    """k cameras on a lens, for depth of field (Renderer.render_blended_views_into).  k = 1 is the camera itself: a pinhole.
+
+    Otherwise the k positions lie on the lens disc through the camera's position, spanned by the right and up vectors the reference's
+    host moves its camera by (right = normalize(direction x (0, 1, 0)), up = normalize(right x direction)), in a fixed pattern:
+    position i at radius R sqrt((i + 1/2) / k) and angle i times the golden angle — equal areas of the disc, no two on one spoke.
+    Every camera looks at the focus point, point + focus_distance * direction, with the camera's fov; whatever lies at that distance
+    stays sharp, the rest is averaged over the lens.  This is the TOE-IN approximation of a thin lens: the cameras are turned towards
+    the focus point, where a thin lens would keep their image planes parallel and shift them; the plane of focus is therefore only
+    approximately a plane (exact on the axis), which for apertures small against the focus distance is what a viewer expects.
+    Computed in doubles and rounded to float.  A camera looking straight up or down has no right vector: ValueError."""
+    if k < 1:
+        raise ValueError("lens_cameras: k must be at least 1")
+    if k == 1:
+        return [_copy_camera(camera)]
+    p = [float(v) for v in camera.point.tuple()]
+    d = [float(v) for v in camera.direction.tuple()]
+    ln = math.sqrt(sum(v * v for v in d))
+    if not (ln > 0.0 and math.isfinite(ln)):
+        raise ValueError("lens_cameras: the camera has no direction")
+    d = [v / ln for v in d]
+
+    def cross(u, v):
+        return [u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]]
+
+    right = cross(d, [0.0, 1.0, 0.0])
+    rn = math.sqrt(sum(v * v for v in right))
+    if not rn > 0.0:
+        raise ValueError("lens_cameras: a camera looking straight up or down has no lens plane of this kind")
+    right = [v / rn for v in right]
+    up = cross(right, d)
+    un = math.sqrt(sum(v * v for v in up))
+    up = [v / un for v in up]
+    focus = [p[j] + float(focus_distance) * d[j] for j in range(3)]
+    out = []
+    for i in range(k):
+        rad, th = float(aperture_radius) * math.sqrt((i + 0.5) / k), i * GOLDEN_ANGLE
+        pos = [p[j] + rad * (math.cos(th) * right[j] + math.sin(th) * up[j]) for j in range(3)]
+        look = [focus[j] - pos[j] for j in range(3)]
+        lk = math.sqrt(sum(v * v for v in look))
+        c = _copy_camera(camera)
+        c.point = V3(*pos)
+        if lk > 0.0 and math.isfinite(lk):
+            c.direction = V3(*[v / lk for v in look])
+        out.append(c)
+    return out
