@@ -178,7 +178,9 @@ bool camera_sane(const lol_frame_camera& c) {
  * the camera is sane (camera_sane: then every ray direction that is finite makes ro + rd * 0 = ro, see march), no component of
  * the origin is a negative zero, max_steps >= 1, and the value lies in [0.001, 100] — a march that ends on its first step, or
  * goes on with a NaN, is left to the loop.  tests/test_gpu_parity.py compares every pixel's distance, id and step count
- * (this step included) with the oracle's either way. */
+ * (this step included) with the oracle's either way.  host_sdf's `d < best` is the reference's tie rule (the first object in file
+ * order wins among equals) only because lol_scene_flatten emits the LOL_OP_TOP records with strictly ascending ids, in file order:
+ * it checks that itself, and tests/test_scene_shapes.py and tests/test_gpu_hostile.py hold it and the ties to the oracle. */
 inline float h_minf(float a, float b) { return a < b ? a : b; }      /* MINSS: b on NaN / equal (float.h:6) */
 inline float h_maxf(float a, float b) { return a > b ? a : b; }
 inline float h_len3(float x, float y, float z) { return __builtin_sqrtf((x * x + y * y) + z * z); }      /* DPPS 0x71 (vec.h:52-56): (x² + y²) + (z² + 0) */

@@ -688,6 +688,19 @@ int lol_scene_flatten(const lol_scene* s, lol_program* out) {
 		out->root_material[i] = s->nodes[s->roots[i]].material;
 	}
 	free(memo);
+	/* One LOL_OP_TOP per object, their ids strictly ascending in program order (1, 2, ...: file order).  Every evaluator of the
+	 * program keeps the reference's tie rule — among objects of EQUAL distance the first in the file wins — by comparing with a
+	 * strict '<' in this order (lol_gpu.hip, host_sdf, is one), so a program that breaks it is never handed out. */
+	if (status == LOL_OK) {
+		uint32_t last = 0, tops = 0;
+		for (uint32_t i = 0; i < out->n_ops; i++)
+			if (out->ops[i].op == LOL_OP_TOP) {
+				if (out->ops[i].id <= last) { status = LOL_ERR_UNSUPPORTED; break; }
+				last = out->ops[i].id;
+				tops++;
+			}
+		if (status == LOL_OK && tops != out->n_roots) status = LOL_ERR_UNSUPPORTED;
+	}
 	if (status == LOL_OK && !out->ops) {            /* a scene without objects: an empty, non-NULL table */
 		out->ops = malloc(sizeof *out->ops);
 		if (!out->ops) status = LOL_ERR_NOMEM;

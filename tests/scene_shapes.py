@@ -188,3 +188,151 @@ MAX_STEPS_SIZE = (37, 19)
 def cameras(sc):
     """the cameras of every batch of the family tests"""
     return S.orbit_cameras(sc, N_VIEWS)
+
+
+# ---- hostile scenes (tests/test_gpu_hostile.py): the inputs that strain what the exact shortcuts are decided from — the culling bounds
+# and the k-d plan, the carried bound, the division skip, the fast roots' range fall-back, the host's own first step — and exact ties
+def stress_scene(rng):
+    """Scenes that lean on the culling bounds: many top-level objects of very different sizes and distances, smoothness
+    from 0.01 to 60 (and 0 / negative: no bound), coordinates up to 10^4, negative radii, cameras inside objects.
+    (The generator of tests/tools/soak.py's `stress` mode, which imports it from here: for a given rng the text is what it has
+    always been, byte for byte — tests/test_scene_shapes.py holds scene 0 of seed 7707 to the recorded text.)"""
+    scale = float(rng.choice([1, 1, 1, 30, 1000]))
+
+    def leaf():
+        c = rng.normal(size=3) * [6, 3, 6] * scale + [0, 1, -8 * scale]
+        if rng.random() < 0.6:
+            return "sphere { point = %s, radius = %s }" % (fmt(c), num(rng.choice([-1, 0, 0.01, 0.5, 2, 9]) * scale))
+        return "box { point = %s, point2 = %s, radius = %s }" % (fmt(c), fmt(rng.uniform(0, 4, 3) * scale), num(rng.choice([0, 0.3, 2]) * scale))
+
+    def tree(d):
+        if d == 0 or rng.random() < 0.35:
+            return leaf() if rng.random() < 0.93 else "plane { y = %s }" % num(rng.uniform(-5, 0) * scale)
+        k = rng.choice([0, -1, 0.01, 0.3, 1, 4, 15, 60]) * scale
+        return "smooth_union { smoothness = %s, a = %s, b = %s }" % (num(k), tree(d - 1), tree(int(rng.integers(0, d))))
+
+    mats = "materials { { shininess = 2, diffuse = (0,0,0), specular = (0,0,0), ambient = (.1,.1,.1) }, { shininess = 9, diffuse = (.5,.4,.3), specular = (.3,.3,.3), ambient = (.1,.1,.1) } }"
+    comps = ["camera { point = %s, direction = %s, fov = %s }" % (fmt(rng.normal(size=3) * [3, 2, 3] * scale), fmt(rng.normal(size=3) * 0.3 + [0, -0.2, -1]), num(rng.uniform(50, 150)))]
+    for _ in range(int(rng.integers(0, 3))):
+        comps.append("point_light { point = %s, diffuse_intensity = (2,2,2), specular_intensity = (1,1,1) }" % fmt(rng.normal(size=3) * 8 * scale + [0, 9 * scale, 0]))
+    order = [0, 1] if rng.random() < 0.5 else [1, 0]
+    objs = []
+    crowd = rng.random() < 0.25                      # many shallow objects: the k-d clusters of the culling plan
+    for _ in range(int(rng.integers(10, 60)) if crowd else int(rng.integers(1, 9))):
+        o = tree(int(rng.integers(0, 2 if crowd else 4)))
+        head, rest = o.split("{", 1)
+        objs.append("%s{ material = #1,%s" % (head, rest))
+    if rng.random() < 0.7:
+        objs.insert(int(rng.integers(0, len(objs) + 1)), "plane { material = #1, y = %s }" % num(rng.uniform(-6, -1) * scale))
+    return mats + "\nscene { " + ",\n".join(comps + objs) + " }\n"
+
+
+@dataclass(frozen=True)
+class Tie:
+    """the objects of a tie scene, in file order, as `.lol` text; `tied`: the 1-based ids of those whose distances are EQUAL binary32
+    values at the camera position — and, where `along_ray`, at every point of the central ray up to the hit"""
+    objects: Tuple[str, ...]
+    tied: Tuple[int, ...]
+    along_ray: bool
+
+
+@dataclass(frozen=True)
+class Hostile:
+    name: str
+    purpose: str
+    text: str = field(repr=False)
+    size: Tuple[int, int] = (23, 13)
+    families: bool = True               # rendered through the supersampled, adaptive, batch and blend kernels too
+    own_kernel: bool = True             # the scene compiler takes it on (False: it legitimately stays on the interpreter)
+    tie: Optional[Tie] = field(default=None, repr=False)
+
+
+HOSTILE_SEED = 20264742           # chosen on the CPU for what tests/test_scene_shapes.py holds the generated scenes to
+N_HOSTILE_GENERATED = 14
+HOSTILE_SIZE = (23, 13)                 # the family tests' own fuzz size
+HOSTILE_CONTRAST = 16
+
+# four materials of four colours, so that a wrong winner of a tie is another colour and not only another id; #0 is what a ray that
+# escapes wears too
+TIE_MATERIALS = ("materials { { shininess = 4, diffuse = (.6,.1,.1), specular = (.2,.2,.2), ambient = (.25,.05,.05) },"
+                 " { shininess = 4, diffuse = (.1,.1,.6), specular = (.2,.2,.2), ambient = (.05,.05,.25) },"
+                 " { shininess = 8, diffuse = (.1,.6,.1), specular = (.3,.3,.3), ambient = (.05,.25,.05) },"
+                 " { shininess = 2, diffuse = (.4,.4,.4), specular = (.1,.1,.1), ambient = (.1,.1,.1) } }\n")
+TIE_HEAD = ("camera { point = (0, 0, 0), direction = (0, 0, -1), fov = 60 }",
+            "point_light { point = (3, 5, 0), diffuse_intensity = (2,2,2), specular_intensity = (1,1,1) }")
+
+
+def tie_text(objects, head=TIE_HEAD):
+    return TIE_MATERIALS + "scene { " + ",\n".join(tuple(head) + tuple(objects)) + " }\n"
+
+
+def _wear(obj, material):
+    head, rest = obj.split("{", 1)
+    return "%s{ material = #%d,%s" % (head, material, rest)
+
+
+def _tie(name, purpose, objects, tied, along_ray=True):
+    return Hostile(name, purpose, tie_text(objects), tie=Tie(tuple(objects), tuple(tied), along_ray))
+
+
+def _twins(name, purpose, obj_a, obj_b, rest):
+    """obj_a wearing #0 then obj_b wearing #1, and the twin scene in the opposite file order: the winner is id 1 in both, its colour
+    is not"""
+    return [_tie(name + "-01", purpose, (_wear(obj_a, 0), _wear(obj_b, 1)) + rest, (1, 2)),
+            _tie(name + "-10", purpose + " (the twin: opposite file order)", (_wear(obj_b, 1), _wear(obj_a, 0)) + rest, (1, 2))]
+
+
+def _tie_crowd():
+    """twelve small spheres on a grid of small integers round three coincident ones (ids 3, 9 and 14 of 16): fifteen bounded objects,
+    which the culling plan splits into k-d clusters and evaluates in another order than the file's; the plane, which has no bound,
+    is evaluated before all of them"""
+    grid = ["sphere { material = #3, point = (%d, %d, %d), radius = 0.5 }" % (x, y, z)
+            for z in (-6, -9, -12) for x, y in ((-6, 1), (-3, -1), (3, 1), (6, -1))]
+    same = "sphere { point = (0, 0, -6), radius = 1 }"
+    objs = grid[:2] + [_wear(same, 0)] + grid[2:6] + ["plane { material = #3, y = -7 }"] + [_wear(same, 1)] + grid[6:10] + [_wear(same, 2)] + grid[10:]
+    return objs
+
+
+_FLOOR = ("plane { material = #3, y = -7 }",)           # (farther from the camera than the tied objects: they are the first step)
+TIE_SCENES = (
+    _twins("tie-spheres", "two identical spheres", "sphere { point = (0, 0, -5), radius = 1 }", "sphere { point = (0, 0, -5), radius = 1 }", _FLOOR)
+    + _twins("tie-boxes", "two identical rounded boxes", "box { point = (0, 0, -5), point2 = (1, 0.5, 0.75), radius = 0.25 }",
+             "box { point = (0, 0, -5), point2 = (1, 0.5, 0.75), radius = 0.25 }", _FLOOR)
+    # sminf(a, a, k) = a - k / 4: the union of two spheres of radius 1 with k = 4 is |p - c| - 1 - 1, the sphere of radius 2 is
+    # |p - c| - 2, and both are exact wherever |p - c| >= 2 (a small integer taken from a larger float): equal everywhere outside
+    + _twins("tie-sphere-union", "a sphere and a smooth union of two spheres of the same value", "sphere { point = (0, 0, -8), radius = 2 }",
+             "smooth_union { smoothness = 4, a = sphere { point = (0, 0, -8), radius = 1 }, b = sphere { point = (0, 0, -8), radius = 1 } }", _FLOOR)
+    + [_tie("tie-crowd", "three coincident spheres in a crowd that the culling plan clusters and re-orders", _tie_crowd(), (3, 9, 14)),
+       # |(-3, 0, -4)| - 1 = 5 - 1 and |(0, 0, -6)| - 2 = 6 - 2: both 4 at the camera and nowhere else on the central ray
+       _tie("tie-camera", "the camera exactly equidistant from two different spheres: a tie on the first step only",
+            ("sphere { material = #0, point = (-3, 0, -4), radius = 1 }", "sphere { material = #1, point = (0, 0, -6), radius = 2 }") + _FLOOR,
+            (1, 2), along_ray=False)]
+)
+
+
+def hostile_texts():
+    rng = np.random.default_rng(HOSTILE_SEED)
+    return [stress_scene(rng) for _ in range(N_HOSTILE_GENERATED)]
+
+
+def _generated():
+    return [Hostile("stress%02d" % i, "scene %d of stress_scene under HOSTILE_SEED" % i, t) for i, t in enumerate(hostile_texts())]
+
+
+HOSTILE = _generated() + TIE_SCENES
+HOSTILE_BY_NAME = {e.name: e for e in HOSTILE}
+HOSTILE_TIES = [e for e in HOSTILE if e.tie is not None]
+
+
+def hostile_scene(e: Hostile) -> "S.Scene":
+    if ("hostile", e.name) not in _scenes:
+        _scenes[("hostile", e.name)] = S.Scene.parse_string(e.text)
+    return _scenes[("hostile", e.name)]
+
+
+# which of HOSTILE, in its order, have an edge AND a smooth area under their own camera at their size and HOSTILE_CONTRAST (what the
+# input is decides: tests/test_scene_shapes.py holds the tuple to adaptive_reference).  Six of the generated scenes are one object
+# seen from inside, or from so near that it fills the frame: they are kept, as what they are.
+# (Cost of one aa_reference frame at s = 4 on one CPU core: 0.10 s for the slowest, stress04 with its 41 objects; no size is reduced.)
+HOSTILE_REFINES_SOME = (True, False, False, True, True, False, True, False, False, True, True, True, True, False,
+                        True, True, True, True, True, True, True, True)

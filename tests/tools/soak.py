@@ -12,6 +12,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 import test_gpu_fuzz as F
 from test_gpu_parity import check_against_oracle, gpu_render
+from scene_shapes import stress_scene
 from loltracer_amd import gpu, scene as S
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
@@ -51,37 +52,6 @@ def flight_render(r, sc, w, h):
                  id=f[3].cpu().numpy().view(np.uint32), steps=f[4].cpu().numpy().view(np.uint32), miss_skip=r.miss_skip_active()) for f in sets]
 
 
-def stress_scene(rng):
-    """Scenes that lean on the culling bounds: many top-level objects of very different sizes and distances, smoothness
-    from 0.01 to 60 (and 0 / negative: no bound), coordinates up to 10^4, negative radii, cameras inside objects."""
-    scale = float(rng.choice([1, 1, 1, 30, 1000]))
-
-    def leaf():
-        c = rng.normal(size=3) * [6, 3, 6] * scale + [0, 1, -8 * scale]
-        if rng.random() < 0.6:
-            return "sphere { point = %s, radius = %s }" % (F.fmt(c), F.num(rng.choice([-1, 0, 0.01, 0.5, 2, 9]) * scale))
-        return "box { point = %s, point2 = %s, radius = %s }" % (F.fmt(c), F.fmt(rng.uniform(0, 4, 3) * scale), F.num(rng.choice([0, 0.3, 2]) * scale))
-
-    def tree(d):
-        if d == 0 or rng.random() < 0.35:
-            return leaf() if rng.random() < 0.93 else "plane { y = %s }" % F.num(rng.uniform(-5, 0) * scale)
-        k = rng.choice([0, -1, 0.01, 0.3, 1, 4, 15, 60]) * scale
-        return "smooth_union { smoothness = %s, a = %s, b = %s }" % (F.num(k), tree(d - 1), tree(int(rng.integers(0, d))))
-
-    mats = "materials { { shininess = 2, diffuse = (0,0,0), specular = (0,0,0), ambient = (.1,.1,.1) }, { shininess = 9, diffuse = (.5,.4,.3), specular = (.3,.3,.3), ambient = (.1,.1,.1) } }"
-    comps = ["camera { point = %s, direction = %s, fov = %s }" % (F.fmt(rng.normal(size=3) * [3, 2, 3] * scale), F.fmt(rng.normal(size=3) * 0.3 + [0, -0.2, -1]), F.num(rng.uniform(50, 150)))]
-    for _ in range(int(rng.integers(0, 3))):
-        comps.append("point_light { point = %s, diffuse_intensity = (2,2,2), specular_intensity = (1,1,1) }" % F.fmt(rng.normal(size=3) * 8 * scale + [0, 9 * scale, 0]))
-    order = [0, 1] if rng.random() < 0.5 else [1, 0]
-    objs = []
-    crowd = rng.random() < 0.25                      # many shallow objects: the k-d clusters of the culling plan
-    for _ in range(int(rng.integers(10, 60)) if crowd else int(rng.integers(1, 9))):
-        o = tree(int(rng.integers(0, 2 if crowd else 4)))
-        head, rest = o.split("{", 1)
-        objs.append("%s{ material = #1,%s" % (head, rest))
-    if rng.random() < 0.7:
-        objs.insert(int(rng.integers(0, len(objs) + 1)), "plane { material = #1, y = %s }" % F.num(rng.uniform(-6, -1) * scale))
-    return mats + "\nscene { " + ",\n".join(comps + objs) + " }\n"
 rs = {m: gpu.Renderer(0, specialize=m) for m in (1, 4)}
 bad = 0
 for i in range(n):
