@@ -9,8 +9,8 @@
  * restated primitives (oracle/lol_oracle.c) and the build's `.lol` reader
  * (loltracer_amd/csrc/lol_scene.c) with what the reference's code computes.
  *
- * naive_renderer.c itself is NOT built: it includes <SDL.h> via renderer.h and
- * SDL2 is not in this image (DESIGN.md "Oracle").
+ * naive_renderer.c itself is built beside this file, unmodified: ref_render.c holds what it
+ * links against and sdl_standin/SDL.h is its <SDL.h> (DESIGN.md "Oracle").
  */
 #include <stdint.h>
 #include <string.h>

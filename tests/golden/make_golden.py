@@ -40,16 +40,24 @@ Outputs (all DATA — inputs and expected outputs, no reference source text):
   ref_scene_programs.json  the four example scenes as the REFERENCE's scene.c builds them, converted by our
                         integration/lol_refscene.c and flattened: the program's tables and the camera, as hex
                         (tests/test_refscene.py holds the build's own .lol reader against them).
-  oracle_frames.npz     XRGB8888 frames + float RGB of the CPU ORACLE (not of the reference:
-                        naive_renderer.c cannot be built here) — regression fixtures that
+  oracle_frames.npz     XRGB8888 frames + float RGB of the CPU ORACLE (not of the reference) — regression fixtures that
                         pin the oracle's output across toolchains / on the GPU box.
+  ref_renderer_frames.npz  frames of the REFERENCE'S OWN RENDERER: the packed XRGB8888 pixels that naive_renderer.c's render_thread
+                        itself stored (the unmodified file, compiled where it lies against oracle/sdl_standin/SDL.h and driven by
+                        oracle/ref_render.c), for every scene and camera tests/reference_frames.py lists: the four example scenes,
+                        the rung and form shapes, the fuzz scenes, the degenerate inputs and the hostile scenes of
+                        tests/scene_shapes.py.  For the hostile scenes also RefPipeline's ids, distances, step counts and colours —
+                        and the generator asserts that RefPipeline's packed pixels ARE render_thread's.
+                        `python tests/golden/make_golden.py --renderer-frames` writes this file alone.
 """
 import ctypes as C
 import json
+import multiprocessing
 import os
 import re
 import struct
 import sys
+import time
 
 import numpy as np
 
@@ -100,10 +108,19 @@ def load_ref():
                                C.POINTER(vp), C.POINTER(vp)], None),
         "ref_sizeof": ([C.c_int], C.c_size_t),
     }
+    # the reference's own renderer (oracle/ref_render.c + naive_renderer.c): a liblol_ref.so kept from before it was part of the
+    # library (oracle/Makefile keeps a prebuilt one where the reference tree is absent) serves everything above and lacks these
+    renderer = {"ref_render_frame": ([vp, C.c_int, C.c_int, vp, C.c_int], None), "ref_scene_set_camera": ([vp, f3], None)}
+    if has_renderer(ref):
+        sig.update(renderer)
     for name, (args, res) in sig.items():
         fn = getattr(ref, name)
         fn.argtypes, fn.restype = args, res
     return ref
+
+
+def has_renderer(ref):
+    return all(hasattr(ref, name) for name in ("ref_render_frame", "ref_scene_set_camera", "render_thread"))
 
 
 # ------------------------------------------------------------------ primitives
@@ -471,6 +488,111 @@ class RefPipeline:
         return rec
 
 
+# ---------------------------------------------- frames of the reference's own render_thread
+
+def render_thread_frame(ref, sc, w, h, cam=None):
+    """one frame of naive_renderer.c's render_thread (256 steps: its MAX_STEPS is a constant), under `cam` (7 floats) if given"""
+    if cam is not None:
+        ref.ref_scene_set_camera(sc, (C.c_float * 7)(*[float(v) for v in cam]))
+    px = np.full((h, w), 0xDEADBEEF, dtype=np.uint32)
+    ref.ref_render_frame(sc, w, h, px.ctypes.data, w * 4)
+    return px
+
+
+def try_build(key):
+    """exit status 0 if the reference's builders take the scene of case `key` (run in a process of its own: vector_get asserts)"""
+    import reference_frames as RF
+    case = {c.key: c for c in RF.cases()}[key]
+    ref = load_ref()
+    sc = Walker(ref, case.text()).run()
+    if not ref.ref_scene_validate_materials(sc):
+        raise SystemExit(3)
+    render_thread_frame(ref, sc, 2, 2)
+    raise SystemExit(0)
+
+
+def renderer_case(key):
+    """every frame of one case → (key, arrays, meta entry, seconds)"""
+    import reference_frames as RF
+    from loltracer_amd import scene as S
+    t0 = time.time()
+    case = {c.key: c for c in RF.cases()}[key]
+    text = case.text()
+    w, h = case.size
+    ref = load_ref()
+    sc = Walker(ref, text).run()
+    assert ref.ref_scene_validate_materials(sc), key
+    ours = S.Scene.parse_string(text)
+    own = (C.c_float * 7)()
+    ref.ref_scene_camera(sc, own)
+    own = np.array(list(own), dtype=np.float32)
+    # the cameras are computed from OUR reading of the text: it must be the camera scene.c built
+    assert own.tobytes() == RF.cam7(ours.camera).tobytes(), (key, "the build's reader and scene.c disagree on the camera")
+    cams = RF.cameras_of(case, ours)
+    rows = np.stack([RF.cam7(c) for _, c in cams])
+    frames = [render_thread_frame(ref, sc, w, h)] + [render_thread_frame(ref, sc, w, h, row) for row in rows[1:]]
+    ref.ref_scene_set_camera(sc, (C.c_float * 7)(*[float(v) for v in own]))
+    arrays = {key + "_xrgb": np.stack(frames), key + "_cams": rows}
+    t_frames = time.time() - t0
+    if case.group == "example":
+        # ref_frames.npz is RefPipeline's composition of every pixel of this very frame: its packed pixels are render_thread's
+        composed = np.load(os.path.join(HERE, "ref_frames.npz"))[key + "_xrgb"]
+        assert np.array_equal(composed, frames[0]), (key, "ref_frames.npz (RefPipeline) and render_thread differ")
+    if case.composed:
+        dump = dump_scene(ref, sc)
+        pipe = RefPipeline(ref, sc, dump)
+        full = [pipe.pixel(x, y, w, h) for y in range(h) for x in range(w)]
+        u = lambda hs: np.array([int(v, 16) for v in hs], dtype=np.uint32)
+        nl = len(dump["lights"])
+        packed = np.array([q["xrgb"] for q in full], dtype=np.uint32).reshape(h, w)
+        # the composition IS the real loop structure: its packed pixels are the ones render_thread stored
+        assert np.array_equal(packed, frames[0]), (key, "RefPipeline and render_thread differ", int((packed != frames[0]).sum()))
+        arrays[key + "_hit_id"] = np.array([q["hit_id"] for q in full], dtype=np.uint32).reshape(h, w)
+        arrays[key + "_march_steps"] = np.array([q["march_steps"] for q in full], dtype=np.uint16).reshape(h, w)
+        arrays[key + "_hit_dist"] = u([q["hit_dist"] for q in full]).view(np.float32).reshape(h, w)
+        arrays[key + "_rgb"] = u([v for q in full for v in q["rgb"]]).view(np.float32).reshape(h, w, 3)
+        arrays[key + "_shadow_steps"] = np.array([v for q in full for v in q["shadow_steps"]], dtype=np.uint16).reshape(h, w, nl)
+    ref.ref_scene_free(sc)
+    entry = {"key": key, "group": case.group, "size": [w, h], "sha256": RF.sha256(text), "cameras": [n for n, _ in cams],
+             "composed": bool(case.composed)}
+    return key, arrays, entry, (t_frames, time.time() - t0)
+
+
+def write_renderer_frames(jobs=8):
+    import subprocess
+    import reference_frames as RF
+    from test_gpu_parity import HOST_LIBM_IS_FMA_VARIANT
+    if not has_renderer(load_ref()):
+        raise SystemExit("oracle/_ref/liblol_ref.so holds no render_thread: run `make -C oracle ref` where /root/reference exists")
+    if not HOST_LIBM_IS_FMA_VARIANT:
+        raise SystemExit("this host's libm would pick the non-FMA powf: ref_renderer_frames.npz is recorded on an FMA host only")
+    cases = RF.cases()
+    # first of all: which scenes can the reference's builders take at all?
+    left_out = []
+    for c in cases:
+        st = subprocess.run([sys.executable, os.path.abspath(__file__), "--try-build", c.key], capture_output=True, text=True)
+        if st.returncode != 0:
+            why = ("scene_validate_materials fails" if st.returncode == 3 else
+                   (st.stderr.strip().splitlines() or ["exit status %d" % st.returncode])[-1])
+            left_out.append({"key": c.key, "group": c.group, "reason": why})
+    assert len(left_out) <= RF.MAX_LEFT_OUT and not any(e["group"] in ("hostile", "tie") for e in left_out), left_out
+    keys = [c.key for c in cases if c.key not in {e["key"] for e in left_out}]
+    arrays, entries, secs = {}, {}, {}
+    with multiprocessing.get_context("fork").Pool(jobs, maxtasksperchild=1) as pool:
+        for key, arr, entry, t in pool.imap_unordered(renderer_case, sorted(keys, key=lambda k: "tree12" not in k)):
+            arrays.update(arr)
+            entries[key], secs[key] = entry, t
+            print("%-32s %2d frames %7.1f s render_thread, %7.1f s in all" % (key, len(entry["cameras"]), t[0], t[1]), flush=True)
+    meta = {"source": "naive_renderer.c's own render_thread via oracle/_ref/liblol_ref.so (oracle/ref_render.c); the composition: "
+                      "make_golden.py RefPipeline", "max_steps": 256, "format": "XRGB8888",
+            "host_libm_is_fma_variant": bool(HOST_LIBM_IS_FMA_VARIANT), "cases": [entries[k] for k in keys], "left_out": left_out}
+    arrays["meta"] = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), dtype=np.uint8)
+    RF.write_npz(os.path.join(HERE, "ref_renderer_frames.npz"), arrays)
+    print("wrote ref_renderer_frames.npz: %d cases, %d frames, %d left out; render_thread %.0f s, with the composition %.0f s (CPU seconds)"
+          % (len(keys), sum(len(e["cameras"]) for e in entries.values()), len(left_out),
+             sum(t[0] for t in secs.values()), sum(t[1] for t in secs.values())))
+
+
 def gen_sdf_points(ref, sc, cam, seed):
     rng = np.random.default_rng(seed)
     pts = []
@@ -571,6 +693,10 @@ def write_converted_programs(ref):
 def main():
     if not os.path.exists(REF_SO):
         raise SystemExit("oracle/_ref/liblol_ref.so missing: run `make -C oracle ref` where /root/reference exists")
+    if sys.argv[1:2] == ["--try-build"]:
+        try_build(sys.argv[2])
+    if sys.argv[1:2] == ["--renderer-frames"]:
+        return write_renderer_frames()
     ref = load_ref()
 
     with open(os.path.join(HERE, "ref_primitives.json"), "w") as f:
@@ -591,6 +717,7 @@ def main():
         u = lambda hs: np.array([int(v, 16) for v in hs], dtype=np.uint32)
         nl = len(scenes[name]["lights"])
         frames[f"{name}_xrgb"] = np.array([q["xrgb"] for q in full], dtype=np.uint32).reshape(H, W)
+        assert np.array_equal(frames[f"{name}_xrgb"], render_thread_frame(ref, sc, W, H)), (name, "RefPipeline and render_thread differ")
         frames[f"{name}_hit_id"] = np.array([q["hit_id"] for q in full], dtype=np.uint32).reshape(H, W)
         frames[f"{name}_march_steps"] = np.array([q["march_steps"] for q in full], dtype=np.uint32).reshape(H, W)
         frames[f"{name}_hit_dist"] = u([q["hit_dist"] for q in full]).view(np.float32).reshape(H, W)
@@ -636,6 +763,7 @@ def main():
         if w == 64:
             frames[f"{name}_{w}x{h}_rgb"] = rgb
     np.savez_compressed(os.path.join(HERE, "oracle_frames.npz"), **frames)
+    write_renderer_frames()
     print("wrote ref_primitives.json, ref_scenes.json, ref_sdf_points.json, ref_pixels.json, ref_frames.npz, ref_camera_path.json, "
           "ref_scene_programs.json, oracle_frames.npz")
 

@@ -15,7 +15,7 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 
 from loltracer_amd import scene as S
-from test_gpu_fuzz import DEGENERATE_CASES, balanced_tree_text, chain_scene, deep_tree_text, fmt, num, rand_scene
+from test_gpu_fuzz import DEGENERATE_CASES, balanced_tree_text, chain_text, deep_tree_text, fmt, num, rand_scene
 
 SCENES_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "scenes")
 TABLES_LDS_MAX_DWORDS = 1024            # lol_kernel.h
@@ -41,7 +41,7 @@ def rung_of(prog) -> Tuple[int, bool]:
 class Shape:
     name: str
     purpose: str
-    build: Callable[[], "S.Scene"] = field(repr=False, compare=False)
+    text: Callable[[], str] = field(repr=False, compare=False)      # the scene as `.lol` text
     n_ops: int
     max_stack: int
     n_lights: int
@@ -59,12 +59,12 @@ _scenes = {}
 
 def scene_of(shape: Shape) -> "S.Scene":
     if shape.name not in _scenes:
-        _scenes[shape.name] = shape.build()
+        _scenes[shape.name] = S.Scene.parse_string(shape.text())
     return _scenes[shape.name]
 
 
 def _file(name):
-    return lambda: S.Scene.parse_file(os.path.join(SCENES_DIR, name + ".lol"))
+    return lambda: open(os.path.join(SCENES_DIR, name + ".lol")).read()
 
 
 def many_materials(n=110, seed=17) -> str:
@@ -94,7 +94,7 @@ def compact_tree_text(depth, **kw):
 def _tree(text_fn, depth, big_table=False):
     def build():
         kw = dict(materials=many_materials(), extra=big_table_extra()) if big_table else {}
-        return S.Scene.parse_string(text_fn(depth, **kw))
+        return text_fn(depth, **kw)
     return build
 
 
@@ -121,9 +121,9 @@ RUNG = {s.name: s for s in RUNG_SHAPES}
 
 # ---- the scene compiler's forms.  (Stack depth means nothing to straight-line code: the 8192-op trees stay on the interpreter.)
 MID = Shape("chain140", "284 ops: the mid-size scene, out of line on the first tier and inlined on the second",
-            lambda: chain_scene(140), n_ops=284, max_stack=2, n_lights=1, rung=(1, False), size=(32, 18))
+            lambda: chain_text(140), n_ops=284, max_stack=2, n_lights=1, rung=(1, False), size=(32, 18))
 BIG = Shape("chain550", "1104 ops: above the inlining limit, the SDF is one out-of-line function and nothing else",
-            lambda: chain_scene(550), n_ops=1104, max_stack=2, n_lights=1, rung=(1, False), size=(24, 13))
+            lambda: chain_text(550), n_ops=1104, max_stack=2, n_lights=1, rung=(1, False), size=(24, 13))
 
 
 @dataclass(frozen=True)

@@ -169,7 +169,7 @@ def test_orbit_frames_at_full_size_match_the_oracle_on_sampled_rows(torch_cuda, 
     r.close()
 
 
-def chain_scene(n_unions, seed=3):
+def chain_text(n_unions, seed=3):
     """One object: a right-leaning chain of n smooth unions of spheres (2n + 2 ops), over a plane, lit and in view."""
     rng = np.random.default_rng(seed)
     body = "sphere { point = (0,0,-5), radius = 1 }"
@@ -181,7 +181,11 @@ def chain_scene(n_unions, seed=3):
             "scene { camera { point = (0, 3, 6), direction = (0, -0.25, -1), fov = 100 },"
             " point_light { point = (0,9,0), diffuse_intensity = (2,2,2), specular_intensity = (2,2,2) }, "
             + body.replace("{", "{ material = #1,", 1) + ", plane { y = -4, material = #1 } }")
-    return S.Scene.parse_string(text)
+    return text
+
+
+def chain_scene(n_unions, seed=3):
+    return S.Scene.parse_string(chain_text(n_unions, seed))
 
 
 @pytest.mark.parametrize("n_unions,inline_max", [(69, None), (69, 0), (130, None), (130, 0)],

@@ -2,7 +2,7 @@
 TABLES_LDS_MAX_DWORDS and on the declared interpreter rung, the rungs are all eight, and every adaptive frame the GPU tests of
 tests/test_gpu_families.py render refines SOME pixels and leaves some — says the oracle's mask, on the CPU.  Likewise the hostile
 scenes of tests/test_gpu_hostile.py: the features they are there for are in their flattened programs, their ties are exact and go
-to the first object in file order on the oracle, and every program of the catalogue has its LOL_OP_TOP ids strictly ascending."""
+to the first object in file order in the REFERENCE's own recorded frame and on the oracle, and every program of the catalogue has its LOL_OP_TOP ids strictly ascending."""
 import ctypes
 import re
 import os
@@ -12,6 +12,7 @@ import pytest
 
 import adaptive_reference as R
 import oracle_lib as O
+import reference_frames as RF
 import scene_shapes as C
 from loltracer_amd import gpu, scene as S
 
@@ -187,7 +188,10 @@ def test_ties_are_exact_and_go_to_the_first_object(e):
     sc = C.hostile_scene(e)
     w, h = e.size
     first = min(e.tie.tied)
-    # the points of the tie: the camera position and, along_ray, the central ray's own points up to the hit (the camera looks down
+    # the reference itself gives the tie to the first object: the frame its own render_thread stored, and the composition beside it
+    # (tests/golden/ref_renderer_frames.npz) ...
+    RF.assert_recorded_tie_goes_to_the_first(e)
+    # ... and so does the oracle.  The points of the tie: the camera position and, along_ray, the central ray's own points up to the hit (the camera looks down
     # -z from the origin, so that they are (0, 0, -t) exactly, t the distance marched: the central pixel's probe gives the hit)
     assert sc.camera.point.tuple() == (0.0, 0.0, 0.0) and sc.camera.direction.tuple() == (0.0, 0.0, -1.0)
     centre = O.probe(sc, w, h, w // 2, h // 2)
