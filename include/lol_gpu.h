@@ -353,8 +353,9 @@ int         lol_gpu_view_samples(const lol_gpu* ctx);
  * lol_render_spec_batch_lin (both kernels of a 257 ... 1024-op scene do); otherwise, and until that module is ready, the
  * interpreter's render_interp_batch_lin renders — same pixels either way (lol_gpu_view_blend_kernel_name, lol_gpu_diag.h).  A
  * module compiled without the switch is the module it was before (same code object, same lol_gpu_kernel_key).
- * Not built: supersampled blends (samples per pixel AND cameras per view), row partitions, a lol_gpu_multi_* form (stripe the
- * views over the devices, one context each), host surfaces, and the renderer.h protocol, which has one camera per frame.
+ * Supersampled blends (samples per pixel AND cameras per view): lol_gpu_render_views_blend_samples below.
+ * Not built: row partitions, a lol_gpu_multi_* form (stripe the views over the devices, one context each), host surfaces, and the
+ * renderer.h protocol, which has one camera per frame.
  */
 #define LOL_GPU_MAX_BLEND 16
 int         lol_gpu_render_views_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view,
@@ -363,6 +364,47 @@ int         lol_gpu_render_views_blend(lol_gpu* ctx, const lol_frame_camera* cam
                                        const lol_gpu_debug* dbg, void* stream);
 int         lol_gpu_set_view_blends(lol_gpu* ctx, int enable);
 int         lol_gpu_view_blends(const lol_gpu* ctx);
+
+/*
+ * Supersampled blends: s x s samples under each of K cameras — a lens blur or a shutter blur whose in-focus and stationary edges
+ * are as smooth as a supersampled frame's.  K = cams_per_view in {1, 2, 4, 8, 16}, s = samples in {1, 2, 4}; `cams` as for
+ * lol_gpu_render_views_blend.  Pixel (x, y) of view v:
+ *   1. for each k, m_k is the LINEAR mean of lol_gpu_set_samples, steps 1 - 2, under cams[v * K + k]: the s^2 samples are the pixels
+ *      (s x + i, s y + j) of the reference's s w x s h frame, taken as clamped linear colours, summed in order j s + i as the
+ *      balanced binary32 tree, and the sum is multiplied by 1 / s^2;
+ *   2. m_0 ... m_{K - 1} are summed in order of k as the balanced binary32 tree of lol_gpu_render_views_blend, step 2, and the sum
+ *      is multiplied by 1 / K;
+ *   3. the result goes through gamma and the context's pixel format exactly as one sample's colour does.
+ * The order of rounding is exactly this — scale by 1 / s^2 per camera first, then the tree over the cameras — and NOT one tree over
+ * K s^2 leaves: the two differ on subnormal channels.
+ * So s = 1 IS lol_gpu_render_views_blend (the call forwards to it: K = 1 with s = 1 keeps all diagnostics), K = 1 with s > 1 IS
+ * lol_gpu_render_views_samples(..., samples, -1, ...) (the call forwards to it), and K equal cameras with s > 1 give that camera's
+ * supersampled view bit for bit.
+ * Addressing, the copy of `cams`, `stream`, the ring of 8 record sets, the fixed tile order and "neither reads nor changes
+ * LOL_GPU_TILES_LPT / _AUTO, lol_gpu_set_samples, lol_gpu_set_adaptive_samples": all as lol_gpu_render_views_blend; what a view's
+ * camera decides is decided per RECORD.  lol_gpu_debug.rgb is the mean after gamma, dense [v][y][x].
+ * With K > 1 and s > 1 the call is one copy of the n_views * K records and two launches on its stream: every camera's linear means
+ * — the s x s samples of a pixel are neighbouring lanes of one wave and are reduced in registers —, then the means over the cameras.
+ * The scratch therefore holds one colour per PIXEL and camera, not per sample: 16 * n_views * K * w * h bytes per call, from the
+ * same ring of 4 sets as lol_gpu_render_views_blend, with the same behaviour when an allocation fails (LOL_GPU_ERR_HIP, nothing
+ * launched, the context stays usable).
+ * Refused, nothing launched and nothing written: s outside {1, 2, 4} (LOL_GPU_ERR_ARG); everything lol_gpu_render_views_blend
+ * refuses, in its order; a number of samples this build's wave patch cannot take (LOL_GPU_ERR_UNSUPPORTED, as lol_gpu_set_samples);
+ * hit_dist, hit_id or steps with K > 1 or s > 1 (LOL_GPU_ERR_UNSUPPORTED); a sample grid of more than 65535 tiles along an axis, or
+ * more than 2^32 - 1 lanes over all n_views * K sample grids (LOL_GPU_ERR_ARG).
+ * Which kernel: after lol_gpu_set_view_blend_samples(ctx, 1) BEFORE lol_gpu_upload_program the scene's own module also carries
+ * lol_render_spec_batch_aa_lin (both kernels of a 257 ... 1024-op scene do); otherwise, and until that module is ready, the
+ * interpreter's render_interp_batch_aa_lin renders — same pixels either way (lol_gpu_view_blend_samples_kernel_name,
+ * lol_gpu_diag.h).  The switch is its own: lol_gpu_set_view_blends and lol_gpu_set_view_samples together do not imply it, and a
+ * module compiled without it is the module it was before (same code object, same lol_gpu_kernel_key).
+ * Not built: an adaptive form (edge-adaptive samples under K cameras), row partitions, a lol_gpu_multi_* form, host surfaces.
+ */
+int         lol_gpu_render_views_blend_samples(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view,
+                                               int w, int h, int max_steps, int samples,
+                                               void* dst, size_t pitch_bytes, size_t view_stride_bytes,
+                                               const lol_gpu_debug* dbg, void* stream);
+int         lol_gpu_set_view_blend_samples(lol_gpu* ctx, int enable);   /* before lol_gpu_upload_program */
+int         lol_gpu_view_blend_samples(const lol_gpu* ctx);
 
 /* Name of the kernel a launch uses (for matching rocprofv3 kernel-trace rows):
  * "lol_render_spec" (scene-specialised, compiled by hipRTC at upload) or "render_interp"; with supersampling

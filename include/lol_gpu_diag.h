@@ -106,6 +106,19 @@ int         lol_gpu_compile_offline_view_blends(const lol_program* prog, const c
  * the test the launch itself makes: "lol_render_spec_batch_lin" / "render_interp_batch_lin"; lol_gpu_render_views' for
  * cams_per_view = 1.  (The second pass is always the library's own blend_resolve.) */
 const char* lol_gpu_view_blend_kernel_name(const lol_gpu* ctx, int cams_per_view);
+/*
+ * ... and for a context that asked for supersampled blends (lol_gpu_set_view_blend_samples) before its upload: enable = 0 writes
+ * exactly what lol_gpu_compile_offline_view_blends(..., others, ...) writes; 1 the same source with lol_render_spec_batch_aa_lin
+ * appended last, and its code object.  `others`: that function's mask of the context's other switches (1 = lol_gpu_set_view_blends,
+ * 2 = lol_gpu_set_samples > 1, 4 = lol_gpu_set_view_batches, 8 = lol_gpu_set_view_samples; LOL_GPU_ERR_ARG outside 0 ... 15).  form
+ * as above.  Needs no device.
+ */
+int         lol_gpu_compile_offline_view_blend_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                                       int enable, int others, int form, char* log, size_t logcap);
+/* The kernel the first pass of the NEXT lol_gpu_render_views_blend_samples(..., cams_per_view, ..., samples, ...) of this context
+ * launches, decided by the test the launch itself makes: "lol_render_spec_batch_aa_lin" / "render_interp_batch_aa_lin";
+ * lol_gpu_view_blend_kernel_name's for samples <= 1, lol_gpu_view_samples_kernel_name's (contrast -1) for cams_per_view <= 1. */
+const char* lol_gpu_view_blend_samples_kernel_name(const lol_gpu* ctx, int cams_per_view, int samples);
 /* The kernel the NEXT lol_gpu_render_views_samples(..., samples, contrast, ...) of this context launches, decided by the test the
  * launch itself makes: "lol_render_spec_batch_aa" / "render_interp_batch_aa" for contrast = -1, the refine pass's
  * "lol_render_spec_batch_aa_list" / "render_interp_batch_aa_list" for an adaptive batch, lol_gpu_render_views' for samples = 1.

@@ -18,8 +18,8 @@ extern "C" {
 int lol_gpu_testing_fail_uploads(lol_gpu* ctx, int n);
 
 /* The next `n` scratch allocations of adaptive batches (lol_gpu_render_views_samples with contrast >= 0) and of blends
- * (lol_gpu_render_views_blend with more than one camera per view) on this context fail as a hipMalloc without memory would: the
- * call returns LOL_GPU_ERR_HIP with nothing launched, and the context stays usable. */
+ * (lol_gpu_render_views_blend and lol_gpu_render_views_blend_samples with more than one camera per view) on this context fail
+ * as a hipMalloc without memory would: the call returns LOL_GPU_ERR_HIP with nothing launched, and the context stays usable. */
 int lol_gpu_testing_fail_view_scratch(lol_gpu* ctx, int n);
 
 /* The next `n` FIRST runs of the scene compiler for a scene of the middle sizes (257 ... 1024 ops: out-of-line form first, inlined

@@ -7,8 +7,10 @@ Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a
 (Renderer.render_views_into) and writes DIR/view_0000.ppm ...; --orbit-samples N supersamples the views of that batch (N x N samples
 per pixel; with --orbit-adaptive T only at the edges of each view); --orbit N --orbit-shutter K blurs each of the N views by the motion
 inside its own exposure: view v is the mean in linear light of cameras v K ... v K + K - 1 of scene.orbit_cameras(scene, N K)
-(Renderer.render_blended_views_into).  --lens R --focus D --lens-samples K renders ONE frame with depth of field: the mean over the K
-cameras of scene.lens_cameras on a lens of radius R focused at distance D.  There is no CPU rendering path."""
+(Renderer.render_blended_views_into); with --orbit-samples S beside it every one of those cameras is supersampled S x S (not with
+--orbit-adaptive).  --lens R --focus D --lens-samples K renders ONE frame with depth of field: the mean over the K cameras of
+scene.lens_cameras on a lens of radius R focused at distance D; with --samples S every lens camera is supersampled S x S (not with
+--adaptive).  There is no CPU rendering path."""
 from __future__ import annotations
 
 import argparse
@@ -34,17 +36,20 @@ def orbit(sc, args, w, h) -> int:
     r = gpu.Renderer(args.device)
     try:
         r.set_view_batches(True)             # before prepare(): the scene's own kernel then carries the batch form
-        if args.orbit_samples > 1:
+        if args.orbit_samples > 1 and shutter == 1:
             r.set_view_samples(True)         # ... and the supersampled batch forms
-        if shutter > 1:
+        if shutter > 1 and args.orbit_samples == 1:
             r.set_view_blends(True)          # ... and the linear-colour form of blends
+        if shutter > 1 and args.orbit_samples > 1:
+            r.set_view_blend_samples(True)   # ... and its supersampled form
         r.prepare(sc)
         views = np.zeros((k, h, w), dtype=np.uint32)
         dev = r.malloc(views.nbytes)
         try:
             t0 = time.perf_counter()
             if shutter > 1:
-                r.render_blended_views_into(dev, S.orbit_cameras(sc, k * shutter), shutter, w, h, args.max_steps)
+                r.render_blended_views_into(dev, S.orbit_cameras(sc, k * shutter), shutter, w, h, args.max_steps,
+                                            samples=args.orbit_samples)
             else:
                 r.render_views_into(dev, S.orbit_cameras(sc, k), w, h, args.max_steps, samples=args.orbit_samples,
                                     adaptive=args.orbit_adaptive if args.orbit_samples > 1 else -1)
@@ -66,14 +71,17 @@ def lens(sc, args, w, h) -> int:
     """one frame averaged over the cameras of a lens into one PPM"""
     r = gpu.Renderer(args.device)
     try:
-        r.set_view_blends(True)
+        if args.samples > 1:
+            r.set_view_blend_samples(True)   # before prepare(): the scene's own kernel then carries the supersampled linear form
+        else:
+            r.set_view_blends(True)
         r.prepare(sc)
         surf = np.zeros((h, w), dtype=np.uint32)
         dev = r.malloc(surf.nbytes)
         try:
             t0 = time.perf_counter()
             r.render_blended_views_into(dev, S.lens_cameras(sc.camera, args.focus, args.lens, args.lens_samples), args.lens_samples,
-                                        w, h, args.max_steps)
+                                        w, h, args.max_steps, samples=args.samples)
             r.sync()
             dt = (time.perf_counter() - t0) * 1e3
             r.memcpy_d2h(surf.ctypes.data, dev, surf.nbytes)
@@ -131,16 +139,19 @@ def main(argv=None) -> int:
         if args.lens:
             print("--orbit does not go with --lens: the lens mode renders one frame", file=sys.stderr)
             return 1
-        if args.orbit_shutter > 1 and (args.orbit_samples != 1 or args.orbit * args.orbit_shutter > gpu.MAX_VIEWS):
-            print(f"--orbit N --orbit-shutter K takes N K <= {gpu.MAX_VIEWS} cameras; not with --orbit-samples", file=sys.stderr)
+        if args.orbit_shutter > 1 and args.orbit * args.orbit_shutter > gpu.MAX_VIEWS:
+            print(f"--orbit N --orbit-shutter K takes N K <= {gpu.MAX_VIEWS} cameras", file=sys.stderr)
+            return 1
+        if args.orbit_shutter > 1 and args.orbit_samples > 1 and args.orbit_adaptive != -1:
+            print("--orbit-shutter K with --orbit-samples S samples every pixel: not with --orbit-adaptive", file=sys.stderr)
             return 1
         return orbit(sc, args, w, h)
     if args.orbit_samples != 1 or args.orbit_adaptive != -1 or args.orbit_shutter != 1:
         print("--orbit-samples, --orbit-adaptive and --orbit-shutter go with --orbit K", file=sys.stderr)
         return 1
     if args.lens:
-        if args.lens < 0 or not args.focus > 0 or args.samples != 1 or args.adaptive != -1 or args.frames != 1:
-            print("--lens R takes a radius > 0 and --focus D > 0; not with --samples, --adaptive or --frames", file=sys.stderr)
+        if args.lens < 0 or not args.focus > 0 or args.adaptive != -1 or args.frames != 1:
+            print("--lens R takes a radius > 0 and --focus D > 0; not with --adaptive or --frames", file=sys.stderr)
             return 1
         return lens(sc, args, w, h)
     r = gpu.Renderer(args.device)

@@ -6,7 +6,7 @@
  */
 #include "lol_gpu_internal.h"
 
-/* lol_kernel.h's, lol_kernel_aa.h's, lol_kernel_batch.h's, lol_kernel_batch_aa.h's and lol_kernel_blend.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
+/* lol_kernel.h's, lol_kernel_aa.h's, lol_kernel_batch.h's, lol_kernel_batch_aa.h's, lol_kernel_blend.h's and lol_kernel_blend_aa.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
 #include "lol_kernel_src.inc"
 
 #pragma GCC visibility push(hidden)
@@ -883,6 +883,17 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 		s += "\tlol::store_linear_view(L, P.rgb);\n";
 		s += "}\n";
 	}
+	/* Supersampled blends (lol_gpu_set_view_blend_samples before the upload, a switch of its own): lol_render_spec_batch_aa's
+	 * pipeline on the sample grid of the block's record, every pixel's samples reduced to their LINEAR mean and that stored into
+	 * the blend's scratch (lol_kernel_blend_aa.h).  Appended after everything else, for the reason above.  No step counters. */
+	if (carries.carries(SWITCH_BATCH_BLEND_AA)) {
+		s += "#include \"lol_kernel_blend_aa.h\"\n";
+		s += head + K[FAM_BATCH_AA_LIN].symbol + "(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
+		s += "\tconst lol::Launch S = lol::sample_launch(lol::view_launch(L, B.views));\n";
+		s += shade("\t", "S", "S", "false", "");
+		s += "\tlol::store_linear_view_aa(L, P.rgb);\n";
+		s += "}\n";
+	}
 	return s;
 }
 
@@ -1002,7 +1013,7 @@ bool has_return_clobbering_branch(const std::vector<char>& code) { return has_re
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
                   std::string& log, std::string* src_out, bool cull, int form, ModuleKernels carries) {
 	const bool aa = carries.carries(SWITCH_AA), batch = carries.carries(SWITCH_BATCH), batch_aa = carries.carries(SWITCH_BATCH_AA);
-	const bool blend = carries.carries(SWITCH_BATCH_BLEND);
+	const bool blend = carries.carries(SWITCH_BATCH_BLEND), blend_aa = carries.carries(SWITCH_BATCH_BLEND_AA);
 	std::string src = generate_source(P, fast, cull, form, carries);
 	if (src_out) *src_out = src;
 	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
@@ -1068,7 +1079,9 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	const std::string disk_key = key + "|" + LOL_KERNEL_H_TEXT + (aa ? std::string("|") + LOL_KERNEL_AA_H_TEXT : std::string()) +
 	                             (batch ? std::string("|batch|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT : std::string()) +
 	                             (batch_aa ? std::string("|batch_aa|") + LOL_KERNEL_BATCH_AA_H_TEXT : std::string()) +
-	                             (blend ? std::string("|blend|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT + "|" + LOL_KERNEL_BLEND_H_TEXT : std::string());
+	                             (blend ? std::string("|blend|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT + "|" + LOL_KERNEL_BLEND_H_TEXT : std::string()) +
+	                             (blend_aa ? std::string("|blend_aa|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT + "|" + LOL_KERNEL_BATCH_AA_H_TEXT +
+	                                         "|" + LOL_KERNEL_BLEND_H_TEXT + "|" + LOL_KERNEL_BLEND_AA_H_TEXT : std::string());
 	if (disk_cache_load(disk_key, code)) {
 		std::lock_guard<std::mutex> lock(g_cache_mutex);
 		g_code_cache[key] = code;
@@ -1080,12 +1093,18 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	/* ... and lol_kernel_batch_aa.h (which includes lol_kernel_batch.h) only where it carries the supersampled batch kernels */
 	/* ... and lol_kernel_blend.h (which includes lol_kernel_batch.h) only where it carries the linear-colour batch kernel: last, so
 	 * that a module without it is handed the very list it was handed before that file existed */
-	const char* hdr_src[5] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT, nullptr };
-	const char* hdr_name[5] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h", nullptr };
-	int n_hdr = batch_aa ? 4 : batch ? 3 : aa ? 2 : 1;
-	if (blend) {
+	/* ... and lol_kernel_blend_aa.h (which includes lol_kernel_batch_aa.h and lol_kernel_blend.h) only where it carries the supersampled
+	 * linear kernel: behind those two, last of all */
+	const char* hdr_src[6] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT, nullptr, nullptr };
+	const char* hdr_name[6] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h", nullptr, nullptr };
+	int n_hdr = batch_aa || blend_aa ? 4 : batch ? 3 : aa ? 2 : 1;
+	if (blend || blend_aa) {
 		n_hdr = std::max(n_hdr, 3);
 		hdr_src[n_hdr] = LOL_KERNEL_BLEND_H_TEXT; hdr_name[n_hdr] = "lol_kernel_blend.h";
+		n_hdr++;
+	}
+	if (blend_aa) {
+		hdr_src[n_hdr] = LOL_KERNEL_BLEND_AA_H_TEXT; hdr_name[n_hdr] = "lol_kernel_blend_aa.h";
 		n_hdr++;
 	}
 	hiprtcProgram prog = nullptr;
@@ -1235,6 +1254,16 @@ int lol_gpu_compile_offline_view_blends(const lol_program* prog, const char* arc
 	/* bit 0: lol_gpu_set_view_blends; bits 1 - 3: the context's other switches beside it (samples > 1, view batches, view samples) */
 	return compile_offline(prog, arch, out_base, assume_fast, { (enable & 2) != 0, (enable & 4) != 0, (enable & 8) != 0, (enable & 1) != 0 },
 	                       form, log, logcap);
+}
+
+/* ... and the module a context with lol_gpu_set_view_blend_samples(ctx, enable) compiles at its upload (lol_gpu_diag.h) */
+int lol_gpu_compile_offline_view_blend_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                               int others, int form, char* log, size_t logcap) {
+	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
+	if (others < 0 || others > 15) return LOL_GPU_ERR_ARG;
+	/* others: lol_gpu_compile_offline_view_blends' mask of the context's other switches */
+	return compile_offline(prog, arch, out_base, assume_fast,
+	                       { (others & 2) != 0, (others & 4) != 0, (others & 8) != 0, (others & 1) != 0, enable != 0 }, form, log, logcap);
 }
 
 static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, ModuleKernels carries,

@@ -99,6 +99,7 @@ const void* interp_kernel(KernelFamily f) {
 	case FAM_BATCH_AA:      return reinterpret_cast<const void*>(&lol::render_interp_batch_aa<SSIZE, KIND, TABLES_GLOBAL>);
 	case FAM_BATCH_AA_LIST: return reinterpret_cast<const void*>(&lol::render_interp_batch_aa_list<SSIZE, KIND, TABLES_GLOBAL>);
 	case FAM_BATCH_LIN:     return reinterpret_cast<const void*>(&lol::render_interp_batch_lin<SSIZE, KIND, TABLES_GLOBAL>);
+	case FAM_BATCH_AA_LIN:  return reinterpret_cast<const void*>(&lol::render_interp_batch_aa_lin<SSIZE, KIND, TABLES_GLOBAL>);
 	default:                return nullptr;
 	}
 }
@@ -1211,6 +1212,16 @@ int lol_gpu_render_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, int
 	return view_records_done(ctx, *S, s, e, "kernel launch (supersampled batch of views)");
 }
 
+/* what lol_gpu_render_views_blend refuses before it looks at anything else, in its order (everything lol_gpu_render_views refuses
+ * first: no program before any word about K) */
+static int blend_refused(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int K, int w, int h, int max_steps, const void* dst,
+                         size_t pitch_bytes, size_t view_stride_bytes) {
+	LOL_TRY(batch_refused(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
+	if (K != 1 && K != 2 && K != 4 && K != 8 && K != 16) return fail(ctx, LOL_GPU_ERR_ARG, "cameras per view must be 1, 2, 4, 8 or 16");
+	if ((long long)n_views * K > LOL_GPU_MAX_VIEWS) return fail(ctx, LOL_GPU_ERR_ARG, "a blend holds at most LOL_GPU_MAX_VIEWS cameras in all");
+	return LOL_GPU_OK;
+}
+
 /*
  * Views averaged over K cameras: two launches on `s` behind ONE copy of the n K records, no host wait between them.
  *  1. the linear-colour batch kernel (lol_kernel_blend.h) over z = v K + k, into the scratch set: everything a batch decides per
@@ -1218,21 +1229,22 @@ int lol_gpu_render_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, int
  *  2. blend_resolve: each pixel's tree over its K colours, gamma, packing, the stores.
  * Scratch: the next set of a ring of its own (lol_gpu_internal.h, BlendSet), behind the blend that used it last; the host waits for
  * that blend only where the set has to grow, or on one of HIP's special stream handles.  Fixed tile order, like any batch.
+ * K > 1 here, and `samples` x `samples` samples per pixel: with samples > 1 pass 1 is the supersampled linear kernel
+ * (lol_kernel_blend_aa.h) over the SAMPLE grids, on the launch of lol_gpu_render_views_samples.  It reduces a pixel's samples in
+ * registers before it stores, so the scratch holds one LinearColour per PIXEL and record either way: the ring, grow_scratch and the
+ * resolve pass are the same for both.
  */
-int lol_gpu_render_views_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view, int w, int h, int max_steps,
-                               void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
-	/* (everything lol_gpu_render_views refuses first, in its order: no program before any word about K) */
-	LOL_TRY(batch_refused(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
-	const int K = cams_per_view;
-	if (K != 1 && K != 2 && K != 4 && K != 8 && K != 16) return fail(ctx, LOL_GPU_ERR_ARG, "cameras per view must be 1, 2, 4, 8 or 16");
-	if ((long long)n_views * K > LOL_GPU_MAX_VIEWS) return fail(ctx, LOL_GPU_ERR_ARG, "a blend holds at most LOL_GPU_MAX_VIEWS cameras in all");
-	if (K == 1) return render_views_plain(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+static int render_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int K, int w, int h, int max_steps, int samples,
+                        void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
+	if (samples > 1 && !lol::samples_fit_wave(samples))
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "this build's wave patch (LOL_WAVE_W x LOL_WAVE_H) does not divide into that many samples per axis");
 	if (dbg && (dbg->hit_dist || dbg->hit_id || dbg->steps))
 		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "hit_dist, hit_id and steps have no single value for a pixel averaged over cameras");
 	const int n_rays = n_views * K;
 	dim3 grid;
-	if (!batch_grid(ctx, w, h, n_rays, &grid))
-		return fail(ctx, LOL_GPU_ERR_ARG, "blend too large for one launch over all its cameras: fewer views per call");
+	if (!batch_grid(ctx, (long long)samples * w, (long long)samples * h, n_rays, &grid))
+		return fail(ctx, LOL_GPU_ERR_ARG, samples > 1 ? "blend too large for one launch in samples over all its cameras: fewer views per call"
+		                                              : "blend too large for one launch over all its cameras: fewer views per call");
 	hipStream_t s;
 	LOL_TRY(batch_stream(ctx, stream, &s));
 	const int si = (int)(ctx->blend_rr++ % lol_gpu::BLEND_SETS);
@@ -1243,14 +1255,18 @@ int lol_gpu_render_views_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n
 	if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.done));
 	lol_gpu::ViewSet* V = nullptr;
 	LOL_TRY(queue_view_records(ctx, cams, n_rays, max_steps, s, &V));
-	batch_range("blend", n_rays, w, h);
+	batch_range(samples > 1 ? "supersampled blend" : "blend", n_rays, w, h);
 	/* 1. the linear colours: the launch's destination is the scratch (no diagnostics: they are the resolve's) */
 	lol::Launch L;
 	batch_launch(ctx, w, h, max_steps, S.d_buf, (size_t)w * 4, nullptr, L);
+	if (samples > 1) {
+		L.fw = (float)(samples * w); L.fh = (float)(samples * h);      /* the size of the sample grid */
+		L.flags |= samples == 4 ? lol::FLAG_SAMPLES_4 : lol::FLAG_SAMPLES_2;
+	}
 	lol::BatchTail B = { V->d_views, 0ull };
 	const char* what = "kernel launch (blend of views, linear pass)";
 	void* args[] = { &L, &B };
-	hipError_t e = launch_family(ctx, FAM_BATCH_LIN, false, args, grid, s);
+	hipError_t e = launch_family(ctx, samples > 1 ? FAM_BATCH_AA_LIN : FAM_BATCH_LIN, false, args, grid, s);
 	/* 2. the means */
 	if (e == hipSuccess) {
 		what = "kernel launch (blend of views, resolve pass)";
@@ -1274,6 +1290,49 @@ int lol_gpu_render_views_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n
 	LOL_TRY(view_records_done(ctx, *V, s, e, what));
 	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (blend of views)", e2);
 	return LOL_GPU_OK;
+}
+
+int lol_gpu_render_views_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view, int w, int h, int max_steps,
+                               void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
+	LOL_TRY(blend_refused(ctx, cams, n_views, cams_per_view, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
+	if (cams_per_view == 1) return render_views_plain(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+	return render_blend(ctx, cams, n_views, cams_per_view, w, h, max_steps, 1, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+}
+
+/*
+ * A supersampled blend: s x s samples under each of K cameras.  s = 1 IS lol_gpu_render_views_blend — the same two functions behind
+ * the same refusals, render_views_plain for K = 1 (all diagnostics) and render_blend with one sample — and K = 1 IS
+ * lol_gpu_render_views_samples without a contrast, which is called.  Otherwise render_blend with the supersampled linear kernel in
+ * pass 1: 1 / s^2 per camera there, the tree over the cameras in blend_resolve.
+ */
+int lol_gpu_render_views_blend_samples(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view, int w, int h,
+                                       int max_steps, int samples, void* dst, size_t pitch_bytes, size_t view_stride_bytes,
+                                       const lol_gpu_debug* dbg, void* stream) {
+	if (!ctx || !cams || !dst) return LOL_GPU_ERR_ARG;
+	if (samples != 1 && samples != 2 && samples != 4) return fail(ctx, LOL_GPU_ERR_ARG, "samples per axis must be 1, 2 or 4");
+	LOL_TRY(blend_refused(ctx, cams, n_views, cams_per_view, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
+	/* s = 1: what lol_gpu_render_views_blend does behind the refusals just made */
+	if (samples == 1 && cams_per_view == 1)
+		return render_views_plain(ctx, cams, n_views, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+	/* K = 1: the supersampled batch (its own refusals — the wave patch, the diagnostics, the grid in samples — are still to be made) */
+	if (cams_per_view == 1)
+		return lol_gpu_render_views_samples(ctx, cams, n_views, w, h, max_steps, samples, -1, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+	return render_blend(ctx, cams, n_views, cams_per_view, w, h, max_steps, samples, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+}
+
+int lol_gpu_set_view_blend_samples(lol_gpu* ctx, int enable) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	ctx->view_blend_samples = enable ? 1 : 0;      /* takes effect at the next lol_gpu_upload_program */
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_view_blend_samples(const lol_gpu* ctx) { return ctx ? ctx->view_blend_samples : LOL_GPU_ERR_ARG; }
+
+const char* lol_gpu_view_blend_samples_kernel_name(const lol_gpu* ctx, int cams_per_view, int samples) {
+	if (!ctx) return "";
+	if (samples <= 1) return lol_gpu_view_blend_kernel_name(ctx, cams_per_view);
+	if (cams_per_view <= 1) return lol_gpu_view_samples_kernel_name(ctx, samples, -1);
+	return family_name(ctx, FAM_BATCH_AA_LIN);
 }
 
 int lol_gpu_set_view_blends(lol_gpu* ctx, int enable) {

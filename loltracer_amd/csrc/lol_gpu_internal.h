@@ -23,6 +23,7 @@
 #include "lol_kernel_batch.h"
 #include "lol_kernel_batch_aa.h"
 #include "lol_kernel_blend.h"
+#include "lol_kernel_blend_aa.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -131,9 +132,10 @@ struct OwnedProgram {
 /* The families of render kernels, each of which exists twice: as an instantiation of the interpreter (lol_kernel*.h) and as a symbol
  * of the scene module (generate_source).  THE list: generate_source emits the symbols, load_scene_kernel looks them up, launch_family
  * (lol_gpu.hip) launches one or the other and the reported kernel names come from here.  A new family is one row plus its kernel. */
-enum KernelFamily { FAM_FRAME, FAM_FRAME_AA, FAM_FRAME_AA_LIST, FAM_BATCH, FAM_BATCH_AA, FAM_BATCH_AA_LIST, FAM_BATCH_LIN, N_FAMILIES };
+enum KernelFamily { FAM_FRAME, FAM_FRAME_AA, FAM_FRAME_AA_LIST, FAM_BATCH, FAM_BATCH_AA, FAM_BATCH_AA_LIST, FAM_BATCH_LIN, FAM_BATCH_AA_LIN,
+                    N_FAMILIES };
 /* the switch of the context that puts a family into the module of the next upload */
-enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA, SWITCH_BATCH_BLEND };
+enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA, SWITCH_BATCH_BLEND, SWITCH_BATCH_BLEND_AA };
 struct FamilyRow {
 	const char*  symbol;        /* in the scene module */
 	const char*  counting;      /* its twin with the per-lane step counters (modules up to LOL_SPEC_TWO_KERNELS_MAX_OPS ops), or none */
@@ -148,17 +150,19 @@ constexpr FamilyRow KERNEL_FAMILIES[N_FAMILIES] = {
 	/* FAM_BATCH_AA      (L, B)           */ { "lol_render_spec_batch_aa",      nullptr,                       "render_interp_batch_aa",      SWITCH_BATCH_AA },
 	/* FAM_BATCH_AA_LIST (L, B, Q)        */ { "lol_render_spec_batch_aa_list", nullptr,                       "render_interp_batch_aa_list", SWITCH_BATCH_AA },
 	/* FAM_BATCH_LIN     (L, B)           */ { "lol_render_spec_batch_lin",     nullptr,                       "render_interp_batch_lin",     SWITCH_BATCH_BLEND },
+	/* FAM_BATCH_AA_LIN  (L, B)           */ { "lol_render_spec_batch_aa_lin",  nullptr,                       "render_interp_batch_aa_lin",  SWITCH_BATCH_BLEND_AA },
 };
 
 /* What a scene module carries beside lol_render_spec and lol_sdf_spec.  Without any of it the source is exactly what it was before
  * these kernels existed.  aa: lol_gpu_set_samples > 1 at the upload; batch: lol_gpu_set_view_batches; batch_aa:
  * lol_gpu_set_view_samples, which brings the plain batch kernels with it (the first pass of an adaptive batch is theirs); blend:
- * lol_gpu_set_view_blends, the linear-colour batch kernel alone (lol_kernel_blend.h). */
+ * lol_gpu_set_view_blends, the linear-colour batch kernel alone (lol_kernel_blend.h); blend_aa: lol_gpu_set_view_blend_samples, its
+ * supersampled form alone (lol_kernel_blend_aa.h) — a switch of its own, NOT implied by blend and batch_aa together. */
 struct ModuleKernels {
-	bool aa = false, batch = false, batch_aa = false, blend = false;
+	bool aa = false, batch = false, batch_aa = false, blend = false, blend_aa = false;
 	bool carries(ModuleSwitch sw) const {
 		return sw == SWITCH_NONE || (sw == SWITCH_AA && aa) || (sw == SWITCH_BATCH && (batch || batch_aa)) || (sw == SWITCH_BATCH_AA && batch_aa) ||
-		       (sw == SWITCH_BATCH_BLEND && blend);
+		       (sw == SWITCH_BATCH_BLEND && blend) || (sw == SWITCH_BATCH_BLEND_AA && blend_aa);
 	}
 };
 
@@ -245,6 +249,7 @@ struct lol_gpu {
 	int          view_batches = 0;       /* lol_gpu_set_view_batches: the next upload's module carries lol_render_spec_batch */
 	int          view_samples = 0;       /* lol_gpu_set_view_samples: ... and lol_render_spec_batch_aa / _aa_list (and the batch kernels) */
 	int          view_blends = 0;        /* lol_gpu_set_view_blends: ... and lol_render_spec_batch_lin */
+	int          view_blend_samples = 0; /* lol_gpu_set_view_blend_samples: ... and lol_render_spec_batch_aa_lin */
 	/* The view records of batches (lol_gpu_render_views, lol_gpu.hip): a ring of sets, one per batch, whatever its stream.  A batch
 	 * fills its set's pinned host copy, queues the copy to the device and the launch behind it on its stream, and records `done`;
 	 * the next batch through the set waits for `copied` on the host (the pinned copy is the host's to write again) and for `done`
@@ -287,8 +292,8 @@ struct lol_gpu {
 	unsigned     view_adaptive_rr = 0;
 	int          view_adaptive_last = -1;      /* the set of the last adaptive batch (lol_gpu_views_refined) */
 	int          fail_view_scratch = 0;        /* lol_gpu_testing_fail_view_scratch: that many scratch allocations of adaptive batches and blends still fail */
-	/* ... of blends (lol_gpu_render_views_blend), a ring of its own: the linear colours [n K][h][w] of pass 1, a lol::LinearColour of
-	 * 16 bytes each.  A blend waits on its set's `done` (behind the last blend that used it) and records it again at its end. */
+	/* ... of blends (lol_gpu_render_views_blend, lol_gpu_render_views_blend_samples), a ring of its own: the linear colours [n K][h][w]
+	 * of pass 1 — per PIXEL, whatever the samples —, a lol::LinearColour of 16 bytes each.  A blend waits on its set's `done` (behind the last blend that used it) and records it again at its end. */
 	struct BlendSet : ScratchSet {
 		hipEvent_t done = nullptr;
 	};

@@ -219,6 +219,18 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_compile_offline_view_blends.restype = C.c_int
         lib.lol_gpu_view_blend_kernel_name.argtypes = [vp, C.c_int]
         lib.lol_gpu_view_blend_kernel_name.restype = C.c_char_p
+        lib.lol_gpu_render_views_blend_samples.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                                           C.c_size_t, C.c_size_t, P(Debug), vp]
+        lib.lol_gpu_render_views_blend_samples.restype = C.c_int
+        lib.lol_gpu_set_view_blend_samples.argtypes = [vp, C.c_int]
+        lib.lol_gpu_set_view_blend_samples.restype = C.c_int
+        lib.lol_gpu_view_blend_samples.argtypes = [vp]
+        lib.lol_gpu_view_blend_samples.restype = C.c_int
+        lib.lol_gpu_compile_offline_view_blend_samples.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                                   C.c_char_p, C.c_size_t]
+        lib.lol_gpu_compile_offline_view_blend_samples.restype = C.c_int
+        lib.lol_gpu_view_blend_samples_kernel_name.argtypes = [vp, C.c_int, C.c_int]
+        lib.lol_gpu_view_blend_samples_kernel_name.restype = C.c_char_p
         lib.lol_gpu_views_refined.argtypes = [vp, P(C.c_int64)]
         lib.lol_gpu_views_refined.restype = C.c_int
         lib.lol_gpu_interp_variant.argtypes = [vp, P(C.c_int), P(C.c_int)]
@@ -339,6 +351,7 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_adaptive_samples", "lol_gpu_render_views", "lol_gpu_set_view_batches", "lol_gpu_view_batches",
     "lol_gpu_render_views_samples", "lol_gpu_set_view_samples", "lol_gpu_view_samples",
     "lol_gpu_render_views_blend", "lol_gpu_set_view_blends", "lol_gpu_view_blends",
+    "lol_gpu_render_views_blend_samples", "lol_gpu_set_view_blend_samples", "lol_gpu_view_blend_samples",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
@@ -347,6 +360,7 @@ DIAG_SYMBOLS = [                                                        # includ
     "lol_gpu_sdf_batch", "lol_gpu_compile_offline_samples", "lol_gpu_adaptive_refined", "lol_gpu_adaptive_pass_ms",
     "lol_gpu_compile_offline_views", "lol_gpu_compile_offline_view_samples", "lol_gpu_view_samples_kernel_name",
     "lol_gpu_views_refined", "lol_gpu_interp_variant", "lol_gpu_compile_offline_view_blends", "lol_gpu_view_blend_kernel_name",
+    "lol_gpu_compile_offline_view_blend_samples", "lol_gpu_view_blend_samples_kernel_name",
 ]
 
 
@@ -410,6 +424,21 @@ def compile_offline_view_blends(program: S.Program, out_base: str, enable: bool 
     mask = int(bool(enable)) | int(bool(samples)) << 1 | int(bool(view_batches)) << 2 | int(bool(view_samples)) << 3
     st = gpu_lib().lol_gpu_compile_offline_view_blends(C.byref(program), arch.encode(), os.fsencode(out_base),
                                                        int(assume_fast), mask, int(form), log, len(log))
+    if st != LOL_GPU_OK:
+        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
+    return log.value.decode(errors="replace")
+
+
+def compile_offline_view_blend_samples(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
+                                       assume_fast: bool = False, view_blends: bool = False, samples: bool = False,
+                                       view_batches: bool = False, view_samples: bool = False) -> str:
+    """compile_offline for a context with set_view_blend_samples(enable) before its upload: adds lol_render_spec_batch_aa_lin, last.
+    form as for compile_offline_views.  view_blends / samples / view_batches / view_samples: the context's other switches set beside
+    it.  Needs no device."""
+    log = C.create_string_buffer(1 << 16)
+    others = int(bool(view_blends)) | int(bool(samples)) << 1 | int(bool(view_batches)) << 2 | int(bool(view_samples)) << 3
+    st = gpu_lib().lol_gpu_compile_offline_view_blend_samples(C.byref(program), arch.encode(), os.fsencode(out_base),
+                                                              int(assume_fast), int(bool(enable)), others, int(form), log, len(log))
     if st != LOL_GPU_OK:
         raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
     return log.value.decode(errors="replace")
@@ -582,14 +611,31 @@ class Renderer:
         """the kernel the first pass of the next render_blended_views_into(..., cameras_per_view, ...) launches"""
         return self._lib.lol_gpu_view_blend_kernel_name(self._ctx, int(cameras_per_view)).decode()
 
+    def set_view_blend_samples(self, enable: bool):
+        """Before prepare(): the scene's own module also carries the supersampled linear-colour batch kernel
+        (lol_render_spec_batch_aa_lin); without it — and until that module is ready — render_blended_views_into(..., samples > 1)
+        runs its first pass on the interpreter's render_interp_batch_aa_lin.  Same pixels either way.  A switch of its own:
+        set_view_blends and set_view_samples together do not imply it."""
+        self._check(self._lib.lol_gpu_set_view_blend_samples(self._ctx, 1 if enable else 0))
+
+    @property
+    def view_blend_samples(self) -> bool:
+        return bool(self._lib.lol_gpu_view_blend_samples(self._ctx))
+
+    def view_blend_samples_kernel_name(self, cameras_per_view: int, samples: int) -> str:
+        """the kernel the first pass of the next render_blended_views_into(..., cameras_per_view, ..., samples=samples) launches"""
+        return self._lib.lol_gpu_view_blend_samples_kernel_name(self._ctx, int(cameras_per_view), int(samples)).decode()
+
     def render_blended_views_into(self, dst_ptr: int, cameras, cameras_per_view: int, w: int, h: int, max_steps: int = 256,
                                   pitch_bytes: int | None = None, view_stride_bytes: int | None = None, debug: Debug | None = None,
-                                  stream: int | None = None):
+                                  stream: int | None = None, samples: int = 1):
         """Asynchronously render len(cameras) / cameras_per_view views of w x h, each the mean IN LINEAR LIGHT of the frames under its
         K = cameras_per_view cameras (lol_gpu_render_views_blend): view v averages cameras[v K ... v K + K - 1] — the cameras of a
         shutter interval (scene.shutter_cameras: motion blur) or of a lens (scene.lens_cameras: depth of field).  K in {1, 2, 4, 8,
         16}; K = 1 is render_views_into.  Addressing and `debug` as render_views_into (with K > 1: rgb alone, the mean after gamma).
-        cameras: scene.Camera or ready scene.FrameCamera objects (the array is copied before the call returns)."""
+        cameras: scene.Camera or ready scene.FrameCamera objects (the array is copied before the call returns).
+        samples > 1: samples x samples samples per pixel under EVERY camera (lol_gpu_render_views_blend_samples): each camera's
+        supersampled linear mean first, then the mean over the cameras; samples in {1, 2, 4}."""
         cams = list(cameras)
         k = int(cameras_per_view)
         if k < 1 or len(cams) % k:
@@ -600,9 +646,14 @@ class Renderer:
             C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
         pitch = pitch_bytes if pitch_bytes is not None else w * 4
         stride = view_stride_bytes if view_stride_bytes is not None else h * pitch
-        self._check(self._lib.lol_gpu_render_views_blend(
-            self._ctx, arr, len(cams) // k, k, w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride,
-            C.byref(debug) if debug is not None else None, _stream_arg(stream)))
+        dbg = C.byref(debug) if debug is not None else None
+        if samples == 1:
+            self._check(self._lib.lol_gpu_render_views_blend(
+                self._ctx, arr, len(cams) // k, k, w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride, dbg, _stream_arg(stream)))
+        else:
+            self._check(self._lib.lol_gpu_render_views_blend_samples(
+                self._ctx, arr, len(cams) // k, k, w, h, max_steps, int(samples), C.c_void_p(dst_ptr), pitch, stride, dbg,
+                _stream_arg(stream)))
 
     def render_host(self, host_ptr: int, w: int, h: int, max_steps: int = 256, camera: S.Camera | None = None,
                     pitch_bytes: int | None = None):
