@@ -617,6 +617,64 @@ int  lol_gpu_assemble_parts(lol_gpu* ctx, const void* parts, int n_parts, int ba
 int  lol_gpu_assemble_parts_at(lol_gpu* ctx, const void* parts, const lol_gpu_rows* part_rows, const uint32_t* part_row0,
                                int n_parts, int w, int h, void* dst, size_t pitch_bytes, void* stream);
 
+/*
+ * Ray queries: what a host asks about the scene's GEOMETRY — what is under the cursor, how far is the thing the camera looks at,
+ * will the camera walk through a wall, distance / object / normal for rays a torch pipeline brings itself — without a frame.
+ *
+ * Ray i is EXACTLY get_intersection(scene, ro_i, rd_i) (naive_renderer.c:48-69) with MAX_STEPS = max_steps, followed by
+ * p = v3add(ro, v3scale(rd, dist)) (:227) and get_normal(scene, p, dist) (:228), in the reference's arithmetic: the same device code
+ * the frames march with.  The normal is the reference's for escaped rays too (no miss skip applies to a query).  Nothing about a
+ * ray is assumed: the direction is used as given (not normalised, may be zero), any component may be non-finite, huge, denormal or
+ * -0, and each ray's answer is the reference's arithmetic on those bits, whatever the other rays of the list are.
+ *
+ * Queries neither use nor change the tile-order state, lol_gpu_set_samples / lol_gpu_set_adaptive_samples, the pixel format or the
+ * record rings: a frame after a query is the frame it would have been.  lol_gpu_set_miss_skip / lol_gpu_set_exact_skips do not apply
+ * (there is no shading); lol_gpu_set_cull applies as it does to frames: same answers either way.
+ *
+ * Out of scope: shading or shadow queries (colour along arbitrary rays), lol_gpu_multi_* forms, rays in host memory beyond the
+ * one-pixel lol_gpu_pick, and the renderer.h protocol.
+ */
+typedef struct lol_gpu_hits {     /* DEVICE pointers, each may be NULL (not all four); element i belongs to ray i */
+	float*    dist;               /* get_intersection().dist                               naive_renderer.c:68 */
+	uint32_t* id;                 /* get_intersection().id: 1-based top-level object, 0 = escaped        :65-66 */
+	uint32_t* steps;              /* iterations of the loop at :56 that ran                                     */
+	float*    normal;             /* 3 floats per ray: get_normal(scene, ro + rd * dist, dist)         :114-125 */
+} lol_gpu_hits;
+/*
+ * rays_dev: n x {ox, oy, oz, dx, dy, dz} in device memory, read only.  A NULL `normal` skips the four taps for the whole launch.
+ * Asynchronous on `stream` (NULL = the context's own stream; LOL_GPU_STREAM_DEFAULT as elsewhere): one launch, no host wait, no
+ * copy, no scratch.  n == 0 returns LOL_GPU_OK with nothing launched; nothing beyond element n - 1 of any output is written.
+ * Refused, with nothing launched and nothing written: no context, NULL rays_dev with n > 0, NULL out or all four outputs NULL,
+ * max_steps < 0, n > 2^32 - 1: LOL_GPU_ERR_ARG; no program: LOL_GPU_ERR_NO_PROGRAM.
+ */
+int  lol_gpu_trace_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_hits* out, void* stream);
+/*
+ * Ray i is the primary ray of pixel (x_i, y_i) = (xy_dev[2i], xy_dev[2i + 1]) of the w x h frame under `cam`, built as a frame
+ * builds it (naive_renderer.c:218-221, :188-190).  For a pixel inside the frame `dist` and `id` ARE lol_gpu_debug.hit_dist and
+ * hit_id of lol_gpu_render_device under that camera, bit for bit, and `steps` is the low 16 bits of its lol_gpu_debug.steps.
+ * Coordinates are not inspected by the host: a pair outside the frame gives the ray that formula gives (the coordinates as `int`).
+ * The sample rays of supersampling (lol_gpu_set_samples) are pixels (s x + i, s y + j) of the s w x s h frame under the same `cam`.
+ * Refusals as for lol_gpu_trace_rays (xy_dev in the place of rays_dev), and LOL_GPU_ERR_ARG for w < 1, h < 1 or a NULL cam.
+ */
+int  lol_gpu_trace_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
+                          const uint32_t* xy_dev, size_t n, const lol_gpu_hits* out, void* stream);
+/*
+ * The host convenience: one lol_gpu_trace_pixels of pixel (x, y) on the context's own stream, through a few dozen bytes of device
+ * memory the context owns from the first pick on; copies back, WAITS, and fills HOST memory.  x, y outside the frame:
+ * LOL_GPU_ERR_ARG.  It orders itself after frames already queued on the context's streams only as far as its own stream does, and
+ * does not touch frames in flight.
+ */
+typedef struct lol_gpu_hit { float dist; uint32_t id, steps; float normal[3]; } lol_gpu_hit;
+int  lol_gpu_pick(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps, int x, int y, lol_gpu_hit* out);
+/*
+ * Which kernel answers: after lol_gpu_set_ray_queries(ctx, 1) BEFORE lol_gpu_upload_program the scene's own module also carries
+ * lol_trace_spec (both kernels of a 257 ... 1024-op scene do); otherwise, and until that module is ready, the interpreter's
+ * trace_interp answers — same bits either way.  A module compiled without the switch is the module it was before the switch
+ * existed: same source, same code object, same lol_gpu_kernel_key.
+ */
+int  lol_gpu_set_ray_queries(lol_gpu* ctx, int enable);
+int  lol_gpu_ray_queries(const lol_gpu* ctx);
+
 #ifdef __cplusplus
 }
 #endif

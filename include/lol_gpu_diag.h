@@ -140,6 +140,17 @@ int         lol_gpu_views_refined(lol_gpu* ctx, int64_t* n);
  */
 int         lol_gpu_adaptive_refined(lol_gpu* ctx, int64_t* n);
 int         lol_gpu_adaptive_pass_ms(lol_gpu* ctx, float ms[3]);
+/* The kernel the NEXT ray query of this context (lol_gpu_trace_rays, lol_gpu_trace_pixels, lol_gpu_pick) launches, decided by the
+ * test the launch itself makes: "lol_trace_spec" / "trace_interp"; "" for a NULL context. */
+const char* lol_gpu_trace_kernel_name(const lol_gpu* ctx);
+/*
+ * ... and the module of a context that asked for ray queries (lol_gpu_set_ray_queries) before its upload: enable = 0 writes exactly
+ * what the module with `others` alone is; 1 the same source with `#include "lol_kernel_rays.h"` and lol_trace_spec appended last, and
+ * its code object.  `others`: lol_gpu_compile_offline_view_blend_samples' mask of the context's other switches with
+ * 16 = lol_gpu_set_view_blend_samples added (LOL_GPU_ERR_ARG outside 0 ... 31).  form as above.  Needs no device.
+ */
+int         lol_gpu_compile_offline_rays(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                         int enable, int others, int form, char* log, size_t logcap);
 
 #ifdef __cplusplus
 }

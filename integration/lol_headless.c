@@ -5,7 +5,7 @@
  *
  *   lol_headless <threads> <scene.lol> [--size WxH] [--frames N] [--out frame.ppm]
  *                [--orbit] [--keys SCRIPT] [--dump-camera FILE] [--pipeline | --pipeline-depth N]
- *                [--format NAME] [--resize-script WxH,WxH,..] [--dump-frames PREFIX]
+ *                [--format NAME] [--resize-script WxH,WxH,..] [--dump-frames PREFIX] [--pick X,Y]
  *                [renderer flags: --device N | --devices A,B,.. --max-steps N --samples N --adaptive T ...]
  *   --format NAME            pixel format of the surface, as SDL names it: xrgb8888 (default), argb8888, bgrx8888,
  *                            rgba8888, abgr8888; rgb565 and index8 exist to see the plug-in refuse them
@@ -16,6 +16,10 @@
  *   --keys "W,W,WA,<,<^,."   held keys per frame (W A S D, _ = Space, c = LCtrl, ^ v < > = arrows): the camera is moved
  *                            by main.c's update_camera before every frame, as the windowed host does with key events
  *   --dump-camera FILE       one line per frame: the camera's point and direction as binary32 hex
+ *   --pick X,Y               after the last frame: what is under pixel (X, Y) of the last frame's size under the camera as it then
+ *                            stands — "pick X,Y: id=.. dist=.. steps=.. normal=(..)", the line `python -m loltracer_amd --pick`
+ *                            prints.  One ray query (lol_gpu_pick) through a context of the host's own on --device N with
+ *                            --max-steps N: ray queries are no part of the renderer.h protocol, so the plug-in is not asked
  *
  * Protocol reproduced from main.c (the caller side of SURVEY.md §8b):
  *   - argv[1] = worker threads, argv[2] = scene file, argv[3..] go to render_prepare  (main.c:223-242)
@@ -61,6 +65,27 @@ static int format_by_name(const char* name, lol_gpu_pixel_format* f, int* bytes_
 	return 0;
 }
 
+/* --pick: one lol_gpu_pick on a context of this host's own (the interpreter answers: one ray does not wait for the scene compiler) */
+static int pick_pixel(const lol_scene* scene, int device, int w, int h, int max_steps, int x, int y) {
+	lol_program prog;
+	lol_gpu* ctx = NULL;
+	lol_gpu_hit hit;
+	lol_frame_camera fc;
+	int st = lol_scene_flatten(scene, &prog);
+	if (st != LOL_OK) { fprintf(stderr, "--pick: cannot flatten scene: %s\n", lol_status_str(st)); return 1; }
+	st = lol_gpu_create(device, &ctx);
+	if (st == LOL_GPU_OK) st = lol_gpu_set_specialize(ctx, 0);
+	if (st == LOL_GPU_OK) st = lol_gpu_upload_program(ctx, &prog);
+	lol_frame_camera_init(&fc, &scene->camera, w, h);
+	if (st == LOL_GPU_OK) st = lol_gpu_pick(ctx, &fc, w, h, max_steps, x, y, &hit);
+	if (st != LOL_GPU_OK) fprintf(stderr, "--pick %d,%d: %s (status %d)\n", x, y, ctx ? lol_gpu_error(ctx) : "no device", st);
+	else printf("pick %d,%d: id=%u dist=%.9g steps=%u normal=(%.9g, %.9g, %.9g)\n", x, y, hit.id, hit.dist, hit.steps,
+	            hit.normal[0], hit.normal[1], hit.normal[2]);
+	if (ctx) lol_gpu_destroy(ctx);
+	lol_program_free(&prog);
+	return st == LOL_GPU_OK ? 0 : 1;
+}
+
 static double now_ms(void) {
 	struct timespec ts;
 	clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -86,6 +111,7 @@ int main(int argc, const char* argv[]) {
 	const char* dump_camera = NULL;
 	const char* resize_script = NULL;
 	const char* dump_frames = NULL;
+	int pick = 0, pick_x = 0, pick_y = 0, device = 0, max_steps = 256;      /* (--device and --max-steps: the plug-in's flags, read here for --pick) */
 	lol_gpu_pixel_format format = { 16, 8, 0, 0, 0, 0, 4, 0, 0 };
 	int bytes_per_pixel = 4;
 	for (int i = 3; i < argc; i++) {
@@ -102,6 +128,12 @@ int main(int argc, const char* argv[]) {
 		}
 		else if (!strcmp(argv[i], "--resize-script") && i + 1 < argc) resize_script = argv[++i];
 		else if (!strcmp(argv[i], "--dump-frames") && i + 1 < argc) dump_frames = argv[++i];
+		else if (!strcmp(argv[i], "--pick") && i + 1 < argc) {
+			if (sscanf(argv[++i], "%d,%d", &pick_x, &pick_y) != 2) { fprintf(stderr, "--pick takes X,Y\n"); return 2; }
+			pick = 1;
+		}
+		else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[i + 1]);          /* (not consumed: the plug-in reads it too) */
+		else if (!strcmp(argv[i], "--max-steps") && i + 1 < argc) max_steps = atoi(argv[i + 1]);
 		else if (!strcmp(argv[i], "--format") && i + 1 < argc) {
 			if (!format_by_name(argv[++i], &format, &bytes_per_pixel)) { fprintf(stderr, "unknown --format %s\n", argv[i]); return 2; }
 		}
@@ -220,6 +252,9 @@ int main(int argc, const char* argv[]) {
 		fclose(fp);
 	}
 
+	int pick_failed = 0;
+	if (pick) pick_failed = pick_pixel(scene, device, w, h, max_steps, pick_x, pick_y);      /* (outside the frame: the library refuses) */
+
 	if (cam_fp) fclose(cam_fp);
 	if (times && frames + pipeline >= 8) {               /* steady state: the median is not moved by the first frames' set-up */
 		const int n = frames + pipeline;
@@ -239,5 +274,5 @@ int main(int argc, const char* argv[]) {
 	lol_scene_free(scene);
 	sem_destroy(&entry);
 	sem_destroy(&exit_);
-	return 0;
+	return pick_failed;
 }

@@ -1,6 +1,6 @@
 """python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N] [--samples N]
                           [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]] [--orbit-shutter K]]
-                          [--lens R --focus D --lens-samples K]
+                          [--lens R (--focus D | --focus-at X,Y) --lens-samples K] [--pick X,Y]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
@@ -10,7 +10,10 @@ inside its own exposure: view v is the mean in linear light of cameras v K ... v
 (Renderer.render_blended_views_into); with --orbit-samples S beside it every one of those cameras is supersampled S x S (not with
 --orbit-adaptive).  --lens R --focus D --lens-samples K renders ONE frame with depth of field: the mean over the K cameras of
 scene.lens_cameras on a lens of radius R focused at distance D; with --samples S every lens camera is supersampled S x S (not with
---adaptive).  There is no CPU rendering path."""
+--adaptive); --focus-at X,Y in the place of --focus D is autofocus: D is the distance, along the camera's axis, of what pixel
+(X, Y) shows (one Renderer.pick; refused when that ray escapes).  --pick X,Y prints the object id, distance, step count and normal
+under pixel (X, Y) of the --size frame (one ray, Renderer.pick); no frame is rendered unless -o is also given.  There is no CPU
+rendering path."""
 from __future__ import annotations
 
 import argparse
@@ -67,6 +70,29 @@ def orbit(sc, args, w, h) -> int:
     return 0
 
 
+def pixel_arg(text, w, h):
+    """"X,Y" -> (x, y) inside the w x h frame, or None"""
+    try:
+        x, y = (int(v) for v in text.split(","))
+    except ValueError:
+        return None
+    return (x, y) if 0 <= x < w and 0 <= y < h else None
+
+
+def pick_line(x, y, p) -> str:
+    """the line --pick prints (lol_headless --pick prints the same)"""
+    return "pick %d,%d: id=%u dist=%.9g steps=%u normal=(%.9g, %.9g, %.9g)" % ((x, y, p["id"], p["dist"], p["steps"]) + tuple(p["normal"]))
+
+
+def axis_cosine(sc, w, h, x, y) -> float:
+    """the cosine between the primary ray of pixel (x, y) and the camera's direction (host arithmetic, in doubles)"""
+    fc = sc.frame_camera(w, h)
+    vx, vy = (x + .5) / w * 2. - 1., 1. - (y + .5) / h * 2.
+    d, right, up = (np.array(v.tuple(), np.float64) for v in (fc.dir, fc.right, fc.up))
+    rd = right * (vx * fc.width) + up * (vy * fc.height) + d
+    return float(rd @ d / (np.linalg.norm(rd) * np.linalg.norm(d)))
+
+
 def lens(sc, args, w, h) -> int:
     """one frame averaged over the cameras of a lens into one PPM"""
     r = gpu.Renderer(args.device)
@@ -76,6 +102,14 @@ def lens(sc, args, w, h) -> int:
         else:
             r.set_view_blends(True)
         r.prepare(sc)
+        if args.focus_at:
+            x, y = pixel_arg(args.focus_at, w, h)
+            p = r.pick(x, y, w, h, args.max_steps)
+            if p["id"] == 0 or not p["dist"] > 0:
+                print(f"--focus-at {x},{y}: the ray of that pixel hits nothing to focus on", file=sys.stderr)
+                return 1
+            args.focus = p["dist"] * axis_cosine(sc, w, h, x, y)
+            print(f"focus at {x},{y}: object {p['id']} at {p['dist']:.6g} along its ray, {args.focus:.6g} along the camera's axis")
         surf = np.zeros((h, w), dtype=np.uint32)
         dev = r.malloc(surf.nbytes)
         try:
@@ -118,8 +152,19 @@ def main(argv=None) -> int:
     ap.add_argument("--focus", type=float, default=0.0, metavar="D", help="with --lens: the distance that stays sharp")
     ap.add_argument("--lens-samples", type=int, default=16, choices=(1, 2, 4, 8, 16), metavar="K",
                     help="with --lens: cameras on the lens")
+    ap.add_argument("--focus-at", default=None, metavar="X,Y",
+                    help="with --lens, in the place of --focus: focus on what pixel X,Y of the frame shows (autofocus)")
+    ap.add_argument("--pick", default=None, metavar="X,Y",
+                    help="print object id, distance, steps and normal under pixel X,Y of the --size frame; no frame unless -o is given")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
+    for name, text in (("--pick", args.pick), ("--focus-at", args.focus_at)):
+        if text is not None and pixel_arg(text, w, h) is None:
+            print(f"{name} takes X,Y inside the {w}x{h} frame", file=sys.stderr)
+            return 1
+    if args.focus_at is not None and (not args.lens or args.focus):
+        print("--focus-at X,Y goes with --lens R, in the place of --focus D", file=sys.stderr)
+        return 1
     try:
         sc = S.Scene.parse_file(args.scene)
     except S.SceneError as e:
@@ -150,15 +195,23 @@ def main(argv=None) -> int:
         print("--orbit-samples, --orbit-adaptive and --orbit-shutter go with --orbit K", file=sys.stderr)
         return 1
     if args.lens:
-        if args.lens < 0 or not args.focus > 0 or args.adaptive != -1 or args.frames != 1:
-            print("--lens R takes a radius > 0 and --focus D > 0; not with --adaptive or --frames", file=sys.stderr)
+        if args.lens < 0 or not (args.focus > 0 or args.focus_at) or args.adaptive != -1 or args.frames != 1 or args.pick:
+            print("--lens R takes a radius > 0 and --focus D > 0 (or --focus-at X,Y); not with --adaptive, --frames or --pick", file=sys.stderr)
             return 1
         return lens(sc, args, w, h)
     r = gpu.Renderer(args.device)
     r.set_samples(args.samples)          # before prepare(): the scene's own kernel then carries the supersampling form
     if args.adaptive != -1:
         r.set_adaptive_samples(args.adaptive)
-    r.prepare(sc)
+    if args.pick:
+        r.set_ray_queries(True)          # ... and the query kernel
+    r.prepare(sc, wait=not args.pick or bool(args.out))      # (one ray does not wait for the scene compiler: the interpreter answers)
+    if args.pick:
+        x, y = pixel_arg(args.pick, w, h)
+        print(pick_line(x, y, r.pick(x, y, w, h, args.max_steps)))
+        if not args.out:
+            r.close()
+            return 0
     surf = np.zeros((h, w), dtype=np.uint32)
     for f in range(args.frames):
         t0 = time.perf_counter()

@@ -6,7 +6,7 @@
  */
 #include "lol_gpu_internal.h"
 
-/* lol_kernel.h's, lol_kernel_aa.h's, lol_kernel_batch.h's, lol_kernel_batch_aa.h's, lol_kernel_blend.h's and lol_kernel_blend_aa.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
+/* lol_kernel.h's, lol_kernel_aa.h's, lol_kernel_batch.h's, lol_kernel_batch_aa.h's, lol_kernel_blend.h's, lol_kernel_blend_aa.h's and lol_kernel_rays.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
 #include "lol_kernel_src.inc"
 
 #pragma GCC visibility push(hidden)
@@ -894,6 +894,17 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 		s += "\tlol::store_linear_view_aa(L, P.rgb);\n";
 		s += "}\n";
 	}
+	/* Ray queries (lol_gpu_set_ray_queries before the upload): get_intersection and get_normal for a list of rays or of pixels, one
+	 * lane per ray, one wave per block (lol_kernel_rays.h) — no Launch, no LDS, no tables.  Appended after everything else, for the
+	 * reason above.  The name does not begin with lol_render_spec: it is no frame. */
+	if (carries.carries(SWITCH_RAYS)) {
+		s += "#include \"lol_kernel_rays.h\"\n";
+		s += "extern \"C\" __global__ __launch_bounds__(64)" + occupancy + " void lol_trace_spec(const lol::RayQuery Q) {\n";
+		s += "\tlol::SpecSdfExact exact;\n";
+		if (any_fast) s += "\tlol::SpecSdfFast fast;\n\tlol::trace_rays(fast, exact, true, Q);\n";
+		else          s += "\tlol::trace_rays(exact, exact, false, Q);\n";
+		s += "}\n";
+	}
 	return s;
 }
 
@@ -1013,7 +1024,7 @@ bool has_return_clobbering_branch(const std::vector<char>& code) { return has_re
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
                   std::string& log, std::string* src_out, bool cull, int form, ModuleKernels carries) {
 	const bool aa = carries.carries(SWITCH_AA), batch = carries.carries(SWITCH_BATCH), batch_aa = carries.carries(SWITCH_BATCH_AA);
-	const bool blend = carries.carries(SWITCH_BATCH_BLEND), blend_aa = carries.carries(SWITCH_BATCH_BLEND_AA);
+	const bool blend = carries.carries(SWITCH_BATCH_BLEND), blend_aa = carries.carries(SWITCH_BATCH_BLEND_AA), rays = carries.carries(SWITCH_RAYS);
 	std::string src = generate_source(P, fast, cull, form, carries);
 	if (src_out) *src_out = src;
 	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
@@ -1081,7 +1092,8 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	                             (batch_aa ? std::string("|batch_aa|") + LOL_KERNEL_BATCH_AA_H_TEXT : std::string()) +
 	                             (blend ? std::string("|blend|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT + "|" + LOL_KERNEL_BLEND_H_TEXT : std::string()) +
 	                             (blend_aa ? std::string("|blend_aa|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT + "|" + LOL_KERNEL_BATCH_AA_H_TEXT +
-	                                         "|" + LOL_KERNEL_BLEND_H_TEXT + "|" + LOL_KERNEL_BLEND_AA_H_TEXT : std::string());
+	                                         "|" + LOL_KERNEL_BLEND_H_TEXT + "|" + LOL_KERNEL_BLEND_AA_H_TEXT : std::string()) +
+	                             (rays ? std::string("|rays|") + LOL_KERNEL_RAYS_H_TEXT : std::string());
 	if (disk_cache_load(disk_key, code)) {
 		std::lock_guard<std::mutex> lock(g_cache_mutex);
 		g_code_cache[key] = code;
@@ -1095,8 +1107,9 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	 * that a module without it is handed the very list it was handed before that file existed */
 	/* ... and lol_kernel_blend_aa.h (which includes lol_kernel_batch_aa.h and lol_kernel_blend.h) only where it carries the supersampled
 	 * linear kernel: behind those two, last of all */
-	const char* hdr_src[6] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT, nullptr, nullptr };
-	const char* hdr_name[6] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h", nullptr, nullptr };
+	/* ... and lol_kernel_rays.h (which includes lol_kernel.h alone) only where it carries the query kernel: behind all of them */
+	const char* hdr_src[7] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT, nullptr, nullptr, nullptr };
+	const char* hdr_name[7] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h", nullptr, nullptr, nullptr };
 	int n_hdr = batch_aa || blend_aa ? 4 : batch ? 3 : aa ? 2 : 1;
 	if (blend || blend_aa) {
 		n_hdr = std::max(n_hdr, 3);
@@ -1105,6 +1118,10 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	}
 	if (blend_aa) {
 		hdr_src[n_hdr] = LOL_KERNEL_BLEND_AA_H_TEXT; hdr_name[n_hdr] = "lol_kernel_blend_aa.h";
+		n_hdr++;
+	}
+	if (rays) {
+		hdr_src[n_hdr] = LOL_KERNEL_RAYS_H_TEXT; hdr_name[n_hdr] = "lol_kernel_rays.h";
 		n_hdr++;
 	}
 	hiprtcProgram prog = nullptr;
@@ -1264,6 +1281,16 @@ int lol_gpu_compile_offline_view_blend_samples(const lol_program* prog, const ch
 	/* others: lol_gpu_compile_offline_view_blends' mask of the context's other switches */
 	return compile_offline(prog, arch, out_base, assume_fast,
 	                       { (others & 2) != 0, (others & 4) != 0, (others & 8) != 0, (others & 1) != 0, enable != 0 }, form, log, logcap);
+}
+
+/* ... and the module a context with lol_gpu_set_ray_queries(ctx, enable) compiles at its upload (lol_gpu_diag.h) */
+int lol_gpu_compile_offline_rays(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                 int others, int form, char* log, size_t logcap) {
+	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
+	if (others < 0 || others > 31) return LOL_GPU_ERR_ARG;
+	/* others: lol_gpu_compile_offline_view_blends' mask of the context's other switches, 16 = lol_gpu_set_view_blend_samples */
+	return compile_offline(prog, arch, out_base, assume_fast,
+	                       { (others & 2) != 0, (others & 4) != 0, (others & 8) != 0, (others & 1) != 0, (others & 16) != 0, enable != 0 }, form, log, logcap);
 }
 
 static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, ModuleKernels carries,

@@ -87,6 +87,16 @@ hipError_t launch_sdf_interp(const uint32_t* mops, uint32_t n_mops, const float*
 	return hipGetLastError();
 }
 
+/* ray queries on the interpreter (lol_kernel_rays.h, trace_interp): per stack class and root kind, like the SDF alone above — neither
+ * reads lights or materials, so where the tables lie (interp_rung) does not matter to them */
+template <int SSIZE>
+hipError_t launch_trace_interp(const lol::RayQuery& Q, hipStream_t s, int sqrt_kind) {
+	dim3 grid((Q.n + 63u) / 64u);
+	if (sqrt_kind == 3) hipLaunchKernelGGL((lol::trace_interp<SSIZE, 3>), grid, dim3(64), 0, s, Q);
+	else                hipLaunchKernelGGL((lol::trace_interp<SSIZE, 0>), grid, dim3(64), 0, s, Q);
+	return hipGetLastError();
+}
+
 /* the interpreter's kernel of a family (lol_gpu_internal.h, KERNEL_FAMILIES) for one stack class, sqrt kind and table placement: its
  * address, for hipLaunchKernel */
 template <int SSIZE, int KIND, bool TABLES_GLOBAL>
@@ -538,6 +548,7 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 	if (ctx->d_adaptive_order) (void)hipFree(ctx->d_adaptive_order);
 	if (ctx->d_bad) (void)hipFree(ctx->d_bad);
 	if (ctx->d_gamma) (void)hipFree(ctx->d_gamma);
+	if (ctx->d_pick) (void)hipFree(ctx->d_pick);
 	if (ctx->tiles.have_events) for (hipEvent_t e : ctx->tiles.ev) (void)hipEventDestroy(e);
 	lpt_release(ctx);
 	delete ctx;                              /* ~SpecTiers: a compiler run still going is waited for, the scene kernels unloaded */
@@ -1710,5 +1721,118 @@ int lol_gpu_sdf_batch(lol_gpu* ctx, const float* pts_dev, float* dist_dev, uint3
 	}
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "sdf kernel launch", e);
 	return LOL_GPU_OK;
+}
+
+/*
+ * Ray queries (include/lol_gpu.h; the kernel: lol_kernel_rays.h).  ONE launch on the caller's stream: no host wait, no copy, no
+ * scratch, and nothing of the context changes but — for a list of pixels — the cached first step of the camera's position
+ * (first_step: a function of that position alone, whoever asks).  The tile-order state, the samples, the pixel format and the record
+ * rings are neither read nor written.
+ */
+/* the scene kernel that answers queries, or nullptr: trace_interp does — the test the launch makes and lol_gpu_trace_kernel_name reports */
+static const SceneKernel* trace_kernel(const lol_gpu* ctx) {
+	const SceneKernel* k = scene_kernel(ctx);
+	return k && k->trace ? k : nullptr;
+}
+
+/* what both sources are refused for */
+static int query_refused(lol_gpu* ctx, const void* list_dev, size_t n, int max_steps, const lol_gpu_hits* out) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (!list_dev && n > 0) return fail(ctx, LOL_GPU_ERR_ARG, "ray query: no list");
+	if (!out || (!out->dist && !out->id && !out->steps && !out->normal)) return fail(ctx, LOL_GPU_ERR_ARG, "ray query: no output");
+	if (max_steps < 0 || n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "ray query: max_steps < 0 or more than 2^32 - 1 rays");
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	return LOL_GPU_OK;
+}
+
+/* `Q`: the source filled in by the caller (rays or xy, flags, camera) */
+static int launch_query(lol_gpu* ctx, lol::RayQuery& Q, size_t n, int max_steps, const lol_gpu_hits* out, void* stream) {
+	if (n == 0) return LOL_GPU_OK;
+	Q.n = (uint32_t)n;
+	Q.max_steps = max_steps;
+	/* the scene's side of what the fast SDF rests on (shadow_settle_ok, whatever lol_gpu_set_exact_skips says: no shadow is cast);
+	 * the rays' side is the kernel's own ballot */
+	if (ctx->finite_scene) Q.flags |= lol::RAYS_SCENE_SANE;
+	if (out->id) Q.flags |= lol::RAYS_WANT_ID;
+	if (out->normal) Q.flags |= lol::RAYS_WANT_NORMAL;
+	Q.out = { out->dist, out->id, out->steps, out->normal };
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	finish_specialise(ctx, false);           /* a scene kernel that has finished compiling takes over here, as at a frame boundary */
+	hipError_t e;
+	if (const SceneKernel* k = trace_kernel(ctx)) {
+		void* args[] = { &Q };
+		e = hipModuleLaunchKernel(k->trace, (Q.n + 63u) / 64u, 1, 1, 64, 1, 1, 0, s, args, nullptr);
+	} else {
+		/* the list every camera may use (with v_div_fixup: upload_program), as lol_gpu_sdf_batch */
+		Q.ops = ctx->d_mops[ctx->cur];
+		Q.n_ops = ctx->n_mops;
+		const int kind = ctx->interp_sqrt_kind;
+		const int cls = interp_stack_class(ctx->h_prog.max_stack);
+		if (cls == 1)      e = launch_trace_interp<1>(Q, s, kind);
+		else if (cls == 3) e = launch_trace_interp<3>(Q, s, kind);
+		else if (cls == 7) e = launch_trace_interp<7>(Q, s, kind);
+		else if (cls == lol::MOP_DEEP_FROM - 1) e = launch_trace_interp<lol::MOP_DEEP_FROM - 1>(Q, s, kind);
+		else               e = launch_trace_interp<lol::MOP_DEEP_SLOTS>(Q, s, kind);
+	}
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "ray query launch", e);
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_trace_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_hits* out, void* stream) {
+	LOL_TRY(query_refused(ctx, rays_dev, n, max_steps, out));
+	lol::RayQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.rays = rays_dev;
+	return launch_query(ctx, Q, n, max_steps, out, stream);
+}
+
+int lol_gpu_trace_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
+                         const uint32_t* xy_dev, size_t n, const lol_gpu_hits* out, void* stream) {
+	LOL_TRY(query_refused(ctx, xy_dev, n, max_steps, out));
+	if (!cam || w < 1 || h < 1) return fail(ctx, LOL_GPU_ERR_ARG, "ray query: no camera or bad frame geometry");
+	lol::RayQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.xy = xy_dev;
+	Q.flags = lol::RAYS_FROM_PIXELS;
+	memcpy(&Q.cam, cam, sizeof Q.cam);
+	Q.fw = (float)w; Q.fh = (float)h;
+	if (n > 0 && first_step(ctx, *cam, max_steps)) { Q.flags |= lol::RAYS_FIRST_STEP; Q.first_dist = ctx->first_dist; Q.first_id = ctx->first_id; }
+	return launch_query(ctx, Q, n, max_steps, out, stream);
+}
+
+int lol_gpu_pick(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps, int x, int y, lol_gpu_hit* out) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (!cam || !out || w < 1 || h < 1 || max_steps < 0) return fail(ctx, LOL_GPU_ERR_ARG, "pick: no camera, no output or bad frame geometry");
+	if (x < 0 || y < 0 || x >= w || y >= h) return fail(ctx, LOL_GPU_ERR_ARG, "pick: the pixel lies outside the frame");
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	/* xy [2] | dist | id | steps | normal [3]: eight dwords, the context's from the first pick on */
+	if (!ctx->d_pick) LOL_HIP(ctx, hipMalloc(&ctx->d_pick, 8 * 4));
+	uint32_t* d = static_cast<uint32_t*>(ctx->d_pick);
+	uint32_t host[8] = { (uint32_t)x, (uint32_t)y, 0, 0, 0, 0, 0, 0 };
+	LOL_HIP(ctx, hipMemcpyAsync(d, host, 2 * 4, hipMemcpyHostToDevice, ctx->stream));
+	const lol_gpu_hits hits = { reinterpret_cast<float*>(d + 2), d + 3, d + 4, reinterpret_cast<float*>(d + 5) };
+	LOL_TRY(lol_gpu_trace_pixels(ctx, cam, w, h, max_steps, d, 1, &hits, ctx->stream));
+	LOL_HIP(ctx, hipMemcpyAsync(host, d, sizeof host, hipMemcpyDeviceToHost, ctx->stream));
+	LOL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	memcpy(&out->dist, &host[2], 4);
+	out->id = host[3];
+	out->steps = host[4];
+	memcpy(out->normal, &host[5], 3 * 4);
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_set_ray_queries(lol_gpu* ctx, int enable) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	ctx->ray_queries = enable ? 1 : 0;       /* takes effect at the next lol_gpu_upload_program */
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_ray_queries(const lol_gpu* ctx) { return ctx ? ctx->ray_queries : LOL_GPU_ERR_ARG; }
+
+const char* lol_gpu_trace_kernel_name(const lol_gpu* ctx) {
+	if (!ctx) return "";
+	return trace_kernel(ctx) ? "lol_trace_spec" : "trace_interp";
 }
 }  // extern "C"

@@ -24,6 +24,7 @@
 #include "lol_kernel_batch_aa.h"
 #include "lol_kernel_blend.h"
 #include "lol_kernel_blend_aa.h"
+#include "lol_kernel_rays.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -135,7 +136,7 @@ struct OwnedProgram {
 enum KernelFamily { FAM_FRAME, FAM_FRAME_AA, FAM_FRAME_AA_LIST, FAM_BATCH, FAM_BATCH_AA, FAM_BATCH_AA_LIST, FAM_BATCH_LIN, FAM_BATCH_AA_LIN,
                     N_FAMILIES };
 /* the switch of the context that puts a family into the module of the next upload */
-enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA, SWITCH_BATCH_BLEND, SWITCH_BATCH_BLEND_AA };
+enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA, SWITCH_BATCH_BLEND, SWITCH_BATCH_BLEND_AA, SWITCH_RAYS };
 struct FamilyRow {
 	const char*  symbol;        /* in the scene module */
 	const char*  counting;      /* its twin with the per-lane step counters (modules up to LOL_SPEC_TWO_KERNELS_MAX_OPS ops), or none */
@@ -157,12 +158,15 @@ constexpr FamilyRow KERNEL_FAMILIES[N_FAMILIES] = {
  * these kernels existed.  aa: lol_gpu_set_samples > 1 at the upload; batch: lol_gpu_set_view_batches; batch_aa:
  * lol_gpu_set_view_samples, which brings the plain batch kernels with it (the first pass of an adaptive batch is theirs); blend:
  * lol_gpu_set_view_blends, the linear-colour batch kernel alone (lol_kernel_blend.h); blend_aa: lol_gpu_set_view_blend_samples, its
- * supersampled form alone (lol_kernel_blend_aa.h) — a switch of its own, NOT implied by blend and batch_aa together. */
+ * supersampled form alone (lol_kernel_blend_aa.h) — a switch of its own, NOT implied by blend and batch_aa together; rays:
+ * lol_gpu_set_ray_queries, lol_trace_spec (lol_kernel_rays.h).  That kernel is no row of KERNEL_FAMILIES: launch_family hands a family
+ * a Launch, a block of lol::BLOCK threads, the tables' LDS and perhaps a counting twin, and a query has none of the four — it lives
+ * beside lol_sdf_spec (SceneKernel::trace), the other kernel that is not a frame. */
 struct ModuleKernels {
-	bool aa = false, batch = false, batch_aa = false, blend = false, blend_aa = false;
+	bool aa = false, batch = false, batch_aa = false, blend = false, blend_aa = false, rays = false;
 	bool carries(ModuleSwitch sw) const {
 		return sw == SWITCH_NONE || (sw == SWITCH_AA && aa) || (sw == SWITCH_BATCH && (batch || batch_aa)) || (sw == SWITCH_BATCH_AA && batch_aa) ||
-		       (sw == SWITCH_BATCH_BLEND && blend) || (sw == SWITCH_BATCH_BLEND_AA && blend_aa);
+		       (sw == SWITCH_BATCH_BLEND && blend) || (sw == SWITCH_BATCH_BLEND_AA && blend_aa) || (sw == SWITCH_RAYS && rays);
 	}
 };
 
@@ -173,6 +177,7 @@ struct SceneKernel {
 	hipFunction_t fn[N_FAMILIES] = {};         /* by family; nullptr: the module was compiled without it, the interpreter renders that family */
 	hipFunction_t counting[N_FAMILIES] = {};   /* the family's counting twin — or fn[] again, where the module holds no twin of it: that one counts */
 	hipFunction_t sdf = nullptr;               /* lol_sdf_spec (lol_gpu_sdf_batch) */
+	hipFunction_t trace = nullptr;             /* lol_trace_spec (ray queries), or nullptr: the module was compiled without it, trace_interp answers */
 	std::string   key;                         /* FNV-1a of the code object (lol_gpu_kernel_key) */
 	explicit operator bool() const { return module != nullptr; }
 	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
@@ -250,6 +255,8 @@ struct lol_gpu {
 	int          view_samples = 0;       /* lol_gpu_set_view_samples: ... and lol_render_spec_batch_aa / _aa_list (and the batch kernels) */
 	int          view_blends = 0;        /* lol_gpu_set_view_blends: ... and lol_render_spec_batch_lin */
 	int          view_blend_samples = 0; /* lol_gpu_set_view_blend_samples: ... and lol_render_spec_batch_aa_lin */
+	int          ray_queries = 0;        /* lol_gpu_set_ray_queries: ... and lol_trace_spec */
+	void*        d_pick = nullptr;       /* lol_gpu_pick's device memory, from the first pick on: xy [2] | dist | id | steps | normal [3] */
 	/* The view records of batches (lol_gpu_render_views, lol_gpu.hip): a ring of sets, one per batch, whatever its stream.  A batch
 	 * fills its set's pinned host copy, queues the copy to the device and the launch behind it on its stream, and records `done`;
 	 * the next batch through the set waits for `copied` on the host (the pinned copy is the host's to write again) and for `done`

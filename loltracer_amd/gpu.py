@@ -72,6 +72,14 @@ class Debug(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("hit_dist", C.c_void_p), ("hit_id", C.c_void_p), ("steps", C.c_void_p)]
 
 
+class Hits(C.Structure):             # lol_gpu_hits: device pointers, each may be NULL (not all four)
+    _fields_ = [("dist", C.c_void_p), ("id", C.c_void_p), ("steps", C.c_void_p), ("normal", C.c_void_p)]
+
+
+class Hit(C.Structure):              # lol_gpu_hit
+    _fields_ = [("dist", C.c_float), ("id", C.c_uint32), ("steps", C.c_uint32), ("normal", C.c_float * 3)]
+
+
 STREAM_DEFAULT = 1        # LOL_GPU_STREAM_DEFAULT: HIP's legacy default stream (hipStreamLegacy)
 
 
@@ -231,6 +239,22 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_compile_offline_view_blend_samples.restype = C.c_int
         lib.lol_gpu_view_blend_samples_kernel_name.argtypes = [vp, C.c_int, C.c_int]
         lib.lol_gpu_view_blend_samples_kernel_name.restype = C.c_char_p
+        # ray queries (include/lol_gpu.h, "Ray queries")
+        lib.lol_gpu_trace_rays.argtypes = [vp, vp, C.c_size_t, C.c_int, P(Hits), vp]
+        lib.lol_gpu_trace_rays.restype = C.c_int
+        lib.lol_gpu_trace_pixels.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, vp, C.c_size_t, P(Hits), vp]
+        lib.lol_gpu_trace_pixels.restype = C.c_int
+        lib.lol_gpu_pick.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(Hit)]
+        lib.lol_gpu_pick.restype = C.c_int
+        lib.lol_gpu_set_ray_queries.argtypes = [vp, C.c_int]
+        lib.lol_gpu_set_ray_queries.restype = C.c_int
+        lib.lol_gpu_ray_queries.argtypes = [vp]
+        lib.lol_gpu_ray_queries.restype = C.c_int
+        lib.lol_gpu_trace_kernel_name.argtypes = [vp]
+        lib.lol_gpu_trace_kernel_name.restype = C.c_char_p
+        lib.lol_gpu_compile_offline_rays.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     C.c_char_p, C.c_size_t]
+        lib.lol_gpu_compile_offline_rays.restype = C.c_int
         lib.lol_gpu_views_refined.argtypes = [vp, P(C.c_int64)]
         lib.lol_gpu_views_refined.restype = C.c_int
         lib.lol_gpu_interp_variant.argtypes = [vp, P(C.c_int), P(C.c_int)]
@@ -352,6 +376,7 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_render_views_samples", "lol_gpu_set_view_samples", "lol_gpu_view_samples",
     "lol_gpu_render_views_blend", "lol_gpu_set_view_blends", "lol_gpu_view_blends",
     "lol_gpu_render_views_blend_samples", "lol_gpu_set_view_blend_samples", "lol_gpu_view_blend_samples",
+    "lol_gpu_trace_rays", "lol_gpu_trace_pixels", "lol_gpu_pick", "lol_gpu_set_ray_queries", "lol_gpu_ray_queries",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
@@ -361,6 +386,7 @@ DIAG_SYMBOLS = [                                                        # includ
     "lol_gpu_compile_offline_views", "lol_gpu_compile_offline_view_samples", "lol_gpu_view_samples_kernel_name",
     "lol_gpu_views_refined", "lol_gpu_interp_variant", "lol_gpu_compile_offline_view_blends", "lol_gpu_view_blend_kernel_name",
     "lol_gpu_compile_offline_view_blend_samples", "lol_gpu_view_blend_samples_kernel_name",
+    "lol_gpu_trace_kernel_name", "lol_gpu_compile_offline_rays",
 ]
 
 
@@ -439,6 +465,22 @@ def compile_offline_view_blend_samples(program: S.Program, out_base: str, enable
     others = int(bool(view_blends)) | int(bool(samples)) << 1 | int(bool(view_batches)) << 2 | int(bool(view_samples)) << 3
     st = gpu_lib().lol_gpu_compile_offline_view_blend_samples(C.byref(program), arch.encode(), os.fsencode(out_base),
                                                               int(assume_fast), int(bool(enable)), others, int(form), log, len(log))
+    if st != LOL_GPU_OK:
+        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
+    return log.value.decode(errors="replace")
+
+
+def compile_offline_rays(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
+                         assume_fast: bool = False, view_blends: bool = False, samples: bool = False, view_batches: bool = False,
+                         view_samples: bool = False, view_blend_samples: bool = False) -> str:
+    """compile_offline for a context with set_ray_queries(enable) before its upload: adds lol_trace_spec, last.  form as for
+    compile_offline_views.  view_blends / samples / view_batches / view_samples / view_blend_samples: the context's other switches
+    set beside it.  Needs no device."""
+    log = C.create_string_buffer(1 << 16)
+    others = (int(bool(view_blends)) | int(bool(samples)) << 1 | int(bool(view_batches)) << 2 | int(bool(view_samples)) << 3 |
+              int(bool(view_blend_samples)) << 4)
+    st = gpu_lib().lol_gpu_compile_offline_rays(C.byref(program), arch.encode(), os.fsencode(out_base),
+                                                int(assume_fast), int(bool(enable)), others, int(form), log, len(log))
     if st != LOL_GPU_OK:
         raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
     return log.value.decode(errors="replace")
@@ -794,6 +836,45 @@ class Renderer:
         """dist[i], id[i] = the scene SDF at pts[i] (n x 3 floats), through the SDF code the frames use (diagnostic)."""
         self._check(self._lib.lol_gpu_sdf_batch(self._ctx, C.c_void_p(pts_ptr), C.c_void_p(dist_ptr), C.c_void_p(id_ptr), n,
                                                 _stream_arg(stream)))
+
+    # ---- ray queries (include/lol_gpu.h, "Ray queries")
+    def set_ray_queries(self, enable: bool):
+        """Before prepare(): the scene's own module also carries the query kernel (lol_trace_spec); without it — and until that
+        module is ready — queries run on the interpreter's trace_interp.  Same answers either way."""
+        self._check(self._lib.lol_gpu_set_ray_queries(self._ctx, 1 if enable else 0))
+
+    @property
+    def ray_queries(self) -> bool:
+        return bool(self._lib.lol_gpu_ray_queries(self._ctx))
+
+    def trace_kernel_name(self) -> str:
+        """the kernel the next trace_rays_into / trace_pixels_into / pick launches"""
+        return self._lib.lol_gpu_trace_kernel_name(self._ctx).decode()
+
+    def trace_rays_into(self, rays_ptr: int, n: int, max_steps: int = 256, dist_ptr: int = 0, id_ptr: int = 0, steps_ptr: int = 0,
+                        normal_ptr: int = 0, stream: int | None = None):
+        """Asynchronously trace n rays (device memory, n x {ox, oy, oz, dx, dy, dz} floats): ray i is the reference's
+        get_intersection + get_normal.  dist / id / steps: n elements each, normal: 3 n floats; 0 = not wanted (not all four)."""
+        hits = Hits(dist_ptr or None, id_ptr or None, steps_ptr or None, normal_ptr or None)
+        self._check(self._lib.lol_gpu_trace_rays(self._ctx, C.c_void_p(rays_ptr), n, max_steps, C.byref(hits), _stream_arg(stream)))
+
+    def trace_pixels_into(self, xy_ptr: int, n: int, w: int, h: int, max_steps: int = 256, dist_ptr: int = 0, id_ptr: int = 0,
+                          steps_ptr: int = 0, normal_ptr: int = 0, stream: int | None = None, camera: S.Camera | None = None,
+                          frame_camera: S.FrameCamera | None = None):
+        """Asynchronously trace the primary rays of n pixels (device memory, n x {x, y} uint32) of the w x h frame under the
+        camera: what a frame's lol_gpu_debug planes hold for those pixels, and the normal."""
+        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        hits = Hits(dist_ptr or None, id_ptr or None, steps_ptr or None, normal_ptr or None)
+        self._check(self._lib.lol_gpu_trace_pixels(self._ctx, C.byref(fc), w, h, max_steps, C.c_void_p(xy_ptr), n, C.byref(hits),
+                                                   _stream_arg(stream)))
+
+    def pick(self, x: int, y: int, w: int, h: int, max_steps: int = 256, camera: S.Camera | None = None,
+             frame_camera: S.FrameCamera | None = None) -> dict:
+        """What is under pixel (x, y) of the w x h frame: {"id", "dist", "steps", "normal"} in host memory (waits)."""
+        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        hit = Hit()
+        self._check(self._lib.lol_gpu_pick(self._ctx, C.byref(fc), w, h, max_steps, int(x), int(y), C.byref(hit)))
+        return {"id": int(hit.id), "dist": float(hit.dist), "steps": int(hit.steps), "normal": tuple(float(v) for v in hit.normal)}
 
     def set_cull(self, enable: bool):
         """Exact bounding-sphere culling of top-level objects in the specialised kernel; takes effect at the next prepare()."""
