@@ -414,9 +414,12 @@ int         lol_gpu_view_blend_samples(const lol_gpu* ctx);
  * "render_interp_batch"; supersampled batches (lol_gpu_render_views_samples) what lol_gpu_view_samples_kernel_name (lol_gpu_diag.h)
  * says. */
 const char* lol_gpu_kernel_name(const lol_gpu* ctx);
-/* Identity of the code that kernel is: 16 hex digits — FNV-1a of the hipRTC code object for "lol_render_spec"; for
- * "render_interp" of {this library's build id (a digest of its sources and compiler flags), the uploaded macro-op lists,
- * the square-root variant}: everything that decides which instructions the interpreter executes.  Profiles record it
+/* Identity of the code that kernel is: 16 hex digits.  For "lol_render_spec", FNV-1a over what the device loads of the hipRTC
+ * code object: every section of the ELF file that is allocated (SHF_ALLOC) and of type PROGBITS or NOTE — the kernels' metadata
+ * (.note), their descriptors (.rodata) and their instructions (.text) — in section-header order, each as its size (8 bytes,
+ * little-endian) followed by its bytes.  Symbol names are not part of it: the compiler's compilation-unit id, a symbol that
+ * follows the text of every header it was handed, does not rename the same instructions.  For "render_interp", FNV-1a of
+ * {this library's build id (a digest of its sources and compiler flags), the uploaded macro-op lists, the square-root variant}: everything that decides which instructions the interpreter executes.  Profiles record it
  * (profiles/pmc_traffic.json) so that a counter figure is only ever quoted for the code it was measured on. */
 const char* lol_gpu_kernel_key(const lol_gpu* ctx);
 /* The environment: the library reads ten LOL_GPU_* switches for A/B runs and debugging (INTEGRATION.md lists them), and honours

@@ -151,6 +151,12 @@ const char* lol_gpu_trace_kernel_name(const lol_gpu* ctx);
  */
 int         lol_gpu_compile_offline_rays(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                          int enable, int others, int form, char* log, size_t logcap);
+/*
+ * lol_gpu_kernel_key's function of a code object (lol_gpu.h says what it covers), for n bytes of one in host memory — a .co of
+ * lol_gpu_compile_offline* — as 16 hex digits and a NUL in out.  A buffer that is no ELF64 little-endian file, or whose section
+ * headers point outside it, gets the FNV-1a of all its bytes; no buffer is read out of bounds.  Needs no device.
+ */
+void        lol_gpu_code_key(const void* code, size_t n, char out[17]);
 
 #ifdef __cplusplus
 }

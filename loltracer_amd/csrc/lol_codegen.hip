@@ -5,8 +5,9 @@
  * long-branch register bug.  (Part of liblol_gpu.so; see lol_gpu_internal.h for how the library is cut.)
  */
 #include "lol_gpu_internal.h"
+#include "lol_code_key.h"
 
-/* lol_kernel.h's, lol_kernel_aa.h's, lol_kernel_batch.h's, lol_kernel_batch_aa.h's, lol_kernel_blend.h's, lol_kernel_blend_aa.h's and lol_kernel_rays.h's text, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
+/* the text of the seven lol_kernel*.h files, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
 #include "lol_kernel_src.inc"
 
 #pragma GCC visibility push(hidden)
@@ -908,12 +909,15 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	return s;
 }
 
-unsigned long long fnv64(const void* data, size_t n);
-std::string fnv_hex(const void* data, size_t n) {
+using lol_key::fnv64;
+static std::string hex16(unsigned long long h) {
 	char b[20];
-	snprintf(b, sizeof b, "%016llx", fnv64(data, n));
+	snprintf(b, sizeof b, "%016llx", h);
 	return b;
 }
+std::string fnv_hex(const void* data, size_t n) { return hex16(fnv64(data, n)); }
+/* the key of a code object: what the device loads of it (lol_code_key.h) */
+std::string code_key_hex(const void* code, size_t n) { return hex16(lol_key::code_key(code, n)); }
 
 /* Process-wide cache of compiled kernels: hosts (and the tests) upload the same scene many times. */
 std::mutex g_cache_mutex;
@@ -945,12 +949,6 @@ std::string disk_cache_path(const std::string& key) {
  * user and must not be writable by group or others (a shared LOL_GPU_CACHE_DIR / XDG_CACHE_HOME would otherwise let
  * another user plant kernels), and the code object must match the checksum stored next to it. */
 bool private_to_user(const struct stat& st) { return st.st_uid == geteuid() && !(st.st_mode & (S_IWGRP | S_IWOTH)); }
-
-unsigned long long fnv64(const void* data, size_t n) {
-	unsigned long long h = 0xcbf29ce484222325ull;
-	for (size_t i = 0; i < n; i++) { h ^= static_cast<const unsigned char*>(data)[i]; h *= 0x100000001b3ull; }
-	return h;
-}
 
 bool disk_cache_load(const std::string& key, std::vector<char>& code) {
 	const std::string path = disk_cache_path(key);
@@ -1023,8 +1021,6 @@ bool has_return_clobbering_branch(const std::vector<char>& code) { return has_re
 /* hipRTC: generated source + lol_kernel.h → code object for `arch`.  Needs no device. */
 bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
                   std::string& log, std::string* src_out, bool cull, int form, ModuleKernels carries) {
-	const bool aa = carries.carries(SWITCH_AA), batch = carries.carries(SWITCH_BATCH), batch_aa = carries.carries(SWITCH_BATCH_AA);
-	const bool blend = carries.carries(SWITCH_BATCH_BLEND), blend_aa = carries.carries(SWITCH_BATCH_BLEND_AA), rays = carries.carries(SWITCH_RAYS);
 	std::string src = generate_source(P, fast, cull, form, carries);
 	if (src_out) *src_out = src;
 	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
@@ -1085,44 +1081,20 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 		auto it = g_code_cache.find(key);
 		if (it != g_code_cache.end()) { code = it->second; log.clear(); return true; }
 	}
-	/* on disk the pipeline source (lol_kernel.h, embedded in this library) is part of the key: another build of the
+	/* on disk the pipeline source (the kernel headers, embedded in this library) is part of the key: another build of the
 	 * library must not pick up this one's kernels */
-	const std::string disk_key = key + "|" + LOL_KERNEL_H_TEXT + (aa ? std::string("|") + LOL_KERNEL_AA_H_TEXT : std::string()) +
-	                             (batch ? std::string("|batch|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT : std::string()) +
-	                             (batch_aa ? std::string("|batch_aa|") + LOL_KERNEL_BATCH_AA_H_TEXT : std::string()) +
-	                             (blend ? std::string("|blend|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT + "|" + LOL_KERNEL_BLEND_H_TEXT : std::string()) +
-	                             (blend_aa ? std::string("|blend_aa|") + LOL_KERNEL_AA_H_TEXT + "|" + LOL_KERNEL_BATCH_H_TEXT + "|" + LOL_KERNEL_BATCH_AA_H_TEXT +
-	                                         "|" + LOL_KERNEL_BLEND_H_TEXT + "|" + LOL_KERNEL_BLEND_AA_H_TEXT : std::string()) +
-	                             (rays ? std::string("|rays|") + LOL_KERNEL_RAYS_H_TEXT : std::string());
+	static const char* const hdr_src[7] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT,
+	                                        LOL_KERNEL_BLEND_H_TEXT, LOL_KERNEL_BLEND_AA_H_TEXT, LOL_KERNEL_RAYS_H_TEXT };
+	static const char* const hdr_name[7] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h",
+	                                         "lol_kernel_blend.h", "lol_kernel_blend_aa.h", "lol_kernel_rays.h" };
+	constexpr int n_hdr = 7;                            /* every module is handed all of them: what it does not #include is never parsed */
+	static const std::string all_headers = [] { std::string t; for (const char* h : hdr_src) { t += '|'; t += h; } return t; }();
+	const std::string disk_key = key + all_headers;
 	if (disk_cache_load(disk_key, code)) {
 		std::lock_guard<std::mutex> lock(g_cache_mutex);
 		g_code_cache[key] = code;
 		log = "(code object from the disk cache)";
 		return true;
-	}
-	/* lol_kernel_aa.h only where the source includes it: hipRTC's compilation-unit id — bytes of the code object — follows the headers */
-	/* ... and lol_kernel_batch.h (which includes lol_kernel_aa.h for pack_pixel) only where the module carries the batch kernel */
-	/* ... and lol_kernel_batch_aa.h (which includes lol_kernel_batch.h) only where it carries the supersampled batch kernels */
-	/* ... and lol_kernel_blend.h (which includes lol_kernel_batch.h) only where it carries the linear-colour batch kernel: last, so
-	 * that a module without it is handed the very list it was handed before that file existed */
-	/* ... and lol_kernel_blend_aa.h (which includes lol_kernel_batch_aa.h and lol_kernel_blend.h) only where it carries the supersampled
-	 * linear kernel: behind those two, last of all */
-	/* ... and lol_kernel_rays.h (which includes lol_kernel.h alone) only where it carries the query kernel: behind all of them */
-	const char* hdr_src[7] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT, nullptr, nullptr, nullptr };
-	const char* hdr_name[7] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h", nullptr, nullptr, nullptr };
-	int n_hdr = batch_aa || blend_aa ? 4 : batch ? 3 : aa ? 2 : 1;
-	if (blend || blend_aa) {
-		n_hdr = std::max(n_hdr, 3);
-		hdr_src[n_hdr] = LOL_KERNEL_BLEND_H_TEXT; hdr_name[n_hdr] = "lol_kernel_blend.h";
-		n_hdr++;
-	}
-	if (blend_aa) {
-		hdr_src[n_hdr] = LOL_KERNEL_BLEND_AA_H_TEXT; hdr_name[n_hdr] = "lol_kernel_blend_aa.h";
-		n_hdr++;
-	}
-	if (rays) {
-		hdr_src[n_hdr] = LOL_KERNEL_RAYS_H_TEXT; hdr_name[n_hdr] = "lol_kernel_rays.h";
-		n_hdr++;
 	}
 	hiprtcProgram prog = nullptr;
 	if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_hdr, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
@@ -1223,6 +1195,11 @@ int lol_gpu_cull_bounds_clusters(const lol_program* prog, uint32_t root, float o
 		n++;
 	}
 	return n;
+}
+
+void lol_gpu_code_key(const void* code, size_t n, char out[17]) {
+	if (!out) return;
+	snprintf(out, 17, "%s", code ? code_key_hex(code, n).c_str() : "");
 }
 
 int lol_gpu_testing_has_return_clobbering_branch(const void* code, size_t n_bytes) {

@@ -178,7 +178,7 @@ struct SceneKernel {
 	hipFunction_t counting[N_FAMILIES] = {};   /* the family's counting twin — or fn[] again, where the module holds no twin of it: that one counts */
 	hipFunction_t sdf = nullptr;               /* lol_sdf_spec (lol_gpu_sdf_batch) */
 	hipFunction_t trace = nullptr;             /* lol_trace_spec (ray queries), or nullptr: the module was compiled without it, trace_interp answers */
-	std::string   key;                         /* FNV-1a of the code object (lol_gpu_kernel_key) */
+	std::string   key;                         /* code_key_hex of the code object (lol_gpu_kernel_key) */
 	explicit operator bool() const { return module != nullptr; }
 	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
 };
@@ -469,6 +469,7 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
  * false: the two differ in length (cannot happen: same records by construction) */
 bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, std::vector<uint32_t>& lists, uint32_t& n_mops);
 std::string fnv_hex(const void* data, size_t n);
+std::string code_key_hex(const void* code, size_t n);      /* SceneKernel::key: FNV-1a over what the device loads of a code object (lol_code_key.h) */
 extern std::mutex g_rtc_mutex;               /* one run of the scene compiler at a time (lol_gpu.hip) */
 
 /* ---- lol_tiers.hip */

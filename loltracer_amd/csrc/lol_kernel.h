@@ -1049,6 +1049,16 @@ __device__ __forceinline__ int frame_row(const Launch& L, int r) {
 	return band * L.cycle_rows + L.offset_rows + (r - band * L.band_rows);
 }
 
+/* The primary ray of pixel (x, y) of a frame of fw x fh pixels, naive_renderer.c:218-221 and get_camera_ray (:188-190) with the
+ * per-frame basis hoisted.  (x, y) need not lie in the frame (lol_kernel_rays.h). */
+__device__ __forceinline__ V3 camera_ray(const Cam& cam, float fw, float fh, int x, int y) {
+	const float vx = ((float)x + .5f) / fw * 2.f - 1.f;
+	const float vy = 1.f - ((float)y + .5f) / fh * 2.f;
+	const V3 cdir = v3(cam.dir);
+	V3 rd = add(scale(v3(cam.right), vx * cam.width), scale(v3(cam.up), vy * cam.height));
+	return normalize(add(rd, cdir));
+}
+
 /*
  * The per-pixel body, naive_renderer.c:217-235, for the pixel this lane owns.
  * `lds` = lights | materials | root_material | out tile (already staged and synchronised); with TABLES_GLOBAL the
@@ -1080,14 +1090,7 @@ __device__ __forceinline__ Pixel shade_pixel(const Launch& L, Sdf& sdf, const u3
 	}
 	const int y = frame_row(L, r);
 
-	/* naive_renderer.c:218-221 */
-	const float vx = ((float)x + .5f) / L.fw * 2.f - 1.f;
-	const float vy = 1.f - ((float)y + .5f) / L.fh * 2.f;
-
-	/* get_camera_ray with the per-frame basis hoisted, naive_renderer.c:188-190 */
-	const V3 ro = v3(L.cam.origin), cdir = v3(L.cam.dir);
-	V3 rd = add(scale(v3(L.cam.right), vx * L.cam.width), scale(v3(L.cam.up), vy * L.cam.height));
-	rd = normalize(add(rd, cdir));
+	const V3 rd = camera_ray(L.cam, L.fw, L.fh, x, y), ro = v3(L.cam.origin);
 
 	const Marched marched = march<COUNT>(sdf, ro, rd, L.max_steps, (L.flags & FLAG_FIRST_STEP) != 0u, L.first_dist, L.first_id);
 
@@ -1154,6 +1157,26 @@ __device__ __forceinline__ Pixel shade_pixel(const Launch& L, Sdf& sdf, const u3
 	V3 c = { maxf_(minf_(total.x, 1.f), 0.f), maxf_(minf_(total.y, 1.f), 0.f), maxf_(minf_(total.z, 1.f), 0.f) };
 
 	return { c, hit, shadow_steps };      /* gamma + colorf_to_pixfmt: store_pixel */
+}
+
+/* Gamma + packing of a clamped linear colour, for the kernels that do not store through store_pixel (supersampled frames, batches
+ * of views, blends); `post` = the colour after gamma where the launch has no gamma table or wants the diagnostic colour.
+ * store_pixel below packs with these steps in lines of its own: calling this from it makes hipcc lay the last blocks of every
+ * ahead-of-time render_interp out differently (8 bytes longer), and the change that moved this function here moved no instruction
+ * (DESIGN.md 3.16).  tests/test_gpu_supersample.py holds both paths against the same CPU packing. */
+__device__ __forceinline__ u32 pack_pixel(const Launch& L, const LaunchTail& T, V3 rgb, V3& post) {
+	const bool by_table = (L.flags & FLAG_GAMMA_TABLE) != 0u;
+	post = rgb;
+	if (!by_table || T.dbg_rgb) {
+		const float g = 1.f / 2.2f;
+		post = { powf_glibc(rgb.x, g), powf_glibc(rgb.y, g), powf_glibc(rgb.z, g) };
+	}
+	u32 r8, g8, b8;
+	if (by_table) { r8 = gamma_u8_table(rgb.x, T.gamma_table); g8 = gamma_u8_table(rgb.y, T.gamma_table); b8 = gamma_u8_table(rgb.z, T.gamma_table); }
+	else { r8 = (u32)(post.x * 255.f) & 0xFFu; g8 = (u32)(post.y * 255.f) & 0xFFu; b8 = (u32)(post.z * 255.f) & 0xFFu; }
+	return (r8 >> (T.fmt_loss & 0xFFu)) << (T.fmt_shift & 0xFFu) |
+	       (g8 >> (T.fmt_loss >> 8 & 0xFFu)) << (T.fmt_shift >> 8 & 0xFFu) |
+	       (b8 >> (T.fmt_loss >> 16 & 0xFFu)) << (T.fmt_shift >> 16 & 0xFFu) | T.fmt_amask;
 }
 
 /* Pack the lane's colour for the surface, write it (and the optional diagnostics).  Every thread of the block must call this. */
@@ -1268,19 +1291,23 @@ __device__ __forceinline__ void stage_common(const Launch& L, u32* lds) {
 	for (u32 i = threadIdx.x; i < L.n_roots; i += BLOCK) l_rootm[i] = L.root_material[i];
 }
 
-/* Generic kernel (ahead of time): the SDF is interpreted from the macro-op list in global memory (scalar loads);
- * LDS holds lights | materials | root_material | out tile like in the specialised kernel.  KIND != 0 selects the
- * proven fast sqrt (the host launches that instantiation only after the exhaustive check passed on the device); a
- * wave that fed it a squared length outside its proven domain shades its pixels again with the plain interpreter,
- * as in the specialised kernel. */
-template <int SSIZE, int KIND, bool TABLES_GLOBAL = false>
-__global__ __launch_bounds__(BLOCK)
-void render_interp(const Launch L) {
-	extern __shared__ u32 lds[];
+/* What every interpreter kernel begins with: the tables into LDS, unless they are read where they lie */
+template <bool TABLES_GLOBAL>
+__device__ __forceinline__ void stage_tables(const Launch& L, u32* lds) {
 	if constexpr (!TABLES_GLOBAL) {
 		stage_common(L, lds);
 		__syncthreads();
 	}
+}
+
+/* Generic kernel (ahead of time): the SDF is interpreted from the macro-op list in global memory (scalar loads);
+ * LDS holds lights | materials | root_material | out tile like in the specialised kernel.  KIND != 0 selects the
+ * proven fast sqrt (the host launches that instantiation only after the exhaustive check passed on the device). */
+template <int SSIZE, int KIND, bool TABLES_GLOBAL = false>
+__global__ __launch_bounds__(BLOCK)
+void render_interp(const Launch L) {
+	extern __shared__ u32 lds[];
+	stage_tables<TABLES_GLOBAL>(L, lds);
 	if (!start_tile_clock<TABLES_GLOBAL>(L, lds)) return;
 	Interp<SSIZE, KIND> sdf{ L.ops, L.n_ops, {}, 0u };
 	Pixel P = shade_pixel<Interp<SSIZE, KIND>, TABLES_GLOBAL>(L, sdf, lds);

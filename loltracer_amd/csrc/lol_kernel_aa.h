@@ -13,9 +13,6 @@
  * patches).  An xor butterfly over those bits, lowest k bit first, IS the tree of the contract, and every lane of the group ends
  * with the same bits (float addition is commutative): a dozen VALU instructions against thousands per sample.  Then the pixel's
  * owner lane (i = j = 0) stores it.
- *
- * A file of its own, not part of lol_kernel.h: hipRTC derives the code object's compilation-unit id from the headers it is given,
- * so a scene module WITHOUT the supersampling kernel keeps the bytes — and the kernel_key — it had before this file existed.
  */
 #pragma once
 #include "lol_kernel.h"
@@ -44,47 +41,33 @@ __device__ __forceinline__ Launch sample_launch(const Launch& L) {
 	return S;
 }
 
-/* gamma + packing of a clamped linear colour, as store_pixel does it (naive_renderer.c:231-235, renderer.h:17-22); `post` = the colour
- * after gamma where the launch has no gamma table or wants the diagnostic colour.
- * A COPY of store_pixel's packing steps (lol_kernel.h): a change to one must be made to the other.  store_pixel itself does not call
- * this, and lol_kernel.h carries no pointer back here, because any change to lol_kernel.h's text changes every plain scene module's
- * code object (hipRTC's compilation-unit id follows the header text: see the top of this file) and with it its kernel_key;
- * tests/test_gpu_supersample.py holds both paths against the same CPU packing. */
-__device__ __forceinline__ u32 pack_pixel(const Launch& L, const LaunchTail& T, V3 rgb, V3& post) {
-	const bool by_table = (L.flags & FLAG_GAMMA_TABLE) != 0u;
-	post = rgb;
-	if (!by_table || T.dbg_rgb) {
-		const float g = 1.f / 2.2f;
-		post = { powf_glibc(rgb.x, g), powf_glibc(rgb.y, g), powf_glibc(rgb.z, g) };
-	}
-	u32 r8, g8, b8;
-	if (by_table) { r8 = gamma_u8_table(rgb.x, T.gamma_table); g8 = gamma_u8_table(rgb.y, T.gamma_table); b8 = gamma_u8_table(rgb.z, T.gamma_table); }
-	else { r8 = (u32)(post.x * 255.f) & 0xFFu; g8 = (u32)(post.y * 255.f) & 0xFFu; b8 = (u32)(post.z * 255.f) & 0xFFu; }
-	return (r8 >> (T.fmt_loss & 0xFFu)) << (T.fmt_shift & 0xFFu) |
-	       (g8 >> (T.fmt_loss >> 8 & 0xFFu)) << (T.fmt_shift >> 8 & 0xFFu) |
-	       (b8 >> (T.fmt_loss >> 16 & 0xFFu)) << (T.fmt_shift >> 16 & 0xFFu) | T.fmt_amask;
-}
-
 /* one level of the tree: this lane's partial sum + the one of the lane `m` apart (same bits on both: + is commutative) */
 __device__ __forceinline__ V3 aa_add_xor(V3 v, int m) {
 	return { v.x + __shfl_xor(v.x, m, 64), v.y + __shfl_xor(v.y, m, 64), v.z + __shfl_xor(v.z, m, 64) };
+}
+
+/* The linear mean of the s x s samples of this lane's pixel on the sample grid's tiles: the tree over k = j s + i, lowest bit first
+ * — the bits of i (lane column: xor 1, 2), then those of j (lane row: xor WAVE_W, 2 WAVE_W) — then 1 / s^2.  Every lane of the
+ * pixel ends with the same bits.  Every lane of the wave must call this, all of them active.
+ * (launched only with an s that samples_fit_wave: the lanes xor-paired here are then the same pixel's samples) */
+__device__ __forceinline__ V3 sample_mean(const Launch& L, V3 rgb) {
+	const int s = samples_of(L.flags);
+	V3 c = aa_add_xor(rgb, 1);
+	if (s == 4) c = aa_add_xor(c, 2);
+	c = aa_add_xor(c, WAVE_W);
+	if (s == 4) c = aa_add_xor(c, 2 * WAVE_W);
+	return scale(c, s == 4 ? 1.f / 16.f : 1.f / 4.f);    /* 1 / s^2 */
 }
 
 /* The mean of each pixel's samples, stored by the pixel's owner lane.  `rgb` = this lane's sample (shade_pixel on sample_launch(L)),
  * the fast SDF's exact fallback already done.  Every lane of the wave must call this, all of them active. */
 template <bool TABLES_GLOBAL = false>
 __device__ __forceinline__ void store_pixel_aa(const Launch& L, V3 rgb) {
-	/* (launched only with an s that samples_fit_wave: the lanes xor-paired below are then the same pixel's samples) */
-	const int s = samples_of(L.flags);
-	/* k = j s + i, lowest bit first: the bits of i (lane column: xor 1, 2), then those of j (lane row: xor WAVE_W, 2 WAVE_W) */
-	V3 c = aa_add_xor(rgb, 1);
-	if (s == 4) c = aa_add_xor(c, 2);
-	c = aa_add_xor(c, WAVE_W);
-	if (s == 4) c = aa_add_xor(c, 2 * WAVE_W);
-	c = scale(c, s == 4 ? 1.f / 16.f : 1.f / 4.f);       /* 1 / s^2 */
+	const V3 c = sample_mean(L, rgb);
 	const LaunchTail T = launch_tail(L);
 	V3 post;
 	const u32 px = pack_pixel(L, T, c, post);
+	const int s = samples_of(L.flags);
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	int bx, by;
 	tile_of_block(L, bx, by);
@@ -103,10 +86,7 @@ template <int SSIZE, int KIND, bool TABLES_GLOBAL = false>
 __global__ __launch_bounds__(BLOCK)
 void render_interp_aa(const Launch L) {
 	extern __shared__ u32 lds[];
-	if constexpr (!TABLES_GLOBAL) {
-		stage_common(L, lds);
-		__syncthreads();
-	}
+	stage_tables<TABLES_GLOBAL>(L, lds);
 	const Launch S = sample_launch(L);
 	Interp<SSIZE, KIND> sdf{ L.ops, L.n_ops, {}, 0u };
 	Pixel P = shade_pixel<Interp<SSIZE, KIND>, TABLES_GLOBAL, false>(S, sdf, lds);
@@ -174,10 +154,7 @@ template <int SSIZE, int KIND, bool TABLES_GLOBAL = false>
 __global__ __launch_bounds__(BLOCK)
 void render_interp_aa_list(const Launch L, const u32* list, const u32* count) {
 	extern __shared__ u32 lds[];
-	if constexpr (!TABLES_GLOBAL) {
-		stage_common(L, lds);
-		__syncthreads();
-	}
+	stage_tables<TABLES_GLOBAL>(L, lds);
 	render_aa_list<TABLES_GLOBAL>(L, list, count, [&](const Launch& S) {
 		Interp<SSIZE, KIND> sdf{ L.ops, L.n_ops, {}, 0u };
 		Pixel P = shade_pixel<Interp<SSIZE, KIND>, TABLES_GLOBAL, false>(S, sdf, lds);

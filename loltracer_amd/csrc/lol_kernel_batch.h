@@ -11,13 +11,11 @@
  * launch_tail() reads the destination, the pixel format and the diagnostic pointers from the kernel-argument segment at Launch's
  * offsets, so the kernels' first argument is a lol::Launch (that of a whole frame of the batch's size: n_rows = band_rows =
  * cycle_rows = h), and the view's destination is not patched into the copy: store_pixel_view packs with pack_pixel
- * (lol_kernel_aa.h) and stores at the view's address itself.  With one-wave blocks (the default 16 x 4 patch) a wave's store is
+ * and stores at the view's address itself.  With one-wave blocks (the default 16 x 4 patch) a wave's store is
  * four whole 64-byte row segments, as store_pixel's is after its trip through LDS.
- *
- * A file of its own, like lol_kernel_aa.h and for the same reason: a scene module without the batch kernel keeps its bytes.
  */
 #pragma once
-#include "lol_kernel_aa.h"
+#include "lol_kernel.h"
 
 namespace lol {
 
@@ -38,14 +36,14 @@ struct BatchArgs { Launch L; BatchTail B; };      /* the kernel-argument segment
 /* this block's view */
 __device__ __forceinline__ u32 view_of_block() { return blockIdx.z; }
 
-/* The launch as shade_pixel sees it: the frame of this block's view.  The record is read through the constant address space — the
- * index is wave-uniform — so it arrives in SGPRs like the kernel arguments it replaces. */
-__device__ __forceinline__ Launch view_launch(const Launch& L, const View* views) {
+/* The launch as shade_pixel sees it: the frame of view v, which must be wave-uniform (a scalar).  The record is read through the
+ * constant address space, so it arrives in SGPRs like the kernel arguments it replaces. */
+__device__ __forceinline__ Launch view_launch_of(const Launch& L, const View* views, u32 v) {
 #if defined(__HIP_DEVICE_COMPILE__)
 	typedef const __attribute__((address_space(4))) View* view_ptr;
-	view_ptr V = (view_ptr)(unsigned long long)views + view_of_block();
+	view_ptr V = (view_ptr)(unsigned long long)views + v;
 #else
-	const View* V = views + view_of_block();
+	const View* V = views + v;
 #endif
 	Launch S = L;
 	for (int i = 0; i < 3; i++) { S.cam.origin[i] = V->cam.origin[i]; S.cam.dir[i] = V->cam.dir[i]; S.cam.right[i] = V->cam.right[i]; S.cam.up[i] = V->cam.up[i]; }
@@ -56,6 +54,8 @@ __device__ __forceinline__ Launch view_launch(const Launch& L, const View* views
 	S.ops = L.ops + V->ops_offset;
 	return S;
 }
+/* ... of this block's view */
+__device__ __forceinline__ Launch view_launch(const Launch& L, const View* views) { return view_launch_of(L, views, view_of_block()); }
 
 /* The view stride is needed by the last few instructions alone: read there, from the kernel-argument segment (launch_tail says why). */
 __device__ __forceinline__ unsigned long long view_stride_px(const BatchTail& B0) {
@@ -97,10 +97,7 @@ template <int SSIZE, int KIND, bool TABLES_GLOBAL = false>
 __global__ __launch_bounds__(BLOCK)
 void render_interp_batch(const Launch L, const BatchTail B) {
 	extern __shared__ u32 lds[];
-	if constexpr (!TABLES_GLOBAL) {
-		stage_common(L, lds);
-		__syncthreads();
-	}
+	stage_tables<TABLES_GLOBAL>(L, lds);
 	const Launch S = view_launch(L, B.views);
 	Interp<SSIZE, KIND> sdf{ S.ops, S.n_ops, {}, 0u };
 	Pixel P = shade_pixel<Interp<SSIZE, KIND>, TABLES_GLOBAL>(S, sdf, lds);

@@ -13,46 +13,22 @@
  * number: a wave looks the view of its group up (binary search, scalar loads), so a wave's entries all belong to ONE view and the
  * camera, the first step, the flags and the macro-op list stay wave-uniform; then it does what render_aa_list does for a frame,
  * through its own slot of Launch::lane_pixels.  The grid fills the device whatever the batch; list lengths stay on the device.
- *
- * A file of its own, like lol_kernel_aa.h and lol_kernel_batch.h and for the same reason: a scene module without these kernels
- * keeps its bytes.
  */
 #pragma once
+#include "lol_kernel_aa.h"
 #include "lol_kernel_batch.h"
 
 namespace lol {
 
-/* view_launch (lol_kernel_batch.h) for view v instead of the block's: v must be wave-uniform (a scalar) */
-__device__ __forceinline__ Launch view_launch_of(const Launch& L, const View* views, u32 v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-	typedef const __attribute__((address_space(4))) View* view_ptr;
-	view_ptr V = (view_ptr)(unsigned long long)views + v;
-#else
-	const View* V = views + v;
-#endif
-	Launch S = L;
-	for (int i = 0; i < 3; i++) { S.cam.origin[i] = V->cam.origin[i]; S.cam.dir[i] = V->cam.dir[i]; S.cam.right[i] = V->cam.right[i]; S.cam.up[i] = V->cam.up[i]; }
-	S.cam.width = V->cam.width; S.cam.height = V->cam.height;
-	S.first_dist = V->first_dist;
-	S.first_id = V->first_id;
-	S.flags = (L.flags & ~VIEW_FLAGS) | (V->flags & VIEW_FLAGS);
-	S.ops = L.ops + V->ops_offset;
-	return S;
-}
-
-/* The mean of each pixel's samples (store_pixel_aa's tree over the same lane bits), stored by the pixel's owner lane at this
- * block's view (store_pixel_view's addressing).  `L`: the KERNEL's launch — w, h in pixels, whole frames; `rgb`: this lane's
- * sample, the fast SDF's exact fallback already done.  Every lane of the wave must call this, all of them active. */
+/* The mean of each pixel's samples (sample_mean), stored by the pixel's owner lane at this block's view (store_pixel_view's
+ * addressing).  `L`: the KERNEL's launch — w, h in pixels, whole frames; `rgb`: this lane's sample, the fast SDF's exact fallback
+ * already done.  Every lane of the wave must call this, all of them active. */
 __device__ __forceinline__ void store_pixel_view_aa(const Launch& L, const BatchTail& B, V3 rgb) {
-	const int s = samples_of(L.flags);
-	V3 c = aa_add_xor(rgb, 1);
-	if (s == 4) c = aa_add_xor(c, 2);
-	c = aa_add_xor(c, WAVE_W);
-	if (s == 4) c = aa_add_xor(c, 2 * WAVE_W);
-	c = scale(c, s == 4 ? 1.f / 16.f : 1.f / 4.f);       /* 1 / s^2 */
+	const V3 c = sample_mean(L, rgb);
 	const LaunchTail T = launch_tail(L);
 	V3 post;
 	const u32 px = pack_pixel(L, T, c, post);
+	const int s = samples_of(L.flags);
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	int bx, by;
 	tile_of_block(L, bx, by);
@@ -72,10 +48,7 @@ template <int SSIZE, int KIND, bool TABLES_GLOBAL = false>
 __global__ __launch_bounds__(BLOCK)
 void render_interp_batch_aa(const Launch L, const BatchTail B) {
 	extern __shared__ u32 lds[];
-	if constexpr (!TABLES_GLOBAL) {
-		stage_common(L, lds);
-		__syncthreads();
-	}
+	stage_tables<TABLES_GLOBAL>(L, lds);
 	const Launch S = sample_launch(view_launch(L, B.views));
 	Interp<SSIZE, KIND> sdf{ S.ops, S.n_ops, {}, 0u };
 	Pixel P = shade_pixel<Interp<SSIZE, KIND>, TABLES_GLOBAL, false>(S, sdf, lds);
@@ -150,10 +123,7 @@ template <int SSIZE, int KIND, bool TABLES_GLOBAL = false>
 __global__ __launch_bounds__(BLOCK)
 void render_interp_batch_aa_list(const Launch L, const BatchTail B, const BatchLists Q) {
 	extern __shared__ u32 lds[];
-	if constexpr (!TABLES_GLOBAL) {
-		stage_common(L, lds);
-		__syncthreads();
-	}
+	stage_tables<TABLES_GLOBAL>(L, lds);
 	render_aa_view_lists<TABLES_GLOBAL>(L, B, Q, [&](const Launch& S) {
 		Interp<SSIZE, KIND> sdf{ S.ops, S.n_ops, {}, 0u };
 		Pixel P = shade_pixel<Interp<SSIZE, KIND>, TABLES_GLOBAL, false>(S, sdf, lds);

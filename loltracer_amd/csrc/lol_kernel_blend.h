@@ -15,8 +15,7 @@
  * dwordx3 per lane in segments of 192 bytes, every other one straddling a line it shares with the next tile; planar, three stores
  * per lane.  Chosen on those grounds; DESIGN.md 3.13 says what was measured of it.
  *
- * No step counters.  A file of its own, like lol_kernel_aa.h and lol_kernel_batch.h and for the same reason: a scene module without
- * this kernel keeps its bytes.
+ * No step counters.
  */
 #pragma once
 #include "lol_kernel_batch.h"
@@ -46,10 +45,7 @@ template <int SSIZE, int KIND, bool TABLES_GLOBAL = false>
 __global__ __launch_bounds__(BLOCK)
 void render_interp_batch_lin(const Launch L, const BatchTail B) {
 	extern __shared__ u32 lds[];
-	if constexpr (!TABLES_GLOBAL) {
-		stage_common(L, lds);
-		__syncthreads();
-	}
+	stage_tables<TABLES_GLOBAL>(L, lds);
 	const Launch S = view_launch(L, B.views);
 	Interp<SSIZE, KIND> sdf{ S.ops, S.n_ops, {}, 0u };
 	Pixel P = shade_pixel<Interp<SSIZE, KIND>, TABLES_GLOBAL, false>(S, sdf, lds);

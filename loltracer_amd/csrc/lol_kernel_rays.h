@@ -9,12 +9,6 @@
  *
  * One wave per block, as in sdf_points: a block is done when its own 64 rays are, rays of a list differ in cost as pixels do, and
  * with neither LDS nor a barrier nothing is gained from a larger block.
- *
- * A file of its own, not part of lol_kernel.h: hipRTC derives the code object's compilation-unit id from the headers it is given,
- * so a scene module WITHOUT the query kernel keeps the bytes — and the kernel_key — it had before this file existed.  For the same
- * reason camera_ray() below is a COPY of the first lines of shade_pixel (lol_kernel.h) and shade_pixel does not call it: any change
- * to lol_kernel.h's text changes every plain scene module's code object (lol_kernel_aa.h, pack_pixel, is the precedent).  A change
- * to one must be made to the other; tests/test_gpu_rays.py holds the two to each other bit for bit (lol_gpu_debug's planes).
  */
 #pragma once
 #include "lol_kernel.h"
@@ -58,16 +52,6 @@ __device__ __forceinline__ RayOut ray_out(const RayQuery& Q0) {
 #else
 	return Q0.out;
 #endif
-}
-
-/* The primary ray of pixel (x, y) of a frame of fw x fh pixels, naive_renderer.c:218-221 and get_camera_ray (:188-190) with the
- * per-frame basis hoisted: shade_pixel's own lines (see the top of this file).  (x, y) need not lie in the frame. */
-__device__ __forceinline__ V3 camera_ray(const Cam& cam, float fw, float fh, int x, int y) {
-	const float vx = ((float)x + .5f) / fw * 2.f - 1.f;
-	const float vy = 1.f - ((float)y + .5f) / fh * 2.f;
-	const V3 cdir = v3(cam.dir);
-	V3 rd = add(scale(v3(cam.right), vx * cam.width), scale(v3(cam.up), vy * cam.height));
-	return normalize(add(rd, cdir));
 }
 
 struct RayHit { float dist; u32 id; u32 steps; V3 n; };

@@ -87,7 +87,7 @@ bool load_scene_kernel(const std::vector<char>& code, uint32_t n_ops, ModuleKern
 		return false;
 	};
 	const bool two = n_ops <= LOL_SPEC_TWO_KERNELS_MAX_OPS;
-	k.key = fnv_hex(code.data(), code.size());
+	k.key = code_key_hex(code.data(), code.size());
 	bool ok = hipModuleLoadData(&k.module, code.data()) == hipSuccess;
 	if (!ok) why = "hipModuleLoadData failed";
 	ok = ok && get(k.sdf, "lol_sdf_spec");

@@ -146,6 +146,8 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_set_pixel_format.restype = C.c_int
         lib.lol_gpu_kernel_key.argtypes = [vp]
         lib.lol_gpu_kernel_key.restype = C.c_char_p
+        lib.lol_gpu_code_key.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
+        lib.lol_gpu_code_key.restype = None
         lib.lol_gpu_roctx_ranges.argtypes = []
         lib.lol_gpu_roctx_ranges.restype = C.c_long
         lib.lol_gpu_sync.argtypes = [vp]
@@ -386,13 +388,20 @@ DIAG_SYMBOLS = [                                                        # includ
     "lol_gpu_compile_offline_views", "lol_gpu_compile_offline_view_samples", "lol_gpu_view_samples_kernel_name",
     "lol_gpu_views_refined", "lol_gpu_interp_variant", "lol_gpu_compile_offline_view_blends", "lol_gpu_view_blend_kernel_name",
     "lol_gpu_compile_offline_view_blend_samples", "lol_gpu_view_blend_samples_kernel_name",
-    "lol_gpu_trace_kernel_name", "lol_gpu_compile_offline_rays",
+    "lol_gpu_trace_kernel_name", "lol_gpu_compile_offline_rays", "lol_gpu_code_key",
 ]
 
 
 def tuning_switches() -> str:
     """lol_gpu_tuning_switches: the LOL_GPU_* A/B switches this process has honoured so far (needs LOL_GPU_TUNING=1)."""
     return gpu_lib().lol_gpu_tuning_switches().decode()
+
+
+def code_key(code: bytes) -> str:
+    """lol_gpu_code_key: the kernel_key of a code object's bytes (a .co of compile_offline*).  Needs no device."""
+    out = C.create_string_buffer(17)
+    gpu_lib().lol_gpu_code_key(code, len(code), out)
+    return out.value.decode()
 
 
 def compile_offline(program: S.Program, out_base: str, arch: str = "gfx950", assume_fast: bool = False) -> str:

@@ -303,7 +303,7 @@ def test_rejected_upload_leaves_the_previous_scene_rendering(torch_cuda, scenes,
 
 
 @pytest.mark.gpu
-def test_kernel_key_names_the_code(torch_cuda, scenes):
+def test_kernel_key_names_the_code(torch_cuda, scenes, tmp_path):
     r = gpu.Renderer(0)
     r.prepare(scenes["scene4"])
     k4 = r.kernel_key()
@@ -323,7 +323,15 @@ def test_kernel_key_names_the_code(torch_cuda, scenes):
     rf = gpu.Renderer(0, specialize=4)                   # interpreter + proven fast paths: other records, other key
     rf.prepare(scenes["scene4"])
     assert rf.kernel_name() == "render_interp" and rf.kernel_key() != i4
-    r.close(); ri.close(); rf.close()
+    # a scene kernel's key is gpu.code_key of its code object — what the device loads of it: a context without the proven shortcuts
+    # (which need a device to prove them) runs the module compile_offline makes in this process
+    rp = gpu.Renderer(0, specialize=3)
+    rp.prepare(scenes["scene4"])
+    base = str(tmp_path / "scene4")
+    gpu.compile_offline(scenes["scene4"].flatten(), base)
+    with open(base + ".co", "rb") as f:
+        assert rp.kernel_name() == "lol_render_spec" and rp.kernel_key() == gpu.code_key(f.read()) != k4
+    r.close(); ri.close(); rf.close(); rp.close()
 
 
 ROCTX_SCRIPT = r"""

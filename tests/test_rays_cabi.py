@@ -4,6 +4,7 @@ import hashlib
 import json
 import os
 import re
+import struct
 import subprocess
 
 import pytest
@@ -72,11 +73,56 @@ def test_without_the_switch_every_module_is_what_it_was(tmp_path, scenes):
         assert b"trace" not in src and b"rays" not in src
 
 
-def test_the_pipeline_header_is_what_it_was():
-    """lol_kernel.h's text is part of every scene module's code object (hipRTC's compilation-unit id follows the headers), so the
-    query kernel lives in a header of its own and lol_kernel.h does not know of it: a plain module keeps its lol_gpu_kernel_key."""
-    text = read(os.path.join(ROOT, "loltracer_amd", "csrc", "lol_kernel.h"))
-    assert "lol_kernel_rays" not in text and "RayQuery" not in text and not re.search(r"\bcamera_ray\(", text) and "trace_rays" not in text
+def fnv64(data, h=0xcbf29ce484222325):
+    for c in data:
+        h = ((h ^ c) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def loaded_sections(path):
+    """[(name, offset, size)] of a code object's allocated PROGBITS and NOTE sections, in section-header order"""
+    text = subprocess.run([READELF, "-S", "-W", path], check=True, stdout=subprocess.PIPE, text=True).stdout
+    rows = re.findall(r"\]\s+(\.\S+)\s+(\w+)\s+[0-9a-f]+\s+([0-9a-f]+)\s+([0-9a-f]+)\s+[0-9a-f]+\s+([A-Za-z]*)\s+\d+\s+\d+\s+\d+", text)
+    return [(name, int(off, 16), int(size, 16)) for name, kind, off, size, flags in rows if "A" in flags and kind in ("PROGBITS", "NOTE")]
+
+
+def test_the_key_covers_what_the_device_loads(tmp_path, scenes):
+    """lol_gpu_kernel_key's function of a code object (gpu.code_key): FNV-1a over the sections the device loads, each as its size and
+    its bytes.  The compilation-unit id hipRTC derives from the header texts — a symbol's NAME — is not in it, so a kernel header may
+    change its text without renaming the instructions of modules that do not change; every loaded byte is; and a buffer that is no
+    sound ELF file gets the hash of all its bytes, whatever its headers claim."""
+    base = str(tmp_path / "scene4")
+    gpu.compile_offline(scenes["scene4"].flatten(), base)
+    co = read(base + ".co", "rb")
+    key = gpu.code_key(co)
+    assert re.fullmatch(r"[0-9a-f]{16}", key) and key != "%016x" % fnv64(co)
+    secs = loaded_sections(base + ".co")
+    assert sorted(n for n, _, _ in secs) == [".note", ".rodata", ".text"]
+    h = 0xcbf29ce484222325
+    for _, off, size in secs:
+        h = fnv64(co[off:off + size], fnv64(struct.pack("<Q", size), h))
+    assert key == "%016x" % h                                             # the definition of include/lol_gpu.h, restated
+    renamed = re.sub(rb"(__hip_cuid_)[0-9a-f]{16}", rb"\g<1>0123456789abcdef", co)
+    assert renamed != co and len(renamed) == len(co) and gpu.code_key(renamed) == key
+    for _, off, size in secs:
+        for at in (off, off + size // 2, off + size - 1):
+            flipped = co[:at] + bytes([co[at] ^ 1]) + co[at + 1:]
+            assert gpu.code_key(flipped) != key, (at, off, size)
+    for n in (10, 63, 64):
+        assert gpu.code_key(co[:n]) == "%016x" % fnv64(co[:n]), n
+    past = co[:40] + struct.pack("<Q", len(co) + 1) + co[48:]                # e_shoff beyond the end
+    assert gpu.code_key(past) == "%016x" % fnv64(past)
+    e_shoff, = struct.unpack_from("<Q", co, 40)
+    e_shnum, = struct.unpack_from("<H", co, 60)
+    text_off = dict((n, off) for n, off, _ in secs)[".text"]
+    for i in range(e_shnum):                                              # .text's header claims a size beyond the file
+        if struct.unpack_from("<Q", co, e_shoff + 64 * i + 24)[0] == text_off:
+            wild = co[:e_shoff + 64 * i + 32] + struct.pack("<Q", len(co)) + co[e_shoff + 64 * i + 40:]
+            assert gpu.code_key(wild) == "%016x" % fnv64(wild)
+            break
+    else:
+        assert False, "no section header for .text"
+    assert gpu.code_key(b"") == "%016x" % fnv64(b"")
 
 
 def test_the_switch_appends_the_query_kernel(tmp_path, scenes):

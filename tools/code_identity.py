@@ -1,0 +1,186 @@
+#!/usr/bin/env python3
+"""Do two builds of this library make the same device code?  Needs no GPU.
+
+Compares this checkout with another built checkout of the repository (`--parent TREE`, `make` already run in its
+loltracer_amd/csrc) and writes what was compared, and the result, as JSON:
+
+  scene modules      for the four example scenes and the mid-size scene of tests/scene_shapes.py in both of its forms, each module
+                     switch on its own plus the query kernel beside all the others, with and without assume_fast: the contents
+                     of .text, .rodata and .note of the hipRTC code object — what lol_gpu_kernel_key covers — must be equal.
+  ahead of time      the six .hip units compiled device-only with the Makefile's flags in both trees: every kernel's bytes and
+                     its .kd descriptor must be equal, by name.
+
+    python tools/code_identity.py --parent ../parent --work /tmp/ident --out profiles/r14_code_identity.json
+
+`--work DIR/parent` is kept and reused when it is there, so a second run only compiles this checkout again.  Exit status 1 when
+anything differs.
+"""
+import argparse
+import hashlib
+import json
+import os
+import struct
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCENES = ("scene", "scene2", "scene3", "scene4")
+# (name, lol_gpu_compile_offline_rays' enable, its mask of the other switches): the module of each lol_gpu_compile_offline* call
+MODULES = (("compile_offline", 0, 0), ("_samples", 0, 2), ("_views", 0, 4), ("_view_samples", 0, 8), ("_view_blends", 0, 1),
+           ("_view_blend_samples", 0, 16), ("_rays+all", 1, 31))
+LOADED = (".text", ".rodata", ".note")
+UNITS = ("lol_gpu", "lol_tiers", "lol_proofs", "lol_codegen", "lol_sched", "lol_multi")
+
+
+# ---------------------------------------------------------------- ELF64 little-endian, as much as is needed
+def sections(data):
+    """{name: (type, flags, addr, offset, size)}"""
+    shoff, = struct.unpack_from("<Q", data, 40)
+    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", data, 58)
+    raw = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + i * shentsize) for i in range(shnum)]
+    names = data[raw[shstrndx][4]:raw[shstrndx][4] + raw[shstrndx][5]]
+    return {names[r[0]:names.index(b"\0", r[0])].decode(): (r[1], r[2], r[3], r[4], r[5]) for r in raw}
+
+
+def section_bytes(data, sec):
+    return data[sec[3]:sec[3] + sec[4]]
+
+
+def kernels(data):
+    """{kernel: (its instructions, its descriptor)} for every symbol NAME that has a NAME.kd beside it"""
+    secs = sections(data)
+    shoff, = struct.unpack_from("<Q", data, 40)
+    shentsize, shnum, _ = struct.unpack_from("<HHH", data, 58)
+    raw = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + i * shentsize) for i in range(shnum)]
+    symtab, strtab = secs[".symtab"], secs[".strtab"]
+    names = section_bytes(data, strtab)
+    syms = {}
+    for at in range(symtab[3], symtab[3] + symtab[4], 24):
+        name, _info, _other, shndx, value, size = struct.unpack_from("<IBBHQQ", data, at)
+        if 0 < shndx < shnum:
+            sec = raw[shndx]
+            syms[names[name:names.index(b"\0", name)].decode()] = data[sec[4] + value - sec[3]:sec[4] + value - sec[3] + size]
+    return {n: (syms[n], syms[n + ".kd"]) for n in syms if n + ".kd" in syms}
+
+
+def sha(b):
+    return hashlib.sha256(b).hexdigest()[:16]
+
+
+# ---------------------------------------------------------------- one build's code objects
+def emit_modules(tree, out_dir):
+    """(worker) every scene module of the build in `tree`, through that tree's own Python mirror, into out_dir"""
+    sys.path[:0] = [tree, os.path.join(tree, "tests")]
+    from loltracer_amd import gpu, scene as S
+    import scene_shapes as C
+    progs = [(n, S.Scene.parse_file(os.path.join(tree, "tests", "golden", "scenes", n + ".lol")).flatten(), 0) for n in SCENES]
+    mid = C.scene_of(C.MID).flatten()
+    progs += [("mid_form1", mid, 1), ("mid_form2", mid, 2)]
+    want = os.environ.get("CODE_IDENTITY_ONLY")
+    lib = gpu.gpu_lib()
+    for name, prog, form in progs:
+        if want and name != want:
+            continue
+        for module, enable, others in MODULES:
+            for fast in (0, 1):
+                base = os.path.join(out_dir, "%s.%s.fast%d" % (name, module, fast))
+                st = lib.lol_gpu_compile_offline_rays(prog, b"gfx950", os.fsencode(base), fast, enable, others, form, None, 0)
+                if st != 0:
+                    raise SystemExit("%s: compile failed (%d)" % (base, st))
+
+
+def compile_modules(tree, out_dir, jobs):
+    os.makedirs(out_dir, exist_ok=True)
+    env = dict(os.environ, LOL_GPU_CACHE_DIR="")               # no disk cache: every module is really compiled
+    env.pop("LOL_GPU_LIB", None)
+    running = []
+    for n in list(SCENES) + ["mid_form1", "mid_form2"]:         # the scene compiler runs one module at a time per process
+        running.append(subprocess.Popen([sys.executable, os.path.abspath(__file__), "--emit", out_dir, "--parent", tree],
+                                        env=dict(env, CODE_IDENTITY_ONLY=n)))
+        if len(running) >= jobs and running.pop(0).wait() != 0:
+            raise SystemExit("a worker failed")
+    if any(p.wait() != 0 for p in running):
+        raise SystemExit("a worker failed")
+
+
+def compile_ahead_of_time(tree, out_dir):
+    """the six units with the Makefile's own flags, device side only, as plain code objects"""
+    os.makedirs(out_dir, exist_ok=True)
+    csrc = os.path.join(tree, "loltracer_amd", "csrc")
+    flags = subprocess.run(["make", "-s", "-C", csrc, "--eval", "print-flags: ; @echo $(HIPCC) $(HIPFLAGS)", "print-flags"],
+                           check=True, stdout=subprocess.PIPE, text=True).stdout.split()
+    subprocess.run(["make", "-s", "-C", csrc, "lol_kernel_src.inc", "lol_build_id.inc"], check=True)
+    running = [subprocess.Popen(flags + ["--cuda-device-only", "--no-gpu-bundle-output", "-c", "-o", os.path.join(out_dir, u + ".aot.co"), u + ".hip"],
+                                cwd=csrc) for u in UNITS]
+    if any(p.wait() != 0 for p in running):
+        raise SystemExit("hipcc failed")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--emit", help=argparse.SUPPRESS)
+    ap.add_argument("--parent", help="a built checkout of the commit to compare with")
+    ap.add_argument("--work", help="directory for the code objects")
+    ap.add_argument("--out", help="the JSON record")
+    ap.add_argument("--jobs", type=int, default=6)
+    ap.add_argument("--compare-only", action="store_true", help="compile nothing: compare what --work holds")
+    a = ap.parse_args()
+    if a.emit:
+        return emit_modules(a.parent, a.emit)
+    old, new = os.path.join(a.work, "parent"), os.path.join(a.work, "this")
+    if not a.compare_only:
+        if not os.path.exists(os.path.join(old, "lol_gpu.aot.co")):
+            compile_ahead_of_time(os.path.abspath(a.parent), old)
+        if not os.path.exists(os.path.join(old, "scene.compile_offline.fast0.co")):
+            compile_modules(os.path.abspath(a.parent), old, a.jobs)
+        compile_ahead_of_time(ROOT, new)
+        compile_modules(ROOT, new, a.jobs)
+
+    def read(d, f):
+        with open(os.path.join(d, f), "rb") as fh:
+            return fh.read()
+
+    differing, modules, units = [], [], []
+    files = sorted(f for f in os.listdir(old) if f.endswith(".co"))
+    assert files == sorted(f for f in os.listdir(new) if f.endswith(".co")), "the two builds wrote different sets of modules"
+    for f in files:
+        x, y = read(old, f), read(new, f)
+        if f.endswith(".aot.co"):
+            kx, ky = kernels(x), kernels(y)
+            bad = sorted(n for n in set(kx) | set(ky) if kx.get(n) != ky.get(n))
+            units.append({"unit": f[:-len(".aot.co")] + ".hip", "kernels": len(ky),
+                          "sha256_16_of_all": sha(b"".join(n.encode() + b"\0" + ky[n][0] + ky[n][1] for n in sorted(ky))), "differing": bad})
+            differing += [f + ": " + n for n in bad]
+        else:
+            sx, sy = sections(x), sections(y)
+            rec = {"module": f[:-3], "file_bytes_differing": sum(p != q for p, q in zip(x, y)) + abs(len(x) - len(y))}
+            for s in LOADED:
+                bx, by = section_bytes(x, sx[s]), section_bytes(y, sy[s])
+                rec[s] = {"bytes": len(by), "sha256_16": sha(by), "equal": bx == by}
+                if bx != by:
+                    differing.append(f + ": " + s)
+            assert hashlib.sha256(read(old, f[:-3] + ".hip")).digest() == hashlib.sha256(read(new, f[:-3] + ".hip")).digest(), f + ": generated source differs"
+            modules.append(rec)
+    head = lambda tree: subprocess.run(["git", "-C", tree, "rev-parse", "HEAD"], stdout=subprocess.PIPE, text=True).stdout.strip()
+    record = {
+        "what": "device code of this change against its parent commit, compared on a machine without a GPU (tools/code_identity.py)",
+        "parent_commit": head(a.parent) if a.parent else None,
+        "compared": {"scene_modules": "contents of .text, .rodata and .note of the hipRTC code object (gfx950), and the generated source",
+                     "ahead_of_time": "every kernel's bytes and its .kd descriptor, by name, of each .hip unit compiled device-only with the Makefile's flags"},
+        "scenes": list(SCENES) + ["scene_shapes.MID form 1", "scene_shapes.MID form 2"],
+        "modules": [m[0] for m in MODULES], "assume_fast": [0, 1],
+        "n_scene_modules": len(modules), "n_ahead_of_time_kernels": sum(u["kernels"] for u in units),
+        "identical": not differing, "differing": differing,
+        "scene_modules": modules, "ahead_of_time_units": units,
+    }
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(record, fh, indent=1)
+            fh.write("\n")
+    print("identical" if not differing else "DIFFERING:\n  " + "\n  ".join(differing[:40]))
+    print("%d scene modules, %d ahead-of-time kernels" % (len(modules), record["n_ahead_of_time_kernels"]))
+    return 1 if differing else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
