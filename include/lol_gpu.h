@@ -203,6 +203,8 @@ void* lol_gpu_next_stream(lol_gpu* ctx);
 int lol_gpu_malloc(lol_gpu* ctx, size_t bytes, void** out);
 int lol_gpu_free(lol_gpu* ctx, void* ptr);
 int lol_gpu_memcpy_d2h(lol_gpu* ctx, void* host, const void* dev, size_t bytes);
+/* ... and the other way, for what a host brings to a query (a list of rays or pixels): waits for the copy */
+int lol_gpu_memcpy_h2d(lol_gpu* ctx, void* dev, const void* host, size_t bytes);
 
 /*
  * Supersampling: s x s samples per pixel on an ordered grid, s in {1, 2, 4} (default 1: one ray per pixel, today's frames byte
@@ -634,8 +636,9 @@ int  lol_gpu_assemble_parts_at(lol_gpu* ctx, const void* parts, const lol_gpu_ro
  * record rings: a frame after a query is the frame it would have been.  lol_gpu_set_miss_skip / lol_gpu_set_exact_skips do not apply
  * (there is no shading); lol_gpu_set_cull applies as it does to frames: same answers either way.
  *
- * Out of scope: shading or shadow queries (colour along arbitrary rays), lol_gpu_multi_* forms, rays in host memory beyond the
- * one-pixel lol_gpu_pick, and the renderer.h protocol.
+ * Out of scope for these entry points: shading or shadow queries (the colour along arbitrary rays is lol_gpu_shade_rays', below; a
+ * shadow factor as an output of its own is not built), lol_gpu_multi_* forms, rays in host memory beyond the one-pixel
+ * lol_gpu_pick, and the renderer.h protocol.
  */
 typedef struct lol_gpu_hits {     /* DEVICE pointers, each may be NULL (not all four); element i belongs to ray i */
 	float*    dist;               /* get_intersection().dist                               naive_renderer.c:68 */
@@ -677,6 +680,60 @@ int  lol_gpu_pick(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int m
  */
 int  lol_gpu_set_ray_queries(lol_gpu* ctx, int enable);
 int  lol_gpu_ray_queries(const lol_gpu* ctx);
+
+/*
+ * Shading queries: the COLOUR the reference computes along rays the host brings itself — an equirectangular panorama or a fisheye,
+ * a torch pipeline with its own camera model, the linear colour of a few pixels without a frame, one sample of a supersampled pixel.
+ *
+ * Ray i is EXACTLY naive_renderer.c:225-232 for one ray (ro, rd): get_intersection(scene, ro, rd) with MAX_STEPS = max_steps,
+ * p = ro + rd * dist, get_normal(scene, p, dist), get_light(scene', p, n, id), v3pow(., 1 / 2.2), colorf_to_pixfmt — where scene' is
+ * the uploaded scene with camera.point = ro: get_light reads the eye position from the scene (:132, :145), and a ray's eye is its
+ * own origin.  For a frame ro is the camera's position, so this is no new definition.  The same device code the frames shade with.
+ *
+ * lol_gpu_set_miss_skip / lol_gpu_set_exact_skips and lol_gpu_set_cull apply as they do to frames: the colours are the same either
+ * way, `steps` counts the steps really marched.  The pixel format (lol_gpu_set_pixel_format) and the proven gamma table are read.
+ * The tile-order state, lol_gpu_set_samples / lol_gpu_set_adaptive_samples and the record rings are neither read nor written: a
+ * frame after a query is the frame it would have been.
+ *
+ * Out of scope: a per-light shadow-factor output, normals (lol_gpu_trace_rays has them), lol_gpu_multi_* forms, rays in host
+ * memory, a shading pick, and the renderer.h protocol.
+ */
+typedef struct lol_gpu_shades {   /* DEVICE pointers, each may be NULL (not all six); element i belongs to ray i */
+	float*    rgb_linear;         /* 3 floats: what get_light() returns (naive_renderer.c:229), clamped, before gamma */
+	float*    rgb;                /* 3 floats: after gamma (:231) — lol_gpu_debug.rgb of that pixel                    */
+	uint32_t* pixel;              /* packed in the context's pixel format (lol_gpu_set_pixel_format), like a frame's   */
+	float*    hit_dist;           /* as lol_gpu_debug                                                                  */
+	uint32_t* hit_id;
+	uint32_t* steps;              /* low 16 bits march steps, high 16 bits shadow steps summed over the lights         */
+} lol_gpu_shades;
+/*
+ * rays_dev: n x {ox, oy, oz, dx, dy, dz} in device memory, read only, used as given like lol_gpu_trace_rays': not normalised, any
+ * component may be zero, non-finite, huge, denormal or -0, and each ray's answer is the reference's arithmetic on those bits,
+ * whatever the other rays of the list are.
+ * Asynchronous on `stream` (NULL = the context's own stream; LOL_GPU_STREAM_DEFAULT as elsewhere): one launch, no host wait, no
+ * copy, no scratch.  n == 0 returns LOL_GPU_OK with nothing launched; nothing beyond element n - 1 of any output is written.
+ * Refused, with nothing launched and nothing written: no context, NULL rays_dev with n > 0, NULL out or all six outputs NULL,
+ * max_steps < 0, n > 2^32 - 1: LOL_GPU_ERR_ARG; no program: LOL_GPU_ERR_NO_PROGRAM.
+ */
+int  lol_gpu_shade_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_shades* out, void* stream);
+/*
+ * Ray i is the primary ray of pixel (x_i, y_i) = (xy_dev[2i], xy_dev[2i + 1]) of the w x h frame under `cam`, built as
+ * lol_gpu_trace_pixels builds it.  For a pixel inside the frame `pixel`, `rgb`, `hit_dist`, `hit_id` and `steps` ARE that pixel of
+ * lol_gpu_render_device and its lol_gpu_debug planes under the same camera, settings and pixel format, bit for bit.  A pair
+ * outside the frame gives the ray that formula gives.  The sample rays of lol_gpu_set_samples(s) are pixels (s x + i, s y + j) of
+ * the s w x s h frame under the same `cam`; their `rgb_linear` are the leaves of that pixel's tree.
+ * Refusals as for lol_gpu_shade_rays (xy_dev in the place of rays_dev), and LOL_GPU_ERR_ARG for w < 1, h < 1 or a NULL cam.
+ */
+int  lol_gpu_shade_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
+                          const uint32_t* xy_dev, size_t n, const lol_gpu_shades* out, void* stream);
+/*
+ * Which kernel answers: after lol_gpu_set_shade_queries(ctx, 1) BEFORE lol_gpu_upload_program the scene's own module also carries
+ * lol_shade_spec (both kernels of a 257 ... 1024-op scene do); otherwise, and until that module is ready, the interpreter's
+ * shade_interp answers — same bits either way.  A module compiled without the switch is the module it was before the switch
+ * existed: same source, same code object, same lol_gpu_kernel_key.
+ */
+int  lol_gpu_set_shade_queries(lol_gpu* ctx, int enable);
+int  lol_gpu_shade_queries(const lol_gpu* ctx);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,17 @@ const char* lol_gpu_trace_kernel_name(const lol_gpu* ctx);
  */
 int         lol_gpu_compile_offline_rays(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                          int enable, int others, int form, char* log, size_t logcap);
+/* The kernel the NEXT shading query of this context (lol_gpu_shade_rays, lol_gpu_shade_pixels) launches, decided by the test the
+ * launch itself makes: "lol_shade_spec" / "shade_interp"; "" for a NULL context. */
+const char* lol_gpu_shade_kernel_name(const lol_gpu* ctx);
+/*
+ * ... and the module of a context that asked for shading queries (lol_gpu_set_shade_queries) before its upload: enable = 0 writes
+ * exactly what the module with `others` alone is; 1 the same source with `#include "lol_kernel_shade.h"` and lol_shade_spec appended
+ * last, and its code object.  `others`: lol_gpu_compile_offline_rays' mask of the context's other switches with
+ * 32 = lol_gpu_set_ray_queries added (LOL_GPU_ERR_ARG outside 0 ... 63).  form as above.  Needs no device.
+ */
+int         lol_gpu_compile_offline_shade(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                          int enable, int others, int form, char* log, size_t logcap);
 /*
  * lol_gpu_kernel_key's function of a code object (lol_gpu.h says what it covers), for n bytes of one in host memory — a .co of
  * lol_gpu_compile_offline* — as 16 hex digits and a NUL in out.  A buffer that is no ELF64 little-endian file, or whose section

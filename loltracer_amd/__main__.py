@@ -1,6 +1,6 @@
 """python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N] [--samples N]
                           [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]] [--orbit-shutter K]]
-                          [--lens R (--focus D | --focus-at X,Y) --lens-samples K] [--pick X,Y]
+                          [--lens R (--focus D | --focus-at X,Y) --lens-samples K] [--pick X,Y] [--panorama WxH -o FILE.ppm]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
@@ -12,8 +12,9 @@ inside its own exposure: view v is the mean in linear light of cameras v K ... v
 scene.lens_cameras on a lens of radius R focused at distance D; with --samples S every lens camera is supersampled S x S (not with
 --adaptive); --focus-at X,Y in the place of --focus D is autofocus: D is the distance, along the camera's axis, of what pixel
 (X, Y) shows (one Renderer.pick; refused when that ray escapes).  --pick X,Y prints the object id, distance, step count and normal
-under pixel (X, Y) of the --size frame (one ray, Renderer.pick); no frame is rendered unless -o is also given.  There is no CPU
-rendering path."""
+under pixel (X, Y) of the --size frame (one ray, Renderer.pick); no frame is rendered unless -o is also given.  --panorama WxH
+writes the equirectangular image of everything round the camera's position: the rays of scene.panorama_rays shaded by ONE shading
+query (Renderer.shade_rays_into) — rays of the host's own making, the reference's colours.  There is no CPU rendering path."""
 from __future__ import annotations
 
 import argparse
@@ -129,6 +130,40 @@ def lens(sc, args, w, h) -> int:
     return 0
 
 
+def panorama(sc, args) -> int:
+    """the equirectangular image round the camera into one PPM: one list of rays, one shading query"""
+    try:
+        w, h = (int(v) for v in args.panorama.lower().split("x"))
+    except ValueError:
+        w = h = 0
+    if w < 1 or h < 1 or not args.out:
+        print("--panorama takes WxH and -o FILE.ppm", file=sys.stderr)
+        return 1
+    rays = S.panorama_rays(sc.camera, w, h)
+    r = gpu.Renderer(args.device)
+    try:
+        r.set_shade_queries(True)            # before prepare(): the scene's own kernel then carries the shading-query form
+        r.prepare(sc)
+        surf = np.zeros((h, w), dtype=np.uint32)
+        d_rays, d_px = r.malloc(rays.nbytes), r.malloc(surf.nbytes)
+        try:
+            r.memcpy_h2d(d_rays, rays.ctypes.data, rays.nbytes)
+            t0 = time.perf_counter()
+            r.shade_rays_into(d_rays, len(rays), args.max_steps, pixel_ptr=d_px)
+            r.sync()
+            dt = (time.perf_counter() - t0) * 1e3
+            r.memcpy_d2h(surf.ctypes.data, d_px, surf.nbytes)
+            name = r.shade_kernel_name()
+        finally:
+            r.free(d_rays)
+            r.free(d_px)
+    finally:
+        r.close()
+    print(f"panorama {w}x{h}: {dt:.3f}ms  {w * h / dt / 1e3:.1f} Mrays/s  [{name}]")
+    write_ppm(args.out, surf)
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m loltracer_amd", description=__doc__.split("\n\n")[1])
     ap.add_argument("scene")
@@ -156,6 +191,8 @@ def main(argv=None) -> int:
                     help="with --lens, in the place of --focus: focus on what pixel X,Y of the frame shows (autofocus)")
     ap.add_argument("--pick", default=None, metavar="X,Y",
                     help="print object id, distance, steps and normal under pixel X,Y of the --size frame; no frame unless -o is given")
+    ap.add_argument("--panorama", default=None, metavar="WxH",
+                    help="the equirectangular image round the camera's position, WxH pixels, through one shading query; -o names the PPM")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     for name, text in (("--pick", args.pick), ("--focus-at", args.focus_at)):
@@ -173,6 +210,11 @@ def main(argv=None) -> int:
     if not sc.validate_materials():
         print("scene_validate_materials failed", file=sys.stderr)
         return 1
+    if args.panorama:
+        if args.orbit or args.lens or args.pick or args.samples != 1 or args.adaptive != -1 or args.frames != 1:
+            print("--panorama does not go with --orbit, --lens, --pick, --samples, --adaptive or --frames", file=sys.stderr)
+            return 1
+        return panorama(sc, args)
     if args.orbit:
         if (args.orbit < 1 or args.orbit > gpu.MAX_VIEWS or args.samples != 1 or args.adaptive != -1 or args.frames != 1
                 or not args.out):

@@ -906,6 +906,17 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 		else          s += "\tlol::trace_rays(exact, exact, false, Q);\n";
 		s += "}\n";
 	}
+	/* Shading queries (lol_gpu_set_shade_queries before the upload): the frames' pipeline for a list of rays or of pixels, one lane per
+	 * ray (lol_kernel_shade.h) — a Launch for the scene's half and a ShadeQuery behind it; which SDF and which shadow loop a wave may
+	 * run is decided in shade_rays.  One counting form.  Appended after everything else, for the reason above. */
+	if (carries.carries(SWITCH_SHADE)) {
+		s += "#include \"lol_kernel_shade.h\"\n";
+		s += head + "lol_shade_spec(const lol::Launch L, const lol::ShadeQuery Q) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
+		s += "\tlol::SpecSdfExact exact;\n";
+		if (any_fast) s += "\tlol::SpecSdfFast fast;\n\tlol::shade_rays<" + tg + ">(fast, exact, true, L, Q, lds);\n";
+		else          s += "\tlol::shade_rays<" + tg + ">(exact, exact, false, L, Q, lds);\n";
+		s += "}\n";
+	}
 	return s;
 }
 
@@ -1083,11 +1094,11 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	}
 	/* on disk the pipeline source (the kernel headers, embedded in this library) is part of the key: another build of the
 	 * library must not pick up this one's kernels */
-	static const char* const hdr_src[7] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT,
-	                                        LOL_KERNEL_BLEND_H_TEXT, LOL_KERNEL_BLEND_AA_H_TEXT, LOL_KERNEL_RAYS_H_TEXT };
-	static const char* const hdr_name[7] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h",
-	                                         "lol_kernel_blend.h", "lol_kernel_blend_aa.h", "lol_kernel_rays.h" };
-	constexpr int n_hdr = 7;                            /* every module is handed all of them: what it does not #include is never parsed */
+	static const char* const hdr_src[8] = { LOL_KERNEL_H_TEXT, LOL_KERNEL_AA_H_TEXT, LOL_KERNEL_BATCH_H_TEXT, LOL_KERNEL_BATCH_AA_H_TEXT,
+	                                        LOL_KERNEL_BLEND_H_TEXT, LOL_KERNEL_BLEND_AA_H_TEXT, LOL_KERNEL_RAYS_H_TEXT, LOL_KERNEL_SHADE_H_TEXT };
+	static const char* const hdr_name[8] = { "lol_kernel.h", "lol_kernel_aa.h", "lol_kernel_batch.h", "lol_kernel_batch_aa.h",
+	                                         "lol_kernel_blend.h", "lol_kernel_blend_aa.h", "lol_kernel_rays.h", "lol_kernel_shade.h" };
+	constexpr int n_hdr = 8;                            /* every module is handed all of them: what it does not #include is never parsed */
 	static const std::string all_headers = [] { std::string t; for (const char* h : hdr_src) { t += '|'; t += h; } return t; }();
 	const std::string disk_key = key + all_headers;
 	if (disk_cache_load(disk_key, code)) {
@@ -1268,6 +1279,17 @@ int lol_gpu_compile_offline_rays(const lol_program* prog, const char* arch, cons
 	/* others: lol_gpu_compile_offline_view_blends' mask of the context's other switches, 16 = lol_gpu_set_view_blend_samples */
 	return compile_offline(prog, arch, out_base, assume_fast,
 	                       { (others & 2) != 0, (others & 4) != 0, (others & 8) != 0, (others & 1) != 0, (others & 16) != 0, enable != 0 }, form, log, logcap);
+}
+
+/* ... and the module a context with lol_gpu_set_shade_queries(ctx, enable) compiles at its upload (lol_gpu_diag.h) */
+int lol_gpu_compile_offline_shade(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                  int others, int form, char* log, size_t logcap) {
+	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
+	if (others < 0 || others > 63) return LOL_GPU_ERR_ARG;
+	/* others: lol_gpu_compile_offline_rays' mask of the context's other switches, 32 = lol_gpu_set_ray_queries */
+	return compile_offline(prog, arch, out_base, assume_fast,
+	                       { (others & 2) != 0, (others & 4) != 0, (others & 8) != 0, (others & 1) != 0, (others & 16) != 0, (others & 32) != 0, enable != 0 },
+	                       form, log, logcap);
 }
 
 static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, ModuleKernels carries,

@@ -1626,6 +1626,12 @@ int lol_gpu_memcpy_d2h(lol_gpu* ctx, void* host, const void* dev, size_t bytes) 
 	LOL_HIP(ctx, hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
 	return LOL_GPU_OK;
 }
+int lol_gpu_memcpy_h2d(lol_gpu* ctx, void* dev, const void* host, size_t bytes) {
+	if (!ctx || !host || !dev) return LOL_GPU_ERR_ARG;
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	LOL_HIP(ctx, hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice));
+	return LOL_GPU_OK;
+}
 
 const char* lol_gpu_kernel_name(const lol_gpu* ctx) { return ctx ? kernel_name(ctx) : ""; }
 
@@ -1834,5 +1840,107 @@ int lol_gpu_ray_queries(const lol_gpu* ctx) { return ctx ? ctx->ray_queries : LO
 const char* lol_gpu_trace_kernel_name(const lol_gpu* ctx) {
 	if (!ctx) return "";
 	return trace_kernel(ctx) ? "lol_trace_spec" : "trace_interp";
+}
+
+/*
+ * Shading queries (include/lol_gpu.h; the kernel: lol_kernel_shade.h).  ONE launch on the caller's stream: no host wait, no copy, no
+ * scratch, and nothing of the context changes but — for a list of pixels — the cached first step of the camera's position.  The
+ * scene's half of the launch is a frame's (scene_launch_fields: tables, ambient, the skips that hold for every camera, the gamma
+ * table, the pixel format); the tile-order state, the samples and the record rings are neither read nor written.
+ */
+/* the scene kernel that answers shading queries, or nullptr: shade_interp does — the test the launch makes and lol_gpu_shade_kernel_name reports */
+static const SceneKernel* shade_kernel(const lol_gpu* ctx) {
+	const SceneKernel* k = scene_kernel(ctx);
+	return k && k->shade ? k : nullptr;
+}
+
+/* what both sources are refused for, as query_refused */
+static int shade_refused(lol_gpu* ctx, const void* list_dev, size_t n, int max_steps, const lol_gpu_shades* out) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (!list_dev && n > 0) return fail(ctx, LOL_GPU_ERR_ARG, "shading query: no list");
+	if (!out || (!out->rgb_linear && !out->rgb && !out->pixel && !out->hit_dist && !out->hit_id && !out->steps))
+		return fail(ctx, LOL_GPU_ERR_ARG, "shading query: no output");
+	if (max_steps < 0 || n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "shading query: max_steps < 0 or more than 2^32 - 1 rays");
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	return LOL_GPU_OK;
+}
+
+/* `Q`: the source filled in by the caller (rays or xy, SHADE_FROM_PIXELS); `cam`: the pixels' camera, or nullptr for a list of rays */
+static int launch_shade(lol_gpu* ctx, lol::ShadeQuery& Q, const lol_frame_camera* cam, int w, int h, size_t n, int max_steps,
+                        const lol_gpu_shades* out, void* stream) {
+	if (n == 0) return LOL_GPU_OK;
+	lol::Launch L;
+	memset(&L, 0, sizeof L);
+	L.max_steps = max_steps;
+	/* the macro-op list every camera may use (with v_div_fixup: upload_program), as launch_query: scene_launch_fields' */
+	scene_launch_fields(ctx, nullptr, L);
+	/* the host's side of what the fast SDF and the settled shadow loop rest on: the scene (shadow_settle_ok) and, where the rays are a
+	 * camera's, the camera, as lol_gpu_render_device; the side of a list's rays is the kernel's own ballot (shade_rays) */
+	const bool sane = !cam || camera_sane(*cam);
+	if (ctx->finite_scene && sane) Q.flags |= lol::SHADE_SCENE_SANE;
+	if (ctx->shadow_settle && sane) L.flags |= lol::FLAG_SHADOW_SETTLED;
+	if (cam) {
+		memcpy(&L.cam, cam, sizeof L.cam);
+		L.fw = (float)w; L.fh = (float)h;
+		L.w = w; L.h = h;
+		if (first_step(ctx, *cam, max_steps)) { L.flags |= lol::FLAG_FIRST_STEP; L.first_dist = ctx->first_dist; L.first_id = ctx->first_id; }
+	}
+	Q.n = (uint32_t)n;
+	Q.out = { out->rgb_linear, out->rgb, out->pixel, out->hit_dist, out->hit_id, out->steps };
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	finish_specialise(ctx, false);           /* a scene kernel that has finished compiling takes over here, as at a frame boundary */
+	/* dynamic LDS: the scene's tables where they are staged (lol_kernel.h, tables_in_lds); no output tile */
+	const lol_program& P = ctx->h_prog;
+	const unsigned lds = lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots) ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
+	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
+	void* args[] = { &L, &Q };
+	hipError_t e;
+	if (const SceneKernel* k = shade_kernel(ctx)) {
+		e = hipModuleLaunchKernel(k->shade, grid.x, 1, 1, lol::BLOCK, 1, 1, lds, s, args, nullptr);
+	} else {
+		const int kind = ctx->interp_sqrt_kind;
+		e = interp_dispatch(ctx, [&](auto v) {
+			constexpr int ssize = decltype(v)::ssize;
+			constexpr bool tables_global = decltype(v)::tables_global;
+			const void* fn = kind == 3 ? reinterpret_cast<const void*>(&lol::shade_interp<ssize, 3, tables_global>)
+			                           : reinterpret_cast<const void*>(&lol::shade_interp<ssize, 0, tables_global>);
+			return hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+		});
+	}
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "shading query launch", e);
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_shade_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_shades* out, void* stream) {
+	LOL_TRY(shade_refused(ctx, rays_dev, n, max_steps, out));
+	lol::ShadeQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.rays = rays_dev;
+	return launch_shade(ctx, Q, nullptr, 0, 0, n, max_steps, out, stream);
+}
+
+int lol_gpu_shade_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
+                         const uint32_t* xy_dev, size_t n, const lol_gpu_shades* out, void* stream) {
+	LOL_TRY(shade_refused(ctx, xy_dev, n, max_steps, out));
+	if (!cam || w < 1 || h < 1) return fail(ctx, LOL_GPU_ERR_ARG, "shading query: no camera or bad frame geometry");
+	lol::ShadeQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.xy = xy_dev;
+	Q.flags = lol::SHADE_FROM_PIXELS;
+	return launch_shade(ctx, Q, cam, w, h, n, max_steps, out, stream);
+}
+
+int lol_gpu_set_shade_queries(lol_gpu* ctx, int enable) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	ctx->shade_queries = enable ? 1 : 0;     /* takes effect at the next lol_gpu_upload_program */
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_shade_queries(const lol_gpu* ctx) { return ctx ? ctx->shade_queries : LOL_GPU_ERR_ARG; }
+
+const char* lol_gpu_shade_kernel_name(const lol_gpu* ctx) {
+	if (!ctx) return "";
+	return shade_kernel(ctx) ? "lol_shade_spec" : "shade_interp";
 }
 }  // extern "C"

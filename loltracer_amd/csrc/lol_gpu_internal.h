@@ -25,6 +25,7 @@
 #include "lol_kernel_blend.h"
 #include "lol_kernel_blend_aa.h"
 #include "lol_kernel_rays.h"
+#include "lol_kernel_shade.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -60,6 +61,9 @@ static_assert(sizeof(lol_frame_camera) == sizeof(lol::Cam), "lol_frame_camera la
 static_assert(sizeof(lol::Launch) % 8 == 0 && offsetof(lol::BatchArgs, B) == sizeof(lol::Launch) &&
               sizeof(lol::BatchArgs) == sizeof(lol::Launch) + sizeof(lol::BatchTail) && sizeof(lol::View) == 18 * 4,
               "kernel-argument layout of the batch kernels");
+/* ... and a shading query's is a Launch and a ShadeQuery behind it (lol_kernel_shade.h, shade_out reads the outputs there) */
+static_assert(offsetof(lol::ShadeArgs, Q) == sizeof(lol::Launch) && sizeof(lol::ShadeArgs) == sizeof(lol::Launch) + sizeof(lol::ShadeQuery),
+              "kernel-argument layout of the shading kernels");
 
 #pragma GCC visibility push(hidden)
 
@@ -136,7 +140,7 @@ struct OwnedProgram {
 enum KernelFamily { FAM_FRAME, FAM_FRAME_AA, FAM_FRAME_AA_LIST, FAM_BATCH, FAM_BATCH_AA, FAM_BATCH_AA_LIST, FAM_BATCH_LIN, FAM_BATCH_AA_LIN,
                     N_FAMILIES };
 /* the switch of the context that puts a family into the module of the next upload */
-enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA, SWITCH_BATCH_BLEND, SWITCH_BATCH_BLEND_AA, SWITCH_RAYS };
+enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA, SWITCH_BATCH_BLEND, SWITCH_BATCH_BLEND_AA, SWITCH_RAYS, SWITCH_SHADE };
 struct FamilyRow {
 	const char*  symbol;        /* in the scene module */
 	const char*  counting;      /* its twin with the per-lane step counters (modules up to LOL_SPEC_TWO_KERNELS_MAX_OPS ops), or none */
@@ -161,12 +165,15 @@ constexpr FamilyRow KERNEL_FAMILIES[N_FAMILIES] = {
  * supersampled form alone (lol_kernel_blend_aa.h) — a switch of its own, NOT implied by blend and batch_aa together; rays:
  * lol_gpu_set_ray_queries, lol_trace_spec (lol_kernel_rays.h).  That kernel is no row of KERNEL_FAMILIES: launch_family hands a family
  * a Launch, a block of lol::BLOCK threads, the tables' LDS and perhaps a counting twin, and a query has none of the four — it lives
- * beside lol_sdf_spec (SceneKernel::trace), the other kernel that is not a frame. */
+ * beside lol_sdf_spec (SceneKernel::trace), the other kernel that is not a frame; shade: lol_gpu_set_shade_queries, lol_shade_spec
+ * (lol_kernel_shade.h), beside it for the same reason (SceneKernel::shade): it takes a Launch and the tables' LDS, but a ShadeQuery
+ * and a grid over a list instead of a frame's tiles, and it has no twin. */
 struct ModuleKernels {
-	bool aa = false, batch = false, batch_aa = false, blend = false, blend_aa = false, rays = false;
+	bool aa = false, batch = false, batch_aa = false, blend = false, blend_aa = false, rays = false, shade = false;
 	bool carries(ModuleSwitch sw) const {
 		return sw == SWITCH_NONE || (sw == SWITCH_AA && aa) || (sw == SWITCH_BATCH && (batch || batch_aa)) || (sw == SWITCH_BATCH_AA && batch_aa) ||
-		       (sw == SWITCH_BATCH_BLEND && blend) || (sw == SWITCH_BATCH_BLEND_AA && blend_aa) || (sw == SWITCH_RAYS && rays);
+		       (sw == SWITCH_BATCH_BLEND && blend) || (sw == SWITCH_BATCH_BLEND_AA && blend_aa) || (sw == SWITCH_RAYS && rays) ||
+		       (sw == SWITCH_SHADE && shade);
 	}
 };
 
@@ -178,6 +185,7 @@ struct SceneKernel {
 	hipFunction_t counting[N_FAMILIES] = {};   /* the family's counting twin — or fn[] again, where the module holds no twin of it: that one counts */
 	hipFunction_t sdf = nullptr;               /* lol_sdf_spec (lol_gpu_sdf_batch) */
 	hipFunction_t trace = nullptr;             /* lol_trace_spec (ray queries), or nullptr: the module was compiled without it, trace_interp answers */
+	hipFunction_t shade = nullptr;             /* lol_shade_spec (shading queries), or nullptr: the module was compiled without it, shade_interp answers */
 	std::string   key;                         /* code_key_hex of the code object (lol_gpu_kernel_key) */
 	explicit operator bool() const { return module != nullptr; }
 	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
@@ -256,6 +264,7 @@ struct lol_gpu {
 	int          view_blends = 0;        /* lol_gpu_set_view_blends: ... and lol_render_spec_batch_lin */
 	int          view_blend_samples = 0; /* lol_gpu_set_view_blend_samples: ... and lol_render_spec_batch_aa_lin */
 	int          ray_queries = 0;        /* lol_gpu_set_ray_queries: ... and lol_trace_spec */
+	int          shade_queries = 0;      /* lol_gpu_set_shade_queries: ... and lol_shade_spec */
 	void*        d_pick = nullptr;       /* lol_gpu_pick's device memory, from the first pick on: xy [2] | dist | id | steps | normal [3] */
 	/* The view records of batches (lol_gpu_render_views, lol_gpu.hip): a ring of sets, one per batch, whatever its stream.  A batch
 	 * fills its set's pinned host copy, queues the copy to the device and the launch behind it on its stream, and records `done`;

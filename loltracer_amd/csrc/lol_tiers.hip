@@ -92,6 +92,7 @@ bool load_scene_kernel(const std::vector<char>& code, uint32_t n_ops, ModuleKern
 	if (!ok) why = "hipModuleLoadData failed";
 	ok = ok && get(k.sdf, "lol_sdf_spec");
 	if (ok && carries.carries(SWITCH_RAYS)) ok = get(k.trace, "lol_trace_spec");
+	if (ok && carries.carries(SWITCH_SHADE)) ok = get(k.shade, "lol_shade_spec");
 	for (int f = 0; ok && f < N_FAMILIES; f++) {
 		const FamilyRow& row = KERNEL_FAMILIES[f];
 		if (!carries.carries(row.needs)) continue;
@@ -220,7 +221,8 @@ void start_specialise(lol_gpu* ctx, const FastPaths& fast) {
 	} catch (...) { T.log = "out of host memory"; return; }
 	job->cull = culling_enabled(ctx->want_cull);
 	/* (what is asked for after the upload renders on the interpreter's kernel of that family) */
-	job->carries = { ctx->samples > 1, ctx->view_batches != 0, ctx->view_samples != 0, ctx->view_blends != 0, ctx->view_blend_samples != 0, ctx->ray_queries != 0 };
+	job->carries = { ctx->samples > 1, ctx->view_batches != 0, ctx->view_samples != 0, ctx->view_blends != 0, ctx->view_blend_samples != 0, ctx->ray_queries != 0,
+	                 ctx->shade_queries != 0 };
 	/* (LOL_GPU_SPEC_INLINE_MAX, a tuning switch, pins ONE form by size) */
 	const bool first_tier = !tuning_env("LOL_GPU_SPEC_INLINE_MAX") && ctx->h_prog.n_ops > LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS &&
 	                        ctx->h_prog.n_ops <= LOL_SPEC_INLINE_MAX_OPS;

@@ -76,6 +76,11 @@ class Hits(C.Structure):             # lol_gpu_hits: device pointers, each may b
     _fields_ = [("dist", C.c_void_p), ("id", C.c_void_p), ("steps", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class Shades(C.Structure):           # lol_gpu_shades: device pointers, each may be NULL (not all six)
+    _fields_ = [("rgb_linear", C.c_void_p), ("rgb", C.c_void_p), ("pixel", C.c_void_p), ("hit_dist", C.c_void_p),
+                ("hit_id", C.c_void_p), ("steps", C.c_void_p)]
+
+
 class Hit(C.Structure):              # lol_gpu_hit
     _fields_ = [("dist", C.c_float), ("id", C.c_uint32), ("steps", C.c_uint32), ("normal", C.c_float * 3)]
 
@@ -166,6 +171,8 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_free.restype = C.c_int
         lib.lol_gpu_memcpy_d2h.argtypes = [vp, vp, vp, C.c_size_t]
         lib.lol_gpu_memcpy_d2h.restype = C.c_int
+        lib.lol_gpu_memcpy_h2d.argtypes = [vp, vp, vp, C.c_size_t]
+        lib.lol_gpu_memcpy_h2d.restype = C.c_int
         lib.lol_gpu_kernel_name.argtypes = [vp]
         lib.lol_gpu_kernel_name.restype = C.c_char_p
         lib.lol_gpu_set_specialize.argtypes = [vp, C.c_int]
@@ -257,6 +264,20 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_compile_offline_rays.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                      C.c_char_p, C.c_size_t]
         lib.lol_gpu_compile_offline_rays.restype = C.c_int
+        # shading queries (include/lol_gpu.h, "Shading queries")
+        lib.lol_gpu_shade_rays.argtypes = [vp, vp, C.c_size_t, C.c_int, P(Shades), vp]
+        lib.lol_gpu_shade_rays.restype = C.c_int
+        lib.lol_gpu_shade_pixels.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, vp, C.c_size_t, P(Shades), vp]
+        lib.lol_gpu_shade_pixels.restype = C.c_int
+        lib.lol_gpu_set_shade_queries.argtypes = [vp, C.c_int]
+        lib.lol_gpu_set_shade_queries.restype = C.c_int
+        lib.lol_gpu_shade_queries.argtypes = [vp]
+        lib.lol_gpu_shade_queries.restype = C.c_int
+        lib.lol_gpu_shade_kernel_name.argtypes = [vp]
+        lib.lol_gpu_shade_kernel_name.restype = C.c_char_p
+        lib.lol_gpu_compile_offline_shade.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_char_p, C.c_size_t]
+        lib.lol_gpu_compile_offline_shade.restype = C.c_int
         lib.lol_gpu_views_refined.argtypes = [vp, P(C.c_int64)]
         lib.lol_gpu_views_refined.restype = C.c_int
         lib.lol_gpu_interp_variant.argtypes = [vp, P(C.c_int), P(C.c_int)]
@@ -379,6 +400,7 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_render_views_blend", "lol_gpu_set_view_blends", "lol_gpu_view_blends",
     "lol_gpu_render_views_blend_samples", "lol_gpu_set_view_blend_samples", "lol_gpu_view_blend_samples",
     "lol_gpu_trace_rays", "lol_gpu_trace_pixels", "lol_gpu_pick", "lol_gpu_set_ray_queries", "lol_gpu_ray_queries",
+    "lol_gpu_shade_rays", "lol_gpu_shade_pixels", "lol_gpu_set_shade_queries", "lol_gpu_shade_queries", "lol_gpu_memcpy_h2d",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
@@ -389,6 +411,7 @@ DIAG_SYMBOLS = [                                                        # includ
     "lol_gpu_views_refined", "lol_gpu_interp_variant", "lol_gpu_compile_offline_view_blends", "lol_gpu_view_blend_kernel_name",
     "lol_gpu_compile_offline_view_blend_samples", "lol_gpu_view_blend_samples_kernel_name",
     "lol_gpu_trace_kernel_name", "lol_gpu_compile_offline_rays", "lol_gpu_code_key",
+    "lol_gpu_shade_kernel_name", "lol_gpu_compile_offline_shade",
 ]
 
 
@@ -490,6 +513,22 @@ def compile_offline_rays(program: S.Program, out_base: str, enable: bool = True,
               int(bool(view_blend_samples)) << 4)
     st = gpu_lib().lol_gpu_compile_offline_rays(C.byref(program), arch.encode(), os.fsencode(out_base),
                                                 int(assume_fast), int(bool(enable)), others, int(form), log, len(log))
+    if st != LOL_GPU_OK:
+        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
+    return log.value.decode(errors="replace")
+
+
+def compile_offline_shade(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
+                          assume_fast: bool = False, view_blends: bool = False, samples: bool = False, view_batches: bool = False,
+                          view_samples: bool = False, view_blend_samples: bool = False, ray_queries: bool = False) -> str:
+    """compile_offline for a context with set_shade_queries(enable) before its upload: adds lol_shade_spec, last.  form as for
+    compile_offline_views.  view_blends / samples / view_batches / view_samples / view_blend_samples / ray_queries: the context's
+    other switches set beside it.  Needs no device."""
+    log = C.create_string_buffer(1 << 16)
+    others = (int(bool(view_blends)) | int(bool(samples)) << 1 | int(bool(view_batches)) << 2 | int(bool(view_samples)) << 3 |
+              int(bool(view_blend_samples)) << 4 | int(bool(ray_queries)) << 5)
+    st = gpu_lib().lol_gpu_compile_offline_shade(C.byref(program), arch.encode(), os.fsencode(out_base),
+                                                 int(assume_fast), int(bool(enable)), others, int(form), log, len(log))
     if st != LOL_GPU_OK:
         raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
     return log.value.decode(errors="replace")
@@ -768,6 +807,10 @@ class Renderer:
         """lol_gpu_memcpy_d2h: waits for the renderer's own streams, then copies device memory to the host."""
         self._check(self._lib.lol_gpu_memcpy_d2h(self._ctx, C.c_void_p(host_ptr), C.c_void_p(dev_ptr), nbytes))
 
+    def memcpy_h2d(self, dev_ptr: int, host_ptr: int, nbytes: int):
+        """lol_gpu_memcpy_h2d: copies host memory to the device and waits for the copy (the list of a query, for hosts without torch)."""
+        self._check(self._lib.lol_gpu_memcpy_h2d(self._ctx, C.c_void_p(dev_ptr), C.c_void_p(host_ptr), nbytes))
+
     def set_frames_in_flight(self, n: int):
         """Frames launched with stream=None go to n streams of the context in turn (1 = sequential, the default; <= 4):
         consecutive frames overlap.  Give frames that may be in flight together destinations of their own."""
@@ -884,6 +927,38 @@ class Renderer:
         hit = Hit()
         self._check(self._lib.lol_gpu_pick(self._ctx, C.byref(fc), w, h, max_steps, int(x), int(y), C.byref(hit)))
         return {"id": int(hit.id), "dist": float(hit.dist), "steps": int(hit.steps), "normal": tuple(float(v) for v in hit.normal)}
+
+    # ---- shading queries (include/lol_gpu.h, "Shading queries")
+    def set_shade_queries(self, enable: bool):
+        """Before prepare(): the scene's own module also carries the shading-query kernel (lol_shade_spec); without it — and until
+        that module is ready — shading queries run on the interpreter's shade_interp.  Same answers either way."""
+        self._check(self._lib.lol_gpu_set_shade_queries(self._ctx, 1 if enable else 0))
+
+    @property
+    def shade_queries(self) -> bool:
+        return bool(self._lib.lol_gpu_shade_queries(self._ctx))
+
+    def shade_kernel_name(self) -> str:
+        """the kernel the next shade_rays_into / shade_pixels_into launches"""
+        return self._lib.lol_gpu_shade_kernel_name(self._ctx).decode()
+
+    def shade_rays_into(self, rays_ptr: int, n: int, max_steps: int = 256, rgb_linear_ptr: int = 0, rgb_ptr: int = 0,
+                        pixel_ptr: int = 0, dist_ptr: int = 0, id_ptr: int = 0, steps_ptr: int = 0, stream: int | None = None):
+        """Asynchronously shade n rays (device memory, n x {ox, oy, oz, dx, dy, dz} floats): ray i is the reference's pixel
+        pipeline with the eye at the ray's origin.  rgb_linear / rgb: 3 n floats (before / after gamma), pixel (the context's
+        pixel format) / dist / id / steps: n elements each; 0 = not wanted (not all six)."""
+        out = Shades(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None, dist_ptr or None, id_ptr or None, steps_ptr or None)
+        self._check(self._lib.lol_gpu_shade_rays(self._ctx, C.c_void_p(rays_ptr), n, max_steps, C.byref(out), _stream_arg(stream)))
+
+    def shade_pixels_into(self, xy_ptr: int, n: int, w: int, h: int, max_steps: int = 256, rgb_linear_ptr: int = 0, rgb_ptr: int = 0,
+                          pixel_ptr: int = 0, dist_ptr: int = 0, id_ptr: int = 0, steps_ptr: int = 0, stream: int | None = None,
+                          camera: S.Camera | None = None, frame_camera: S.FrameCamera | None = None):
+        """Asynchronously shade the primary rays of n pixels (device memory, n x {x, y} uint32) of the w x h frame under the
+        camera: what a frame and its lol_gpu_debug planes hold for those pixels, and the linear colour."""
+        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        out = Shades(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None, dist_ptr or None, id_ptr or None, steps_ptr or None)
+        self._check(self._lib.lol_gpu_shade_pixels(self._ctx, C.byref(fc), w, h, max_steps, C.c_void_p(xy_ptr), n, C.byref(out),
+                                                   _stream_arg(stream)))
 
     def set_cull(self, enable: bool):
         """Exact bounding-sphere culling of top-level objects in the specialised kernel; takes effect at the next prepare()."""

@@ -340,3 +340,30 @@ def lens_cameras(camera: Camera, focus_distance: float, aperture_radius: float, 
             c.direction = V3(*[v / lk for v in look])
         out.append(c)
     return out
+
+
+def panorama_rays(camera: Camera, w: int, h: int):
+    """The rays of a w x h equirectangular panorama from the camera's position, for Renderer.shade_rays_into: float32 [h w, 6],
+    row-major, each {ox, oy, oz, dx, dy, dz}.
+
+    Pixel (x, y) looks along longitude ((x + .5) / w * 2 - 1) pi and latitude (.5 - (y + .5) / h) pi:
+    cos(lat) sin(lon) right + sin(lat) up + cos(lat) cos(lon) dir, in the basis lol_frame_camera_init gives the camera (dir
+    normalised here) — the image's centre looks where the camera does, its left and right edges meet behind it, its top row looks
+    up.  Computed in doubles, normalised, then rounded to float: the rays are data, a shading query's contract starts at their bits.
+    The field of view plays no part."""
+    import numpy as np
+    if w < 1 or h < 1:
+        raise ValueError("panorama_rays: w and h must be at least 1")
+    fc = FrameCamera()
+    host_lib().lol_frame_camera_init(C.byref(fc), C.byref(camera), w, h)
+    d, right, up = (np.array(v.tuple(), np.float64) for v in (fc.dir, fc.right, fc.up))
+    d, right, up = (v / (np.linalg.norm(v) or 1.0) for v in (d, right, up))
+    lon = ((np.arange(w, dtype=np.float64) + .5) / w * 2. - 1.) * math.pi
+    lat = (.5 - (np.arange(h, dtype=np.float64) + .5) / h) * math.pi
+    lon, lat = np.meshgrid(lon, lat)                                # [h, w]
+    rd = ((np.cos(lat) * np.sin(lon))[..., None] * right + np.sin(lat)[..., None] * up + (np.cos(lat) * np.cos(lon))[..., None] * d)
+    rd /= np.linalg.norm(rd, axis=-1, keepdims=True)
+    rays = np.empty((h * w, 6), np.float32)
+    rays[:, :3] = np.array(camera.point.tuple(), np.float32)
+    rays[:, 3:] = rd.reshape(-1, 3).astype(np.float32)
+    return rays

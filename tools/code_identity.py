@@ -8,7 +8,8 @@ loltracer_amd/csrc) and writes what was compared, and the result, as JSON:
                      switch on its own plus the query kernel beside all the others, with and without assume_fast: the contents
                      of .text, .rodata and .note of the hipRTC code object — what lol_gpu_kernel_key covers — must be equal.
   ahead of time      the six .hip units compiled device-only with the Makefile's flags in both trees: every kernel's bytes and
-                     its .kd descriptor must be equal, by name.
+                     its .kd descriptor (but the code's offset from it, a position in the file) must be equal, by name; kernels only
+                     this checkout has are listed as `added`.
 
     python tools/code_identity.py --parent ../parent --work /tmp/ident --out profiles/r14_code_identity.json
 
@@ -60,7 +61,10 @@ def kernels(data):
         if 0 < shndx < shnum:
             sec = raw[shndx]
             syms[names[name:names.index(b"\0", name)].decode()] = data[sec[4] + value - sec[3]:sec[4] + value - sec[3] + size]
-    return {n: (syms[n], syms[n + ".kd"]) for n in syms if n + ".kd" in syms}
+    # kernel_code_entry_byte_offset (bytes 16 ... 23 of a descriptor) is where the code lies relative to the descriptor: a position in
+    # the file, which moves for every kernel of a unit when the unit gains one.  Everything else a descriptor holds is compared.
+    entry = lambda kd: kd[:16] + bytes(8) + kd[24:]      # noqa: E731
+    return {n: (syms[n], entry(syms[n + ".kd"])) for n in syms if n + ".kd" in syms}
 
 
 def sha(b):
@@ -147,8 +151,8 @@ def main():
         x, y = read(old, f), read(new, f)
         if f.endswith(".aot.co"):
             kx, ky = kernels(x), kernels(y)
-            bad = sorted(n for n in set(kx) | set(ky) if kx.get(n) != ky.get(n))
-            units.append({"unit": f[:-len(".aot.co")] + ".hip", "kernels": len(ky),
+            bad = sorted(n for n in kx if kx[n] != ky.get(n))               # every kernel the other build has; new ones are listed, not compared
+            units.append({"unit": f[:-len(".aot.co")] + ".hip", "kernels": len(ky), "added": sorted(set(ky) - set(kx)),
                           "sha256_16_of_all": sha(b"".join(n.encode() + b"\0" + ky[n][0] + ky[n][1] for n in sorted(ky))), "differing": bad})
             differing += [f + ": " + n for n in bad]
         else:
