@@ -228,6 +228,54 @@ CarryConsts carry_constants(const std::vector<CullTest>& tests) {
 	return c;
 }
 
+/* The object's own last value as a carried bound (fast SDF, outermost run of ONE object; emit_sdf).  An object of spheres and round
+ * boxes under smooth unions with k > 0 is 1-Lipschitz in real arithmetic: its primitives are, and sminf(a, b) = b + (a - b) h -
+ * k h (1 - h) has the gradient h grad a + (1 - h) grad b wherever h = .5 + .5 (b - a) / k is not clamped (dS/dh = (a - b) -
+ * k (1 - 2h) = 0 there) and is a or b where it is.  So with D the object's real value, (C, R) its bounding sphere (analyse_roots:
+ * D(p) >= |p - C| - R), x = D(p(t)), y = D(p(T)) and the point roundings of carry_constants (|p| <= |p - C| + |C| <= D + R + |C|):
+ *   x (1 + e) >= y (1 - e) - rho ((1 + e) t - (1 - e) T) - 2 e (R + |C|) - 2 sqrt(3) eta                 for t >= T >= 0.
+ * The binary32 value of the plain SDF differs from D by at most et (|p - C| + Rm) <= et (D + 2 Rm), et = 40 * 2^-24 * levels
+ * (make_test: a primitive 2^-24 * 4M, a smooth minimum 2^-24 (4M + 8.5k) on top of its operands' error, k <= 4R), where M bounds the
+ * magnitude of every intermediate value: a leaf's is at most |p - c_i| + m_i <= |p - C| + |C - c_i| + m_i with m_i = |r_i| for a
+ * sphere and |b_i| + r_i for a round box.  For radii >= 0 that is within |p - C| + R, but a sphere of NEGATIVE radius is bounded
+ * with radius 0 (analyse_roots) while its value is |p - c_i| + |r_i|: so Rm = max(R, max_i (|C - c_i| + m_i)) stands for R in every
+ * term below (R <= Rm keeps the point roundings' |p| <= D + R + |C| true as well).  The fast SDF's value V is the plain value or NaN,
+ * or the wave shades again (lol_kernel.h, unproven).  Hence y (1 + et) >= V - 2 et Rm, and the plain value at t is >=
+ * x (1 - et) - 2 et Rm.  It is > |best| — the object loses eval_dist's minimum and eval's strict '<' and its tie rule alike, for
+ * either sign of best — where, with kap = (1 - et) / (1 + e),
+ *   g + cT T > |best| + ct t,   g = a V - E,   a = kap (1 - e) / (1 + et),   cT = rho (1 - e) kap,   ct = rho (1 - et),
+ *   E = kap (2 et Rm (1 - e) / (1 + et) + 2 e (Rm + |C|) + 2 sqrt(3) eta) + 2 et Rm.
+ * After every evaluation of the object at rt = T on a ray that may carry, the kernel folds
+ *   lb' = G - |G| 2^-20,   G = fma(T, ctt, fma(|V|, -dl, V) - Ef)
+ * into the register of the cluster bound, lb = max(lb', lb) (a NaN V leaves lb: maxf_), with dl >= 1 - a + 4e (V (1 - dl) for
+ * V >= 0, V (1 + dl) for V < 0: below a V in both signs, the two roundings of the inner expression included), Ef >= E (1 + 4e) +
+ * 2^-100 and ctt = cT (1 - 2^-20); the 2^-20 in lb' covers the roundings of G and of lb' itself.  The check at a later t is the
+ * cluster bound's own, fl(fma(t, ctc, |best|)) < lb, with ctc the larger of the two bounds' ct (1 + 2^-20).  Constants are rounded
+ * towards the safe side; tests/test_cull_value_carry_bound.py re-derives them in rational arithmetic from the scene's tree. */
+struct ValueCarryConsts { float dl = 0.f, ef = 0.f, ctt = 0.f, ctc = 0.f; };
+ValueCarryConsts value_carry_constants(const lol_program& P, const RootBound& r) {
+	const double e = 0x1p-24, rho = 1.0 + 0x1p-20, et = 40.0 * 0x1p-24 * (double)r.levels;
+	const double cn = sqrt(r.c[0] * r.c[0] + r.c[1] * r.c[1] + r.c[2] * r.c[2]) * (1.0 + 0x1p-40);
+	double R = r.r;                                                       /* Rm: the bound's radius, or what a leaf's magnitude asks for */
+	for (uint32_t i = r.first; i < r.top; i++) {
+		const lol_op& o = P.ops[i];
+		if (o.op != LOL_OP_SPHERE && o.op != LOL_OP_RBOX) continue;
+		const double dx = o.f[0] - r.c[0], dy = o.f[1] - r.c[1], dz = o.f[2] - r.c[2];
+		const double m = o.op == LOL_OP_SPHERE ? fabs((double)o.f[3])
+		                                       : sqrt((double)o.f[3] * o.f[3] + (double)o.f[4] * o.f[4] + (double)o.f[5] * o.f[5]) + fabs((double)o.f[6]);
+		R = fmax(R, (sqrt(dx * dx + dy * dy + dz * dz) + m) * (1.0 + 0x1p-40));
+	}
+	R *= 1.0 + 0x1p-40;
+	const double kap = (1.0 - et) / (1.0 + e), a = kap * (1.0 - e) / (1.0 + et);
+	const double E = kap * (2.0 * et * R * (1.0 - e) / (1.0 + et) + 2.0 * e * (R + cn) + 0x1p-73) + 2.0 * et * R;
+	ValueCarryConsts c;
+	c.dl = f_up(1.0 - a + 4.0 * e);
+	c.ef = f_up(E * (1.0 + 4.0 * e) + 0x1p-100);
+	c.ctt = f_down(rho * (1.0 - e) * kap * (1.0 - 0x1p-20));
+	c.ctc = f_up(rho * (1.0 - et) * (1.0 + 0x1p-20));
+	return c;
+}
+
 std::vector<CullTest> cluster_tests(const RootBound& r) {
 	std::vector<CullTest> t;
 	for (const Sphere& c : r.clusters) t.push_back(make_test(c));
@@ -467,6 +515,14 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 	bool carry = fast && !out_of_line && !plan.intervals.empty();
 	if (const char* e = tuning_env("LOL_GPU_CULL_CARRY")) carry = carry && atoi(e) != 0;
 	else carry = carry && !plan.intervals[0].both.empty();
+	/* ... and the object's own last value folded into the same lb (value_carry_constants), where the carry is on and the outermost run
+	 * is ONE object: a run of several would need every object's bound per step, which is what cost scene.lol's group 2.7 % with the
+	 * cluster carry.  The carried check then comes BEFORE the cool-down counter: the evaluations taken under cool-down refresh lb, and
+	 * the first step at which the object has stopped winning is skipped without waiting for the counter to run out.
+	 * LOL_GPU_CULL_VALUE_CARRY=0 / 1: off / on (still only for a single object behind a carried bound). */
+	bool vcarry = carry && plan.intervals[0].end == plan.intervals[0].begin + 1 && roots[plan.order[plan.intervals[0].begin]].bounded;
+	if (const char* e = tuning_env("LOL_GPU_CULL_VALUE_CARRY")) vcarry = vcarry && atoi(e) != 0;
+	const ValueCarryConsts vc = vcarry ? value_carry_constants(P, roots[plan.order[plan.intervals[0].begin]]) : ValueCarryConsts();
 	std::string carry_decl;
 	if (carry)
 		carry_decl = "\tfloat lb = -__builtin_inff(), rt = 0.f;\n\tbool carry = false;\n"
@@ -543,9 +599,12 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 			 * wave on a ray that may carry, sets lb anew (one v_sqrt per sphere).  A failed full test leaves lb as it is: still a
 			 * bound, only an older one. */
 			const CarryConsts cc = carry_constants(tests);
-			snprintf(line, sizeof line, "\t\t{ bool need%d = true;\n\t\t  if (cool[0] == 0u) {\n"
+			const float ctc = vcarry && vc.ctc > cc.ctc ? vc.ctc : cc.ctc;      /* one left-hand side for both bounds: the more conservative */
+			snprintf(line, sizeof line, vcarry ? "\t\t{ bool need%d = true;\n\t\t  {\n"
+			         "\t\t  if (vote(!(__builtin_fmaf(rt, %s, __builtin_fabsf(best)) < lb)) == 0) need%d = false; else if (cool[0] == 0u) {\n"
+			         : "\t\t{ bool need%d = true;\n\t\t  if (cool[0] == 0u) {\n"
 			         "\t\t  if (vote(!(__builtin_fmaf(rt, %s, __builtin_fabsf(best)) < lb)) == 0) need%d = false; else {\n",
-			         k0, fbits(cc.ctc).c_str(), k0);
+			         k0, fbits(ctc).c_str(), k0);
 			s += line;
 			s += decl;
 			snprintf(line, sizeof line, "\t\t  need%d = ((", k0);
@@ -559,7 +618,9 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 				         k0 + (int)j, fbits(cc.a[j]).c_str(), fbits(cc.b[j]).c_str());
 				s += line;
 			}
-			snprintf(line, sizeof line, "\t\t    const float lg = __builtin_fmaf(rt, %s, lm);\n\t\t    lb = __builtin_fmaf(__builtin_fabsf(lg), -0x1p-20f, lg);\n"
+			snprintf(line, sizeof line, vcarry ? "\t\t    const float lg = __builtin_fmaf(rt, %s, lm);\n\t\t    lb = maxf_(__builtin_fmaf(__builtin_fabsf(lg), -0x1p-20f, lg), lb);\n"
+			         "\t\t  }\n\t\t  } else cool[0]--; }\n\t\t  if (need%d) {\n"
+			         : "\t\t    const float lg = __builtin_fmaf(rt, %s, lm);\n\t\t    lb = __builtin_fmaf(__builtin_fabsf(lg), -0x1p-20f, lg);\n"
 			         "\t\t  }\n\t\t  } } else cool[0]--;\n\t\t  if (need%d) {\n", fbits(cc.ctt).c_str(), k0);
 			s += line;
 		} else if (with_cooldown) {
@@ -721,6 +782,12 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 			snprintf(line, sizeof line, "\t\tif (t%d < best) { best = t%d; best_id = %uu; }\n", d, d, R.id);
 		s += line;
 		if (R.id > max_id_seen) max_id_seen = R.id;
+		if (vcarry && oi == plan.intervals[0].begin) {      /* the value just computed bounds the object further along the ray (value_carry_constants) */
+			snprintf(line, sizeof line, "\t\tif (carry) {\n\t\t  const float vg = __builtin_fmaf(rt, %s, __builtin_fmaf(__builtin_fabsf(t%d), -%s, t%d) - %s);\n"
+			         "\t\t  lb = maxf_(__builtin_fmaf(__builtin_fabsf(vg), -0x1p-20f, vg), lb);\n\t\t}\n",
+			         fbits(vc.ctt).c_str(), d, fbits(vc.dl).c_str(), d, fbits(vc.ef).c_str());
+			s += line;
+		}
 		for (uint32_t k = 0; k < runs_ending[oi + 1]; k++) s += "\t\t} }\n";               /* every run that ends here */
 	}
 	if (!out_of_line) s += "\t}\n";
