@@ -70,51 +70,53 @@ int         lol_gpu_powf_batch(lol_gpu* ctx, const float* x_dev, const float* y_
  */
 int         lol_gpu_sdf_batch(lol_gpu* ctx, const float* pts_dev, float* dist_dev, uint32_t* id_dev, size_t n, void* stream);
 /*
- * lol_gpu_compile_offline (lol_gpu.h) for a context that asked for supersampling (lol_gpu_set_samples) before its upload:
- * samples = 1 writes exactly what lol_gpu_compile_offline writes; 2 and 4 the same source with the kernels lol_render_spec_aa
- * and lol_render_spec_aa_list appended, and its code object — so that the supersampling kernels' ISA can be inspected without a
- * device.  LOL_GPU_ERR_ARG for any other number of samples.
+ * The scene module of a context whose switches before its upload were `switches`, compiled without a device: writes
+ * `<out_base>.hip` (the generated source) and `<out_base>.co` (its code object for `arch`), so that every kernel's ISA can be
+ * inspected.  `switches` is a mask, one bit per call that puts kernels into a module, in the order the scene compiler appends them:
+ *     1  lol_gpu_set_samples > 1           lol_render_spec_aa, lol_render_spec_aa_list
+ *     2  lol_gpu_set_view_batches          lol_render_spec_batch (and, up to 256 ops, lol_render_spec_batch_steps)
+ *     4  lol_gpu_set_view_samples          lol_render_spec_batch_aa, lol_render_spec_batch_aa_list — and what 2 adds, which it brings
+ *     8  lol_gpu_set_view_blends           lol_render_spec_batch_lin
+ *    16  lol_gpu_set_view_blend_samples    lol_render_spec_batch_aa_lin
+ *    32  lol_gpu_set_ray_queries           lol_trace_spec
+ *    64  lol_gpu_set_shade_queries         lol_shade_spec
+ * 0 writes exactly what lol_gpu_compile_offline (lol_gpu.h) writes, and a module without a switch is the module that switch never
+ * existed for.  form: 0 = the form a scene of this size ends up with, 1 = the SDF as one out-of-line function, 2 = inlined — the two
+ * kernels a scene of 257 ... 1024 ops gets one after the other.  assume_fast, log: as for lol_gpu_compile_offline.
+ * LOL_GPU_ERR_ARG for a mask outside 0 ... 127, any other form, or no program.
  */
+int         lol_gpu_compile_offline_module(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                           unsigned switches, int form, char* log, size_t logcap);
+/* The seven entry points from before that one: each is lol_gpu_compile_offline_module for one mask, with a refusal of its own.
+ * ... the module with mask (samples > 1 ? 1 : 0), form 0.  LOL_GPU_ERR_ARG for samples other than 1, 2 and 4. */
 int         lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                             int samples, char* log, size_t logcap);
-/*
- * ... and for a context that asked for batches of views (lol_gpu_set_view_batches) before its upload: enable = 0 writes exactly
- * what lol_gpu_compile_offline writes; otherwise the same source with lol_render_spec_batch (and, up to 256 ops,
- * lol_render_spec_batch_steps) appended, and its code object.  form: 0 = the form a scene of this size ends up with, 1 = the SDF as
- * one out-of-line function, 2 = inlined — the two kernels a scene of 257 ... 1024 ops gets one after the other.  LOL_GPU_ERR_ARG
- * for any other form.
- */
+/* ... the module with mask (enable ? 2 : 0) */
 int         lol_gpu_compile_offline_views(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                           int enable, int form, char* log, size_t logcap);
-/*
- * ... and for a context that asked for supersampled batches (lol_gpu_set_view_samples) before its upload: enable = 0 writes exactly
- * what lol_gpu_compile_offline writes; otherwise what lol_gpu_compile_offline_views writes with lol_render_spec_batch_aa and
- * lol_render_spec_batch_aa_list appended, and its code object.  form as above.
- */
+/* ... the module with mask (enable ? 4 : 0) */
 int         lol_gpu_compile_offline_view_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                                  int enable, int form, char* log, size_t logcap);
-/*
- * ... and for a context that asked for blends of views (lol_gpu_set_view_blends) before its upload: enable = 0 writes exactly what
- * lol_gpu_compile_offline writes; 1 the same source with lol_render_spec_batch_lin appended, and its code object.  form as above.
- * `enable` is a mask, so that the module of a context with several switches set can be inspected too: 1 = lol_gpu_set_view_blends,
- * 2 = lol_gpu_set_samples > 1, 4 = lol_gpu_set_view_batches, 8 = lol_gpu_set_view_samples — the kernels of each, in the order the
- * scene compiler appends them, the linear kernel last.  LOL_GPU_ERR_ARG outside 0 ... 15.  Needs no device.
- */
+/* ... the module with the mask that `enable` is in an order of its own: 1 = lol_gpu_set_view_blends, 2 = lol_gpu_set_samples > 1,
+ * 4 = lol_gpu_set_view_batches, 8 = lol_gpu_set_view_samples.  LOL_GPU_ERR_ARG outside 0 ... 15. */
 int         lol_gpu_compile_offline_view_blends(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
                                                 int enable, int form, char* log, size_t logcap);
+/* ... the module with mask (enable ? 16 : 0) and the switches of `others`, in lol_gpu_compile_offline_view_blends' order.
+ * LOL_GPU_ERR_ARG for others outside 0 ... 15. */
+int         lol_gpu_compile_offline_view_blend_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                                       int enable, int others, int form, char* log, size_t logcap);
+/* ... the module with mask (enable ? 32 : 0) and the switches of `others`, in that order with 16 = lol_gpu_set_view_blend_samples
+ * added.  LOL_GPU_ERR_ARG for others outside 0 ... 31. */
+int         lol_gpu_compile_offline_rays(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                         int enable, int others, int form, char* log, size_t logcap);
+/* ... the module with mask (enable ? 64 : 0) and the switches of `others`, in that order with 32 = lol_gpu_set_ray_queries added.
+ * LOL_GPU_ERR_ARG for others outside 0 ... 63. */
+int         lol_gpu_compile_offline_shade(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                                          int enable, int others, int form, char* log, size_t logcap);
 /* The kernel the first pass of the NEXT lol_gpu_render_views_blend(..., cams_per_view, ...) of this context launches, decided by
  * the test the launch itself makes: "lol_render_spec_batch_lin" / "render_interp_batch_lin"; lol_gpu_render_views' for
  * cams_per_view = 1.  (The second pass is always the library's own blend_resolve.) */
 const char* lol_gpu_view_blend_kernel_name(const lol_gpu* ctx, int cams_per_view);
-/*
- * ... and for a context that asked for supersampled blends (lol_gpu_set_view_blend_samples) before its upload: enable = 0 writes
- * exactly what lol_gpu_compile_offline_view_blends(..., others, ...) writes; 1 the same source with lol_render_spec_batch_aa_lin
- * appended last, and its code object.  `others`: that function's mask of the context's other switches (1 = lol_gpu_set_view_blends,
- * 2 = lol_gpu_set_samples > 1, 4 = lol_gpu_set_view_batches, 8 = lol_gpu_set_view_samples; LOL_GPU_ERR_ARG outside 0 ... 15).  form
- * as above.  Needs no device.
- */
-int         lol_gpu_compile_offline_view_blend_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
-                                                       int enable, int others, int form, char* log, size_t logcap);
 /* The kernel the first pass of the NEXT lol_gpu_render_views_blend_samples(..., cams_per_view, ..., samples, ...) of this context
  * launches, decided by the test the launch itself makes: "lol_render_spec_batch_aa_lin" / "render_interp_batch_aa_lin";
  * lol_gpu_view_blend_kernel_name's for samples <= 1, lol_gpu_view_samples_kernel_name's (contrast -1) for cams_per_view <= 1. */
@@ -143,25 +145,9 @@ int         lol_gpu_adaptive_pass_ms(lol_gpu* ctx, float ms[3]);
 /* The kernel the NEXT ray query of this context (lol_gpu_trace_rays, lol_gpu_trace_pixels, lol_gpu_pick) launches, decided by the
  * test the launch itself makes: "lol_trace_spec" / "trace_interp"; "" for a NULL context. */
 const char* lol_gpu_trace_kernel_name(const lol_gpu* ctx);
-/*
- * ... and the module of a context that asked for ray queries (lol_gpu_set_ray_queries) before its upload: enable = 0 writes exactly
- * what the module with `others` alone is; 1 the same source with `#include "lol_kernel_rays.h"` and lol_trace_spec appended last, and
- * its code object.  `others`: lol_gpu_compile_offline_view_blend_samples' mask of the context's other switches with
- * 16 = lol_gpu_set_view_blend_samples added (LOL_GPU_ERR_ARG outside 0 ... 31).  form as above.  Needs no device.
- */
-int         lol_gpu_compile_offline_rays(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
-                                         int enable, int others, int form, char* log, size_t logcap);
 /* The kernel the NEXT shading query of this context (lol_gpu_shade_rays, lol_gpu_shade_pixels) launches, decided by the test the
  * launch itself makes: "lol_shade_spec" / "shade_interp"; "" for a NULL context. */
 const char* lol_gpu_shade_kernel_name(const lol_gpu* ctx);
-/*
- * ... and the module of a context that asked for shading queries (lol_gpu_set_shade_queries) before its upload: enable = 0 writes
- * exactly what the module with `others` alone is; 1 the same source with `#include "lol_kernel_shade.h"` and lol_shade_spec appended
- * last, and its code object.  `others`: lol_gpu_compile_offline_rays' mask of the context's other switches with
- * 32 = lol_gpu_set_ray_queries added (LOL_GPU_ERR_ARG outside 0 ... 63).  form as above.  Needs no device.
- */
-int         lol_gpu_compile_offline_shade(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
-                                          int enable, int others, int form, char* log, size_t logcap);
 /*
  * lol_gpu_kernel_key's function of a code object (lol_gpu.h says what it covers), for n bytes of one in host memory — a .co of
  * lol_gpu_compile_offline* — as 16 hex digits and a NUL in out.  A buffer that is no ELF64 little-endian file, or whose section

@@ -819,7 +819,9 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	const bool ool = spec_out_of_line(P, form);
 	const std::vector<RootBound> roots = analyse_roots(P);
 	const CullPlan plan = plan_culling(roots, cull);
-	s += "#include \"lol_kernel.h\"\n";
+	/* the header of a switch's block (MODULE_SWITCHES) */
+	auto include = [](ModuleSwitch sw) { return std::string("#include \"") + MODULE_SWITCHES[sw].header + "\"\n"; };
+	s += include(SWITCH_NONE);
 	s += "namespace lol {\n";
 	/* Register budget.  The SDF of one object is a long dependent chain (every smooth min waits for the one below
 	 * it) fed by independent primitives, and the kernel is compiled with the max-ILP scheduling strategy
@@ -892,7 +894,7 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * — and the same code object and kernel_key — as before supersampling existed.  No step counters: hit_dist, hit_id and steps
 	 * have no single value for a pixel of several samples (lol_gpu_render_device refuses them). */
 	if (carries.carries(SWITCH_AA)) {
-		s += "#include \"lol_kernel_aa.h\"\n";
+		s += include(SWITCH_AA);
 		s += head + K[FAM_FRAME_AA].symbol + "(const lol::Launch L) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tconst lol::Launch S = lol::sample_launch(L);\n";
 		s += shade("\t", "L", "S", "false", "");
@@ -911,7 +913,7 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * (lol_kernel_batch.h), stored at that view's address.  Appended after everything else, for the reason above.  With and without
 	 * the step counters like the frame kernel: a batch with lol_gpu_debug::steps runs the counting twin. */
 	if (carries.carries(SWITCH_BATCH)) {
-		s += "#include \"lol_kernel_batch.h\"\n";
+		s += include(SWITCH_BATCH);
 		s += "template <bool COUNT> __device__ __forceinline__ void lol_spec_batch_body(const lol::Launch& L, const lol::BatchTail& B, lol::u32* lds) {\n" + stage;
 		s += "\tconst lol::Launch S = lol::view_launch(L, B.views);\n";
 		s += shade("\t", "S", "S", "COUNT", "const lol::Pixel P = ");
@@ -926,7 +928,7 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * store (lol_kernel_batch_aa.h), and the same for the per-view lists of an adaptive batch.  Appended after everything else,
 	 * for the reason above.  No step counters. */
 	if (carries.carries(SWITCH_BATCH_AA)) {
-		s += "#include \"lol_kernel_batch_aa.h\"\n";
+		s += include(SWITCH_BATCH_AA);
 		s += head + K[FAM_BATCH_AA].symbol + "(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tconst lol::Launch S = lol::sample_launch(lol::view_launch(L, B.views));\n";
 		s += shade("\t", "S", "S", "false", "");
@@ -944,7 +946,7 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * record, the clamped LINEAR colour stored into the blend's scratch instead of a packed pixel (lol_kernel_blend.h).  Appended
 	 * after everything else, for the reason above.  No step counters. */
 	if (carries.carries(SWITCH_BATCH_BLEND)) {
-		s += "#include \"lol_kernel_blend.h\"\n";
+		s += include(SWITCH_BATCH_BLEND);
 		s += head + K[FAM_BATCH_LIN].symbol + "(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tconst lol::Launch S = lol::view_launch(L, B.views);\n";
 		s += shade("\t", "S", "S", "false", "");
@@ -955,7 +957,7 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * pipeline on the sample grid of the block's record, every pixel's samples reduced to their LINEAR mean and that stored into
 	 * the blend's scratch (lol_kernel_blend_aa.h).  Appended after everything else, for the reason above.  No step counters. */
 	if (carries.carries(SWITCH_BATCH_BLEND_AA)) {
-		s += "#include \"lol_kernel_blend_aa.h\"\n";
+		s += include(SWITCH_BATCH_BLEND_AA);
 		s += head + K[FAM_BATCH_AA_LIN].symbol + "(const lol::Launch L, const lol::BatchTail B) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tconst lol::Launch S = lol::sample_launch(lol::view_launch(L, B.views));\n";
 		s += shade("\t", "S", "S", "false", "");
@@ -966,7 +968,7 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * lane per ray, one wave per block (lol_kernel_rays.h) — no Launch, no LDS, no tables.  Appended after everything else, for the
 	 * reason above.  The name does not begin with lol_render_spec: it is no frame. */
 	if (carries.carries(SWITCH_RAYS)) {
-		s += "#include \"lol_kernel_rays.h\"\n";
+		s += include(SWITCH_RAYS);
 		s += "extern \"C\" __global__ __launch_bounds__(64)" + occupancy + " void lol_trace_spec(const lol::RayQuery Q) {\n";
 		s += "\tlol::SpecSdfExact exact;\n";
 		if (any_fast) s += "\tlol::SpecSdfFast fast;\n\tlol::trace_rays(fast, exact, true, Q);\n";
@@ -977,7 +979,7 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	 * ray (lol_kernel_shade.h) — a Launch for the scene's half and a ShadeQuery behind it; which SDF and which shadow loop a wave may
 	 * run is decided in shade_rays.  One counting form.  Appended after everything else, for the reason above. */
 	if (carries.carries(SWITCH_SHADE)) {
-		s += "#include \"lol_kernel_shade.h\"\n";
+		s += include(SWITCH_SHADE);
 		s += head + "lol_shade_spec(const lol::Launch L, const lol::ShadeQuery Q) {\n\textern __shared__ lol::u32 lds[];\n" + stage;
 		s += "\tlol::SpecSdfExact exact;\n";
 		if (any_fast) s += "\tlol::SpecSdfFast fast;\n\tlol::shade_rays<" + tg + ">(fast, exact, true, L, Q, lds);\n";
@@ -1285,83 +1287,13 @@ int lol_gpu_testing_has_return_clobbering_branch(const void* code, size_t n_byte
 	return has_return_clobbering_branch(code, n_bytes) ? 1 : 0;
 }
 
-/* Offline use (tests, ISA inspection; needs no device): compile the scene-specialised kernel for
- * `arch` and write `<out_base>.hip` (generated source) and `<out_base>.co` (code object). */
-int lol_gpu_compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
-                            char* log, size_t logcap) {
-	return lol_gpu_compile_offline_samples(prog, arch, out_base, assume_fast, 1, log, logcap);
-}
-
-/* ... the module a context with lol_gpu_set_samples(ctx, samples) compiles at its upload: with samples > 1 it also carries
- * lol_render_spec_aa (lol_gpu_diag.h) */
-static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, ModuleKernels carries,
-                           int form, char* log, size_t logcap);
-
-int lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples,
-                                    char* log, size_t logcap) {
-	if (samples != 1 && samples != 2 && samples != 4) return LOL_GPU_ERR_ARG;
-	return compile_offline(prog, arch, out_base, assume_fast, { samples > 1, false, false }, SPEC_BY_SIZE, log, logcap);
-}
-
-/* ... the module a context with lol_gpu_set_view_batches(ctx, 1) compiles at its upload, in the form of one of its tiers
- * (lol_gpu_diag.h) */
-int lol_gpu_compile_offline_views(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable, int form,
-                                  char* log, size_t logcap) {
+/* Offline use (tests, ISA inspection; needs no device): compile the scene module with the switches of mask `switches` for `arch` and
+ * write `<out_base>.hip` (generated source) and `<out_base>.co` (code object); lol_gpu_diag.h */
+int lol_gpu_compile_offline_module(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, unsigned switches,
+                                   int form, char* log, size_t logcap) {
+	if (!prog || !arch || switches > ALL_SWITCHES) return LOL_GPU_ERR_ARG;
 	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
-	return compile_offline(prog, arch, out_base, assume_fast, { false, enable != 0, false }, form, log, logcap);
-}
-
-/* ... and the module a context with lol_gpu_set_view_samples(ctx, 1) compiles at its upload (lol_gpu_diag.h) */
-int lol_gpu_compile_offline_view_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
-                                         int form, char* log, size_t logcap) {
-	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
-	return compile_offline(prog, arch, out_base, assume_fast, { false, false, enable != 0 }, form, log, logcap);
-}
-
-/* ... and the module a context with lol_gpu_set_view_blends(ctx, 1) compiles at its upload (lol_gpu_diag.h) */
-int lol_gpu_compile_offline_view_blends(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
-                                        int form, char* log, size_t logcap) {
-	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
-	if (enable < 0 || enable > 15) return LOL_GPU_ERR_ARG;
-	/* bit 0: lol_gpu_set_view_blends; bits 1 - 3: the context's other switches beside it (samples > 1, view batches, view samples) */
-	return compile_offline(prog, arch, out_base, assume_fast, { (enable & 2) != 0, (enable & 4) != 0, (enable & 8) != 0, (enable & 1) != 0 },
-	                       form, log, logcap);
-}
-
-/* ... and the module a context with lol_gpu_set_view_blend_samples(ctx, enable) compiles at its upload (lol_gpu_diag.h) */
-int lol_gpu_compile_offline_view_blend_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
-                                               int others, int form, char* log, size_t logcap) {
-	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
-	if (others < 0 || others > 15) return LOL_GPU_ERR_ARG;
-	/* others: lol_gpu_compile_offline_view_blends' mask of the context's other switches */
-	return compile_offline(prog, arch, out_base, assume_fast,
-	                       { (others & 2) != 0, (others & 4) != 0, (others & 8) != 0, (others & 1) != 0, enable != 0 }, form, log, logcap);
-}
-
-/* ... and the module a context with lol_gpu_set_ray_queries(ctx, enable) compiles at its upload (lol_gpu_diag.h) */
-int lol_gpu_compile_offline_rays(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
-                                 int others, int form, char* log, size_t logcap) {
-	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
-	if (others < 0 || others > 31) return LOL_GPU_ERR_ARG;
-	/* others: lol_gpu_compile_offline_view_blends' mask of the context's other switches, 16 = lol_gpu_set_view_blend_samples */
-	return compile_offline(prog, arch, out_base, assume_fast,
-	                       { (others & 2) != 0, (others & 4) != 0, (others & 8) != 0, (others & 1) != 0, (others & 16) != 0, enable != 0 }, form, log, logcap);
-}
-
-/* ... and the module a context with lol_gpu_set_shade_queries(ctx, enable) compiles at its upload (lol_gpu_diag.h) */
-int lol_gpu_compile_offline_shade(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
-                                  int others, int form, char* log, size_t logcap) {
-	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
-	if (others < 0 || others > 63) return LOL_GPU_ERR_ARG;
-	/* others: lol_gpu_compile_offline_rays' mask of the context's other switches, 32 = lol_gpu_set_ray_queries */
-	return compile_offline(prog, arch, out_base, assume_fast,
-	                       { (others & 2) != 0, (others & 4) != 0, (others & 8) != 0, (others & 1) != 0, (others & 16) != 0, (others & 32) != 0, enable != 0 },
-	                       form, log, logcap);
-}
-
-static int compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, ModuleKernels carries,
-                           int form, char* log, size_t logcap) {
-	if (!prog || !arch) return LOL_GPU_ERR_ARG;
+	const ModuleKernels carries = { switches };
 	std::vector<char> code;
 	std::string lg, src;
 	FastPaths fast;
@@ -1391,6 +1323,60 @@ static int compile_offline(const lol_program* prog, const char* arch, const char
 		if (ok) if (FILE* f = fopen((base + ".co").c_str(), "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
 	}
 	return ok ? LOL_GPU_OK : LOL_GPU_ERR_UNSUPPORTED;
+}
+
+/* The entry points from before that one, each the module of a mask (lol_gpu_diag.h).  Their `others` is a mask in an order of its
+ * own, the one in which the switches came to be. */
+static unsigned on(int enable, ModuleSwitch sw) { return enable ? switch_bit(sw) : 0u; }
+static unsigned switches_of(int others) {
+	return on(others & 1, SWITCH_BATCH_BLEND) | on(others & 2, SWITCH_AA) | on(others & 4, SWITCH_BATCH) | on(others & 8, SWITCH_BATCH_AA) |
+	       on(others & 16, SWITCH_BATCH_BLEND_AA) | on(others & 32, SWITCH_RAYS);
+}
+
+int lol_gpu_compile_offline(const lol_program* prog, const char* arch, const char* out_base, int assume_fast,
+                            char* log, size_t logcap) {
+	return lol_gpu_compile_offline_module(prog, arch, out_base, assume_fast, 0, SPEC_BY_SIZE, log, logcap);
+}
+
+int lol_gpu_compile_offline_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int samples,
+                                    char* log, size_t logcap) {
+	if (samples != 1 && samples != 2 && samples != 4) return LOL_GPU_ERR_ARG;
+	return lol_gpu_compile_offline_module(prog, arch, out_base, assume_fast, on(samples > 1, SWITCH_AA), SPEC_BY_SIZE, log, logcap);
+}
+
+int lol_gpu_compile_offline_views(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable, int form,
+                                  char* log, size_t logcap) {
+	return lol_gpu_compile_offline_module(prog, arch, out_base, assume_fast, on(enable, SWITCH_BATCH), form, log, logcap);
+}
+
+int lol_gpu_compile_offline_view_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                         int form, char* log, size_t logcap) {
+	return lol_gpu_compile_offline_module(prog, arch, out_base, assume_fast, on(enable, SWITCH_BATCH_AA), form, log, logcap);
+}
+
+/* (`enable` is the mask here: bit 0 is the switch itself) */
+int lol_gpu_compile_offline_view_blends(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                        int form, char* log, size_t logcap) {
+	if (enable < 0 || enable > 15) return LOL_GPU_ERR_ARG;
+	return lol_gpu_compile_offline_module(prog, arch, out_base, assume_fast, switches_of(enable), form, log, logcap);
+}
+
+int lol_gpu_compile_offline_view_blend_samples(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                               int others, int form, char* log, size_t logcap) {
+	if (others < 0 || others > 15) return LOL_GPU_ERR_ARG;
+	return lol_gpu_compile_offline_module(prog, arch, out_base, assume_fast, switches_of(others) | on(enable, SWITCH_BATCH_BLEND_AA), form, log, logcap);
+}
+
+int lol_gpu_compile_offline_rays(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                 int others, int form, char* log, size_t logcap) {
+	if (others < 0 || others > 31) return LOL_GPU_ERR_ARG;
+	return lol_gpu_compile_offline_module(prog, arch, out_base, assume_fast, switches_of(others) | on(enable, SWITCH_RAYS), form, log, logcap);
+}
+
+int lol_gpu_compile_offline_shade(const lol_program* prog, const char* arch, const char* out_base, int assume_fast, int enable,
+                                  int others, int form, char* log, size_t logcap) {
+	if (others < 0 || others > 63) return LOL_GPU_ERR_ARG;
+	return lol_gpu_compile_offline_module(prog, arch, out_base, assume_fast, switches_of(others) | on(enable, SWITCH_SHADE), form, log, logcap);
 }
 
 }  // extern "C"

@@ -1331,14 +1331,6 @@ int lol_gpu_render_views_blend_samples(lol_gpu* ctx, const lol_frame_camera* cam
 	return render_blend(ctx, cams, n_views, cams_per_view, w, h, max_steps, samples, dst, pitch_bytes, view_stride_bytes, dbg, stream);
 }
 
-int lol_gpu_set_view_blend_samples(lol_gpu* ctx, int enable) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	ctx->view_blend_samples = enable ? 1 : 0;      /* takes effect at the next lol_gpu_upload_program */
-	return LOL_GPU_OK;
-}
-
-int lol_gpu_view_blend_samples(const lol_gpu* ctx) { return ctx ? ctx->view_blend_samples : LOL_GPU_ERR_ARG; }
-
 const char* lol_gpu_view_blend_samples_kernel_name(const lol_gpu* ctx, int cams_per_view, int samples) {
 	if (!ctx) return "";
 	if (samples <= 1) return lol_gpu_view_blend_kernel_name(ctx, cams_per_view);
@@ -1346,26 +1338,10 @@ const char* lol_gpu_view_blend_samples_kernel_name(const lol_gpu* ctx, int cams_
 	return family_name(ctx, FAM_BATCH_AA_LIN);
 }
 
-int lol_gpu_set_view_blends(lol_gpu* ctx, int enable) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	ctx->view_blends = enable ? 1 : 0;       /* takes effect at the next lol_gpu_upload_program */
-	return LOL_GPU_OK;
-}
-
-int lol_gpu_view_blends(const lol_gpu* ctx) { return ctx ? ctx->view_blends : LOL_GPU_ERR_ARG; }
-
 const char* lol_gpu_view_blend_kernel_name(const lol_gpu* ctx, int cams_per_view) {
 	if (!ctx) return "";
 	return family_name(ctx, cams_per_view <= 1 ? FAM_BATCH : FAM_BATCH_LIN);
 }
-
-int lol_gpu_set_view_samples(lol_gpu* ctx, int enable) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	ctx->view_samples = enable ? 1 : 0;      /* takes effect at the next lol_gpu_upload_program */
-	return LOL_GPU_OK;
-}
-
-int lol_gpu_view_samples(const lol_gpu* ctx) { return ctx ? ctx->view_samples : LOL_GPU_ERR_ARG; }
 
 const char* lol_gpu_view_samples_kernel_name(const lol_gpu* ctx, int samples, int contrast) {
 	if (!ctx) return "";
@@ -1401,14 +1377,6 @@ int lol_gpu_testing_fail_view_scratch(lol_gpu* ctx, int n) {
 	ctx->fail_view_scratch = n;
 	return LOL_GPU_OK;
 }
-
-int lol_gpu_set_view_batches(lol_gpu* ctx, int enable) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	ctx->view_batches = enable ? 1 : 0;      /* takes effect at the next lol_gpu_upload_program */
-	return LOL_GPU_OK;
-}
-
-int lol_gpu_view_batches(const lol_gpu* ctx) { return ctx ? ctx->view_batches : LOL_GPU_ERR_ARG; }
 
 int lol_gpu_set_pixel_format(lol_gpu* ctx, const lol_gpu_pixel_format* fmt) {
 	if (!ctx) return LOL_GPU_ERR_ARG;
@@ -1646,6 +1614,26 @@ int lol_gpu_set_samples(lol_gpu* ctx, int samples) {
 
 int lol_gpu_samples(const lol_gpu* ctx) { return ctx ? ctx->samples : LOL_GPU_ERR_ARG; }
 
+/* The module switches beside it (lol_gpu_internal.h, MODULE_SWITCHES): each takes effect at the next lol_gpu_upload_program */
+static int set_module_switch(lol_gpu* ctx, ModuleSwitch sw, int enable) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	ctx->module_switches = enable ? ctx->module_switches | switch_bit(sw) : ctx->module_switches & ~switch_bit(sw);
+	return LOL_GPU_OK;
+}
+static int module_switch(const lol_gpu* ctx, ModuleSwitch sw) { return ctx ? (ctx->module_switches & switch_bit(sw)) != 0 : LOL_GPU_ERR_ARG; }
+int lol_gpu_set_view_batches(lol_gpu* ctx, int enable)       { return set_module_switch(ctx, SWITCH_BATCH, enable); }
+int lol_gpu_set_view_samples(lol_gpu* ctx, int enable)       { return set_module_switch(ctx, SWITCH_BATCH_AA, enable); }
+int lol_gpu_set_view_blends(lol_gpu* ctx, int enable)        { return set_module_switch(ctx, SWITCH_BATCH_BLEND, enable); }
+int lol_gpu_set_view_blend_samples(lol_gpu* ctx, int enable) { return set_module_switch(ctx, SWITCH_BATCH_BLEND_AA, enable); }
+int lol_gpu_set_ray_queries(lol_gpu* ctx, int enable)        { return set_module_switch(ctx, SWITCH_RAYS, enable); }
+int lol_gpu_set_shade_queries(lol_gpu* ctx, int enable)      { return set_module_switch(ctx, SWITCH_SHADE, enable); }
+int lol_gpu_view_batches(const lol_gpu* ctx)       { return module_switch(ctx, SWITCH_BATCH); }
+int lol_gpu_view_samples(const lol_gpu* ctx)       { return module_switch(ctx, SWITCH_BATCH_AA); }
+int lol_gpu_view_blends(const lol_gpu* ctx)        { return module_switch(ctx, SWITCH_BATCH_BLEND); }
+int lol_gpu_view_blend_samples(const lol_gpu* ctx) { return module_switch(ctx, SWITCH_BATCH_BLEND_AA); }
+int lol_gpu_ray_queries(const lol_gpu* ctx)        { return module_switch(ctx, SWITCH_RAYS); }
+int lol_gpu_shade_queries(const lol_gpu* ctx)      { return module_switch(ctx, SWITCH_SHADE); }
+
 int lol_gpu_set_adaptive_samples(lol_gpu* ctx, int contrast) {
 	if (!ctx) return LOL_GPU_ERR_ARG;
 	if (contrast < -1 || contrast > 255) return fail(ctx, LOL_GPU_ERR_ARG, "adaptive contrast must be -1 (off) or 0 ... 255");
@@ -1829,14 +1817,6 @@ int lol_gpu_pick(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int ma
 	return LOL_GPU_OK;
 }
 
-int lol_gpu_set_ray_queries(lol_gpu* ctx, int enable) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	ctx->ray_queries = enable ? 1 : 0;       /* takes effect at the next lol_gpu_upload_program */
-	return LOL_GPU_OK;
-}
-
-int lol_gpu_ray_queries(const lol_gpu* ctx) { return ctx ? ctx->ray_queries : LOL_GPU_ERR_ARG; }
-
 const char* lol_gpu_trace_kernel_name(const lol_gpu* ctx) {
 	if (!ctx) return "";
 	return trace_kernel(ctx) ? "lol_trace_spec" : "trace_interp";
@@ -1930,14 +1910,6 @@ int lol_gpu_shade_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h
 	Q.flags = lol::SHADE_FROM_PIXELS;
 	return launch_shade(ctx, Q, cam, w, h, n, max_steps, out, stream);
 }
-
-int lol_gpu_set_shade_queries(lol_gpu* ctx, int enable) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	ctx->shade_queries = enable ? 1 : 0;     /* takes effect at the next lol_gpu_upload_program */
-	return LOL_GPU_OK;
-}
-
-int lol_gpu_shade_queries(const lol_gpu* ctx) { return ctx ? ctx->shade_queries : LOL_GPU_ERR_ARG; }
 
 const char* lol_gpu_shade_kernel_name(const lol_gpu* ctx) {
 	if (!ctx) return "";

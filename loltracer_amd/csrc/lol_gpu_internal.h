@@ -139,8 +139,11 @@ struct OwnedProgram {
  * (lol_gpu.hip) launches one or the other and the reported kernel names come from here.  A new family is one row plus its kernel. */
 enum KernelFamily { FAM_FRAME, FAM_FRAME_AA, FAM_FRAME_AA_LIST, FAM_BATCH, FAM_BATCH_AA, FAM_BATCH_AA_LIST, FAM_BATCH_LIN, FAM_BATCH_AA_LIN,
                     N_FAMILIES };
-/* the switch of the context that puts a family into the module of the next upload */
-enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA, SWITCH_BATCH_BLEND, SWITCH_BATCH_BLEND_AA, SWITCH_RAYS, SWITCH_SHADE };
+/* the switch that puts a family into the module of the next upload: a row of MODULE_SWITCHES below */
+enum ModuleSwitch { SWITCH_NONE, SWITCH_AA, SWITCH_BATCH, SWITCH_BATCH_AA, SWITCH_BATCH_BLEND, SWITCH_BATCH_BLEND_AA, SWITCH_RAYS, SWITCH_SHADE,
+                    N_SWITCHES };
+constexpr unsigned switch_bit(int sw) { return (1u << sw) >> 1; }      /* 1u << (sw - 1), and none for SWITCH_NONE */
+constexpr unsigned ALL_SWITCHES = (1u << (N_SWITCHES - 1)) - 1;
 struct FamilyRow {
 	const char*  symbol;        /* in the scene module */
 	const char*  counting;      /* its twin with the per-lane step counters (modules up to LOL_SPEC_TWO_KERNELS_MAX_OPS ops), or none */
@@ -158,23 +161,45 @@ constexpr FamilyRow KERNEL_FAMILIES[N_FAMILIES] = {
 	/* FAM_BATCH_AA_LIN  (L, B)           */ { "lol_render_spec_batch_aa_lin",  nullptr,                       "render_interp_batch_aa_lin",  SWITCH_BATCH_BLEND_AA },
 };
 
-/* What a scene module carries beside lol_render_spec and lol_sdf_spec.  Without any of it the source is exactly what it was before
- * these kernels existed.  aa: lol_gpu_set_samples > 1 at the upload; batch: lol_gpu_set_view_batches; batch_aa:
- * lol_gpu_set_view_samples, which brings the plain batch kernels with it (the first pass of an adaptive batch is theirs); blend:
- * lol_gpu_set_view_blends, the linear-colour batch kernel alone (lol_kernel_blend.h); blend_aa: lol_gpu_set_view_blend_samples, its
- * supersampled form alone (lol_kernel_blend_aa.h) — a switch of its own, NOT implied by blend and batch_aa together; rays:
- * lol_gpu_set_ray_queries, lol_trace_spec (lol_kernel_rays.h).  That kernel is no row of KERNEL_FAMILIES: launch_family hands a family
- * a Launch, a block of lol::BLOCK threads, the tables' LDS and perhaps a counting twin, and a query has none of the four — it lives
- * beside lol_sdf_spec (SceneKernel::trace), the other kernel that is not a frame; shade: lol_gpu_set_shade_queries, lol_shade_spec
- * (lol_kernel_shade.h), beside it for the same reason (SceneKernel::shade): it takes a Launch and the tables' LDS, but a ShadeQuery
- * and a grid over a list instead of a frame's tiles, and it has no twin. */
+/* What a scene module carries beside lol_render_spec and lol_sdf_spec, one row per switch.  THE list: a module is a mask of
+ * switch_bit()s — the context's (lol_gpu::module_switches, module_kernels_of), an offline compile's (lol_gpu_compile_offline_module,
+ * whose documentation in lol_gpu_diag.h restates these rows) —, generate_source includes a row's header in the block it appends for
+ * it, and what a switch brings with it is said here alone.  Without any switch the source is exactly what it was before these
+ * kernels existed.  A new switch is one row, its block in generate_source, and its public setter. */
+struct SwitchRow {
+	const char* setter;         /* the public call that sets it before an upload */
+	const char* header;         /* what the block generate_source appends for it includes */
+	unsigned    brings;         /* the switches that come with it */
+};
+constexpr SwitchRow MODULE_SWITCHES[N_SWITCHES] = {
+	/* SWITCH_NONE */           { nullptr,                          "lol_kernel.h",          0 },
+	/* SWITCH_AA (samples > 1 at the upload) */
+	                            { "lol_gpu_set_samples",            "lol_kernel_aa.h",       0 },
+	/* SWITCH_BATCH */          { "lol_gpu_set_view_batches",       "lol_kernel_batch.h",    0 },
+	/* SWITCH_BATCH_AA: the first pass of an adaptive batch is the plain batch kernels' */
+	                            { "lol_gpu_set_view_samples",       "lol_kernel_batch_aa.h", switch_bit(SWITCH_BATCH) },
+	/* SWITCH_BATCH_BLEND: the linear-colour batch kernel alone */
+	                            { "lol_gpu_set_view_blends",        "lol_kernel_blend.h",    0 },
+	/* SWITCH_BATCH_BLEND_AA: its supersampled form alone — a switch of its own, NOT implied by BATCH_BLEND and BATCH_AA together */
+	                            { "lol_gpu_set_view_blend_samples", "lol_kernel_blend_aa.h", 0 },
+	/* SWITCH_RAYS: lol_trace_spec.  That kernel is no row of KERNEL_FAMILIES: launch_family hands a family a Launch, a block of
+	 * lol::BLOCK threads, the tables' LDS and perhaps a counting twin, and a query has none of the four — it lives beside lol_sdf_spec
+	 * (SceneKernel::trace), the other kernel that is not a frame */
+	                            { "lol_gpu_set_ray_queries",        "lol_kernel_rays.h",     0 },
+	/* SWITCH_SHADE: lol_shade_spec, beside it for the same reason (SceneKernel::shade): it takes a Launch and the tables' LDS, but a
+	 * ShadeQuery and a grid over a list instead of a frame's tiles, and it has no twin */
+	                            { "lol_gpu_set_shade_queries",      "lol_kernel_shade.h",    0 },
+};
+/* `mask` and what its switches bring (one pass: nothing that is brought brings anything itself) */
+constexpr unsigned switch_closure(unsigned mask) {
+	unsigned all = mask;
+	for (int sw = SWITCH_AA; sw < N_SWITCHES; sw++)
+		if (mask & switch_bit(sw)) all |= MODULE_SWITCHES[sw].brings;
+	return all;
+}
 struct ModuleKernels {
-	bool aa = false, batch = false, batch_aa = false, blend = false, blend_aa = false, rays = false, shade = false;
-	bool carries(ModuleSwitch sw) const {
-		return sw == SWITCH_NONE || (sw == SWITCH_AA && aa) || (sw == SWITCH_BATCH && (batch || batch_aa)) || (sw == SWITCH_BATCH_AA && batch_aa) ||
-		       (sw == SWITCH_BATCH_BLEND && blend) || (sw == SWITCH_BATCH_BLEND_AA && blend_aa) || (sw == SWITCH_RAYS && rays) ||
-		       (sw == SWITCH_SHADE && shade);
-	}
+	unsigned mask = 0;          /* of switch_bit()s, as set: carries() adds what they bring */
+	bool carries(ModuleSwitch sw) const { return sw == SWITCH_NONE || (switch_closure(mask) & switch_bit(sw)) != 0; }
 };
 
 /* One code object of the scene compiler, loaded with every kernel generate_source put in it or not at all (load_scene_kernel,
@@ -259,12 +284,7 @@ struct lol_gpu {
 	std::string  interp_aa_key;          /* ... and of its supersampling kernel (render_interp_aa) */
 	int          samples = 1;            /* lol_gpu_set_samples: samples per pixel along each axis of the frames launched from now on */
 	int          adaptive = -1;          /* lol_gpu_set_adaptive_samples: the contrast T, or -1 (off) */
-	int          view_batches = 0;       /* lol_gpu_set_view_batches: the next upload's module carries lol_render_spec_batch */
-	int          view_samples = 0;       /* lol_gpu_set_view_samples: ... and lol_render_spec_batch_aa / _aa_list (and the batch kernels) */
-	int          view_blends = 0;        /* lol_gpu_set_view_blends: ... and lol_render_spec_batch_lin */
-	int          view_blend_samples = 0; /* lol_gpu_set_view_blend_samples: ... and lol_render_spec_batch_aa_lin */
-	int          ray_queries = 0;        /* lol_gpu_set_ray_queries: ... and lol_trace_spec */
-	int          shade_queries = 0;      /* lol_gpu_set_shade_queries: ... and lol_shade_spec */
+	unsigned     module_switches = 0; /* the switch_bit()s set by lol_gpu_set_view_batches ... lol_gpu_set_shade_queries (MODULE_SWITCHES) */
 	void*        d_pick = nullptr;       /* lol_gpu_pick's device memory, from the first pick on: xy [2] | dist | id | steps | normal [3] */
 	/* The view records of batches (lol_gpu_render_views, lol_gpu.hip): a ring of sets, one per batch, whatever its stream.  A batch
 	 * fills its set's pinned host copy, queues the copy to the device and the launch behind it on its stream, and records `done`;
@@ -412,6 +432,12 @@ struct lol_gpu {
 	unsigned     frame_rr = 0;
 	char         err[512] = { 0 };
 };
+
+/* the module of an upload: the switches set, and supersampling when the context's frames have more than one sample (what is asked
+ * for after the upload renders on the interpreter's kernel of that family) */
+inline ModuleKernels module_kernels_of(const lol_gpu* ctx) {
+	return { ctx->module_switches | (ctx->samples > 1 ? switch_bit(SWITCH_AA) : 0u) };
+}
 
 /* an A/B switch from the environment, honoured only beside LOL_GPU_TUNING=1 and recorded when it is (lol_gpu.hip) */
 const char* lol_gpu_internal_tuning_env(const char* name);

@@ -220,9 +220,7 @@ void start_specialise(lol_gpu* ctx, const FastPaths& fast) {
 		if (!sw.empty()) job->note += "tuning switches in effect (LOL_GPU_TUNING=1): " + sw + "\n";
 	} catch (...) { T.log = "out of host memory"; return; }
 	job->cull = culling_enabled(ctx->want_cull);
-	/* (what is asked for after the upload renders on the interpreter's kernel of that family) */
-	job->carries = { ctx->samples > 1, ctx->view_batches != 0, ctx->view_samples != 0, ctx->view_blends != 0, ctx->view_blend_samples != 0, ctx->ray_queries != 0,
-	                 ctx->shade_queries != 0 };
+	job->carries = module_kernels_of(ctx);
 	/* (LOL_GPU_SPEC_INLINE_MAX, a tuning switch, pins ONE form by size) */
 	const bool first_tier = !tuning_env("LOL_GPU_SPEC_INLINE_MAX") && ctx->h_prog.n_ops > LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS &&
 	                        ctx->h_prog.n_ops <= LOL_SPEC_INLINE_MAX_OPS;

@@ -191,6 +191,8 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_compile_offline.restype = C.c_int
         lib.lol_gpu_compile_offline_samples.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
         lib.lol_gpu_compile_offline_samples.restype = C.c_int
+        lib.lol_gpu_compile_offline_module.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_char_p, C.c_size_t]
+        lib.lol_gpu_compile_offline_module.restype = C.c_int
         lib.lol_gpu_set_samples.argtypes = [vp, C.c_int]
         lib.lol_gpu_set_samples.restype = C.c_int
         lib.lol_gpu_samples.argtypes = [vp]
@@ -411,7 +413,7 @@ DIAG_SYMBOLS = [                                                        # includ
     "lol_gpu_views_refined", "lol_gpu_interp_variant", "lol_gpu_compile_offline_view_blends", "lol_gpu_view_blend_kernel_name",
     "lol_gpu_compile_offline_view_blend_samples", "lol_gpu_view_blend_samples_kernel_name",
     "lol_gpu_trace_kernel_name", "lol_gpu_compile_offline_rays", "lol_gpu_code_key",
-    "lol_gpu_shade_kernel_name", "lol_gpu_compile_offline_shade",
+    "lol_gpu_shade_kernel_name", "lol_gpu_compile_offline_shade", "lol_gpu_compile_offline_module",
 ]
 
 
@@ -427,111 +429,79 @@ def code_key(code: bytes) -> str:
     return out.value.decode()
 
 
-def compile_offline(program: S.Program, out_base: str, arch: str = "gfx950", assume_fast: bool = False) -> str:
-    """hipRTC-compile the scene-specialised kernel without a device; returns the compiler log."""
+# the module switches, by their setters' names: bit i of lol_gpu_compile_offline_module's mask (include/lol_gpu_diag.h)
+MODULE_SWITCHES = ("samples", "view_batches", "view_samples", "view_blends", "view_blend_samples", "ray_queries", "shade_queries")
+
+
+def compile_offline_module(program: S.Program, out_base: str, switches=(), form: int = 0, arch: str = "gfx950",
+                           assume_fast: bool = False) -> str:
+    """hipRTC-compile the scene module a context with `switches` set before its upload gets (names of MODULE_SWITCHES; "samples":
+    set_samples > 1), without a device: writes out_base.hip and out_base.co and returns the compiler log.  form: 0 by the scene's
+    size, 1 the SDF out of line, 2 inlined (the two kernels of a 257 ... 1024-op scene)."""
+    unknown = set(switches) - set(MODULE_SWITCHES)
+    if unknown:
+        raise ValueError("no module switch: " + ", ".join(sorted(unknown)))
+    mask = sum(1 << MODULE_SWITCHES.index(name) for name in set(switches))
     log = C.create_string_buffer(1 << 16)
-    st = gpu_lib().lol_gpu_compile_offline(C.byref(program), arch.encode(), os.fsencode(out_base),
-                                           int(assume_fast), log, len(log))
+    st = gpu_lib().lol_gpu_compile_offline_module(C.byref(program), arch.encode(), os.fsencode(out_base), int(assume_fast), mask,
+                                                  int(form), log, len(log))
     if st != LOL_GPU_OK:
         raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
     return log.value.decode(errors="replace")
+
+
+# The entry points from before compile_offline_module, one per switch: `enable` is that switch, the keywords the others beside it.
+def _offline(program, out_base, form, arch, assume_fast, **switches) -> str:
+    return compile_offline_module(program, out_base, [name for name, on in switches.items() if on], form, arch, assume_fast)
+
+
+def compile_offline(program: S.Program, out_base: str, arch: str = "gfx950", assume_fast: bool = False) -> str:
+    return _offline(program, out_base, 0, arch, assume_fast)
 
 
 def compile_offline_samples(program: S.Program, out_base: str, samples: int, arch: str = "gfx950",
                             assume_fast: bool = False) -> str:
-    """compile_offline for a context with set_samples(samples) before its upload: samples > 1 adds lol_render_spec_aa."""
-    log = C.create_string_buffer(1 << 16)
-    st = gpu_lib().lol_gpu_compile_offline_samples(C.byref(program), arch.encode(), os.fsencode(out_base),
-                                                   int(assume_fast), int(samples), log, len(log))
-    if st != LOL_GPU_OK:
-        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
-    return log.value.decode(errors="replace")
+    if samples not in (1, 2, 4):
+        raise GpuError(-3, "samples per axis must be 1, 2 or 4")
+    return _offline(program, out_base, 0, arch, assume_fast, samples=samples > 1)
 
 
 def compile_offline_views(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
                           assume_fast: bool = False) -> str:
-    """compile_offline for a context with set_view_batches(enable) before its upload: adds lol_render_spec_batch.  form: 0 by the
-    scene's size, 1 the SDF out of line, 2 inlined (the two kernels of a 257 ... 1024-op scene)."""
-    log = C.create_string_buffer(1 << 16)
-    st = gpu_lib().lol_gpu_compile_offline_views(C.byref(program), arch.encode(), os.fsencode(out_base),
-                                                 int(assume_fast), int(bool(enable)), int(form), log, len(log))
-    if st != LOL_GPU_OK:
-        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
-    return log.value.decode(errors="replace")
+    return _offline(program, out_base, form, arch, assume_fast, view_batches=enable)
 
 
 def compile_offline_view_samples(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
                                  assume_fast: bool = False) -> str:
-    """compile_offline for a context with set_view_samples(enable) before its upload: what compile_offline_views writes, with
-    lol_render_spec_batch_aa and lol_render_spec_batch_aa_list appended.  form as for compile_offline_views."""
-    log = C.create_string_buffer(1 << 16)
-    st = gpu_lib().lol_gpu_compile_offline_view_samples(C.byref(program), arch.encode(), os.fsencode(out_base),
-                                                        int(assume_fast), int(bool(enable)), int(form), log, len(log))
-    if st != LOL_GPU_OK:
-        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
-    return log.value.decode(errors="replace")
+    return _offline(program, out_base, form, arch, assume_fast, view_samples=enable)
 
 
 def compile_offline_view_blends(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
                                 assume_fast: bool = False, samples: bool = False, view_batches: bool = False,
                                 view_samples: bool = False) -> str:
-    """compile_offline for a context with set_view_blends(enable) before its upload: adds lol_render_spec_batch_lin.  form as for
-    compile_offline_views.  samples / view_batches / view_samples: the context's other switches set beside it (set_samples > 1,
-    set_view_batches, set_view_samples).  Needs no device."""
-    log = C.create_string_buffer(1 << 16)
-    mask = int(bool(enable)) | int(bool(samples)) << 1 | int(bool(view_batches)) << 2 | int(bool(view_samples)) << 3
-    st = gpu_lib().lol_gpu_compile_offline_view_blends(C.byref(program), arch.encode(), os.fsencode(out_base),
-                                                       int(assume_fast), mask, int(form), log, len(log))
-    if st != LOL_GPU_OK:
-        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
-    return log.value.decode(errors="replace")
+    return _offline(program, out_base, form, arch, assume_fast, view_blends=enable, samples=samples, view_batches=view_batches,
+                    view_samples=view_samples)
 
 
 def compile_offline_view_blend_samples(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
                                        assume_fast: bool = False, view_blends: bool = False, samples: bool = False,
                                        view_batches: bool = False, view_samples: bool = False) -> str:
-    """compile_offline for a context with set_view_blend_samples(enable) before its upload: adds lol_render_spec_batch_aa_lin, last.
-    form as for compile_offline_views.  view_blends / samples / view_batches / view_samples: the context's other switches set beside
-    it.  Needs no device."""
-    log = C.create_string_buffer(1 << 16)
-    others = int(bool(view_blends)) | int(bool(samples)) << 1 | int(bool(view_batches)) << 2 | int(bool(view_samples)) << 3
-    st = gpu_lib().lol_gpu_compile_offline_view_blend_samples(C.byref(program), arch.encode(), os.fsencode(out_base),
-                                                              int(assume_fast), int(bool(enable)), others, int(form), log, len(log))
-    if st != LOL_GPU_OK:
-        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
-    return log.value.decode(errors="replace")
+    return _offline(program, out_base, form, arch, assume_fast, view_blend_samples=enable, view_blends=view_blends, samples=samples,
+                    view_batches=view_batches, view_samples=view_samples)
 
 
 def compile_offline_rays(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
                          assume_fast: bool = False, view_blends: bool = False, samples: bool = False, view_batches: bool = False,
                          view_samples: bool = False, view_blend_samples: bool = False) -> str:
-    """compile_offline for a context with set_ray_queries(enable) before its upload: adds lol_trace_spec, last.  form as for
-    compile_offline_views.  view_blends / samples / view_batches / view_samples / view_blend_samples: the context's other switches
-    set beside it.  Needs no device."""
-    log = C.create_string_buffer(1 << 16)
-    others = (int(bool(view_blends)) | int(bool(samples)) << 1 | int(bool(view_batches)) << 2 | int(bool(view_samples)) << 3 |
-              int(bool(view_blend_samples)) << 4)
-    st = gpu_lib().lol_gpu_compile_offline_rays(C.byref(program), arch.encode(), os.fsencode(out_base),
-                                                int(assume_fast), int(bool(enable)), others, int(form), log, len(log))
-    if st != LOL_GPU_OK:
-        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
-    return log.value.decode(errors="replace")
+    return _offline(program, out_base, form, arch, assume_fast, ray_queries=enable, view_blends=view_blends, samples=samples,
+                    view_batches=view_batches, view_samples=view_samples, view_blend_samples=view_blend_samples)
 
 
 def compile_offline_shade(program: S.Program, out_base: str, enable: bool = True, form: int = 0, arch: str = "gfx950",
                           assume_fast: bool = False, view_blends: bool = False, samples: bool = False, view_batches: bool = False,
                           view_samples: bool = False, view_blend_samples: bool = False, ray_queries: bool = False) -> str:
-    """compile_offline for a context with set_shade_queries(enable) before its upload: adds lol_shade_spec, last.  form as for
-    compile_offline_views.  view_blends / samples / view_batches / view_samples / view_blend_samples / ray_queries: the context's
-    other switches set beside it.  Needs no device."""
-    log = C.create_string_buffer(1 << 16)
-    others = (int(bool(view_blends)) | int(bool(samples)) << 1 | int(bool(view_batches)) << 2 | int(bool(view_samples)) << 3 |
-              int(bool(view_blend_samples)) << 4 | int(bool(ray_queries)) << 5)
-    st = gpu_lib().lol_gpu_compile_offline_shade(C.byref(program), arch.encode(), os.fsencode(out_base),
-                                                 int(assume_fast), int(bool(enable)), others, int(form), log, len(log))
-    if st != LOL_GPU_OK:
-        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
-    return log.value.decode(errors="replace")
+    return _offline(program, out_base, form, arch, assume_fast, shade_queries=enable, view_blends=view_blends, samples=samples,
+                    view_batches=view_batches, view_samples=view_samples, view_blend_samples=view_blend_samples, ray_queries=ray_queries)
 
 
 MAX_VIEWS = 4096                     # LOL_GPU_MAX_VIEWS

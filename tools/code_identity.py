@@ -10,6 +10,8 @@ loltracer_amd/csrc) and writes what was compared, and the result, as JSON:
   ahead of time      the six .hip units compiled device-only with the Makefile's flags in both trees: every kernel's bytes and
                      its .kd descriptor (but the code's offset from it, a position in the file) must be equal, by name; kernels only
                      this checkout has are listed as `added`.
+  every mask         with --masks: scene4's module for each of the 128 sets of module switches, through lol_gpu_compile_offline_shade
+                     (the one call that reaches them all): the generated source and the loaded sections must be equal.
 
     python tools/code_identity.py --parent ../parent --work /tmp/ident --out profiles/r14_code_identity.json
 
@@ -31,6 +33,8 @@ MODULES = (("compile_offline", 0, 0), ("_samples", 0, 2), ("_views", 0, 4), ("_v
            ("_view_blend_samples", 0, 16), ("_rays+all", 1, 31))
 LOADED = (".text", ".rodata", ".note")
 UNITS = ("lol_gpu", "lol_tiers", "lol_proofs", "lol_codegen", "lol_sched", "lol_multi")
+N_MASKS = 128                         # seven module switches
+MAX_JOBS = 16
 
 
 # ---------------------------------------------------------------- ELF64 little-endian, as much as is needed
@@ -93,18 +97,47 @@ def emit_modules(tree, out_dir):
                     raise SystemExit("%s: compile failed (%d)" % (base, st))
 
 
-def compile_modules(tree, out_dir, jobs):
-    os.makedirs(out_dir, exist_ok=True)
+def emit_masks(tree, out_dir, part, parts):
+    """(worker) scene4's module for every `parts`-th mask from `part` on, through that tree's lol_gpu_compile_offline_shade"""
+    sys.path[:0] = [tree, os.path.join(tree, "tests")]
+    from loltracer_amd import gpu, scene as S
+    prog = S.Scene.parse_file(os.path.join(tree, "tests", "golden", "scenes", "scene4.lol")).flatten()
+    lib = gpu.gpu_lib()
+    for mask in range(part, N_MASKS, parts):
+        # the mask's bits in the order of the switches (1 samples > 1, 2 view batches, 4 view samples, 8 view blends, 16 blend samples,
+        # 32 ray queries, 64 shading queries) as that call takes them: `enable` and `others` = 1 view blends, 2 samples > 1, ...
+        enable, others = mask >> 6, (mask & 0x30) | (mask & 7) << 1 | (mask >> 3 & 1)
+        base = os.path.join(out_dir, "mask%03d" % mask)
+        st = lib.lol_gpu_compile_offline_shade(prog, b"gfx950", os.fsencode(base), 0, enable, others, 0, None, 0)
+        if st != 0:
+            raise SystemExit("%s: compile failed (%d)" % (base, st))
+
+
+def run_workers(commands, jobs):
     env = dict(os.environ, LOL_GPU_CACHE_DIR="")               # no disk cache: every module is really compiled
     env.pop("LOL_GPU_LIB", None)
     running = []
-    for n in list(SCENES) + ["mid_form1", "mid_form2"]:         # the scene compiler runs one module at a time per process
-        running.append(subprocess.Popen([sys.executable, os.path.abspath(__file__), "--emit", out_dir, "--parent", tree],
-                                        env=dict(env, CODE_IDENTITY_ONLY=n)))
+    for args, extra in commands:                                # the scene compiler runs one module at a time per process
+        running.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + args, env=dict(env, **extra)))
         if len(running) >= jobs and running.pop(0).wait() != 0:
             raise SystemExit("a worker failed")
     if any(p.wait() != 0 for p in running):
         raise SystemExit("a worker failed")
+
+
+def compile_modules(tree, out_dir, jobs):
+    os.makedirs(out_dir, exist_ok=True)
+    run_workers([(["--emit", out_dir, "--parent", tree], {"CODE_IDENTITY_ONLY": n}) for n in list(SCENES) + ["mid_form1", "mid_form2"]], jobs)
+
+
+def compile_masks(tree, out_dir, jobs):
+    os.makedirs(out_dir, exist_ok=True)
+    run_workers([(["--emit-masks", out_dir, "--parent", tree, "--part", "%d/%d" % (i, jobs)], {}) for i in range(jobs)], jobs)
+
+
+def loaded_sha(data):
+    secs = sections(data)
+    return sha(b"".join(section_bytes(data, secs[s]) for s in LOADED))
 
 
 def compile_ahead_of_time(tree, out_dir):
@@ -123,6 +156,9 @@ def compile_ahead_of_time(tree, out_dir):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--emit", help=argparse.SUPPRESS)
+    ap.add_argument("--emit-masks", help=argparse.SUPPRESS)
+    ap.add_argument("--part", help=argparse.SUPPRESS)
+    ap.add_argument("--masks", action="store_true", help="also compare scene4's module for every set of module switches")
     ap.add_argument("--parent", help="a built checkout of the commit to compare with")
     ap.add_argument("--work", help="directory for the code objects")
     ap.add_argument("--out", help="the JSON record")
@@ -131,6 +167,9 @@ def main():
     a = ap.parse_args()
     if a.emit:
         return emit_modules(a.parent, a.emit)
+    if a.emit_masks:
+        return emit_masks(a.parent, a.emit_masks, *map(int, a.part.split("/")))
+    a.jobs = max(1, min(a.jobs, MAX_JOBS))
     old, new = os.path.join(a.work, "parent"), os.path.join(a.work, "this")
     if not a.compare_only:
         if not os.path.exists(os.path.join(old, "lol_gpu.aot.co")):
@@ -139,6 +178,10 @@ def main():
             compile_modules(os.path.abspath(a.parent), old, a.jobs)
         compile_ahead_of_time(ROOT, new)
         compile_modules(ROOT, new, a.jobs)
+        if a.masks:
+            if not os.path.exists(os.path.join(old, "masks", "mask%03d.co" % (N_MASKS - 1))):
+                compile_masks(os.path.abspath(a.parent), os.path.join(old, "masks"), a.jobs)
+            compile_masks(ROOT, os.path.join(new, "masks"), a.jobs)
 
     def read(d, f):
         with open(os.path.join(d, f), "rb") as fh:
@@ -165,6 +208,23 @@ def main():
                     differing.append(f + ": " + s)
             assert hashlib.sha256(read(old, f[:-3] + ".hip")).digest() == hashlib.sha256(read(new, f[:-3] + ".hip")).digest(), f + ": generated source differs"
             modules.append(rec)
+    masks = []
+    if a.masks:
+        for mask in range(N_MASKS):
+            f = os.path.join("masks", "mask%03d" % mask)
+            src, co = (read(old, f + ".hip"), read(new, f + ".hip")), (read(old, f + ".co"), read(new, f + ".co"))
+            rec = {"mask": mask, "source_sha256_16": sha(src[1]), "loaded_sha256_16": loaded_sha(co[1]),
+                   "equal": src[0] == src[1] and loaded_sha(co[0]) == loaded_sha(co[1])}
+            masks.append(rec)
+            if not rec["equal"]:
+                differing.append(f)
+    # the key of scene4's plain module (lol_gpu_kernel_key of the frames of the flagship workload), by this checkout's library
+    sys.path.insert(0, ROOT)
+    from loltracer_amd import gpu
+    plain = "scene4.compile_offline.fast0.co"
+    keys = {"parent": gpu.code_key(read(old, plain)), "this": gpu.code_key(read(new, plain))}
+    if keys["parent"] != keys["this"]:
+        differing.append(plain + ": code key")
     head = lambda tree: subprocess.run(["git", "-C", tree, "rev-parse", "HEAD"], stdout=subprocess.PIPE, text=True).stdout.strip()
     record = {
         "what": "device code of this change against its parent commit, compared on a machine without a GPU (tools/code_identity.py)",
@@ -175,14 +235,22 @@ def main():
         "modules": [m[0] for m in MODULES], "assume_fast": [0, 1],
         "n_scene_modules": len(modules), "n_ahead_of_time_kernels": sum(u["kernels"] for u in units),
         "identical": not differing, "differing": differing,
+        "scene4_plain_module_code_key": keys,
         "scene_modules": modules, "ahead_of_time_units": units,
     }
+    if a.masks:
+        record["every_mask"] = {"what": "scene4's module for each set of module switches (bit values: include/lol_gpu_diag.h, "
+                                        "lol_gpu_compile_offline_module), assume_fast 0, through lol_gpu_compile_offline_shade in both trees: "
+                                        "SHA-256 of the generated source and of .text + .rodata + .note",
+                                "n": len(masks), "n_equal": sum(m["equal"] for m in masks), "masks": masks}
     if a.out:
         with open(a.out, "w") as fh:
             json.dump(record, fh, indent=1)
             fh.write("\n")
     print("identical" if not differing else "DIFFERING:\n  " + "\n  ".join(differing[:40]))
     print("%d scene modules, %d ahead-of-time kernels" % (len(modules), record["n_ahead_of_time_kernels"]))
+    if a.masks:
+        print("%d of %d masks equal" % (record["every_mask"]["n_equal"], len(masks)))
     return 1 if differing else 0
 
 
