@@ -735,6 +735,54 @@ int  lol_gpu_shade_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 int  lol_gpu_set_shade_queries(lol_gpu* ctx, int enable);
 int  lol_gpu_shade_queries(const lol_gpu* ctx);
 
+/*
+ * Scene views: a batch whose every view brings its own SCENE — the frames of an animation in one launch, a moving object blurred over
+ * its exposure.  The modes above vary the pixel's area, the camera and the ray; this one varies the numbers of the scene: where its
+ * objects are and how large, its smoothness constants, lights, materials and ambient colour — everything but its structure.
+ * `cams` and `scenes` are HOST memory and hold n_views * K entries each, K = cams_per_view in {1, 2, 4, 8, 16}; both, and the tables
+ * the programs point to, are copied before the call returns.  Record r = v * K + k is one camera and one scene.
+ * Record r is EXACTLY the frame that a context with this context's settings — the pixel format, lol_gpu_set_exact_skips and
+ * lol_gpu_set_cull — renders under cams[r] after lol_gpu_upload_program(&scenes[r]).  With K = 1 view v IS that frame: the packed
+ * pixels, rgb, hit_dist, hit_id and steps, addressed and with dense diagnostics as in lol_gpu_render_views.  With K > 1 view v is
+ * lol_gpu_render_views_blend's pixel with sample k taken from record v K + k: the balanced binary32 tree over the K clamped linear
+ * colours, the factor 1 / K, gamma and packing are unchanged; rgb is the mean after gamma; hit_dist, hit_id and steps are refused
+ * (LOL_GPU_ERR_UNSUPPORTED) as for any blend.
+ * Every scene must have the uploaded program's STRUCTURE: equal n_ops, n_lights, n_materials, n_roots and max_stack, and equal
+ * ops[i].op and ops[i].id for every i.  Everything else may differ per record — every f[] of every op, lights, materials,
+ * root_material, ambient_color — and nothing about the numbers is assumed: a NaN centre in one record is that record's business alone.
+ * Everything an upload or a frame decides from the program or the camera is decided per record, from that record's own scene and
+ * camera: the three exact skips, whether the scene is finite (which of the interpreter's two lists runs), the primary march's first
+ * step, what a camera beyond the sane range switches off.  No proof runs on the device during the call: a smoothness constant the
+ * upload did not prove takes the plain sminf — same bits.
+ * The context's own scene, kernels, lol_gpu_kernel_key, tile-order state, sample settings and the record rings of the other batches
+ * are neither read nor changed: a frame after the call is the frame it would have been.
+ * Asynchronous on `stream` like lol_gpu_render_views: one copy of the records and their data (each record's macro-op lists where the
+ * interpreter renders, its tables, its numbers) and, with K = 1, one launch; a blend adds lol_gpu_render_views_blend's resolve pass
+ * and takes its scratch from that call's ring of 4 sets.  The records and their data go through a ring of 8 sets of their own that
+ * grow on demand, under the rules of lol_gpu_render_views' ring (HIP's special stream handles included).
+ * Refused, with nothing launched and nothing written: a scene whose structure differs, a NULL table that a count speaks of, a
+ * root_material out of range, K outside {1, 2, 4, 8, 16} — LOL_GPU_ERR_ARG; everything lol_gpu_render_views_blend refuses, with
+ * n_views * K <= LOL_GPU_MAX_VIEWS; no program — LOL_GPU_ERR_NO_PROGRAM; an allocation that fails — LOL_GPU_ERR_HIP, and the context
+ * stays usable.
+ * Which kernel: after lol_gpu_set_scene_views(ctx, 1) BEFORE lol_gpu_upload_program, with specialisation on and a program of at most
+ * 256 ops, the scene compiler also makes the STRUCTURE MODULE behind the scene's own: the scene's SDF as straight-line code
+ * specialised on the structure alone, every number read from the record (lol_render_param_batch, lol_render_param_batch_lin) —
+ * objects in file order, no culling, no proven shortcut.  A code object of its own, not a switch of the scene's module: that module
+ * and lol_gpu_kernel_key are what they are without the setter, and all scenes of one structure share the structure module in the
+ * code-object cache.  lol_gpu_specialize_wait waits for it too.  Otherwise, until it is loaded, or if it failed, the interpreter's
+ * render_interp_scene_batch / render_interp_scene_batch_lin render on each record's own lists — same bits either way
+ * (lol_gpu_scene_views_kernel_name, lol_gpu_scene_views_state: lol_gpu_diag.h).  Opt-in, and not the default for a reason: on the one scene
+ * measured (scene4) the interpreter with the upload's proven fast paths was the faster of the two (README.md quotes the numbers).
+ * Out of scope: supersampled and adaptive forms, ray and shading queries over per-record scenes, row partitions, lol_gpu_multi_*
+ * forms, host surfaces and the renderer.h protocol; and the structure module is not kept across uploads of the same structure
+ * (each upload loads it anew, from the cache).
+ */
+int  lol_gpu_render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views, int cams_per_view,
+                                int w, int h, int max_steps, void* dst, size_t pitch_bytes, size_t view_stride_bytes,
+                                const lol_gpu_debug* dbg, void* stream);
+int  lol_gpu_set_scene_views(lol_gpu* ctx, int enable);   /* before lol_gpu_upload_program */
+int  lol_gpu_scene_views(const lol_gpu* ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,21 @@ const char* lol_gpu_view_blend_kernel_name(const lol_gpu* ctx, int cams_per_view
  * launches, decided by the test the launch itself makes: "lol_render_spec_batch_aa_lin" / "render_interp_batch_aa_lin";
  * lol_gpu_view_blend_kernel_name's for samples <= 1, lol_gpu_view_samples_kernel_name's (contrast -1) for cams_per_view <= 1. */
 const char* lol_gpu_view_blend_samples_kernel_name(const lol_gpu* ctx, int cams_per_view, int samples);
+/* ... and of lol_gpu_render_scene_views(..., cams_per_view, ...): "lol_render_param_batch" / "lol_render_param_batch_lin" (the structure
+ * module) or "render_interp_scene_batch" / "render_interp_scene_batch_lin" (the interpreter on each record's own lists) */
+const char* lol_gpu_scene_views_kernel_name(const lol_gpu* ctx, int cams_per_view);
+/* The structure module of the uploaded program: 0 none (no lol_gpu_set_scene_views before the upload, specialisation off, or more than
+ * 256 ops), 1 being compiled (or compiled and not yet loaded: the next batch or lol_gpu_specialize_wait loads it), 2 in use, -1 failed
+ * (the interpreter's kernels render; the reason goes to stderr once). */
+int         lol_gpu_scene_views_state(const lol_gpu* ctx);
+/* What the last upload proved on the device for the INTERPRETER's kernels, which is also what the lists of scene views are built with:
+ * the sqrt kind its kernels are instantiated with (0 plain sqrtf, 3 sqrt_r2), how many of the program's smoothness constants have a
+ * proven fast blend factor, and how many of those also without v_div_fixup.  All 0 with lol_gpu_set_specialize(ctx, 0) or 3 (plain
+ * arithmetic) and before any upload. */
+int         lol_gpu_interp_fast_paths(const lol_gpu* ctx, int* sqrt_kind, unsigned* n_div, unsigned* n_div_no_fixup);
+/* No device needed: the structure module of `prog` — `<out_base>.hip` (source that depends on the program's structure alone: two
+ * programs of one structure give the same bytes) and `<out_base>.co`. */
+int         lol_gpu_compile_offline_scene_views(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap);
 /* The kernel the NEXT lol_gpu_render_views_samples(..., samples, contrast, ...) of this context launches, decided by the test the
  * launch itself makes: "lol_render_spec_batch_aa" / "render_interp_batch_aa" for contrast = -1, the refine pass's
  * "lol_render_spec_batch_aa_list" / "render_interp_batch_aa_list" for an adaptive batch, lol_gpu_render_views' for samples = 1.

@@ -114,6 +114,10 @@ int  lol_scene_parse_file  (const char* path, lol_scene** out, char* errbuf, siz
 int  lol_scene_parse_string(const char* text, size_t len, lol_scene** out, char* errbuf, size_t errcap);
 void lol_scene_free(lol_scene* scene);
 
+/* A deep copy of `scene` in *out (free with lol_scene_free): equal counts and equal bytes in every table.  LOL_ERR_NOMEM when memory
+ * runs out, LOL_ERR_IO for a NULL `scene` or `out` (what the parsers answer a NULL argument with); *out is then NULL. */
+int  lol_scene_clone(const lol_scene* scene, lol_scene** out);
+
 /* scene_new() defaults: no objects, camera at origin looking +z, fov pi/2 (scene.c:44-58). */
 lol_scene* lol_scene_new(void);
 

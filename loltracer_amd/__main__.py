@@ -1,6 +1,7 @@
 """python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N] [--samples N]
                           [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]] [--orbit-shutter K]]
                           [--lens R (--focus D | --focus-at X,Y) --lens-samples K] [--pick X,Y] [--panorama WxH -o FILE.ppm]
+                          [--tween B.lol --frames N [--tween-shutter K] -o DIR]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
@@ -14,7 +15,11 @@ scene.lens_cameras on a lens of radius R focused at distance D; with --samples S
 (X, Y) shows (one Renderer.pick; refused when that ray escapes).  --pick X,Y prints the object id, distance, step count and normal
 under pixel (X, Y) of the --size frame (one ray, Renderer.pick); no frame is rendered unless -o is also given.  --panorama WxH
 writes the equirectangular image of everything round the camera's position: the rays of scene.panorama_rays shaded by ONE shading
-query (Renderer.shade_rays_into) — rays of the host's own making, the reference's colours.  There is no CPU rendering path."""
+query (Renderer.shade_rays_into) — rays of the host's own making, the reference's colours.  A.lol --tween B.lol --frames N renders
+the N frames of an animation from scene A to scene B (same structure, other numbers: scene.tween) in ONE launch, every frame under a
+scene of its own (Renderer.render_scene_views_into), and writes DIR/frame_0000.ppm ...; with --tween-shutter K each frame is the mean
+in linear light of K scenes spread over its exposure (scene.shutter_times): objects that move are blurred.  The camera is A's.
+There is no CPU rendering path."""
 from __future__ import annotations
 
 import argparse
@@ -68,6 +73,43 @@ def orbit(sc, args, w, h) -> int:
     os.makedirs(args.out, exist_ok=True)
     for v in range(k):
         write_ppm(os.path.join(args.out, f"view_{v:04d}.ppm"), views[v])
+    return 0
+
+
+def tween_frames(sc, args, w, h) -> int:
+    """N frames from scene A to scene B in one launch into N PPMs"""
+    try:
+        other = S.Scene.parse_file(args.tween)
+    except S.SceneError as e:
+        print(e.message, file=sys.stderr)
+        return 1
+    if not S.same_structure(sc, other):
+        print("--tween: the two scenes differ in structure (objects, their nesting, lights or materials)", file=sys.stderr)
+        return 1
+    n, k = args.frames, args.tween_shutter
+    scenes = [S.tween(sc, other, t) for f in range(n) for t in S.shutter_times(f, n, k)]
+    r = gpu.Renderer(args.device)
+    try:
+        # (no set_scene_views: the interpreter's kernels with the upload's proven fast paths were the faster route where both were
+        # measured, DESIGN.md 3.18; a host whose scenes gain from the structure module sets it before prepare())
+        r.prepare(sc)
+        frames = np.zeros((n, h, w), dtype=np.uint32)
+        dev = r.malloc(frames.nbytes)
+        try:
+            t0 = time.perf_counter()
+            r.render_scene_views_into(dev, [sc.camera] * len(scenes), scenes, w, h, k, args.max_steps)
+            r.sync()
+            dt = (time.perf_counter() - t0) * 1e3
+            r.memcpy_d2h(frames.ctypes.data, dev, frames.nbytes)
+            name = r.scene_views_kernel_name(k)
+        finally:
+            r.free(dev)
+    finally:
+        r.close()
+    print(f"{n} frames of {w}x{h} over {k} scene(s) each: {dt:.3f}ms  {n * w * h / dt / 1e3:.1f} Mpixels/s  [{name}]")
+    os.makedirs(args.out, exist_ok=True)
+    for f in range(n):
+        write_ppm(os.path.join(args.out, f"frame_{f:04d}.ppm"), frames[f])
     return 0
 
 
@@ -193,6 +235,10 @@ def main(argv=None) -> int:
                     help="print object id, distance, steps and normal under pixel X,Y of the --size frame; no frame unless -o is given")
     ap.add_argument("--panorama", default=None, metavar="WxH",
                     help="the equirectangular image round the camera's position, WxH pixels, through one shading query; -o names the PPM")
+    ap.add_argument("--tween", default=None, metavar="B.lol",
+                    help="with --frames N and -o DIR: N frames from this scene to B.lol (same structure) in one launch")
+    ap.add_argument("--tween-shutter", type=int, default=1, choices=(1, 2, 4, 8, 16), metavar="K",
+                    help="with --tween: every frame is the mean of K scenes of its own exposure (motion blur of moving objects)")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     for name, text in (("--pick", args.pick), ("--focus-at", args.focus_at)):
@@ -210,6 +256,16 @@ def main(argv=None) -> int:
     if not sc.validate_materials():
         print("scene_validate_materials failed", file=sys.stderr)
         return 1
+    if args.tween_shutter != 1 and not args.tween:
+        print("--tween-shutter goes with --tween B.lol", file=sys.stderr)
+        return 1
+    if args.tween:
+        if (args.panorama or args.orbit or args.lens or args.pick or args.samples != 1 or args.adaptive != -1 or not args.out
+                or args.frames < 1 or args.frames * args.tween_shutter > gpu.MAX_VIEWS):
+            print(f"--tween B.lol takes --frames N (N K <= {gpu.MAX_VIEWS} scenes with --tween-shutter K) and -o DIR; not with "
+                  "--panorama, --orbit, --lens, --pick, --samples or --adaptive", file=sys.stderr)
+            return 1
+        return tween_frames(sc, args, w, h)
     if args.panorama:
         if args.orbit or args.lens or args.pick or args.samples != 1 or args.adaptive != -1 or args.frames != 1:
             print("--panorama does not go with --orbit, --lens, --pick, --samples, --adaptive or --frames", file=sys.stderr)

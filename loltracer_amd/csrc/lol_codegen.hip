@@ -7,7 +7,7 @@
 #include "lol_gpu_internal.h"
 #include "lol_code_key.h"
 
-/* the text of the seven lol_kernel*.h files, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
+/* the text of the lol_kernel*.h files, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
 #include "lol_kernel_src.inc"
 
 #pragma GCC visibility push(hidden)
@@ -496,10 +496,18 @@ bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, 
  * as the post-order program; the objects themselves in the order of `plan` (file order when culling is off).
  * out_of_line: the body becomes ONE real function (`<name>_fn`, __noinline__) that the march, normal and shadow
  * loops call, instead of being inlined into each of them — for large scenes, whose straight-line SDF would
- * otherwise be replicated six times (three loops x fast / exact) and outgrow the instruction cache. */
+ * otherwise be replicated six times (three loops x fast / exact) and outgrow the instruction cache.
+ * `param` (the structure module, generate_structure_source: fast == nullptr, an empty plan, inlined): every number of the scene is
+ * not a literal but a read K[7 i + j] of op i's f[j] through the member pointer K — the source then depends on the structure alone. */
 void emit_sdf(std::string& s, const lol_program& P, const char* name, const FastPaths* fast, bool out_of_line,
-              const std::vector<RootBound>& roots, const CullPlan& plan, const std::string& occupancy) {
+              const std::vector<RootBound>& roots, const CullPlan& plan, const std::string& occupancy, bool param = false) {
 	char line[768];
+	auto num = [&](uint32_t i, int j) -> std::string {
+		if (!param) return fbits(P.ops[i].f[j]);
+		char b[32];
+		snprintf(b, sizeof b, "K[%u]", (unsigned)lol::OP_NUMBERS * i + (unsigned)j);
+		return b;
+	};
 	const int fsqrt = fast ? fast->sqrt_kind : 0;
 	char fs[32] = "";
 	if (fsqrt) snprintf(fs, sizeof fs, "_fast<%d>", fsqrt);
@@ -546,6 +554,7 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 		         "\t__device__ __forceinline__ void loop_done() { %s%s }\n", name, fast ? "true" : "false", P.n_roots >= 3 ? "true" : "false", cool_decl,
 		         carry_decl.c_str(), plan.intervals.empty() ? "" : "cool[0] = 0u;", carry ? " lb = -__builtin_inff(); carry = false;" : "");
 		s += line;
+		if (param) s += "\tparam_ptr K = nullptr;\n";
 	}
 	/* The body twice where it is inlined: eval() — distance and object id — for the primary march and the normal taps, and
 	 * eval_dist() — the distance alone — for the shadow marches, which never look at the id.  There an object joins the running
@@ -703,17 +712,17 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 					object_has_nr = true;
 				} else
 				snprintf(line, sizeof line, "\t\tconst float t%d = sd_sphere%s(p, %s, %s, %s, %s%s);\n", t, fs,
-				         fbits(o.f[0]).c_str(), fbits(o.f[1]).c_str(), fbits(o.f[2]).c_str(), fbits(o.f[3]).c_str(),
+				         num(n.op, 0).c_str(), num(n.op, 1).c_str(), num(n.op, 2).c_str(), num(n.op, 3).c_str(),
 				         fsqrt ? ", rg" : "");
 				s += line; return t++;
 			case LOL_OP_RBOX:
 				snprintf(line, sizeof line, "\t\tconst float t%d = sd_round_box%s(p, %s, %s, %s, %s, %s, %s, %s%s);\n", t,
 				         fs,
-				         fbits(o.f[0]).c_str(), fbits(o.f[1]).c_str(), fbits(o.f[2]).c_str(), fbits(o.f[3]).c_str(),
-				         fbits(o.f[4]).c_str(), fbits(o.f[5]).c_str(), fbits(o.f[6]).c_str(), fsqrt ? ", rg" : "");
+				         num(n.op, 0).c_str(), num(n.op, 1).c_str(), num(n.op, 2).c_str(), num(n.op, 3).c_str(),
+				         num(n.op, 4).c_str(), num(n.op, 5).c_str(), num(n.op, 6).c_str(), fsqrt ? ", rg" : "");
 				s += line; return t++;
 			case LOL_OP_PLANE:
-				snprintf(line, sizeof line, "\t\tconst float t%d = p.y - %s;\n", t, fbits(o.f[0]).c_str());
+				snprintf(line, sizeof line, "\t\tconst float t%d = p.y - %s;\n", t, num(n.op, 0).c_str());
 				s += line; return t++;
 			default: break;
 			}
@@ -727,7 +736,7 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 			/* the arithmetic shortcut only where the SDF is inlined: in the out-of-line function its four-way branching
 			 * costs more than it saves (504-op chain: 100 -> 42 Mpixels/s) */
 			const bool sat_arith = !out_of_line && ks > 0.f;
-			const std::string kk = fbits(o.f[0]), k2 = fbits(2.0f * o.f[0]), hrk = fbits(0.5f * (1.0f / o.f[0])), kss = fbits(ks);
+			const std::string kk = num(n.op, 0), k2 = fbits(2.0f * o.f[0]), hrk = fbits(0.5f * (1.0f / o.f[0])), kss = fbits(ks);
 			if (proven && ks > 0.f && sat_cull_min_prims > 0 && nodes[n.a].bound.ok && nodes[n.a].prims >= (uint32_t)sat_cull_min_prims) {
 				const int b = emit_node(n.b);
 				const CullTest ct = make_test(nodes[n.a].bound);
@@ -1098,13 +1107,11 @@ bool has_return_clobbering_branch(const void* data, size_t n_bytes) {
 }
 bool has_return_clobbering_branch(const std::vector<char>& code) { return has_return_clobbering_branch(code.data(), code.size()); }
 
-/* hipRTC: generated source + lol_kernel.h → code object for `arch`.  Needs no device. */
-bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
-                  std::string& log, std::string* src_out, bool cull, int form, ModuleKernels carries) {
-	std::string src = generate_source(P, fast, cull, form, carries);
-	if (src_out) *src_out = src;
-	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
-		if (FILE* f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
+/* `src` → code object.  out_of_line: the source holds an out-of-line SDF function (what the refusal after dropped options is about).
+ * structure: the source is a structure module's (generate_structure_source), which is handed lol_kernel_scenes.h as well — a scene
+ * module is handed exactly the headers it always was, so what the compiler makes of it does not change. */
+static bool compile_source(const std::string& src, bool out_of_line, bool structure, const std::string& arch, std::vector<char>& code,
+                           std::string& log) {
 	int rtc_major = 0, rtc_minor = 0;
 	(void)hiprtcVersion(&rtc_major, &rtc_minor);
 	/* the option list first: it is part of the cache key (a changed flag — -ffp-contract above all — must never be served
@@ -1169,7 +1176,12 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	                                         "lol_kernel_blend.h", "lol_kernel_blend_aa.h", "lol_kernel_rays.h", "lol_kernel_shade.h" };
 	constexpr int n_hdr = 8;                            /* every module is handed all of them: what it does not #include is never parsed */
 	static const std::string all_headers = [] { std::string t; for (const char* h : hdr_src) { t += '|'; t += h; } return t; }();
-	const std::string disk_key = key + all_headers;
+	const char* use_src[n_hdr + 1];
+	const char* use_name[n_hdr + 1];
+	for (int i = 0; i < n_hdr; i++) { use_src[i] = hdr_src[i]; use_name[i] = hdr_name[i]; }
+	use_src[n_hdr] = LOL_KERNEL_SCENES_H_TEXT; use_name[n_hdr] = "lol_kernel_scenes.h";
+	const int n_use = structure ? n_hdr + 1 : n_hdr;
+	const std::string disk_key = key + all_headers + (structure ? std::string("|") + LOL_KERNEL_SCENES_H_TEXT : std::string());
 	if (disk_cache_load(disk_key, code)) {
 		std::lock_guard<std::mutex> lock(g_cache_mutex);
 		g_code_cache[key] = code;
@@ -1177,7 +1189,7 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 		return true;
 	}
 	hiprtcProgram prog = nullptr;
-	if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_hdr, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
+	if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_use, use_src, use_name) != HIPRTC_SUCCESS) {
 		log = "hiprtcCreateProgram failed";
 		return false;
 	}
@@ -1198,7 +1210,7 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 			options_dropped = true;
 			hiprtcDestroyProgram(&prog);
 			prog = nullptr;
-			if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_hdr, hdr_src, hdr_name) != HIPRTC_SUCCESS) {
+			if (hiprtcCreateProgram(&prog, src.c_str(), "lol_render_spec.hip", n_use, use_src, use_name) != HIPRTC_SUCCESS) {
 				log = "hiprtcCreateProgram failed";
 				return false;
 			}
@@ -1226,7 +1238,7 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 		code.clear();
 		return false;
 	}
-	if (options_dropped && spec_out_of_line(P, form)) {
+	if (options_dropped && out_of_line) {
 		/* The retry above also dropped -amdgpu-long-branch-factor=0, the option that KEEPS the compiler from that bug, and an
 		 * out-of-line SDF is where it bites (a function beyond s_cbranch's reach).  The pattern check would be all that is left
 		 * between this code object and a launch that never ends: not enough — the interpreter renders this scene. */
@@ -1241,6 +1253,50 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	}
 	if (!options_dropped) disk_cache_store(disk_key, code);
 	return true;
+}
+
+/* hipRTC: generated source + lol_kernel.h → code object for `arch`.  Needs no device. */
+bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string& arch, std::vector<char>& code,
+                  std::string& log, std::string* src_out, bool cull, int form, ModuleKernels carries) {
+	std::string src = generate_source(P, fast, cull, form, carries);
+	if (src_out) *src_out = src;
+	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
+		if (FILE* f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
+	return compile_source(src, spec_out_of_line(P, form), false, arch, code, log);
+}
+
+/* The structure module (lol_kernel_scenes.h; lol_gpu_render_scene_views): the scene's SDF emitted ONCE — no fast form, no culling plan,
+ * inlined, objects in file order —, every number a read K[7 i + j] through a member pointer in the constant address space, so the numbers
+ * arrive by scalar loads and feed the VALU as SGPR operands while the SDF stays straight-line code.  Nothing of the text depends on a
+ * number of `P`: all scenes of one structure share the source, the code object and its place in the disk cache.  Two kernels:
+ * lol_render_param_batch (counts steps: it serves a batch with or without lol_gpu_debug::steps) and lol_render_param_batch_lin. */
+std::string generate_structure_source(const lol_program& P) {
+	std::string s = "#include \"lol_kernel_scenes.h\"\nnamespace lol {\n";
+	const std::vector<RootBound> roots = analyse_roots(P);
+	const CullPlan plan = plan_culling(roots, false);        /* file order, no test */
+	const int waves_lo = P.n_ops <= 32 ? 8 : P.n_ops <= 96 ? 6 : 4, waves_hi = 8;      /* (generate_source: the register budget) */
+	const std::string occupancy = " __attribute__((amdgpu_waves_per_eu(" + std::to_string(waves_lo) + ", " + std::to_string(waves_hi) + ")))";
+	emit_sdf(s, P, "ParamSdf", nullptr, false, roots, plan, occupancy, true);
+	s += "}  // namespace lol\n";
+	const bool tables_global = !lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots);
+	const std::string tg = tables_global ? "true" : "false";
+	s += "template <bool LIN> __device__ __forceinline__ void lol_param_body(const lol::Launch& L, const lol::SceneTail& B, lol::u32* lds) {\n";
+	s += "\tconst lol::Launch S = lol::scene_launch(L, B);\n";
+	if (!tables_global) s += "\tlol::stage_common(S, lds);\n\t__syncthreads();\n";
+	s += "\tlol::ParamSdf sdf;\n\tsdf.K = lol::scene_numbers(B);\n";
+	s += "\tconst lol::Pixel P = lol::shade_pixel<lol::ParamSdf, " + tg + ", !LIN>(S, sdf, lds);\n";
+	s += "\tif constexpr (LIN) lol::store_linear_view(L, P.rgb);\n\telse lol::store_pixel_view(L, lol::batch_tail(B), P);\n}\n";
+	const std::string head = "extern \"C\" __global__ __launch_bounds__(lol::BLOCK)" + occupancy + " void ";
+	const std::string tail = "(const lol::Launch L, const lol::SceneTail B) {\n\textern __shared__ lol::u32 lds[];\n\tlol_param_body<";
+	s += head + "lol_render_param_batch" + tail + "false>(L, B, lds);\n}\n";
+	s += head + "lol_render_param_batch_lin" + tail + "true>(L, B, lds);\n}\n";
+	return s;
+}
+
+bool compile_structure(const lol_program& P, const std::string& arch, std::vector<char>& code, std::string& log, std::string* src_out) {
+	const std::string src = generate_structure_source(P);
+	if (src_out) *src_out = src;
+	return compile_source(src, false, true, arch, code, log);
 }
 
 #pragma GCC visibility pop
@@ -1310,6 +1366,31 @@ int lol_gpu_compile_offline_module(const lol_program* prog, const char* arch, co
 		BigStackThread th;
 		auto work = [&]() {
 			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), form, carries); }
+			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
+		};
+		bool started = false;
+		try { started = th.start(work); } catch (...) { started = false; }
+		if (started) th.join(); else work();
+	}
+	if (log && logcap) snprintf(log, logcap, "%s", lg.c_str());
+	if (out_base && out_base[0]) {
+		std::string base = out_base;
+		if (FILE* f = fopen((base + ".hip").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
+		if (ok) if (FILE* f = fopen((base + ".co").c_str(), "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
+	}
+	return ok ? LOL_GPU_OK : LOL_GPU_ERR_UNSUPPORTED;
+}
+
+/* ... and the structure module of `prog` (lol_gpu_set_scene_views): `<out_base>.hip` and `<out_base>.co`; lol_gpu_diag.h */
+int lol_gpu_compile_offline_scene_views(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap) {
+	if (!prog || !arch || prog->n_ops > LOL_MAX_OPS || (prog->n_ops && !prog->ops)) return LOL_GPU_ERR_ARG;
+	std::vector<char> code;
+	std::string lg, src;
+	bool ok = false;
+	{
+		BigStackThread th;
+		auto work = [&]() {
+			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_structure(*prog, arch, code, lg, &src); }
 			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
 		};
 		bool started = false;

@@ -545,6 +545,12 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 		if (S.copied) (void)hipEventDestroy(S.copied);
 		if (S.done) (void)hipEventDestroy(S.done);
 	}
+	for (lol_gpu::SceneViewSet& S : ctx->scene_view_sets) {
+		if (S.d_buf) (void)hipFree(S.d_buf);
+		if (S.h_buf) (void)hipHostFree(S.h_buf);
+		if (S.copied) (void)hipEventDestroy(S.copied);
+		if (S.done) (void)hipEventDestroy(S.done);
+	}
 	if (ctx->d_adaptive_order) (void)hipFree(ctx->d_adaptive_order);
 	if (ctx->d_bad) (void)hipFree(ctx->d_bad);
 	if (ctx->d_gamma) (void)hipFree(ctx->d_gamma);
@@ -681,6 +687,7 @@ static int upload_program(lol_gpu* ctx, const lol_program* prog) {
 		id += "|render_interp_aa";
 		interp_aa_key = fnv_hex(id.data(), id.size());
 	}
+	FastPaths fast_kept = fast;                       /* (may throw: before the commit) */
 	ctx->h_own.assign(*prog);                         /* the last fallible step (host memory; all or nothing itself): the old scene is intact until here */
 	/* commit (nothing below allocates on the way to the new scene being in place) */
 	ctx->generation++;
@@ -692,6 +699,7 @@ static int upload_program(lol_gpu* ctx, const lol_program* prog) {
 	ctx->gamma_table = fast.gamma_ok;
 	ctx->interp_key.swap(interp_key);
 	ctx->interp_aa_key.swap(interp_aa_key);
+	ctx->fast = std::move(fast_kept);
 	resolve_skips(ctx);
 	/* the scene compiler starts on its own thread; the new scene renders on the interpreter until its kernel is there
 	 * (a failed specialisation is not an error either: the interpreter goes on rendering) */
@@ -1245,6 +1253,23 @@ static int blend_refused(lol_gpu* ctx, const lol_frame_camera* cams, int n_views
  * registers before it stores, so the scratch holds one LinearColour per PIXEL and record either way: the ring, grow_scratch and the
  * resolve pass are the same for both.
  */
+/* pass 2 of a blend (blend_resolve) behind pass 1's launch `L`, whose scratch `lin` holds the linear colours [v K + k][y][x] */
+static hipError_t launch_blend_resolve(const lol_gpu* ctx, const lol::Launch& L, const uint32_t* scratch, int n_views, int K, int w, int h, void* dst,
+                                       size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, hipStream_t s) {
+	const BlendOut O = { static_cast<uint32_t*>(dst), (uint32_t)(pitch_bytes / 4), (unsigned long long)(view_stride_bytes / 4),
+	                     ctx->fmt_shift, ctx->fmt_loss, ctx->fmt_amask, L.flags & lol::FLAG_GAMMA_TABLE,
+	                     dbg ? dbg->rgb : nullptr, L.gamma_table };
+	const lol::LinearColour* lin = reinterpret_cast<const lol::LinearColour*>(scratch);
+	const dim3 rgrid((w + CLASSIFY_W - 1) / CLASSIFY_W, (h + CLASSIFY_H - 1) / CLASSIFY_H, n_views);
+	switch (K) {
+	case 2:  hipLaunchKernelGGL(blend_resolve<2>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
+	case 4:  hipLaunchKernelGGL(blend_resolve<4>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
+	case 8:  hipLaunchKernelGGL(blend_resolve<8>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
+	default: hipLaunchKernelGGL(blend_resolve<16>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
+	}
+	return hipGetLastError();
+}
+
 static int render_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int K, int w, int h, int max_steps, int samples,
                         void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
 	if (samples > 1 && !lol::samples_fit_wave(samples))
@@ -1281,18 +1306,7 @@ static int render_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views,
 	/* 2. the means */
 	if (e == hipSuccess) {
 		what = "kernel launch (blend of views, resolve pass)";
-		const BlendOut O = { static_cast<uint32_t*>(dst), (uint32_t)(pitch_bytes / 4), (unsigned long long)(view_stride_bytes / 4),
-		                     ctx->fmt_shift, ctx->fmt_loss, ctx->fmt_amask, L.flags & lol::FLAG_GAMMA_TABLE,
-		                     dbg ? dbg->rgb : nullptr, L.gamma_table };
-		const lol::LinearColour* lin = reinterpret_cast<const lol::LinearColour*>(S.d_buf);
-		const dim3 rgrid((w + CLASSIFY_W - 1) / CLASSIFY_W, (h + CLASSIFY_H - 1) / CLASSIFY_H, n_views);
-		switch (K) {
-		case 2:  hipLaunchKernelGGL(blend_resolve<2>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
-		case 4:  hipLaunchKernelGGL(blend_resolve<4>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
-		case 8:  hipLaunchKernelGGL(blend_resolve<8>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
-		default: hipLaunchKernelGGL(blend_resolve<16>, rgrid, dim3(64), 0, s, lin, w, h, O); break;
-		}
-		e = hipGetLastError();
+		e = launch_blend_resolve(ctx, L, S.d_buf, n_views, K, w, h, dst, pitch_bytes, view_stride_bytes, dbg, s);
 	}
 	if (g_roctx.pop) g_roctx.pop();
 	/* (recorded even behind a failed launch, like the view records' event and for the same reason) */
@@ -1915,4 +1929,239 @@ const char* lol_gpu_shade_kernel_name(const lol_gpu* ctx) {
 	if (!ctx) return "";
 	return shade_kernel(ctx) ? "lol_shade_spec" : "shade_interp";
 }
+}  // extern "C"
+
+/*
+ * Scene views (lol_gpu_render_scene_views): a batch whose every record brings a camera AND a scene of the uploaded program's
+ * structure (lol_kernel_scenes.h).  Everything an upload decides from the program and a frame from the camera is decided here per
+ * record, from that record's own scene and camera, on the host: the three exact skips, finite_scene (which of its two lists the
+ * record runs), the primary march's first step (host_sdf on that scene), what an insane camera switches off.  No device proof runs:
+ * the lists are built with what the upload proved (lol_gpu::fast), and a smoothness constant it did not prove takes the plain sminf.
+ * One copy — the records and, behind them, every record's lists, tables and numbers — from a ring of sets of their own under
+ * view_sets' rules, and with K = 1 one launch; a blend adds the resolve pass and scratch ring of lol_gpu_render_views_blend.
+ * The context's scene, kernels, keys, tile-order state, sample settings and view-record ring are neither read nor changed.
+ */
+static bool same_structure(const lol_program& A, const lol_program& B) {
+	if (A.n_ops != B.n_ops || A.n_lights != B.n_lights || A.n_materials != B.n_materials || A.n_roots != B.n_roots || A.max_stack != B.max_stack)
+		return false;
+	for (uint32_t i = 0; i < A.n_ops; i++)
+		if (A.ops[i].op != B.ops[i].op || A.ops[i].id != B.ops[i].id) return false;
+	return true;
+}
+
+/* the address of the interpreter's scene-view kernel for one stack class, sqrt kind and table placement */
+template <int SSIZE, int KIND, bool TABLES_GLOBAL>
+static const void* scene_interp_kernel(bool lin) {
+	return lin ? reinterpret_cast<const void*>(&lol::render_interp_scene_batch_lin<SSIZE, KIND, TABLES_GLOBAL>)
+	           : reinterpret_cast<const void*>(&lol::render_interp_scene_batch<SSIZE, KIND, TABLES_GLOBAL>);
+}
+
+/* ONE launch over the records: the structure module's kernel where it is loaded, else the interpreter's instantiation for the
+ * program's rung (the structure's: every record has it).  `args`: (L, B) for both. */
+static hipError_t launch_scene_views(const lol_gpu* ctx, bool lin, void** args, dim3 grid, hipStream_t s) {
+	const lol_program& P = ctx->h_prog;
+	const unsigned lds = lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u;
+	const StructureKernel& k = ctx->tiers.structure;
+	if (k) return hipModuleLaunchKernel(lin ? k.lin : k.batch, grid.x, grid.y, grid.z, lol::BLOCK, 1, 1, lds, s, args, nullptr);
+	const int kind = ctx->interp_sqrt_kind;
+	return interp_dispatch(ctx, [&](auto v) {
+		constexpr int ssize = decltype(v)::ssize;
+		constexpr bool tables_global = decltype(v)::tables_global;
+		const void* fn = kind == 3 ? scene_interp_kernel<ssize, 3, tables_global>(lin) : scene_interp_kernel<ssize, 0, tables_global>(lin);
+		return hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	});
+}
+
+/* the records of a call and their data, on the host: SceneView r and, in `data`, what its offsets point to (each part on a multiple
+ * of four dwords: the macro-op records want 16 bytes).  `lists`: the interpreter renders, so every record needs its pair of lists. */
+static int build_scene_records(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n, int max_steps, bool lists,
+                               std::vector<lol::SceneView>& views, std::vector<uint32_t>& data) {
+	views.resize((size_t)n);
+	data.clear();
+	std::vector<float> stack;
+	std::vector<uint32_t> mops;
+	auto align = [&]() { data.resize((data.size() + 3u) & ~(size_t)3u, 0u); };
+	const bool cull = culling_enabled(ctx->want_cull);
+	for (int r = 0; r < n; r++) {
+		const lol_program& P = scenes[r];
+		const lol_frame_camera& cam = cams[r];
+		lol::SceneView& V = views[(size_t)r];
+		memset(&V, 0, sizeof V);
+		memcpy(&V.cam, &cam, sizeof V.cam);
+		const bool sane = camera_sane(cam), finite = shadow_settle_ok(P);
+		const unsigned want = ctx->want_skips;
+		V.flags = ((want & 1u) && miss_skip_ok(P) ? lol::FLAG_MISS_SKIP : 0u) | ((want & 2u) && dark_skip_ok(P) ? lol::FLAG_DARK_SKIP : 0u) |
+		          ((want & 4u) && finite && sane ? lol::FLAG_SHADOW_SETTLED : 0u);
+		/* the first step (first_step, on this record's scene): a sane camera, no negative zero in its origin, a value in [EPSILON, MAX_DIST] */
+		if (max_steps >= 1 && sane) {
+			const float origin[3] = { cam.origin.x, cam.origin.y, cam.origin.z };
+			uint32_t bits[3];
+			memcpy(bits, origin, sizeof bits);
+			float d = 0.f; uint32_t id = 0;
+			if (bits[0] != 0x80000000u && bits[1] != 0x80000000u && bits[2] != 0x80000000u && host_sdf(P, origin, stack, &d, &id) &&
+			    d >= 0.001f && d <= 100.f) { V.flags |= lol::FLAG_FIRST_STEP; V.first_dist = d; V.first_id = id; }
+		}
+		V.ambient[0] = P.ambient_color.x; V.ambient[1] = P.ambient_color.y; V.ambient[2] = P.ambient_color.z;
+		if (lists) {
+			uint32_t n_mops = 0;
+			if (!build_interp_lists(P, ctx->fast, cull, mops, n_mops)) return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "interpreter lists differ in length");
+			align();
+			V.n_mops = n_mops;
+			V.ops_offset = (uint32_t)data.size() + (finite && sane ? n_mops * (uint32_t)lol::MOP_DWORDS : 0u);
+			data.insert(data.end(), mops.begin(), mops.end());
+		}
+		align();
+		V.tables_offset = (uint32_t)data.size();
+		const size_t nt = lol::table_dwords(P.n_lights, P.n_materials, P.n_roots);
+		data.resize(data.size() + nt);
+		{
+			uint32_t* t = data.data() + V.tables_offset;
+			if (P.n_lights) memcpy(t, P.lights, (size_t)P.n_lights * sizeof(lol_light));
+			t += (size_t)P.n_lights * lol::LIGHT_DWORDS;
+			memcpy(t, P.materials, (size_t)P.n_materials * sizeof(lol_material));
+			t += (size_t)P.n_materials * lol::MATERIAL_DWORDS;
+			if (P.n_roots) memcpy(t, P.root_material, (size_t)P.n_roots * 4);
+		}
+		align();
+		V.nums_offset = (uint32_t)data.size();
+		data.resize(data.size() + (size_t)P.n_ops * lol::OP_NUMBERS);
+		for (uint32_t i = 0; i < P.n_ops; i++) memcpy(data.data() + V.nums_offset + (size_t)i * lol::OP_NUMBERS, P.ops[i].f, sizeof P.ops[i].f);
+		if (data.size() > 0x7FFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "the scenes of one call hold more than 2^31 dwords: fewer views per call");
+	}
+	align();
+	return LOL_GPU_OK;
+}
+
+/* the next set of the ring filled with the records and their data, and its copy to the device queued on `s` (queue_view_records) */
+static int queue_scene_records(lol_gpu* ctx, const std::vector<lol::SceneView>& views, const std::vector<uint32_t>& data, hipStream_t s,
+                               lol_gpu::SceneViewSet** out) {
+	lol_gpu::SceneViewSet& S = ctx->scene_view_sets[ctx->scene_view_rr++ % lol_gpu::SCENE_VIEW_SETS];
+	if (!S.copied) LOL_HIP(ctx, hipEventCreateWithFlags(&S.copied, hipEventDisableTiming));
+	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+	const size_t head = views.size() * lol::SCENE_VIEW_DWORDS, need = head + data.size();
+	if (need > S.cap) {
+		if (S.used) LOL_HIP(ctx, hipEventSynchronize(S.done));
+		if (S.d_buf) (void)hipFree(S.d_buf);
+		if (S.h_buf) (void)hipHostFree(S.h_buf);
+		S.d_buf = nullptr; S.h_buf = nullptr; S.cap = 0; S.used = false;
+		const size_t want = std::max<size_t>(4096, need + need / 2);
+		hipError_t me = hipMalloc(reinterpret_cast<void**>(&S.d_buf), want * 4);
+		if (me == hipSuccess) me = hipHostMalloc(reinterpret_cast<void**>(&S.h_buf), want * 4, hipHostMallocDefault);
+		if (me != hipSuccess) {
+			if (S.d_buf) (void)hipFree(S.d_buf);
+			S.d_buf = nullptr; S.h_buf = nullptr;
+			(void)hipGetLastError();
+			return fail(ctx, LOL_GPU_ERR_HIP, "records of a batch of scene views", me);
+		}
+		S.cap = want;
+	}
+	if (S.used) {
+		LOL_HIP(ctx, hipEventSynchronize(S.copied));
+		LOL_TRY(wait_on_stream(ctx, s, S.done));
+	}
+	memcpy(S.h_buf, views.data(), head * 4);
+	if (!data.empty()) memcpy(S.h_buf + head, data.data(), data.size() * 4);
+	LOL_HIP(ctx, hipMemcpyAsync(S.d_buf, S.h_buf, need * 4, hipMemcpyHostToDevice, s));
+	LOL_HIP(ctx, hipEventRecord(S.copied, s));
+	*out = &S;
+	return LOL_GPU_OK;
+}
+
+static int render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views, int K, int w, int h,
+                              int max_steps, void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
+	if (!ctx || !cams || !scenes || !dst) return LOL_GPU_ERR_ARG;
+	LOL_TRY(blend_refused(ctx, cams, n_views, K, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
+	const int n = n_views * K;
+	const lol_program& U = ctx->h_prog;
+	for (int r = 0; r < n; r++) {
+		const lol_program& P = scenes[r];
+		if ((P.n_ops && !P.ops) || (P.n_lights && !P.lights) || !P.materials || (P.n_roots && !P.root_material))
+			return fail(ctx, LOL_GPU_ERR_ARG, "malformed scene of a view: a table is missing");
+		if (P.n_ops != U.n_ops || !same_structure(U, P))
+			return fail(ctx, LOL_GPU_ERR_ARG, "a view's scene has not the uploaded program's structure (counts, opcodes, ids)");
+		for (uint32_t i = 0; i < P.n_roots; i++)
+			if (P.root_material[i] >= P.n_materials) return fail(ctx, LOL_GPU_ERR_ARG, "material index out of range in a view's scene");
+	}
+	if (K > 1 && dbg && (dbg->hit_dist || dbg->hit_id || dbg->steps))
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "hit_dist, hit_id and steps have no single value for a pixel averaged over scenes");
+	dim3 grid;
+	if (!batch_grid(ctx, w, h, n, &grid))
+		return fail(ctx, LOL_GPU_ERR_ARG, "batch too large for one launch over all its records: fewer views per call");
+	hipStream_t s;
+	LOL_TRY(batch_stream(ctx, stream, &s));              /* (the frame boundary: a structure module that has finished is loaded here) */
+	std::vector<lol::SceneView> views;
+	std::vector<uint32_t> data;
+	LOL_TRY(build_scene_records(ctx, cams, scenes, n, max_steps, !ctx->tiers.structure, views, data));
+	lol_gpu::BlendSet* scratch = nullptr;
+	if (K > 1) {
+		const int si = (int)(ctx->blend_rr++ % lol_gpu::BLEND_SETS);
+		scratch = &ctx->blend_sets[si];
+		if (!scratch->done) LOL_HIP(ctx, hipEventCreateWithFlags(&scratch->done, hipEventDisableTiming));
+		LOL_TRY(grow_scratch(ctx, *scratch, scratch->done, (size_t)n * (size_t)w * (size_t)h * sizeof(lol::LinearColour), si, ctx->blend_last,
+		                     &ctx->fail_view_scratch, "scratch of a blend of scene views"));
+		if (scratch->used) LOL_TRY(wait_on_stream(ctx, s, scratch->done));
+	}
+	lol_gpu::SceneViewSet* S = nullptr;
+	LOL_TRY(queue_scene_records(ctx, views, data, s, &S));
+	batch_range(K > 1 ? "blend of scene views" : "scene views", n, w, h);
+	lol::Launch L;
+	if (K > 1) batch_launch(ctx, w, h, max_steps, scratch->d_buf, (size_t)w * 4, nullptr, L);
+	else       batch_launch(ctx, w, h, max_steps, dst, pitch_bytes, dbg, L);
+	lol::SceneTail B = { reinterpret_cast<const lol::SceneView*>(S->d_buf), K > 1 ? 0ull : (unsigned long long)(view_stride_bytes / 4),
+	                     S->d_buf + views.size() * lol::SCENE_VIEW_DWORDS };
+	void* args[] = { &L, &B };
+	const char* what = "kernel launch (scene views)";
+	hipError_t e = launch_scene_views(ctx, K > 1, args, grid, s);
+	if (e == hipSuccess && K > 1) {
+		what = "kernel launch (blend of scene views, resolve pass)";
+		e = launch_blend_resolve(ctx, L, scratch->d_buf, n_views, K, w, h, dst, pitch_bytes, view_stride_bytes, dbg, s);
+	}
+	if (g_roctx.pop) g_roctx.pop();
+	/* (both events recorded even behind a failed launch: the copy is queued, and the sets' next users must find them recorded) */
+	hipError_t e2 = hipEventRecord(S->done, s);
+	S->used = true;
+	if (scratch) {
+		const hipError_t e3 = hipEventRecord(scratch->done, s);
+		scratch->used = true;
+		if (e2 == hipSuccess) e2 = e3;
+	}
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, what, e);
+	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (scene views)", e2);
+	return LOL_GPU_OK;
+}
+
+extern "C" {
+
+int lol_gpu_render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views, int cams_per_view,
+                               int w, int h, int max_steps, void* dst, size_t pitch_bytes, size_t view_stride_bytes,
+                               const lol_gpu_debug* dbg, void* stream) {
+	try { return render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream); }
+	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a batch"); }
+	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a batch"); }
+}
+
+int lol_gpu_set_scene_views(lol_gpu* ctx, int enable) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	ctx->want_scene_views = enable ? 1 : 0;      /* takes effect at the next lol_gpu_upload_program */
+	return LOL_GPU_OK;
+}
+int lol_gpu_scene_views(const lol_gpu* ctx) { return ctx ? ctx->want_scene_views : LOL_GPU_ERR_ARG; }
+
+const char* lol_gpu_scene_views_kernel_name(const lol_gpu* ctx, int cams_per_view) {
+	if (!ctx) return "";
+	const bool lin = cams_per_view > 1;
+	if (ctx->tiers.structure) return lin ? "lol_render_param_batch_lin" : "lol_render_param_batch";
+	return lin ? "render_interp_scene_batch_lin" : "render_interp_scene_batch";
+}
+
+int lol_gpu_interp_fast_paths(const lol_gpu* ctx, int* sqrt_kind, unsigned* n_div, unsigned* n_div_no_fixup) {
+	if (!ctx || !sqrt_kind || !n_div || !n_div_no_fixup) return LOL_GPU_ERR_ARG;
+	*sqrt_kind = ctx->have_prog ? ctx->interp_sqrt_kind : 0;
+	*n_div = ctx->have_prog ? (unsigned)ctx->fast.div_ok.size() : 0u;
+	*n_div_no_fixup = ctx->have_prog ? (unsigned)ctx->fast.div_nf_ok.size() : 0u;
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_scene_views_state(const lol_gpu* ctx) { return ctx ? ctx->tiers.structure_state : LOL_GPU_ERR_ARG; }
+
 }  // extern "C"

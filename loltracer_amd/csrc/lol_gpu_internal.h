@@ -26,6 +26,7 @@
 #include "lol_kernel_blend_aa.h"
 #include "lol_kernel_rays.h"
 #include "lol_kernel_shade.h"
+#include "lol_kernel_scenes.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -62,6 +63,9 @@ static_assert(sizeof(lol::Launch) % 8 == 0 && offsetof(lol::BatchArgs, B) == siz
               sizeof(lol::BatchArgs) == sizeof(lol::Launch) + sizeof(lol::BatchTail) && sizeof(lol::View) == 18 * 4,
               "kernel-argument layout of the batch kernels");
 /* ... and a shading query's is a Launch and a ShadeQuery behind it (lol_kernel_shade.h, shade_out reads the outputs there) */
+/* ... and a batch of scene views' is a Launch and a SceneTail behind it, which begins like a BatchTail (lol_kernel_scenes.h) */
+static_assert(offsetof(lol::SceneTail, views) == offsetof(lol::BatchTail, views) && offsetof(lol::SceneTail, view_stride_px) == offsetof(lol::BatchTail, view_stride_px),
+              "kernel-argument layout of the scene-view kernels");
 static_assert(offsetof(lol::ShadeArgs, Q) == sizeof(lol::Launch) && sizeof(lol::ShadeArgs) == sizeof(lol::Launch) + sizeof(lol::ShadeQuery),
               "kernel-argument layout of the shading kernels");
 
@@ -216,6 +220,17 @@ struct SceneKernel {
 	void unload() { if (module) (void)hipModuleUnload(module); *this = SceneKernel(); }
 };
 
+/* The structure module (lol_codegen.hip, generate_structure_source): a code object of its own beside the scene's, with its own load,
+ * unload and key — no row of MODULE_SWITCHES.  Both kernels or none. */
+struct StructureKernel {
+	hipModule_t   module = nullptr;
+	hipFunction_t batch = nullptr;             /* lol_render_param_batch (counts steps) */
+	hipFunction_t lin = nullptr;               /* lol_render_param_batch_lin */
+	std::string   key;                         /* code_key_hex of the code object */
+	explicit operator bool() const { return module != nullptr; }
+	void unload() { if (module) (void)hipModuleUnload(module); *this = StructureKernel(); }
+};
+
 struct SpecJob;
 /* The tiers of the scene compiler: interpreter -> [out-of-line kernel ->] scene kernel (lol_tiers.hip) */
 struct SpecTiers {
@@ -234,6 +249,12 @@ struct SpecTiers {
 	                                           * stays loaded until the next upload (which drains the device) or the end of the context */
 	std::vector<std::unique_ptr<SpecJob>> old_jobs;   /* runs for programs since replaced: dropped when they have finished */
 	std::string  log;                         /* lol_gpu_specialize_log */
+	/* the structure module of the uploaded program (lol_gpu_set_scene_views before the upload): compiled by the first run's thread
+	 * after the scene's own module, loaded at the frame boundary or wait that finds it finished */
+	std::unique_ptr<SpecJob> structure_job;   /* that run, from the boundary that took its scene kernel until its structure module is there */
+	StructureKernel structure;                /* empty: the interpreter's scene-view kernels render */
+	int          structure_state = 0;         /* lol_gpu_scene_views_state: 0 none, 1 compiling, 2 in use, -1 failed */
+	std::string  structure_log;
 	double       compile_ms = 0;              /* how long the last finished run took (wall clock of its thread) */
 	/* what the next upload asks for */
 	bool         want = true;                 /* lol_gpu_set_specialize */
@@ -284,6 +305,20 @@ struct lol_gpu {
 	std::string  interp_aa_key;          /* ... and of its supersampling kernel (render_interp_aa) */
 	int          samples = 1;            /* lol_gpu_set_samples: samples per pixel along each axis of the frames launched from now on */
 	int          adaptive = -1;          /* lol_gpu_set_adaptive_samples: the contrast T, or -1 (off) */
+	int          want_scene_views = 0;   /* lol_gpu_set_scene_views: the next upload also compiles the structure module */
+	FastPaths    fast;                   /* what the upload proved on the device: the lists of scene views are built with it */
+	/* The records of scene views and their data (lol_gpu.hip, lol_gpu_render_scene_views): a ring of sets of their own, one per call, under view_sets' rules.
+	 * One buffer per set: the records, and behind them every record's lists, tables and numbers. */
+	struct SceneViewSet {
+		uint32_t*  h_buf = nullptr;          /* pinned */
+		uint32_t*  d_buf = nullptr;
+		size_t     cap = 0;                  /* dwords both hold */
+		hipEvent_t copied = nullptr, done = nullptr;
+		bool       used = false;             /* both events have been recorded */
+	};
+	static constexpr int SCENE_VIEW_SETS = 8;
+	SceneViewSet scene_view_sets[SCENE_VIEW_SETS];
+	unsigned     scene_view_rr = 0;
 	unsigned     module_switches = 0; /* the switch_bit()s set by lol_gpu_set_view_batches ... lol_gpu_set_shade_queries (MODULE_SWITCHES) */
 	void*        d_pick = nullptr;       /* lol_gpu_pick's device memory, from the first pick on: xy [2] | dist | id | steps | normal [3] */
 	/* The view records of batches (lol_gpu_render_views, lol_gpu.hip): a ring of sets, one per batch, whatever its stream.  A batch
@@ -502,6 +537,9 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
                   std::string& log, std::string* src_out = nullptr, bool cull = true, int form = SPEC_BY_SIZE, ModuleKernels carries = {});
 /* the interpreter's two macro-op lists for `P`, one after the other (with / without v_div_fixup in the proven blend factors);
  * false: the two differ in length (cannot happen: same records by construction) */
+/* the structure module of `P`: source that depends on P's structure alone (opcodes, ids, counts), and its code object */
+std::string generate_structure_source(const lol_program& P);
+bool compile_structure(const lol_program& P, const std::string& arch, std::vector<char>& code, std::string& log, std::string* src_out = nullptr);
 bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, std::vector<uint32_t>& lists, uint32_t& n_mops);
 std::string fnv_hex(const void* data, size_t n);
 std::string code_key_hex(const void* code, size_t n);      /* SceneKernel::key: FNV-1a over what the device loads of a code object (lol_code_key.h) */
@@ -516,6 +554,11 @@ void start_specialise(lol_gpu* ctx, const FastPaths& fast);
 bool finish_specialise(lol_gpu* ctx, bool wait);
 /* the scene kernel frames run, or nullptr: the interpreter */
 inline const SceneKernel* scene_kernel(const lol_gpu* ctx) { return ctx->tiers.kernel ? &ctx->tiers.kernel : nullptr; }
+
+/* all or nothing: both kernels of the structure module, or `why` not */
+bool load_structure_kernel(const std::vector<char>& code, StructureKernel& k, std::string& why);
+/* does an upload of `P` on this context compile a structure module? */
+bool structure_module_wanted(const lol_gpu* ctx, const lol_program& P);
 
 /* ---- lol_sched.hip */
 struct FrameTables { const uint32_t* order; uint32_t* cost; const uint32_t* lanes; unsigned short* pixel_cost; uint32_t n_waves; };

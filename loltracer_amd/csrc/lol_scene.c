@@ -523,6 +523,29 @@ void lol_scene_free(lol_scene* s) {
 	free(s);
 }
 
+int lol_scene_clone(const lol_scene* scene, lol_scene** out) {
+	if (out) *out = NULL;
+	if (!scene || !out) return LOL_ERR_IO;
+	lol_scene* c = calloc(1, sizeof *c);
+	if (!c) return LOL_ERR_NOMEM;
+	*c = *scene;
+	c->materials = NULL; c->lights = NULL; c->nodes = NULL; c->roots = NULL;
+	/* (an empty table stays NULL, as in a scene that never had an entry) */
+#define LOL_CLONE_TABLE(field, count)                                                      \
+	if (scene->count) {                                                                    \
+		c->field = malloc(scene->count * sizeof *c->field);                                \
+		if (!c->field) { lol_scene_free(c); return LOL_ERR_NOMEM; }                        \
+		memcpy(c->field, scene->field, scene->count * sizeof *c->field);                   \
+	}
+	LOL_CLONE_TABLE(materials, n_materials)
+	LOL_CLONE_TABLE(lights, n_lights)
+	LOL_CLONE_TABLE(nodes, n_nodes)
+	LOL_CLONE_TABLE(roots, n_roots)
+#undef LOL_CLONE_TABLE
+	*out = c;
+	return LOL_OK;
+}
+
 int lol_scene_parse_string(const char* text, size_t len, lol_scene** out, char* errbuf, size_t errcap) {
 	if (out) *out = NULL;
 	if (errbuf && errcap) errbuf[0] = 0;

@@ -25,6 +25,12 @@ struct SpecJob {
 	bool cull = true;
 	int form = SPEC_BY_SIZE;
 	ModuleKernels carries;             /* what the module holds beside the frame kernel */
+	/* the structure module (lol_gpu_set_scene_views), compiled by this run's thread AFTER the scene's own module: `done` says the
+	 * scene's kernel is there, `structure_done` that this one is (or was not to be had: structure_ok) */
+	bool want_structure = false, structure_done = false, structure_ok = false;
+	std::vector<char> structure_code;
+	std::string structure_log;
+	bool all_done() const { return done && (!want_structure || structure_done); }      /* (under `mu`) */
 	BigStackThread th;
 	/* A run is never left behind: hipRTC cannot be interrupted, and a thread still inside it when the process exits crashes in the
 	 * compiler's own teardown (comgr is loaded on first use, so its statics go BEFORE this library's: with a process-lifetime
@@ -35,6 +41,8 @@ struct SpecJob {
 SpecTiers::SpecTiers() = default;
 SpecTiers::~SpecTiers() {
 	job.reset();
+	structure_job.reset();
+	structure.unload();
 	old_jobs.clear();
 	kernel.unload();
 	retired.unload();
@@ -46,7 +54,7 @@ namespace {
 void reap(std::vector<std::unique_ptr<SpecJob>>& jobs) {
 	jobs.erase(std::remove_if(jobs.begin(), jobs.end(), [](const std::unique_ptr<SpecJob>& j) {
 		std::lock_guard<std::mutex> lock(j->mu);
-		return j->done;
+		return j->all_done();
 	}), jobs.end());
 }
 
@@ -62,12 +70,28 @@ void launch_job(SpecJob* job) {
 			std::lock_guard<std::mutex> rtc(g_rtc_mutex);
 			ok = compile_spec(job->prog->p, job->fast.get(), job->arch, code, log, nullptr, job->cull, job->form, job->carries);
 		} catch (...) { ok = false; log = "the scene compiler ran out of memory"; }
+		{
+			std::lock_guard<std::mutex> lock(job->mu);
+			job->compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - job->started).count();
+			job->code = std::move(code);
+			job->log = std::move(log);
+			job->ok = ok;
+			job->done = true;
+			job->cv.notify_all();
+		}
+		if (!job->want_structure) return;
+		bool sok = false;
+		std::vector<char> scode;
+		std::string slog;
+		try {
+			std::lock_guard<std::mutex> rtc(g_rtc_mutex);
+			sok = compile_structure(job->prog->p, job->arch, scode, slog);
+		} catch (...) { sok = false; slog = "the scene compiler ran out of memory"; }
 		std::lock_guard<std::mutex> lock(job->mu);
-		job->compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - job->started).count();
-		job->code = std::move(code);
-		job->log = std::move(log);
-		job->ok = ok;
-		job->done = true;
+		job->structure_code = std::move(scode);
+		job->structure_log = std::move(slog);
+		job->structure_ok = sok;
+		job->structure_done = true;
 		job->cv.notify_all();
 	};
 	const char* async = tuning_env("LOL_GPU_ASYNC_COMPILE");
@@ -174,17 +198,59 @@ std::unique_ptr<SpecJob> take_finished(SpecTiers& T, bool wait) {
 	return std::move(T.job);
 }
 
+/* the run whose structure module is awaited, once that is there (with `wait`: waited for): its outcome takes effect */
+bool finish_structure(SpecTiers& T, bool wait) {
+	if (!T.structure_job) return false;
+	SpecJob& job = *T.structure_job;
+	{
+		std::unique_lock<std::mutex> lock(job.mu);
+		if (!job.structure_done && !wait) return false;
+		job.cv.wait(lock, [&] { return job.structure_done; });
+	}
+	std::string why = job.structure_log;
+	if (job.structure_ok && load_structure_kernel(job.structure_code, T.structure, why)) {
+		T.structure_state = 2;
+		T.structure_log = job.structure_log;
+	} else {
+		T.structure_state = -1;
+		T.structure_log = why;
+		fprintf(stderr, "lol_gpu: the structure module was not to be had, scene views render on the interpreter: %s\n", why.c_str());
+	}
+	T.structure_job.reset();
+	return true;
+}
+
 }  // namespace
+
+bool load_structure_kernel(const std::vector<char>& code, StructureKernel& k, std::string& why) {
+	k.key = code_key_hex(code.data(), code.size());
+	bool ok = hipModuleLoadData(&k.module, code.data()) == hipSuccess;
+	if (!ok) why = "hipModuleLoadData failed";
+	if (ok && hipModuleGetFunction(&k.batch, k.module, "lol_render_param_batch") != hipSuccess) { ok = false; why = "lol_render_param_batch not found in the compiled module"; }
+	if (ok && hipModuleGetFunction(&k.lin, k.module, "lol_render_param_batch_lin") != hipSuccess) { ok = false; why = "lol_render_param_batch_lin not found in the compiled module"; }
+	if (ok) return true;
+	k.unload();
+	(void)hipGetLastError();
+	return false;
+}
+
+bool structure_module_wanted(const lol_gpu* ctx, const lol_program& P) {
+	return ctx->want_scene_views && P.n_ops <= LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS;
+}
 
 void start_specialise(lol_gpu* ctx, const FastPaths& fast) {
 	SpecTiers& T = ctx->tiers;
 	T.kernel.unload();
 	T.retired.unload();
+	T.structure.unload();
+	T.structure_state = 0;
+	T.structure_log.clear();
 	ctx->kernel_epoch++;                                /* the interpreter renders the new scene until its kernel is there */
 	T.log.clear();
 	T.tier = SpecTiers::OFF;
 	T.second_wanted = false;
 	if (std::unique_ptr<SpecJob> prev = std::move(T.job)) T.old_jobs.push_back(std::move(prev));      /* its result is not wanted any more */
+	if (std::unique_ptr<SpecJob> prev = std::move(T.structure_job)) T.old_jobs.push_back(std::move(prev));
 	reap(T.old_jobs);
 	const char* env = tuning_env("LOL_GPU_SPECIALIZE");
 	if (!T.want || (env && env[0] == '0')) return;
@@ -221,6 +287,8 @@ void start_specialise(lol_gpu* ctx, const FastPaths& fast) {
 	} catch (...) { T.log = "out of host memory"; return; }
 	job->cull = culling_enabled(ctx->want_cull);
 	job->carries = module_kernels_of(ctx);
+	job->want_structure = structure_module_wanted(ctx, ctx->h_prog);
+	if (job->want_structure) T.structure_state = 1;
 	/* (LOL_GPU_SPEC_INLINE_MAX, a tuning switch, pins ONE form by size) */
 	const bool first_tier = !tuning_env("LOL_GPU_SPEC_INLINE_MAX") && ctx->h_prog.n_ops > LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS &&
 	                        ctx->h_prog.n_ops <= LOL_SPEC_INLINE_MAX_OPS;
@@ -240,7 +308,9 @@ bool finish_specialise(lol_gpu* ctx, bool wait) {
 	while ((wait || !changed) && (job = take_finished(ctx->tiers, wait))) {
 		apply(ctx, *job, outcome_of(ctx->tiers, *job));
 		changed = true;
+		if (job->want_structure) ctx->tiers.structure_job = std::move(job);      /* its thread is still at work on the structure module */
 	}
+	if (finish_structure(ctx->tiers, wait)) changed = true;
 	return changed;
 }
 

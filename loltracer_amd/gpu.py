@@ -280,6 +280,21 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_compile_offline_shade.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                       C.c_char_p, C.c_size_t]
         lib.lol_gpu_compile_offline_shade.restype = C.c_int
+        lib.lol_gpu_render_scene_views.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                                   C.c_size_t, C.c_size_t, P(Debug), vp]
+        lib.lol_gpu_render_scene_views.restype = C.c_int
+        lib.lol_gpu_set_scene_views.argtypes = [vp, C.c_int]
+        lib.lol_gpu_set_scene_views.restype = C.c_int
+        lib.lol_gpu_scene_views.argtypes = [vp]
+        lib.lol_gpu_scene_views.restype = C.c_int
+        lib.lol_gpu_scene_views_kernel_name.argtypes = [vp, C.c_int]
+        lib.lol_gpu_scene_views_kernel_name.restype = C.c_char_p
+        lib.lol_gpu_scene_views_state.argtypes = [vp]
+        lib.lol_gpu_scene_views_state.restype = C.c_int
+        lib.lol_gpu_interp_fast_paths.argtypes = [vp, P(C.c_int), P(C.c_uint), P(C.c_uint)]
+        lib.lol_gpu_interp_fast_paths.restype = C.c_int
+        lib.lol_gpu_compile_offline_scene_views.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
+        lib.lol_gpu_compile_offline_scene_views.restype = C.c_int
         lib.lol_gpu_views_refined.argtypes = [vp, P(C.c_int64)]
         lib.lol_gpu_views_refined.restype = C.c_int
         lib.lol_gpu_interp_variant.argtypes = [vp, P(C.c_int), P(C.c_int)]
@@ -403,6 +418,7 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_render_views_blend_samples", "lol_gpu_set_view_blend_samples", "lol_gpu_view_blend_samples",
     "lol_gpu_trace_rays", "lol_gpu_trace_pixels", "lol_gpu_pick", "lol_gpu_set_ray_queries", "lol_gpu_ray_queries",
     "lol_gpu_shade_rays", "lol_gpu_shade_pixels", "lol_gpu_set_shade_queries", "lol_gpu_shade_queries", "lol_gpu_memcpy_h2d",
+    "lol_gpu_render_scene_views", "lol_gpu_set_scene_views", "lol_gpu_scene_views",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
@@ -414,6 +430,8 @@ DIAG_SYMBOLS = [                                                        # includ
     "lol_gpu_compile_offline_view_blend_samples", "lol_gpu_view_blend_samples_kernel_name",
     "lol_gpu_trace_kernel_name", "lol_gpu_compile_offline_rays", "lol_gpu_code_key",
     "lol_gpu_shade_kernel_name", "lol_gpu_compile_offline_shade", "lol_gpu_compile_offline_module",
+    "lol_gpu_scene_views_kernel_name", "lol_gpu_scene_views_state", "lol_gpu_compile_offline_scene_views",
+    "lol_gpu_interp_fast_paths",
 ]
 
 
@@ -502,6 +520,17 @@ def compile_offline_shade(program: S.Program, out_base: str, enable: bool = True
                           view_samples: bool = False, view_blend_samples: bool = False, ray_queries: bool = False) -> str:
     return _offline(program, out_base, form, arch, assume_fast, shade_queries=enable, view_blends=view_blends, samples=samples,
                     view_batches=view_batches, view_samples=view_samples, view_blend_samples=view_blend_samples, ray_queries=ray_queries)
+
+
+def compile_offline_scene_views(program: S.Program, out_base: str, arch: str = "gfx950") -> str:
+    """hipRTC-compile the STRUCTURE module of `program` (Renderer.set_scene_views) without a device: writes out_base.hip and
+    out_base.co and returns the compiler log.  The source depends on the program's structure alone — opcodes, ids and counts — so
+    two programs of one structure give the same two files, byte for byte."""
+    log = C.create_string_buffer(1 << 16)
+    st = gpu_lib().lol_gpu_compile_offline_scene_views(C.byref(program), arch.encode(), os.fsencode(out_base), log, len(log))
+    if st != LOL_GPU_OK:
+        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
+    return log.value.decode(errors="replace")
 
 
 MAX_VIEWS = 4096                     # LOL_GPU_MAX_VIEWS
@@ -714,6 +743,77 @@ class Renderer:
             self._check(self._lib.lol_gpu_render_views_blend_samples(
                 self._ctx, arr, len(cams) // k, k, w, h, max_steps, int(samples), C.c_void_p(dst_ptr), pitch, stride, dbg,
                 _stream_arg(stream)))
+
+    def set_scene_views(self, enable: bool):
+        """Before prepare(): the scene compiler also makes the STRUCTURE module behind the scene's own (lol_render_param_batch,
+        lol_render_param_batch_lin: the scene's SDF specialised on its structure alone, every number read from the view's record);
+        render_scene_views_into runs on it once it is loaded (specialize_wait waits for it too).  Without it — and until it is
+        loaded, with specialisation off, or for a program of more than 256 ops — the interpreter's render_interp_scene_batch /
+        _lin render on every record's own lists.  Same pixels either way; the scene's own module and kernel_key() do not change.
+        Opt-in for a reason: for scene4 the interpreter with the upload's proven fast paths was the faster of the two (DESIGN.md
+        3.18, tools/scene_views_rate.py measures a host's own scenes)."""
+        self._check(self._lib.lol_gpu_set_scene_views(self._ctx, 1 if enable else 0))
+
+    @property
+    def scene_views(self) -> bool:
+        return bool(self._lib.lol_gpu_scene_views(self._ctx))
+
+    def scene_views_kernel_name(self, cameras_per_view: int = 1) -> str:
+        """the kernel the next render_scene_views_into(..., cameras_per_view=...) launches (of a blend: its first pass)"""
+        return self._lib.lol_gpu_scene_views_kernel_name(self._ctx, int(cameras_per_view)).decode()
+
+    def scene_views_state(self) -> int:
+        """the structure module of the uploaded program: 0 none, 1 compiling, 2 in use, -1 failed"""
+        return int(self._lib.lol_gpu_scene_views_state(self._ctx))
+
+    def interp_fast_paths(self) -> tuple:
+        """(sqrt_kind, proven, proven_without_fixup): what the last upload proved for the interpreter's kernels — the sqrt kind they
+        run with (0 plain, 3 the proven fast root) and how many smoothness constants of the program have a proven fast blend factor
+        (and how many of those also without v_div_fixup).  The lists of scene views are built with exactly this."""
+        kind, n, nf = C.c_int(), C.c_uint(), C.c_uint()
+        self._check(self._lib.lol_gpu_interp_fast_paths(self._ctx, C.byref(kind), C.byref(n), C.byref(nf)))
+        return int(kind.value), int(n.value), int(nf.value)
+
+    def render_scene_views_into(self, dst_ptr: int, cameras, scenes, w: int, h: int, cameras_per_view: int = 1, max_steps: int = 256,
+                                pitch_bytes: int | None = None, view_stride_bytes: int | None = None, debug: Debug | None = None,
+                                stream: int | None = None):
+        """Asynchronously render len(scenes) / cameras_per_view views of w x h, every RECORD under a camera and a scene of its own
+        (lol_gpu_render_scene_views): record r is the frame this renderer would render under cameras[r] after prepare(scenes[r]).
+        With K = cameras_per_view = 1 view v is that frame, with every diagnostic of `debug`; with K in {2, 4, 8, 16} view v is the
+        mean IN LINEAR LIGHT of records v K ... v K + K - 1, as render_blended_views_into averages cameras (rgb alone).
+        scenes: scene.Scene objects (flattened here) or ready scene.Program objects, all of the prepared scene's structure
+        (scene.same_structure; scene.tween gives such scenes).  cameras: scene.Camera / scene.FrameCamera objects, one per record,
+        or None: every record's own scene's camera.  Both arrays are copied before the call returns.  Addressing as
+        render_views_into."""
+        items = list(scenes)
+        k = int(cameras_per_view)
+        if k < 1 or len(items) % k:
+            raise ValueError("render_scene_views_into: len(scenes) must be a multiple of cameras_per_view")
+        cams = list(cameras) if cameras is not None else [None] * len(items)
+        if len(cams) != len(items):
+            raise ValueError("render_scene_views_into: one camera per scene")
+        keep = []                                    # the flattened programs live until the call has copied them
+        progs = (S.Program * max(1, len(items)))()
+        arr = (S.FrameCamera * max(1, len(items)))()
+        for i, (sc, c) in enumerate(zip(items, cams)):
+            prog = sc if isinstance(sc, S.Program) else sc.flatten()
+            keep.append(prog)
+            C.memmove(C.byref(progs, i * C.sizeof(S.Program)), C.byref(prog), C.sizeof(S.Program))
+            if isinstance(c, S.FrameCamera):
+                fc = c
+            elif isinstance(sc, S.Program):
+                if c is None:
+                    raise ValueError("render_scene_views_into: a Program has no camera of its own")
+                fc = self.scene.frame_camera(w, h, c)
+            else:
+                fc = sc.frame_camera(w, h, c)
+            C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
+        pitch = pitch_bytes if pitch_bytes is not None else w * 4
+        stride = view_stride_bytes if view_stride_bytes is not None else h * pitch
+        dbg = C.byref(debug) if debug is not None else None
+        self._check(self._lib.lol_gpu_render_scene_views(
+            self._ctx, arr, progs, len(items) // k, k, w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride, dbg, _stream_arg(stream)))
+        del keep
 
     def render_host(self, host_ptr: int, w: int, h: int, max_steps: int = 256, camera: S.Camera | None = None,
                     pitch_bytes: int | None = None):

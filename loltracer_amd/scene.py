@@ -122,6 +122,8 @@ def host_lib() -> C.CDLL:
         lib.lol_scene_parse_string.restype = C.c_int
         lib.lol_scene_free.argtypes = [P(SceneStruct)]
         lib.lol_scene_free.restype = None
+        lib.lol_scene_clone.argtypes = [P(SceneStruct), P(P(SceneStruct))]
+        lib.lol_scene_clone.restype = C.c_int
         lib.lol_scene_new.argtypes = []
         lib.lol_scene_new.restype = P(SceneStruct)
         lib.lol_scene_validate_materials.argtypes = [P(SceneStruct)]
@@ -164,6 +166,26 @@ class Scene:
         if st != LOL_OK:
             raise SceneError(st, err.value.decode() or lib.lol_status_str(st).decode())
         return cls(out)
+
+    def clone(self) -> "Scene":
+        """lol_scene_clone: a deep copy — equal counts, equal bytes in every table — that is this object's own to change."""
+        lib = host_lib()
+        out = C.POINTER(SceneStruct)()
+        st = lib.lol_scene_clone(self._ptr, C.byref(out))
+        if st != LOL_OK:
+            raise SceneError(st, lib.lol_status_str(st).decode())
+        return Scene(out)
+
+    def tables(self) -> bytes:
+        """Everything the scene says, as bytes: counts, ambient colour and camera, then nodes, roots, materials and lights."""
+        c = self.c
+        head = b"".join(int(n).to_bytes(8, "little") for n in (c.n_materials, c.n_lights, c.n_nodes, c.n_roots))
+        head += bytes(memoryview(c.ambient_color).cast("B")) + bytes(memoryview(c.camera).cast("B"))
+        parts = [head]
+        for ptr, n, t in ((c.nodes, c.n_nodes, Node), (c.roots, c.n_roots, C.c_int32), (c.materials, c.n_materials, Material),
+                          (c.lights, c.n_lights, Light)):
+            parts.append(C.string_at(ptr, n * C.sizeof(t)) if n else b"")
+        return b"".join(parts)
 
     @property
     def ptr(self):
@@ -216,6 +238,73 @@ class Scene:
             self.close()
         except Exception:
             pass
+
+
+def same_structure(a: "Scene", b: "Scene") -> bool:
+    """Do a and b differ in numbers alone?  Equal counts of nodes, roots, materials and lights, equal roots, and equal type and
+    children node by node.  Such scenes flatten to programs of equal counts, opcodes and ids: what
+    Renderer.render_scene_views_into asks of the scenes of one call.  Which material an object wears is a number here, as it is
+    there (root_material may differ per record)."""
+    ca, cb = a.c, b.c
+    if (ca.n_nodes, ca.n_roots, ca.n_materials, ca.n_lights) != (cb.n_nodes, cb.n_roots, cb.n_materials, cb.n_lights):
+        return False
+    for i in range(ca.n_roots):
+        if ca.roots[i] != cb.roots[i]:
+            return False
+    for i in range(ca.n_nodes):
+        x, y = ca.nodes[i], cb.nodes[i]
+        if (x.type, x.a, x.b) != (y.type, y.a, y.b):
+            return False
+    return True
+
+
+def _lerp32(a, b, t):
+    """a + (b - a) * t, every operation a binary32 operation (numpy float32 scalars or arrays: no double in between)"""
+    import numpy as np
+    with np.errstate(all="ignore"):
+        return np.float32(a) + (np.float32(b) - np.float32(a)) * np.float32(t)
+
+
+def tween(a: "Scene", b: "Scene", t: float) -> "Scene":
+    """The scene between a (t = 0) and b (t = 1): a clone of a in which every float of the nodes (point, radius, half_extent,
+    smoothness), of the lights, of the materials and of the ambient colour is a + (b - a) * t, each operation in float32 with t
+    rounded to float32 first.  The structure — node types, children, roots —, the material indices and the camera are a's; a and b must
+    have the same structure (same_structure), else ValueError.  tween(a, b, 0) is a's numbers and tween(a, b, 1) b's wherever
+    b - a is exact, which it is for the numbers scenes are written with."""
+    if not same_structure(a, b):
+        raise ValueError("tween: the two scenes differ in structure")
+    import numpy as np
+    t = np.float32(t)
+    out = a.clone()
+    ca, cb, co = a.c, b.c, out.c
+
+    def blend(dst, x, y, cls):
+        n = C.sizeof(cls) // 4
+        fx = np.frombuffer(bytes(memoryview(x).cast("B")), dtype=np.float32)
+        fy = np.frombuffer(bytes(memoryview(y).cast("B")), dtype=np.float32)
+        C.memmove(C.byref(dst), np.ascontiguousarray(_lerp32(fx, fy, t), dtype=np.float32).tobytes(), 4 * n)
+
+    for i in range(ca.n_nodes):
+        x, y, o = ca.nodes[i], cb.nodes[i], co.nodes[i]
+        blend(o.point, x.point, y.point, V3)
+        blend(o.half_extent, x.half_extent, y.half_extent, V3)
+        o.radius = float(_lerp32(x.radius, y.radius, t))
+        o.smoothness = float(_lerp32(x.smoothness, y.smoothness, t))
+    for i in range(ca.n_lights):
+        blend(co.lights[i], ca.lights[i], cb.lights[i], Light)
+    for i in range(ca.n_materials):
+        blend(co.materials[i], ca.materials[i], cb.materials[i], Material)
+    blend(co.ambient_color, ca.ambient_color, cb.ambient_color, V3)
+    return out
+
+
+def shutter_times(frame: int, frames: int, k: int) -> list:
+    """The times of the k scenes of frame `frame` of `frames` frames that run from t = 0 to t = 1, each frame's exposure one of
+    `frames` equal parts of that interval: scene i of the frame stands at the midpoint of the i-th of k equal parts of its exposure,
+    the way shutter_cameras spreads its cameras.  k = 1: the middle of the frame's part."""
+    if frames < 1 or k < 1 or not 0 <= frame < frames:
+        raise ValueError("shutter_times: frames and k must be at least 1 and 0 <= frame < frames")
+    return [(frame + (i + 0.5) / k) / frames for i in range(k)]
 
 
 def orbit_cameras(scene: "Scene", n: int) -> list:
