@@ -531,6 +531,23 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 	bool vcarry = carry && plan.intervals[0].end == plan.intervals[0].begin + 1 && roots[plan.order[plan.intervals[0].begin]].bounded;
 	if (const char* e = tuning_env("LOL_GPU_CULL_VALUE_CARRY")) vcarry = vcarry && atoi(e) != 0;
 	const ValueCarryConsts vc = vcarry ? value_carry_constants(P, roots[plan.order[plan.intervals[0].begin]]) : ValueCarryConsts();
+	/* ID_FROM_LAST, for the inlined fast SDF of a scene of exactly TWO top-level objects — the scenes that keep the id in their march
+	 * (ASK_ID_ONCE below); every other scene keeps its source byte for byte.  The primary march evaluates through eval_rec(): the
+	 * distance alone, like eval_dist(), plus a RECORD — each object's value at this step per lane, +inf for an object the culling
+	 * skipped — and decides the id once, after the loop, from the record of the lane's own last step (lol_kernel.h, march; id_of
+	 * below).  Per step: one v_min_f32 per object instead of the compares and selects of the strict-'<' / lower-id rule.
+	 * What it rests on: an object's value that is NaN or infinite re-shades the wave through the plain pipeline — every value
+	 * recorded goes through nanacc = fma(value, 0, nanacc) (lol_kernel.h, unproven) — so the rules only have to agree for finite
+	 * values, where "the lowest id among the objects at the minimum" IS what the strict '<' and the lower-id tie rule of eval()
+	 * leave, in any evaluation order (-0 == +0 in both).  They differ for t = +inf alone (t < +inf is false: eval() keeps id 0) and
+	 * for NaN.  A skipped object's plain value strictly loses (open_test), which is what its +inf in the record says.
+	 * Measured on one box, six alternating repetitions (profiles/r19_ab_last_step_id.txt): scene4 C3 +0.9 %.
+	 * LOL_GPU_LAST_STEP_ID=0 beside LOL_GPU_TUNING: off.
+	 * Only for scenes of at most 32 ops (the scenes that keep 8 waves per SIMD, generate_source): eval_rec() is a third copy of the
+	 * inlined body, and what it saves per step is a fixed couple of dozen cycles — 6 % of a step of scene4's 12 ops, under 1 % of a
+	 * step of a hundred, for a third more code to fetch. */
+	bool last_id = fast && !out_of_line && !param && P.n_roots == 2 && P.n_ops <= 32;
+	if (const char* e = tuning_env("LOL_GPU_LAST_STEP_ID")) last_id = last_id && atoi(e) != 0;
 	std::string carry_decl;
 	if (carry)
 		carry_decl = "\tfloat lb = -__builtin_inff(), rt = 0.f;\n\tbool carry = false;\n"
@@ -555,19 +572,39 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 		         carry_decl.c_str(), plan.intervals.empty() ? "" : "cool[0] = 0u;", carry ? " lb = -__builtin_inff(); carry = false;" : "");
 		s += line;
 		if (param) s += "\tparam_ptr K = nullptr;\n";
+		if (last_id) {
+			/* the record's two slots in the order of the ids: rec0 the object of the lower id, which a tie goes to */
+			const uint32_t ida = roots[0].id, idb = roots[1].id;
+			snprintf(line, sizeof line, "\tstatic constexpr bool ID_FROM_LAST = true;\n"
+			         "\t__device__ __forceinline__ u32 id_of(float rec0, float rec1) const { return rec0 == vmin_(rec0, rec1) ? %uu : %uu; }\n",
+			         ida < idb ? ida : idb, ida < idb ? idb : ida);
+			s += line;
+		}
 	}
 	/* The body twice where it is inlined: eval() — distance and object id — for the primary march and the normal taps, and
 	 * eval_dist() — the distance alone — for the shadow marches, which never look at the id.  There an object joins the running
 	 * minimum with ONE v_min_f32 instead of the compare(s) and selects of the strict-'<' / lower-id-wins rule: the two agree on the
 	 * value except for the sign of a zero (two objects at distance -0 and +0 of the same point), and a shadow march's results —
 	 * its factor maxf(res, 0) and its step count — are the same for s = -0 and s = +0: t + s, 50 s / t compared with 0, and
-	 * maxf(+-0, 0) = +0 all are (lol_kernel.h, soft_shadow).  A NaN value is dropped by either form. */
-	for (int pass = 0; pass < (out_of_line ? 1 : 2); pass++) {
-	const bool dist_only = pass == 1;
+	 * maxf(+-0, 0) = +0 all are (lol_kernel.h, soft_shadow).  A NaN value is dropped by either form.
+	 * ... and once more, FIRST, for an ID_FROM_LAST scene: eval_rec(), eval_dist() plus the record of each object's value (last_id above). */
+	auto rec_slot = [&](size_t oi) { return roots[plan.order[oi]].id > roots[plan.order[oi ^ 1]].id ? 1 : 0; };      /* (two objects) */
+	for (int turn = 0; turn < (out_of_line ? 1 : last_id ? 3 : 2); turn++) {
+	const int pass = last_id ? (turn + 2) % 3 : turn;                          /* (eval_rec comes first; eval and eval_dist stay where they were) */
+	const bool rec = pass == 2, dist_only = pass >= 1;
 	if (!out_of_line)
-		s += dist_only ? "\t__device__ __forceinline__ void eval_dist(V3 p, float& best) {\n"
+		s += rec       ? "\t__device__ __forceinline__ void eval_rec(V3 p, float& best, float& rec0, float& rec1) {\n"
+		   : dist_only ? "\t__device__ __forceinline__ void eval_dist(V3 p, float& best) {\n"
 		               : "\t__device__ __forceinline__ void eval(V3 p, float& best, u32& best_id) {\n";
 	s += dist_only ? "\t\tbest = __builtin_inff();\n" : "\t\tbest = __builtin_inff(); best_id = 0u;\n";
+	if (rec)                            /* an object behind a test that lets the wave skip it is recorded as +inf: it strictly loses */
+		for (size_t oi = 0; oi < plan.order.size(); oi++)
+			for (const CullInterval& iv : plan.intervals)
+				if (iv.begin <= oi && oi < iv.end) {
+					snprintf(line, sizeof line, "\t\trec%d = __builtin_inff();\n", rec_slot(oi));
+					s += line;
+					break;
+				}
 	int t = 0, n_tests = 0;
 	/* After a test that did not allow the skip, the next `cooldown` evaluations of this SDF object do not test
 	 * again (a ray that is near the object now is near it on its next steps too): the test costs 11 VALU
@@ -779,8 +816,12 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 		};
 		object_has_nr = false;
 		const int d = emit_node((int)nodes.size() - 1);
-		if (object_has_nr) {                 /* a NaN from a sphere without range tracker reaches the object's value: 0 * NaN (or inf) = NaN */
-			snprintf(line, sizeof line, "\t\tnanacc = __builtin_fmaf(t%d, 0.f, nanacc);\n", d);
+		if (object_has_nr || rec) {          /* a NaN from a sphere without range tracker reaches the object's value: 0 * NaN (or inf) = NaN */
+			snprintf(line, sizeof line, "\t\tnanacc = __builtin_fmaf(t%d, 0.f, nanacc);\n", d);      /* (... and every value the record takes) */
+			s += line;
+		}
+		if (rec) {
+			snprintf(line, sizeof line, "\t\trec%d = t%d;\n", rec_slot(oi), d);
 			s += line;
 		}
 		if (dist_only)

@@ -879,7 +879,19 @@ struct Marched { float dist, prev; u32 steps; u32 id; bool ask; };
  * took at least one turn of the loop (wave-uniform: every lane takes the first turn of a loop that runs at all) and did not escape.
  * Round 6 (profiles/r6_ab_id_asked_once.txt): scene.lol's four flat objects +3.6 % (C2), scene4's two -0.8 % (C3) — the extra
  * evaluation per pixel against 8 cycles per object and step — hence per scene; the interpreter -0.4 ... -0.9 % / +2.5 %: it keeps
- * the id in its march. */
+ * the id in its march.
+ *
+ * Sdf::ID_FROM_LAST (the fast SDF of a scene of exactly two top-level objects, the scenes that keep the id in their march:
+ * lol_codegen.hip, last_id): since only the LAST step's id is used, the march evaluates the distance alone here too, through
+ * eval_rec(), which also leaves each object's value at this step in a record (+inf for an object the culling skipped).  A lane that
+ * breaks leaves EXEC, so its record stays that of its own last step, and the id is decided once after the loop: the lowest id among
+ * the objects whose recorded value equals the lane's minimum (Sdf::id_of) — eval()'s strict '<' with its lower-id tie rule, for
+ * every value that is finite; a value that is not has gone through nanacc, and the wave is shaded again by the plain pipeline.  No
+ * evaluation more per pixel, which is what ASK_ID_ONCE lost on scene4.  A loop that takes no turn keeps first_id; an escaped ray
+ * gets 0 as before. */
+template <class S> constexpr auto id_from_last(int) -> decltype(S::ID_FROM_LAST) { return S::ID_FROM_LAST; }
+template <class S> constexpr bool id_from_last(long) { return false; }
+
 template <bool COUNT, class Sdf>
 __device__ __forceinline__ Marched march(Sdf& sdf, V3 ro, V3 rd, int max_steps, bool first_given, float first_dist, u32 first_id) {
 	const float EPSILON = 0.001f, MAX_DIST = 100.f;
@@ -888,6 +900,7 @@ __device__ __forceinline__ Marched march(Sdf& sdf, V3 ro, V3 rd, int max_steps, 
 	float dist = skip_first ? first_dist : 0.f, prev = 0.f;
 	u32 id = skip_first ? first_id : 0u, steps = skip_first ? 1u : 0u;
 	const int first_turn = skip_first ? 1 : 0;
+	[[maybe_unused]] float rec0 = 0.f, rec1 = 0.f;
 	ray_begin(sdf, rd, 0);
 	for (int i = first_turn; i < max_steps; i++) {
 		V3 p = add(ro, scale(rd, dist));
@@ -896,6 +909,8 @@ __device__ __forceinline__ Marched march(Sdf& sdf, V3 ro, V3 rd, int max_steps, 
 		if constexpr (Sdf::ASK_ID_ONCE) {
 			sdf.eval_dist(p, d);
 			prev = dist;
+		} else if constexpr (id_from_last<Sdf>(0)) {
+			sdf.eval_rec(p, d, rec0, rec1);
 		} else {
 			u32 did;
 			sdf.eval(p, d, did);
@@ -906,6 +921,9 @@ __device__ __forceinline__ Marched march(Sdf& sdf, V3 ro, V3 rd, int max_steps, 
 		if (d < EPSILON || dist > MAX_DIST) break;
 	}
 	sdf.loop_done();
+	if constexpr (id_from_last<Sdf>(0)) {
+		if (first_turn < max_steps) id = sdf.id_of(rec0, rec1);      /* (wave-uniform: every lane takes the first turn of a loop that runs) */
+	}
 	const bool far = dist >= MAX_DIST;
 	if (far) id = 0;
 	if constexpr (Sdf::ASK_ID_ONCE) {
