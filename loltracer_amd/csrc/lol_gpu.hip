@@ -238,23 +238,46 @@ bool host_sdf(const lol_program& P, const float p[3], std::vector<float>& st, fl
 	*id_out = best_id;
 	return true;
 }
-/* FLAG_FIRST_STEP for a frame of `cam`?  Fills ctx->first_dist / first_id (kept while the camera stays where it is). */
-bool first_step(lol_gpu* ctx, const lol_frame_camera& cam, int max_steps) {
+/* may a frame of `cam` take its first step on the host at all: what is decided before the SDF is asked */
+bool first_step_possible(const lol_frame_camera& cam, int max_steps) {
 	if (max_steps < 1 || !camera_sane(cam)) return false;
-	float origin[3] = { cam.origin.x, cam.origin.y, cam.origin.z };
 	uint32_t bits[3];
-	memcpy(bits, origin, sizeof bits);
+	memcpy(bits, &cam.origin, sizeof bits);
 	for (uint32_t b : bits) if (b == 0x80000000u) return false;
-	if (ctx->first_gen != ctx->generation || memcmp(ctx->first_origin, origin, sizeof origin) != 0) {
-		float d = 0.f; uint32_t id = 0;
-		bool ok = false;
-		try { ok = host_sdf(ctx->h_prog, origin, ctx->first_stack, &d, &id); } catch (...) { ok = false; }
-		ctx->first_dist = ok ? d : __builtin_nanf("");
-		ctx->first_id = id;
+	return true;
+}
+/* FLAG_FIRST_STEP for a frame of `cam` over program `P`?  *dist and *id: the SDF at the camera's position (NaN where host_sdf
+ * could not say, or threw), written whenever the camera allows the question. */
+constexpr float FIRST_STEP_MIN = 0.001f, FIRST_STEP_MAX = 100.f;      /* the reference's EPSILON and MAX_DIST */
+bool program_first_step(const lol_program& P, const lol_frame_camera& cam, int max_steps, std::vector<float>& stack, float* dist, uint32_t* id) {
+	if (!first_step_possible(cam, max_steps)) return false;
+	const float origin[3] = { cam.origin.x, cam.origin.y, cam.origin.z };
+	bool ok = false;
+	*dist = 0.f; *id = 0;
+	try { ok = host_sdf(P, origin, stack, dist, id); } catch (...) { ok = false; }
+	if (!ok) *dist = __builtin_nanf("");
+	return *dist >= FIRST_STEP_MIN && *dist <= FIRST_STEP_MAX;
+}
+/* ... over the uploaded program: the answer, ctx->first_dist and first_id are kept while the camera stays where it is (what the
+ * camera rules out by itself never reaches the cache) */
+bool first_step(lol_gpu* ctx, const lol_frame_camera& cam, int max_steps) {
+	if (!first_step_possible(cam, max_steps)) return false;
+	if (ctx->first_gen != ctx->generation || memcmp(ctx->first_origin, &cam.origin, sizeof ctx->first_origin) != 0) {
+		ctx->first_taken = program_first_step(ctx->h_prog, cam, max_steps, ctx->first_stack, &ctx->first_dist, &ctx->first_id);
 		ctx->first_gen = ctx->generation;
-		memcpy(ctx->first_origin, origin, sizeof origin);
+		memcpy(ctx->first_origin, &cam.origin, sizeof ctx->first_origin);
 	}
-	return ctx->first_dist >= 0.001f && ctx->first_dist <= 100.f;
+	return ctx->first_taken;
+}
+/* What a record — a frame's Launch, a lol::View, a lol::SceneView — owes to its camera: FLAG_SHADOW_SETTLED (`settle`: the scene
+ * qualifies and the host wants it), FLAG_FIRST_STEP with its value (`first`: program_first_step's answer, `dist` and `id` with it).
+ * True: the record runs the second copy of the macro-op list, the one without v_div_fixup (`finite`: shadow_settle_ok(scene)). */
+template <class Record>
+bool camera_fields(Record& R, const lol_frame_camera& cam, bool finite, bool settle, bool first, float dist, uint32_t id) {
+	const bool sane = camera_sane(cam);
+	if (settle && sane) R.flags |= lol::FLAG_SHADOW_SETTLED;
+	if (first) { R.flags |= lol::FLAG_FIRST_STEP; R.first_dist = dist; R.first_id = id; }
+	return finite && sane;
 }
 
 /* ---- optional roctx ranges (LOL_GPU_ROCTX=1): one range per frame launch, visible to `rocprofv3 --marker-trace`.
@@ -476,6 +499,88 @@ __global__ __launch_bounds__(64) void blend_resolve(const lol::LinearColour* lin
 	O.dst[v * O.view_stride_px + (unsigned long long)y * O.pitch_px + (unsigned long long)x] = px;
 }
 
+/* not by hipStreamWaitEvent on HIP's special handles (the legacy default stream, the per-thread one): this HIP's hipStreamWaitEvent
+ * dereferences the handle it is given and crashes (lol_sched.hip says the same) — there the host waits for the event */
+int wait_on_stream(lol_gpu* ctx, hipStream_t s, hipEvent_t ev) {
+	const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
+	if (!special) LOL_HIP(ctx, hipStreamWaitEvent(s, ev, 0));
+	else LOL_HIP(ctx, hipEventSynchronize(ev));
+	return LOL_GPU_OK;
+}
+
+/*
+ * The protocol of the context's rings of per-call device sets (lol_gpu_internal.h, RingSet), written once: take, copy, done, free.
+ */
+void ring_release(RingSet& S) {
+	if (S.d_buf) (void)hipFree(S.d_buf);
+	if (S.h_buf) (void)hipHostFree(S.h_buf);
+	S.d_buf = nullptr; S.h_buf = nullptr; S.bytes = 0; S.used = false;
+}
+/* take: `S`, the ring's next set, is this call's, of at least `need` bytes, for work queued on `s`.  Its events are created on first
+ * use.  Where it must grow — to `grow_to` bytes — the host waits for the set's last user and the buffers are replaced; an allocation
+ * that fails leaves the set empty and the thread's last error cleared (the host's next HIP call must not trip over it), and `what`
+ * in the context's error.  Then the waits: for `copied` on the host — the pinned half is the host's to write once the set's last
+ * COPY has run (a ring's length of calls ago: a host that queues faster than the device renders is held that far ahead of it here)
+ * —, for `done` on `s`: the device half is this call's once the set's last LAUNCH has finished, whatever stream it ran on.
+ * `inject`: lol_gpu_testing_fail_view_scratch's counter, for the rings it is about. */
+enum RingKind : unsigned { RING_SCRATCH = 0, RING_PINNED = 1, RING_TIMED = 2 };
+int ensure_event(lol_gpu* ctx, hipEvent_t* ev, bool timed = false) {
+	if (!*ev) LOL_HIP(ctx, hipEventCreateWithFlags(ev, timed ? hipEventDefault : hipEventDisableTiming));
+	return LOL_GPU_OK;
+}
+int ring_take(lol_gpu* ctx, RingSet& S, size_t need, size_t grow_to, unsigned kind, hipStream_t s, int* inject, const char* what) {
+	const bool pinned = kind & RING_PINNED;
+	LOL_TRY(ensure_event(ctx, &S.done, kind & RING_TIMED));
+	if (pinned) LOL_TRY(ensure_event(ctx, &S.copied));
+	if (need > S.bytes) {
+		if (S.used) LOL_HIP(ctx, hipEventSynchronize(S.done));
+		ring_release(S);
+		const bool injected = inject && *inject > 0;
+		if (injected) --*inject;
+		hipError_t me = injected ? hipErrorOutOfMemory : hipMalloc(reinterpret_cast<void**>(&S.d_buf), grow_to);
+		if (me == hipSuccess && pinned) me = hipHostMalloc(reinterpret_cast<void**>(&S.h_buf), grow_to, hipHostMallocDefault);
+		if (me != hipSuccess) {
+			ring_release(S);
+			(void)hipGetLastError();
+			return fail(ctx, LOL_GPU_ERR_HIP, what, me);
+		}
+		S.bytes = grow_to;
+	}
+	if (S.used && pinned) LOL_HIP(ctx, hipEventSynchronize(S.copied));
+	if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.done));
+	return LOL_GPU_OK;
+}
+/* copy: the first `bytes` of the pinned half to the device on `s`, and `copied` behind them */
+hipError_t ring_copy(RingSet& S, size_t bytes, hipStream_t s) {
+	const hipError_t e = hipMemcpyAsync(S.d_buf, S.h_buf, bytes, hipMemcpyHostToDevice, s);
+	const hipError_t e2 = hipEventRecord(S.copied, s);
+	return e != hipSuccess ? e : e2;
+}
+/* done: `done` behind the last thing the call queued on `s` through `S` (and through `also`, the set of a second ring the same call
+ * took).  `e`: what that last thing returned, `what` it was.  Called on EVERY path once anything has been queued — behind a failed
+ * launch, a failed copy — because the work before it is queued, and the set's next user must find it behind the event it waits for. */
+int ring_done(lol_gpu* ctx, RingSet& S, hipStream_t s, hipError_t e, const char* what, RingSet* also = nullptr) {
+	hipError_t e2 = hipEventRecord(S.done, s);
+	S.used = true;
+	if (also) {
+		const hipError_t e3 = hipEventRecord(also->done, s);
+		also->used = true;
+		if (e2 == hipSuccess) e2 = e3;
+	}
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, what, e);
+	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (behind a call's last launch)", e2);
+	return LOL_GPU_OK;
+}
+/* free: at the end of the context, its streams drained */
+template <class Set, int N>
+void ring_free(Ring<Set, N>& ring) {
+	for (RingSet& S : ring.sets) {
+		ring_release(S);
+		if (S.copied) (void)hipEventDestroy(S.copied);
+		if (S.done) (void)hipEventDestroy(S.done);
+	}
+}
+
 }  // namespace
 
 extern "C" {
@@ -527,30 +632,13 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 		if (ctx->pipe_copied[i]) (void)hipEventDestroy(ctx->pipe_copied[i]);
 	}
 
-	for (lol_gpu::AdaptiveSet& S : ctx->adaptive_sets) {
-		if (S.d_buf) (void)hipFree(S.d_buf);
+	ring_free(ctx->view_records);
+	ring_free(ctx->scene_view_records);
+	ring_free(ctx->adaptive_batches);
+	ring_free(ctx->blends);
+	ring_free(ctx->adaptive_frames);
+	for (lol_gpu::AdaptiveFrameSet& S : ctx->adaptive_frames.sets)
 		for (hipEvent_t ev : S.ev) if (ev) (void)hipEventDestroy(ev);
-	}
-	for (lol_gpu::ViewAdaptiveSet& S : ctx->view_adaptive_sets) {
-		if (S.d_buf) (void)hipFree(S.d_buf);
-		if (S.done) (void)hipEventDestroy(S.done);
-	}
-	for (lol_gpu::BlendSet& S : ctx->blend_sets) {
-		if (S.d_buf) (void)hipFree(S.d_buf);
-		if (S.done) (void)hipEventDestroy(S.done);
-	}
-	for (lol_gpu::ViewSet& S : ctx->view_sets) {
-		if (S.d_views) (void)hipFree(S.d_views);
-		if (S.h_views) (void)hipHostFree(S.h_views);
-		if (S.copied) (void)hipEventDestroy(S.copied);
-		if (S.done) (void)hipEventDestroy(S.done);
-	}
-	for (lol_gpu::SceneViewSet& S : ctx->scene_view_sets) {
-		if (S.d_buf) (void)hipFree(S.d_buf);
-		if (S.h_buf) (void)hipHostFree(S.h_buf);
-		if (S.copied) (void)hipEventDestroy(S.copied);
-		if (S.done) (void)hipEventDestroy(S.done);
-	}
 	if (ctx->d_adaptive_order) (void)hipFree(ctx->d_adaptive_order);
 	if (ctx->d_bad) (void)hipFree(ctx->d_bad);
 	if (ctx->d_gamma) (void)hipFree(ctx->d_gamma);
@@ -740,36 +828,6 @@ static int ensure_refine_grid(lol_gpu* ctx) {
 	return LOL_GPU_OK;
 }
 
-/* not by hipStreamWaitEvent on HIP's special handles (the legacy default stream, the per-thread one): this HIP's hipStreamWaitEvent
- * dereferences the handle it is given and crashes (lol_sched.hip says the same) — there the host waits for the event */
-static int wait_on_stream(lol_gpu* ctx, hipStream_t s, hipEvent_t ev) {
-	const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
-	if (!special) LOL_HIP(ctx, hipStreamWaitEvent(s, ev, 0));
-	else LOL_HIP(ctx, hipEventSynchronize(ev));
-	return LOL_GPU_OK;
-}
-
-/* The scratch of set `si` of a ring (lol_gpu_internal.h, ScratchSet) grows to `need` bytes: the host waits for `behind`, the event of
- * the set's last user, and the old buffer goes with what pointed into it (`last`: the ring's set that lol_gpu_*_refined reads).
- * `inject`: lol_gpu_testing_fail_view_scratch's counter, for the ring it is about. */
-static int grow_scratch(lol_gpu* ctx, lol_gpu::ScratchSet& S, hipEvent_t behind, size_t need, int si, int& last, int* inject, const char* what) {
-	if (need <= S.bytes) return LOL_GPU_OK;
-	if (S.used) LOL_HIP(ctx, hipEventSynchronize(behind));
-	if (S.d_buf) (void)hipFree(S.d_buf);
-	S.d_buf = nullptr; S.bytes = 0; S.d_counts = nullptr; S.used = false;
-	if (last == si) last = -1;
-	const bool injected = inject && *inject > 0;
-	if (injected) --*inject;
-	const hipError_t me = injected ? hipErrorOutOfMemory : hipMalloc(reinterpret_cast<void**>(&S.d_buf), need);
-	if (me != hipSuccess) {
-		S.d_buf = nullptr;
-		(void)hipGetLastError();             /* (the thread's last error: the host's next HIP call must not trip over it) */
-		return fail(ctx, LOL_GPU_ERR_HIP, what, me);
-	}
-	S.bytes = need;
-	return LOL_GPU_OK;
-}
-
 /* The part of a launch that is the uploaded scene's and the context's: program and tables, ambient, the exact skips that hold for
  * every camera, the gamma table, the surface's pixel format, the diagnostics' buffers.  What depends on the camera (which copy of the
  * macro-op list, FLAG_SHADOW_SETTLED, the first step) is the caller's: per frame, or per view of a batch. */
@@ -821,51 +879,53 @@ static int render_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_gpu_deb
 	LOL_TRY(ensure_refine_grid(ctx));
 	const uint32_t per_wave = 64u / (uint32_t)(ss * ss);
 	const uint32_t blocks = (uint32_t)std::min<size_t>(ctx->adaptive_blocks, (px + per_wave - 1) / per_wave);
-	const int si = (int)(ctx->adaptive_rr++ % lol_gpu::ADAPTIVE_SETS);
-	lol_gpu::AdaptiveSet& S = ctx->adaptive_sets[si];
-	for (hipEvent_t& ev : S.ev) if (!ev) LOL_HIP(ctx, hipEventCreate(&ev));
-	LOL_TRY(grow_scratch(ctx, S, S.ev[3], (3 * px + 64 + (size_t)ctx->adaptive_blocks * 64) * 4, si, ctx->adaptive_last, nullptr,
-	                     "scratch of an adaptive frame"));
+	lol_gpu::AdaptiveFrameSet& S = ctx->adaptive_frames.next();
+	for (hipEvent_t& ev : S.ev) LOL_TRY(ensure_event(ctx, &ev, true));
+	const size_t need = (3 * px + 64 + (size_t)ctx->adaptive_blocks * 64) * 4;
+	LOL_TRY(ring_take(ctx, S, need, need, RING_TIMED, s, nullptr, "scratch of an adaptive frame"));
 	uint32_t* xrgb = S.d_buf;
 	uint32_t* ids = xrgb + px;
 	uint32_t* list = ids + px;
 	uint32_t* count = list + px;
 	uint32_t* lanes = count + 64;
-	if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.ev[3]));      /* behind the set's last frame, whatever stream it ran on */
-	LOL_HIP(ctx, hipEventRecord(S.ev[0], s));
-	LOL_HIP(ctx, hipMemsetAsync(count, 0, 4, s));
+	/* from here on things are queued on `s`: whatever fails, the rest is skipped and the set's `done` recorded behind what is there */
+	const char* what = "hipEventRecord (adaptive frame)";
+	hipError_t e = hipEventRecord(S.ev[0], s);
+	if (e == hipSuccess) { what = "hipMemsetAsync (adaptive frame)"; e = hipMemsetAsync(count, 0, 4, s); }
 
 	/* 1. the plain frame */
-	lol::Launch L = plain_pass_of(A, xrgb, ids, dbg);
-	dim3 grid((w + lol::TILE_W - 1) / lol::TILE_W, (h + lol::TILE_H - 1) / lol::TILE_H);
-	if (ctx->tiles.mode == LOL_GPU_TILES_COLS) {
-		L.flags |= lol::FLAG_TILE_COLS;
-		const unsigned t = grid.x; grid.x = grid.y; grid.y = t;
+	if (e == hipSuccess) {
+		lol::Launch L = plain_pass_of(A, xrgb, ids, dbg);
+		dim3 grid((w + lol::TILE_W - 1) / lol::TILE_W, (h + lol::TILE_H - 1) / lol::TILE_H);
+		if (ctx->tiles.mode == LOL_GPU_TILES_COLS) {
+			L.flags |= lol::FLAG_TILE_COLS;
+			const unsigned t = grid.x; grid.x = grid.y; grid.y = t;
+		}
+		what = "kernel launch (adaptive frame, plain pass)";
+		void* args[] = { &L };
+		e = launch_family(ctx, FAM_FRAME, false, args, grid, s);
 	}
-	void* plain_args[] = { &L };
-	hipError_t e = launch_family(ctx, FAM_FRAME, false, plain_args, grid, s);
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (adaptive frame, plain pass)", e);
-	LOL_HIP(ctx, hipEventRecord(S.ev[1], s));
-
+	if (e == hipSuccess) { what = "hipEventRecord (adaptive frame)"; e = hipEventRecord(S.ev[1], s); }
 	/* 2. classify and compact */
-	hipLaunchKernelGGL(adaptive_classify, dim3((w + CLASSIFY_W - 1) / CLASSIFY_W, (h + CLASSIFY_H - 1) / CLASSIFY_H), dim3(64), 0, s,
-	                   xrgb, ids, w, h, ctx->adaptive, A.dst, A.pitch_px, A.fmt_shift, A.fmt_loss, A.fmt_amask, list, count);
-	e = hipGetLastError();
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (adaptive frame, classify pass)", e);
-	LOL_HIP(ctx, hipEventRecord(S.ev[2], s));
-
+	if (e == hipSuccess) {
+		what = "kernel launch (adaptive frame, classify pass)";
+		hipLaunchKernelGGL(adaptive_classify, dim3((w + CLASSIFY_W - 1) / CLASSIFY_W, (h + CLASSIFY_H - 1) / CLASSIFY_H), dim3(64), 0, s,
+		                   xrgb, ids, w, h, ctx->adaptive, A.dst, A.pitch_px, A.fmt_shift, A.fmt_loss, A.fmt_amask, list, count);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) { what = "hipEventRecord (adaptive frame)"; e = hipEventRecord(S.ev[2], s); }
 	/* 3. the s x s pixels of the list */
-	lol::Launch R = A;
-	R.n_rows = h; R.band_rows = h; R.cycle_rows = h; R.offset_rows = 0;
-	R.tile_order = ctx->d_adaptive_order; R.tile_stride = ctx->adaptive_stride; R.lane_pixels = lanes;
-	void* refine_args[] = { &R, &list, &count };
-	e = launch_family(ctx, FAM_FRAME_AA_LIST, false, refine_args, dim3(blocks), s);
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "kernel launch (adaptive frame, refine pass)", e);
-	LOL_HIP(ctx, hipEventRecord(S.ev[3], s));
-	S.used = true;
-	S.d_counts = count;
-	ctx->adaptive_last = si;
-	return LOL_GPU_OK;
+	if (e == hipSuccess) {
+		lol::Launch R = A;
+		R.n_rows = h; R.band_rows = h; R.cycle_rows = h; R.offset_rows = 0;
+		R.tile_order = ctx->d_adaptive_order; R.tile_stride = ctx->adaptive_stride; R.lane_pixels = lanes;
+		what = "kernel launch (adaptive frame, refine pass)";
+		void* args[] = { &R, &list, &count };
+		e = launch_family(ctx, FAM_FRAME_AA_LIST, false, args, dim3(blocks), s);
+	}
+	S.d_count = count;
+	ctx->adaptive_last = &S;
+	return ring_done(ctx, S, s, e, what);
 }
 
 int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
@@ -907,10 +967,9 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
 	L.n_rows = n_rows;
 	L.band_rows = R->band_rows; L.cycle_rows = R->cycle_rows; L.offset_rows = R->offset_rows;
 	scene_launch_fields(ctx, dbg, L);
-	if (ctx->finite_scene && camera_sane(*cam)) L.ops += (size_t)ctx->n_mops * lol::MOP_DWORDS;
-	if (ctx->shadow_settle && camera_sane(*cam)) L.flags |= lol::FLAG_SHADOW_SETTLED;
+	const bool first = first_step(ctx, *cam, max_steps);
+	if (camera_fields(L, *cam, ctx->finite_scene, ctx->shadow_settle, first, ctx->first_dist, ctx->first_id)) L.ops += (size_t)ctx->n_mops * lol::MOP_DWORDS;
 	if (aa) L.flags |= ss == 4 ? lol::FLAG_SAMPLES_4 : lol::FLAG_SAMPLES_2;
-	if (first_step(ctx, *cam, max_steps)) { L.flags |= lol::FLAG_FIRST_STEP; L.first_dist = ctx->first_dist; L.first_id = ctx->first_id; }
 	L.dst = static_cast<uint32_t*>(dst);
 	L.pitch_px = (uint32_t)(pitch_bytes / 4);
 
@@ -971,11 +1030,11 @@ int lol_gpu_render_device(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
  * records on the same stream.  Everything lol_gpu_render_device decides per frame from the camera is decided here per view and
  * goes into the view's record: which copy of the macro-op list, FLAG_SHADOW_SETTLED (camera_sane), FLAG_FIRST_STEP and its value
  * (first_step).  Fixed tile order; the longest-first tables, AUTO's trials and what they remember of the last frame are neither
- * read nor written.  Records: the next set of the ring (lol_gpu_internal.h, ViewSet).
+ * read nor written.  Records: the next set of their ring (lol_gpu_internal.h, lol_gpu::view_records).
  *
  * The pieces, shared by lol_gpu_render_views and lol_gpu_render_views_samples: what both refuse (batch_refused), the launch of a
  * whole frame of the batch's size with one sample per pixel (batch_launch), the view records queued on the batch's stream
- * (queue_view_records) and the event behind the batch's last launch (view_records_done).
+ * (queue_view_records) and the event behind the batch's last launch (ring_done).
  */
 static int batch_refused(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps, const void* dst, size_t pitch_bytes,
                          size_t view_stride_bytes) {
@@ -1018,53 +1077,26 @@ static int batch_stream(lol_gpu* ctx, void* stream, hipStream_t* s) {
 	return LOL_GPU_OK;
 }
 
-/* the view records of a batch: the next set of the ring filled, and its copy to the device queued on `s` */
-static int queue_view_records(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int max_steps, hipStream_t s, lol_gpu::ViewSet** out) {
-	lol_gpu::ViewSet& S = ctx->view_sets[ctx->view_rr++ % lol_gpu::VIEW_SETS];
-	if (!S.copied) LOL_HIP(ctx, hipEventCreateWithFlags(&S.copied, hipEventDisableTiming));
-	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-	if ((size_t)n_views > S.cap) {
-		if (S.used) LOL_HIP(ctx, hipEventSynchronize(S.done));
-		if (S.d_views) (void)hipFree(S.d_views);
-		if (S.h_views) (void)hipHostFree(S.h_views);
-		S.d_views = nullptr; S.h_views = nullptr; S.cap = 0; S.used = false;
-		const size_t want = std::max<size_t>(64, (size_t)n_views);
-		LOL_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&S.d_views), want * sizeof(lol::View)));
-		LOL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&S.h_views), want * sizeof(lol::View), hipHostMallocDefault));
-		S.cap = want;
-	}
-	if (S.used) {
-		/* The pinned copy is the host's to write once the set's last COPY has run (VIEW_SETS batches ago: in practice long done; a host
-		 * that queues faster than the device renders is held VIEW_SETS batches ahead of it here).  The device copy is this batch's once
-		 * the set's last LAUNCH has finished, whatever stream it ran on. */
-		LOL_HIP(ctx, hipEventSynchronize(S.copied));
-		LOL_TRY(wait_on_stream(ctx, s, S.done));
-	}
-	const bool settle = ctx->shadow_settle, finite = ctx->finite_scene;
+/* the view records of a batch: the next set of the ring filled — everything a frame decides from its camera, per record — and its
+ * copy to the device queued on `s`.  The batch's last launch goes to ring_done with the set. */
+static int queue_view_records(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int max_steps, hipStream_t s, RingSet** out) {
+	RingSet& S = ctx->view_records.next();
+	const size_t bytes = (size_t)n_views * sizeof(lol::View);
+	LOL_TRY(ring_take(ctx, S, bytes, std::max<size_t>(64, (size_t)n_views) * sizeof(lol::View), RING_PINNED, s, nullptr, "records of a batch of views"));
+	lol::View* views = reinterpret_cast<lol::View*>(S.h_buf);
 	for (int v = 0; v < n_views; v++) {
-		lol::View& V = S.h_views[v];
+		lol::View& V = views[v];
 		memcpy(&V.cam, &cams[v], sizeof V.cam);
-		const bool sane = camera_sane(cams[v]);
-		V.flags = settle && sane ? lol::FLAG_SHADOW_SETTLED : 0u;
-		V.ops_offset = finite && sane ? ctx->n_mops * (uint32_t)lol::MOP_DWORDS : 0u;
-		V.first_dist = 0.f; V.first_id = 0u;
-		if (first_step(ctx, cams[v], max_steps)) { V.flags |= lol::FLAG_FIRST_STEP; V.first_dist = ctx->first_dist; V.first_id = ctx->first_id; }
+		V.flags = 0u; V.first_dist = 0.f; V.first_id = 0u;
+		const bool first = first_step(ctx, cams[v], max_steps);
+		V.ops_offset = camera_fields(V, cams[v], ctx->finite_scene, ctx->shadow_settle, first, ctx->first_dist, ctx->first_id)
+		               ? ctx->n_mops * (uint32_t)lol::MOP_DWORDS : 0u;
 	}
-	LOL_HIP(ctx, hipMemcpyAsync(S.d_views, S.h_views, (size_t)n_views * sizeof(lol::View), hipMemcpyHostToDevice, s));
-	LOL_HIP(ctx, hipEventRecord(S.copied, s));
 	*out = &S;
-	return LOL_GPU_OK;
+	const hipError_t e = ring_copy(S, bytes, s);
+	return e == hipSuccess ? LOL_GPU_OK : ring_done(ctx, S, s, e, "copy of the records of a batch of views");
 }
-
-/* behind the batch's last launch (`e`: what it returned).  Recorded even behind a failed launch: the copy is queued, and the set's
- * next user must find both events recorded. */
-static int view_records_done(lol_gpu* ctx, lol_gpu::ViewSet& S, hipStream_t s, hipError_t e, const char* what) {
-	const hipError_t e2 = hipEventRecord(S.done, s);
-	S.used = true;
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, what, e);
-	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (batch of views)", e2);
-	return LOL_GPU_OK;
-}
+static const lol::View* device_views(const RingSet* S) { return reinterpret_cast<const lol::View*>(S->d_buf); }
 
 static void batch_range(const char* what, int n_views, int w, int h) {
 	g_roctx.init();
@@ -1086,14 +1118,14 @@ static int render_views_plain(lol_gpu* ctx, const lol_frame_camera* cams, int n_
 	batch_launch(ctx, w, h, max_steps, dst, pitch_bytes, dbg, L);
 	hipStream_t s;
 	LOL_TRY(batch_stream(ctx, stream, &s));
-	lol_gpu::ViewSet* S = nullptr;
+	RingSet* S = nullptr;
 	LOL_TRY(queue_view_records(ctx, cams, n_views, max_steps, s, &S));
-	lol::BatchTail B = { S->d_views, (unsigned long long)(view_stride_bytes / 4) };
+	lol::BatchTail B = { device_views(S), (unsigned long long)(view_stride_bytes / 4) };
 	batch_range("batch", n_views, w, h);
 	void* args[] = { &L, &B };
 	const hipError_t e = launch_family(ctx, FAM_BATCH, dbg && dbg->steps, args, grid, s);
 	if (g_roctx.pop) g_roctx.pop();
-	return view_records_done(ctx, *S, s, e, "kernel launch (batch of views)");
+	return ring_done(ctx, *S, s, e, "kernel launch (batch of views)");
 }
 
 int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int w, int h, int max_steps,
@@ -1112,8 +1144,7 @@ int lol_gpu_render_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views
  *  2. adaptive_classify_views: every view's mask from its own pixels; unrefined pixels go to `dst`, refined ones to the view's list;
  *  3. view_group_prefix: the lists' lengths into the numbering of their groups;
  *  4. the refine pass (lol_kernel_batch_aa.h, render_aa_view_lists) on a grid that fills the device.
- * Scratch: the next set of a ring of its own (lol_gpu_internal.h, ViewAdaptiveSet), behind the batch that used it last; the host
- * waits for that batch only where the set has to grow, or on one of HIP's special stream handles.
+ * Scratch: the next set of a ring of its own (lol_gpu_internal.h, lol_gpu::adaptive_batches), under the rings' protocol (ring_take).
  */
 static int render_views_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_frame_camera* cams, int n_views, int samples, int contrast,
                                  size_t view_stride_bytes, const lol_gpu_debug* dbg, hipStream_t s) {
@@ -1123,20 +1154,16 @@ static int render_views_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_f
 	const uint32_t per_wave = 64u / (uint32_t)(samples * samples);
 	/* (every view's list ends with a group that may be partly filled: at most n_views groups more than the entries need) */
 	const uint32_t blocks = (uint32_t)std::min<size_t>(ctx->adaptive_blocks, (px + per_wave - 1) / per_wave * (size_t)n_views);
-	const int si = (int)(ctx->view_adaptive_rr++ % lol_gpu::VIEW_ADAPTIVE_SETS);
-	lol_gpu::ViewAdaptiveSet& S = ctx->view_adaptive_sets[si];
-	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-	const size_t tables = 2 * ((size_t)n_views + 1);
-	LOL_TRY(grow_scratch(ctx, S, S.done, (3 * all + tables + (size_t)ctx->adaptive_blocks * 64) * 4, si, ctx->view_adaptive_last,
-	                     &ctx->fail_view_scratch, "scratch of an adaptive batch"));
+	lol_gpu::AdaptiveBatchSet& S = ctx->adaptive_batches.next();
+	const size_t need = (3 * all + 2 * ((size_t)n_views + 1) + (size_t)ctx->adaptive_blocks * 64) * 4;
+	LOL_TRY(ring_take(ctx, S, need, need, RING_SCRATCH, s, &ctx->fail_view_scratch, "scratch of an adaptive batch"));
 	uint32_t* xrgb = S.d_buf;
 	uint32_t* ids = xrgb + all;
 	uint32_t* lists = ids + all;
 	uint32_t* counts = lists + all;
 	uint32_t* prefix = counts + n_views + 1;
 	uint32_t* lanes = prefix + n_views + 1;
-	if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.done));
-	lol_gpu::ViewSet* V = nullptr;
+	RingSet* V = nullptr;
 	LOL_TRY(queue_view_records(ctx, cams, n_views, A.max_steps, s, &V));
 	const char* what = "hipMemsetAsync (adaptive batch)";
 	hipError_t e = hipMemsetAsync(counts, 0, ((size_t)n_views + 1) * 4, s);
@@ -1144,7 +1171,7 @@ static int render_views_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_f
 	/* 1. the plain batch */
 	if (e == hipSuccess) {
 		lol::Launch L = plain_pass_of(A, xrgb, ids, dbg);
-		lol::BatchTail B = { V->d_views, (unsigned long long)px };
+		lol::BatchTail B = { device_views(V), (unsigned long long)px };
 		dim3 grid;
 		(void)batch_grid(ctx, w, h, n_views, &grid);      /* (a part of the sample grid the caller has checked) */
 		what = "kernel launch (adaptive batch, plain pass)";
@@ -1170,20 +1197,15 @@ static int render_views_adaptive(lol_gpu* ctx, const lol::Launch& A, const lol_f
 		lol::Launch R = A;
 		R.flags &= ~lol::FLAG_TILE_COLS;                  /* (a one-dimensional grid) */
 		R.tile_order = ctx->d_adaptive_order; R.tile_stride = ctx->adaptive_stride; R.lane_pixels = lanes;
-		lol::BatchTail B = { V->d_views, (unsigned long long)(view_stride_bytes / 4) };
+		lol::BatchTail B = { device_views(V), (unsigned long long)(view_stride_bytes / 4) };
 		lol::BatchLists Q = { lists, counts, prefix, (uint32_t)n_views };
 		what = "kernel launch (adaptive batch, refine pass)";
 		void* args[] = { &R, &B, &Q };
 		e = launch_family(ctx, FAM_BATCH_AA_LIST, false, args, dim3(blocks), s);
 	}
-	/* (recorded even behind a failed launch, like the view records' event and for the same reason) */
-	const hipError_t e2 = hipEventRecord(S.done, s);
-	S.used = true;
 	S.d_counts = counts; S.n_views = n_views;
-	ctx->view_adaptive_last = si;
-	LOL_TRY(view_records_done(ctx, *V, s, e, what));
-	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (adaptive batch)", e2);
-	return LOL_GPU_OK;
+	ctx->view_adaptive_last = &S;
+	return ring_done(ctx, S, s, e, what, V);
 }
 
 /*
@@ -1221,14 +1243,14 @@ int lol_gpu_render_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, int
 	hipStream_t s;
 	LOL_TRY(batch_stream(ctx, stream, &s));
 	if (adaptive) return render_views_adaptive(ctx, L, cams, n_views, samples, contrast, view_stride_bytes, dbg, s);
-	lol_gpu::ViewSet* S = nullptr;
+	RingSet* S = nullptr;
 	LOL_TRY(queue_view_records(ctx, cams, n_views, max_steps, s, &S));
-	lol::BatchTail B = { S->d_views, (unsigned long long)(view_stride_bytes / 4) };
+	lol::BatchTail B = { device_views(S), (unsigned long long)(view_stride_bytes / 4) };
 	batch_range("supersampled batch", n_views, w, h);
 	void* args[] = { &L, &B };
 	const hipError_t e = launch_family(ctx, FAM_BATCH_AA, false, args, grid, s);
 	if (g_roctx.pop) g_roctx.pop();
-	return view_records_done(ctx, *S, s, e, "kernel launch (supersampled batch of views)");
+	return ring_done(ctx, *S, s, e, "kernel launch (supersampled batch of views)");
 }
 
 /* what lol_gpu_render_views_blend refuses before it looks at anything else, in its order (everything lol_gpu_render_views refuses
@@ -1246,12 +1268,12 @@ static int blend_refused(lol_gpu* ctx, const lol_frame_camera* cams, int n_views
  *  1. the linear-colour batch kernel (lol_kernel_blend.h) over z = v K + k, into the scratch set: everything a batch decides per
  *     view is decided per RECORD (queue_view_records), so a group may mix sane and insane cameras;
  *  2. blend_resolve: each pixel's tree over its K colours, gamma, packing, the stores.
- * Scratch: the next set of a ring of its own (lol_gpu_internal.h, BlendSet), behind the blend that used it last; the host waits for
- * that blend only where the set has to grow, or on one of HIP's special stream handles.  Fixed tile order, like any batch.
+ * Scratch: the next set of a ring of its own (lol_gpu_internal.h, lol_gpu::blends), under the rings' protocol (ring_take).  Fixed
+ * tile order, like any batch.
  * K > 1 here, and `samples` x `samples` samples per pixel: with samples > 1 pass 1 is the supersampled linear kernel
  * (lol_kernel_blend_aa.h) over the SAMPLE grids, on the launch of lol_gpu_render_views_samples.  It reduces a pixel's samples in
- * registers before it stores, so the scratch holds one LinearColour per PIXEL and record either way: the ring, grow_scratch and the
- * resolve pass are the same for both.
+ * registers before it stores, so the scratch holds one LinearColour per PIXEL and record either way: the ring and the resolve pass
+ * are the same for both.
  */
 /* pass 2 of a blend (blend_resolve) behind pass 1's launch `L`, whose scratch `lin` holds the linear colours [v K + k][y][x] */
 static hipError_t launch_blend_resolve(const lol_gpu* ctx, const lol::Launch& L, const uint32_t* scratch, int n_views, int K, int w, int h, void* dst,
@@ -1283,13 +1305,10 @@ static int render_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views,
 		                                              : "blend too large for one launch over all its cameras: fewer views per call");
 	hipStream_t s;
 	LOL_TRY(batch_stream(ctx, stream, &s));
-	const int si = (int)(ctx->blend_rr++ % lol_gpu::BLEND_SETS);
-	lol_gpu::BlendSet& S = ctx->blend_sets[si];
-	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-	LOL_TRY(grow_scratch(ctx, S, S.done, (size_t)n_rays * (size_t)w * (size_t)h * sizeof(lol::LinearColour), si, ctx->blend_last,
-	                     &ctx->fail_view_scratch, "scratch of a blend of views"));
-	if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.done));
-	lol_gpu::ViewSet* V = nullptr;
+	RingSet& S = ctx->blends.next();
+	const size_t need = (size_t)n_rays * (size_t)w * (size_t)h * sizeof(lol::LinearColour);
+	LOL_TRY(ring_take(ctx, S, need, need, RING_SCRATCH, s, &ctx->fail_view_scratch, "scratch of a blend of views"));
+	RingSet* V = nullptr;
 	LOL_TRY(queue_view_records(ctx, cams, n_rays, max_steps, s, &V));
 	batch_range(samples > 1 ? "supersampled blend" : "blend", n_rays, w, h);
 	/* 1. the linear colours: the launch's destination is the scratch (no diagnostics: they are the resolve's) */
@@ -1299,7 +1318,7 @@ static int render_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views,
 		L.fw = (float)(samples * w); L.fh = (float)(samples * h);      /* the size of the sample grid */
 		L.flags |= samples == 4 ? lol::FLAG_SAMPLES_4 : lol::FLAG_SAMPLES_2;
 	}
-	lol::BatchTail B = { V->d_views, 0ull };
+	lol::BatchTail B = { device_views(V), 0ull };
 	const char* what = "kernel launch (blend of views, linear pass)";
 	void* args[] = { &L, &B };
 	hipError_t e = launch_family(ctx, samples > 1 ? FAM_BATCH_AA_LIN : FAM_BATCH_LIN, false, args, grid, s);
@@ -1309,12 +1328,7 @@ static int render_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views,
 		e = launch_blend_resolve(ctx, L, S.d_buf, n_views, K, w, h, dst, pitch_bytes, view_stride_bytes, dbg, s);
 	}
 	if (g_roctx.pop) g_roctx.pop();
-	/* (recorded even behind a failed launch, like the view records' event and for the same reason) */
-	const hipError_t e2 = hipEventRecord(S.done, s);
-	S.used = true;
-	LOL_TRY(view_records_done(ctx, *V, s, e, what));
-	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (blend of views)", e2);
-	return LOL_GPU_OK;
+	return ring_done(ctx, S, s, e, what, V);
 }
 
 int lol_gpu_render_views_blend(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view, int w, int h, int max_steps,
@@ -1373,9 +1387,9 @@ int lol_gpu_interp_variant(lol_gpu* ctx, int* ssize, int* tables_global) {
 
 int lol_gpu_views_refined(lol_gpu* ctx, int64_t* n) {
 	if (!ctx || !n) return LOL_GPU_ERR_ARG;
-	if (ctx->view_adaptive_last < 0 || !ctx->view_adaptive_sets[ctx->view_adaptive_last].d_counts)
-		return fail(ctx, LOL_GPU_ERR_ARG, "no adaptive batch has been launched");
-	lol_gpu::ViewAdaptiveSet& S = ctx->view_adaptive_sets[ctx->view_adaptive_last];
+	/* (`used`: the set's `done` is behind that batch, and its buffer has not been replaced since) */
+	if (!ctx->view_adaptive_last || !ctx->view_adaptive_last->used) return fail(ctx, LOL_GPU_ERR_ARG, "no adaptive batch has been launched");
+	lol_gpu::AdaptiveBatchSet& S = *ctx->view_adaptive_last;
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
 	LOL_HIP(ctx, hipEventSynchronize(S.done));
 	std::vector<uint32_t> c;
@@ -1660,31 +1674,29 @@ int lol_gpu_set_adaptive_samples(lol_gpu* ctx, int contrast) {
 int lol_gpu_adaptive_samples(const lol_gpu* ctx) { return ctx ? ctx->adaptive : LOL_GPU_ERR_ARG; }
 
 /* the set of the context's last adaptive frame, waited for */
-static int last_adaptive_set(lol_gpu* ctx, lol_gpu::AdaptiveSet** out) {
-	if (ctx->adaptive_last < 0 || !ctx->adaptive_sets[ctx->adaptive_last].d_counts)
-		return fail(ctx, LOL_GPU_ERR_ARG, "no adaptive frame has been launched");
-	lol_gpu::AdaptiveSet& S = ctx->adaptive_sets[ctx->adaptive_last];
+static int last_adaptive_set(lol_gpu* ctx, lol_gpu::AdaptiveFrameSet** out) {
+	if (!ctx->adaptive_last || !ctx->adaptive_last->used) return fail(ctx, LOL_GPU_ERR_ARG, "no adaptive frame has been launched");
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	LOL_HIP(ctx, hipEventSynchronize(S.ev[3]));
-	*out = &S;
+	LOL_HIP(ctx, hipEventSynchronize(ctx->adaptive_last->done));
+	*out = ctx->adaptive_last;
 	return LOL_GPU_OK;
 }
 
 int lol_gpu_adaptive_refined(lol_gpu* ctx, int64_t* n) {
 	if (!ctx || !n) return LOL_GPU_ERR_ARG;
-	lol_gpu::AdaptiveSet* S = nullptr;
+	lol_gpu::AdaptiveFrameSet* S = nullptr;
 	LOL_TRY(last_adaptive_set(ctx, &S));
 	uint32_t c = 0;
-	LOL_HIP(ctx, hipMemcpy(&c, S->d_counts, 4, hipMemcpyDeviceToHost));
+	LOL_HIP(ctx, hipMemcpy(&c, S->d_count, 4, hipMemcpyDeviceToHost));
 	*n = c;
 	return LOL_GPU_OK;
 }
 
 int lol_gpu_adaptive_pass_ms(lol_gpu* ctx, float ms[3]) {
 	if (!ctx || !ms) return LOL_GPU_ERR_ARG;
-	lol_gpu::AdaptiveSet* S = nullptr;
+	lol_gpu::AdaptiveFrameSet* S = nullptr;
 	LOL_TRY(last_adaptive_set(ctx, &S));
-	for (int i = 0; i < 3; i++) LOL_HIP(ctx, hipEventElapsedTime(&ms[i], S->ev[i], S->ev[i + 1]));
+	for (int i = 0; i < 3; i++) LOL_HIP(ctx, hipEventElapsedTime(&ms[i], S->ev[i], i < 2 ? S->ev[i + 1] : S->done));
 	return LOL_GPU_OK;
 }
 
@@ -1935,10 +1947,10 @@ const char* lol_gpu_shade_kernel_name(const lol_gpu* ctx) {
  * Scene views (lol_gpu_render_scene_views): a batch whose every record brings a camera AND a scene of the uploaded program's
  * structure (lol_kernel_scenes.h).  Everything an upload decides from the program and a frame from the camera is decided here per
  * record, from that record's own scene and camera, on the host: the three exact skips, finite_scene (which of its two lists the
- * record runs), the primary march's first step (host_sdf on that scene), what an insane camera switches off.  No device proof runs:
- * the lists are built with what the upload proved (lol_gpu::fast), and a smoothness constant it did not prove takes the plain sminf.
- * One copy — the records and, behind them, every record's lists, tables and numbers — from a ring of sets of their own under
- * view_sets' rules, and with K = 1 one launch; a blend adds the resolve pass and scratch ring of lol_gpu_render_views_blend.
+ * record runs), the primary march's first step (program_first_step on that scene), what an insane camera switches off.  No device
+ * proof runs: the lists are built with what the upload proved (lol_gpu::fast), and a smoothness constant it did not prove takes the
+ * plain sminf.  One copy — the records and, behind them, every record's lists, tables and numbers — from a ring of sets of their own
+ * (lol_gpu::scene_view_records), and with K = 1 one launch; a blend adds the resolve pass and scratch ring of lol_gpu_render_views_blend.
  * The context's scene, kernels, keys, tile-order state, sample settings and view-record ring are neither read nor changed.
  */
 static bool same_structure(const lol_program& A, const lol_program& B) {
@@ -1988,26 +2000,19 @@ static int build_scene_records(lol_gpu* ctx, const lol_frame_camera* cams, const
 		lol::SceneView& V = views[(size_t)r];
 		memset(&V, 0, sizeof V);
 		memcpy(&V.cam, &cam, sizeof V.cam);
-		const bool sane = camera_sane(cam), finite = shadow_settle_ok(P);
+		const bool finite = shadow_settle_ok(P);
 		const unsigned want = ctx->want_skips;
-		V.flags = ((want & 1u) && miss_skip_ok(P) ? lol::FLAG_MISS_SKIP : 0u) | ((want & 2u) && dark_skip_ok(P) ? lol::FLAG_DARK_SKIP : 0u) |
-		          ((want & 4u) && finite && sane ? lol::FLAG_SHADOW_SETTLED : 0u);
-		/* the first step (first_step, on this record's scene): a sane camera, no negative zero in its origin, a value in [EPSILON, MAX_DIST] */
-		if (max_steps >= 1 && sane) {
-			const float origin[3] = { cam.origin.x, cam.origin.y, cam.origin.z };
-			uint32_t bits[3];
-			memcpy(bits, origin, sizeof bits);
-			float d = 0.f; uint32_t id = 0;
-			if (bits[0] != 0x80000000u && bits[1] != 0x80000000u && bits[2] != 0x80000000u && host_sdf(P, origin, stack, &d, &id) &&
-			    d >= 0.001f && d <= 100.f) { V.flags |= lol::FLAG_FIRST_STEP; V.first_dist = d; V.first_id = id; }
-		}
+		V.flags = ((want & 1u) && miss_skip_ok(P) ? lol::FLAG_MISS_SKIP : 0u) | ((want & 2u) && dark_skip_ok(P) ? lol::FLAG_DARK_SKIP : 0u);
+		float d = 0.f; uint32_t id = 0;
+		const bool first = program_first_step(P, cam, max_steps, stack, &d, &id);      /* (on this record's scene: nothing is kept) */
+		const bool second_list = camera_fields(V, cam, finite, (want & 4u) && finite, first, d, id);
 		V.ambient[0] = P.ambient_color.x; V.ambient[1] = P.ambient_color.y; V.ambient[2] = P.ambient_color.z;
 		if (lists) {
 			uint32_t n_mops = 0;
 			if (!build_interp_lists(P, ctx->fast, cull, mops, n_mops)) return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "interpreter lists differ in length");
 			align();
 			V.n_mops = n_mops;
-			V.ops_offset = (uint32_t)data.size() + (finite && sane ? n_mops * (uint32_t)lol::MOP_DWORDS : 0u);
+			V.ops_offset = (uint32_t)data.size() + (second_list ? n_mops * (uint32_t)lol::MOP_DWORDS : 0u);
 			data.insert(data.end(), mops.begin(), mops.end());
 		}
 		align();
@@ -2033,38 +2038,15 @@ static int build_scene_records(lol_gpu* ctx, const lol_frame_camera* cams, const
 }
 
 /* the next set of the ring filled with the records and their data, and its copy to the device queued on `s` (queue_view_records) */
-static int queue_scene_records(lol_gpu* ctx, const std::vector<lol::SceneView>& views, const std::vector<uint32_t>& data, hipStream_t s,
-                               lol_gpu::SceneViewSet** out) {
-	lol_gpu::SceneViewSet& S = ctx->scene_view_sets[ctx->scene_view_rr++ % lol_gpu::SCENE_VIEW_SETS];
-	if (!S.copied) LOL_HIP(ctx, hipEventCreateWithFlags(&S.copied, hipEventDisableTiming));
-	if (!S.done) LOL_HIP(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+static int queue_scene_records(lol_gpu* ctx, const std::vector<lol::SceneView>& views, const std::vector<uint32_t>& data, hipStream_t s, RingSet** out) {
+	RingSet& S = ctx->scene_view_records.next();
 	const size_t head = views.size() * lol::SCENE_VIEW_DWORDS, need = head + data.size();
-	if (need > S.cap) {
-		if (S.used) LOL_HIP(ctx, hipEventSynchronize(S.done));
-		if (S.d_buf) (void)hipFree(S.d_buf);
-		if (S.h_buf) (void)hipHostFree(S.h_buf);
-		S.d_buf = nullptr; S.h_buf = nullptr; S.cap = 0; S.used = false;
-		const size_t want = std::max<size_t>(4096, need + need / 2);
-		hipError_t me = hipMalloc(reinterpret_cast<void**>(&S.d_buf), want * 4);
-		if (me == hipSuccess) me = hipHostMalloc(reinterpret_cast<void**>(&S.h_buf), want * 4, hipHostMallocDefault);
-		if (me != hipSuccess) {
-			if (S.d_buf) (void)hipFree(S.d_buf);
-			S.d_buf = nullptr; S.h_buf = nullptr;
-			(void)hipGetLastError();
-			return fail(ctx, LOL_GPU_ERR_HIP, "records of a batch of scene views", me);
-		}
-		S.cap = want;
-	}
-	if (S.used) {
-		LOL_HIP(ctx, hipEventSynchronize(S.copied));
-		LOL_TRY(wait_on_stream(ctx, s, S.done));
-	}
+	LOL_TRY(ring_take(ctx, S, need * 4, std::max<size_t>(4096, need + need / 2) * 4, RING_PINNED, s, nullptr, "records of a batch of scene views"));
 	memcpy(S.h_buf, views.data(), head * 4);
 	if (!data.empty()) memcpy(S.h_buf + head, data.data(), data.size() * 4);
-	LOL_HIP(ctx, hipMemcpyAsync(S.d_buf, S.h_buf, need * 4, hipMemcpyHostToDevice, s));
-	LOL_HIP(ctx, hipEventRecord(S.copied, s));
 	*out = &S;
-	return LOL_GPU_OK;
+	const hipError_t e = ring_copy(S, need * 4, s);
+	return e == hipSuccess ? LOL_GPU_OK : ring_done(ctx, S, s, e, "copy of the records of a batch of scene views");
 }
 
 static int render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views, int K, int w, int h,
@@ -2092,16 +2074,13 @@ static int render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const 
 	std::vector<lol::SceneView> views;
 	std::vector<uint32_t> data;
 	LOL_TRY(build_scene_records(ctx, cams, scenes, n, max_steps, !ctx->tiers.structure, views, data));
-	lol_gpu::BlendSet* scratch = nullptr;
+	RingSet* scratch = nullptr;
 	if (K > 1) {
-		const int si = (int)(ctx->blend_rr++ % lol_gpu::BLEND_SETS);
-		scratch = &ctx->blend_sets[si];
-		if (!scratch->done) LOL_HIP(ctx, hipEventCreateWithFlags(&scratch->done, hipEventDisableTiming));
-		LOL_TRY(grow_scratch(ctx, *scratch, scratch->done, (size_t)n * (size_t)w * (size_t)h * sizeof(lol::LinearColour), si, ctx->blend_last,
-		                     &ctx->fail_view_scratch, "scratch of a blend of scene views"));
-		if (scratch->used) LOL_TRY(wait_on_stream(ctx, s, scratch->done));
+		scratch = &ctx->blends.next();
+		const size_t need = (size_t)n * (size_t)w * (size_t)h * sizeof(lol::LinearColour);
+		LOL_TRY(ring_take(ctx, *scratch, need, need, RING_SCRATCH, s, &ctx->fail_view_scratch, "scratch of a blend of scene views"));
 	}
-	lol_gpu::SceneViewSet* S = nullptr;
+	RingSet* S = nullptr;
 	LOL_TRY(queue_scene_records(ctx, views, data, s, &S));
 	batch_range(K > 1 ? "blend of scene views" : "scene views", n, w, h);
 	lol::Launch L;
@@ -2117,17 +2096,7 @@ static int render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const 
 		e = launch_blend_resolve(ctx, L, scratch->d_buf, n_views, K, w, h, dst, pitch_bytes, view_stride_bytes, dbg, s);
 	}
 	if (g_roctx.pop) g_roctx.pop();
-	/* (both events recorded even behind a failed launch: the copy is queued, and the sets' next users must find them recorded) */
-	hipError_t e2 = hipEventRecord(S->done, s);
-	S->used = true;
-	if (scratch) {
-		const hipError_t e3 = hipEventRecord(scratch->done, s);
-		scratch->used = true;
-		if (e2 == hipSuccess) e2 = e3;
-	}
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, what, e);
-	if (e2 != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "hipEventRecord (scene views)", e2);
-	return LOL_GPU_OK;
+	return ring_done(ctx, *S, s, e, what, scratch);
 }
 
 extern "C" {

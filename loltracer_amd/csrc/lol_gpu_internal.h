@@ -265,6 +265,24 @@ struct SpecTiers {
 	~SpecTiers();                             /* waits for every run (a thread must not outlive the library) and unloads both kernels */
 };
 
+/* One set of a ring of per-call device sets, and the ring.  A call takes the ring's next set, whatever its stream, queues its work
+ * through it and records `done` behind the last of it; the set's next user — N calls later — waits for `done` on its stream, and on
+ * the host only where the set must grow or the stream is one of HIP's special handles.  A pinned set is filled by the host, copied to
+ * the device on the call's stream and `copied` recorded behind the copy: the host may write the pinned half again once that has run.
+ * Written once, for every ring of the context, in lol_gpu.hip (ring_take, ring_copy, ring_done, ring_free). */
+struct RingSet {
+	uint32_t*  d_buf = nullptr;
+	uint32_t*  h_buf = nullptr;              /* pinned, of as many bytes; rings of records only */
+	size_t     bytes = 0;                    /* each holds */
+	hipEvent_t copied = nullptr, done = nullptr;
+	bool       used = false;                 /* the set's events have been recorded: somebody may still be using it */
+};
+template <class Set, int N> struct Ring {
+	Set      sets[N];
+	unsigned rr = 0;
+	Set&     next() { return sets[rr++ % N]; }
+};
+
 struct lol_gpu {
 	int          device = -1;
 	hipStream_t  stream = nullptr;
@@ -307,73 +325,36 @@ struct lol_gpu {
 	int          adaptive = -1;          /* lol_gpu_set_adaptive_samples: the contrast T, or -1 (off) */
 	int          want_scene_views = 0;   /* lol_gpu_set_scene_views: the next upload also compiles the structure module */
 	FastPaths    fast;                   /* what the upload proved on the device: the lists of scene views are built with it */
-	/* The records of scene views and their data (lol_gpu.hip, lol_gpu_render_scene_views): a ring of sets of their own, one per call, under view_sets' rules.
-	 * One buffer per set: the records, and behind them every record's lists, tables and numbers. */
-	struct SceneViewSet {
-		uint32_t*  h_buf = nullptr;          /* pinned */
-		uint32_t*  d_buf = nullptr;
-		size_t     cap = 0;                  /* dwords both hold */
-		hipEvent_t copied = nullptr, done = nullptr;
-		bool       used = false;             /* both events have been recorded */
-	};
-	static constexpr int SCENE_VIEW_SETS = 8;
-	SceneViewSet scene_view_sets[SCENE_VIEW_SETS];
-	unsigned     scene_view_rr = 0;
 	unsigned     module_switches = 0; /* the switch_bit()s set by lol_gpu_set_view_batches ... lol_gpu_set_shade_queries (MODULE_SWITCHES) */
 	void*        d_pick = nullptr;       /* lol_gpu_pick's device memory, from the first pick on: xy [2] | dist | id | steps | normal [3] */
-	/* The view records of batches (lol_gpu_render_views, lol_gpu.hip): a ring of sets, one per batch, whatever its stream.  A batch
-	 * fills its set's pinned host copy, queues the copy to the device and the launch behind it on its stream, and records `done`;
-	 * the next batch through the set waits for `copied` on the host (the pinned copy is the host's to write again) and for `done`
-	 * on its stream.  Sets grow with the batch, freed in lol_gpu_destroy. */
-	struct ViewSet {
-		lol::View* h_views = nullptr;        /* pinned */
-		lol::View* d_views = nullptr;
-		size_t     cap = 0;                  /* views both hold */
-		hipEvent_t copied = nullptr, done = nullptr;
-		bool       used = false;             /* both events have been recorded */
+	/* The five rings of per-call device sets (RingSet above; the protocol: ring_take, ring_copy, ring_done, ring_free in lol_gpu.hip).
+	 * Sets grow with what they serve and are freed in lol_gpu_destroy.
+	 *   view_records        a batch's lol::View records, pinned and on the device (queue_view_records): at least 64 views a set
+	 *   scene_view_records  the records of scene views and, behind them, every record's lists, tables and numbers
+	 *                       (lol_gpu_render_scene_views): at least 4096 dwords a set, grown by half more than is needed
+	 *   adaptive_frames     scratch of adaptive frames (render_adaptive): xrgb [w h] | ids [w h] | list [w h] | count [64] | lane table
+	 *                       [64 per refine block].  `done` is TIMED: ev[0] marks a frame's start, ev[1] and ev[2] the ends of its first
+	 *                       two passes, `done` its end (lol_gpu_adaptive_pass_ms)
+	 *   adaptive_batches    scratch of adaptive batches (render_views_adaptive): xrgb [n w h] | ids [n w h] | lists [n w h] | counts
+	 *                       [n + 1] | prefix [n + 1] | lane table — for n views of w x h: 12 n w h bytes + 8 (n + 1) + 256 per refine block
+	 *   blends              scratch of blends (render_blend) and of blends of scene views: the linear colours [n K][h][w] of pass 1 —
+	 *                       per PIXEL, whatever the samples —, a lol::LinearColour of 16 bytes each
+	 * The two adaptive rings remember their last set, which lol_gpu_adaptive_refined / _pass_ms and lol_gpu_views_refined read. */
+	Ring<RingSet, 8> view_records, scene_view_records;
+	struct AdaptiveFrameSet : RingSet {
+		hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
+		uint32_t*  d_count = nullptr;        /* in d_buf: the length of the list of the set's last frame */
 	};
-	static constexpr int VIEW_SETS = 8;
-	ViewSet      view_sets[VIEW_SETS];
-	unsigned     view_rr = 0;
-	/* Scratch of adaptive frames and batches: two rings of sets, one set per frame or batch, whatever its stream; sets grow with what
-	 * they serve (grow_scratch, lol_gpu.hip), freed in lol_gpu_destroy */
-	struct ScratchSet {
-		uint32_t*  d_buf = nullptr;
-		size_t     bytes = 0;
-		uint32_t*  d_counts = nullptr;       /* in d_buf: the length(s) of the list(s) of the set's last frame or batch */
-		bool       used = false;             /* the event that ends the set's last use has been recorded */
+	Ring<AdaptiveFrameSet, 4> adaptive_frames;
+	AdaptiveFrameSet* adaptive_last = nullptr;
+	struct AdaptiveBatchSet : RingSet {
+		uint32_t*  d_counts = nullptr;       /* in d_buf: the lengths of the lists of the set's last batch ... */
+		int        n_views = 0;              /* ... one per view */
 	};
-	/* ... of frames (render_adaptive): xrgb [w h] | ids [w h] | list [w h] | count [64] | lane table [64 per refine block].  A frame
-	 * waits on its set's `ev[3]` (behind the last frame that used it) with hipStreamWaitEvent and records it again at its end; ev[0]
-	 * marks its start, ev[1] and ev[2] the ends of its first two passes (lol_gpu_adaptive_pass_ms). */
-	struct AdaptiveSet : ScratchSet {
-		hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-	};
-	static constexpr int ADAPTIVE_SETS = 4;
-	AdaptiveSet  adaptive_sets[ADAPTIVE_SETS];
-	/* ... of batches (render_views_adaptive), a ring of its own: xrgb [n w h] | ids [n w h] | lists [n w h] | counts [n + 1] |
-	 * prefix [n + 1] | lane table — for n views of w x h: 12 n w h bytes + 8 (n + 1) + 256 per refine block.  A batch waits on its
-	 * set's `done` (behind the last batch that used it) and records it again at its end. */
-	struct ViewAdaptiveSet : ScratchSet {
-		int        n_views = 0;              /* how many views the set's last batch had: d_counts holds that many */
-		hipEvent_t done = nullptr;
-	};
-	static constexpr int VIEW_ADAPTIVE_SETS = 4;
-	ViewAdaptiveSet view_adaptive_sets[VIEW_ADAPTIVE_SETS];
-	unsigned     view_adaptive_rr = 0;
-	int          view_adaptive_last = -1;      /* the set of the last adaptive batch (lol_gpu_views_refined) */
+	Ring<AdaptiveBatchSet, 4> adaptive_batches;
+	AdaptiveBatchSet* view_adaptive_last = nullptr;
+	Ring<RingSet, 4> blends;
 	int          fail_view_scratch = 0;        /* lol_gpu_testing_fail_view_scratch: that many scratch allocations of adaptive batches and blends still fail */
-	/* ... of blends (lol_gpu_render_views_blend, lol_gpu_render_views_blend_samples), a ring of its own: the linear colours [n K][h][w]
-	 * of pass 1 — per PIXEL, whatever the samples —, a lol::LinearColour of 16 bytes each.  A blend waits on its set's `done` (behind the last blend that used it) and records it again at its end. */
-	struct BlendSet : ScratchSet {
-		hipEvent_t done = nullptr;
-	};
-	static constexpr int BLEND_SETS = 4;
-	BlendSet     blend_sets[BLEND_SETS];
-	unsigned     blend_rr = 0;
-	int          blend_last = -1;              /* (grow_scratch's `last`: nothing reads a blend's set afterwards) */
-	unsigned     adaptive_rr = 0;
-	int          adaptive_last = -1;     /* the set of the last adaptive frame (lol_gpu_adaptive_refined) */
 	uint32_t*    d_adaptive_order = nullptr;   /* the refine pass's block -> lane-table slot table: slot b at tile_slot(b, stride) */
 	uint32_t     adaptive_blocks = 0, adaptive_stride = 0;      /* its size in blocks (the most a refine grid has); ceil(blocks / 8) */
 	int          fail_uploads = 0;       /* lol_gpu_testing_fail_uploads: that many uploads still fail at the copy */
@@ -415,9 +396,11 @@ struct lol_gpu {
 		float mon_ratio[MONITOR_WINDOW] = {};
 	} tiles;
 	int          generation = 0;         /* uploads so far */
-	/* the primary march's first step (first_step): sdf(camera origin) of program `first_gen`, kept while the camera stays where it is */
+	/* the primary march's first step (first_step): program_first_step of program `first_gen` at `first_origin`, kept while the camera
+	 * stays where it is */
 	float        first_origin[3] = { 0, 0, 0 };
 	int          first_gen = -1;
+	bool         first_taken = false;
 	float        first_dist = 0;
 	uint32_t     first_id = 0;
 	std::vector<float> first_stack;

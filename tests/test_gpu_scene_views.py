@@ -395,6 +395,70 @@ def test_ten_calls_back_to_back(torch_cuda, scenes, arm, streams):
         r.close()
 
 
+@pytest.mark.parametrize("arm", ARMS)
+def test_blends_of_views_and_of_scene_views_share_one_scratch_ring(torch_cuda, scenes, arm):
+    """Three blends of views and three blends of scene views (K = 2, 2 views of 16 x 8 each), alternating, queued back to back with
+    NO wait between them on one context with two streams: six uses of the scratch ring both calls take their sets from, which has
+    4 — the fifth and sixth take a set whose last user, a call of the OTHER kind, may still be running.  Each of the six is its own
+    reference.  Queued once."""
+    base = scenes["scene4"]
+    w, h, k = 16, 8, 2
+    orbit = S.orbit_cameras(base, 16)
+    moved = moving(scenes, "scene4", 6, k)                                     # 12 scenes: four for each call of scene views
+    calls = []
+    for i in range(6):
+        cams = [orbit[(2 * i + j) % 16] for j in range(2 * k)]                   # no two calls under the same cameras
+        calls.append((cams, moved[4 * (i // 2):4 * (i // 2) + 4] if i % 2 else [base] * (2 * k)))
+    r = open_renderer(base, arm)
+    try:
+        r.set_frames_in_flight(2)
+        outs = [V.alloc_batch(torch_cuda, 2, w, h, w + 3, h * (w + 3) + 5, ("rgb",)) for _ in calls]
+        torch_cuda.cuda.synchronize()
+        for i, (out, (cams, scs)) in enumerate(zip(outs, calls)):
+            if i % 2:
+                r.render_scene_views_into(out["frame"].data_ptr(), cams, scs, w, h, k, MAX_STEPS, pitch_bytes=(w + 3) * 4,
+                                          view_stride_bytes=(h * (w + 3) + 5) * 4, debug=out["dbg"])
+            else:
+                r.render_blended_views_into(out["frame"].data_ptr(), cams, k, w, h, MAX_STEPS, pitch_bytes=(w + 3) * 4,
+                                            view_stride_bytes=(h * (w + 3) + 5) * 4, debug=out["dbg"])
+        r.sync()
+        for i, (out, (cams, scs)) in enumerate(zip(outs, calls)):
+            b = V.collect(out, *out["geom"])
+            px, rgb = R.render_blend(scs, cams, k, w, h, max_steps=MAX_STEPS)
+            assert np.array_equal(b["xrgb"], px), f"call {i} ({arm}): pixels differ from the reference"
+            assert np.array_equal(bits(b["rgb"]), bits(rgb)), f"call {i} ({arm}): rgb differs from the reference"
+            assert V.untouched_outside_views(b, 2, w, h, w + 3, h * (w + 3) + 5), f"call {i}"
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("arm", ARMS)
+def test_the_first_step_of_a_record_is_the_frames(torch_cuda, scenes, arm):
+    """Two records whose camera decides the primary march's first step in a way of its own: an origin with a negative zero in x (the
+    step is not given: every lane takes it), and an origin inside scene4's blob (the first value lies below EPSILON: the step is
+    not given either, and ends the march).  Hit distance, hit id and both step counts of each record equal those of the frame a
+    fresh context renders under that camera after uploading that record's scene."""
+    base = scenes["scene4"]
+    a, _, c = variants(scenes, "scene4")                                        # (c differs from scene4 in materials alone: the blob is where it was)
+    scs = [a, c]
+    cams = [V.cam_at(-0.0, 6.0, 3.0, 0.0, -0.5, -1.0), V.cam_at(0.0, 1.0, -6.0, 0.0, 0.0, -1.0)]
+    r = open_renderer(base, arm)
+    try:
+        b = render(torch_cuda, r, cams, scs)
+        for v in range(2):
+            fresh = gpu.Renderer(0, specialize=False)
+            try:
+                fresh.prepare(scs[v])
+                g = V.render_single(torch_cuda, fresh, cams[v], W, H, MAX_STEPS)
+            finally:
+                fresh.close()
+            V.assert_view_is_frame(b, v, g, f"record {v} ({arm})")
+        inside = b["dist"][1]
+        assert (b["steps"][1] & 0xFFFF).max() == 1 and float(inside.max()) < 0.001, "the second camera is not inside the blob"
+    finally:
+        r.close()
+
+
 def test_a_call_before_the_structure_module_is_loaded(torch_cuda, scenes):
     """a context that asked for the module renders from the first call on: on the interpreter's kernels (with the upload's fast paths)
     while the module is being compiled, on the module once a call's boundary or specialize_wait has loaded it — the same frames"""

@@ -447,6 +447,40 @@ def test_batches_in_flight_on_two_streams(torch_cuda, scenes):
         r.close()
 
 
+def test_the_scratch_grows_at_the_wrap_of_its_ring(torch_cuda, scenes):
+    """Five adaptive batches (s = 2, T = 16) queued back to back with NO wait between them, over two streams.  The first four hold 2
+    views of 16 x 8 and fill the ring of scratch sets; the fifth holds 3 views of 32 x 16, so it takes set 0 again and must GROW it
+    while the first batch, which classified its pixels there, may still be in flight.  Every pixel of every batch is the adaptive
+    reference's, and views_refined() afterwards is the reference's count for the fifth batch: the ring's last set is the one that
+    grew.  Queued once."""
+    sc = scenes["scene4"]
+    orbit = S.orbit_cameras(sc, K)
+    s, T = 2, 16
+    plans = [(16, 8, [0, 1]), (16, 8, [2, 3]), (16, 8, [4, 5]), (16, 8, [6, 8]), (32, 16, list(SOME_BUT_NOT_ALL))]
+    r = gpu.Renderer(0)
+    r.set_view_samples(True)
+    r.prepare(sc)
+    try:
+        r.set_frames_in_flight(2)
+        outs = [alloc(torch_cuda, len(idx), w, h, pitch_px=w + 3, stride_px=h * (w + 3) + 5) for w, h, idx in plans]
+        torch_cuda.cuda.synchronize()
+        for out, (w, h, idx) in zip(outs, plans):
+            queue(r, out, [orbit[i] for i in idx], s, T)
+        r.sync()
+        for g, (out, (w, h, idx)) in enumerate(zip(outs, plans)):
+            collect(out)
+            assert out["outside_untouched"], f"batch {g}"
+            refined = 0
+            for v, i in enumerate(idx):
+                ox, orgb, m = oracle("scene4", sc, i, orbit[i], w, h, s, T)
+                assert np.array_equal(out["xrgb"][v], ox) and np.array_equal(bits(out["rgb"][v]), bits(orgb)), f"batch {g} view {v}"
+                refined += int(m.sum())
+        assert 0 < refined < 3 * 32 * 16                         # (of the fifth batch: the loop's last)
+        assert r.views_refined() == refined
+    finally:
+        r.close()
+
+
 def test_late_switch_and_tiering(torch_cuda, scenes):
     """The switch set after the upload: the module has none of the new kernels, batches run on the interpreter's, same pixels (and
     frames keep the scene's kernel).  The switch on, one batch before specialize_wait() and one after: same pixels from whichever

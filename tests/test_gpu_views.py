@@ -377,6 +377,39 @@ def test_batches_in_flight_on_two_streams(torch_cuda, scenes):
         r.close()
 
 
+def test_the_view_records_grow_at_the_wrap_of_their_ring(torch_cuda, scenes):
+    """Nine batches queued back to back with NO wait between them, over two streams.  The first eight hold 2 views each and fill the
+    ring of view records, whose sets hold 64 views at least; the ninth holds 65 — one past that floor —, so it takes set 0 again and
+    must GROW it while the first batch, which read its records from there, may still be in flight.  Every view of every batch is
+    the oracle's frame of ITS camera (no two views share one), and nothing is written outside the views.  Queued once."""
+    sc = scenes["scene4"]
+    w, h = 16, 8
+    sizes = [2] * 8 + [65]
+    index, at = [], 0
+    for k in sizes:
+        index.append(list(range(at, at + k)))
+        at += k
+    groups = [[bench.orbit_camera(i, 256) for i in idx] for idx in index]
+    r = gpu.Renderer(0)
+    r.set_view_batches(True)
+    r.prepare(sc)
+    try:
+        r.set_frames_in_flight(2)
+        pitch_px, stride_px = w + 3, h * (w + 3) + 5           # padding after every row and every view: it keeps its sentinel
+        outs = [alloc_batch(torch_cuda, len(cams), w, h, pitch_px, stride_px) for cams in groups]
+        torch_cuda.cuda.synchronize()
+        for out, cams in zip(outs, groups):
+            queue_batch(r, out, cams)
+        r.sync()
+        for g, (out, cams) in enumerate(zip(outs, groups)):
+            collect(out, *out["geom"])
+            assert untouched_outside_views(out, len(cams), w, h, pitch_px, stride_px), f"batch {g}"
+            for v, cam in enumerate(cams):
+                assert_view_is_oracle(out, v, oracle_view("scene4-orbit", sc, index[g][v], cam, w, h), f"batch {g} view {v}")
+    finally:
+        r.close()
+
+
 def test_the_orbit_host_writes_one_ppm_per_view(torch_cuda, scenes, tmp_path):
     """python -m loltracer_amd SCENE --orbit K --size WxH -o DIR: K PPMs from one batch, each the oracle's frame under
     scene.orbit_cameras(scene, K)[v]; options a batch cannot honour are refused, not ignored."""

@@ -12,7 +12,9 @@ lasts at least --window-s; a host clock around the window, which ends in a devic
 upload: device events would not see that); --windows windows per arm, median and range recorded, in milliseconds per 64 frames.
 The programs and frame cameras are made before the windows: flattening a scene is the host's work in every arm.
 With --shutter K the arms b, f and c are also timed as blends of K scenes per frame (there is no arm a for a blend: a context has one
-scene).  One JSON document on stdout (or --out FILE).
+scene).  With --small-batches REPS, what a CALL costs the host: REPS plain batches of 8 views at 64x36 back to back per window, a
+host clock around the calls alone and around the calls and the synchronise behind them, in microseconds per call.  One JSON
+document on stdout (or --out FILE).
 
     python tools/scene_views_rate.py --out profiles/r18_scene_views_rate.json                                  (on the GPU box)
 """
@@ -71,6 +73,8 @@ def main():
     ap.add_argument("--scene", default="scene4")
     ap.add_argument("--frames", type=int, default=FRAMES)
     ap.add_argument("--shutter", type=int, default=4, choices=(1, 2, 4, 8, 16))
+    ap.add_argument("--small-batches", type=int, default=0, metavar="REPS",
+                    help="also time REPS plain batches of 8 views at 64x36 per window, a host clock around the calls")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -165,6 +169,31 @@ def main():
         doc["blend"]["f_over_c"] = round(doc["blend"]["arms"]["f"]["median_ms"] / doc["blend"]["arms"]["c"]["median_ms"], 4)
         doc["blend"]["fastest_of_b_f_c"] = fastest(doc["blend"]["arms"], "bfc")
         doc["blend"]["b_over_c"] = round(doc["blend"]["arms"]["b"]["median_ms"] / doc["blend"]["arms"]["c"]["median_ms"], 4)
+    if args.small_batches:                                # what a CALL costs the host: plain batches too small to keep the device busy
+        reps, k, bw, bh = args.small_batches, 8, 64, 36
+        plain = gpu.Renderer(0)
+        plain.set_view_batches(True)
+        plain.prepare(sc)
+        cams = [sc.frame_camera(bw, bh, c) for c in S.orbit_cameras(sc, k)]      # made before the windows, like the programs
+        small = torch.zeros((k, bh, bw), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        queued, synced = [], []
+        for i in range(args.windows + 1):                 # (the first window warms up)
+            plain.sync()
+            t0 = time.perf_counter()
+            for _ in range(reps):                         # no synchronise in here: the clock is around the calls
+                plain.render_views_into(small.data_ptr(), cams, bw, bh, MAX_STEPS)
+            t1 = time.perf_counter()
+            plain.sync()
+            t2 = time.perf_counter()
+            if i:
+                queued.append((t1 - t0) * 1e6 / reps)
+                synced.append((t2 - t0) * 1e6 / reps)
+        spread = lambda us: {"median": round(statistics.median(us), 3), "min": round(min(us), 3), "max": round(max(us), 3)}  # noqa: E731
+        doc["small_batches"] = {"what": "%d x render_views_into of %d views at %dx%d back to back, no synchronise between them" % (reps, k, bw, bh),
+                                "unit": "microseconds per call", "kernel": plain.view_samples_kernel_name(1, -1), "windows": args.windows,
+                                "host_clock_around_the_calls": spread(queued), "and_the_synchronise_behind_them": spread(synced)}
+        plain.close()
     doc["kernel_keys"] = {"interpreter_context": interp.kernel_key(), "fast_interpreter_context": fast.kernel_key(),
                           "structure_context": struct.kernel_key()}
     doc["fast_interpreter_proofs"] = dict(zip(("sqrt_kind", "proven_blend_factors", "proven_without_fixup"), fast.interp_fast_paths()))
