@@ -773,7 +773,8 @@ int  lol_gpu_shade_queries(const lol_gpu* ctx);
  * render_interp_scene_batch / render_interp_scene_batch_lin render on each record's own lists — same bits either way
  * (lol_gpu_scene_views_kernel_name, lol_gpu_scene_views_state: lol_gpu_diag.h).  Opt-in, and not the default for a reason: on the one scene
  * measured (scene4) the interpreter with the upload's proven fast paths was the faster of the two (README.md quotes the numbers).
- * Out of scope: supersampled and adaptive forms, ray and shading queries over per-record scenes, row partitions, lol_gpu_multi_*
+ * Out of scope: an adaptive form (of the supersampled and adaptive forms that batches of views have, the supersampled one is
+ * lol_gpu_render_scene_views_samples below), ray and shading queries over per-record scenes, row partitions, lol_gpu_multi_*
  * forms, host surfaces and the renderer.h protocol; and the structure module is not kept across uploads of the same structure
  * (each upload loads it anew, from the cache).
  */
@@ -782,6 +783,52 @@ int  lol_gpu_render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, cons
                                 const lol_gpu_debug* dbg, void* stream);
 int  lol_gpu_set_scene_views(lol_gpu* ctx, int enable);   /* before lol_gpu_upload_program */
 int  lol_gpu_scene_views(const lol_gpu* ctx);
+
+/*
+ * Supersampled scene views: lol_gpu_render_scene_views with `samples` x `samples` = s x s samples per pixel, s in {1, 2, 4} — an
+ * antialiased animation in one launch, a motion-blurred object whose stationary edges are smooth as well.
+ * Record r = v * K + k is one camera and one scene, as in lol_gpu_render_scene_views; K = cams_per_view in {1, 2, 4, 8, 16}.
+ * Pixel (x, y) of view v:
+ *  1. for each k, m_k is the linear mean of lol_gpu_set_samples' steps 1 - 2 taken on record r's OWN scene under cams[r]: the s^2
+ *     samples are pixels (s x + i, s y + j) of the reference's s w x s h frame of scenes[r], as clamped linear colours, in the order
+ *     j s + i, summed as the balanced binary32 tree, and the sum multiplied by 1 / s^2;
+ *  2. m_0 ... m_{K-1} are summed as the tree of lol_gpu_render_views_blend, and the sum is multiplied by 1 / K;
+ *  3. gamma and the context's pixel format follow, as for one sample.
+ * The rounding order is that of lol_gpu_render_views_blend_samples: two trees, one after the other, not one tree over K s^2 leaves.
+ * Three identities: s = 1 IS lol_gpu_render_scene_views — the call forwards to it, so K = 1 keeps all diagnostics.  With K = 1 and
+ * s > 1 view v IS the frame that a context with lol_gpu_set_samples(s) renders under cams[v] after
+ * lol_gpu_upload_program(&scenes[v]), bit for bit.  And when every record carries the uploaded scene the call IS
+ * lol_gpu_render_views_blend_samples.
+ * What carries over unchanged from lol_gpu_render_scene_views: everything an upload or a frame decides is decided per record, on the
+ * host, from that record's own scene and camera — the three exact skips, which of the interpreter's lists runs, the primary march's
+ * first step, what an insane camera switches off.  The first step is sdf(cam.origin) and so the same for every sample of a record.
+ * No proof runs on the device.  The context's scene, kernels, lol_gpu_kernel_key, tile-order state, sample settings
+ * (lol_gpu_set_samples and lol_gpu_set_adaptive_samples are not read: the samples are this argument) and the other rings are neither
+ * read nor changed.
+ * Resources: with K = 1 one copy of the records and one launch over the sample grids of all records.  With K > 1 the same launch
+ * writes one LinearColour per PIXEL and record into the blend's scratch ring — 16 * n_views * K * w * h bytes, the ring of 4 sets
+ * that lol_gpu_render_views_blend uses, a pixel's samples being reduced in registers — and the resolve pass follows.  The records go
+ * through scene views' ring of 8 sets.  No new ring and no new scratch layout.
+ * Diagnostics: lol_gpu_debug.rgb is the mean after gamma, dense [v][y][x]; hit_dist, hit_id and steps are refused with
+ * LOL_GPU_ERR_UNSUPPORTED whenever s > 1 or K > 1.
+ * Refused, with nothing launched and nothing written, and the context stays usable: s outside {1, 2, 4} — LOL_GPU_ERR_ARG, checked
+ * first; then everything lol_gpu_render_scene_views refuses, in its order; a sample count this build's wave patch cannot take —
+ * LOL_GPU_ERR_UNSUPPORTED (as lol_gpu_set_samples); a sample grid of more than 65535 tiles along an axis, or more than 2^32 - 1
+ * lanes over all n_views * K sample grids — LOL_GPU_ERR_ARG.
+ * Which kernel: after lol_gpu_set_scene_view_samples(ctx, 1) BEFORE lol_gpu_upload_program the STRUCTURE MODULE is made with two more
+ * kernels, lol_render_param_batch_aa and lol_render_param_batch_aa_lin.  The setter brings lol_gpu_set_scene_views with it; it makes
+ * another source of that module, hence another code object and cache entry, and without it the structure module is byte for byte
+ * what it is without this call's existence.  Without the setter, until the module is loaded, or if it failed, the interpreter's
+ * render_interp_scene_batch_aa / render_interp_scene_batch_aa_lin render on each record's own lists — same bits either way
+ * (lol_gpu_scene_view_samples_kernel_name: lol_gpu_diag.h).
+ * Out of scope: an adaptive form, ray and shading queries over per-record scenes, row partitions, lol_gpu_multi_* forms,
+ * host surfaces and the renderer.h protocol.
+ */
+int  lol_gpu_render_scene_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views,
+                                        int cams_per_view, int w, int h, int max_steps, int samples, void* dst, size_t pitch_bytes,
+                                        size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream);
+int  lol_gpu_set_scene_view_samples(lol_gpu* ctx, int enable);   /* before lol_gpu_upload_program */
+int  lol_gpu_scene_view_samples(const lol_gpu* ctx);
 
 #ifdef __cplusplus
 }

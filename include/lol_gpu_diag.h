@@ -136,6 +136,13 @@ int         lol_gpu_interp_fast_paths(const lol_gpu* ctx, int* sqrt_kind, unsign
 /* No device needed: the structure module of `prog` — `<out_base>.hip` (source that depends on the program's structure alone: two
  * programs of one structure give the same bytes) and `<out_base>.co`. */
 int         lol_gpu_compile_offline_scene_views(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap);
+/* The kernel the NEXT lol_gpu_render_scene_views_samples(..., cams_per_view, ..., samples, ...) launches (of a blend: its first pass):
+ * "lol_render_param_batch_aa" / "lol_render_param_batch_aa_lin" (a structure module made after lol_gpu_set_scene_view_samples) or
+ * "render_interp_scene_batch_aa" / "render_interp_scene_batch_aa_lin"; lol_gpu_scene_views_kernel_name's for samples <= 1. */
+const char* lol_gpu_scene_view_samples_kernel_name(const lol_gpu* ctx, int cams_per_view, int samples);
+/* No device needed: the structure module of `prog` as lol_gpu_set_scene_view_samples asks for it, with all four kernels —
+ * `<out_base>.hip` (it depends on the structure alone, and differs from lol_gpu_compile_offline_scene_views') and `<out_base>.co`. */
+int         lol_gpu_compile_offline_scene_view_samples(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap);
 /* The kernel the NEXT lol_gpu_render_views_samples(..., samples, contrast, ...) of this context launches, decided by the test the
  * launch itself makes: "lol_render_spec_batch_aa" / "render_interp_batch_aa" for contrast = -1, the refine pass's
  * "lol_render_spec_batch_aa_list" / "render_interp_batch_aa_list" for an adaptive batch, lol_gpu_render_views' for samples = 1.

@@ -1,7 +1,7 @@
 """python -m loltracer_amd scene.lol [-o frame.ppm] [--size WxH] [--max-steps N] [--device D] [--frames N] [--samples N]
                           [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]] [--orbit-shutter K]]
                           [--lens R (--focus D | --focus-at X,Y) --lens-samples K] [--pick X,Y] [--panorama WxH -o FILE.ppm]
-                          [--tween B.lol --frames N [--tween-shutter K] -o DIR]
+                          [--tween B.lol --frames N [--tween-samples S] [--tween-shutter K] -o DIR]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
@@ -18,7 +18,9 @@ writes the equirectangular image of everything round the camera's position: the 
 query (Renderer.shade_rays_into) — rays of the host's own making, the reference's colours.  A.lol --tween B.lol --frames N renders
 the N frames of an animation from scene A to scene B (same structure, other numbers: scene.tween) in ONE launch, every frame under a
 scene of its own (Renderer.render_scene_views_into), and writes DIR/frame_0000.ppm ...; with --tween-shutter K each frame is the mean
-in linear light of K scenes spread over its exposure (scene.shutter_times): objects that move are blurred.  The camera is A's.
+in linear light of K scenes spread over its exposure (scene.shutter_times): objects that move are blurred; with --tween-samples S
+every one of those scenes is supersampled S x S (the samples= of that call; --samples stays refused beside --tween: it is the frame
+setting of a context, which that call does not read).  The camera is A's.
 There is no CPU rendering path."""
 from __future__ import annotations
 
@@ -97,16 +99,17 @@ def tween_frames(sc, args, w, h) -> int:
         dev = r.malloc(frames.nbytes)
         try:
             t0 = time.perf_counter()
-            r.render_scene_views_into(dev, [sc.camera] * len(scenes), scenes, w, h, k, args.max_steps)
+            r.render_scene_views_into(dev, [sc.camera] * len(scenes), scenes, w, h, k, args.max_steps, samples=args.tween_samples)
             r.sync()
             dt = (time.perf_counter() - t0) * 1e3
             r.memcpy_d2h(frames.ctypes.data, dev, frames.nbytes)
-            name = r.scene_views_kernel_name(k)
+            name = r.scene_view_samples_kernel_name(k, args.tween_samples)
         finally:
             r.free(dev)
     finally:
         r.close()
-    print(f"{n} frames of {w}x{h} over {k} scene(s) each: {dt:.3f}ms  {n * w * h / dt / 1e3:.1f} Mpixels/s  [{name}]")
+    ss = args.tween_samples
+    print(f"{n} frames of {w}x{h} over {k} scene(s) each{f', {ss}x{ss} samples per pixel' if ss > 1 else ''}: {dt:.3f}ms  {n * w * h / dt / 1e3:.1f} Mpixels/s  [{name}]")
     os.makedirs(args.out, exist_ok=True)
     for f in range(n):
         write_ppm(os.path.join(args.out, f"frame_{f:04d}.ppm"), frames[f])
@@ -239,6 +242,8 @@ def main(argv=None) -> int:
                     help="with --frames N and -o DIR: N frames from this scene to B.lol (same structure) in one launch")
     ap.add_argument("--tween-shutter", type=int, default=1, choices=(1, 2, 4, 8, 16), metavar="K",
                     help="with --tween: every frame is the mean of K scenes of its own exposure (motion blur of moving objects)")
+    ap.add_argument("--tween-samples", type=int, default=1, choices=(1, 2, 4), metavar="S",
+                    help="with --tween: S x S samples per pixel under every scene of every frame")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     for name, text in (("--pick", args.pick), ("--focus-at", args.focus_at)):
@@ -256,8 +261,8 @@ def main(argv=None) -> int:
     if not sc.validate_materials():
         print("scene_validate_materials failed", file=sys.stderr)
         return 1
-    if args.tween_shutter != 1 and not args.tween:
-        print("--tween-shutter goes with --tween B.lol", file=sys.stderr)
+    if (args.tween_shutter != 1 or args.tween_samples != 1) and not args.tween:
+        print("--tween-shutter and --tween-samples go with --tween B.lol", file=sys.stderr)
         return 1
     if args.tween:
         if (args.panorama or args.orbit or args.lens or args.pick or args.samples != 1 or args.adaptive != -1 or not args.out

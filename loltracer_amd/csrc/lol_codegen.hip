@@ -1149,9 +1149,10 @@ bool has_return_clobbering_branch(const void* data, size_t n_bytes) {
 bool has_return_clobbering_branch(const std::vector<char>& code) { return has_return_clobbering_branch(code.data(), code.size()); }
 
 /* `src` → code object.  out_of_line: the source holds an out-of-line SDF function (what the refusal after dropped options is about).
- * structure: the source is a structure module's (generate_structure_source), which is handed lol_kernel_scenes.h as well — a scene
- * module is handed exactly the headers it always was, so what the compiler makes of it does not change. */
-static bool compile_source(const std::string& src, bool out_of_line, bool structure, const std::string& arch, std::vector<char>& code,
+ * structure: the source is a structure module's (generate_structure_source), which is handed lol_kernel_scenes.h as well (1), and
+ * with the supersampled kernels lol_kernel_scenes_aa.h too (2) — a scene module, and a structure module without them, is handed
+ * exactly the headers it always was, so what the compiler makes of it and where the disk cache keeps it do not change. */
+static bool compile_source(const std::string& src, bool out_of_line, int structure, const std::string& arch, std::vector<char>& code,
                            std::string& log) {
 	int rtc_major = 0, rtc_minor = 0;
 	(void)hiprtcVersion(&rtc_major, &rtc_minor);
@@ -1217,12 +1218,14 @@ static bool compile_source(const std::string& src, bool out_of_line, bool struct
 	                                         "lol_kernel_blend.h", "lol_kernel_blend_aa.h", "lol_kernel_rays.h", "lol_kernel_shade.h" };
 	constexpr int n_hdr = 8;                            /* every module is handed all of them: what it does not #include is never parsed */
 	static const std::string all_headers = [] { std::string t; for (const char* h : hdr_src) { t += '|'; t += h; } return t; }();
-	const char* use_src[n_hdr + 1];
-	const char* use_name[n_hdr + 1];
+	const char* use_src[n_hdr + 2];
+	const char* use_name[n_hdr + 2];
 	for (int i = 0; i < n_hdr; i++) { use_src[i] = hdr_src[i]; use_name[i] = hdr_name[i]; }
 	use_src[n_hdr] = LOL_KERNEL_SCENES_H_TEXT; use_name[n_hdr] = "lol_kernel_scenes.h";
-	const int n_use = structure ? n_hdr + 1 : n_hdr;
-	const std::string disk_key = key + all_headers + (structure ? std::string("|") + LOL_KERNEL_SCENES_H_TEXT : std::string());
+	use_src[n_hdr + 1] = LOL_KERNEL_SCENES_AA_H_TEXT; use_name[n_hdr + 1] = "lol_kernel_scenes_aa.h";
+	const int n_use = n_hdr + structure;
+	const std::string disk_key = key + all_headers + (structure ? std::string("|") + LOL_KERNEL_SCENES_H_TEXT : std::string()) +
+	                             (structure > 1 ? std::string("|") + LOL_KERNEL_SCENES_AA_H_TEXT : std::string());
 	if (disk_cache_load(disk_key, code)) {
 		std::lock_guard<std::mutex> lock(g_cache_mutex);
 		g_code_cache[key] = code;
@@ -1303,16 +1306,19 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 	if (src_out) *src_out = src;
 	if (const char* dump = tuning_env("LOL_GPU_DUMP_SPEC_SOURCE"))       /* debugging aid: the source as really generated on this device */
 		if (FILE* f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
-	return compile_source(src, spec_out_of_line(P, form), false, arch, code, log);
+	return compile_source(src, spec_out_of_line(P, form), 0, arch, code, log);
 }
 
 /* The structure module (lol_kernel_scenes.h; lol_gpu_render_scene_views): the scene's SDF emitted ONCE — no fast form, no culling plan,
  * inlined, objects in file order —, every number a read K[7 i + j] through a member pointer in the constant address space, so the numbers
  * arrive by scalar loads and feed the VALU as SGPR operands while the SDF stays straight-line code.  Nothing of the text depends on a
  * number of `P`: all scenes of one structure share the source, the code object and its place in the disk cache.  Two kernels:
- * lol_render_param_batch (counts steps: it serves a batch with or without lol_gpu_debug::steps) and lol_render_param_batch_lin. */
-std::string generate_structure_source(const lol_program& P) {
-	std::string s = "#include \"lol_kernel_scenes.h\"\nnamespace lol {\n";
+ * lol_render_param_batch (counts steps: it serves a batch with or without lol_gpu_debug::steps) and lol_render_param_batch_lin.
+ * `samples` (lol_gpu_set_scene_view_samples): two more, lol_render_param_batch_aa and lol_render_param_batch_aa_lin — the same body
+ * with sample_launch applied to the record's launch and the supersampled batches' stores (lol_kernel_scenes_aa.h), the same
+ * ParamSdf, register budget and LDS.  Without it the text is what it was before those existed, byte for byte. */
+std::string generate_structure_source(const lol_program& P, bool samples) {
+	std::string s = samples ? "#include \"lol_kernel_scenes_aa.h\"\nnamespace lol {\n" : "#include \"lol_kernel_scenes.h\"\nnamespace lol {\n";
 	const std::vector<RootBound> roots = analyse_roots(P);
 	const CullPlan plan = plan_culling(roots, false);        /* file order, no test */
 	const int waves_lo = P.n_ops <= 32 ? 8 : P.n_ops <= 96 ? 6 : 4, waves_hi = 8;      /* (generate_source: the register budget) */
@@ -1331,13 +1337,25 @@ std::string generate_structure_source(const lol_program& P) {
 	const std::string tail = "(const lol::Launch L, const lol::SceneTail B) {\n\textern __shared__ lol::u32 lds[];\n\tlol_param_body<";
 	s += head + "lol_render_param_batch" + tail + "false>(L, B, lds);\n}\n";
 	s += head + "lol_render_param_batch_lin" + tail + "true>(L, B, lds);\n}\n";
+	if (!samples) return s;
+	/* (every lane reaches the store: the butterfly of sample_mean needs the whole wave) */
+	s += "template <bool LIN> __device__ __forceinline__ void lol_param_body_aa(const lol::Launch& L, const lol::SceneTail& B, lol::u32* lds) {\n";
+	s += "\tconst lol::Launch R = lol::scene_launch(L, B);\n";
+	if (!tables_global) s += "\tlol::stage_common(R, lds);\n\t__syncthreads();\n";
+	s += "\tconst lol::Launch S = lol::sample_launch(R);\n";
+	s += "\tlol::ParamSdf sdf;\n\tsdf.K = lol::scene_numbers(B);\n";
+	s += "\tconst lol::Pixel P = lol::shade_pixel<lol::ParamSdf, " + tg + ", false>(S, sdf, lds);\n";
+	s += "\tif constexpr (LIN) lol::store_linear_view_aa(L, P.rgb);\n\telse lol::store_pixel_view_aa(L, lol::batch_tail(B), P.rgb);\n}\n";
+	const std::string tail_aa = "(const lol::Launch L, const lol::SceneTail B) {\n\textern __shared__ lol::u32 lds[];\n\tlol_param_body_aa<";
+	s += head + "lol_render_param_batch_aa" + tail_aa + "false>(L, B, lds);\n}\n";
+	s += head + "lol_render_param_batch_aa_lin" + tail_aa + "true>(L, B, lds);\n}\n";
 	return s;
 }
 
-bool compile_structure(const lol_program& P, const std::string& arch, std::vector<char>& code, std::string& log, std::string* src_out) {
-	const std::string src = generate_structure_source(P);
+bool compile_structure(const lol_program& P, const std::string& arch, std::vector<char>& code, std::string& log, std::string* src_out, bool samples) {
+	const std::string src = generate_structure_source(P, samples);
 	if (src_out) *src_out = src;
-	return compile_source(src, false, true, arch, code, log);
+	return compile_source(src, false, samples ? 2 : 1, arch, code, log);
 }
 
 #pragma GCC visibility pop
@@ -1422,8 +1440,9 @@ int lol_gpu_compile_offline_module(const lol_program* prog, const char* arch, co
 	return ok ? LOL_GPU_OK : LOL_GPU_ERR_UNSUPPORTED;
 }
 
-/* ... and the structure module of `prog` (lol_gpu_set_scene_views): `<out_base>.hip` and `<out_base>.co`; lol_gpu_diag.h */
-int lol_gpu_compile_offline_scene_views(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap) {
+/* ... and the structure module of `prog` (lol_gpu_set_scene_views; `samples`: lol_gpu_set_scene_view_samples): `<out_base>.hip` and
+ * `<out_base>.co`; lol_gpu_diag.h */
+static int compile_offline_structure(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap, bool samples) {
 	if (!prog || !arch || prog->n_ops > LOL_MAX_OPS || (prog->n_ops && !prog->ops)) return LOL_GPU_ERR_ARG;
 	std::vector<char> code;
 	std::string lg, src;
@@ -1431,7 +1450,7 @@ int lol_gpu_compile_offline_scene_views(const lol_program* prog, const char* arc
 	{
 		BigStackThread th;
 		auto work = [&]() {
-			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_structure(*prog, arch, code, lg, &src); }
+			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_structure(*prog, arch, code, lg, &src, samples); }
 			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
 		};
 		bool started = false;
@@ -1445,6 +1464,12 @@ int lol_gpu_compile_offline_scene_views(const lol_program* prog, const char* arc
 		if (ok) if (FILE* f = fopen((base + ".co").c_str(), "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
 	}
 	return ok ? LOL_GPU_OK : LOL_GPU_ERR_UNSUPPORTED;
+}
+int lol_gpu_compile_offline_scene_views(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap) {
+	return compile_offline_structure(prog, arch, out_base, log, logcap, false);
+}
+int lol_gpu_compile_offline_scene_view_samples(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap) {
+	return compile_offline_structure(prog, arch, out_base, log, logcap, true);
 }
 
 /* The entry points from before that one, each the module of a mask (lol_gpu_diag.h).  Their `others` is a mask in an order of its

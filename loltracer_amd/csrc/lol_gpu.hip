@@ -1961,25 +1961,36 @@ static bool same_structure(const lol_program& A, const lol_program& B) {
 	return true;
 }
 
-/* the address of the interpreter's scene-view kernel for one stack class, sqrt kind and table placement */
+/* the address of the interpreter's scene-view kernel for one stack class, sqrt kind and table placement; `aa`: the supersampled ones
+ * (lol_kernel_scenes_aa.h) */
 template <int SSIZE, int KIND, bool TABLES_GLOBAL>
-static const void* scene_interp_kernel(bool lin) {
+static const void* scene_interp_kernel(bool lin, bool aa) {
+	if (aa) return lin ? reinterpret_cast<const void*>(&lol::render_interp_scene_batch_aa_lin<SSIZE, KIND, TABLES_GLOBAL>)
+	                   : reinterpret_cast<const void*>(&lol::render_interp_scene_batch_aa<SSIZE, KIND, TABLES_GLOBAL>);
 	return lin ? reinterpret_cast<const void*>(&lol::render_interp_scene_batch_lin<SSIZE, KIND, TABLES_GLOBAL>)
 	           : reinterpret_cast<const void*>(&lol::render_interp_scene_batch<SSIZE, KIND, TABLES_GLOBAL>);
 }
 
+/* the structure module's kernel for a call, or nullptr: the interpreter renders it.  A module made without
+ * lol_gpu_set_scene_view_samples has no supersampled kernels: those calls then go to the interpreter's. */
+static hipFunction_t structure_kernel(const lol_gpu* ctx, bool lin, bool aa) {
+	const StructureKernel& k = ctx->tiers.structure;
+	if (!k) return nullptr;
+	return aa ? (lin ? k.aa_lin : k.batch_aa) : (lin ? k.lin : k.batch);
+}
+
 /* ONE launch over the records: the structure module's kernel where it is loaded, else the interpreter's instantiation for the
- * program's rung (the structure's: every record has it).  `args`: (L, B) for both. */
-static hipError_t launch_scene_views(const lol_gpu* ctx, bool lin, void** args, dim3 grid, hipStream_t s) {
+ * program's rung (the structure's: every record has it).  `args`: (L, B) for all four of either form. */
+static hipError_t launch_scene_views(const lol_gpu* ctx, bool lin, bool aa, void** args, dim3 grid, hipStream_t s) {
 	const lol_program& P = ctx->h_prog;
 	const unsigned lds = lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u;
-	const StructureKernel& k = ctx->tiers.structure;
-	if (k) return hipModuleLaunchKernel(lin ? k.lin : k.batch, grid.x, grid.y, grid.z, lol::BLOCK, 1, 1, lds, s, args, nullptr);
+	if (const hipFunction_t f = structure_kernel(ctx, lin, aa))
+		return hipModuleLaunchKernel(f, grid.x, grid.y, grid.z, lol::BLOCK, 1, 1, lds, s, args, nullptr);
 	const int kind = ctx->interp_sqrt_kind;
 	return interp_dispatch(ctx, [&](auto v) {
 		constexpr int ssize = decltype(v)::ssize;
 		constexpr bool tables_global = decltype(v)::tables_global;
-		const void* fn = kind == 3 ? scene_interp_kernel<ssize, 3, tables_global>(lin) : scene_interp_kernel<ssize, 0, tables_global>(lin);
+		const void* fn = kind == 3 ? scene_interp_kernel<ssize, 3, tables_global>(lin, aa) : scene_interp_kernel<ssize, 0, tables_global>(lin, aa);
 		return hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
 	});
 }
@@ -2049,9 +2060,15 @@ static int queue_scene_records(lol_gpu* ctx, const std::vector<lol::SceneView>& 
 	return e == hipSuccess ? LOL_GPU_OK : ring_done(ctx, S, s, e, "copy of the records of a batch of scene views");
 }
 
+/* `samples` x `samples` samples per pixel (lol_gpu_render_scene_views_samples; 1: lol_gpu_render_scene_views).  Nothing in the records
+ * depends on it: with samples > 1 the launch is the one of lol_gpu_render_views_samples — counted in samples, the sample grid's size
+ * in fw / fh, the sample bits in the flags — and the kernels are the supersampled ones, which reduce a pixel's samples in registers:
+ * the destination, the scratch (one LinearColour per PIXEL and record) and the resolve pass are those of one sample. */
 static int render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views, int K, int w, int h,
-                              int max_steps, void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream) {
+                              int max_steps, int samples, void* dst, size_t pitch_bytes, size_t view_stride_bytes, const lol_gpu_debug* dbg,
+                              void* stream) {
 	if (!ctx || !cams || !scenes || !dst) return LOL_GPU_ERR_ARG;
+	if (samples != 1 && samples != 2 && samples != 4) return fail(ctx, LOL_GPU_ERR_ARG, "samples per axis must be 1, 2 or 4");
 	LOL_TRY(blend_refused(ctx, cams, n_views, K, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
 	const int n = n_views * K;
 	const lol_program& U = ctx->h_prog;
@@ -2064,16 +2081,21 @@ static int render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const 
 		for (uint32_t i = 0; i < P.n_roots; i++)
 			if (P.root_material[i] >= P.n_materials) return fail(ctx, LOL_GPU_ERR_ARG, "material index out of range in a view's scene");
 	}
-	if (K > 1 && dbg && (dbg->hit_dist || dbg->hit_id || dbg->steps))
-		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "hit_dist, hit_id and steps have no single value for a pixel averaged over scenes");
+	const bool aa = samples > 1;
+	if (aa && !lol::samples_fit_wave(samples))
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "this build's wave patch (LOL_WAVE_W x LOL_WAVE_H) does not divide into that many samples per axis");
+	if ((K > 1 || aa) && dbg && (dbg->hit_dist || dbg->hit_id || dbg->steps))
+		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, aa ? "hit_dist, hit_id and steps have no single value for a supersampled pixel"
+		                                             : "hit_dist, hit_id and steps have no single value for a pixel averaged over scenes");
 	dim3 grid;
-	if (!batch_grid(ctx, w, h, n, &grid))
-		return fail(ctx, LOL_GPU_ERR_ARG, "batch too large for one launch over all its records: fewer views per call");
+	if (!batch_grid(ctx, (long long)samples * w, (long long)samples * h, n, &grid))
+		return fail(ctx, LOL_GPU_ERR_ARG, aa ? "batch too large for one launch in samples over all its records: fewer views per call"
+		                                     : "batch too large for one launch over all its records: fewer views per call");
 	hipStream_t s;
 	LOL_TRY(batch_stream(ctx, stream, &s));              /* (the frame boundary: a structure module that has finished is loaded here) */
 	std::vector<lol::SceneView> views;
 	std::vector<uint32_t> data;
-	LOL_TRY(build_scene_records(ctx, cams, scenes, n, max_steps, !ctx->tiers.structure, views, data));
+	LOL_TRY(build_scene_records(ctx, cams, scenes, n, max_steps, !structure_kernel(ctx, K > 1, aa), views, data));
 	RingSet* scratch = nullptr;
 	if (K > 1) {
 		scratch = &ctx->blends.next();
@@ -2082,17 +2104,21 @@ static int render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const 
 	}
 	RingSet* S = nullptr;
 	LOL_TRY(queue_scene_records(ctx, views, data, s, &S));
-	batch_range(K > 1 ? "blend of scene views" : "scene views", n, w, h);
+	batch_range(aa ? (K > 1 ? "supersampled blend of scene views" : "supersampled scene views") : K > 1 ? "blend of scene views" : "scene views", n, w, h);
 	lol::Launch L;
 	if (K > 1) batch_launch(ctx, w, h, max_steps, scratch->d_buf, (size_t)w * 4, nullptr, L);
 	else       batch_launch(ctx, w, h, max_steps, dst, pitch_bytes, dbg, L);
+	if (aa) {
+		L.fw = (float)(samples * w); L.fh = (float)(samples * h);      /* the size of the sample grid */
+		L.flags |= samples == 4 ? lol::FLAG_SAMPLES_4 : lol::FLAG_SAMPLES_2;
+	}
 	lol::SceneTail B = { reinterpret_cast<const lol::SceneView*>(S->d_buf), K > 1 ? 0ull : (unsigned long long)(view_stride_bytes / 4),
 	                     S->d_buf + views.size() * lol::SCENE_VIEW_DWORDS };
 	void* args[] = { &L, &B };
-	const char* what = "kernel launch (scene views)";
-	hipError_t e = launch_scene_views(ctx, K > 1, args, grid, s);
+	const char* what = aa ? "kernel launch (supersampled scene views)" : "kernel launch (scene views)";
+	hipError_t e = launch_scene_views(ctx, K > 1, aa, args, grid, s);
 	if (e == hipSuccess && K > 1) {
-		what = "kernel launch (blend of scene views, resolve pass)";
+		what = aa ? "kernel launch (supersampled blend of scene views, resolve pass)" : "kernel launch (blend of scene views, resolve pass)";
 		e = launch_blend_resolve(ctx, L, scratch->d_buf, n_views, K, w, h, dst, pitch_bytes, view_stride_bytes, dbg, s);
 	}
 	if (g_roctx.pop) g_roctx.pop();
@@ -2104,9 +2130,37 @@ extern "C" {
 int lol_gpu_render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views, int cams_per_view,
                                int w, int h, int max_steps, void* dst, size_t pitch_bytes, size_t view_stride_bytes,
                                const lol_gpu_debug* dbg, void* stream) {
-	try { return render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream); }
+	try { return render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, 1, dst, pitch_bytes, view_stride_bytes, dbg, stream); }
 	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a batch"); }
 	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a batch"); }
+}
+
+/* s = 1 IS lol_gpu_render_scene_views: the call forwards to it behind the one refusal that comes first */
+int lol_gpu_render_scene_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views, int cams_per_view,
+                                       int w, int h, int max_steps, int samples, void* dst, size_t pitch_bytes, size_t view_stride_bytes,
+                                       const lol_gpu_debug* dbg, void* stream) {
+	if (!ctx || !cams || !scenes || !dst) return LOL_GPU_ERR_ARG;
+	if (samples != 1 && samples != 2 && samples != 4) return fail(ctx, LOL_GPU_ERR_ARG, "samples per axis must be 1, 2 or 4");
+	if (samples == 1)
+		return lol_gpu_render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+	try { return render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, samples, dst, pitch_bytes, view_stride_bytes, dbg, stream); }
+	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a batch"); }
+	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a batch"); }
+}
+
+int lol_gpu_set_scene_view_samples(lol_gpu* ctx, int enable) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	ctx->want_scene_view_samples = enable ? 1 : 0;      /* takes effect at the next lol_gpu_upload_program; brings lol_gpu_set_scene_views */
+	return LOL_GPU_OK;
+}
+int lol_gpu_scene_view_samples(const lol_gpu* ctx) { return ctx ? ctx->want_scene_view_samples : LOL_GPU_ERR_ARG; }
+
+const char* lol_gpu_scene_view_samples_kernel_name(const lol_gpu* ctx, int cams_per_view, int samples) {
+	if (!ctx) return "";
+	if (samples <= 1) return lol_gpu_scene_views_kernel_name(ctx, cams_per_view);
+	const bool lin = cams_per_view > 1;
+	if (structure_kernel(ctx, lin, true)) return lin ? "lol_render_param_batch_aa_lin" : "lol_render_param_batch_aa";
+	return lin ? "render_interp_scene_batch_aa_lin" : "render_interp_scene_batch_aa";
 }
 
 int lol_gpu_set_scene_views(lol_gpu* ctx, int enable) {

@@ -27,6 +27,7 @@
 #include "lol_kernel_rays.h"
 #include "lol_kernel_shade.h"
 #include "lol_kernel_scenes.h"
+#include "lol_kernel_scenes_aa.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -221,11 +222,17 @@ struct SceneKernel {
 };
 
 /* The structure module (lol_codegen.hip, generate_structure_source): a code object of its own beside the scene's, with its own load,
- * unload and key — no row of MODULE_SWITCHES.  Both kernels or none. */
+ * unload and key — no row of MODULE_SWITCHES.  Both kernels or none.
+ * lol_gpu_set_scene_view_samples is no row of MODULE_SWITCHES either, and for the same reason: those rows say what the SCENE's module
+ * carries, and the two supersampled kernels belong to this code object — another source of it (generate_structure_source with
+ * `samples`), hence another code object and cache entry.  All four kernels or none then; without that switch the last two stay null
+ * and the interpreter's render_interp_scene_batch_aa / _aa_lin render the supersampled calls. */
 struct StructureKernel {
 	hipModule_t   module = nullptr;
 	hipFunction_t batch = nullptr;             /* lol_render_param_batch (counts steps) */
 	hipFunction_t lin = nullptr;               /* lol_render_param_batch_lin */
+	hipFunction_t batch_aa = nullptr;          /* lol_render_param_batch_aa     (only in a module made with `samples`) */
+	hipFunction_t aa_lin = nullptr;            /* lol_render_param_batch_aa_lin (... both or neither) */
 	std::string   key;                         /* code_key_hex of the code object */
 	explicit operator bool() const { return module != nullptr; }
 	void unload() { if (module) (void)hipModuleUnload(module); *this = StructureKernel(); }
@@ -324,6 +331,7 @@ struct lol_gpu {
 	int          samples = 1;            /* lol_gpu_set_samples: samples per pixel along each axis of the frames launched from now on */
 	int          adaptive = -1;          /* lol_gpu_set_adaptive_samples: the contrast T, or -1 (off) */
 	int          want_scene_views = 0;   /* lol_gpu_set_scene_views: the next upload also compiles the structure module */
+	int          want_scene_view_samples = 0;   /* lol_gpu_set_scene_view_samples: ... with its two supersampled kernels (brings want_scene_views) */
 	FastPaths    fast;                   /* what the upload proved on the device: the lists of scene views are built with it */
 	unsigned     module_switches = 0; /* the switch_bit()s set by lol_gpu_set_view_batches ... lol_gpu_set_shade_queries (MODULE_SWITCHES) */
 	void*        d_pick = nullptr;       /* lol_gpu_pick's device memory, from the first pick on: xy [2] | dist | id | steps | normal [3] */
@@ -521,8 +529,10 @@ bool compile_spec(const lol_program& P, const FastPaths* fast, const std::string
 /* the interpreter's two macro-op lists for `P`, one after the other (with / without v_div_fixup in the proven blend factors);
  * false: the two differ in length (cannot happen: same records by construction) */
 /* the structure module of `P`: source that depends on P's structure alone (opcodes, ids, counts), and its code object */
-std::string generate_structure_source(const lol_program& P);
-bool compile_structure(const lol_program& P, const std::string& arch, std::vector<char>& code, std::string& log, std::string* src_out = nullptr);
+/* (`samples`: with lol_render_param_batch_aa and lol_render_param_batch_aa_lin — another source, another code object) */
+std::string generate_structure_source(const lol_program& P, bool samples = false);
+bool compile_structure(const lol_program& P, const std::string& arch, std::vector<char>& code, std::string& log, std::string* src_out = nullptr,
+                       bool samples = false);
 bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, std::vector<uint32_t>& lists, uint32_t& n_mops);
 std::string fnv_hex(const void* data, size_t n);
 std::string code_key_hex(const void* code, size_t n);      /* SceneKernel::key: FNV-1a over what the device loads of a code object (lol_code_key.h) */
@@ -538,8 +548,8 @@ bool finish_specialise(lol_gpu* ctx, bool wait);
 /* the scene kernel frames run, or nullptr: the interpreter */
 inline const SceneKernel* scene_kernel(const lol_gpu* ctx) { return ctx->tiers.kernel ? &ctx->tiers.kernel : nullptr; }
 
-/* all or nothing: both kernels of the structure module, or `why` not */
-bool load_structure_kernel(const std::vector<char>& code, StructureKernel& k, std::string& why);
+/* all or nothing for what the source carries: both kernels of the structure module, with `samples` all four, or `why` not */
+bool load_structure_kernel(const std::vector<char>& code, StructureKernel& k, std::string& why, bool samples = false);
 /* does an upload of `P` on this context compile a structure module? */
 bool structure_module_wanted(const lol_gpu* ctx, const lol_program& P);
 

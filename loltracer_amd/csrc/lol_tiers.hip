@@ -28,6 +28,7 @@ struct SpecJob {
 	/* the structure module (lol_gpu_set_scene_views), compiled by this run's thread AFTER the scene's own module: `done` says the
 	 * scene's kernel is there, `structure_done` that this one is (or was not to be had: structure_ok) */
 	bool want_structure = false, structure_done = false, structure_ok = false;
+	bool structure_samples = false;    /* lol_gpu_set_scene_view_samples: the structure module with its two supersampled kernels */
 	std::vector<char> structure_code;
 	std::string structure_log;
 	bool all_done() const { return done && (!want_structure || structure_done); }      /* (under `mu`) */
@@ -85,7 +86,7 @@ void launch_job(SpecJob* job) {
 		std::string slog;
 		try {
 			std::lock_guard<std::mutex> rtc(g_rtc_mutex);
-			sok = compile_structure(job->prog->p, job->arch, scode, slog);
+			sok = compile_structure(job->prog->p, job->arch, scode, slog, nullptr, job->structure_samples);
 		} catch (...) { sok = false; slog = "the scene compiler ran out of memory"; }
 		std::lock_guard<std::mutex> lock(job->mu);
 		job->structure_code = std::move(scode);
@@ -208,7 +209,7 @@ bool finish_structure(SpecTiers& T, bool wait) {
 		job.cv.wait(lock, [&] { return job.structure_done; });
 	}
 	std::string why = job.structure_log;
-	if (job.structure_ok && load_structure_kernel(job.structure_code, T.structure, why)) {
+	if (job.structure_ok && load_structure_kernel(job.structure_code, T.structure, why, job.structure_samples)) {
 		T.structure_state = 2;
 		T.structure_log = job.structure_log;
 	} else {
@@ -222,12 +223,14 @@ bool finish_structure(SpecTiers& T, bool wait) {
 
 }  // namespace
 
-bool load_structure_kernel(const std::vector<char>& code, StructureKernel& k, std::string& why) {
+bool load_structure_kernel(const std::vector<char>& code, StructureKernel& k, std::string& why, bool samples) {
 	k.key = code_key_hex(code.data(), code.size());
 	bool ok = hipModuleLoadData(&k.module, code.data()) == hipSuccess;
 	if (!ok) why = "hipModuleLoadData failed";
 	if (ok && hipModuleGetFunction(&k.batch, k.module, "lol_render_param_batch") != hipSuccess) { ok = false; why = "lol_render_param_batch not found in the compiled module"; }
 	if (ok && hipModuleGetFunction(&k.lin, k.module, "lol_render_param_batch_lin") != hipSuccess) { ok = false; why = "lol_render_param_batch_lin not found in the compiled module"; }
+	if (ok && samples && hipModuleGetFunction(&k.batch_aa, k.module, "lol_render_param_batch_aa") != hipSuccess) { ok = false; why = "lol_render_param_batch_aa not found in the compiled module"; }
+	if (ok && samples && hipModuleGetFunction(&k.aa_lin, k.module, "lol_render_param_batch_aa_lin") != hipSuccess) { ok = false; why = "lol_render_param_batch_aa_lin not found in the compiled module"; }
 	if (ok) return true;
 	k.unload();
 	(void)hipGetLastError();
@@ -235,7 +238,7 @@ bool load_structure_kernel(const std::vector<char>& code, StructureKernel& k, st
 }
 
 bool structure_module_wanted(const lol_gpu* ctx, const lol_program& P) {
-	return ctx->want_scene_views && P.n_ops <= LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS;
+	return (ctx->want_scene_views || ctx->want_scene_view_samples) && P.n_ops <= LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS;
 }
 
 void start_specialise(lol_gpu* ctx, const FastPaths& fast) {
@@ -288,6 +291,7 @@ void start_specialise(lol_gpu* ctx, const FastPaths& fast) {
 	job->cull = culling_enabled(ctx->want_cull);
 	job->carries = module_kernels_of(ctx);
 	job->want_structure = structure_module_wanted(ctx, ctx->h_prog);
+	job->structure_samples = ctx->want_scene_view_samples != 0;
 	if (job->want_structure) T.structure_state = 1;
 	/* (LOL_GPU_SPEC_INLINE_MAX, a tuning switch, pins ONE form by size) */
 	const bool first_tier = !tuning_env("LOL_GPU_SPEC_INLINE_MAX") && ctx->h_prog.n_ops > LOL_SPEC_FIRST_TIER_INLINE_MAX_OPS &&

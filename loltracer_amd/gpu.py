@@ -295,6 +295,17 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_interp_fast_paths.restype = C.c_int
         lib.lol_gpu_compile_offline_scene_views.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
         lib.lol_gpu_compile_offline_scene_views.restype = C.c_int
+        lib.lol_gpu_render_scene_views_samples.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                           C.c_int, vp, C.c_size_t, C.c_size_t, P(Debug), vp]
+        lib.lol_gpu_render_scene_views_samples.restype = C.c_int
+        lib.lol_gpu_set_scene_view_samples.argtypes = [vp, C.c_int]
+        lib.lol_gpu_set_scene_view_samples.restype = C.c_int
+        lib.lol_gpu_scene_view_samples.argtypes = [vp]
+        lib.lol_gpu_scene_view_samples.restype = C.c_int
+        lib.lol_gpu_scene_view_samples_kernel_name.argtypes = [vp, C.c_int, C.c_int]
+        lib.lol_gpu_scene_view_samples_kernel_name.restype = C.c_char_p
+        lib.lol_gpu_compile_offline_scene_view_samples.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
+        lib.lol_gpu_compile_offline_scene_view_samples.restype = C.c_int
         lib.lol_gpu_views_refined.argtypes = [vp, P(C.c_int64)]
         lib.lol_gpu_views_refined.restype = C.c_int
         lib.lol_gpu_interp_variant.argtypes = [vp, P(C.c_int), P(C.c_int)]
@@ -419,6 +430,7 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_trace_rays", "lol_gpu_trace_pixels", "lol_gpu_pick", "lol_gpu_set_ray_queries", "lol_gpu_ray_queries",
     "lol_gpu_shade_rays", "lol_gpu_shade_pixels", "lol_gpu_set_shade_queries", "lol_gpu_shade_queries", "lol_gpu_memcpy_h2d",
     "lol_gpu_render_scene_views", "lol_gpu_set_scene_views", "lol_gpu_scene_views",
+    "lol_gpu_render_scene_views_samples", "lol_gpu_set_scene_view_samples", "lol_gpu_scene_view_samples",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
@@ -432,6 +444,7 @@ DIAG_SYMBOLS = [                                                        # includ
     "lol_gpu_shade_kernel_name", "lol_gpu_compile_offline_shade", "lol_gpu_compile_offline_module",
     "lol_gpu_scene_views_kernel_name", "lol_gpu_scene_views_state", "lol_gpu_compile_offline_scene_views",
     "lol_gpu_interp_fast_paths",
+    "lol_gpu_scene_view_samples_kernel_name", "lol_gpu_compile_offline_scene_view_samples",
 ]
 
 
@@ -528,6 +541,17 @@ def compile_offline_scene_views(program: S.Program, out_base: str, arch: str = "
     two programs of one structure give the same two files, byte for byte."""
     log = C.create_string_buffer(1 << 16)
     st = gpu_lib().lol_gpu_compile_offline_scene_views(C.byref(program), arch.encode(), os.fsencode(out_base), log, len(log))
+    if st != LOL_GPU_OK:
+        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
+    return log.value.decode(errors="replace")
+
+
+def compile_offline_scene_view_samples(program: S.Program, out_base: str, arch: str = "gfx950") -> str:
+    """compile_offline_scene_views for the structure module that Renderer.set_scene_view_samples asks for: the same SDF and the two
+    kernels of that module, and lol_render_param_batch_aa / lol_render_param_batch_aa_lin behind them.  Another source than
+    compile_offline_scene_views writes, hence another code object; it too depends on the program's structure alone."""
+    log = C.create_string_buffer(1 << 16)
+    st = gpu_lib().lol_gpu_compile_offline_scene_view_samples(C.byref(program), arch.encode(), os.fsencode(out_base), log, len(log))
     if st != LOL_GPU_OK:
         raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
     return log.value.decode(errors="replace")
@@ -762,6 +786,22 @@ class Renderer:
         """the kernel the next render_scene_views_into(..., cameras_per_view=...) launches (of a blend: its first pass)"""
         return self._lib.lol_gpu_scene_views_kernel_name(self._ctx, int(cameras_per_view)).decode()
 
+    def set_scene_view_samples(self, enable: bool):
+        """Before prepare(): set_scene_views, and the structure module is made with two more kernels (lol_render_param_batch_aa,
+        lol_render_param_batch_aa_lin) on which render_scene_views_into(..., samples=2 or 4) runs once the module is loaded.  Without
+        it — and until the module is loaded — the interpreter's render_interp_scene_batch_aa / _aa_lin render those calls.  Same
+        pixels either way.  Another source of the structure module, hence another code object: without this switch that module is
+        byte for byte what set_scene_views alone gives."""
+        self._check(self._lib.lol_gpu_set_scene_view_samples(self._ctx, 1 if enable else 0))
+
+    @property
+    def scene_view_samples(self) -> bool:
+        return bool(self._lib.lol_gpu_scene_view_samples(self._ctx))
+
+    def scene_view_samples_kernel_name(self, cameras_per_view: int = 1, samples: int = 2) -> str:
+        """the kernel the next render_scene_views_into(..., cameras_per_view=..., samples=...) launches (of a blend: its first pass)"""
+        return self._lib.lol_gpu_scene_view_samples_kernel_name(self._ctx, int(cameras_per_view), int(samples)).decode()
+
     def scene_views_state(self) -> int:
         """the structure module of the uploaded program: 0 none, 1 compiling, 2 in use, -1 failed"""
         return int(self._lib.lol_gpu_scene_views_state(self._ctx))
@@ -776,7 +816,7 @@ class Renderer:
 
     def render_scene_views_into(self, dst_ptr: int, cameras, scenes, w: int, h: int, cameras_per_view: int = 1, max_steps: int = 256,
                                 pitch_bytes: int | None = None, view_stride_bytes: int | None = None, debug: Debug | None = None,
-                                stream: int | None = None):
+                                stream: int | None = None, samples: int = 1):
         """Asynchronously render len(scenes) / cameras_per_view views of w x h, every RECORD under a camera and a scene of its own
         (lol_gpu_render_scene_views): record r is the frame this renderer would render under cameras[r] after prepare(scenes[r]).
         With K = cameras_per_view = 1 view v is that frame, with every diagnostic of `debug`; with K in {2, 4, 8, 16} view v is the
@@ -784,7 +824,10 @@ class Renderer:
         scenes: scene.Scene objects (flattened here) or ready scene.Program objects, all of the prepared scene's structure
         (scene.same_structure; scene.tween gives such scenes).  cameras: scene.Camera / scene.FrameCamera objects, one per record,
         or None: every record's own scene's camera.  Both arrays are copied before the call returns.  Addressing as
-        render_views_into."""
+        render_views_into.
+        samples = s in {2, 4} (lol_gpu_render_scene_views_samples): s x s samples per pixel under every record — each record's pixel
+        is the linear mean of its samples as a frame after set_samples(s) takes it, on that record's own scene; then the mean over
+        the K records as before, gamma and packing.  `debug` then takes rgb alone.  samples = 1 is the call without it."""
         items = list(scenes)
         k = int(cameras_per_view)
         if k < 1 or len(items) % k:
@@ -811,8 +854,13 @@ class Renderer:
         pitch = pitch_bytes if pitch_bytes is not None else w * 4
         stride = view_stride_bytes if view_stride_bytes is not None else h * pitch
         dbg = C.byref(debug) if debug is not None else None
-        self._check(self._lib.lol_gpu_render_scene_views(
-            self._ctx, arr, progs, len(items) // k, k, w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride, dbg, _stream_arg(stream)))
+        if int(samples) == 1:
+            self._check(self._lib.lol_gpu_render_scene_views(
+                self._ctx, arr, progs, len(items) // k, k, w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride, dbg, _stream_arg(stream)))
+        else:
+            self._check(self._lib.lol_gpu_render_scene_views_samples(
+                self._ctx, arr, progs, len(items) // k, k, w, h, max_steps, int(samples), C.c_void_p(dst_ptr), pitch, stride, dbg,
+                _stream_arg(stream)))
         del keep
 
     def render_host(self, host_ptr: int, w: int, h: int, max_steps: int = 256, camera: S.Camera | None = None,
