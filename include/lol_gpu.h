@@ -636,8 +636,8 @@ int  lol_gpu_assemble_parts_at(lol_gpu* ctx, const void* parts, const lol_gpu_ro
  * record rings: a frame after a query is the frame it would have been.  lol_gpu_set_miss_skip / lol_gpu_set_exact_skips do not apply
  * (there is no shading); lol_gpu_set_cull applies as it does to frames: same answers either way.
  *
- * Out of scope for these entry points: shading or shadow queries (the colour along arbitrary rays is lol_gpu_shade_rays', below; a
- * shadow factor as an output of its own is not built), lol_gpu_multi_* forms, rays in host memory beyond the one-pixel
+ * Out of scope for these entry points: shading or shadow queries (the colour along arbitrary rays is lol_gpu_shade_rays', below; the
+ * shadow factor of every light is an output of lol_gpu_light_rays, further below), lol_gpu_multi_* forms, rays in host memory beyond the one-pixel
  * lol_gpu_pick, and the renderer.h protocol.
  */
 typedef struct lol_gpu_hits {     /* DEVICE pointers, each may be NULL (not all four); element i belongs to ray i */
@@ -695,7 +695,7 @@ int  lol_gpu_ray_queries(const lol_gpu* ctx);
  * The tile-order state, lol_gpu_set_samples / lol_gpu_set_adaptive_samples and the record rings are neither read nor written: a
  * frame after a query is the frame it would have been.
  *
- * Out of scope: a per-light shadow-factor output, normals (lol_gpu_trace_rays has them), lol_gpu_multi_* forms, rays in host
+ * Out of scope: a per-light shadow-factor output (lol_gpu_light_rays has it, below), normals (lol_gpu_trace_rays has them), lol_gpu_multi_* forms, rays in host
  * memory, a shading pick, and the renderer.h protocol.
  */
 typedef struct lol_gpu_shades {   /* DEVICE pointers, each may be NULL (not all six); element i belongs to ray i */
@@ -829,6 +829,85 @@ int  lol_gpu_render_scene_views_samples(lol_gpu* ctx, const lol_frame_camera* ca
                                         size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream);
 int  lol_gpu_set_scene_view_samples(lol_gpu* ctx, int enable);   /* before lol_gpu_upload_program */
 int  lol_gpu_scene_view_samples(const lol_gpu* ctx);
+
+/*
+ * Light passes and relighting: a new LOOK without a march.  The look of a scene is what a host changes most often once the rays are
+ * fixed: the colour and strength of its lights, the colours of its materials, the ambient colour.  get_light (naive_renderer.c:129-175)
+ * is linear in the look once three scalars per light are known, and the expensive part of a pixel — the march, the normal, the shadow
+ * marches — fixes them.  Captured once (lol_gpu_light_rays, lol_gpu_light_pixels), they make any number of looks in a memory-bound
+ * pass (lol_gpu_relight), each THE REFERENCE'S PIXEL FOR THE CHANGED SCENE, bit for bit: the pass executes the same binary32
+ * operations in the same order.  The planes are also the per-light outputs a compositing host expects: shadow and incidence per light.
+ *
+ * Ray i, its march, hit point p, normal n and eye (the ray's own origin) are exactly those of lol_gpu_shade_rays /
+ * lol_gpu_shade_pixels.  For each light l of the uploaded scene, in file order:
+ *   shadow_l = in_shadow(scene, light_l, p)                                     naive_renderer.c:136 (:93-100, :73-90)
+ *   di_l     = clamp(v3dot(n, light_dir_l), 0, 1)                               :148
+ *   si_l     = di_l * powf(clamp(v3dot(reflected_dir_l, camera_dir), 0, 1),     :158-161, camera_dir from the ray's origin
+ *                          material(id).shininess)
+ *   steps_l  = iterations of the loop at :80 that ran for light l
+ */
+typedef struct lol_gpu_light_factor { float shadow, diffuse_incidence, specular_incidence; uint32_t shadow_steps; } lol_gpu_light_factor;  /* 16 bytes */
+
+typedef struct lol_gpu_light_passes {     /* DEVICE pointers */
+	lol_gpu_light_factor* factors;  /* light-major planes: light l of ray i at factors[l * light_stride + i]; 16-byte aligned */
+	size_t    light_stride;         /* elements between planes; 0 = n; else >= n */
+	uint32_t* hit_id;               /* as lol_gpu_shades.hit_id */
+	float*    hit_dist;             /* optional */
+	uint32_t* march_steps;          /* optional: low 16 bits of lol_gpu_shades.steps */
+} lol_gpu_light_passes;
+
+typedef struct lol_gpu_relit { float* rgb_linear; float* rgb; uint32_t* pixel; } lol_gpu_relit;   /* as lol_gpu_shades'; each may be NULL, not all three */
+/*
+ * Capture.  Every factor is the reference's value, for every ray and every light: the escaped-wave skip and the zero-incidence skip
+ * are OFF for these launches, whatever lol_gpu_set_exact_skips says — a look may give material #0 a diffuse colour or a light an
+ * infinite intensity, and then the values those skips leave uncomputed are no longer multiplied into +-0.  The settled-shadow exit
+ * (bit 2) applies as it does to frames: it changes no factor; shadow_steps counts the steps really marched, and after
+ * lol_gpu_set_exact_skips(ctx, 0) it is the reference's count.  lol_gpu_set_cull applies as it does to frames.  Rays are used as
+ * given, as lol_gpu_shade_rays uses them (NaN, infinite, zero and unnormalised rays are accepted; the same per-wave test decides
+ * between the fast and the exact SDF).  lol_gpu_light_pixels is lol_gpu_shade_pixels' list of pixels, or with xy_dev == NULL every
+ * pixel of the frame: ray i is pixel (i % w, i / w), and n must be w * h.
+ * Asynchronous on `stream` as lol_gpu_shade_rays: one launch, no copy, no scratch, no host wait; nothing of the frames' state — tile
+ * order, samples, rings — is read or written.  n == 0 returns LOL_GPU_OK with nothing launched; nothing beyond element n - 1 of any
+ * plane, and nothing between the planes, is written.  A scene with no lights may pass factors == NULL.
+ * Which kernel: the interpreter's light_interp, always (see "Out of scope").
+ *
+ * Resolve.  Element i of lol_gpu_relight: with m' = look.materials[id_i ? look.root_material[id_i - 1] : 0], Id'_l, Is'_l and
+ * ambient' the look's,
+ *   total = 0
+ *   for l in file order:  total += (Id'_l * (shadow_l * di_l)) * m'.diffuse          :150-155
+ *                         total += (Is'_l * (shadow_l * si_l)) * m'.specular         :163-168
+ *   total += ambient' * m'.ambient                                                   :171-172
+ *   rgb_linear = v3clamp(total, 0, 1);  rgb = v3pow(., 1 / 2.2);  pixel = the context's pixel format
+ * bracketed and rounded exactly as written.  `look` is HOST memory (NULL = the uploaded program: the context's own device tables are
+ * read and nothing is copied) and may differ from the uploaded program in the lights' diffuse and specular intensities, the
+ * materials' diffuse, specular and ambient colours, and ambient_color — any bits, NaN and infinite included.  Everything else must be
+ * bitwise equal, which the host checks before anything is queued: n_ops, n_lights, n_materials, n_roots and max_stack; every
+ * ops[i].op, .id and .f[]; every lights[l].point; every materials[m].shininess (as bits: a NaN shininess equals itself); every
+ * root_material[].  So lol_gpu_relight(look) over planes captured from rays R IS lol_gpu_shade_rays of R on a context that uploaded
+ * the look — rgb_linear, rgb and pixel, bit for bit —, over the planes of all pixels it IS lol_gpu_render_device's frame of the look,
+ * and with look == NULL the capturing context's own shading query or frame.  An id in the planes beyond n_roots (no capture writes
+ * one) is taken for 0.
+ * The look's tables are copied before the call returns, through a ring of 8 sets of their own under the rules of lol_gpu_render_views'
+ * ring (HIP's special stream handles included); an allocation that fails returns LOL_GPU_ERR_HIP with nothing launched, and the
+ * context stays usable.  One copy and one launch, asynchronous on `stream`.
+ *
+ * Refused, with nothing launched and nothing written — LOL_GPU_ERR_ARG: no context, NULL rays_dev with n > 0, NULL out / in; NULL
+ * hit_id; NULL factors while the program has lights, or factors not 16-byte aligned; light_stride neither 0 nor >= n; all three of
+ * lol_gpu_relit NULL; max_steps < 0 or n > 2^32 - 1; w < 1, h < 1 or NULL cam; xy_dev == NULL with n != w * h; a look that differs
+ * in anything it may not differ in, a NULL table that one of its counts speaks of, a root_material out of range.
+ * LOL_GPU_ERR_NO_PROGRAM: no program uploaded.
+ *
+ * Out of scope: a scene-module capture kernel (a lol_light_spec would be one more module switch, and folding it into the shading
+ * switch would change the code object of every module compiled with that switch: the interpreter captures, at the interpreter's
+ * speed); capture over batches, blends, samples or per-record scenes; moving a light or changing a shininess (they change the
+ * factors: capture again); lol_gpu_multi_* forms; planes in host memory; and the renderer.h protocol.
+ */
+int  lol_gpu_light_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_light_passes* out, void* stream);
+int  lol_gpu_light_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
+                          const uint32_t* xy_dev /* NULL: every pixel, i = y*w + x, n must be w*h */, size_t n,
+                          const lol_gpu_light_passes* out, void* stream);
+int  lol_gpu_relight(lol_gpu* ctx, const lol_program* look /* HOST; NULL = the uploaded program */,
+                     const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,7 @@
                           [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]] [--orbit-shutter K]]
                           [--lens R (--focus D | --focus-at X,Y) --lens-samples K] [--pick X,Y] [--panorama WxH -o FILE.ppm]
                           [--tween B.lol --frames N [--tween-samples S] [--tween-shutter K] -o DIR]
+                          [--relight LOOK.lol [LOOK2.lol ...] -o DIR]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
@@ -20,7 +21,11 @@ the N frames of an animation from scene A to scene B (same structure, other numb
 scene of its own (Renderer.render_scene_views_into), and writes DIR/frame_0000.ppm ...; with --tween-shutter K each frame is the mean
 in linear light of K scenes spread over its exposure (scene.shutter_times): objects that move are blurred; with --tween-samples S
 every one of those scenes is supersampled S x S (the samples= of that call; --samples stays refused beside --tween: it is the frame
-setting of a context, which that call does not read).  The camera is A's.
+setting of a context, which that call does not read).  The camera is A's.  SCENE.lol --relight LOOK.lol [LOOK2.lol ...] -o DIR
+captures the light passes of every pixel of the --size frame ONCE (Renderer.light_pixels_into) and makes one frame per look from them
+without marching again (Renderer.relight_into): DIR/look_0000.ppm ... are the frames of the looks' scenes, byte for byte.  A look is
+the scene with other light intensities, material colours or ambient colour (scene.same_geometry); one that differs in anything else
+is refused with its first difference.  The camera is SCENE's.
 There is no CPU rendering path."""
 from __future__ import annotations
 
@@ -113,6 +118,51 @@ def tween_frames(sc, args, w, h) -> int:
     os.makedirs(args.out, exist_ok=True)
     for f in range(n):
         write_ppm(os.path.join(args.out, f"frame_{f:04d}.ppm"), frames[f])
+    return 0
+
+
+def relight_frames(sc, args, w, h) -> int:
+    """one capture of every pixel, one relight per look, one PPM per look"""
+    looks = []
+    for path in args.relight:
+        try:
+            look = S.Scene.parse_file(path)
+        except S.SceneError as e:
+            print(e.message, file=sys.stderr)
+            return 1
+        why = S.geometry_difference(sc, look)
+        if why is not None:
+            print(f"--relight {path}: not a look of {args.scene}: {why}", file=sys.stderr)
+            return 1
+        looks.append(look)
+    n, nl = w * h, len(sc.lights())
+    r = gpu.Renderer(args.device)
+    try:
+        r.prepare(sc, wait=False)            # (the capture runs on the interpreter: nothing waits for the scene compiler)
+        frames = np.zeros((len(looks), h, w), dtype=np.uint32)
+        d_factors = r.malloc(16 * n * nl) if nl else 0
+        d_id, d_px = r.malloc(4 * n), r.malloc(4 * n)
+        try:
+            t0 = time.perf_counter()
+            r.light_pixels_into(n, w, h, args.max_steps, factors_ptr=d_factors, id_ptr=d_id)
+            r.sync()
+            capture_ms = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            for i, look in enumerate(looks):
+                r.relight_into(look, n, factors_ptr=d_factors, id_ptr=d_id, pixel_ptr=d_px)
+                r.sync()
+                r.memcpy_d2h(frames[i].ctypes.data, d_px, 4 * n)
+            dt = (time.perf_counter() - t0) * 1e3
+        finally:
+            for d in (d_factors, d_id, d_px):
+                if d:
+                    r.free(d)
+    finally:
+        r.close()
+    print(f"{len(looks)} look(s) of {w}x{h}: capture {capture_ms:.3f}ms, relights and copies {dt:.3f}ms  [light_interp, relight_rays]")
+    os.makedirs(args.out, exist_ok=True)
+    for i in range(len(looks)):
+        write_ppm(os.path.join(args.out, f"look_{i:04d}.ppm"), frames[i])
     return 0
 
 
@@ -244,6 +294,9 @@ def main(argv=None) -> int:
                     help="with --tween: every frame is the mean of K scenes of its own exposure (motion blur of moving objects)")
     ap.add_argument("--tween-samples", type=int, default=1, choices=(1, 2, 4), metavar="S",
                     help="with --tween: S x S samples per pixel under every scene of every frame")
+    ap.add_argument("--relight", default=None, nargs="+", metavar="LOOK.lol",
+                    help="with -o DIR: one capture of the frame's light passes, then one frame per look (same geometry, other light "
+                         "intensities, material colours, ambient colour) without marching again")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     for name, text in (("--pick", args.pick), ("--focus-at", args.focus_at)):
@@ -264,6 +317,13 @@ def main(argv=None) -> int:
     if (args.tween_shutter != 1 or args.tween_samples != 1) and not args.tween:
         print("--tween-shutter and --tween-samples go with --tween B.lol", file=sys.stderr)
         return 1
+    if args.relight:
+        if (args.tween or args.panorama or args.orbit or args.lens or args.pick or args.samples != 1 or args.adaptive != -1
+                or args.frames != 1 or not args.out):
+            print("--relight LOOK.lol ... takes -o DIR; not with --tween, --panorama, --orbit, --lens, --pick, --samples, --adaptive "
+                  "or --frames", file=sys.stderr)
+            return 1
+        return relight_frames(sc, args, w, h)
     if args.tween:
         if (args.panorama or args.orbit or args.lens or args.pick or args.samples != 1 or args.adaptive != -1 or not args.out
                 or args.frames < 1 or args.frames * args.tween_shutter > gpu.MAX_VIEWS):

@@ -547,7 +547,10 @@ int ring_take(lol_gpu* ctx, RingSet& S, size_t need, size_t grow_to, unsigned ki
 		S.bytes = grow_to;
 	}
 	if (S.used && pinned) LOL_HIP(ctx, hipEventSynchronize(S.copied));
-	if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.done));
+	/* (an event recorded on one of HIP's special handles is waited for on the host too, whatever `s` is: a stream's
+	 * hipStreamWaitEvent for an event last recorded on the legacy default stream crashed in this HIP — the GPU suite found it) */
+	if (S.used && S.done_special) LOL_HIP(ctx, hipEventSynchronize(S.done));
+	else if (S.used) LOL_TRY(wait_on_stream(ctx, s, S.done));
 	return LOL_GPU_OK;
 }
 /* copy: the first `bytes` of the pinned half to the device on `s`, and `copied` behind them */
@@ -560,11 +563,14 @@ hipError_t ring_copy(RingSet& S, size_t bytes, hipStream_t s) {
  * took).  `e`: what that last thing returned, `what` it was.  Called on EVERY path once anything has been queued — behind a failed
  * launch, a failed copy — because the work before it is queued, and the set's next user must find it behind the event it waits for. */
 int ring_done(lol_gpu* ctx, RingSet& S, hipStream_t s, hipError_t e, const char* what, RingSet* also = nullptr) {
+	const bool special = s == hipStreamLegacy || s == hipStreamPerThread || s == nullptr;
 	hipError_t e2 = hipEventRecord(S.done, s);
 	S.used = true;
+	S.done_special = special;
 	if (also) {
 		const hipError_t e3 = hipEventRecord(also->done, s);
 		also->used = true;
+		also->done_special = special;
 		if (e2 == hipSuccess) e2 = e3;
 	}
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, what, e);
@@ -636,6 +642,7 @@ void lol_gpu_destroy(lol_gpu* ctx) {
 	ring_free(ctx->scene_view_records);
 	ring_free(ctx->adaptive_batches);
 	ring_free(ctx->blends);
+	ring_free(ctx->looks);
 	ring_free(ctx->adaptive_frames);
 	for (lol_gpu::AdaptiveFrameSet& S : ctx->adaptive_frames.sets)
 		for (hipEvent_t ev : S.ev) if (ev) (void)hipEventDestroy(ev);
@@ -2187,4 +2194,163 @@ int lol_gpu_interp_fast_paths(const lol_gpu* ctx, int* sqrt_kind, unsigned* n_di
 
 int lol_gpu_scene_views_state(const lol_gpu* ctx) { return ctx ? ctx->tiers.structure_state : LOL_GPU_ERR_ARG; }
 
+
+/*
+ * Light passes and relighting (include/lol_gpu.h; the kernels: lol_kernel_light.h).  A capture is a shading query's launch — ONE, on
+ * the caller's stream, no host wait, no copy, no scratch — with the two skips that rest on the uploaded look cleared, on the
+ * interpreter's light_interp always.  A relight copies the look's tables through a ring of their own (lol_gpu::looks) and launches
+ * relight_rays behind the copy; with no look it reads the context's own tables and copies nothing.
+ */
+/* what the planes of both calls are refused for, once the program is known to be there */
+static int passes_refused(lol_gpu* ctx, const lol_gpu_light_passes* p, size_t n, const char* who) {
+	(void)who;
+	if (!p->hit_id) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no hit_id plane");
+	if (ctx->h_prog.n_lights && !p->factors) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no factors, and the program has lights");
+	if (reinterpret_cast<uintptr_t>(p->factors) & 15u) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: factors must be 16-byte aligned");
+	if (p->light_stride != 0 && p->light_stride < n) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: light_stride is neither 0 nor at least n");
+	return LOL_GPU_OK;
+}
+
+static int light_refused(lol_gpu* ctx, const void* list_dev, bool need_list, size_t n, int max_steps, const lol_gpu_light_passes* out) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (need_list && !list_dev && n > 0) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no list");
+	if (!out) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no output");
+	if (max_steps < 0 || n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: max_steps < 0 or more than 2^32 - 1 rays");
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	return passes_refused(ctx, out, n, "capture");
+}
+
+/* `Q`: the source filled in by the caller (rays or xy, the SHADE_ / LIGHT_ flags); `cam`: the pixels' camera, or nullptr for a list of rays */
+static int launch_light(lol_gpu* ctx, lol::LightQuery& Q, const lol_frame_camera* cam, int w, int h, size_t n, int max_steps,
+                        const lol_gpu_light_passes* out, void* stream) {
+	if (n == 0) return LOL_GPU_OK;
+	lol::Launch L;
+	memset(&L, 0, sizeof L);
+	L.max_steps = max_steps;
+	scene_launch_fields(ctx, nullptr, L);
+	/* every factor of every ray: the skips that rest on the uploaded look are off, whatever the context's switches say */
+	L.flags &= ~(lol::FLAG_MISS_SKIP | lol::FLAG_DARK_SKIP);
+	const bool sane = !cam || camera_sane(*cam);
+	if (ctx->finite_scene && sane) Q.flags |= lol::SHADE_SCENE_SANE;
+	if (ctx->shadow_settle && sane) L.flags |= lol::FLAG_SHADOW_SETTLED;
+	if (cam) {
+		memcpy(&L.cam, cam, sizeof L.cam);
+		L.fw = (float)w; L.fh = (float)h;
+		L.w = w; L.h = h;
+		if (first_step(ctx, *cam, max_steps)) { L.flags |= lol::FLAG_FIRST_STEP; L.first_dist = ctx->first_dist; L.first_id = ctx->first_id; }
+	}
+	Q.n = (uint32_t)n;
+	Q.stride = out->light_stride ? out->light_stride : n;
+	Q.out = { reinterpret_cast<lol::LightFactor*>(out->factors), out->hit_id, out->hit_dist, out->march_steps };
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	const lol_program& P = ctx->h_prog;
+	const unsigned lds = lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots) ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
+	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
+	void* args[] = { &L, &Q };
+	const int kind = ctx->interp_sqrt_kind;
+	const hipError_t e = interp_dispatch(ctx, [&](auto v) {
+		constexpr int ssize = decltype(v)::ssize;
+		constexpr bool tables_global = decltype(v)::tables_global;
+		const void* fn = kind == 3 ? reinterpret_cast<const void*>(&lol::light_interp<ssize, 3, tables_global>)
+		                           : reinterpret_cast<const void*>(&lol::light_interp<ssize, 0, tables_global>);
+		return hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	});
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "light pass launch", e);
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_light_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_light_passes* out, void* stream) {
+	LOL_TRY(light_refused(ctx, rays_dev, true, n, max_steps, out));
+	lol::LightQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.rays = rays_dev;
+	return launch_light(ctx, Q, nullptr, 0, 0, n, max_steps, out, stream);
+}
+
+int lol_gpu_light_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
+                         const uint32_t* xy_dev, size_t n, const lol_gpu_light_passes* out, void* stream) {
+	LOL_TRY(light_refused(ctx, xy_dev, false, n, max_steps, out));
+	if (!cam || w < 1 || h < 1) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no camera or bad frame geometry");
+	if (!xy_dev && n != (size_t)w * (size_t)h) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no list of pixels, and n is not w * h");
+	lol::LightQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.xy = xy_dev;
+	Q.flags = lol::SHADE_FROM_PIXELS | (xy_dev ? 0u : lol::LIGHT_ALL_PIXELS);
+	return launch_light(ctx, Q, cam, w, h, n, max_steps, out, stream);
+}
+
+/* What a look may not differ from the uploaded program in, or nullptr: the first difference, for the context's error */
+static const char* look_differs(const lol_program& U, const lol_program& K) {
+	if (K.n_ops != U.n_ops || K.n_lights != U.n_lights || K.n_materials != U.n_materials || K.n_roots != U.n_roots || K.max_stack != U.max_stack)
+		return "relight: the look differs from the uploaded program in a count (ops, lights, materials, roots, max_stack)";
+	if ((K.n_ops && !K.ops) || (K.n_lights && !K.lights) || !K.materials || (K.n_roots && !K.root_material))
+		return "relight: malformed look: a table is missing";
+	for (uint32_t i = 0; i < K.n_ops; i++)
+		if (K.ops[i].op != U.ops[i].op || K.ops[i].id != U.ops[i].id || memcmp(K.ops[i].f, U.ops[i].f, sizeof K.ops[i].f) != 0)
+			return "relight: the look differs from the uploaded program in an op (opcode, id or a number): capture again";
+	for (uint32_t l = 0; l < K.n_lights; l++)
+		if (memcmp(&K.lights[l].point, &U.lights[l].point, sizeof K.lights[l].point) != 0)
+			return "relight: the look moves a light: capture again";
+	for (uint32_t m = 0; m < K.n_materials; m++)
+		if (memcmp(&K.materials[m].shininess, &U.materials[m].shininess, 4) != 0)
+			return "relight: the look changes a shininess: capture again";
+	for (uint32_t i = 0; i < K.n_roots; i++) {
+		if (K.root_material[i] >= K.n_materials) return "relight: material index out of range in the look";
+		if (K.root_material[i] != U.root_material[i]) return "relight: the look gives an object another material: capture again";
+	}
+	return nullptr;
+}
+
+int lol_gpu_relight(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (!in || !out) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no planes or no output");
+	if (!out->rgb_linear && !out->rgb && !out->pixel) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no output");
+	if (n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight: more than 2^32 - 1 elements");
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	LOL_TRY(passes_refused(ctx, in, n, "relight"));
+	if (look) if (const char* why = look_differs(ctx->h_prog, *look)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	if (n == 0) return LOL_GPU_OK;
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	lol::Launch L;
+	memset(&L, 0, sizeof L);
+	scene_launch_fields(ctx, nullptr, L);       /* counts, the context's own tables and ambient colour, gamma table, pixel format */
+	const lol_program& P = ctx->h_prog;
+	RingSet* S = nullptr;
+	if (look) {
+		/* lights | materials | root_material of the look, as an upload lays them out */
+		const size_t need = lol::table_dwords(P.n_lights, P.n_materials, P.n_roots);
+		S = &ctx->looks.next();
+		LOL_TRY(ring_take(ctx, *S, need * 4, std::max<size_t>(1024, need + need / 2) * 4, RING_PINNED, s, nullptr, "tables of a look"));
+		uint32_t* t = S->h_buf;
+		if (P.n_lights) memcpy(t, look->lights, (size_t)P.n_lights * sizeof(lol_light));
+		t += (size_t)P.n_lights * lol::LIGHT_DWORDS;
+		memcpy(t, look->materials, (size_t)P.n_materials * sizeof(lol_material));
+		t += (size_t)P.n_materials * lol::MATERIAL_DWORDS;
+		if (P.n_roots) memcpy(t, look->root_material, (size_t)P.n_roots * 4);
+		const hipError_t ce = ring_copy(*S, need * 4, s);
+		if (ce != hipSuccess) return ring_done(ctx, *S, s, ce, "copy of the tables of a look");
+		L.lights        = S->d_buf;
+		L.materials     = L.lights + (size_t)P.n_lights * lol::LIGHT_DWORDS;
+		L.root_material = L.materials + (size_t)P.n_materials * lol::MATERIAL_DWORDS;
+		L.ambient[0] = look->ambient_color.x; L.ambient[1] = look->ambient_color.y; L.ambient[2] = look->ambient_color.z;
+	}
+	lol::RelightQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
+	Q.stride = in->light_stride ? in->light_stride : n;
+	Q.hit_id = in->hit_id;
+	Q.n = (uint32_t)n;
+	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
+	const bool in_lds = lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots);
+	const unsigned lds = in_lds ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
+	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
+	void* args[] = { &L, &Q };
+	const void* fn = in_lds ? reinterpret_cast<const void*>(&lol::relight_rays<false>) : reinterpret_cast<const void*>(&lol::relight_rays<true>);
+	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	if (S) return ring_done(ctx, *S, s, e, "relight launch");
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "relight launch", e);
+	return LOL_GPU_OK;
+}
 }  // extern "C"

@@ -28,6 +28,7 @@
 #include "lol_kernel_shade.h"
 #include "lol_kernel_scenes.h"
 #include "lol_kernel_scenes_aa.h"
+#include "lol_kernel_light.h"      /* last, and its kernels are instantiated last in lol_gpu.hip: the code objects of the others stay what they are */
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -69,6 +70,10 @@ static_assert(offsetof(lol::SceneTail, views) == offsetof(lol::BatchTail, views)
               "kernel-argument layout of the scene-view kernels");
 static_assert(offsetof(lol::ShadeArgs, Q) == sizeof(lol::Launch) && sizeof(lol::ShadeArgs) == sizeof(lol::Launch) + sizeof(lol::ShadeQuery),
               "kernel-argument layout of the shading kernels");
+/* ... and a capture's is a Launch and a LightQuery behind it (lol_kernel_light.h, light_out reads the outputs there) */
+static_assert(offsetof(lol::LightArgs, Q) == sizeof(lol::Launch) && sizeof(lol::LightArgs) == sizeof(lol::Launch) + sizeof(lol::LightQuery) &&
+              sizeof(lol::LightFactor) == sizeof(lol_gpu_light_factor) && sizeof(lol_gpu_light_factor) == 16,
+              "kernel-argument layout of the capture kernels, and the factor's");
 
 #pragma GCC visibility push(hidden)
 
@@ -283,6 +288,7 @@ struct RingSet {
 	size_t     bytes = 0;                    /* each holds */
 	hipEvent_t copied = nullptr, done = nullptr;
 	bool       used = false;                 /* the set's events have been recorded: somebody may still be using it */
+	bool       done_special = false;         /* `done` was last recorded on one of HIP's special stream handles: the next user waits for it on the host */
 };
 template <class Set, int N> struct Ring {
 	Set      sets[N];
@@ -335,7 +341,7 @@ struct lol_gpu {
 	FastPaths    fast;                   /* what the upload proved on the device: the lists of scene views are built with it */
 	unsigned     module_switches = 0; /* the switch_bit()s set by lol_gpu_set_view_batches ... lol_gpu_set_shade_queries (MODULE_SWITCHES) */
 	void*        d_pick = nullptr;       /* lol_gpu_pick's device memory, from the first pick on: xy [2] | dist | id | steps | normal [3] */
-	/* The five rings of per-call device sets (RingSet above; the protocol: ring_take, ring_copy, ring_done, ring_free in lol_gpu.hip).
+	/* The six rings of per-call device sets (RingSet above; the protocol: ring_take, ring_copy, ring_done, ring_free in lol_gpu.hip).
 	 * Sets grow with what they serve and are freed in lol_gpu_destroy.
 	 *   view_records        a batch's lol::View records, pinned and on the device (queue_view_records): at least 64 views a set
 	 *   scene_view_records  the records of scene views and, behind them, every record's lists, tables and numbers
@@ -347,6 +353,8 @@ struct lol_gpu {
 	 *                       [n + 1] | prefix [n + 1] | lane table — for n views of w x h: 12 n w h bytes + 8 (n + 1) + 256 per refine block
 	 *   blends              scratch of blends (render_blend) and of blends of scene views: the linear colours [n K][h][w] of pass 1 —
 	 *                       per PIXEL, whatever the samples —, a lol::LinearColour of 16 bytes each
+	 *   looks               the tables of a look (lol_gpu_relight): lights | materials | root_material, pinned and on the device, at
+	 *                       least 1024 dwords a set, grown by half more than is needed
 	 * The two adaptive rings remember their last set, which lol_gpu_adaptive_refined / _pass_ms and lol_gpu_views_refined read. */
 	Ring<RingSet, 8> view_records, scene_view_records;
 	struct AdaptiveFrameSet : RingSet {
@@ -362,6 +370,7 @@ struct lol_gpu {
 	Ring<AdaptiveBatchSet, 4> adaptive_batches;
 	AdaptiveBatchSet* view_adaptive_last = nullptr;
 	Ring<RingSet, 4> blends;
+	Ring<RingSet, 8> looks;
 	int          fail_view_scratch = 0;        /* lol_gpu_testing_fail_view_scratch: that many scratch allocations of adaptive batches and blends still fail */
 	uint32_t*    d_adaptive_order = nullptr;   /* the refine pass's block -> lane-table slot table: slot b at tile_slot(b, stride) */
 	uint32_t     adaptive_blocks = 0, adaptive_stride = 0;      /* its size in blocks (the most a refine grid has); ceil(blocks / 8) */

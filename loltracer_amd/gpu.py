@@ -81,6 +81,19 @@ class Shades(C.Structure):           # lol_gpu_shades: device pointers, each may
                 ("hit_id", C.c_void_p), ("steps", C.c_void_p)]
 
 
+class LightFactor(C.Structure):      # lol_gpu_light_factor: 16 bytes
+    _fields_ = [("shadow", C.c_float), ("diffuse_incidence", C.c_float), ("specular_incidence", C.c_float), ("shadow_steps", C.c_uint32)]
+
+
+class LightPasses(C.Structure):      # lol_gpu_light_passes: device pointers; hit_dist and march_steps are optional
+    _fields_ = [("factors", C.c_void_p), ("light_stride", C.c_size_t), ("hit_id", C.c_void_p), ("hit_dist", C.c_void_p),
+                ("march_steps", C.c_void_p)]
+
+
+class Relit(C.Structure):            # lol_gpu_relit: device pointers, each may be NULL (not all three)
+    _fields_ = [("rgb_linear", C.c_void_p), ("rgb", C.c_void_p), ("pixel", C.c_void_p)]
+
+
 class Hit(C.Structure):              # lol_gpu_hit
     _fields_ = [("dist", C.c_float), ("id", C.c_uint32), ("steps", C.c_uint32), ("normal", C.c_float * 3)]
 
@@ -280,6 +293,13 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_compile_offline_shade.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                       C.c_char_p, C.c_size_t]
         lib.lol_gpu_compile_offline_shade.restype = C.c_int
+        # light passes and relighting (include/lol_gpu.h, "Light passes and relighting")
+        lib.lol_gpu_light_rays.argtypes = [vp, vp, C.c_size_t, C.c_int, P(LightPasses), vp]
+        lib.lol_gpu_light_rays.restype = C.c_int
+        lib.lol_gpu_light_pixels.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, vp, C.c_size_t, P(LightPasses), vp]
+        lib.lol_gpu_light_pixels.restype = C.c_int
+        lib.lol_gpu_relight.argtypes = [vp, P(S.Program), P(LightPasses), C.c_size_t, P(Relit), vp]
+        lib.lol_gpu_relight.restype = C.c_int
         lib.lol_gpu_render_scene_views.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
                                                    C.c_size_t, C.c_size_t, P(Debug), vp]
         lib.lol_gpu_render_scene_views.restype = C.c_int
@@ -431,6 +451,7 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_shade_rays", "lol_gpu_shade_pixels", "lol_gpu_set_shade_queries", "lol_gpu_shade_queries", "lol_gpu_memcpy_h2d",
     "lol_gpu_render_scene_views", "lol_gpu_set_scene_views", "lol_gpu_scene_views",
     "lol_gpu_render_scene_views_samples", "lol_gpu_set_scene_view_samples", "lol_gpu_scene_view_samples",
+    "lol_gpu_light_rays", "lol_gpu_light_pixels", "lol_gpu_relight",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
@@ -1077,6 +1098,39 @@ class Renderer:
         out = Shades(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None, dist_ptr or None, id_ptr or None, steps_ptr or None)
         self._check(self._lib.lol_gpu_shade_pixels(self._ctx, C.byref(fc), w, h, max_steps, C.c_void_p(xy_ptr), n, C.byref(out),
                                                    _stream_arg(stream)))
+
+    def light_rays_into(self, rays_ptr: int, n: int, max_steps: int = 256, factors_ptr: int = 0, id_ptr: int = 0, dist_ptr: int = 0,
+                        steps_ptr: int = 0, light_stride: int = 0, stream: int | None = None):
+        """Asynchronously capture the light passes of n rays (device memory, n x {ox, oy, oz, dx, dy, dz} floats, the rays of
+        shade_rays_into): per light l of the scene, in file order, one LightFactor (16 bytes: shadow factor, diffuse and specular
+        incidence, shadow steps) at factors[l * light_stride + i] (light_stride = 0: n), and id (needed) / dist / march steps: n
+        elements each.  Every factor is the reference's, for every ray: no skip that rests on the look applies.  relight_into makes
+        pixels of them under any look."""
+        out = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, steps_ptr or None)
+        self._check(self._lib.lol_gpu_light_rays(self._ctx, C.c_void_p(rays_ptr), n, max_steps, C.byref(out), _stream_arg(stream)))
+
+    def light_pixels_into(self, n: int, w: int, h: int, max_steps: int = 256, xy_ptr: int = 0, factors_ptr: int = 0, id_ptr: int = 0,
+                          dist_ptr: int = 0, steps_ptr: int = 0, light_stride: int = 0, stream: int | None = None,
+                          camera: S.Camera | None = None, frame_camera: S.FrameCamera | None = None):
+        """light_rays_into for the primary rays of n pixels (device memory, n x {x, y} uint32) of the w x h frame under the camera;
+        xy_ptr = 0: every pixel of the frame, element i = y w + x, and n must be w h."""
+        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        out = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, steps_ptr or None)
+        self._check(self._lib.lol_gpu_light_pixels(self._ctx, C.byref(fc), w, h, max_steps, C.c_void_p(xy_ptr) if xy_ptr else None, n,
+                                                   C.byref(out), _stream_arg(stream)))
+
+    def relight_into(self, look, n: int, factors_ptr: int = 0, id_ptr: int = 0, rgb_linear_ptr: int = 0, rgb_ptr: int = 0,
+                     pixel_ptr: int = 0, light_stride: int = 0, stream: int | None = None):
+        """Asynchronously make n elements of captured light passes into colours under `look`: a scene.Scene (flattened here) or a
+        ready scene.Program with the prepared scene's geometry (scene.same_geometry; scene.Scene.with_look gives such scenes), or
+        None: the prepared scene itself.  Element i is the pixel shade_rays_into gives ray i on a renderer that prepared the look,
+        bit for bit: rgb_linear / rgb: 3 n floats, pixel: n elements in this renderer's pixel format; 0 = not wanted (not all
+        three).  The look's tables are copied before the call returns."""
+        prog = None if look is None else look if isinstance(look, S.Program) else look.flatten()
+        planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
+        out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
+        self._check(self._lib.lol_gpu_relight(self._ctx, C.byref(prog) if prog is not None else None, C.byref(planes), n, C.byref(out),
+                                              _stream_arg(stream)))
 
     def set_cull(self, enable: bool):
         """Exact bounding-sphere culling of top-level objects in the specialised kernel; takes effect at the next prepare()."""

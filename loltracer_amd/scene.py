@@ -176,6 +176,36 @@ class Scene:
             raise SceneError(st, lib.lol_status_str(st).decode())
         return Scene(out)
 
+    def with_look(self, lights=None, materials=None, ambient=None) -> "Scene":
+        """A clone with another LOOK: only the numbers lol_gpu_relight lets a look differ in are replaced, so same_geometry(self,
+        clone) holds by construction.  lights: one entry per light, (diffuse_intensity, specular_intensity), each a 3-tuple or None
+        (keep); materials: one entry per material, (diffuse, specular, ambient) likewise; ambient: a 3-tuple.  A whole entry, or the
+        whole argument, may be None.  The numbers are stored as floats whatever they are: NaN and infinities included."""
+        out = self.clone()
+        c = out.c
+
+        def put(dst, v):
+            if v is not None:
+                dst.x, dst.y, dst.z = (float(t) for t in v)
+
+        if lights is not None:
+            if len(lights) != c.n_lights:
+                raise ValueError("with_look: one entry per light")
+            for i, e in enumerate(lights):
+                if e is not None:
+                    put(c.lights[i].diffuse_intensity, e[0])
+                    put(c.lights[i].specular_intensity, e[1])
+        if materials is not None:
+            if len(materials) != c.n_materials:
+                raise ValueError("with_look: one entry per material")
+            for i, e in enumerate(materials):
+                if e is not None:
+                    put(c.materials[i].diffuse, e[0])
+                    put(c.materials[i].specular, e[1])
+                    put(c.materials[i].ambient, e[2])
+        put(c.ambient_color, ambient)
+        return out
+
     def tables(self) -> bytes:
         """Everything the scene says, as bytes: counts, ambient colour and camera, then nodes, roots, materials and lights."""
         c = self.c
@@ -256,6 +286,41 @@ def same_structure(a: "Scene", b: "Scene") -> bool:
         if (x.type, x.a, x.b) != (y.type, y.a, y.b):
             return False
     return True
+
+
+def geometry_difference(a, b):
+    """The first thing in which b differs from a that a LOOK may not differ in, as a sentence, or None: what lol_gpu_relight checks
+    of a look against the uploaded program (include/lol_gpu.h), in its order.  a, b: Scene objects (flattened here) or Programs.
+    Equal must be, bit for bit: the counts of ops, lights, materials and roots and max_stack; every op's opcode, id and numbers;
+    every light's point; every material's shininess (a NaN shininess equals itself); every root's material index.  Free are the
+    lights' intensities, the materials' three colours and the ambient colour."""
+    pa = a if isinstance(a, Program) else a.flatten()
+    pb = b if isinstance(b, Program) else b.flatten()
+    for f in ("n_ops", "n_lights", "n_materials", "n_roots", "max_stack"):
+        if getattr(pa, f) != getattr(pb, f):
+            return f"{f} differs: {getattr(pa, f)} and {getattr(pb, f)}"
+    for i in range(pa.n_ops):
+        x, y = pa.ops[i], pb.ops[i]
+        if (x.op, x.id) != (y.op, y.id):
+            return f"op {i} differs in opcode or id"
+        if bytes(memoryview(x.f).cast("B")) != bytes(memoryview(y.f).cast("B")):
+            return f"op {i} (object {x.id}) differs in a number: {list(x.f)} and {list(y.f)}"
+    for i in range(pa.n_lights):
+        if bytes(memoryview(pa.lights[i].point).cast("B")) != bytes(memoryview(pb.lights[i].point).cast("B")):
+            return f"light {i} stands at {pa.lights[i].point.tuple()} and at {pb.lights[i].point.tuple()}"
+    for i in range(pa.n_materials):
+        if C.string_at(C.addressof(pa.materials[i]), 4) != C.string_at(C.addressof(pb.materials[i]), 4):
+            return f"material {i} has shininess {pa.materials[i].shininess} and {pb.materials[i].shininess}"
+    for i in range(pa.n_roots):
+        if pa.root_material[i] != pb.root_material[i]:
+            return f"object {i + 1} wears material {pa.root_material[i]} and {pb.root_material[i]}"
+    return None
+
+
+def same_geometry(a, b) -> bool:
+    """Is b a LOOK of a — the scene with other light intensities, material colours or ambient colour, and nothing else changed?
+    The predicate lol_gpu_relight's host check implements (geometry_difference says what differs)."""
+    return geometry_difference(a, b) is None
 
 
 def _lerp32(a, b, t):
