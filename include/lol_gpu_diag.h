@@ -133,6 +133,18 @@ int         lol_gpu_scene_views_state(const lol_gpu* ctx);
  * proven fast blend factor, and how many of those also without v_div_fixup.  All 0 with lol_gpu_set_specialize(ctx, 0) or 3 (plain
  * arithmetic) and before any upload. */
 int         lol_gpu_interp_fast_paths(const lol_gpu* ctx, int* sqrt_kind, unsigned* n_div, unsigned* n_div_no_fixup);
+/* The arithmetic of the per-pixel code around the loops in the scene kernel's fast pipeline (lol_kernel.h, ShadeMath), as the last
+ * upload decided it, and the two exhaustive comparisons on this device that it rests on.  In use: root_kind (0 the plain sqrtf, else
+ * the lol::sqrt_fast kind) and rcp_form (0 the division, else the corrections of lol::rcp_fast) — both 0 before an upload, with plain
+ * arithmetic (lol_gpu_set_specialize 0 / 3) and with LOL_GPU_SHADE_MATH=0.  Proofs ([0] the one-correction reciprocal, [1] the
+ * two-correction one): on how many of the 2^32 floats shortcut and division differ (~0: not run) and the interval of bit patterns
+ * around 1.0f that holds none of them (0 ... 0xFFFFFFFF: they agree everywhere). */
+typedef struct lol_gpu_shade_math_info {
+	int32_t  root_kind, rcp_form;
+	uint32_t proof_lo[2], proof_hi[2];
+	uint64_t proof_mismatches[2];
+} lol_gpu_shade_math_info;
+int         lol_gpu_shade_math(const lol_gpu* ctx, lol_gpu_shade_math_info* out);
 /* No device needed: the structure module of `prog` — `<out_base>.hip` (source that depends on the program's structure alone: two
  * programs of one structure give the same bytes) and `<out_base>.co`. */
 int         lol_gpu_compile_offline_scene_views(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap);

@@ -849,11 +849,16 @@ void emit_sdf(std::string& s, const lol_program& P, const char* name, const Fast
 		         "\t__device__ __forceinline__ void eval(V3 p, float& best, u32& best_id) {\n"
 		         "\t\tconst SdfOut o = %s_fn(p.x, p.y, p.z, rg.lo, rg.hi);\n"
 		         "\t\tbest = o.best; best_id = o.id; rg.lo = o.lo; rg.hi = o.hi; nanacc += o.nanacc;\n\t}\n"
-		         "\t__device__ __forceinline__ void eval_dist(V3 p, float& best) { u32 unused; eval(p, best, unused); }\n};\n", name, fast ? "true" : "false", name);
+		         "\t__device__ __forceinline__ void eval_dist(V3 p, float& best) { u32 unused; eval(p, best, unused); }\n", name, fast ? "true" : "false", name);
 		s += line;
-	} else {
-		s += "};\n";
 	}
+	/* the arithmetic of the shading around the loops that the device has proven for the fast pipeline (lol_kernel.h, ShadeMath); a
+	 * struct without it — the plain SDF, LOL_GPU_SHADE_MATH=0 — is the text it was */
+	if (fast && fast->shade_root) {
+		snprintf(line, sizeof line, "\tstruct Shade { static constexpr int ROOT = %d, RCP = %d; };\n", fast->shade_root, fast->shade_rcp);
+		s += line;
+	}
+	s += "};\n";
 }
 bool spec_out_of_line(const lol_program& P, int form) {
 	if (form == SPEC_OUT_OF_LINE) return true;
@@ -1415,6 +1420,8 @@ int lol_gpu_compile_offline_module(const lol_program* prog, const char* arch, co
 	if (assume_fast) {                 /* ISA inspection only: pretend every shortcut was proven */
 		fast.sqrt_kind = assume_fast >= 1 && assume_fast <= 3 ? 4 - assume_fast : 3;   /* 1 → sqrt_r2, 2 → sqrt_gs, 3 → sqrt_pm */
 		fast.sqrt_tiny_ok = true;
+		/* (the shading's arithmetic as an MI355X proves it: the one-correction reciprocal) */
+		if (shade_math_wanted()) { fast.shade_root = fast.sqrt_kind; fast.shade_rcp = 1; }
 		for (uint32_t i = 0; i < prog->n_ops; i++)
 			if ((prog->ops[i].op == LOL_OP_SMIN || prog->ops[i].op == LOL_OP_SMIN_R) && !fast.has(prog->ops[i].f[0]))
 				{ fast.div_ok.push_back(prog->ops[i].f[0]); fast.div_nf_ok.push_back(prog->ops[i].f[0]); }

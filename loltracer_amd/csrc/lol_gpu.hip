@@ -2192,6 +2192,18 @@ int lol_gpu_interp_fast_paths(const lol_gpu* ctx, int* sqrt_kind, unsigned* n_di
 	return LOL_GPU_OK;
 }
 
+int lol_gpu_shade_math(const lol_gpu* ctx, lol_gpu_shade_math_info* out) {
+	if (!ctx || !out) return LOL_GPU_ERR_ARG;
+	memset(out, 0, sizeof *out);
+	if (ctx->have_prog) {
+		const FastPaths& F = ctx->fast;
+		out->root_kind = F.shade_root; out->rcp_form = F.shade_rcp;
+	}
+	const IntervalProof* P[2] = { &ctx->shade_proofs.rcp[0], &ctx->shade_proofs.rcp[1] };
+	for (int i = 0; i < 2; i++) { out->proof_lo[i] = P[i]->lo; out->proof_hi[i] = P[i]->hi; out->proof_mismatches[i] = P[i]->mismatches; }
+	return LOL_GPU_OK;
+}
+
 int lol_gpu_scene_views_state(const lol_gpu* ctx) { return ctx ? ctx->tiers.structure_state : LOL_GPU_ERR_ARG; }
 
 

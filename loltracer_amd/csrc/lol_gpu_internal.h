@@ -105,7 +105,25 @@ struct BigStackThread {
 
 /* What the device has proven about its own arithmetic, as far as the scene at hand needs it (lol_proofs.hip: prove_fast_paths);
  * the generator (lol_codegen.hip) and the interpreter's lists use a shortcut only where this says so. */
+/* One exhaustive comparison of a shortcut with the expression it replaces, over all 2^32 floats: on how many they differ, and
+ * the interval of bit patterns around 1.0f that holds none of them — (0, 0xFFFFFFFF) when they agree everywhere, empty (lo > hi)
+ * when they differ at 1.0f itself. */
+struct IntervalProof {
+	unsigned long long mismatches = ~0ull;      /* ~0: not run, or could not run */
+	uint32_t lo = 1u, hi = 0u;
+	bool ran() const { return mismatches != ~0ull; }
+	bool covers(uint32_t a, uint32_t b) const { return ran() && lo <= a && b <= hi; }
+};
+/* ... of the arithmetic of the fast pipeline's shading (lol_kernel.h, ShadeMath) */
+struct ShadeProofs {
+	bool ran = false;
+	IntervalProof rcp[2];                 /* lol::rcp_fast<1>, <2> against 1.0f / x */
+};
+
 struct FastPaths {
+	/* the shading around the loops (lol_kernel.h, ShadeMath; generated into the fast SDF as its member type Shade): */
+	int shade_root = 0;                   /* len() through sqrt_fast<shade_root>: sqrt_kind, or 0 (LOL_GPU_SHADE_MATH=0) */
+	int shade_rcp = 0;                    /* 1.0f / len through rcp_fast<shade_rcp>: the cheapest form proven on [2^-48, 2^64]; 0 the division */
 	int sqrt_kind = 0;                    /* 0 plain sqrtf; 1 sqrt_pm, 2 sqrt_gs, 3 sqrt_r2 — proven on this device */
 	bool sqrt_tiny_ok = false;            /* ... and NaN-or-tiny below its domain: spheres may drop the range tracker (sd_sphere_fast_nr) */
 	std::vector<float> div_ok;            /* smoothness constants k whose smin_h_fast verified */
@@ -387,6 +405,7 @@ struct lol_gpu {
 	bool         sqrt_tiny_ok = false;   /* the second counter of that run was 0 too (sd_sphere_fast_nr) */
 	struct DivProof { uint32_t k_bits; bool ok, no_fixup_ok; };
 	std::vector<DivProof> div_verified;  /* per smoothness constant: smin_h_fast proven / proven without v_div_fixup too */
+	ShadeProofs  shade_proofs;           /* the reciprocal of the fast pipeline's shading (lol_proofs.hip, prove_shade_math) */
 	unsigned long long* d_bad = nullptr; /* mismatch counter of the verification kernels */
 	float*       d_gamma = nullptr;      /* gamma thresholds (lol_kernel.h, gamma_u8_table): GAMMA_LEVELS + 1 floats */
 	int          gamma_verified = -1;    /* -1 not run, 1 the table route == the powf route for every float in [0, 1] on this device, 0 not */
@@ -477,6 +496,9 @@ inline ModuleKernels module_kernels_of(const lol_gpu* ctx) {
 /* an A/B switch from the environment, honoured only beside LOL_GPU_TUNING=1 and recorded when it is (lol_gpu.hip) */
 const char* lol_gpu_internal_tuning_env(const char* name);
 static inline const char* tuning_env(const char* name) { return lol_gpu_internal_tuning_env(name); }
+/* LOL_GPU_SHADE_MATH=0 beside LOL_GPU_TUNING: the shading around the loops with the plain sqrtf and divisions in the fast pipeline too
+ * (lol_kernel.h, ShadeMath); every other value, and none, leaves the proven root and reciprocal on */
+static inline bool shade_math_wanted() { const char* e = tuning_env("LOL_GPU_SHADE_MATH"); return !(e && e[0] == '0' && !e[1]); }
 
 int fail(lol_gpu* ctx, int status, const char* what, hipError_t e = hipSuccess);
 #define LOL_HIP(ctx, call)                                                        \

@@ -430,6 +430,22 @@ __device__ __forceinline__ float sqrt_pm(float x) {
 	r = ep > 0.f ? rp : r;
 	return r;
 }
+/* 1.0f / x as v_rcp_f32 and FORM (1 or 2) Newton corrections, each an exact residual and an fma: 3 or 5 instructions for the 11 of
+ * the correctly rounded division (v_div_scale twice, v_rcp, five fma, v_div_fmas, v_div_fixup).  Used by the fast pipeline's shading
+ * (ShadeMath) only for lengths in [2^-48, 2^64] — the roots of squared lengths in the fast root's proven domain — and only after
+ * lol_proofs.hip has run every float through it and through 1.0f / x on this device and found that interval free of differences
+ * (verify_shade_kernel). */
+template <int FORM> __device__ __forceinline__ float rcp_fast(float x) {
+	float r = __builtin_amdgcn_rcpf(x);
+	float e = __builtin_fmaf(-x, r, 1.f);
+	r = __builtin_fmaf(e, r, r);
+	if (FORM == 2) {
+		e = __builtin_fmaf(-x, r, 1.f);
+		r = __builtin_fmaf(e, r, r);
+	}
+	return r;
+}
+constexpr u32 RCP_FAST_MIN_BITS = 0x27800000u, RCP_FAST_MAX_BITS = 0x5f800000u;      /* 2^-48, 2^64 */
 /* Unsigned min / max of the bit patterns of every squared length an evaluation took the root of:
  * for non-negative floats the bit order is the value order (NaN sorts above inf). */
 struct Range {
@@ -998,6 +1014,45 @@ __device__ __forceinline__ float soft_shadow(Sdf& sdf, V3 p, V3 dir, float max_d
 	return maxf_(res, 0.f);
 }
 
+/* The roots and reciprocals of the per-pixel code AROUND the loops — the five normalisations of a pixel (primary ray, normal,
+ * direction to the camera, one per light) — in the arithmetic the Sdf at hand allows.  An Sdf may name it in a
+ * member type Shade (lol_codegen.hip emits one into the specialised kernel's fast SDF, from what the device has proven); every other
+ * Sdf — the plain ones, the interpreter's — gets PlainShade: __builtin_sqrtf and `/`, hipcc's 16 + 11 instructions per normalisation.
+ *   ROOT      the lol::sqrt_fast KIND for len(): 5 instructions (sqrt_r2).  A squared length outside the root's proven domain
+ *             [2^-96, inf) — zero included, NaN and inf — is remembered in `bad` (an unsigned maximum of bit patterns moved down by the
+ *             lower bound: one v_sub, one v_max) and settle() turns it into the Sdf's nanacc, so that the wave is shaded again by the
+ *             plain pipeline (unproven): the proven domain decides, not what the root returned;
+ *   RCP       the lol::rcp_fast FORM for 1.0f / len, only beside ROOT: a length that is the root of a squared length in that domain
+ *             lies in [2^-48, 2^64], the interval the generator asked the proof for, so `bad` covers it. */
+struct PlainShade { static constexpr int ROOT = 0, RCP = 0; };
+template <class S> constexpr auto shade_traits(int) -> typename S::Shade { return {}; }
+template <class S> constexpr PlainShade shade_traits(long) { return {}; }
+template <class T>
+struct ShadeMath {
+	u32 bad = 0u;
+	__device__ __forceinline__ float len(V3 v) {
+		const float l2 = len2(v);
+		if constexpr (T::ROOT != 0) {
+			const u32 d = __builtin_bit_cast(u32, l2) - SQRT_FAST_MIN_BITS;
+			bad = d > bad ? d : bad;
+			return sqrt_fast<T::ROOT>(l2);
+		} else {
+			return __builtin_sqrtf(l2);
+		}
+	}
+	__device__ __forceinline__ float inv(float l) {
+		if constexpr (T::ROOT != 0 && T::RCP != 0) return rcp_fast<T::RCP>(l);
+		else return 1.0f / l;
+	}
+	__device__ __forceinline__ V3 normalize(V3 v) { return scale(v, inv(len(v))); }
+	/* call after the last len(): a squared length outside the proven domain makes this lane's nanacc NaN */
+	template <class Sdf>
+	__device__ __forceinline__ void settle(Sdf& sdf) {
+		if constexpr (T::ROOT != 0)
+			if (bad >= F32_INF_BITS - SQRT_FAST_MIN_BITS) sdf.nanacc = __builtin_nanf("");
+	}
+};
+
 /* get_normal, naive_renderer.c:114-125: k0=(1,-1,-1) k1=(-1,-1,1) k2=(-1,1,-1) k3=(1,1,1);
  * n = normalize(k0*s0 + (k1*s1 + (k2*s2 + k3*s3))), s_i = sdf(p + k_i*h).  The taps run as a rolled loop from
  * k3 down to k0 (one copy of the SDF code instead of four; + is commutative, so adding each new term on the
@@ -1007,8 +1062,8 @@ __device__ __forceinline__ float soft_shadow(Sdf& sdf, V3 p, V3 dir, float max_d
  * the loop takes one turn more, FIRST, at the point its march's last step evaluated — the same copy of the SDF code.  Then the
  * wave knows whether anything was hit at all: `lit` = false is FLAG_MISS_SKIP's "every ray of this wave escaped: no normal, no
  * shadows" (shade_pixel), and the taps are not taken. */
-template <class Sdf>
-__device__ __forceinline__ V3 normal_and_id(Sdf& sdf, V3 ro, V3 rd, const Marched& hit, V3 p, bool miss_skip, u32& id, bool& lit) {
+template <class Sdf, class SM>
+__device__ __forceinline__ V3 normal_and_id(Sdf& sdf, V3 ro, V3 rd, const Marched& hit, V3 p, bool miss_skip, u32& id, bool& lit, SM& sm) {
 	const float h = hit.dist / 100.f;
 	const float nh = -1.f * h;       /* v3scale(k, h) multiplies; -1*h == -h bit for bit */
 	V3 acc = { 0.f, 0.f, 0.f };
@@ -1033,7 +1088,13 @@ __device__ __forceinline__ V3 normal_and_id(Sdf& sdf, V3 ro, V3 rd, const Marche
 		V3 term = { px ? s : ns, py ? s : ns, pz ? s : ns };
 		acc = k == 3 ? term : add(term, acc);
 	}
-	return lit ? normalize(acc) : acc;
+	return lit ? sm.normalize(acc) : acc;
+}
+/* ... in plain arithmetic, whatever the Sdf (ray and light queries) */
+template <class Sdf>
+__device__ __forceinline__ V3 normal_and_id(Sdf& sdf, V3 ro, V3 rd, const Marched& hit, V3 p, bool miss_skip, u32& id, bool& lit) {
+	ShadeMath<PlainShade> sm;
+	return normal_and_id(sdf, ro, rd, hit, p, miss_skip, id, lit, sm);
 }
 
 __device__ __forceinline__ V3 lds_v3(const u32* base) {
@@ -1069,12 +1130,17 @@ __device__ __forceinline__ int frame_row(const Launch& L, int r) {
 
 /* The primary ray of pixel (x, y) of a frame of fw x fh pixels, naive_renderer.c:218-221 and get_camera_ray (:188-190) with the
  * per-frame basis hoisted.  (x, y) need not lie in the frame (lol_kernel_rays.h). */
-__device__ __forceinline__ V3 camera_ray(const Cam& cam, float fw, float fh, int x, int y) {
+template <class SM>
+__device__ __forceinline__ V3 camera_ray(const Cam& cam, float fw, float fh, int x, int y, SM& sm) {
 	const float vx = ((float)x + .5f) / fw * 2.f - 1.f;
 	const float vy = 1.f - ((float)y + .5f) / fh * 2.f;
 	const V3 cdir = v3(cam.dir);
 	V3 rd = add(scale(v3(cam.right), vx * cam.width), scale(v3(cam.up), vy * cam.height));
-	return normalize(add(rd, cdir));
+	return sm.normalize(add(rd, cdir));
+}
+__device__ __forceinline__ V3 camera_ray(const Cam& cam, float fw, float fh, int x, int y) {
+	ShadeMath<PlainShade> sm;
+	return camera_ray(cam, fw, fh, x, y, sm);
 }
 
 /*
@@ -1108,7 +1174,8 @@ __device__ __forceinline__ Pixel shade_pixel(const Launch& L, Sdf& sdf, const u3
 	}
 	const int y = frame_row(L, r);
 
-	const V3 rd = camera_ray(L.cam, L.fw, L.fh, x, y), ro = v3(L.cam.origin);
+	ShadeMath<decltype(shade_traits<Sdf>(0))> sm;      /* roots and reciprocals outside the loops: plain, or what the device proved for this Sdf */
+	const V3 rd = camera_ray(L.cam, L.fw, L.fh, x, y, sm), ro = v3(L.cam.origin);
 
 	const Marched marched = march<COUNT>(sdf, ro, rd, L.max_steps, (L.flags & FLAG_FIRST_STEP) != 0u, L.first_dist, L.first_id);
 
@@ -1124,7 +1191,7 @@ __device__ __forceinline__ Pixel shade_pixel(const Launch& L, Sdf& sdf, const u3
 	const V3 p = add(ro, scale(rd, marched.dist));
 	bool lit;
 	Hit hit = { marched.dist, 0u, marched.steps };
-	const V3 n = normal_and_id(sdf, ro, rd, marched, p, (L.flags & FLAG_MISS_SKIP) != 0u, hit.id, lit);
+	const V3 n = normal_and_id(sdf, ro, rd, marched, p, (L.flags & FLAG_MISS_SKIP) != 0u, hit.id, lit, sm);
 
 	/* get_material, naive_renderer.c:103-112 (per-lane table lookups) */
 	u32 mid = hit.id ? l_rootm[hit.id - 1] : 0u;
@@ -1136,12 +1203,12 @@ __device__ __forceinline__ Pixel shade_pixel(const Launch& L, Sdf& sdf, const u3
 	V3 total = { 0.f, 0.f, 0.f };
 	u32 shadow_steps = 0;
 	if (lit) {
-		const V3 camera_dir = normalize(sub(ro, p));
+		const V3 camera_dir = sm.normalize(sub(ro, p));
 		for (u32 li = 0; li < L.n_lights; li++) {
 			const u32* lp = l_light + li * LIGHT_DWORDS;
 			V3 to_light = sub(lds_v3(lp), p);
-			float light_dist = len(to_light);
-			V3 light_dir = scale(to_light, 1.0f / light_dist);      /* == v3normalize(light - p) */
+			float light_dist = sm.len(to_light);
+			V3 light_dir = scale(to_light, sm.inv(light_dist));      /* == v3normalize(light - p) */
 			float di = clampf_(dot(n, light_dir), 0.f, 1.f);
 			/*
 			 * With di == 0 (surface faces away from the light; clamp also maps NaN to 0) both terms of this
@@ -1170,6 +1237,7 @@ __device__ __forceinline__ Pixel shade_pixel(const Launch& L, Sdf& sdf, const u3
 			total = add(total, Is);
 		}
 	}
+	sm.settle(sdf);
 	total = add(total, mul(v3(L.ambient), m_amb));
 	/* v3clamp: max(min(v, 1), 0) — NaN → 1 (vec.h:63-65) */
 	V3 c = { maxf_(minf_(total.x, 1.f), 0.f), maxf_(minf_(total.y, 1.f), 0.f), maxf_(minf_(total.z, 1.f), 0.f) };

@@ -68,6 +68,32 @@ __global__ __launch_bounds__(VERIFY_THREADS) void verify_div_kernel(float k, flo
 	if (m) atomicAdd(bad + 1, (unsigned long long)m);
 }
 
+/* The reciprocal of the fast pipeline's shading (lol_kernel.h, ShadeMath), in the manner of verify_sqrt_kernel: every float through
+ * rcp_fast<FORM>(x), FORM = 1, 2, and through the 1.0f / x it replaces.
+ * out[0] counts the floats on which they differ; out[1] becomes the largest differing bit pattern below
+ * that of 1.0f, plus one, and out[2] the smallest above it, minus one: [out[1], out[2]] is the largest interval around 1.0f that
+ * holds no difference (start: 0 and 0xFFFFFFFF — they agree everywhere; a difference at 1.0f itself empties it). */
+constexpr uint32_t ONE_BITS = 0x3f800000u;
+template <int FORM>
+__global__ __launch_bounds__(VERIFY_THREADS) void verify_shade_kernel(unsigned long long* out) {
+	uint32_t base = blockIdx.x * VERIFY_THREADS + threadIdx.x;
+	unsigned n = 0;
+	uint32_t lo = 0u, hi = 0xFFFFFFFFu;
+	for (uint32_t it = 0; it < VERIFY_ITERS; it++) {
+		const uint32_t xb = base + it * (VERIFY_BLOCKS * VERIFY_THREADS);
+		const float x = __builtin_bit_cast(float, xb);
+		if (same_float(lol::rcp_fast<FORM>(x), 1.0f / x)) continue;
+		n++;
+		if (xb <= ONE_BITS && xb + 1u > lo) lo = xb + 1u;
+		if (xb >= ONE_BITS && xb - 1u < hi) hi = xb - 1u;
+	}
+	if (n) {
+		atomicAdd(out, (unsigned long long)n);
+		atomicMax(out + 1, (unsigned long long)lo);
+		atomicMin(out + 2, (unsigned long long)hi);
+	}
+}
+
 /* The gamma staircase (lol_kernel.h, "gamma + quantisation").  Thread k finds T[k], the smallest float in [0, 1] whose channel
  * value (Uint8)(powf(c, 1 / 2.2f) * 255) is >= k, by bisection over the bit patterns (for floats >= +0 the order of the bits is
  * the order of the values) — which presumes the staircase monotone; verify_gamma_kernel then proves table route == powf route
@@ -122,6 +148,34 @@ unsigned long long run_verify(lol_gpu* ctx, int sqrt_kind, float k, unsigned lon
 	return bad[0];
 }
 
+/* one run of verify_shade_kernel for the reciprocal form `form`.  A run that could not be made leaves IntervalProof::mismatches at ~0 */
+IntervalProof run_verify_shade(lol_gpu* ctx, int form) {
+	IntervalProof P;
+	unsigned long long* d = nullptr;
+	if (hipMalloc(reinterpret_cast<void**>(&d), 3 * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); return P; }
+	unsigned long long v[3] = { 0ull, 0ull, 0xFFFFFFFFull };
+	bool ok = hipMemcpy(d, v, sizeof v, hipMemcpyHostToDevice) == hipSuccess;
+	if (ok) {
+		const dim3 grid(VERIFY_BLOCKS), block(VERIFY_THREADS);
+		if (form == 2) hipLaunchKernelGGL(verify_shade_kernel<2>, grid, block, 0, ctx->stream, d);
+		else           hipLaunchKernelGGL(verify_shade_kernel<1>, grid, block, 0, ctx->stream, d);
+		ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess &&
+		     hipMemcpy(v, d, sizeof v, hipMemcpyDeviceToHost) == hipSuccess;
+	}
+	(void)hipFree(d);
+	if (!ok) { (void)hipGetLastError(); return P; }
+	P.mismatches = v[0]; P.lo = (uint32_t)v[1]; P.hi = (uint32_t)v[2];
+	return P;
+}
+
+/* the two proofs of the shading's reciprocal, once per device and process (prove_fast_paths) */
+void prove_shade_math(lol_gpu* ctx) {
+	if (ctx->shade_proofs.ran) return;
+	ctx->shade_proofs.rcp[1] = run_verify_shade(ctx, 2);
+	ctx->shade_proofs.rcp[0] = run_verify_shade(ctx, 1);
+	ctx->shade_proofs.ran = true;
+}
+
 /* the thresholds alone (a context whose device another context of this process has proven) */
 bool build_gamma_table(lol_gpu* ctx) {
 	if (ctx->d_gamma) return true;
@@ -150,6 +204,7 @@ unsigned long long run_verify_gamma(lol_gpu* ctx) {
 struct DeviceProofs {
 	int  sqrt_verified = -1; bool sqrt_tiny_ok = false;
 	int  gamma_verified = -1;
+	ShadeProofs shade;
 	std::vector<lol_gpu::DivProof> div;
 };
 std::mutex g_proofs_mutex;
@@ -162,6 +217,7 @@ void proofs_from_process(lol_gpu* ctx) {
 	const DeviceProofs& P = it->second;
 	if (ctx->sqrt_verified < 0 && P.sqrt_verified >= 0) { ctx->sqrt_verified = P.sqrt_verified; ctx->sqrt_tiny_ok = P.sqrt_tiny_ok; }
 	if (ctx->gamma_verified < 0) ctx->gamma_verified = P.gamma_verified;
+	if (!ctx->shade_proofs.ran) ctx->shade_proofs = P.shade;
 	for (const auto& e : P.div) {
 		bool known = false;
 		for (const auto& c : ctx->div_verified) known = known || c.k_bits == e.k_bits;
@@ -173,6 +229,7 @@ void proofs_to_process(const lol_gpu* ctx) {
 	DeviceProofs& P = g_proofs[ctx->device];
 	if (ctx->sqrt_verified >= 0) { P.sqrt_verified = ctx->sqrt_verified; P.sqrt_tiny_ok = ctx->sqrt_tiny_ok; }
 	if (ctx->gamma_verified >= 0) P.gamma_verified = ctx->gamma_verified;
+	if (ctx->shade_proofs.ran) P.shade = ctx->shade_proofs;
 	for (const auto& e : ctx->div_verified) {
 		bool known = false;
 		for (const auto& c : P.div) known = known || c.k_bits == e.k_bits;
@@ -193,6 +250,16 @@ FastPaths prove_fast_paths(lol_gpu* ctx, const lol_program& prog) {
 	}
 	fast.sqrt_kind = ctx->sqrt_verified;
 	fast.sqrt_tiny_ok = ctx->sqrt_tiny_ok;
+	/* the shading around the loops (lol_kernel.h, ShadeMath): the proven root for its lengths; for 1.0f / len the reciprocal form
+	 * that is proven on every length such a root can return (MI355X: both forms agree with the division on every normal x up to
+	 * 2^126, so one correction does).  LOL_GPU_SHADE_MATH=0 beside LOL_GPU_TUNING: the plain sqrtf and divisions as before. */
+	if (fast.sqrt_kind && shade_math_wanted()) {
+		prove_shade_math(ctx);
+		const ShadeProofs& S = ctx->shade_proofs;
+		fast.shade_root = fast.sqrt_kind;
+		for (int form = 1; form <= 2 && !fast.shade_rcp; form++)      /* (cheapest proven sequence wins, as for the roots) */
+			if (S.rcp[form - 1].covers(lol::RCP_FAST_MIN_BITS, lol::RCP_FAST_MAX_BITS)) fast.shade_rcp = form;
+	}
 	/* gamma + quantisation through the table (lol_kernel.h) */
 	if (ctx->gamma_verified < 0) ctx->gamma_verified = run_verify_gamma(ctx) == 0 ? 1 : 0;
 	else if (ctx->gamma_verified == 1 && !ctx->d_gamma && !build_gamma_table(ctx)) ctx->gamma_verified = 0;      /* proven by another context of this device: only the table */

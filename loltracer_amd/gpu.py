@@ -94,6 +94,11 @@ class Relit(C.Structure):            # lol_gpu_relit: device pointers, each may 
     _fields_ = [("rgb_linear", C.c_void_p), ("rgb", C.c_void_p), ("pixel", C.c_void_p)]
 
 
+class ShadeMathInfo(C.Structure):    # lol_gpu_shade_math_info (include/lol_gpu_diag.h)
+    _fields_ = [("root_kind", C.c_int32), ("rcp_form", C.c_int32), ("proof_lo", C.c_uint32 * 2), ("proof_hi", C.c_uint32 * 2),
+                ("proof_mismatches", C.c_uint64 * 2)]
+
+
 class Hit(C.Structure):              # lol_gpu_hit
     _fields_ = [("dist", C.c_float), ("id", C.c_uint32), ("steps", C.c_uint32), ("normal", C.c_float * 3)]
 
@@ -313,6 +318,9 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_scene_views_state.restype = C.c_int
         lib.lol_gpu_interp_fast_paths.argtypes = [vp, P(C.c_int), P(C.c_uint), P(C.c_uint)]
         lib.lol_gpu_interp_fast_paths.restype = C.c_int
+        if hasattr(lib, "lol_gpu_shade_math"):       # (a library named by LOL_GPU_LIB for an A/B run may be the parent commit's)
+            lib.lol_gpu_shade_math.argtypes = [vp, P(ShadeMathInfo)]
+            lib.lol_gpu_shade_math.restype = C.c_int
         lib.lol_gpu_compile_offline_scene_views.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
         lib.lol_gpu_compile_offline_scene_views.restype = C.c_int
         lib.lol_gpu_render_scene_views_samples.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -464,7 +472,7 @@ DIAG_SYMBOLS = [                                                        # includ
     "lol_gpu_trace_kernel_name", "lol_gpu_compile_offline_rays", "lol_gpu_code_key",
     "lol_gpu_shade_kernel_name", "lol_gpu_compile_offline_shade", "lol_gpu_compile_offline_module",
     "lol_gpu_scene_views_kernel_name", "lol_gpu_scene_views_state", "lol_gpu_compile_offline_scene_views",
-    "lol_gpu_interp_fast_paths",
+    "lol_gpu_interp_fast_paths", "lol_gpu_shade_math",
     "lol_gpu_scene_view_samples_kernel_name", "lol_gpu_compile_offline_scene_view_samples",
 ]
 
@@ -834,6 +842,18 @@ class Renderer:
         kind, n, nf = C.c_int(), C.c_uint(), C.c_uint()
         self._check(self._lib.lol_gpu_interp_fast_paths(self._ctx, C.byref(kind), C.byref(n), C.byref(nf)))
         return int(kind.value), int(n.value), int(nf.value)
+
+    def shade_math(self) -> dict:
+        """lol_gpu_shade_math: the arithmetic of the per-pixel code around the loops in the scene kernel's fast pipeline — "root_kind",
+        "rcp_form" as the last upload decided them — and under "proofs" the two exhaustive comparisons behind the reciprocal ("rcp1",
+        "rcp2": mismatches over all 2^32 floats, None when not run, and the interval of bit patterns around 1.0f without one)."""
+        info = ShadeMathInfo()
+        self._check(self._lib.lol_gpu_shade_math(self._ctx, C.byref(info)))
+        proofs = {}
+        for i, name in enumerate(("rcp1", "rcp2")):
+            n = int(info.proof_mismatches[i])
+            proofs[name] = {"mismatches": None if n == 2 ** 64 - 1 else n, "interval": (int(info.proof_lo[i]), int(info.proof_hi[i]))}
+        return {"root_kind": int(info.root_kind), "rcp_form": int(info.rcp_form), "proofs": proofs}
 
     def render_scene_views_into(self, dst_ptr: int, cameras, scenes, w: int, h: int, cameras_per_view: int = 1, max_steps: int = 256,
                                 pitch_bytes: int | None = None, view_stride_bytes: int | None = None, debug: Debug | None = None,
