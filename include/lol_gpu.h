@@ -899,7 +899,8 @@ typedef struct lol_gpu_relit { float* rgb_linear; float* rgb; uint32_t* pixel; }
  *
  * Out of scope: a scene-module capture kernel (a lol_light_spec would be one more module switch, and folding it into the shading
  * switch would change the code object of every module compiled with that switch: the interpreter captures, at the interpreter's
- * speed); capture over batches, blends, samples or per-record scenes; moving a light or changing a shininess (they change the
+ * speed); capture in ONE launch over batches, blends or samples (lol_gpu_light_views, below, covers them with one capture launch
+ * per camera, and lol_gpu_relight_views resolves them); per-record scenes; moving a light or changing a shininess (they change the
  * factors: capture again); lol_gpu_multi_* forms; planes in host memory; and the renderer.h protocol.
  */
 int  lol_gpu_light_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_light_passes* out, void* stream);
@@ -908,6 +909,54 @@ int  lol_gpu_light_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int 
                           const lol_gpu_light_passes* out, void* stream);
 int  lol_gpu_relight(lol_gpu* ctx, const lol_program* look /* HOST; NULL = the uploaded program */,
                      const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream);
+
+/*
+ * Relit views: the AVERAGED pictures of a look without a march — the supersampled frame (lol_gpu_set_samples), the blend over K
+ * cameras (lol_gpu_render_views_blend: motion blur, depth of field) and the supersampled blend (lol_gpu_render_views_blend_samples),
+ * from captured light passes.  All of those average in LINEAR light, in a fixed binary32 tree, before gamma; averaging relit 8-bit
+ * pixels on the host is not that (see lol_gpu_render_views_blend).  Sample (i, j) of pixel (x, y) is by contract pixel (s x + i,
+ * s y + j) of the s w x s h frame under the same camera (lol_frame_camera_init gives the same bits for both sizes), so a capture of
+ * every pixel of that frame holds every sample, and the camera of a blend is one more capture.
+ *
+ * The planes.  K = cams_per_view in {1, 2, 4, 8, 16}, s = samples in {1, 2, 4}.  LEAF (v, k, Y, X) — sample column X < s w, sample row
+ * Y < s h under cams[v K + k] — is element e = ((v K + k) s h + Y) s w + X of N = n_views K s^2 w h.  The factor planes are
+ * light-major over all N elements (light l of element e at factors[l * light_stride + e]; light_stride 0 = N, else >= N); hit_id,
+ * hit_dist and march_steps are dense over e.
+ *
+ * lol_gpu_light_views is a host loop of n_views * K CAPTURE LAUNCHES and nothing else: record r = v K + k is exactly
+ * lol_gpu_light_pixels(ctx, &cams[r], s w, s h, max_steps, NULL, s^2 w h, ...) into the planes r s^2 w h elements further on, with the
+ * light stride of the whole; everything that call takes applies per record (the settled-shadow exit, culling, the per-camera
+ * decisions).  The whole call is validated before the first launch: refused, nothing is launched; a HIP failure in the loop is
+ * reported as that call reports it, with the earlier records queued.
+ *
+ * lol_gpu_relight_views makes pixel (x, y) of view v, bracketed and rounded exactly so:
+ *   1. per leaf, c = the rgb_linear of lol_gpu_relight for its element under `look` (an id beyond n_roots is taken for 0);
+ *   2. per camera k, m_k = the balanced binary32 tree over the s^2 leaves (s x + i, s y + j) in order j s + i, times 1 / s^2
+ *      (s = 1: the leaf itself, unscaled);
+ *   3. the balanced tree over m_0 ... m_{K-1} in order of k, times 1 / K (K = 1: m_0 itself);
+ *   4. gamma and the context's pixel format, exactly as for one sample's colour.
+ * Each camera's scale first, then the tree over the cameras: the order lol_gpu_render_views_blend_samples fixes.  The outputs are
+ * dense over pixels, at index (v h + y) w + x: rgb_linear the mean before gamma (the render calls do not expose it), rgb the mean
+ * after gamma, pixel the packed pixel; any subset, not none.  So, bit for bit: K = 1 and s = 1 is lol_gpu_relight over N elements
+ * (the call forwards to it); K = 1, s > 1 over a capture of all samples is lol_gpu_render_device's frame of a context that uploaded
+ * the look and has lol_gpu_set_samples(s); K > 1 is the view of lol_gpu_render_views_blend / _blend_samples on such a context; and
+ * look == NULL gives the capturing context's own views.
+ * The look is checked, copied and ringed exactly as lol_gpu_relight does (the same ring of 8 sets, the same refusals).  One copy and
+ * ONE launch (relight_views), asynchronous on `stream`; nothing of the frames' state — tile order, samples, rings of batches and
+ * blends — is read or written.
+ *
+ * Refused, with nothing launched and nothing written — LOL_GPU_ERR_ARG: everything lol_gpu_relight and lol_gpu_light_pixels refuse
+ * (NULL cams among it); cams_per_view outside {1, 2, 4, 8, 16}; samples outside {1, 2, 4}; n_views < 1, w < 1 or h < 1;
+ * N > 2^32 - 1; a light_stride neither 0 nor >= N.  LOL_GPU_ERR_NO_PROGRAM: no program uploaded.
+ *
+ * Out of scope: a scene-module capture kernel (as above); edge-adaptive relit supersampling; per-record scenes; lol_gpu_multi_*
+ * forms; planes in host memory; pitch or stride addressing of the outputs.
+ */
+int  lol_gpu_light_views(lol_gpu* ctx, const lol_frame_camera* cams /* HOST */, int n_views, int cams_per_view,
+                         int w, int h, int samples, int max_steps, const lol_gpu_light_passes* out, void* stream);
+int  lol_gpu_relight_views(lol_gpu* ctx, const lol_program* look /* HOST; NULL = the uploaded program */,
+                           const lol_gpu_light_passes* in, int n_views, int cams_per_view, int w, int h, int samples,
+                           const lol_gpu_relit* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
                           [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]] [--orbit-shutter K]]
                           [--lens R (--focus D | --focus-at X,Y) --lens-samples K] [--pick X,Y] [--panorama WxH -o FILE.ppm]
                           [--tween B.lol --frames N [--tween-samples S] [--tween-shutter K] -o DIR]
-                          [--relight LOOK.lol [LOOK2.lol ...] -o DIR]
+                          [--relight LOOK.lol [LOOK2.lol ...] [--samples S] [--lens R --focus D --lens-samples K] -o DIR]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
@@ -25,7 +25,10 @@ setting of a context, which that call does not read).  The camera is A's.  SCENE
 captures the light passes of every pixel of the --size frame ONCE (Renderer.light_pixels_into) and makes one frame per look from them
 without marching again (Renderer.relight_into): DIR/look_0000.ppm ... are the frames of the looks' scenes, byte for byte.  A look is
 the scene with other light intensities, material colours or ambient colour (scene.same_geometry); one that differs in anything else
-is refused with its first difference.  The camera is SCENE's.
+is refused with its first difference.  The camera is SCENE's.  With --samples S, or --lens R --focus D --lens-samples K [--samples S],
+beside --relight the looks are AVERAGED frames: every sample under every lens camera is captured once (Renderer.light_views_into: one
+capture per camera) and each look is resolved in linear light before gamma (Renderer.relight_views_into) — the files LOOK.lol with
+the same flags and without --relight writes, byte for byte.  Not with --adaptive or --focus-at.
 There is no CPU rendering path."""
 from __future__ import annotations
 
@@ -135,23 +138,33 @@ def relight_frames(sc, args, w, h) -> int:
             print(f"--relight {path}: not a look of {args.scene}: {why}", file=sys.stderr)
             return 1
         looks.append(look)
-    n, nl = w * h, len(sc.lights())
+    # the leaves of the frame: s x s samples under each of the K cameras of the lens (one camera, the scene's, without --lens)
+    s, k = args.samples, args.lens_samples if args.lens else 1
+    cams = S.lens_cameras(sc.camera, args.focus, args.lens, k) if args.lens else [sc.camera]
+    averaged = s > 1 or k > 1
+    n, nl = k * s * s * w * h, len(sc.lights())
     r = gpu.Renderer(args.device)
     try:
         r.prepare(sc, wait=False)            # (the capture runs on the interpreter: nothing waits for the scene compiler)
         frames = np.zeros((len(looks), h, w), dtype=np.uint32)
         d_factors = r.malloc(16 * n * nl) if nl else 0
-        d_id, d_px = r.malloc(4 * n), r.malloc(4 * n)
+        d_id, d_px = r.malloc(4 * n), r.malloc(4 * w * h)
         try:
             t0 = time.perf_counter()
-            r.light_pixels_into(n, w, h, args.max_steps, factors_ptr=d_factors, id_ptr=d_id)
+            if averaged:
+                r.light_views_into(cams, k, w, h, s, args.max_steps, factors_ptr=d_factors, id_ptr=d_id)
+            else:
+                r.light_pixels_into(n, w, h, args.max_steps, factors_ptr=d_factors, id_ptr=d_id)
             r.sync()
             capture_ms = (time.perf_counter() - t0) * 1e3
             t0 = time.perf_counter()
             for i, look in enumerate(looks):
-                r.relight_into(look, n, factors_ptr=d_factors, id_ptr=d_id, pixel_ptr=d_px)
+                if averaged:
+                    r.relight_views_into(look, 1, k, w, h, s, factors_ptr=d_factors, id_ptr=d_id, pixel_ptr=d_px)
+                else:
+                    r.relight_into(look, n, factors_ptr=d_factors, id_ptr=d_id, pixel_ptr=d_px)
                 r.sync()
-                r.memcpy_d2h(frames[i].ctypes.data, d_px, 4 * n)
+                r.memcpy_d2h(frames[i].ctypes.data, d_px, 4 * w * h)
             dt = (time.perf_counter() - t0) * 1e3
         finally:
             for d in (d_factors, d_id, d_px):
@@ -159,7 +172,9 @@ def relight_frames(sc, args, w, h) -> int:
                     r.free(d)
     finally:
         r.close()
-    print(f"{len(looks)} look(s) of {w}x{h}: capture {capture_ms:.3f}ms, relights and copies {dt:.3f}ms  [light_interp, relight_rays]")
+    shape = f", {s}x{s} samples per pixel" * (s > 1) + f", {k} lens cameras" * (k > 1)
+    print(f"{len(looks)} look(s) of {w}x{h}{shape}: capture {capture_ms:.3f}ms, relights and copies {dt:.3f}ms  "
+          f"[light_interp, {'relight_views' if averaged else 'relight_rays'}]")
     os.makedirs(args.out, exist_ok=True)
     for i in range(len(looks)):
         write_ppm(os.path.join(args.out, f"look_{i:04d}.ppm"), frames[i])
@@ -318,10 +333,13 @@ def main(argv=None) -> int:
         print("--tween-shutter and --tween-samples go with --tween B.lol", file=sys.stderr)
         return 1
     if args.relight:
-        if (args.tween or args.panorama or args.orbit or args.lens or args.pick or args.samples != 1 or args.adaptive != -1
-                or args.frames != 1 or not args.out):
-            print("--relight LOOK.lol ... takes -o DIR; not with --tween, --panorama, --orbit, --lens, --pick, --samples, --adaptive "
-                  "or --frames", file=sys.stderr)
+        if (args.tween or args.panorama or args.orbit or args.pick or args.focus_at or args.adaptive != -1 or args.frames != 1
+                or not args.out):
+            print("--relight LOOK.lol ... takes -o DIR, and --samples S or --lens R --focus D --lens-samples K for averaged frames; "
+                  "not with --tween, --panorama, --orbit, --pick, --focus-at, --adaptive or --frames", file=sys.stderr)
+            return 1
+        if args.lens < 0 or (args.lens and not args.focus > 0) or (args.focus and not args.lens):
+            print("--relight with --lens R takes a radius > 0 and --focus D > 0", file=sys.stderr)
             return 1
         return relight_frames(sc, args, w, h)
     if args.tween:

@@ -2314,22 +2314,14 @@ static const char* look_differs(const lol_program& U, const lol_program& K) {
 	return nullptr;
 }
 
-int lol_gpu_relight(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	if (!in || !out) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no planes or no output");
-	if (!out->rgb_linear && !out->rgb && !out->pixel) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no output");
-	if (n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight: more than 2^32 - 1 elements");
-	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
-	LOL_TRY(passes_refused(ctx, in, n, "relight"));
-	if (look) if (const char* why = look_differs(ctx->h_prog, *look)) return fail(ctx, LOL_GPU_ERR_ARG, why);
-	if (n == 0) return LOL_GPU_OK;
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-	lol::Launch L;
+/* The Launch of a resolve under `look` (nullptr: the context's own tables, nothing copied): counts, gamma table and pixel format the
+ * context's; a look's lights | materials | root_material go through lol_gpu::looks onto the device behind what `s` holds, and `S` is
+ * then the ring's set, which the caller hands to ring_done with its launch. */
+static int relight_launch_fields(lol_gpu* ctx, const lol_program* look, hipStream_t s, lol::Launch& L, RingSet*& S) {
 	memset(&L, 0, sizeof L);
 	scene_launch_fields(ctx, nullptr, L);       /* counts, the context's own tables and ambient colour, gamma table, pixel format */
 	const lol_program& P = ctx->h_prog;
-	RingSet* S = nullptr;
+	S = nullptr;
 	if (look) {
 		/* lights | materials | root_material of the look, as an upload lays them out */
 		const size_t need = lol::table_dwords(P.n_lights, P.n_materials, P.n_roots);
@@ -2348,6 +2340,24 @@ int lol_gpu_relight(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_p
 		L.root_material = L.materials + (size_t)P.n_materials * lol::MATERIAL_DWORDS;
 		L.ambient[0] = look->ambient_color.x; L.ambient[1] = look->ambient_color.y; L.ambient[2] = look->ambient_color.z;
 	}
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_relight(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (!in || !out) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no planes or no output");
+	if (!out->rgb_linear && !out->rgb && !out->pixel) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no output");
+	if (n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight: more than 2^32 - 1 elements");
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	LOL_TRY(passes_refused(ctx, in, n, "relight"));
+	if (look) if (const char* why = look_differs(ctx->h_prog, *look)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	if (n == 0) return LOL_GPU_OK;
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	lol::Launch L;
+	RingSet* S;
+	LOL_TRY(relight_launch_fields(ctx, look, s, L, S));
+	const lol_program& P = ctx->h_prog;
 	lol::RelightQuery Q;
 	memset(&Q, 0, sizeof Q);
 	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
@@ -2360,6 +2370,89 @@ int lol_gpu_relight(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_p
 	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
 	void* args[] = { &L, &Q };
 	const void* fn = in_lds ? reinterpret_cast<const void*>(&lol::relight_rays<false>) : reinterpret_cast<const void*>(&lol::relight_rays<true>);
+	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	if (S) return ring_done(ctx, *S, s, e, "relight launch");
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "relight launch", e);
+	return LOL_GPU_OK;
+}
+
+/*
+ * Relit averaged pixels (include/lol_gpu.h, "Relit views"; the kernel: lol_kernel_light_views.h).  The capture is a host loop over
+ * lol_gpu_light_pixels — n_views K launches, record r into the planes at r s^2 w h — and adds no kernel and no capture path; the
+ * resolve is lol_gpu_relight's copy of the look and ONE launch of relight_views.
+ */
+/* What both calls refuse in the shape of the planes, in this order; *n_out = N = n_views K s^2 w h */
+static int views_shape_refused(lol_gpu* ctx, int n_views, int cams_per_view, int w, int h, int samples, size_t* n_out) {
+	if (n_views < 1 || w < 1 || h < 1) return fail(ctx, LOL_GPU_ERR_ARG, "relit views: n_views < 1 or bad frame geometry");
+	const int K = cams_per_view, s = samples;
+	if (K != 1 && K != 2 && K != 4 && K != 8 && K != 16) return fail(ctx, LOL_GPU_ERR_ARG, "relit views: cams_per_view must be 1, 2, 4, 8 or 16");
+	if (s != 1 && s != 2 && s != 4) return fail(ctx, LOL_GPU_ERR_ARG, "relit views: samples must be 1, 2 or 4");
+	const unsigned __int128 N = (unsigned __int128)n_views * (unsigned)K * (unsigned)(s * s) * (unsigned)w * (unsigned)h;
+	if (N > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relit views: more than 2^32 - 1 elements");
+	*n_out = (size_t)N;
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_light_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view, int w, int h, int samples,
+                        int max_steps, const lol_gpu_light_passes* out, void* stream) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (!out) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no output");
+	if (max_steps < 0) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: max_steps < 0 or more than 2^32 - 1 rays");
+	if (!cams) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no camera or bad frame geometry");
+	size_t N = 0;
+	LOL_TRY(views_shape_refused(ctx, n_views, cams_per_view, w, h, samples, &N));
+	LOL_TRY(light_refused(ctx, nullptr, false, N, max_steps, out));        /* no program; the planes, against all N elements */
+	/* the whole call has passed: record r is lol_gpu_light_pixels of the s w x s h frame under cams[r], r s^2 w h elements further on */
+	const size_t per = N / ((size_t)n_views * (size_t)cams_per_view);
+	const int records = n_views * cams_per_view;
+	for (int r = 0; r < records; r++) {
+		const size_t at = (size_t)r * per;
+		lol_gpu_light_passes sub;
+		sub.factors      = out->factors ? out->factors + at : nullptr;
+		sub.light_stride = out->light_stride ? out->light_stride : N;
+		sub.hit_id       = out->hit_id + at;
+		sub.hit_dist     = out->hit_dist ? out->hit_dist + at : nullptr;
+		sub.march_steps  = out->march_steps ? out->march_steps + at : nullptr;
+		LOL_TRY(lol_gpu_light_pixels(ctx, &cams[r], samples * w, samples * h, max_steps, nullptr, per, &sub, stream));
+	}
+	return LOL_GPU_OK;
+}
+
+int lol_gpu_relight_views(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, int n_views, int cams_per_view,
+                          int w, int h, int samples, const lol_gpu_relit* out, void* stream) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (!in || !out) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no planes or no output");
+	if (!out->rgb_linear && !out->rgb && !out->pixel) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no output");
+	size_t N = 0;
+	LOL_TRY(views_shape_refused(ctx, n_views, cams_per_view, w, h, samples, &N));
+	if (cams_per_view == 1 && samples == 1) return lol_gpu_relight(ctx, look, in, N, out, stream);      /* a pixel is its one leaf */
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	LOL_TRY(passes_refused(ctx, in, N, "relight"));
+	if (look) if (const char* why = look_differs(ctx->h_prog, *look)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	lol::Launch L;
+	RingSet* S;
+	LOL_TRY(relight_launch_fields(ctx, look, s, L, S));
+	const lol_program& P = ctx->h_prog;
+	lol::RelightViewsQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
+	Q.stride = in->light_stride ? in->light_stride : N;
+	Q.hit_id = in->hit_id;
+	Q.n_pixels = (uint32_t)((size_t)n_views * (size_t)w * (size_t)h);
+	Q.w = (uint32_t)w; Q.h = (uint32_t)h;
+	Q.s_log2 = samples == 4 ? 2u : samples == 2 ? 1u : 0u;
+	Q.cams = (uint32_t)cams_per_view;
+	Q.last_view = (uint32_t)n_views - 1u;
+	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
+	const bool in_lds = lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots);
+	const unsigned lds = in_lds ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
+	/* a wave per 64 pixels, whatever s and K: it takes them in s^2 rounds of 64 / s^2 */
+	const unsigned long long lanes = ((unsigned long long)Q.n_pixels + 63u) / 64u * 64u;
+	const dim3 grid((unsigned)((lanes + lol::BLOCK - 1) / lol::BLOCK));
+	void* args[] = { &L, &Q };
+	const void* fn = in_lds ? reinterpret_cast<const void*>(&lol::relight_views<false>) : reinterpret_cast<const void*>(&lol::relight_views<true>);
 	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
 	if (S) return ring_done(ctx, *S, s, e, "relight launch");
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "relight launch", e);

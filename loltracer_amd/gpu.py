@@ -305,6 +305,11 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_light_pixels.restype = C.c_int
         lib.lol_gpu_relight.argtypes = [vp, P(S.Program), P(LightPasses), C.c_size_t, P(Relit), vp]
         lib.lol_gpu_relight.restype = C.c_int
+        # relit views (include/lol_gpu.h, "Relit views")
+        lib.lol_gpu_light_views.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(LightPasses), vp]
+        lib.lol_gpu_light_views.restype = C.c_int
+        lib.lol_gpu_relight_views.argtypes = [vp, P(S.Program), P(LightPasses), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(Relit), vp]
+        lib.lol_gpu_relight_views.restype = C.c_int
         lib.lol_gpu_render_scene_views.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
                                                    C.c_size_t, C.c_size_t, P(Debug), vp]
         lib.lol_gpu_render_scene_views.restype = C.c_int
@@ -459,7 +464,7 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_shade_rays", "lol_gpu_shade_pixels", "lol_gpu_set_shade_queries", "lol_gpu_shade_queries", "lol_gpu_memcpy_h2d",
     "lol_gpu_render_scene_views", "lol_gpu_set_scene_views", "lol_gpu_scene_views",
     "lol_gpu_render_scene_views_samples", "lol_gpu_set_scene_view_samples", "lol_gpu_scene_view_samples",
-    "lol_gpu_light_rays", "lol_gpu_light_pixels", "lol_gpu_relight",
+    "lol_gpu_light_rays", "lol_gpu_light_pixels", "lol_gpu_relight", "lol_gpu_light_views", "lol_gpu_relight_views",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
@@ -1151,6 +1156,43 @@ class Renderer:
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
         self._check(self._lib.lol_gpu_relight(self._ctx, C.byref(prog) if prog is not None else None, C.byref(planes), n, C.byref(out),
                                               _stream_arg(stream)))
+
+    def light_views_into(self, cameras, cameras_per_view: int, w: int, h: int, samples: int = 1, max_steps: int = 256,
+                         factors_ptr: int = 0, id_ptr: int = 0, dist_ptr: int = 0, steps_ptr: int = 0, light_stride: int = 0,
+                         stream: int | None = None):
+        """Asynchronously capture the light passes of every LEAF of len(cameras) / cameras_per_view views of w x h with samples x
+        samples samples per pixel (lol_gpu_light_views): camera r's samples x w by samples x h sample grid is light_pixels_into of
+        that frame, into the planes r samples^2 w h elements further on — one capture launch per camera.  Element
+        ((v K + k) s h + Y) s w + X is sample column X, sample row Y under cameras[v K + k]; N = len(cameras) s^2 w h elements,
+        light_stride = 0: N.  cameras: scene.Camera or ready scene.FrameCamera objects.  relight_views_into makes the averaged
+        pixels of any look from them."""
+        cams = list(cameras)
+        k = int(cameras_per_view)
+        if k < 1 or len(cams) % k:
+            raise ValueError("light_views_into: len(cameras) must be a multiple of cameras_per_view")
+        arr = (S.FrameCamera * max(1, len(cams)))()
+        for i, c in enumerate(cams):
+            fc = c if isinstance(c, S.FrameCamera) else self.scene.frame_camera(w, h, c)
+            C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
+        out = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, steps_ptr or None)
+        self._check(self._lib.lol_gpu_light_views(self._ctx, arr, len(cams) // k, k, w, h, int(samples), max_steps, C.byref(out),
+                                                  _stream_arg(stream)))
+
+    def relight_views_into(self, look, n_views: int, cameras_per_view: int, w: int, h: int, samples: int = 1, factors_ptr: int = 0,
+                           id_ptr: int = 0, rgb_linear_ptr: int = 0, rgb_ptr: int = 0, pixel_ptr: int = 0, light_stride: int = 0,
+                           stream: int | None = None):
+        """Asynchronously make the n_views averaged views of w x h under `look` (as relight_into takes it: a scene.Scene, a ready
+        scene.Program, or None) from the planes of light_views_into (lol_gpu_relight_views): per leaf relight_into's linear colour,
+        per camera the tree mean over its samples x samples leaves, then the tree mean over the cameras_per_view cameras, then gamma
+        and this renderer's pixel format — the supersampled frame, the blend, or the supersampled blend of a renderer that prepared
+        the look, bit for bit, in one copy and one launch.  rgb_linear / rgb: 3 floats per pixel, pixel: one element, dense over
+        [view, y, x]; 0 = not wanted (not all three)."""
+        prog = None if look is None else look if isinstance(look, S.Program) else look.flatten()
+        planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
+        out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
+        self._check(self._lib.lol_gpu_relight_views(self._ctx, C.byref(prog) if prog is not None else None, C.byref(planes),
+                                                    int(n_views), int(cameras_per_view), w, h, int(samples), C.byref(out),
+                                                    _stream_arg(stream)))
 
     def set_cull(self, enable: bool):
         """Exact bounding-sphere culling of top-level objects in the specialised kernel; takes effect at the next prepare()."""
