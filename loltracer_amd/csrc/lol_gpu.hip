@@ -78,25 +78,6 @@ std::mutex g_rtc_mutex;
 
 namespace {
 
-template <int SSIZE>
-hipError_t launch_sdf_interp(const uint32_t* mops, uint32_t n_mops, const float* pts, float* dist, uint32_t* id, uint32_t n,
-                             hipStream_t s, int sqrt_kind) {
-	dim3 grid((n + 63) / 64);
-	if (sqrt_kind == 3) hipLaunchKernelGGL((lol::sdf_points_interp<SSIZE, 3>), grid, dim3(64), 0, s, mops, n_mops, pts, dist, id, n);
-	else                hipLaunchKernelGGL((lol::sdf_points_interp<SSIZE, 0>), grid, dim3(64), 0, s, mops, n_mops, pts, dist, id, n);
-	return hipGetLastError();
-}
-
-/* ray queries on the interpreter (lol_kernel_rays.h, trace_interp): per stack class and root kind, like the SDF alone above — neither
- * reads lights or materials, so where the tables lie (interp_rung) does not matter to them */
-template <int SSIZE>
-hipError_t launch_trace_interp(const lol::RayQuery& Q, hipStream_t s, int sqrt_kind) {
-	dim3 grid((Q.n + 63u) / 64u);
-	if (sqrt_kind == 3) hipLaunchKernelGGL((lol::trace_interp<SSIZE, 3>), grid, dim3(64), 0, s, Q);
-	else                hipLaunchKernelGGL((lol::trace_interp<SSIZE, 0>), grid, dim3(64), 0, s, Q);
-	return hipGetLastError();
-}
-
 /* the interpreter's kernel of a family (lol_gpu_internal.h, KERNEL_FAMILIES) for one stack class, sqrt kind and table placement: its
  * address, for hipLaunchKernel */
 template <int SSIZE, int KIND, bool TABLES_GLOBAL>
@@ -319,7 +300,7 @@ KernelFamily frame_family(const lol_gpu* ctx) { return ctx->samples == 1 ? FAM_F
 const char* kernel_name(const lol_gpu* ctx) { return family_name(ctx, frame_family(ctx)); }
 
 /* The interpreter's instantiation for the program's stack class and table placement — THE ladder, for every kernel the interpreter
- * has (launch_family): launch(ssize, tables_global) is called with the two as compile-time constants. */
+ * has (launch_family, the list queries, lol_gpu_sdf_batch): launch(InterpVariant) is called with the two as compile-time constants. */
 template <int SSIZE, bool TABLES_GLOBAL = false> struct InterpVariant {
 	static constexpr int ssize = SSIZE;
 	static constexpr bool tables_global = TABLES_GLOBAL;
@@ -333,23 +314,27 @@ InterpRung interp_rung(const lol_program& P) {
 	if (lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots)) return { cls, false };
 	return { cls <= 3 ? 3 : cls <= lol::MOP_DEEP_FROM - 1 ? lol::MOP_DEEP_FROM - 1 : lol::MOP_DEEP_SLOTS, true };
 }
+/* the five stack classes with the tables in LDS — and ALL the rungs of a kernel that reads no table (the SDF alone, a ray query):
+ * lol_gpu_sdf_batch and ray_query come here directly */
+template <class Launcher>
+hipError_t stack_class_dispatch(int ssize, Launcher&& launch) {
+	switch (ssize) {
+	case 1:  return launch(InterpVariant<1>());
+	case 3:  return launch(InterpVariant<3>());
+	case 7:  return launch(InterpVariant<7>());
+	case lol::MOP_DEEP_FROM - 1: return launch(InterpVariant<lol::MOP_DEEP_FROM - 1>());
+	case lol::MOP_DEEP_SLOTS:    return launch(InterpVariant<lol::MOP_DEEP_SLOTS>());
+	}
+	return hipErrorInvalidValue;           /* a class without an instantiation: never a silent substitute */
+}
 template <class Launcher>
 hipError_t interp_dispatch(const lol_gpu* ctx, Launcher&& launch) {
 	const InterpRung r = interp_rung(ctx->h_prog);
-	if (!r.tables_global) {
-		switch (r.ssize) {
-		case 1:  return launch(InterpVariant<1>());
-		case 3:  return launch(InterpVariant<3>());
-		case 7:  return launch(InterpVariant<7>());
-		case lol::MOP_DEEP_FROM - 1: return launch(InterpVariant<lol::MOP_DEEP_FROM - 1>());
-		case lol::MOP_DEEP_SLOTS:    return launch(InterpVariant<lol::MOP_DEEP_SLOTS>());
-		}
-	} else {
-		switch (r.ssize) {
-		case 3:  return launch(InterpVariant<3, true>());
-		case lol::MOP_DEEP_FROM - 1: return launch(InterpVariant<lol::MOP_DEEP_FROM - 1, true>());
-		case lol::MOP_DEEP_SLOTS:    return launch(InterpVariant<lol::MOP_DEEP_SLOTS, true>());
-		}
+	if (!r.tables_global) return stack_class_dispatch(r.ssize, launch);
+	switch (r.ssize) {
+	case 3:  return launch(InterpVariant<3, true>());
+	case lol::MOP_DEEP_FROM - 1: return launch(InterpVariant<lol::MOP_DEEP_FROM - 1, true>());
+	case lol::MOP_DEEP_SLOTS:    return launch(InterpVariant<lol::MOP_DEEP_SLOTS, true>());
 	}
 	return hipErrorInvalidValue;           /* a rung without an instantiation: never a silent substitute */
 }
@@ -1738,94 +1723,223 @@ int lol_gpu_sdf_batch(lol_gpu* ctx, const float* pts_dev, float* dist_dev, uint3
 		void* args[] = { &pts_dev, &dist_dev, &id_dev, &n32 };
 		e = hipModuleLaunchKernel(k->sdf, (n32 + 63) / 64, 1, 1, 64, 1, 1, 0, s, args, nullptr);
 	} else {
+		/* per stack class and root kind; the SDF alone reads no lights or materials, so where the tables lie (interp_rung) does not matter */
 		const int kind = ctx->interp_sqrt_kind;
-		const int cls = interp_stack_class(ctx->h_prog.max_stack);
-		if (cls == 1)      e = launch_sdf_interp<1>(ctx->d_mops[ctx->cur], ctx->n_mops, pts_dev, dist_dev, id_dev, n32, s, kind);
-		else if (cls == 3) e = launch_sdf_interp<3>(ctx->d_mops[ctx->cur], ctx->n_mops, pts_dev, dist_dev, id_dev, n32, s, kind);
-		else if (cls == 7) e = launch_sdf_interp<7>(ctx->d_mops[ctx->cur], ctx->n_mops, pts_dev, dist_dev, id_dev, n32, s, kind);
-		else if (cls == lol::MOP_DEEP_FROM - 1) e = launch_sdf_interp<lol::MOP_DEEP_FROM - 1>(ctx->d_mops[ctx->cur], ctx->n_mops, pts_dev, dist_dev, id_dev, n32, s, kind);
-		else               e = launch_sdf_interp<lol::MOP_DEEP_SLOTS>(ctx->d_mops[ctx->cur], ctx->n_mops, pts_dev, dist_dev, id_dev, n32, s, kind);
+		e = stack_class_dispatch(interp_stack_class(ctx->h_prog.max_stack), [&](auto v) {
+			constexpr int ssize = decltype(v)::ssize;
+			const dim3 grid((n32 + 63) / 64);
+			const uint32_t* mops = ctx->d_mops[ctx->cur];
+			if (kind == 3) hipLaunchKernelGGL((lol::sdf_points_interp<ssize, 3>), grid, dim3(64), 0, s, mops, ctx->n_mops, pts_dev, dist_dev, id_dev, n32);
+			else           hipLaunchKernelGGL((lol::sdf_points_interp<ssize, 0>), grid, dim3(64), 0, s, mops, ctx->n_mops, pts_dev, dist_dev, id_dev, n32);
+			return hipGetLastError();
+		});
 	}
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "sdf kernel launch", e);
 	return LOL_GPU_OK;
 }
 
+}  // extern "C"
+
 /*
- * Ray queries (include/lol_gpu.h; the kernel: lol_kernel_rays.h).  ONE launch on the caller's stream: no host wait, no copy, no
- * scratch, and nothing of the context changes but — for a list of pixels — the cached first step of the camera's position
- * (first_step: a function of that position alone, whoever asks).  The tile-order state, the samples, the pixel format and the record
- * rings are neither read nor written.
+ * List queries: ray queries, shading queries and light passes (include/lol_gpu.h; the kernels: lol_kernel_rays.h, lol_kernel_shade.h,
+ * lol_kernel_light.h).  Each call is ONE launch over a list of n elements on the caller's stream: no host wait, no copy, no scratch,
+ * and nothing of the context changes but — for a list of pixels — the cached first step of the camera's position (first_step: a
+ * function of that position alone, whoever asks).  The tile-order state, the samples and the record rings are neither read nor
+ * written.  What the families share stands here once:
+ *   QuerySource         where a call's elements come from, and the name its family's refusals carry
+ *   source_refused      every refusal of a *_rays or *_pixels call, in the order a host sees them
+ *   launch_on_stream    the call's device, its stream, the launch and the launch's error
+ *   launch_scene_query  the scene's half of a shading query's or a capture's launch: the Launch, what rests on the camera, the tables' LDS
  */
+struct QuerySource {
+	const char*     who;             /* "ray query", "shading query", "light passes": what the family's refusals begin with */
+	const float*    rays;            /* a list of rays, or ... */
+	const uint32_t* xy;              /* ... (`pixels`) of pixels of the w x h frame under `cam` */
+	bool            pixels;
+	const lol_frame_camera* cam;
+	int             w, h;
+	size_t          n;
+	int             max_steps;
+	void*           stream;
+	bool            list_optional;   /* a capture's: no list is every pixel of the frame, n = w h */
+};
+static QuerySource rays_source(const char* who, const float* rays, size_t n, int max_steps, void* stream) {
+	return { who, rays, nullptr, false, nullptr, 0, 0, n, max_steps, stream, false };
+}
+static QuerySource pixels_source(const char* who, const lol_frame_camera* cam, int w, int h, const uint32_t* xy, size_t n, int max_steps,
+                                 void* stream, bool list_optional = false) {
+	return { who, nullptr, xy, true, cam, w, h, n, max_steps, stream, list_optional };
+}
+
+/* what the planes of a capture or of a relight are refused for, once the program is known to be there */
+static int passes_refused(lol_gpu* ctx, const lol_gpu_light_passes* p, size_t n) {
+	if (!p->hit_id) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no hit_id plane");
+	if (ctx->h_prog.n_lights && !p->factors) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no factors, and the program has lights");
+	if (reinterpret_cast<uintptr_t>(p->factors) & 15u) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: factors must be 16-byte aligned");
+	if (p->light_stride != 0 && p->light_stride < n) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: light_stride is neither 0 nor at least n");
+	return LOL_GPU_OK;
+}
+
+/* The refusals of a list query, in THE order (tests/test_gpu_rays.py, test_refusals, and its three siblings pin it): a bad argument
+ * beats a missing program, and a missing program the camera and the frame's geometry — which are asked for with n = 0 too.
+ * `no_output`: the family's own test of its outputs; `planes`: a capture's, held to passes_refused where the parent held them. */
+static int source_refused(lol_gpu* ctx, const QuerySource& src, bool no_output, const lol_gpu_light_passes* planes = nullptr) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	auto refuse = [&](const char* why) {
+		char text[128];
+		snprintf(text, sizeof text, "%s: %s", src.who, why);
+		return fail(ctx, LOL_GPU_ERR_ARG, text);           /* (fail copies the text) */
+	};
+	if (!(src.pixels ? (const void*)src.xy : (const void*)src.rays) && !src.list_optional && src.n > 0) return refuse("no list");
+	if (no_output) return refuse("no output");
+	if (src.max_steps < 0 || src.n > 0xFFFFFFFFu) return refuse("max_steps < 0 or more than 2^32 - 1 rays");
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	if (planes) LOL_TRY(passes_refused(ctx, planes, src.n));
+	if (!src.pixels) return LOL_GPU_OK;
+	if (!src.cam || src.w < 1 || src.h < 1) return refuse("no camera or bad frame geometry");
+	if (!src.xy && src.list_optional && src.n != (size_t)src.w * (size_t)src.h) return refuse("no list of pixels, and n is not w * h");
+	return LOL_GPU_OK;
+}
+
+/* `launch(s)` on the context's device and the call's stream; `what` names the launch where it fails */
+template <class Launch>
+static int launch_on_stream(lol_gpu* ctx, void* stream, const char* what, Launch&& launch) {
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	const hipError_t e = launch(s);
+	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, what, e);
+	return LOL_GPU_OK;
+}
+
+/* dynamic LDS of the kernels that stage the scene's tables and nothing else (lol_kernel.h, tables_in_lds): no output tile */
+static unsigned tables_lds_bytes(const lol_program& P) {
+	return lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots) ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
+}
+
+/* ---- ray queries.  A RayQuery carries its own camera: no Launch, no tables, a wave per block. */
 /* the scene kernel that answers queries, or nullptr: trace_interp does — the test the launch makes and lol_gpu_trace_kernel_name reports */
 static const SceneKernel* trace_kernel(const lol_gpu* ctx) {
 	const SceneKernel* k = scene_kernel(ctx);
 	return k && k->trace ? k : nullptr;
 }
 
-/* what both sources are refused for */
-static int query_refused(lol_gpu* ctx, const void* list_dev, size_t n, int max_steps, const lol_gpu_hits* out) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	if (!list_dev && n > 0) return fail(ctx, LOL_GPU_ERR_ARG, "ray query: no list");
-	if (!out || (!out->dist && !out->id && !out->steps && !out->normal)) return fail(ctx, LOL_GPU_ERR_ARG, "ray query: no output");
-	if (max_steps < 0 || n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "ray query: max_steps < 0 or more than 2^32 - 1 rays");
-	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
-	return LOL_GPU_OK;
-}
-
-/* `Q`: the source filled in by the caller (rays or xy, flags, camera) */
-static int launch_query(lol_gpu* ctx, lol::RayQuery& Q, size_t n, int max_steps, const lol_gpu_hits* out, void* stream) {
-	if (n == 0) return LOL_GPU_OK;
-	Q.n = (uint32_t)n;
-	Q.max_steps = max_steps;
+static int ray_query(lol_gpu* ctx, const QuerySource& src, const lol_gpu_hits* out) {
+	LOL_TRY(source_refused(ctx, src, !out || (!out->dist && !out->id && !out->steps && !out->normal)));
+	if (src.n == 0) return LOL_GPU_OK;
+	lol::RayQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.rays = src.rays;
+	Q.xy = src.xy;
+	Q.n = (uint32_t)src.n;
+	Q.max_steps = src.max_steps;
+	if (src.pixels) {
+		Q.flags = lol::RAYS_FROM_PIXELS;
+		memcpy(&Q.cam, src.cam, sizeof Q.cam);
+		Q.fw = (float)src.w; Q.fh = (float)src.h;
+		if (first_step(ctx, *src.cam, src.max_steps)) { Q.flags |= lol::RAYS_FIRST_STEP; Q.first_dist = ctx->first_dist; Q.first_id = ctx->first_id; }
+	}
 	/* the scene's side of what the fast SDF rests on (shadow_settle_ok, whatever lol_gpu_set_exact_skips says: no shadow is cast);
 	 * the rays' side is the kernel's own ballot */
 	if (ctx->finite_scene) Q.flags |= lol::RAYS_SCENE_SANE;
 	if (out->id) Q.flags |= lol::RAYS_WANT_ID;
 	if (out->normal) Q.flags |= lol::RAYS_WANT_NORMAL;
 	Q.out = { out->dist, out->id, out->steps, out->normal };
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-	finish_specialise(ctx, false);           /* a scene kernel that has finished compiling takes over here, as at a frame boundary */
-	hipError_t e;
-	if (const SceneKernel* k = trace_kernel(ctx)) {
-		void* args[] = { &Q };
-		e = hipModuleLaunchKernel(k->trace, (Q.n + 63u) / 64u, 1, 1, 64, 1, 1, 0, s, args, nullptr);
-	} else {
-		/* the list every camera may use (with v_div_fixup: upload_program), as lol_gpu_sdf_batch */
+	return launch_on_stream(ctx, src.stream, "ray query launch", [&](hipStream_t s) {
+		finish_specialise(ctx, false);           /* a scene kernel that has finished compiling takes over here, as at a frame boundary */
+		const dim3 grid((Q.n + 63u) / 64u);
+		if (const SceneKernel* k = trace_kernel(ctx)) {
+			void* args[] = { &Q };
+			return hipModuleLaunchKernel(k->trace, grid.x, 1, 1, 64, 1, 1, 0, s, args, nullptr);
+		}
+		/* the list every camera may use (with v_div_fixup: upload_program), as lol_gpu_sdf_batch; per stack class and root kind, as there */
 		Q.ops = ctx->d_mops[ctx->cur];
 		Q.n_ops = ctx->n_mops;
 		const int kind = ctx->interp_sqrt_kind;
-		const int cls = interp_stack_class(ctx->h_prog.max_stack);
-		if (cls == 1)      e = launch_trace_interp<1>(Q, s, kind);
-		else if (cls == 3) e = launch_trace_interp<3>(Q, s, kind);
-		else if (cls == 7) e = launch_trace_interp<7>(Q, s, kind);
-		else if (cls == lol::MOP_DEEP_FROM - 1) e = launch_trace_interp<lol::MOP_DEEP_FROM - 1>(Q, s, kind);
-		else               e = launch_trace_interp<lol::MOP_DEEP_SLOTS>(Q, s, kind);
-	}
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "ray query launch", e);
-	return LOL_GPU_OK;
+		return stack_class_dispatch(interp_stack_class(ctx->h_prog.max_stack), [&](auto v) {
+			constexpr int ssize = decltype(v)::ssize;
+			if (kind == 3) hipLaunchKernelGGL((lol::trace_interp<ssize, 3>), grid, dim3(64), 0, s, Q);
+			else           hipLaunchKernelGGL((lol::trace_interp<ssize, 0>), grid, dim3(64), 0, s, Q);
+			return hipGetLastError();
+		});
+	});
 }
 
+/* ---- shading queries.  The scene's half of the launch is a frame's (scene_launch_fields: tables, ambient, the skips that hold for
+ * every camera, the gamma table, the pixel format). */
+/* the scene kernel that answers shading queries, or nullptr: shade_interp does — the test the launch makes and lol_gpu_shade_kernel_name reports */
+static const SceneKernel* shade_kernel(const lol_gpu* ctx) {
+	const SceneKernel* k = scene_kernel(ctx);
+	return k && k->shade ? k : nullptr;
+}
+/* ... at a launch: a scene kernel that has finished compiling takes over here, as at a frame boundary */
+static hipFunction_t shade_module_fn(lol_gpu* ctx) {
+	finish_specialise(ctx, false);
+	const SceneKernel* k = shade_kernel(ctx);
+	return k ? k->shade : nullptr;
+}
+
+/* The scene's half of a shading query or a capture, and the launch; nothing for n = 0.  `Q`: zeroed but for the family's own fields;
+ * its source is filled in here.  `clear_look_skips`: a capture's — every factor of every ray, so the two skips that rest on the
+ * uploaded look are off, whatever the context's switches say.  `module_fn`: the scene module's kernel at this launch, where the family
+ * has one (a capture has none: light_interp always, and no tier takes over at a capture).  `interp_kernel(variant, kind)`: the
+ * interpreter's instantiation. */
+template <class Query, class InterpKernel>
+static int launch_scene_query(lol_gpu* ctx, const QuerySource& src, Query& Q, bool clear_look_skips, hipFunction_t (*module_fn)(lol_gpu*),
+                              const char* what, InterpKernel&& interp_kernel) {
+	if (src.n == 0) return LOL_GPU_OK;
+	lol::Launch L;
+	memset(&L, 0, sizeof L);
+	L.max_steps = src.max_steps;
+	/* the macro-op list every camera may use (with v_div_fixup: upload_program), as ray_query: scene_launch_fields' */
+	scene_launch_fields(ctx, nullptr, L);
+	if (clear_look_skips) L.flags &= ~(lol::FLAG_MISS_SKIP | lol::FLAG_DARK_SKIP);
+	/* the host's side of what the fast SDF and the settled shadow loop rest on: the scene (shadow_settle_ok) and, where the rays are a
+	 * camera's, the camera, as lol_gpu_render_device; the side of a list's rays is the kernel's own ballot (shade_rays, light_rays) */
+	const bool sane = !src.pixels || camera_sane(*src.cam);
+	if (ctx->finite_scene && sane) Q.flags |= lol::SHADE_SCENE_SANE;
+	if (ctx->shadow_settle && sane) L.flags |= lol::FLAG_SHADOW_SETTLED;
+	if (src.pixels) {
+		Q.flags |= lol::SHADE_FROM_PIXELS;
+		memcpy(&L.cam, src.cam, sizeof L.cam);
+		L.fw = (float)src.w; L.fh = (float)src.h;
+		L.w = src.w; L.h = src.h;
+		if (first_step(ctx, *src.cam, src.max_steps)) { L.flags |= lol::FLAG_FIRST_STEP; L.first_dist = ctx->first_dist; L.first_id = ctx->first_id; }
+	}
+	Q.rays = src.rays;
+	Q.xy = src.xy;
+	Q.n = (uint32_t)src.n;
+	return launch_on_stream(ctx, src.stream, what, [&](hipStream_t s) {
+		const hipFunction_t fn = module_fn ? module_fn(ctx) : nullptr;
+		const unsigned lds = tables_lds_bytes(ctx->h_prog);
+		const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
+		void* args[] = { &L, &Q };
+		if (fn) return hipModuleLaunchKernel(fn, grid.x, 1, 1, lol::BLOCK, 1, 1, lds, s, args, nullptr);
+		const int kind = ctx->interp_sqrt_kind;
+		return interp_dispatch(ctx, [&](auto v) {
+			const void* k = kind == 3 ? interp_kernel(v, std::integral_constant<int, 3>()) : interp_kernel(v, std::integral_constant<int, 0>());
+			return hipLaunchKernel(k, grid, dim3(lol::BLOCK), args, lds, s);
+		});
+	});
+}
+
+static int shade_query(lol_gpu* ctx, const QuerySource& src, const lol_gpu_shades* out) {
+	LOL_TRY(source_refused(ctx, src, !out || (!out->rgb_linear && !out->rgb && !out->pixel && !out->hit_dist && !out->hit_id && !out->steps)));
+	lol::ShadeQuery Q = {};
+	Q.out = { out->rgb_linear, out->rgb, out->pixel, out->hit_dist, out->hit_id, out->steps };
+	return launch_scene_query(ctx, src, Q, false, shade_module_fn, "shading query launch", [](auto v, auto kind) {
+		return reinterpret_cast<const void*>(&lol::shade_interp<decltype(v)::ssize, decltype(kind)::value, decltype(v)::tables_global>);
+	});
+}
+
+extern "C" {
+
 int lol_gpu_trace_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_hits* out, void* stream) {
-	LOL_TRY(query_refused(ctx, rays_dev, n, max_steps, out));
-	lol::RayQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.rays = rays_dev;
-	return launch_query(ctx, Q, n, max_steps, out, stream);
+	return ray_query(ctx, rays_source("ray query", rays_dev, n, max_steps, stream), out);
 }
 
 int lol_gpu_trace_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
                          const uint32_t* xy_dev, size_t n, const lol_gpu_hits* out, void* stream) {
-	LOL_TRY(query_refused(ctx, xy_dev, n, max_steps, out));
-	if (!cam || w < 1 || h < 1) return fail(ctx, LOL_GPU_ERR_ARG, "ray query: no camera or bad frame geometry");
-	lol::RayQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.xy = xy_dev;
-	Q.flags = lol::RAYS_FROM_PIXELS;
-	memcpy(&Q.cam, cam, sizeof Q.cam);
-	Q.fw = (float)w; Q.fh = (float)h;
-	if (n > 0 && first_step(ctx, *cam, max_steps)) { Q.flags |= lol::RAYS_FIRST_STEP; Q.first_dist = ctx->first_dist; Q.first_id = ctx->first_id; }
-	return launch_query(ctx, Q, n, max_steps, out, stream);
+	return ray_query(ctx, pixels_source("ray query", cam, w, h, xy_dev, n, max_steps, stream), out);
 }
 
 int lol_gpu_pick(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps, int x, int y, lol_gpu_hit* out) {
@@ -1855,93 +1969,13 @@ const char* lol_gpu_trace_kernel_name(const lol_gpu* ctx) {
 	return trace_kernel(ctx) ? "lol_trace_spec" : "trace_interp";
 }
 
-/*
- * Shading queries (include/lol_gpu.h; the kernel: lol_kernel_shade.h).  ONE launch on the caller's stream: no host wait, no copy, no
- * scratch, and nothing of the context changes but — for a list of pixels — the cached first step of the camera's position.  The
- * scene's half of the launch is a frame's (scene_launch_fields: tables, ambient, the skips that hold for every camera, the gamma
- * table, the pixel format); the tile-order state, the samples and the record rings are neither read nor written.
- */
-/* the scene kernel that answers shading queries, or nullptr: shade_interp does — the test the launch makes and lol_gpu_shade_kernel_name reports */
-static const SceneKernel* shade_kernel(const lol_gpu* ctx) {
-	const SceneKernel* k = scene_kernel(ctx);
-	return k && k->shade ? k : nullptr;
-}
-
-/* what both sources are refused for, as query_refused */
-static int shade_refused(lol_gpu* ctx, const void* list_dev, size_t n, int max_steps, const lol_gpu_shades* out) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	if (!list_dev && n > 0) return fail(ctx, LOL_GPU_ERR_ARG, "shading query: no list");
-	if (!out || (!out->rgb_linear && !out->rgb && !out->pixel && !out->hit_dist && !out->hit_id && !out->steps))
-		return fail(ctx, LOL_GPU_ERR_ARG, "shading query: no output");
-	if (max_steps < 0 || n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "shading query: max_steps < 0 or more than 2^32 - 1 rays");
-	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
-	return LOL_GPU_OK;
-}
-
-/* `Q`: the source filled in by the caller (rays or xy, SHADE_FROM_PIXELS); `cam`: the pixels' camera, or nullptr for a list of rays */
-static int launch_shade(lol_gpu* ctx, lol::ShadeQuery& Q, const lol_frame_camera* cam, int w, int h, size_t n, int max_steps,
-                        const lol_gpu_shades* out, void* stream) {
-	if (n == 0) return LOL_GPU_OK;
-	lol::Launch L;
-	memset(&L, 0, sizeof L);
-	L.max_steps = max_steps;
-	/* the macro-op list every camera may use (with v_div_fixup: upload_program), as launch_query: scene_launch_fields' */
-	scene_launch_fields(ctx, nullptr, L);
-	/* the host's side of what the fast SDF and the settled shadow loop rest on: the scene (shadow_settle_ok) and, where the rays are a
-	 * camera's, the camera, as lol_gpu_render_device; the side of a list's rays is the kernel's own ballot (shade_rays) */
-	const bool sane = !cam || camera_sane(*cam);
-	if (ctx->finite_scene && sane) Q.flags |= lol::SHADE_SCENE_SANE;
-	if (ctx->shadow_settle && sane) L.flags |= lol::FLAG_SHADOW_SETTLED;
-	if (cam) {
-		memcpy(&L.cam, cam, sizeof L.cam);
-		L.fw = (float)w; L.fh = (float)h;
-		L.w = w; L.h = h;
-		if (first_step(ctx, *cam, max_steps)) { L.flags |= lol::FLAG_FIRST_STEP; L.first_dist = ctx->first_dist; L.first_id = ctx->first_id; }
-	}
-	Q.n = (uint32_t)n;
-	Q.out = { out->rgb_linear, out->rgb, out->pixel, out->hit_dist, out->hit_id, out->steps };
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-	finish_specialise(ctx, false);           /* a scene kernel that has finished compiling takes over here, as at a frame boundary */
-	/* dynamic LDS: the scene's tables where they are staged (lol_kernel.h, tables_in_lds); no output tile */
-	const lol_program& P = ctx->h_prog;
-	const unsigned lds = lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots) ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
-	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
-	void* args[] = { &L, &Q };
-	hipError_t e;
-	if (const SceneKernel* k = shade_kernel(ctx)) {
-		e = hipModuleLaunchKernel(k->shade, grid.x, 1, 1, lol::BLOCK, 1, 1, lds, s, args, nullptr);
-	} else {
-		const int kind = ctx->interp_sqrt_kind;
-		e = interp_dispatch(ctx, [&](auto v) {
-			constexpr int ssize = decltype(v)::ssize;
-			constexpr bool tables_global = decltype(v)::tables_global;
-			const void* fn = kind == 3 ? reinterpret_cast<const void*>(&lol::shade_interp<ssize, 3, tables_global>)
-			                           : reinterpret_cast<const void*>(&lol::shade_interp<ssize, 0, tables_global>);
-			return hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
-		});
-	}
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "shading query launch", e);
-	return LOL_GPU_OK;
-}
-
 int lol_gpu_shade_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_shades* out, void* stream) {
-	LOL_TRY(shade_refused(ctx, rays_dev, n, max_steps, out));
-	lol::ShadeQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.rays = rays_dev;
-	return launch_shade(ctx, Q, nullptr, 0, 0, n, max_steps, out, stream);
+	return shade_query(ctx, rays_source("shading query", rays_dev, n, max_steps, stream), out);
 }
 
 int lol_gpu_shade_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
                          const uint32_t* xy_dev, size_t n, const lol_gpu_shades* out, void* stream) {
-	LOL_TRY(shade_refused(ctx, xy_dev, n, max_steps, out));
-	if (!cam || w < 1 || h < 1) return fail(ctx, LOL_GPU_ERR_ARG, "shading query: no camera or bad frame geometry");
-	lol::ShadeQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.xy = xy_dev;
-	Q.flags = lol::SHADE_FROM_PIXELS;
-	return launch_shade(ctx, Q, cam, w, h, n, max_steps, out, stream);
+	return shade_query(ctx, pixels_source("shading query", cam, w, h, xy_dev, n, max_steps, stream), out);
 }
 
 const char* lol_gpu_shade_kernel_name(const lol_gpu* ctx) {
@@ -2207,89 +2241,24 @@ int lol_gpu_shade_math(const lol_gpu* ctx, lol_gpu_shade_math_info* out) {
 int lol_gpu_scene_views_state(const lol_gpu* ctx) { return ctx ? ctx->tiers.structure_state : LOL_GPU_ERR_ARG; }
 
 
+}  // extern "C"
+
 /*
- * Light passes and relighting (include/lol_gpu.h; the kernels: lol_kernel_light.h).  A capture is a shading query's launch — ONE, on
- * the caller's stream, no host wait, no copy, no scratch — with the two skips that rest on the uploaded look cleared, on the
- * interpreter's light_interp always.  A relight copies the look's tables through a ring of their own (lol_gpu::looks) and launches
- * relight_rays behind the copy; with no look it reads the context's own tables and copies nothing.
+ * Light passes and relighting (include/lol_gpu.h; the kernels: lol_kernel_light.h).  A capture is a list query (above), launched as
+ * a shading query is (launch_scene_query) with the two skips that rest on the uploaded look cleared, on the interpreter's light_interp
+ * always.  A resolve — lol_gpu_relight, and lol_gpu_relight_views below — is refused by relit_refused and look_refused and launched
+ * by launch_resolve: it copies the look's tables through a ring of their own (lol_gpu::looks) and launches its kernel behind the copy;
+ * with no look it reads the context's own tables and copies nothing.
  */
-/* what the planes of both calls are refused for, once the program is known to be there */
-static int passes_refused(lol_gpu* ctx, const lol_gpu_light_passes* p, size_t n, const char* who) {
-	(void)who;
-	if (!p->hit_id) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no hit_id plane");
-	if (ctx->h_prog.n_lights && !p->factors) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no factors, and the program has lights");
-	if (reinterpret_cast<uintptr_t>(p->factors) & 15u) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: factors must be 16-byte aligned");
-	if (p->light_stride != 0 && p->light_stride < n) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: light_stride is neither 0 nor at least n");
-	return LOL_GPU_OK;
-}
-
-static int light_refused(lol_gpu* ctx, const void* list_dev, bool need_list, size_t n, int max_steps, const lol_gpu_light_passes* out) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	if (need_list && !list_dev && n > 0) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no list");
-	if (!out) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no output");
-	if (max_steps < 0 || n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: max_steps < 0 or more than 2^32 - 1 rays");
-	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
-	return passes_refused(ctx, out, n, "capture");
-}
-
-/* `Q`: the source filled in by the caller (rays or xy, the SHADE_ / LIGHT_ flags); `cam`: the pixels' camera, or nullptr for a list of rays */
-static int launch_light(lol_gpu* ctx, lol::LightQuery& Q, const lol_frame_camera* cam, int w, int h, size_t n, int max_steps,
-                        const lol_gpu_light_passes* out, void* stream) {
-	if (n == 0) return LOL_GPU_OK;
-	lol::Launch L;
-	memset(&L, 0, sizeof L);
-	L.max_steps = max_steps;
-	scene_launch_fields(ctx, nullptr, L);
-	/* every factor of every ray: the skips that rest on the uploaded look are off, whatever the context's switches say */
-	L.flags &= ~(lol::FLAG_MISS_SKIP | lol::FLAG_DARK_SKIP);
-	const bool sane = !cam || camera_sane(*cam);
-	if (ctx->finite_scene && sane) Q.flags |= lol::SHADE_SCENE_SANE;
-	if (ctx->shadow_settle && sane) L.flags |= lol::FLAG_SHADOW_SETTLED;
-	if (cam) {
-		memcpy(&L.cam, cam, sizeof L.cam);
-		L.fw = (float)w; L.fh = (float)h;
-		L.w = w; L.h = h;
-		if (first_step(ctx, *cam, max_steps)) { L.flags |= lol::FLAG_FIRST_STEP; L.first_dist = ctx->first_dist; L.first_id = ctx->first_id; }
-	}
-	Q.n = (uint32_t)n;
-	Q.stride = out->light_stride ? out->light_stride : n;
+static int light_query(lol_gpu* ctx, const QuerySource& src, const lol_gpu_light_passes* out) {
+	LOL_TRY(source_refused(ctx, src, !out, out));
+	lol::LightQuery Q = {};
+	if (src.pixels && !src.xy) Q.flags = lol::LIGHT_ALL_PIXELS;
+	Q.stride = out->light_stride ? out->light_stride : src.n;
 	Q.out = { reinterpret_cast<lol::LightFactor*>(out->factors), out->hit_id, out->hit_dist, out->march_steps };
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-	const lol_program& P = ctx->h_prog;
-	const unsigned lds = lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots) ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
-	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
-	void* args[] = { &L, &Q };
-	const int kind = ctx->interp_sqrt_kind;
-	const hipError_t e = interp_dispatch(ctx, [&](auto v) {
-		constexpr int ssize = decltype(v)::ssize;
-		constexpr bool tables_global = decltype(v)::tables_global;
-		const void* fn = kind == 3 ? reinterpret_cast<const void*>(&lol::light_interp<ssize, 3, tables_global>)
-		                           : reinterpret_cast<const void*>(&lol::light_interp<ssize, 0, tables_global>);
-		return hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	return launch_scene_query(ctx, src, Q, true, nullptr, "light pass launch", [](auto v, auto kind) {
+		return reinterpret_cast<const void*>(&lol::light_interp<decltype(v)::ssize, decltype(kind)::value, decltype(v)::tables_global>);
 	});
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "light pass launch", e);
-	return LOL_GPU_OK;
-}
-
-int lol_gpu_light_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_light_passes* out, void* stream) {
-	LOL_TRY(light_refused(ctx, rays_dev, true, n, max_steps, out));
-	lol::LightQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.rays = rays_dev;
-	return launch_light(ctx, Q, nullptr, 0, 0, n, max_steps, out, stream);
-}
-
-int lol_gpu_light_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
-                         const uint32_t* xy_dev, size_t n, const lol_gpu_light_passes* out, void* stream) {
-	LOL_TRY(light_refused(ctx, xy_dev, false, n, max_steps, out));
-	if (!cam || w < 1 || h < 1) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no camera or bad frame geometry");
-	if (!xy_dev && n != (size_t)w * (size_t)h) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no list of pixels, and n is not w * h");
-	lol::LightQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.xy = xy_dev;
-	Q.flags = lol::SHADE_FROM_PIXELS | (xy_dev ? 0u : lol::LIGHT_ALL_PIXELS);
-	return launch_light(ctx, Q, cam, w, h, n, max_steps, out, stream);
 }
 
 /* What a look may not differ from the uploaded program in, or nullptr: the first difference, for the context's error */
@@ -2343,34 +2312,36 @@ static int relight_launch_fields(lol_gpu* ctx, const lol_program* look, hipStrea
 	return LOL_GPU_OK;
 }
 
-int lol_gpu_relight(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream) {
+/* What both resolves refuse, in two halves, because each call refuses its own count of elements between them: first the planes and
+ * the outputs ... */
+static int relit_refused(lol_gpu* ctx, const lol_gpu_light_passes* in, const lol_gpu_relit* out) {
 	if (!ctx) return LOL_GPU_ERR_ARG;
 	if (!in || !out) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no planes or no output");
 	if (!out->rgb_linear && !out->rgb && !out->pixel) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no output");
-	if (n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight: more than 2^32 - 1 elements");
+	return LOL_GPU_OK;
+}
+/* ... then, with the count n known to be sound: the program, the planes against n, the look */
+static int look_refused(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t n) {
 	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
-	LOL_TRY(passes_refused(ctx, in, n, "relight"));
+	LOL_TRY(passes_refused(ctx, in, n));
 	if (look) if (const char* why = look_differs(ctx->h_prog, *look)) return fail(ctx, LOL_GPU_ERR_ARG, why);
-	if (n == 0) return LOL_GPU_OK;
+	return LOL_GPU_OK;
+}
+
+/* Everything behind a resolve's filled query: the Launch under the look, the tables' LDS, a block per lol::BLOCK of `lanes`, the kernel
+ * for where the tables lie, and the look's ring set handed back */
+template <class Query>
+static int launch_resolve(lol_gpu* ctx, const lol_program* look, void* stream, Query& Q, unsigned long long lanes, const void* fn_lds, const void* fn_global) {
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
 	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
 	lol::Launch L;
 	RingSet* S;
 	LOL_TRY(relight_launch_fields(ctx, look, s, L, S));
 	const lol_program& P = ctx->h_prog;
-	lol::RelightQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
-	Q.stride = in->light_stride ? in->light_stride : n;
-	Q.hit_id = in->hit_id;
-	Q.n = (uint32_t)n;
-	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
-	const bool in_lds = lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots);
-	const unsigned lds = in_lds ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
-	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
+	const dim3 grid((unsigned)((lanes + lol::BLOCK - 1) / lol::BLOCK));
 	void* args[] = { &L, &Q };
-	const void* fn = in_lds ? reinterpret_cast<const void*>(&lol::relight_rays<false>) : reinterpret_cast<const void*>(&lol::relight_rays<true>);
-	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	const void* fn = lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots) ? fn_lds : fn_global;
+	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, tables_lds_bytes(P), s);
 	if (S) return ring_done(ctx, *S, s, e, "relight launch");
 	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "relight launch", e);
 	return LOL_GPU_OK;
@@ -2393,6 +2364,32 @@ static int views_shape_refused(lol_gpu* ctx, int n_views, int cams_per_view, int
 	return LOL_GPU_OK;
 }
 
+extern "C" {
+
+int lol_gpu_light_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_light_passes* out, void* stream) {
+	return light_query(ctx, rays_source("light passes", rays_dev, n, max_steps, stream), out);
+}
+
+int lol_gpu_light_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
+                         const uint32_t* xy_dev, size_t n, const lol_gpu_light_passes* out, void* stream) {
+	return light_query(ctx, pixels_source("light passes", cam, w, h, xy_dev, n, max_steps, stream, true), out);
+}
+
+int lol_gpu_relight(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream) {
+	LOL_TRY(relit_refused(ctx, in, out));
+	if (n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight: more than 2^32 - 1 elements");
+	LOL_TRY(look_refused(ctx, look, in, n));
+	if (n == 0) return LOL_GPU_OK;
+	lol::RelightQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
+	Q.stride = in->light_stride ? in->light_stride : n;
+	Q.hit_id = in->hit_id;
+	Q.n = (uint32_t)n;
+	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
+	return launch_resolve(ctx, look, stream, Q, Q.n, reinterpret_cast<const void*>(&lol::relight_rays<false>), reinterpret_cast<const void*>(&lol::relight_rays<true>));
+}
+
 int lol_gpu_light_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view, int w, int h, int samples,
                         int max_steps, const lol_gpu_light_passes* out, void* stream) {
 	if (!ctx) return LOL_GPU_ERR_ARG;
@@ -2401,7 +2398,9 @@ int lol_gpu_light_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views,
 	if (!cams) return fail(ctx, LOL_GPU_ERR_ARG, "light passes: no camera or bad frame geometry");
 	size_t N = 0;
 	LOL_TRY(views_shape_refused(ctx, n_views, cams_per_view, w, h, samples, &N));
-	LOL_TRY(light_refused(ctx, nullptr, false, N, max_steps, out));        /* no program; the planes, against all N elements */
+	QuerySource all = rays_source("light passes", nullptr, N, max_steps, stream);       /* no program; the planes, against all N elements */
+	all.list_optional = true;
+	LOL_TRY(source_refused(ctx, all, false, out));
 	/* the whole call has passed: record r is lol_gpu_light_pixels of the s w x s h frame under cams[r], r s^2 w h elements further on */
 	const size_t per = N / ((size_t)n_views * (size_t)cams_per_view);
 	const int records = n_views * cams_per_view;
@@ -2420,21 +2419,11 @@ int lol_gpu_light_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views,
 
 int lol_gpu_relight_views(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, int n_views, int cams_per_view,
                           int w, int h, int samples, const lol_gpu_relit* out, void* stream) {
-	if (!ctx) return LOL_GPU_ERR_ARG;
-	if (!in || !out) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no planes or no output");
-	if (!out->rgb_linear && !out->rgb && !out->pixel) return fail(ctx, LOL_GPU_ERR_ARG, "relight: no output");
+	LOL_TRY(relit_refused(ctx, in, out));
 	size_t N = 0;
 	LOL_TRY(views_shape_refused(ctx, n_views, cams_per_view, w, h, samples, &N));
 	if (cams_per_view == 1 && samples == 1) return lol_gpu_relight(ctx, look, in, N, out, stream);      /* a pixel is its one leaf */
-	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
-	LOL_TRY(passes_refused(ctx, in, N, "relight"));
-	if (look) if (const char* why = look_differs(ctx->h_prog, *look)) return fail(ctx, LOL_GPU_ERR_ARG, why);
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-	lol::Launch L;
-	RingSet* S;
-	LOL_TRY(relight_launch_fields(ctx, look, s, L, S));
-	const lol_program& P = ctx->h_prog;
+	LOL_TRY(look_refused(ctx, look, in, N));
 	lol::RelightViewsQuery Q;
 	memset(&Q, 0, sizeof Q);
 	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
@@ -2446,16 +2435,8 @@ int lol_gpu_relight_views(lol_gpu* ctx, const lol_program* look, const lol_gpu_l
 	Q.cams = (uint32_t)cams_per_view;
 	Q.last_view = (uint32_t)n_views - 1u;
 	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
-	const bool in_lds = lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots);
-	const unsigned lds = in_lds ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
 	/* a wave per 64 pixels, whatever s and K: it takes them in s^2 rounds of 64 / s^2 */
 	const unsigned long long lanes = ((unsigned long long)Q.n_pixels + 63u) / 64u * 64u;
-	const dim3 grid((unsigned)((lanes + lol::BLOCK - 1) / lol::BLOCK));
-	void* args[] = { &L, &Q };
-	const void* fn = in_lds ? reinterpret_cast<const void*>(&lol::relight_views<false>) : reinterpret_cast<const void*>(&lol::relight_views<true>);
-	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
-	if (S) return ring_done(ctx, *S, s, e, "relight launch");
-	if (e != hipSuccess) return fail(ctx, LOL_GPU_ERR_HIP, "relight launch", e);
-	return LOL_GPU_OK;
+	return launch_resolve(ctx, look, stream, Q, lanes, reinterpret_cast<const void*>(&lol::relight_views<false>), reinterpret_cast<const void*>(&lol::relight_views<true>));
 }
 }  // extern "C"

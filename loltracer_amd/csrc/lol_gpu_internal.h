@@ -3,8 +3,10 @@
  * the proven shortcuts (FastPaths), and the few functions that cross from one unit to another.  Nothing here is part of the
  * C ABI (include/lol_gpu.h); everything declared between the visibility pragmas stays inside the library.
  *
- *   lol_gpu.hip      the context and the C ABI around it: upload, frames (device and host surfaces, frames in flight), the
- *                    first march step, diagnostics
+ *   lol_gpu.hip      the context and the C ABI around it: upload, frames (device and host surfaces, frames in flight, adaptive
+ *                    frames), the first march step, the rings of per-call device sets, batches of views (plain, supersampled,
+ *                    blended) and of scene views, the interpreter's ladder, the SDF alone, the list queries (ray queries,
+ *                    shading queries, light passes) and the relight resolves, diagnostics
  *   lol_tiers.hip    the tiers of the scene compiler: its runs on their own threads, the kernels they load, the swaps at frame
  *                    boundaries, lol_gpu_specialize_*
  *   lol_proofs.hip   the exhaustive on-device proofs of the fast paths, the gamma table, lol_gpu_verify_*

@@ -25,8 +25,7 @@
 
 namespace lol {
 
-/* LightQuery::flags: SHADE_FROM_PIXELS and SHADE_SCENE_SANE of lol_kernel_shade.h, and */
-constexpr u32 LIGHT_ALL_PIXELS = 4u;    /* with SHADE_FROM_PIXELS: there is no list, ray i is pixel (i % w, i / w) of the Launch's frame */
+/* LightQuery::flags: SHADE_FROM_PIXELS, SHADE_SCENE_SANE and LIGHT_ALL_PIXELS of lol_kernel_shade.h */
 
 struct alignas(16) LightFactor { float shadow, di, si; u32 shadow_steps; };      /* = lol_gpu_light_factor */
 struct LightOut { LightFactor* factors; u32* hit_id; float* hit_dist; u32* march_steps; };
@@ -97,34 +96,16 @@ __device__ __forceinline__ Hit light_ray(const Launch& L, const LightQuery& Q, S
 	return hit;
 }
 
-/* Ray i of the capture (a lane beyond n: ray n - 1), as fetch_ray, with the all-pixels form beside the two lists */
-__device__ __forceinline__ void light_fetch_ray(const Launch& L, const LightQuery& Q, u32 i, V3& ro, V3& rd) {
-	u32 j = i < Q.n ? i : Q.n - 1u;
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm volatile("" : "+v"(j));
-#endif
-	if (Q.flags & SHADE_FROM_PIXELS) {
-		u32 x, y;
-		if (Q.flags & LIGHT_ALL_PIXELS) { y = j / (u32)L.w; x = j - y * (u32)L.w; }
-		else { x = Q.xy[2ull * j]; y = Q.xy[2ull * j + 1ull]; }
-		ro = v3(L.cam.origin);
-		rd = camera_ray(L.cam, L.fw, L.fh, (int)x, (int)y);
-	} else {
-		const float* r = Q.rays + 6ull * j;
-		ro = { r[0], r[1], r[2] };
-		rd = { r[3], r[4], r[5] };
-	}
-}
-
 /* The whole capture kernel, after the tables are staged: shade_rays with light_ray in the place of shade_ray — the same ballot
  * decides what a wave of a list may assume about its rays, the same second pass follows a fast SDF that left what was proven for it
- * (it stores every factor again: same lanes, same addresses, in order). */
+ * (it stores every factor again: same lanes, same addresses, in order).  A copy of shade_rays' driver and of its ballot, not a call:
+ * either fold moved all 16 light_interp (lol_kernel_shade.h, shade_rays, "Not folded"). */
 template <bool TABLES_GLOBAL, class SdfFast, class SdfExact>
 __device__ __forceinline__ void light_rays(SdfFast& fast, SdfExact& exact, bool have_fast, const Launch& L, const LightQuery& Q, const u32* lds) {
 	const u32 i = blockIdx.x * (u32)BLOCK + threadIdx.x;
 	const bool from_pixels = (Q.flags & SHADE_FROM_PIXELS) != 0u, store = i < Q.n;
 	V3 ro, rd;
-	light_fetch_ray(L, Q, i, ro, rd);
+	fetch_ray<true>(L, Q, i, ro, rd);
 	const bool first_given = (L.flags & FLAG_FIRST_STEP) != 0u;
 	bool sane = true;
 	if (!from_pixels) {
@@ -142,7 +123,7 @@ __device__ __forceinline__ void light_rays(SdfFast& fast, SdfExact& exact, bool 
 		plain = unproven(fast);
 	}
 	if (plain) {
-		light_fetch_ray(L, Q, i, ro, rd);
+		fetch_ray<true>(L, Q, i, ro, rd);
 		hit = light_ray<SdfExact, TABLES_GLOBAL>(L, Q, exact, lds, ro, rd, first_given, from_pixels && settled, i, store);
 	}
 	if (store) {

@@ -29,6 +29,7 @@ namespace lol {
 constexpr u32 SHADE_FROM_PIXELS = 1u;   /* the rays are the primary rays of the pixels in `xy` under Launch::cam; else the list `rays` */
 constexpr u32 SHADE_SCENE_SANE = 2u;    /* the host's side of what the fast SDF rests on holds: every number of the scene finite and below
                                          * 10^15 (lol_gpu.hip, shadow_settle_ok) and, for SHADE_FROM_PIXELS, of the camera too (camera_sane) */
+constexpr u32 LIGHT_ALL_PIXELS = 4u;    /* a capture's alone (lol_kernel_light.h), with SHADE_FROM_PIXELS: there is no list, ray i is pixel (i % w, i / w) of the Launch's frame */
 
 struct ShadeOut { float* rgb_linear; float* rgb; u32* pixel; float* hit_dist; u32* hit_id; u32* steps; };   /* each may be NULL; element i belongs to ray i */
 
@@ -121,14 +122,18 @@ __device__ __forceinline__ Pixel shade_ray(const Launch& L, Sdf& sdf, const u32*
 
 /* Ray i of the query (a lane beyond n: ray n - 1), read or built where a pipeline begins.  A wave that shades again through the exact
  * pipeline fetches its rays AGAIN, through an index the compiler cannot see through: kept live for that rare second pass, a
- * per-lane origin and direction are six VGPRs held through the whole first one, in a kernel compiled for 64. */
-__device__ __forceinline__ void fetch_ray(const Launch& L, const ShadeQuery& Q, u32 i, V3& ro, V3& rd) {
+ * per-lane origin and direction are six VGPRs held through the whole first one, in a kernel compiled for 64.  `Query`: a ShadeQuery or
+ * a capture's LightQuery (lol_kernel_light.h); ALL_PIXELS_FORM: the capture's, the only one that compiles the LIGHT_ALL_PIXELS branch. */
+template <bool ALL_PIXELS_FORM = false, class Query>
+__device__ __forceinline__ void fetch_ray(const Launch& L, const Query& Q, u32 i, V3& ro, V3& rd) {
 	u32 j = i < Q.n ? i : Q.n - 1u;
 #if defined(__HIP_DEVICE_COMPILE__)
 	asm volatile("" : "+v"(j));
 #endif
 	if (Q.flags & SHADE_FROM_PIXELS) {
-		const u32 x = Q.xy[2ull * j], y = Q.xy[2ull * j + 1ull];
+		u32 x, y;
+		if (ALL_PIXELS_FORM && (Q.flags & LIGHT_ALL_PIXELS)) { y = j / (u32)L.w; x = j - y * (u32)L.w; }
+		else { x = Q.xy[2ull * j]; y = Q.xy[2ull * j + 1ull]; }
 		ro = v3(L.cam.origin);
 		rd = camera_ray(L.cam, L.fw, L.fh, (int)x, (int)y);
 	} else {
@@ -153,6 +158,10 @@ __device__ __forceinline__ void fetch_ray(const Launch& L, const ShadeQuery& Q, 
  * SDF left what was proven for it (unproven).  The rays of SHADE_FROM_PIXELS are a frame's: the host's camera_sane is the whole
  * test, FLAG_SHADOW_SETTLED is the frame's, and a wave that shades again does so under the launch's flag, as render_interp's does —
  * so `steps` is lol_gpu_debug.steps of that pixel, shadow steps included.
+ *
+ * Not folded: the ballot below stands three times — here, in light_rays and, without the length, in trace_rays — because
+ * one forceinline helper for it left all 16 shade_interp and all 16 light_interp different (root kind 3: 4 bytes longer); and one
+ * driver for this function and light_rays, with the per-ray body as a functor, left all 16 light_interp different (same lengths).
  */
 template <bool TABLES_GLOBAL, class SdfFast, class SdfExact>
 __device__ __forceinline__ void shade_rays(SdfFast& fast, SdfExact& exact, bool have_fast, const Launch& L, const ShadeQuery& Q, const u32* lds) {

@@ -18,7 +18,7 @@ import shade_reference as SR
 from loltracer_amd import gpu
 from loltracer_amd import scene as S
 from loltracer_amd.__main__ import main as cli_main
-from test_gpu_shades import LOSSY, all_pixels, frame, shade_rays, stream_of
+from test_gpu_shades import LOSSY, all_pixels, frame, refusal, shade_rays, stream_of
 from test_light_reference import looks_of
 
 pytestmark = pytest.mark.gpu
@@ -371,14 +371,34 @@ def test_degenerate_scenes(torch_cuda, name, mode):
 
 
 # ------------------------------------------------------------------------------------------------------------------- 7. refusals
-def status(call):
-    with pytest.raises(gpu.GpuError) as e:
-        call()
-    return e.value.status
+# what lol_gpu_error() says after each refusal of test_refusals: the text is part of what a host sees
+REFUSAL_TEXT = {
+    "no program": "no scene program uploaded",
+    "no list": "light passes: no list",
+    "max_steps or n": "light passes: max_steps < 0 or more than 2^32 - 1 rays",
+    "geometry": "light passes: no camera or bad frame geometry",
+    "not all pixels": "light passes: no list of pixels, and n is not w * h",
+    "no hit_id": "light passes: no hit_id plane",
+    "no factors": "light passes: no factors, and the program has lights",
+    "misaligned": "light passes: factors must be 16-byte aligned",
+    "stride": "light passes: light_stride is neither 0 nor at least n",
+    "relight: no output": "relight: no output",
+    "relight: n": "relight: more than 2^32 - 1 elements",
+}
+# ... and after each look of forbidden_looks, by its name there
+LOOK_TEXT = {
+    "f[]": "relight: the look differs from the uploaded program in an op (opcode, id or a number): capture again",
+    "light point": "relight: the look moves a light: capture again",
+    "shininess": "relight: the look changes a shininess: capture again",
+    "root_material": "relight: the look gives an object another material: capture again",
+    "a count": "relight: the look differs from the uploaded program in a count (ops, lights, materials, roots, max_stack)",
+    "NULL materials": "relight: malformed look: a table is missing",
+    "root_material out of range": "relight: material index out of range in the look",
+}
 
 
 def test_refusals(torch_cuda, scenes):
-    """every line of the header's list, with nothing written"""
+    """every line of the header's list, with nothing written; the status, the text of lol_gpu_error() and the ORDER of the refusals"""
     sc = scenes["scene4"]
     rays = ray_list(sc)[:64]
     d_rays = torch_cuda.from_numpy(np.ascontiguousarray(rays).copy()).to("cuda:0")
@@ -387,6 +407,7 @@ def test_refusals(torch_cuda, scenes):
     a, ra, ca = p.args(), p.relight_args(), c.args()
     lib = gpu.gpu_lib()
     fc = sc.frame_camera(8, 8)
+    T = REFUSAL_TEXT
     torch_cuda.cuda.synchronize()
 
     def passes(**kw):
@@ -396,10 +417,15 @@ def test_refusals(torch_cuda, scenes):
     relit = gpu.Relit(*(ca[f + "_ptr"] for f in RELIT))
     empty = gpu.Renderer(0)
     try:
-        assert status(lambda: empty.light_rays_into(d_rays.data_ptr(), 64, **a)) == -4
-        assert status(lambda: empty.light_rays_into(d_rays.data_ptr(), 64, -1, **a)) == -3               # a bad argument first
+        assert refusal(lambda: empty.light_rays_into(d_rays.data_ptr(), 64, **a)) == (-4, T["no program"])
+        assert refusal(lambda: empty.light_rays_into(d_rays.data_ptr(), 64, -1, **a)) == (-3, T["max_steps or n"])        # a bad argument first
         assert lib.lol_gpu_light_pixels(empty._ctx, fc, 8, 8, 256, None, 64, passes(), None) == -4
         assert lib.lol_gpu_relight(empty._ctx, None, passes(), 64, relit, None) == -4
+        # the order, without a program: a list of pixels asks for the program BEFORE the camera and the frame's geometry
+        assert lib.lol_gpu_light_pixels(empty._ctx, fc, 0, 8, 256, d_xy.data_ptr(), 64, passes(), None) == -4
+        assert lib.lol_gpu_light_pixels(empty._ctx, None, 8, 8, 256, d_xy.data_ptr(), 64, passes(), None) == -4
+        assert lib.lol_gpu_light_pixels(empty._ctx, fc, 8, 8, -1, d_xy.data_ptr(), 64, passes(), None) == -3
+        assert lib.lol_gpu_light_rays(empty._ctx, d_rays.data_ptr(), 64, -1, passes(), None) == -3
     finally:
         empty.close()
     r = open_renderer(sc, 1)
@@ -407,26 +433,27 @@ def test_refusals(torch_cuda, scenes):
         assert lib.lol_gpu_light_rays(None, d_rays.data_ptr(), 64, 256, passes(), None) == -3            # no context
         assert lib.lol_gpu_light_pixels(None, fc, 8, 8, 256, None, 64, passes(), None) == -3
         assert lib.lol_gpu_relight(None, None, passes(), 64, relit, None) == -3
-        assert status(lambda: r.light_rays_into(0, 64, **a)) == -3                                       # no rays
+        assert refusal(lambda: r.light_rays_into(0, 64, **a)) == (-3, T["no list"])                                       # no rays
         assert lib.lol_gpu_light_rays(r._ctx, d_rays.data_ptr(), 64, 256, None, None) == -3              # no lol_gpu_light_passes
         assert lib.lol_gpu_relight(r._ctx, None, None, 64, relit, None) == -3
         assert lib.lol_gpu_relight(r._ctx, None, passes(), 64, None, None) == -3                         # no lol_gpu_relit
-        assert status(lambda: r.light_rays_into(d_rays.data_ptr(), 64, **dict(a, id_ptr=0))) == -3       # no hit_id
-        assert status(lambda: r.relight_into(None, 64, **dict(ra, id_ptr=0), **ca)) == -3
-        assert status(lambda: r.light_rays_into(d_rays.data_ptr(), 64, **dict(a, factors_ptr=0))) == -3  # no factors, two lights
-        assert status(lambda: r.relight_into(None, 64, **dict(ra, factors_ptr=0), **ca)) == -3
-        assert status(lambda: r.light_rays_into(d_rays.data_ptr(), 64, **dict(a, factors_ptr=a["factors_ptr"] + 4))) == -3   # misaligned
-        assert status(lambda: r.light_rays_into(d_rays.data_ptr(), 64, **dict(a, light_stride=63))) == -3
-        assert status(lambda: r.relight_into(None, 64, **dict(ra, light_stride=63), **ca)) == -3
-        assert status(lambda: r.relight_into(None, 64, **ra)) == -3                                      # all three outputs NULL
-        assert status(lambda: r.light_rays_into(d_rays.data_ptr(), 64, -1, **a)) == -3                   # max_steps < 0
-        assert status(lambda: r.light_rays_into(d_rays.data_ptr(), 1 << 32, **a)) == -3                  # n > 2^32 - 1
-        assert status(lambda: r.relight_into(None, 1 << 32, **ra, **ca)) == -3
-        assert status(lambda: r.light_pixels_into(64, 0, 8, frame_camera=fc, xy_ptr=d_xy.data_ptr(), **a)) == -3
-        assert status(lambda: r.light_pixels_into(64, 8, 0, frame_camera=fc, xy_ptr=d_xy.data_ptr(), **a)) == -3
-        assert status(lambda: r.light_pixels_into(64, 8, 8, -1, xy_ptr=d_xy.data_ptr(), **a)) == -3
+        assert refusal(lambda: r.light_rays_into(d_rays.data_ptr(), 64, **dict(a, id_ptr=0))) == (-3, T["no hit_id"])     # no hit_id
+        assert refusal(lambda: r.relight_into(None, 64, **dict(ra, id_ptr=0), **ca)) == (-3, T["no hit_id"])
+        assert refusal(lambda: r.light_rays_into(d_rays.data_ptr(), 64, **dict(a, factors_ptr=0))) == (-3, T["no factors"])       # no factors, two lights
+        assert refusal(lambda: r.relight_into(None, 64, **dict(ra, factors_ptr=0), **ca)) == (-3, T["no factors"])
+        assert refusal(lambda: r.light_rays_into(d_rays.data_ptr(), 64, **dict(a, factors_ptr=a["factors_ptr"] + 4))) == (-3, T["misaligned"])
+        assert refusal(lambda: r.light_rays_into(d_rays.data_ptr(), 64, **dict(a, light_stride=63))) == (-3, T["stride"])
+        assert refusal(lambda: r.relight_into(None, 64, **dict(ra, light_stride=63), **ca)) == (-3, T["stride"])
+        assert refusal(lambda: r.relight_into(None, 64, **ra)) == (-3, T["relight: no output"])                           # all three outputs NULL
+        assert refusal(lambda: r.light_rays_into(d_rays.data_ptr(), 64, -1, **a)) == (-3, T["max_steps or n"])            # max_steps < 0
+        assert refusal(lambda: r.light_rays_into(d_rays.data_ptr(), 1 << 32, **a)) == (-3, T["max_steps or n"])           # n > 2^32 - 1
+        assert refusal(lambda: r.relight_into(None, 1 << 32, **ra, **ca)) == (-3, T["relight: n"])
+        assert refusal(lambda: r.light_pixels_into(64, 0, 8, frame_camera=fc, xy_ptr=d_xy.data_ptr(), **a)) == (-3, T["geometry"])
+        assert refusal(lambda: r.light_pixels_into(64, 8, 0, frame_camera=fc, xy_ptr=d_xy.data_ptr(), **a)) == (-3, T["geometry"])
+        assert refusal(lambda: r.light_pixels_into(64, 8, 8, -1, xy_ptr=d_xy.data_ptr(), **a)) == (-3, T["max_steps or n"])
         assert lib.lol_gpu_light_pixels(r._ctx, None, 8, 8, 256, d_xy.data_ptr(), 64, passes(), None) == -3      # no camera
-        assert status(lambda: r.light_pixels_into(63, 8, 8, **a)) == -3                                  # no list, and n != w h
+        assert lib.lol_gpu_light_pixels(r._ctx, None, 8, 8, 256, d_xy.data_ptr(), 0, passes(), None) == -3       # ... with n = 0 too
+        assert refusal(lambda: r.light_pixels_into(63, 8, 8, **a)) == (-3, T["not all pixels"])                           # no list, and n != w h
         # n = 0: fine, with no list at all, and nothing launched
         r.light_rays_into(0, 0, **a)
         r.light_pixels_into(0, 8, 8, xy_ptr=d_xy.data_ptr(), **a)
@@ -488,7 +515,7 @@ def test_forbidden_looks_and_the_frame_after(torch_cuda, scenes, mode):
         c = Colours(torch_cuda, p.n)
         for what, prog in forbidden_looks(sc):
             try:
-                assert status(lambda: r.relight_into(prog, p.n, **p.relight_args(), **c.args())) == -3, what
+                assert refusal(lambda: r.relight_into(prog, p.n, **p.relight_args(), **c.args())) == (-3, LOOK_TEXT[what]), what
             finally:
                 restore(what, prog)
             r.sync()

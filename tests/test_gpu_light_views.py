@@ -21,8 +21,8 @@ import test_gpu_views as V
 from loltracer_amd import gpu
 from loltracer_amd import scene as S
 from loltracer_amd.__main__ import main as cli_main
-from test_gpu_light import (FACTORS, RELIT, SENTINEL, Colours, Planes, assert_same, capture_pixels, forbidden_looks, open_renderer,
-                            relight, restore, scene_with_lights, status)
+from test_gpu_light import (FACTORS, LOOK_TEXT, RELIT, SENTINEL, Colours, Planes, assert_same, capture_pixels, forbidden_looks,
+                            open_renderer, refusal, relight, restore, scene_with_lights)
 from test_gpu_shades import LOSSY, frame, stream_of
 from test_light_reference import looks_of
 
@@ -295,6 +295,7 @@ def test_refusals(torch_cuda, scenes):
         assert light(empty._ctx) == -4 and resolve(empty._ctx) == -4                       # no program uploaded
         assert resolve(empty._ctx, k=1, s=1) == -4                                         # ... through the forwarded call too
         assert light(empty._ctx, k=3) == -3 and resolve(empty._ctx, s=3) == -3             # a bad argument first
+        assert light(empty._ctx, k=2) == -4                                                # ... and K and s before the program
     finally:
         empty.close()
     r = open_renderer(sc, 1)
@@ -320,13 +321,13 @@ def test_refusals(torch_cuda, scenes):
         assert light(r._ctx, out=False) == -3                                              # no lol_gpu_light_passes
         assert resolve(r._ctx, planes=False) == -3 and resolve(r._ctx, out=None) == -3
         assert resolve(r._ctx, out=gpu.Relit(None, None, None)) == -3                      # all three outputs NULL
-        assert status(lambda: r.relight_views_into(None, n_views, k, w, h, s, **ra)) == -3
-        assert status(lambda: r.light_views_into(cams + cams[:1], 3, w, h, s, **a)) == -3
+        assert refusal(lambda: r.relight_views_into(None, n_views, k, w, h, s, **ra)) == (-3, "relight: no output")
+        assert refusal(lambda: r.light_views_into(cams + cams[:1], 3, w, h, s, **a)) == (-3, "relit views: cams_per_view must be 1, 2, 4, 8 or 16")
         with pytest.raises(ValueError):
             r.light_views_into(cams[:1], 2, w, h, s, **a)                                  # not a whole number of views
         for what, prog in forbidden_looks(sc):                                             # what a look may not differ in
             try:
-                assert status(lambda: r.relight_views_into(prog, n_views, k, w, h, s, **ra, **ca)) == -3, what
+                assert refusal(lambda: r.relight_views_into(prog, n_views, k, w, h, s, **ra, **ca)) == (-3, LOOK_TEXT[what]), what
             finally:
                 restore(what, prog)
         r.sync()

@@ -16,6 +16,7 @@ from loltracer_amd import gpu
 from test_gpu_families import FORMS, INTERP
 from test_gpu_hostile import tie_cameras
 from test_gpu_parity import gpu_render
+from test_gpu_shades import refusal
 
 pytestmark = pytest.mark.gpu
 
@@ -204,8 +205,9 @@ def test_max_steps(torch_cuda, scenes, name, mode):
 def test_rungs_and_forms(torch_cuda, t):
     """one shape per rung of the interpreter's ladder, with and without the fast paths, and one per form of the scene compiler: 130
     rays of kinds (a) - (c).  The library says which kernel ran, and that is held to what the case was written for."""
+    assert {u.shape.rung[0] for u in INTERP} == {1, 3, 7, 11, 63}      # trace_interp's five stack classes (it reads no tables) all have a case
     sc = C.scene_of(t.shape)
-    rays = np.resize(R.ray_set(sc, SEED, "abc"), (130, 6))           # (a sparse scene has few hits to start (b) and (c) from: its rays repeat)
+    rays = np.resize(R.ray_set(sc, SEED, "abc"), (130, 6))          # (a sparse scene has few hits to start (b) and (c) from: its rays repeat)
     want = R.reference(sc, rays)
     r = gpu.Renderer(0, specialize=t.specialize)
     try:
@@ -387,49 +389,64 @@ def test_a_frame_after_a_query_is_the_frame_it_would_have_been(torch_cuda, scene
         r.close()
 
 
+# what lol_gpu_error() says after each refusal of test_refusals: the text is part of what a host sees
+REFUSAL_TEXT = {
+    "no program": "no scene program uploaded",
+    "no list": "ray query: no list",
+    "no output": "ray query: no output",
+    "max_steps or n": "ray query: max_steps < 0 or more than 2^32 - 1 rays",
+    "geometry": "ray query: no camera or bad frame geometry",
+    "pick outside": "pick: the pixel lies outside the frame",
+    "pick geometry": "pick: no camera, no output or bad frame geometry",
+}
+
+
 def test_refusals(torch_cuda, scenes):
-    """what the header says, with nothing written"""
+    """what the header says, with nothing written; the status, the text of lol_gpu_error() and the ORDER of the refusals"""
     sc = scenes["scene4"]
     rays = R.ray_set(sc, SEED)[:64]
     d_rays = torch_cuda.from_numpy(np.ascontiguousarray(rays).copy()).to("cuda:0")
     d_xy = torch_cuda.zeros(128, dtype=torch_cuda.int32, device="cuda:0")
     out = Outputs(torch_cuda, 64)
     lib = gpu.gpu_lib()
+    T = REFUSAL_TEXT
     torch_cuda.cuda.synchronize()
-
-    def status(call):
-        with pytest.raises(gpu.GpuError) as e:
-            call()
-        return e.value.status
 
     empty = gpu.Renderer(0)
     try:
-        assert status(lambda: empty.trace_rays_into(d_rays.data_ptr(), 64, **out.ptrs())) == -4
-        assert status(lambda: empty.trace_rays_into(d_rays.data_ptr(), 64, -1, **out.ptrs())) == -3      # a bad argument first
+        assert refusal(lambda: empty.trace_rays_into(d_rays.data_ptr(), 64, **out.ptrs())) == (-4, T["no program"])
+        assert refusal(lambda: empty.trace_rays_into(d_rays.data_ptr(), 64, -1, **out.ptrs())) == (-3, T["max_steps or n"])      # a bad argument first
         fc = sc.frame_camera(8, 8)
         hits = gpu.Hits(*(out.ptrs()[f + "_ptr"] for f in FIELDS))
         assert lib.lol_gpu_trace_pixels(empty._ctx, fc, 8, 8, 256, d_xy.data_ptr(), 64, hits, None) == -4
         hit = gpu.Hit()
         assert lib.lol_gpu_pick(empty._ctx, fc, 8, 8, 256, 0, 0, hit) == -4
+        # the order, without a program: a list of pixels asks for the program BEFORE the camera and the frame's geometry, a pick after
+        assert lib.lol_gpu_trace_pixels(empty._ctx, fc, 0, 8, 256, d_xy.data_ptr(), 64, hits, None) == -4
+        assert lib.lol_gpu_trace_pixels(empty._ctx, None, 8, 8, 256, d_xy.data_ptr(), 64, hits, None) == -4
+        assert lib.lol_gpu_trace_pixels(empty._ctx, fc, 8, 8, -1, d_xy.data_ptr(), 64, hits, None) == -3
+        assert lib.lol_gpu_trace_rays(empty._ctx, d_rays.data_ptr(), 64, -1, hits, None) == -3
+        assert lib.lol_gpu_pick(empty._ctx, fc, 0, 8, 256, 0, 0, hit) == -3
     finally:
         empty.close()
     r = open_renderer(sc, 1)
     try:
         fc = sc.frame_camera(8, 8)
         hits = gpu.Hits(*(out.ptrs()[f + "_ptr"] for f in FIELDS))
-        assert status(lambda: r.trace_rays_into(0, 64, **out.ptrs())) == -3                              # no rays
-        assert status(lambda: r.trace_rays_into(d_rays.data_ptr(), 64)) == -3                            # all four outputs NULL
+        assert refusal(lambda: r.trace_rays_into(0, 64, **out.ptrs())) == (-3, T["no list"])                              # no rays
+        assert refusal(lambda: r.trace_rays_into(d_rays.data_ptr(), 64)) == (-3, T["no output"])                          # all four outputs NULL
         assert lib.lol_gpu_trace_rays(r._ctx, d_rays.data_ptr(), 64, 256, None, None) == -3              # no lol_gpu_hits
-        assert status(lambda: r.trace_rays_into(d_rays.data_ptr(), 64, -1, **out.ptrs())) == -3          # max_steps < 0
-        assert status(lambda: r.trace_rays_into(d_rays.data_ptr(), 1 << 32, **out.ptrs())) == -3         # n > 2^32 - 1
-        assert status(lambda: r.trace_pixels_into(0, 64, 8, 8, **out.ptrs())) == -3
-        assert status(lambda: r.trace_pixels_into(d_xy.data_ptr(), 64, 0, 8, frame_camera=fc, **out.ptrs())) == -3
-        assert status(lambda: r.trace_pixels_into(d_xy.data_ptr(), 64, 8, 0, frame_camera=fc, **out.ptrs())) == -3
-        assert status(lambda: r.trace_pixels_into(d_xy.data_ptr(), 64, 8, 8, -1, **out.ptrs())) == -3
+        assert refusal(lambda: r.trace_rays_into(d_rays.data_ptr(), 64, -1, **out.ptrs())) == (-3, T["max_steps or n"])   # max_steps < 0
+        assert refusal(lambda: r.trace_rays_into(d_rays.data_ptr(), 1 << 32, **out.ptrs())) == (-3, T["max_steps or n"])  # n > 2^32 - 1
+        assert refusal(lambda: r.trace_pixels_into(0, 64, 8, 8, **out.ptrs())) == (-3, T["no list"])
+        assert refusal(lambda: r.trace_pixels_into(d_xy.data_ptr(), 64, 0, 8, frame_camera=fc, **out.ptrs())) == (-3, T["geometry"])
+        assert refusal(lambda: r.trace_pixels_into(d_xy.data_ptr(), 64, 8, 0, frame_camera=fc, **out.ptrs())) == (-3, T["geometry"])
+        assert refusal(lambda: r.trace_pixels_into(d_xy.data_ptr(), 64, 8, 8, -1, **out.ptrs())) == (-3, T["max_steps or n"])
         assert lib.lol_gpu_trace_pixels(r._ctx, None, 8, 8, 256, d_xy.data_ptr(), 64, hits, None) == -3  # no camera
+        assert lib.lol_gpu_trace_pixels(r._ctx, None, 8, 8, 256, d_xy.data_ptr(), 0, hits, None) == -3   # ... with n = 0 too
         for x, y in ((-1, 0), (0, -1), (8, 0), (0, 8)):
-            assert status(lambda: r.pick(x, y, 8, 8)) == -3
-        assert status(lambda: r.pick(0, 0, 8, 8, max_steps=-1)) == -3
+            assert refusal(lambda: r.pick(x, y, 8, 8)) == (-3, T["pick outside"])
+        assert refusal(lambda: r.pick(0, 0, 8, 8, max_steps=-1)) == (-3, T["pick geometry"])
         assert lib.lol_gpu_pick(r._ctx, fc, 8, 8, 256, 0, 0, None) == -3
         # n = 0: fine, with no list at all, and nothing launched
         r.trace_rays_into(0, 0, **out.ptrs())

@@ -134,6 +134,44 @@ def test_points_where_the_fast_root_has_no_proof(scenes, mode):
     r.close()
 
 
+@pytest.mark.parametrize("mode", [4, 0], ids=["interp", "interp-plain"])
+@pytest.mark.parametrize("name", ["scene", "scene4", "tree5", "tree9", "tree12"])
+def test_every_stack_class_of_the_interpreter(name, mode):
+    """lol_gpu_sdf_batch on each of the interpreter's five operand-stack classes — 1, 3, 7, 11, 63: one shape of tests/scene_shapes.py
+    each, and the library says which class ran — at 64 points: 60 round the scene and four that no object is near or that are not
+    numbers.  Distances and ids are the oracle's, bit for bit."""
+    import ctypes as C
+    import torch
+    import scene_shapes as SH
+    shape = SH.RUNG[name]
+    sc = SH.scene_of(shape)
+    rng = np.random.default_rng(20261020)
+    pts = np.concatenate([rng.normal((0, 1, -6), 3.0, (60, 3)).astype(np.float32),
+                          np.array([[1e20, 0, 0], [0, -3e38, 0], [np.inf, 1, 1], [np.nan, 0, 0]], dtype=np.float32)])
+    l = O.lib()
+    want_d = np.zeros(len(pts), dtype=np.float32)
+    want_id = np.zeros(len(pts), dtype=np.int32)
+    for i, p in enumerate(pts):
+        oid = C.c_uint32()
+        want_d[i] = l.lol_oracle_sdf(sc.ptr, float(p[0]), float(p[1]), float(p[2]), C.byref(oid))
+        want_id[i] = oid.value
+    r = gpu.Renderer(0, specialize=mode)
+    try:
+        r.prepare(sc)
+        assert r.kernel_name() == "render_interp" and r.interp_variant() == shape.rung == (shape.rung[0], False)
+        d_pts = torch.from_numpy(pts.copy()).cuda()
+        d_dist = torch.zeros(len(pts), dtype=torch.float32, device="cuda")
+        d_id = torch.full((len(pts),), 77, dtype=torch.int32, device="cuda")
+        r.sdf_batch(d_pts.data_ptr(), d_dist.data_ptr(), d_id.data_ptr(), len(pts), stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        got = d_dist.cpu().numpy()
+        both_nan = np.isnan(got) & np.isnan(want_d)
+        assert np.array_equal(got.view(np.uint32)[~both_nan], want_d.view(np.uint32)[~both_nan])
+        assert np.array_equal(d_id.cpu().numpy(), want_id)
+    finally:
+        r.close()
+
+
 @pytest.mark.gpu
 def test_shadow_ray_that_never_moves():
     """A shadow ray whose first sample lies EXACTLY on a surface: s = 0, 50 s / t = 0 / 0 = NaN, t stays 0, the reference's factor is

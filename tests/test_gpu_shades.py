@@ -408,47 +408,70 @@ def test_a_frame_after_a_query_is_the_frame_it_would_have_been(torch_cuda, scene
         r.close()
 
 
+def refusal(call):
+    """(status, text) of the GpuError that `call` raises: the text is what lol_gpu_error() returned, which GpuError puts behind the
+    status's name"""
+    with pytest.raises(gpu.GpuError) as e:
+        call()
+    st = e.value.status
+    head = f"lol_gpu: {gpu._STATUS.get(st, st)}: "
+    assert str(e.value).startswith(head), str(e.value)
+    return st, str(e.value)[len(head):]
+
+
+# what lol_gpu_error() says after each refusal of test_refusals: the text is part of what a host sees
+REFUSAL_TEXT = {
+    "no program": "no scene program uploaded",
+    "no list": "shading query: no list",
+    "no output": "shading query: no output",
+    "max_steps or n": "shading query: max_steps < 0 or more than 2^32 - 1 rays",
+    "geometry": "shading query: no camera or bad frame geometry",
+}
+
+
 def test_refusals(torch_cuda, scenes):
-    """what the header says, with nothing written"""
+    """what the header says, with nothing written; the status, the text of lol_gpu_error() and the ORDER of the refusals"""
     sc = scenes["scene4"]
     rays = SR.shade_ray_set(sc, SEED)[:64]
     d_rays = torch_cuda.from_numpy(np.ascontiguousarray(rays).copy()).to("cuda:0")
     d_xy = torch_cuda.zeros(128, dtype=torch_cuda.int32, device="cuda:0")
     out = Outputs(torch_cuda, 64)
     lib = gpu.gpu_lib()
+    T = REFUSAL_TEXT
     torch_cuda.cuda.synchronize()
-
-    def status(call):
-        with pytest.raises(gpu.GpuError) as e:
-            call()
-        return e.value.status
 
     def shades():
         return gpu.Shades(*(out.ptrs()[f + "_ptr"] for f in FIELDS))
 
     empty = gpu.Renderer(0)
     try:
-        assert status(lambda: empty.shade_rays_into(d_rays.data_ptr(), 64, **out.ptrs())) == -4
-        assert status(lambda: empty.shade_rays_into(d_rays.data_ptr(), 64, -1, **out.ptrs())) == -3      # a bad argument first
+        assert refusal(lambda: empty.shade_rays_into(d_rays.data_ptr(), 64, **out.ptrs())) == (-4, T["no program"])
+        assert refusal(lambda: empty.shade_rays_into(d_rays.data_ptr(), 64, -1, **out.ptrs())) == (-3, T["max_steps or n"])      # a bad argument first
         fc = sc.frame_camera(8, 8)
         assert lib.lol_gpu_shade_pixels(empty._ctx, fc, 8, 8, 256, d_xy.data_ptr(), 64, shades(), None) == -4
+        # the order, without a program: a list of pixels asks for the program BEFORE the camera and the frame's geometry
+        assert lib.lol_gpu_shade_pixels(empty._ctx, fc, 0, 8, 256, d_xy.data_ptr(), 64, shades(), None) == -4
+        assert lib.lol_gpu_shade_pixels(empty._ctx, None, 8, 8, 256, d_xy.data_ptr(), 64, shades(), None) == -4
+        assert lib.lol_gpu_shade_pixels(empty._ctx, fc, 8, 8, -1, d_xy.data_ptr(), 64, shades(), None) == -3
+        assert lib.lol_gpu_shade_rays(empty._ctx, d_rays.data_ptr(), 64, -1, shades(), None) == -3
     finally:
         empty.close()
     r = open_renderer(sc, 1)
     try:
         fc = sc.frame_camera(8, 8)
         assert lib.lol_gpu_shade_rays(None, d_rays.data_ptr(), 64, 256, shades(), None) == -3            # no context
-        assert status(lambda: r.shade_rays_into(0, 64, **out.ptrs())) == -3                              # no rays
-        assert status(lambda: r.shade_rays_into(d_rays.data_ptr(), 64)) == -3                            # all six outputs NULL
+        assert refusal(lambda: r.shade_rays_into(0, 64, **out.ptrs())) == (-3, T["no list"])                              # no rays
+        assert refusal(lambda: r.shade_rays_into(d_rays.data_ptr(), 64)) == (-3, T["no output"])                          # all six outputs NULL
         assert lib.lol_gpu_shade_rays(r._ctx, d_rays.data_ptr(), 64, 256, None, None) == -3              # no lol_gpu_shades
-        assert status(lambda: r.shade_rays_into(d_rays.data_ptr(), 64, -1, **out.ptrs())) == -3          # max_steps < 0
-        assert status(lambda: r.shade_rays_into(d_rays.data_ptr(), 1 << 32, **out.ptrs())) == -3         # n > 2^32 - 1
-        assert status(lambda: r.shade_pixels_into(0, 64, 8, 8, **out.ptrs())) == -3
-        assert status(lambda: r.shade_pixels_into(d_xy.data_ptr(), 64, 0, 8, frame_camera=fc, **out.ptrs())) == -3
-        assert status(lambda: r.shade_pixels_into(d_xy.data_ptr(), 64, 8, 0, frame_camera=fc, **out.ptrs())) == -3
-        assert status(lambda: r.shade_pixels_into(d_xy.data_ptr(), 64, 8, 8, -1, **out.ptrs())) == -3
-        assert status(lambda: r.shade_pixels_into(d_xy.data_ptr(), 64, 8, 8)) == -3
+        assert refusal(lambda: r.shade_rays_into(d_rays.data_ptr(), 64, -1, **out.ptrs())) == (-3, T["max_steps or n"])   # max_steps < 0
+        assert refusal(lambda: r.shade_rays_into(d_rays.data_ptr(), 1 << 32, **out.ptrs())) == (-3, T["max_steps or n"])  # n > 2^32 - 1
+        assert refusal(lambda: r.shade_pixels_into(0, 64, 8, 8, **out.ptrs())) == (-3, T["no list"])
+        assert refusal(lambda: r.shade_pixels_into(d_xy.data_ptr(), 64, 0, 8, frame_camera=fc, **out.ptrs())) == (-3, T["geometry"])
+        assert refusal(lambda: r.shade_pixels_into(d_xy.data_ptr(), 64, 8, 0, frame_camera=fc, **out.ptrs())) == (-3, T["geometry"])
+        assert refusal(lambda: r.shade_pixels_into(d_xy.data_ptr(), 64, 8, 8, -1, **out.ptrs())) == (-3, T["max_steps or n"])
+        assert refusal(lambda: r.shade_pixels_into(d_xy.data_ptr(), 64, 8, 8)) == (-3, T["no output"])
         assert lib.lol_gpu_shade_pixels(r._ctx, None, 8, 8, 256, d_xy.data_ptr(), 64, shades(), None) == -3      # no camera
+        assert lib.lol_gpu_shade_pixels(r._ctx, None, 8, 8, 256, d_xy.data_ptr(), 0, shades(), None) == -3       # ... with n = 0 too
         # n = 0: fine, with no list at all, and nothing launched
         r.shade_rays_into(0, 0, **out.ptrs())
         r.shade_pixels_into(0, 0, 8, 8, **out.ptrs())
