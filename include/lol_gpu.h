@@ -901,7 +901,7 @@ typedef struct lol_gpu_relit { float* rgb_linear; float* rgb; uint32_t* pixel; }
  * switch would change the code object of every module compiled with that switch: the interpreter captures, at the interpreter's
  * speed); capture in ONE launch over batches, blends or samples (lol_gpu_light_views, below, covers them with one capture launch
  * per camera, and lol_gpu_relight_views resolves them); per-record scenes; moving a light or changing a shininess (they change the
- * factors: capture again); lol_gpu_multi_* forms; planes in host memory; and the renderer.h protocol.
+ * factors: capture again, or update the planes — "Light updates", below); lol_gpu_multi_* forms; planes in host memory; and the renderer.h protocol.
  */
 int  lol_gpu_light_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_light_passes* out, void* stream);
 int  lol_gpu_light_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
@@ -957,6 +957,68 @@ int  lol_gpu_light_views(lol_gpu* ctx, const lol_frame_camera* cams /* HOST */, 
 int  lol_gpu_relight_views(lol_gpu* ctx, const lol_program* look /* HOST; NULL = the uploaded program */,
                            const lol_gpu_light_passes* in, int n_views, int cams_per_view, int w, int h, int samples,
                            const lol_gpu_relit* out, void* stream);
+
+/*
+ * Light updates: captured planes brought to a look that MOVES LIGHTS or changes a SHININESS, without the primary march.  Those two
+ * edits change the factors, so lol_gpu_relight refuses them ("capture again") — but a capture is the primary march of every ray,
+ * the four normal taps and a shadow march towards every light, and almost all of it is unchanged: the march's result is in the planes
+ * (hit_dist, hit_id), the hit point is p = ro + rd * dist on those bits, the normal is four SDF values at p, the factors of lights that
+ * stand where they stood are in their planes, and a shininess enters specular_incidence alone.
+ *
+ * Definition.  The context has uploaded program U; the planes (factors light-major, hit_id, hit_dist) hold a capture of some source —
+ * a list of rays, or pixels of a w x h frame under a camera — under U.  An update takes the SAME source, a HOST program `look` and two
+ * masks of lights (bit l = light l):
+ *   - `look` has U's geometry: equal counts, ops (opcode, id, every number) and root_material.  It may differ from U in any
+ *     lights[l].point, any materials[m].shininess, and in what a look of lol_gpu_relight may differ in;
+ *   - for every light l of march_lights, element i of plane l becomes the whole lol_gpu_light_factor a capture of ray i gives on a
+ *     context that uploaded `look`, with the same lol_gpu_set_exact_skips: shadow, diffuse_incidence, specular_incidence and
+ *     shadow_steps;
+ *   - for every light l of specular_lights that is not in march_lights, the 4 bytes of specular_incidence alone become that capture's;
+ *     the other 12 bytes of the element stay as they are.  For a light that did not move, where only a shininess changed: no shadow
+ *     march is made;
+ *   - the planes of lights in neither mask, hit_id, hit_dist and march_steps are not written.
+ * The arithmetic is the capture's with its march replaced by a read: dist = hit_dist[i], id = hit_id[i] (an id above n_roots is taken
+ * for 0), p = ro + rd * dist, the normal's four taps at p, the direction to the eye, and per chosen light the capture's own loop body
+ * on the look's tables.  Rays that escaped (dist = +inf), NaN, infinite and zero rays go through the same expressions.  So the updated
+ * planes are bit for bit a fresh capture under `look`, and lol_gpu_relight_held of them is the reference's pixel for the look's scene.
+ * shadow_steps counts the steps really marched: the reference's count after lol_gpu_set_exact_skips(ctx, 0); otherwise the settled
+ * shadow exit applies where it would on a context that uploaded the look (the look's light points are part of that test).
+ * ONE DIFFERENCE from a capture: for a ray LIST with the settled exit on, a wave of a capture can fall back to the plain, unsettled
+ * pass because of something its PRIMARY march met; an update has no primary march, and such a wave may keep the settled count in
+ * shadow_steps.  The three floats are equal in every case, and for pixel sources all 16 bytes are.
+ *
+ * One asynchronous launch (light_update_interp: the interpreter's, always) behind one small copy of the look's tables through the
+ * ring of 8 sets lol_gpu_relight uses; no host wait; nothing of the frames' state is read or written.  There is no max_steps: nothing
+ * marches from the eye.  n == 0, or both masks 0, launches nothing.
+ *
+ * Refused, with nothing queued — LOL_GPU_ERR_ARG: everything the capture of the same source refuses; a NULL look; hit_dist == NULL;
+ * a mask bit at or above n_lights (lights from the 64th on cannot be updated: capture again); a look that differs from U in a count,
+ * an op, a root_material or a missing table.  LOL_GPU_ERR_NO_PROGRAM: no program uploaded.
+ *
+ * Resolving updated planes.  lol_gpu_relight checks a look against the UPLOADED program, and updated planes hold another one.
+ * lol_gpu_relight_held and lol_gpu_relight_views_held are those resolves with that one check changed: `held` (HOST) says what the
+ * planes hold; it must have U's geometry as a look of an update must, and `look` (NULL = the uploaded program) must equal `held`
+ * in every light point and shininess as bits, and in everything else a look must equal U in.  held == NULL forwards to lol_gpu_relight
+ * / lol_gpu_relight_views, which keep every status, text and order they have.
+ *
+ * Averaged pictures need no capture path of their own: record r of lol_gpu_light_views is lol_gpu_light_pixels of the s w x s h grid
+ * under cams[r], r s^2 w h elements further on, so a host updates it with lol_gpu_light_update_pixels(ctx, look, &cams[r], s w, s h,
+ * NULL, s^2 w h, ...) on planes offset by as many elements (light_stride that of the whole), and resolves with
+ * lol_gpu_relight_views_held.
+ *
+ * Out of scope: a scene-module form of the update; *_views update calls; updates over per-record scenes; moving geometry;
+ * lol_gpu_multi_* forms; planes in host memory; the renderer.h protocol; lights beyond the 64th.
+ */
+int  lol_gpu_light_update_rays(lol_gpu* ctx, const lol_program* look /* HOST, not NULL */, const float* rays_dev, size_t n,
+                               uint64_t march_lights, uint64_t specular_lights, const lol_gpu_light_passes* planes, void* stream);
+int  lol_gpu_light_update_pixels(lol_gpu* ctx, const lol_program* look /* HOST, not NULL */, const lol_frame_camera* cam, int w, int h,
+                                 const uint32_t* xy_dev /* NULL: every pixel, n must be w*h */, size_t n,
+                                 uint64_t march_lights, uint64_t specular_lights, const lol_gpu_light_passes* planes, void* stream);
+int  lol_gpu_relight_held(lol_gpu* ctx, const lol_program* look /* HOST; NULL = the uploaded program */,
+                          const lol_program* held /* HOST; what the planes hold; NULL = the uploaded program */,
+                          const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream);
+int  lol_gpu_relight_views_held(lol_gpu* ctx, const lol_program* look, const lol_program* held, const lol_gpu_light_passes* in,
+                                int n_views, int cams_per_view, int w, int h, int samples, const lol_gpu_relit* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
                           [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]] [--orbit-shutter K]]
                           [--lens R (--focus D | --focus-at X,Y) --lens-samples K] [--pick X,Y] [--panorama WxH -o FILE.ppm]
                           [--tween B.lol --frames N [--tween-samples S] [--tween-shutter K] -o DIR]
-                          [--relight LOOK.lol [LOOK2.lol ...] [--samples S] [--lens R --focus D --lens-samples K] -o DIR]
+                          [--relight LOOK.lol [LOOK2.lol ...] [--samples S] [--lens R --focus D --lens-samples K] [--move-lights] -o DIR]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
@@ -28,7 +28,10 @@ the scene with other light intensities, material colours or ambient colour (scen
 is refused with its first difference.  The camera is SCENE's.  With --samples S, or --lens R --focus D --lens-samples K [--samples S],
 beside --relight the looks are AVERAGED frames: every sample under every lens camera is captured once (Renderer.light_views_into: one
 capture per camera) and each look is resolved in linear light before gamma (Renderer.relight_views_into) — the files LOOK.lol with
-the same flags and without --relight writes, byte for byte.  Not with --adaptive or --focus-at.
+the same flags and without --relight writes, byte for byte.  Not with --adaptive or --focus-at.  With --move-lights beside --relight
+the looks may also MOVE LIGHTS or change a shininess: each look is reached from the one before by scene.light_changes, one light update
+(Renderer.light_update_pixels_into: no primary march, a shadow march only towards lights that moved) and relight_into(held=look);
+the files are again what LOOK.lol alone writes, byte for byte.  Not with --samples, --lens, --adaptive or --focus-at.
 There is no CPU rendering path."""
 from __future__ import annotations
 
@@ -133,7 +136,7 @@ def relight_frames(sc, args, w, h) -> int:
         except S.SceneError as e:
             print(e.message, file=sys.stderr)
             return 1
-        why = S.geometry_difference(sc, look)
+        why = S.geometry_difference(sc, look, lighting=not args.move_lights)
         if why is not None:
             print(f"--relight {path}: not a look of {args.scene}: {why}", file=sys.stderr)
             return 1
@@ -149,32 +152,39 @@ def relight_frames(sc, args, w, h) -> int:
         frames = np.zeros((len(looks), h, w), dtype=np.uint32)
         d_factors = r.malloc(16 * n * nl) if nl else 0
         d_id, d_px = r.malloc(4 * n), r.malloc(4 * w * h)
+        d_dist = r.malloc(4 * n) if args.move_lights else 0       # an update reads the march's distance back
+        held = sc                                                 # what the planes hold: each look is reached from the one before
         try:
             t0 = time.perf_counter()
             if averaged:
                 r.light_views_into(cams, k, w, h, s, args.max_steps, factors_ptr=d_factors, id_ptr=d_id)
             else:
-                r.light_pixels_into(n, w, h, args.max_steps, factors_ptr=d_factors, id_ptr=d_id)
+                r.light_pixels_into(n, w, h, args.max_steps, factors_ptr=d_factors, id_ptr=d_id, dist_ptr=d_dist)
             r.sync()
             capture_ms = (time.perf_counter() - t0) * 1e3
             t0 = time.perf_counter()
             for i, look in enumerate(looks):
                 if averaged:
                     r.relight_views_into(look, 1, k, w, h, s, factors_ptr=d_factors, id_ptr=d_id, pixel_ptr=d_px)
+                elif args.move_lights:
+                    march, specular = S.light_changes(held, look)
+                    r.light_update_pixels_into(look, n, w, h, march, specular, factors_ptr=d_factors, id_ptr=d_id, dist_ptr=d_dist)
+                    r.relight_into(look, n, factors_ptr=d_factors, id_ptr=d_id, pixel_ptr=d_px, held=look)
+                    held = look
                 else:
                     r.relight_into(look, n, factors_ptr=d_factors, id_ptr=d_id, pixel_ptr=d_px)
                 r.sync()
                 r.memcpy_d2h(frames[i].ctypes.data, d_px, 4 * w * h)
             dt = (time.perf_counter() - t0) * 1e3
         finally:
-            for d in (d_factors, d_id, d_px):
+            for d in (d_factors, d_id, d_px, d_dist):
                 if d:
                     r.free(d)
     finally:
         r.close()
     shape = f", {s}x{s} samples per pixel" * (s > 1) + f", {k} lens cameras" * (k > 1)
     print(f"{len(looks)} look(s) of {w}x{h}{shape}: capture {capture_ms:.3f}ms, relights and copies {dt:.3f}ms  "
-          f"[light_interp, {'relight_views' if averaged else 'relight_rays'}]")
+          f"[light_interp, {'light_update_interp, ' * bool(args.move_lights)}{'relight_views' if averaged else 'relight_rays'}]")
     os.makedirs(args.out, exist_ok=True)
     for i in range(len(looks)):
         write_ppm(os.path.join(args.out, f"look_{i:04d}.ppm"), frames[i])
@@ -312,6 +322,9 @@ def main(argv=None) -> int:
     ap.add_argument("--relight", default=None, nargs="+", metavar="LOOK.lol",
                     help="with -o DIR: one capture of the frame's light passes, then one frame per look (same geometry, other light "
                          "intensities, material colours, ambient colour) without marching again")
+    ap.add_argument("--move-lights", action="store_true",
+                    help="with --relight: the looks may also move lights or change a shininess; each is reached from the one before by a "
+                         "light update, without the primary march (not with --samples, --lens, --adaptive or --focus-at)")
     args = ap.parse_args(argv)
     w, h = (int(v) for v in args.size.lower().split("x"))
     for name, text in (("--pick", args.pick), ("--focus-at", args.focus_at)):
@@ -331,6 +344,9 @@ def main(argv=None) -> int:
         return 1
     if (args.tween_shutter != 1 or args.tween_samples != 1) and not args.tween:
         print("--tween-shutter and --tween-samples go with --tween B.lol", file=sys.stderr)
+        return 1
+    if args.move_lights and (not args.relight or args.samples != 1 or args.lens or args.adaptive != -1 or args.focus_at):
+        print("--move-lights goes with --relight LOOK.lol ... -o DIR; not with --samples, --lens, --adaptive or --focus-at", file=sys.stderr)
         return 1
     if args.relight:
         if (args.tween or args.panorama or args.orbit or args.pick or args.focus_at or args.adaptive != -1 or args.frames != 1

@@ -2364,6 +2364,38 @@ static int views_shape_refused(lol_gpu* ctx, int n_views, int cams_per_view, int
 	return LOL_GPU_OK;
 }
 
+/* a resolve of n elements whose every refusal has passed */
+static int relight_launch(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream) {
+	if (n == 0) return LOL_GPU_OK;
+	lol::RelightQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
+	Q.stride = in->light_stride ? in->light_stride : n;
+	Q.hit_id = in->hit_id;
+	Q.n = (uint32_t)n;
+	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
+	return launch_resolve(ctx, look, stream, Q, Q.n, reinterpret_cast<const void*>(&lol::relight_rays<false>), reinterpret_cast<const void*>(&lol::relight_rays<true>));
+}
+
+/* ... and of averaged views over N leaves (not K = 1 with s = 1: that is relight_launch) */
+static int relight_views_launch(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t N, int n_views, int cams_per_view,
+                                int w, int h, int samples, const lol_gpu_relit* out, void* stream) {
+	lol::RelightViewsQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
+	Q.stride = in->light_stride ? in->light_stride : N;
+	Q.hit_id = in->hit_id;
+	Q.n_pixels = (uint32_t)((size_t)n_views * (size_t)w * (size_t)h);
+	Q.w = (uint32_t)w; Q.h = (uint32_t)h;
+	Q.s_log2 = samples == 4 ? 2u : samples == 2 ? 1u : 0u;
+	Q.cams = (uint32_t)cams_per_view;
+	Q.last_view = (uint32_t)n_views - 1u;
+	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
+	/* a wave per 64 pixels, whatever s and K: it takes them in s^2 rounds of 64 / s^2 */
+	const unsigned long long lanes = ((unsigned long long)Q.n_pixels + 63u) / 64u * 64u;
+	return launch_resolve(ctx, look, stream, Q, lanes, reinterpret_cast<const void*>(&lol::relight_views<false>), reinterpret_cast<const void*>(&lol::relight_views<true>));
+}
+
 extern "C" {
 
 int lol_gpu_light_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_light_passes* out, void* stream) {
@@ -2379,15 +2411,7 @@ int lol_gpu_relight(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_p
 	LOL_TRY(relit_refused(ctx, in, out));
 	if (n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight: more than 2^32 - 1 elements");
 	LOL_TRY(look_refused(ctx, look, in, n));
-	if (n == 0) return LOL_GPU_OK;
-	lol::RelightQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
-	Q.stride = in->light_stride ? in->light_stride : n;
-	Q.hit_id = in->hit_id;
-	Q.n = (uint32_t)n;
-	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
-	return launch_resolve(ctx, look, stream, Q, Q.n, reinterpret_cast<const void*>(&lol::relight_rays<false>), reinterpret_cast<const void*>(&lol::relight_rays<true>));
+	return relight_launch(ctx, look, in, n, out, stream);
 }
 
 int lol_gpu_light_views(lol_gpu* ctx, const lol_frame_camera* cams, int n_views, int cams_per_view, int w, int h, int samples,
@@ -2424,19 +2448,131 @@ int lol_gpu_relight_views(lol_gpu* ctx, const lol_program* look, const lol_gpu_l
 	LOL_TRY(views_shape_refused(ctx, n_views, cams_per_view, w, h, samples, &N));
 	if (cams_per_view == 1 && samples == 1) return lol_gpu_relight(ctx, look, in, N, out, stream);      /* a pixel is its one leaf */
 	LOL_TRY(look_refused(ctx, look, in, N));
-	lol::RelightViewsQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
-	Q.stride = in->light_stride ? in->light_stride : N;
-	Q.hit_id = in->hit_id;
-	Q.n_pixels = (uint32_t)((size_t)n_views * (size_t)w * (size_t)h);
-	Q.w = (uint32_t)w; Q.h = (uint32_t)h;
-	Q.s_log2 = samples == 4 ? 2u : samples == 2 ? 1u : 0u;
-	Q.cams = (uint32_t)cams_per_view;
-	Q.last_view = (uint32_t)n_views - 1u;
-	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
-	/* a wave per 64 pixels, whatever s and K: it takes them in s^2 rounds of 64 / s^2 */
-	const unsigned long long lanes = ((unsigned long long)Q.n_pixels + 63u) / 64u * 64u;
-	return launch_resolve(ctx, look, stream, Q, lanes, reinterpret_cast<const void*>(&lol::relight_views<false>), reinterpret_cast<const void*>(&lol::relight_views<true>));
+	return relight_views_launch(ctx, look, in, N, n_views, cams_per_view, w, h, samples, out, stream);
+}
+}  // extern "C"
+
+/*
+ * Light updates and the resolves of updated planes (include/lol_gpu.h, "Light updates"; the kernel: lol_kernel_light_update.h).  An
+ * update is a list query over the source its capture had (QuerySource, source_refused) and ONE launch of light_update_interp behind the
+ * copy of the look's tables through lol_gpu::looks (relight_launch_fields): the Launch's tables are the look's, its macro-op lists the
+ * context's.  What the settled shadow loop and the fast SDF rest on is decided as launch_scene_query decides it, from the LOOK
+ * (shadow_settle_ok: its light points are part of the test) — what a context that uploaded the look would have cached.  Nothing of the
+ * frames' state is read or written, the cached first step included: nothing marches from the eye.
+ */
+/* What `K` (a look of an update, or what planes are said to hold) may not differ from the uploaded program in: look_differs' tests
+ * without the two for light points and shininess, in its order and wording.  nullptr, or the first difference written to `text`. */
+static const char* geometry_differs(const lol_program& U, const lol_program& K, const char* who, const char* noun, char (&text)[160]) {
+	auto say = [&](const char* fmt) { snprintf(text, sizeof text, fmt, who, noun); return text; };
+	if (K.n_ops != U.n_ops || K.n_lights != U.n_lights || K.n_materials != U.n_materials || K.n_roots != U.n_roots || K.max_stack != U.max_stack)
+		return say("%s: the %s differs from the uploaded program in a count (ops, lights, materials, roots, max_stack)");
+	if ((K.n_ops && !K.ops) || (K.n_lights && !K.lights) || !K.materials || (K.n_roots && !K.root_material))
+		return say("%s: malformed %s: a table is missing");
+	for (uint32_t i = 0; i < K.n_ops; i++)
+		if (K.ops[i].op != U.ops[i].op || K.ops[i].id != U.ops[i].id || memcmp(K.ops[i].f, U.ops[i].f, sizeof K.ops[i].f) != 0)
+			return say("%s: the %s differs from the uploaded program in an op (opcode, id or a number): capture again");
+	for (uint32_t i = 0; i < K.n_roots; i++) {
+		if (K.root_material[i] >= K.n_materials) return say("%s: material index out of range in the %s");
+		if (K.root_material[i] != U.root_material[i]) return say("%s: the %s gives an object another material: capture again");
+	}
+	return nullptr;
+}
+
+static int light_update(lol_gpu* ctx, const lol_program* look, const QuerySource& src, uint64_t march_lights, uint64_t specular_lights,
+                        const lol_gpu_light_passes* planes) {
+	if (!ctx) return LOL_GPU_ERR_ARG;
+	if (!look) return fail(ctx, LOL_GPU_ERR_ARG, "light update: no look");
+	LOL_TRY(source_refused(ctx, src, !planes, planes));
+	if (!planes->hit_dist) return fail(ctx, LOL_GPU_ERR_ARG, "light update: no hit_dist plane");
+	const lol_program& P = ctx->h_prog;
+	const uint64_t masks = march_lights | specular_lights;
+	if (P.n_lights < 64u && (masks >> P.n_lights) != 0)
+		return fail(ctx, LOL_GPU_ERR_ARG, "light update: a mask names a light the program has not (lights from the 64th on: capture again)");
+	char text[160];
+	if (const char* why = geometry_differs(P, *look, "light update", "look", text)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	if (src.n == 0 || masks == 0) return LOL_GPU_OK;
+
+	lol::LightUpdateQuery Q = {};
+	Q.rays = src.rays;
+	Q.xy = src.xy;
+	Q.n = (uint32_t)src.n;
+	Q.march_lights = march_lights;
+	Q.specular_lights = specular_lights;
+	Q.stride = planes->light_stride ? planes->light_stride : src.n;
+	Q.factors = reinterpret_cast<lol::LightFactor*>(planes->factors);
+	Q.hit_id = planes->hit_id;
+	Q.hit_dist = planes->hit_dist;
+
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = src.stream ? static_cast<hipStream_t>(src.stream) : ctx->stream;
+	lol::Launch L;
+	RingSet* S = nullptr;
+	LOL_TRY(relight_launch_fields(ctx, look, s, L, S));       /* the context's lists, counts and gamma table; the look's tables, behind their copy */
+	L.flags &= ~(lol::FLAG_MISS_SKIP | lol::FLAG_DARK_SKIP);     /* every factor of every ray, as at a capture */
+	/* launch_scene_query's two decisions, with the look's answer in the place of the context's cached ones */
+	const bool finite = shadow_settle_ok(*look), sane = !src.pixels || camera_sane(*src.cam);
+	if (finite && sane) Q.flags |= lol::SHADE_SCENE_SANE;
+	if ((ctx->want_skips & 4u) && finite && sane) L.flags |= lol::FLAG_SHADOW_SETTLED;
+	if (src.pixels) {
+		Q.flags |= lol::SHADE_FROM_PIXELS | (src.xy ? 0u : lol::LIGHT_ALL_PIXELS);
+		memcpy(&L.cam, src.cam, sizeof L.cam);
+		L.fw = (float)src.w; L.fh = (float)src.h;
+		L.w = src.w; L.h = src.h;
+	}
+	const unsigned lds = tables_lds_bytes(P);
+	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
+	void* args[] = { &L, &Q };
+	const int kind = ctx->interp_sqrt_kind;
+	const hipError_t e = interp_dispatch(ctx, [&](auto v) {
+		constexpr int ssize = decltype(v)::ssize;
+		constexpr bool tables_global = decltype(v)::tables_global;
+		const void* k = kind == 3 ? reinterpret_cast<const void*>(&lol::light_update_interp<ssize, 3, tables_global>)
+		                          : reinterpret_cast<const void*>(&lol::light_update_interp<ssize, 0, tables_global>);
+		return hipLaunchKernel(k, grid, dim3(lol::BLOCK), args, lds, s);
+	});
+	return ring_done(ctx, *S, s, e, "light update launch");
+}
+
+/* look_refused for planes that hold `held`, not the uploaded program: `held` has the program's geometry, and the look equals `held`
+ * where a look must equal what was captured — light points and shininess included */
+static int held_look_refused(lol_gpu* ctx, const lol_program* look, const lol_program& held, const lol_gpu_light_passes* in, size_t n) {
+	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
+	LOL_TRY(passes_refused(ctx, in, n));
+	char text[160];
+	if (const char* why = geometry_differs(ctx->h_prog, held, "relight", "held program", text)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	if (const char* why = look_differs(held, look ? *look : ctx->h_prog)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	return LOL_GPU_OK;
+}
+
+extern "C" {
+
+int lol_gpu_light_update_rays(lol_gpu* ctx, const lol_program* look, const float* rays_dev, size_t n, uint64_t march_lights,
+                              uint64_t specular_lights, const lol_gpu_light_passes* planes, void* stream) {
+	return light_update(ctx, look, rays_source("light update", rays_dev, n, 0, stream), march_lights, specular_lights, planes);
+}
+
+int lol_gpu_light_update_pixels(lol_gpu* ctx, const lol_program* look, const lol_frame_camera* cam, int w, int h, const uint32_t* xy_dev,
+                                size_t n, uint64_t march_lights, uint64_t specular_lights, const lol_gpu_light_passes* planes, void* stream) {
+	return light_update(ctx, look, pixels_source("light update", cam, w, h, xy_dev, n, 0, stream, true), march_lights, specular_lights, planes);
+}
+
+int lol_gpu_relight_held(lol_gpu* ctx, const lol_program* look, const lol_program* held, const lol_gpu_light_passes* in, size_t n,
+                         const lol_gpu_relit* out, void* stream) {
+	if (!held) return lol_gpu_relight(ctx, look, in, n, out, stream);
+	LOL_TRY(relit_refused(ctx, in, out));
+	if (n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight: more than 2^32 - 1 elements");
+	LOL_TRY(held_look_refused(ctx, look, *held, in, n));
+	return relight_launch(ctx, look, in, n, out, stream);
+}
+
+int lol_gpu_relight_views_held(lol_gpu* ctx, const lol_program* look, const lol_program* held, const lol_gpu_light_passes* in, int n_views,
+                               int cams_per_view, int w, int h, int samples, const lol_gpu_relit* out, void* stream) {
+	if (!held) return lol_gpu_relight_views(ctx, look, in, n_views, cams_per_view, w, h, samples, out, stream);
+	LOL_TRY(relit_refused(ctx, in, out));
+	size_t N = 0;
+	LOL_TRY(views_shape_refused(ctx, n_views, cams_per_view, w, h, samples, &N));
+	LOL_TRY(held_look_refused(ctx, look, *held, in, N));
+	if (cams_per_view == 1 && samples == 1) return relight_launch(ctx, look, in, N, out, stream);       /* a pixel is its one leaf */
+	return relight_views_launch(ctx, look, in, N, n_views, cams_per_view, w, h, samples, out, stream);
 }
 }  // extern "C"

@@ -310,6 +310,17 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_light_views.restype = C.c_int
         lib.lol_gpu_relight_views.argtypes = [vp, P(S.Program), P(LightPasses), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(Relit), vp]
         lib.lol_gpu_relight_views.restype = C.c_int
+        # light updates (include/lol_gpu.h, "Light updates")
+        lib.lol_gpu_light_update_rays.argtypes = [vp, P(S.Program), vp, C.c_size_t, C.c_uint64, C.c_uint64, P(LightPasses), vp]
+        lib.lol_gpu_light_update_rays.restype = C.c_int
+        lib.lol_gpu_light_update_pixels.argtypes = [vp, P(S.Program), P(S.FrameCamera), C.c_int, C.c_int, vp, C.c_size_t, C.c_uint64,
+                                                    C.c_uint64, P(LightPasses), vp]
+        lib.lol_gpu_light_update_pixels.restype = C.c_int
+        lib.lol_gpu_relight_held.argtypes = [vp, P(S.Program), P(S.Program), P(LightPasses), C.c_size_t, P(Relit), vp]
+        lib.lol_gpu_relight_held.restype = C.c_int
+        lib.lol_gpu_relight_views_held.argtypes = [vp, P(S.Program), P(S.Program), P(LightPasses), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_int, P(Relit), vp]
+        lib.lol_gpu_relight_views_held.restype = C.c_int
         lib.lol_gpu_render_scene_views.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
                                                    C.c_size_t, C.c_size_t, P(Debug), vp]
         lib.lol_gpu_render_scene_views.restype = C.c_int
@@ -465,6 +476,7 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_render_scene_views", "lol_gpu_set_scene_views", "lol_gpu_scene_views",
     "lol_gpu_render_scene_views_samples", "lol_gpu_set_scene_view_samples", "lol_gpu_scene_view_samples",
     "lol_gpu_light_rays", "lol_gpu_light_pixels", "lol_gpu_relight", "lol_gpu_light_views", "lol_gpu_relight_views",
+    "lol_gpu_light_update_rays", "lol_gpu_light_update_pixels", "lol_gpu_relight_held", "lol_gpu_relight_views_held",
 ]
 
 DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
@@ -1145,17 +1157,47 @@ class Renderer:
                                                    C.byref(out), _stream_arg(stream)))
 
     def relight_into(self, look, n: int, factors_ptr: int = 0, id_ptr: int = 0, rgb_linear_ptr: int = 0, rgb_ptr: int = 0,
-                     pixel_ptr: int = 0, light_stride: int = 0, stream: int | None = None):
+                     pixel_ptr: int = 0, light_stride: int = 0, stream: int | None = None, held=None):
         """Asynchronously make n elements of captured light passes into colours under `look`: a scene.Scene (flattened here) or a
         ready scene.Program with the prepared scene's geometry (scene.same_geometry; scene.Scene.with_look gives such scenes), or
         None: the prepared scene itself.  Element i is the pixel shade_rays_into gives ray i on a renderer that prepared the look,
         bit for bit: rgb_linear / rgb: 3 n floats, pixel: n elements in this renderer's pixel format; 0 = not wanted (not all
-        three).  The look's tables are copied before the call returns."""
+        three).  The look's tables are copied before the call returns.  held (a Scene or a Program; None: the prepared scene): what
+        the planes hold after light_update_*_into brought them to another look — the look must then stand where `held` stands
+        (lol_gpu_relight_held)."""
         prog = None if look is None else look if isinstance(look, S.Program) else look.flatten()
         planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
+        if held is not None:
+            hp = held if isinstance(held, S.Program) else held.flatten()
+            self._check(self._lib.lol_gpu_relight_held(self._ctx, C.byref(prog) if prog is not None else None, C.byref(hp), C.byref(planes),
+                                                       n, C.byref(out), _stream_arg(stream)))
+            return
         self._check(self._lib.lol_gpu_relight(self._ctx, C.byref(prog) if prog is not None else None, C.byref(planes), n, C.byref(out),
                                               _stream_arg(stream)))
+
+    def light_update_rays_into(self, look, rays_ptr: int, n: int, march_lights: int = 0, specular_lights: int = 0, factors_ptr: int = 0,
+                               id_ptr: int = 0, dist_ptr: int = 0, light_stride: int = 0, stream: int | None = None):
+        """Asynchronously bring the planes of a capture of n rays (light_rays_into of the same rays: factors, id and dist, all
+        needed) to `look` — as relight_into takes it, but not None: the prepared scene's geometry with other light points or
+        shininesses (scene.Scene.with_lighting) — without the primary march (lol_gpu_light_update_rays).  Bit l of march_lights:
+        light l's whole factor is computed again; bit l of specular_lights (and not of march_lights): its specular incidence alone,
+        with no shadow march.  scene.light_changes gives both masks.  Resolve with relight_into(..., held=look)."""
+        prog = look if isinstance(look, S.Program) else look.flatten() if look is not None else None
+        planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, None)
+        self._check(self._lib.lol_gpu_light_update_rays(self._ctx, C.byref(prog) if prog is not None else None, C.c_void_p(rays_ptr), n,
+                                                        int(march_lights), int(specular_lights), C.byref(planes), _stream_arg(stream)))
+
+    def light_update_pixels_into(self, look, n: int, w: int, h: int, march_lights: int = 0, specular_lights: int = 0, xy_ptr: int = 0,
+                                 factors_ptr: int = 0, id_ptr: int = 0, dist_ptr: int = 0, light_stride: int = 0,
+                                 stream: int | None = None, camera: S.Camera | None = None, frame_camera: S.FrameCamera | None = None):
+        """light_update_rays_into for the planes of light_pixels_into: the same n, w, h, camera and xy_ptr (0: every pixel)."""
+        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        prog = look if isinstance(look, S.Program) else look.flatten() if look is not None else None
+        planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, None)
+        self._check(self._lib.lol_gpu_light_update_pixels(self._ctx, C.byref(prog) if prog is not None else None, C.byref(fc), w, h,
+                                                          C.c_void_p(xy_ptr) if xy_ptr else None, n, int(march_lights),
+                                                          int(specular_lights), C.byref(planes), _stream_arg(stream)))
 
     def light_views_into(self, cameras, cameras_per_view: int, w: int, h: int, samples: int = 1, max_steps: int = 256,
                          factors_ptr: int = 0, id_ptr: int = 0, dist_ptr: int = 0, steps_ptr: int = 0, light_stride: int = 0,
@@ -1186,13 +1228,27 @@ class Renderer:
         per camera the tree mean over its samples x samples leaves, then the tree mean over the cameras_per_view cameras, then gamma
         and this renderer's pixel format — the supersampled frame, the blend, or the supersampled blend of a renderer that prepared
         the look, bit for bit, in one copy and one launch.  rgb_linear / rgb: 3 floats per pixel, pixel: one element, dense over
-        [view, y, x]; 0 = not wanted (not all three)."""
+        [view, y, x]; 0 = not wanted (not all three).  Planes that a light update brought to another look: relight_views_held_into."""
         prog = None if look is None else look if isinstance(look, S.Program) else look.flatten()
         planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
         self._check(self._lib.lol_gpu_relight_views(self._ctx, C.byref(prog) if prog is not None else None, C.byref(planes),
                                                     int(n_views), int(cameras_per_view), w, h, int(samples), C.byref(out),
                                                     _stream_arg(stream)))
+
+    def relight_views_held_into(self, look, held, n_views: int, cameras_per_view: int, w: int, h: int, samples: int = 1,
+                                factors_ptr: int = 0, id_ptr: int = 0, rgb_linear_ptr: int = 0, rgb_ptr: int = 0, pixel_ptr: int = 0,
+                                light_stride: int = 0, stream: int | None = None):
+        """relight_views_into for planes that hold `held` (a Scene or a Program; None: the prepared scene, which is
+        relight_views_into itself) after light_update_pixels_into brought them there record by record: the look must stand where
+        `held` stands (lol_gpu_relight_views_held).  What relight_into's held= is to relight_into."""
+        prog = None if look is None else look if isinstance(look, S.Program) else look.flatten()
+        hp = None if held is None else held if isinstance(held, S.Program) else held.flatten()
+        planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
+        out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
+        self._check(self._lib.lol_gpu_relight_views_held(self._ctx, C.byref(prog) if prog is not None else None,
+                                                         C.byref(hp) if hp is not None else None, C.byref(planes), int(n_views),
+                                                         int(cameras_per_view), w, h, int(samples), C.byref(out), _stream_arg(stream)))
 
     def set_cull(self, enable: bool):
         """Exact bounding-sphere culling of top-level objects in the specialised kernel; takes effect at the next prepare()."""

@@ -206,6 +206,26 @@ class Scene:
         put(c.ambient_color, ambient)
         return out
 
+    def with_lighting(self, points=None, shininess=None) -> "Scene":
+        """A clone with other LIGHTING GEOMETRY: what a light update (Renderer.light_update_*_into) lets a look differ in beyond
+        with_look's numbers.  points: one entry per light, a 3-tuple or None (keep); shininess: one entry per material, a number or
+        None.  Either argument may be None.  The numbers are stored as floats whatever they are: NaN and infinities included."""
+        out = self.clone()
+        c = out.c
+        if points is not None:
+            if len(points) != c.n_lights:
+                raise ValueError("with_lighting: one entry per light")
+            for i, e in enumerate(points):
+                if e is not None:
+                    c.lights[i].point.x, c.lights[i].point.y, c.lights[i].point.z = (float(t) for t in e)
+        if shininess is not None:
+            if len(shininess) != c.n_materials:
+                raise ValueError("with_lighting: one entry per material")
+            for i, e in enumerate(shininess):
+                if e is not None:
+                    c.materials[i].shininess = float(e)
+        return out
+
     def tables(self) -> bytes:
         """Everything the scene says, as bytes: counts, ambient colour and camera, then nodes, roots, materials and lights."""
         c = self.c
@@ -288,12 +308,13 @@ def same_structure(a: "Scene", b: "Scene") -> bool:
     return True
 
 
-def geometry_difference(a, b):
+def geometry_difference(a, b, lighting=True):
     """The first thing in which b differs from a that a LOOK may not differ in, as a sentence, or None: what lol_gpu_relight checks
     of a look against the uploaded program (include/lol_gpu.h), in its order.  a, b: Scene objects (flattened here) or Programs.
     Equal must be, bit for bit: the counts of ops, lights, materials and roots and max_stack; every op's opcode, id and numbers;
     every light's point; every material's shininess (a NaN shininess equals itself); every root's material index.  Free are the
-    lights' intensities, the materials' three colours and the ambient colour."""
+    lights' intensities, the materials' three colours and the ambient colour.  lighting=False leaves the lights' points and the
+    shininesses free too: what a light update checks of its look (light_changes)."""
     pa = a if isinstance(a, Program) else a.flatten()
     pb = b if isinstance(b, Program) else b.flatten()
     for f in ("n_ops", "n_lights", "n_materials", "n_roots", "max_stack"):
@@ -305,10 +326,10 @@ def geometry_difference(a, b):
             return f"op {i} differs in opcode or id"
         if bytes(memoryview(x.f).cast("B")) != bytes(memoryview(y.f).cast("B")):
             return f"op {i} (object {x.id}) differs in a number: {list(x.f)} and {list(y.f)}"
-    for i in range(pa.n_lights):
+    for i in range(pa.n_lights if lighting else 0):
         if bytes(memoryview(pa.lights[i].point).cast("B")) != bytes(memoryview(pb.lights[i].point).cast("B")):
             return f"light {i} stands at {pa.lights[i].point.tuple()} and at {pb.lights[i].point.tuple()}"
-    for i in range(pa.n_materials):
+    for i in range(pa.n_materials if lighting else 0):
         if C.string_at(C.addressof(pa.materials[i]), 4) != C.string_at(C.addressof(pb.materials[i]), 4):
             return f"material {i} has shininess {pa.materials[i].shininess} and {pb.materials[i].shininess}"
     for i in range(pa.n_roots):
@@ -321,6 +342,26 @@ def same_geometry(a, b) -> bool:
     """Is b a LOOK of a — the scene with other light intensities, material colours or ambient colour, and nothing else changed?
     The predicate lol_gpu_relight's host check implements (geometry_difference says what differs)."""
     return geometry_difference(a, b) is None
+
+
+def light_changes(held, look):
+    """(march_mask, specular_mask) of the light update that brings planes holding `held` to `look` (Renderer.light_update_*_into;
+    Scene objects or Programs).  Bit l of the first mask: light l's point differs, as bits — its whole factor is computed again.  If
+    any material's shininess differs, as bits, every other light goes into the second mask: its specular incidence alone.  Anything
+    else of the geometry that differs raises ValueError with geometry_difference's sentence; lights from the 64th on cannot be
+    updated and raise too."""
+    pa = held if isinstance(held, Program) else held.flatten()
+    pb = look if isinstance(look, Program) else look.flatten()
+    why = geometry_difference(pa, pb, lighting=False)
+    if why is not None:
+        raise ValueError(why)
+    moved = [i for i in range(pa.n_lights)
+             if bytes(memoryview(pa.lights[i].point).cast("B")) != bytes(memoryview(pb.lights[i].point).cast("B"))]
+    shiny = any(C.string_at(C.addressof(pa.materials[i]), 4) != C.string_at(C.addressof(pb.materials[i]), 4) for i in range(pa.n_materials))
+    if (moved and moved[-1] >= 64) or (shiny and pa.n_lights > 64):
+        raise ValueError("lights from the 64th on cannot be updated: capture again")
+    march = sum(1 << i for i in moved)
+    return march, (((1 << pa.n_lights) - 1) & ~march) if shiny else 0
 
 
 def _lerp32(a, b, t):
