@@ -191,7 +191,11 @@ def cameras(sc):
 
 
 # ---- hostile scenes (tests/test_gpu_hostile.py): the inputs that strain what the exact shortcuts are decided from — the culling bounds
-# and the k-d plan, the carried bound, the division skip, the fast roots' range fall-back, the host's own first step — and exact ties
+# and the k-d plan, the carried bound, the division skip, the fast roots' range fall-back, the host's own first step — and exact ties.
+# Its users: tests/test_gpu_hostile.py (every kernel that renders frames), tests/reference_frames.py (the recorded frames of the
+# reference's own renderer), the pixel lists of the ties in tests/test_gpu_rays.py and test_gpu_shades.py, and — with lists of rays
+# made from each scene's culling bounds, tests/hostile_rays.py — tests/test_gpu_hostile_queries.py (ray and shading queries, light
+# passes, the resolves, light updates), whose inputs tests/test_hostile_rays.py holds on the CPU
 def stress_scene(rng):
     """Scenes that lean on the culling bounds: many top-level objects of very different sizes and distances, smoothness
     from 0.01 to 60 (and 0 / negative: no bound), coordinates up to 10^4, negative radii, cameras inside objects.

@@ -131,10 +131,12 @@ def relight_held(torch, r, look, p, held, want=RELIT, stream="torch"):
     return c.collect()
 
 
-def run_case(torch, sc, look, mode, source, rays, what, exacts=(False, True), stride_pad=0):
+def run_case(torch, sc, look, mode, source, rays, what, exacts=(False, True), stride_pad=0, size=(W, H)):
     """the whole of one (scene, mode, source): both settings of the exact skips, every pair of masks one after the other on the same
-    planes (each against the planes as they were before it), then the relight"""
+    planes (each against the planes as they were before it), then the relight.  size: the frame of source "pixels", whose camera
+    rays `rays` are"""
     nl = len(sc.lights())
+    w, h = size
     a, b = open_renderer(sc, MODES[mode]), open_renderer(look, MODES[mode])
     try:
         for exact in exacts:
@@ -147,8 +149,8 @@ def run_case(torch, sc, look, mode, source, rays, what, exacts=(False, True), st
                 pa, _ = capture(torch, a, rays, stride=stride)
                 pb, got_b = capture(torch, b, rays, stride=stride)
             else:
-                pa, _ = capture_pixels(torch, a, W, H)
-                pb, got_b = capture_pixels(torch, b, W, H)
+                pa, _ = capture_pixels(torch, a, w, h)
+                pb, got_b = capture_pixels(torch, b, w, h)
             all16 = exact or source == "pixels"
             # 3. B's planes are the oracle's, from B's own hit_dist and hit_id
             ref = UR.reference(look, rays, got_b["dist"], got_b["id"])
@@ -159,7 +161,7 @@ def run_case(torch, sc, look, mode, source, rays, what, exacts=(False, True), st
                 if source == "rays":
                     a.light_update_rays_into(look, d_rays.data_ptr(), n, march, spec, stream=torch.cuda.current_stream().cuda_stream, **update_args(pa))
                 else:
-                    a.light_update_pixels_into(look, n, W, H, march, spec, stream=torch.cuda.current_stream().cuda_stream, **update_args(pa))
+                    a.light_update_pixels_into(look, n, w, h, march, spec, stream=torch.cuda.current_stream().cuda_stream, **update_args(pa))
                 a.sync()
                 torch.cuda.synchronize()
                 assert_updated(before, raw(pa), want, n, nl, stride, march, spec, all16, f"{what} exact={exact} masks=({march}, {spec})")
@@ -169,7 +171,7 @@ def run_case(torch, sc, look, mode, source, rays, what, exacts=(False, True), st
             if source == "rays":
                 assert_same(got, shade_rays(torch, b, rays, want=RELIT), RELIT, f"{what} exact={exact}: relight against B's shading query")
             else:
-                assert_same(got, frame(torch, b, W, H), ("rgb", "pixel"), f"{what} exact={exact}: relight against B's frame")
+                assert_same(got, frame(torch, b, w, h), ("rgb", "pixel"), f"{what} exact={exact}: relight against B's frame")
     finally:
         b.close()
         a.close()
