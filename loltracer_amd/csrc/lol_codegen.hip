@@ -6,6 +6,8 @@
  */
 #include "lol_gpu_internal.h"
 #include "lol_code_key.h"
+#include <cstdarg>
+#include <stdexcept>
 
 /* the text of the lol_kernel*.h files, embedded at build time (csrc/Makefile: lol_kernel_src.inc) for hipRTC */
 #include "lol_kernel_src.inc"
@@ -13,11 +15,30 @@
 #pragma GCC visibility push(hidden)
 /* ------------------------------------------------- scene → HIP source (the "JIT") */
 
+/* Appends printf-style to `s`.  It measures first, so no line is ever cut off, whatever its length: the generator's longest, the
+ * saturation-culling site of SdfEmitter with its seven literals of 37 bytes, is some 620 bytes at four-digit temporaries.  The
+ * compiler checks the arguments against the literal, so a site that has two forms makes two calls instead of choosing a literal.
+ * (Hidden like everything here, but not static: tools/spec_source.cpp --selftest calls it.) */
+void appendf(std::string& s, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+void appendf(std::string& s, const char* fmt, ...) {
+	va_list ap, measure;
+	va_start(ap, fmt);
+	va_copy(measure, ap);
+	const int n = vsnprintf(nullptr, 0, fmt, measure);
+	va_end(measure);
+	if (n < 0) { va_end(ap); throw std::length_error("appendf"); }
+	const size_t at = s.size();
+	s.resize(at + (size_t)n + 1);                    /* (vsnprintf writes the terminator too) */
+	vsnprintf(&s[at], (size_t)n + 1, fmt, ap);
+	va_end(ap);
+	s.resize(at + (size_t)n);
+}
+
 std::string fbits(float v) {
 	uint32_t u;
 	memcpy(&u, &v, 4);
-	char b[48];
-	snprintf(b, sizeof b, "__builtin_bit_cast(float, 0x%08xu)", u);
+	std::string b;
+	appendf(b, "__builtin_bit_cast(float, 0x%08xu)", u);
 	return b;
 }
 
@@ -68,11 +89,11 @@ Sphere enclose(const Sphere& a, const Sphere& b) {
 }
 
 void cluster_bounds(const lol_program& P, RootBound& R);
+static bool sane(double v) { return v - v == 0.0 && fabs(v) < 1e15; }      /* finite, and of a size a bound can be made from */
 
 std::vector<RootBound> analyse_roots(const lol_program& P) {
 	std::vector<RootBound> roots;
 	std::vector<Sphere> st;
-	auto sane = [](double v) { return v - v == 0.0 && fabs(v) < 1e15; };
 	RootBound cur;
 	for (uint32_t i = 0; i < P.n_ops; i++) {
 		const lol_op& o = P.ops[i];
@@ -163,7 +184,6 @@ void cluster_bounds(const lol_program& P, RootBound& R) {
 		if (cost < best) { best = cost; cut = c; }
 	}
 	const Sphere a = hull(0, cut), b = hull(cut, leaves.size());
-	auto sane = [](double v) { return v - v == 0.0 && fabs(v) < 1e15; };
 	if (!a.ok || !b.ok || !sane(a.r) || !sane(b.r)) return;
 	if (fmax(a.r, b.r) > 0.75 * R.r) return;
 	R.clusters = { a, b };
@@ -366,6 +386,31 @@ CullPlan plan_culling(const std::vector<RootBound>& roots, bool enabled) {
 	return plan;
 }
 
+/* One walk of a plan for both of its consumers (build_mops and SdfEmitter): per object, in the order of evaluation, the runs that
+ * open in front of it — plan.intervals[first_run, first_run + n_open), outer first —, how many runs end behind it (runs nest: they
+ * are the innermost n_close of those open), and whether the tie rule applies to it. */
+struct PlanStep {
+	const RootBound* root = nullptr;
+	size_t   first_run = 0;
+	uint32_t n_open = 0, n_close = 0;
+	bool     tie = false;                 /* evaluated after an object that follows it in the file: a tie goes to the lower id */
+};
+std::vector<PlanStep> walk_plan(const std::vector<RootBound>& roots, const CullPlan& plan) {
+	std::vector<PlanStep> steps(plan.order.size());
+	for (const CullInterval& iv : plan.intervals) { steps[iv.begin].n_open++; steps[iv.end - 1].n_close++; }
+	size_t next_run = 0;                  /* (plan_culling sorts the runs by where they begin) */
+	uint32_t max_id_seen = 0;
+	for (size_t oi = 0; oi < steps.size(); oi++) {
+		PlanStep& st = steps[oi];
+		st.root = &roots[plan.order[oi]];
+		st.first_run = next_run;
+		next_run += st.n_open;
+		st.tie = st.root->id < max_id_seen;
+		if (st.root->id > max_id_seen) max_id_seen = st.root->id;
+	}
+	return steps;
+}
+
 /*
  * Post-order program → macro-ops of the interpreter (lol_kernel.h, Interp).  The accumulator is the top of the
  * post-order operand stack:
@@ -406,23 +451,20 @@ std::vector<uint32_t> build_mops(const lol_program& P, const FastPaths* fast, co
 	const bool fuse_pops = !deep && !(tuning_env("LOL_GPU_INTERP_FUSE_POPS") && tuning_env("LOL_GPU_INTERP_FUSE_POPS")[0] == '0');     /* A/B switch */
 	const std::vector<CullInterval>& ivs = plan.intervals;
 	const bool group_first = plan.group && !ivs.empty() && ivs[0].begin == plan.n_unbounded && ivs[0].end == plan.order.size();
-	std::vector<size_t> at(ivs.size());              /* where each test's constants record went */
-	std::vector<uint32_t> begins(plan.order.size() + 1, 0);
-	for (const CullInterval& iv : ivs) begins[iv.begin]++;
-	std::vector<std::vector<size_t>> ends_at(plan.order.size() + 1);      /* the runs that end after object oi - 1 (linear, not a scan per object) */
-	for (size_t k = 0; k < ivs.size(); k++) ends_at[ivs[k].end].push_back(k);
-	uint32_t max_id_seen = 0;
-	size_t next_iv = 0;
-	for (size_t oi = 0; oi < plan.order.size(); oi++) {
-		const RootBound& R = roots[plan.order[oi]];
-		for (uint32_t n = 0; n < begins[oi]; n++, next_iv++) {             /* (never at oi == 0: plan_culling) */
-			const CullInterval& iv = ivs[next_iv];
+	const std::vector<PlanStep> steps = walk_plan(roots, plan);
+	auto opens_at = [&](size_t pos) { return pos < steps.size() ? steps[pos].n_open : 0u; };      /* runs that begin at a position */
+	std::vector<size_t> open;                        /* where the constants records of the runs now open went, outer first */
+	for (size_t oi = 0; oi < steps.size(); oi++) {
+		const PlanStep& st = steps[oi];
+		const RootBound& R = *st.root;
+		for (uint32_t n = 0; n < st.n_open; n++) {                         /* (never at oi == 0: plan_culling) */
+			const CullInterval& iv = ivs[st.first_run + n];
 			uint32_t c[lol::MOP_DWORDS] = { 0 };
-			c[0] = (n + 1 < begins[oi] ? lol::CULLC_NEXT : 0u) | (begins[iv.end] ? lol::CULLC_AFTER : 0u);
+			c[0] = (n + 1 < st.n_open ? lol::CULLC_NEXT : 0u) | (opens_at(iv.end) ? lol::CULLC_AFTER : 0u);
 			for (int j = 0; j < 3; j++) c[2 + j] = fbits32(iv.test.c[j]);
 			c[5] = fbits32(iv.test.rm);
 			c[6] = fbits32(iv.test.k);
-			at[next_iv] = out.size();
+			open.push_back(out.size());
 			out.insert(out.end(), c, c + lol::MOP_DWORDS);
 		}
 		int depth = 0;                                   /* post-order stack depth before the current op */
@@ -467,16 +509,18 @@ std::vector<uint32_t> build_mops(const lol_program& P, const FastPaths* fast, co
 			emitted = true;
 			out.insert(out.end(), m, m + lol::MOP_DWORDS);
 		}
-		out[last] |= lol::MOP_TOP | lol::MOPB_TAIL | (R.id < max_id_seen ? lol::MOP_TIE : 0u);
+		out[last] |= lol::MOP_TOP | lol::MOPB_TAIL | (st.tie ? lol::MOP_TIE : 0u);
 		out[last + 1] = R.id;
-		if (R.id > max_id_seen) max_id_seen = R.id;
-		if (begins[oi + 1]) {
+		if (const uint32_t n_next = opens_at(oi + 1)) {
 			const bool group_here = group_first && oi + 1 == plan.n_unbounded;
 			if (group_here) out[last] |= lol::MOPB_CULL_NEXT;
-			if (begins[oi + 1] > (group_here ? 1u : 0u)) out[last] |= lol::MOPB_CULL_CHAIN;
+			if (n_next > (group_here ? 1u : 0u)) out[last] |= lol::MOPB_CULL_CHAIN;
 		}
-		for (size_t k : ends_at[oi + 1])                                   /* every run that ends here: how far its test jumps */
-			out[at[k] + 1] = (uint32_t)((out.size() - at[k]) / lol::MOP_DWORDS - 1);
+		for (uint32_t n = 0; n < st.n_close; n++) {                        /* every run that ends here: how far its test jumps */
+			const size_t at = open.back();
+			open.pop_back();
+			out[at + 1] = (uint32_t)((out.size() - at) / lol::MOP_DWORDS - 1);
+		}
 	}
 	return out;
 }
@@ -492,6 +536,425 @@ bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, 
 	return true;
 }
 
+/* ------------------------------------------------- the scene's SDF as HIP text (emit_sdf)
+ * What form one struct takes: every decision, taken once (decide_form) before any text is written. */
+struct SdfForm {
+	bool out_of_line = false;       /* the body is ONE real function `<name>_fn` instead of being inlined into every loop (emit_sdf) */
+	bool param = false;             /* the structure module's: every number a read K[7 i + j] instead of a literal (emit_sdf) */
+	int  fsqrt = 0;                 /* the proven root of the fast SDF's primitives (FastPaths::sqrt_kind), 0: the plain one */
+	bool nan_flag = false;          /* spheres may drop the range tracker (sd_sphere_fast_nr) */
+	bool carry = false;             /* the culling bound of the outermost run is carried along the ray (carry_constants) */
+	bool vcarry = false;            /* ... and the object's own last value is folded into it, with the constants `vc` */
+	ValueCarryConsts vc;
+	bool last_id = false;           /* ID_FROM_LAST: a third body, eval_rec(), and the id decided once after the march */
+	int  sat_cull_min_prims = 32;   /* operands of a smooth union from this many primitives on get a saturation test; 0: none */
+	int  cooldown = 3;              /* evaluations that do not test again after a test that did not allow the skip */
+};
+
+SdfForm decide_form(const lol_program& P, const FastPaths* fast, bool out_of_line, bool param, const std::vector<RootBound>& roots,
+                    const CullPlan& plan) {
+	SdfForm f;
+	f.out_of_line = out_of_line;
+	f.param = param;
+	f.fsqrt = fast ? fast->sqrt_kind : 0;
+	/* spheres of radius >= 2^-20 carry no range tracker where the device has shown the fast root harmless below its proven domain
+	 * (lol_kernel.h, sd_sphere_fast_nr): a NaN reaches the object's value instead, which is looked at once */
+	f.nan_flag = fast && fast->sqrt_tiny_ok;
+	/* In the inlined fast SDF, the culling bound carried along the ray (carry_constants): `lb` per lane, `rt` the t of the
+	 * point being evaluated, `carry` whether this loop's ray may set lb (ray_begin; lol_kernel.h, march / soft_shadow).  Out of
+	 * line the body keeps the plain test: its state would be per call.  By default only where the outermost run is ONE object behind
+	 * its two cluster spheres: measured on one box, six alternating repetitions (profiles/r7_ab_cull_carry.txt), scene4 C3
+	 * +5.5 %, orbit +2.7 %, but scene.lol's group of three objects (C2) -2.7 %: its rays keep failing the group test, and the
+	 * carried check is one fma, a compare and a branch more on every test.  LOL_GPU_CULL_CARRY=0 / 1: off / on wherever inlined. */
+	f.carry = fast && !out_of_line && !plan.intervals.empty();
+	if (const char* e = tuning_env("LOL_GPU_CULL_CARRY")) f.carry = f.carry && atoi(e) != 0;
+	else f.carry = f.carry && !plan.intervals[0].both.empty();
+	/* ... and the object's own last value folded into the same lb (value_carry_constants), where the carry is on and the outermost run
+	 * is ONE object: a run of several would need every object's bound per step, which is what cost scene.lol's group 2.7 % with the
+	 * cluster carry.  The carried check then comes BEFORE the cool-down counter: the evaluations taken under cool-down refresh lb, and
+	 * the first step at which the object has stopped winning is skipped without waiting for the counter to run out.
+	 * LOL_GPU_CULL_VALUE_CARRY=0 / 1: off / on (still only for a single object behind a carried bound). */
+	f.vcarry = f.carry && plan.intervals[0].end == plan.intervals[0].begin + 1 && roots[plan.order[plan.intervals[0].begin]].bounded;
+	if (const char* e = tuning_env("LOL_GPU_CULL_VALUE_CARRY")) f.vcarry = f.vcarry && atoi(e) != 0;
+	if (f.vcarry) f.vc = value_carry_constants(P, roots[plan.order[plan.intervals[0].begin]]);
+	/* ID_FROM_LAST, for the inlined fast SDF of a scene of exactly TWO top-level objects — the scenes that keep the id in their march
+	 * (ASK_ID_ONCE, SdfEmitter::head_inlined); every other scene keeps its source byte for byte.  The primary march evaluates through
+	 * eval_rec(): the distance alone, like eval_dist(), plus a RECORD — each object's value at this step per lane, +inf for an object
+	 * the culling skipped — and decides the id once, after the loop, from the record of the lane's own last step (lol_kernel.h, march;
+	 * id_of).  Per step: one v_min_f32 per object instead of the compares and selects of the strict-'<' / lower-id rule.
+	 * What it rests on: an object's value that is NaN or infinite re-shades the wave through the plain pipeline — every value
+	 * recorded goes through nanacc = fma(value, 0, nanacc) (lol_kernel.h, unproven) — so the rules only have to agree for finite
+	 * values, where "the lowest id among the objects at the minimum" IS what the strict '<' and the lower-id tie rule of eval()
+	 * leave, in any evaluation order (-0 == +0 in both).  They differ for t = +inf alone (t < +inf is false: eval() keeps id 0) and
+	 * for NaN.  A skipped object's plain value strictly loses (the tests of SdfEmitter), which is what its +inf in the record says.
+	 * Measured on one box, six alternating repetitions (profiles/r19_ab_last_step_id.txt): scene4 C3 +0.9 %.
+	 * LOL_GPU_LAST_STEP_ID=0 beside LOL_GPU_TUNING: off.
+	 * Only for scenes of at most 32 ops (the scenes that keep 8 waves per SIMD, register_budget): eval_rec() is a third copy of the
+	 * inlined body, and what it saves per step is a fixed couple of dozen cycles — 6 % of a step of scene4's 12 ops, under 1 % of a
+	 * step of a hundred, for a third more code to fetch. */
+	f.last_id = fast && !out_of_line && !param && P.n_roots == 2 && P.n_ops <= 32;
+	if (const char* e = tuning_env("LOL_GPU_LAST_STEP_ID")) f.last_id = f.last_id && atoi(e) != 0;
+	/* LOL_GPU_SAT_CULL_MIN_PRIMS: `a` operands of a smooth union with at least this many primitives get a saturation-
+	 * culling test (SdfEmitter::emit_sat_culled_union); 0 = none.  Measured (tools/tree_scene_ab.py, balanced trees of spheres at
+	 * 1080p, profiles/r2_tree_scene_ab.jsonl): the 17-instruction test pays from a few dozen primitives — 128 spheres
+	 * 232 -> 405 Mpixels/s, 256 spheres 127 -> 166 at 32 (375 / 157 at 16); with a test on every operand scene4
+	 * loses 14 %, a 32-sphere tree 30 %. */
+	if (const char* e = tuning_env("LOL_GPU_SAT_CULL_MIN_PRIMS")) f.sat_cull_min_prims = atoi(e);
+	/* After a test that did not allow the skip, the next `cooldown` evaluations of this SDF object do not test
+	 * again (a ray that is near the object now is near it on its next steps too): the test costs 11 VALU
+	 * instructions, and where it keeps failing that is pure overhead.  Never testing is always allowed — the
+	 * test only ever permits a skip — so this changes no result.  `cool` lives in the Sdf struct, wave-uniform;
+	 * only the outermost test keeps one. */
+	f.cooldown = 3;
+	return f;
+}
+
+/* An object's expression tree from its post-order ops (child `a` / `b` = the operands of sminf(a, b, k)), each node with the
+ * bounding sphere of what is under it (analyse_roots' rules) for the saturation test. */
+struct Node { uint32_t op; int a, b; Sphere bound; uint32_t prims; bool fon = false; };      /* fon: the fast SDF's value of this node is finite or NaN */
+std::vector<Node> object_nodes(const lol_program& P, const RootBound& R, const FastPaths* fast, const SdfForm& f) {
+	std::vector<Node> nodes;
+	std::vector<int> st;
+	for (uint32_t i = R.first; i < R.top; i++) {
+		const lol_op& o = P.ops[i];
+		Node n{ i, -1, -1, { false, { 0, 0, 0 }, 0, 1 }, 1 };
+		if (o.op == LOL_OP_SPHERE) {
+			n.fon = f.fsqrt && f.nan_flag && o.f[3] >= 0x1p-20f && std::isfinite(o.f[3]);      /* sd_sphere_fast_nr (emit_node) */
+			n.bound = { sane(o.f[0]) && sane(o.f[1]) && sane(o.f[2]) && sane(o.f[3]), { o.f[0], o.f[1], o.f[2] }, o.f[3] > 0 ? (double)o.f[3] : 0.0, 1 };
+		} else if (o.op == LOL_OP_RBOX) {
+			bool ok = true;
+			for (int j = 0; j < 7; j++) ok = ok && sane(o.f[j]);
+			ok = ok && o.f[3] >= 0 && o.f[4] >= 0 && o.f[5] >= 0 && o.f[6] >= 0;
+			const double hb = sqrt((double)o.f[3] * o.f[3] + (double)o.f[4] * o.f[4] + (double)o.f[5] * o.f[5]);
+			n.bound = { ok, { o.f[0], o.f[1], o.f[2] }, hb * (1.0 + 1e-12) + o.f[6], 1 };
+		} else if (o.op == LOL_OP_SMIN || o.op == LOL_OP_SMIN_R) {
+			const int top = st.back(); st.pop_back();
+			const int under = st.back(); st.pop_back();
+			n.a = o.op == LOL_OP_SMIN ? under : top;
+			n.b = o.op == LOL_OP_SMIN ? top : under;
+			n.bound = enclose(nodes[n.a].bound, nodes[n.b].bound);
+			if (!(sane(o.f[0]) && o.f[0] > 0)) n.bound.ok = false;
+			n.bound.r += 0.25 * (double)o.f[0];
+			n.bound.levels++;
+			if (!sane(n.bound.r)) n.bound.ok = false;
+			n.prims = nodes[n.a].prims + nodes[n.b].prims;
+			n.fon = nodes[n.a].fon && nodes[n.b].fon && fast && fast->has(o.f[0]);
+		}
+		st.push_back((int)nodes.size());
+		nodes.push_back(n);
+	}
+	return nodes;
+}
+
+/* The body is emitted once per pass where it is inlined: eval() — distance and object id — for the primary march and the normal
+ * taps, and eval_dist() — the distance alone — for the shadow marches, which never look at the id.  There an object joins the running
+ * minimum with ONE v_min_f32 instead of the compare(s) and selects of the strict-'<' / lower-id-wins rule: the two agree on the
+ * value except for the sign of a zero (two objects at distance -0 and +0 of the same point), and a shadow march's results —
+ * its factor maxf(res, 0) and its step count — are the same for s = -0 and s = +0: t + s, 50 s / t compared with 0, and
+ * maxf(+-0, 0) = +0 all are (lol_kernel.h, soft_shadow).  A NaN value is dropped by either form.
+ * ... and once more for an ID_FROM_LAST scene: eval_rec(), eval_dist() plus the record of each object's value (SdfForm::last_id).
+ * Out of line there is the one function, which is eval(). */
+enum class Pass { Eval, EvalDist, EvalRec };
+
+/* The writer of one struct: the form, the plan's walk, the text so far, and the counters of the pass being written. */
+struct SdfEmitter {
+	std::string& s;
+	const lol_program& P;
+	const char* name;
+	const FastPaths* fast;
+	const std::vector<RootBound>& roots;
+	const CullPlan& plan;
+	const SdfForm f;
+	const std::vector<PlanStep> steps;
+	std::string fs;                       /* "_fast<n>": the suffix of the primitives with the proven root (run) */
+	int  t = 0, n_tests = 0;             /* the next temporary and the next test of this pass: t<n>, cl<n> / sl<n> */
+	bool object_has_nr = false;           /* the object being written has a value that is voted on for NaN (emit_node) */
+
+	/* number j of op i: a literal, or the structure module's read of it */
+	std::string num(uint32_t i, int j) const {
+		if (!f.param) return fbits(P.ops[i].f[j]);
+		std::string k;
+		appendf(k, "K[%u]", (unsigned)lol::OP_NUMBERS * i + (unsigned)j);
+		return k;
+	}
+	/* only the outermost test keeps a cool-down counter (wave-uniform state in the Sdf struct) */
+	const char* cool_decl() const { return plan.intervals.empty() ? "" : "\tu32 cool[1] = {};\n"; }
+	int rec_slot(size_t oi) const { return roots[plan.order[oi]].id > roots[plan.order[oi ^ 1]].id ? 1 : 0; }      /* (two objects) */
+
+	/* ---- the struct's head */
+	void head_out_of_line() {
+		/* out of line the cool-down state is per call (always 0: every evaluation tests) */
+		/* (amdgpu_waves_per_eu applies to kernels only: the function is scheduled with the default register budget) */
+		appendf(s, "__device__ __noinline__ SdfOut %s_fn(float px, float py, float pz, u32 rg_lo, u32 rg_hi) {\n"
+		        "\t\tconst V3 p = { px, py, pz };\n\t\tRange rg; rg.lo = rg_lo; rg.hi = rg_hi;\n\t\tfloat nanacc = 0.f;\n\t\tfloat best; u32 best_id;\n\t%s",
+		        name, cool_decl());
+	}
+	void head_inlined() {
+		const char* carry_decl = !f.carry ? "" :
+			"\tfloat lb = -__builtin_inff(), rt = 0.f;\n\tbool carry = false;\n"
+			"\t__device__ __forceinline__ void ray_begin(V3 rd) { carry = vote(!(len2(rd) <= 0x1.00001p+0f)) == 0; }\n"
+			"\t__device__ __forceinline__ void ray_at(float t) { rt = t; }\n";
+		/* ASSUME_SETTLED: the fast pipeline only runs under FLAG_SHADOW_SETTLED (generate_source; lol_kernel.h, soft_shadow).
+		 * loop_done(): what the wave-uniform cool-down counter is after a loop that lanes leave one by one (lol_kernel.h, Interp) */
+		/* ASK_ID_ONCE: the primary march evaluates the distance alone and asks for the id of its last step once (lol_kernel.h,
+		 * march) — from three top-level objects on, where a v_min per object and step outweighs the one evaluation more per pixel
+		 * (measured: scene.lol's four objects +3.6 %, scene4's two -0.8 %; profiles/r6_ab_id_asked_once.txt) */
+		appendf(s, "struct %s {\n\tstatic constexpr bool ASSUME_SETTLED = %s;\n\tstatic constexpr bool ASK_ID_ONCE = %s;\n\tRange rg;\n\tfloat nanacc = 0.f;\n%s%s"
+		        "\t__device__ __forceinline__ void loop_done() { %s%s }\n", name, fast ? "true" : "false", P.n_roots >= 3 ? "true" : "false", cool_decl(),
+		        carry_decl, plan.intervals.empty() ? "" : "cool[0] = 0u;", f.carry ? " lb = -__builtin_inff(); carry = false;" : "");
+		if (f.param) s += "\tparam_ptr K = nullptr;\n";
+		if (f.last_id) {
+			/* the record's two slots in the order of the ids: rec0 the object of the lower id, which a tie goes to */
+			const uint32_t ida = roots[0].id, idb = roots[1].id;
+			appendf(s, "\tstatic constexpr bool ID_FROM_LAST = true;\n"
+			        "\t__device__ __forceinline__ u32 id_of(float rec0, float rec1) const { return rec0 == vmin_(rec0, rec1) ? %uu : %uu; }\n",
+			        ida < idb ? ida : idb, ida < idb ? idb : ida);
+		}
+	}
+
+	/* ---- one pass */
+	void pass_prologue(Pass pass) {
+		if (!f.out_of_line)
+			s += pass == Pass::EvalRec    ? "\t__device__ __forceinline__ void eval_rec(V3 p, float& best, float& rec0, float& rec1) {\n"
+			   : pass == Pass::EvalDist ? "\t__device__ __forceinline__ void eval_dist(V3 p, float& best) {\n"
+			                            : "\t__device__ __forceinline__ void eval(V3 p, float& best, u32& best_id) {\n";
+		s += pass == Pass::Eval ? "\t\tbest = __builtin_inff(); best_id = 0u;\n" : "\t\tbest = __builtin_inff();\n";
+		if (pass != Pass::EvalRec) return;
+		/* an object behind a test that lets the wave skip it is recorded as +inf: it strictly loses */
+		for (size_t oi = 0; oi < plan.order.size(); oi++)
+			for (const CullInterval& iv : plan.intervals)
+				if (iv.begin <= oi && oi < iv.end) {
+					appendf(s, "\t\trec%d = __builtin_inff();\n", rec_slot(oi));
+					break;
+				}
+	}
+	void emit_pass(Pass pass) {
+		pass_prologue(pass);
+		t = 0;
+		n_tests = 0;
+		for (size_t oi = 0; oi < steps.size(); oi++) emit_object(pass, oi);
+		if (!f.out_of_line) s += "\t}\n";
+	}
+	void emit_object(Pass pass, size_t oi) {
+		const PlanStep& st = steps[oi];
+		for (uint32_t n = 0; n < st.n_open; n++) {                            /* outer runs first */
+			const size_t run = st.first_run + n;
+			if (run != 0) open_test_plain(plan.intervals[run]);
+			else if (f.carry) open_test_carried(plan.intervals[run]);
+			else open_test_cooldown(plan.intervals[run]);
+		}
+		const std::vector<Node> nodes = object_nodes(P, *st.root, fast, f);
+		object_has_nr = false;
+		const int d = emit_node(nodes, (int)nodes.size() - 1);
+		const bool rec = pass == Pass::EvalRec;
+		/* a NaN from a sphere without range tracker reaches the object's value: 0 * NaN (or inf) = NaN (... and every value the record takes) */
+		if (object_has_nr || rec) appendf(s, "\t\tnanacc = __builtin_fmaf(t%d, 0.f, nanacc);\n", d);
+		if (rec) appendf(s, "\t\trec%d = t%d;\n", rec_slot(oi), d);
+		join_minimum(pass, st, d);
+		if (f.vcarry && oi == plan.intervals[0].begin) value_carry_update(d);
+		for (uint32_t n = 0; n < st.n_close; n++) s += "\t\t} }\n";           /* every run that ends here */
+	}
+
+	/* ---- the tests in front of a run.  One test = one bounding sphere; a run guarded by several (an object's two cluster spheres)
+	 * is skipped where ALL pass.  This writes their declarations into `decl` and the votes that say "some lane needs the run" into
+	 * `votes`, and returns the number of the first. */
+	static std::vector<CullTest> tests_of(const CullInterval& iv) { return iv.both.empty() ? std::vector<CullTest>{ iv.test } : iv.both; }
+	int declare_tests(const std::vector<CullTest>& tests, std::string& decl, std::string& votes) {
+		const int k0 = n_tests;
+		for (const CullTest& ct : tests) {
+			const int k = n_tests++;
+			appendf(decl,
+			        "\t\t  const float cx%d = p.x - %s, cy%d = p.y - %s, cz%d = p.z - %s;\n"
+			        "\t\t  const float cl%d = (cx%d * cx%d + cy%d * cy%d) + cz%d * cz%d;\n"
+			        "\t\t  const float cu%d = (best + %s) * %s;\n",
+			        k, fbits(ct.c[0]).c_str(), k, fbits(ct.c[1]).c_str(), k, fbits(ct.c[2]).c_str(),
+			        k, k, k, k, k, k, k, k, fbits(ct.rm).c_str(), fbits(ct.k).c_str());
+			appendf(votes, "%svote(!(cl%d > cu%d * cu%d)) | vote(!(cu%d > 0.f))", votes.empty() ? "" : " | ", k, k, k, k);
+		}
+		return k0;
+	}
+	/* an inner run: tested at every evaluation */
+	void open_test_plain(const CullInterval& iv) {
+		std::string decl, votes;
+		declare_tests(tests_of(iv), decl, votes);
+		s += "\t\t{\n" + decl + "\t\t  if (((" + votes + ")) != 0) {\n";
+	}
+	/* the outermost run: tested unless the cool-down counter runs (SdfForm::cooldown) */
+	void open_test_cooldown(const CullInterval& iv) {
+		std::string decl, votes;
+		const int k0 = declare_tests(tests_of(iv), decl, votes);
+		appendf(s, "\t\t{ bool need%d = true;\n\t\t  if (cool[0] == 0u) {\n", k0);
+		s += decl;
+		appendf(s, "\t\t  need%d = ((", k0);
+		s += votes;
+		appendf(s, ")) != 0;\n\t\t  if (need%d) cool[0] = %du;\n\t\t  } else cool[0]--;\n\t\t  if (need%d) {\n", k0, f.cooldown, k0);
+	}
+	/* the outermost run of a struct that carries its bound: the carried bound first (one fma and one compare); where a lane fails it,
+	 * the full test — which, passed by the whole wave on a ray that may carry, sets lb anew (one v_sqrt per sphere).  A failed full
+	 * test leaves lb as it is: still a bound, only an older one.  With the value carry the carried check comes before the counter
+	 * (SdfForm::vcarry) and the new bound joins lb by maxf_. */
+	void open_test_carried(const CullInterval& iv) {
+		const std::vector<CullTest> tests = tests_of(iv);
+		std::string decl, votes;
+		const int k0 = declare_tests(tests, decl, votes);
+		const CarryConsts cc = carry_constants(tests);
+		const float ctc = f.vcarry && f.vc.ctc > cc.ctc ? f.vc.ctc : cc.ctc;      /* one left-hand side for both bounds: the more conservative */
+		if (f.vcarry)
+			appendf(s, "\t\t{ bool need%d = true;\n\t\t  {\n"
+			        "\t\t  if (vote(!(__builtin_fmaf(rt, %s, __builtin_fabsf(best)) < lb)) == 0) need%d = false; else if (cool[0] == 0u) {\n",
+			        k0, fbits(ctc).c_str(), k0);
+		else
+			appendf(s, "\t\t{ bool need%d = true;\n\t\t  if (cool[0] == 0u) {\n"
+			        "\t\t  if (vote(!(__builtin_fmaf(rt, %s, __builtin_fabsf(best)) < lb)) == 0) need%d = false; else {\n",
+			        k0, fbits(ctc).c_str(), k0);
+		s += decl;
+		appendf(s, "\t\t  need%d = ((", k0);
+		s += votes;
+		appendf(s, ")) != 0;\n\t\t  if (need%d) cool[0] = %du;\n\t\t  else if (carry) {\n", k0, f.cooldown);
+		for (size_t j = 0; j < tests.size(); j++) {
+			if (j) appendf(s, "\t\t    lm = vmin_(__builtin_fmaf(__builtin_amdgcn_sqrtf(cl%d), %s, %s), lm);\n",
+			               k0 + (int)j, fbits(cc.a[j]).c_str(), fbits(cc.b[j]).c_str());
+			else   appendf(s, "\t\t    float lm = __builtin_fmaf(__builtin_amdgcn_sqrtf(cl%d), %s, %s);\n",
+			               k0 + (int)j, fbits(cc.a[j]).c_str(), fbits(cc.b[j]).c_str());
+		}
+		if (f.vcarry)
+			appendf(s, "\t\t    const float lg = __builtin_fmaf(rt, %s, lm);\n\t\t    lb = maxf_(__builtin_fmaf(__builtin_fabsf(lg), -0x1p-20f, lg), lb);\n"
+			        "\t\t  }\n\t\t  } else cool[0]--; }\n\t\t  if (need%d) {\n", fbits(cc.ctt).c_str(), k0);
+		else
+			appendf(s, "\t\t    const float lg = __builtin_fmaf(rt, %s, lm);\n\t\t    lb = __builtin_fmaf(__builtin_fabsf(lg), -0x1p-20f, lg);\n"
+			        "\t\t  }\n\t\t  } } else cool[0]--;\n\t\t  if (need%d) {\n", fbits(cc.ctt).c_str(), k0);
+	}
+
+	/* ---- an object's expression: one SSA temporary per node, returned by number */
+	/* what the call of one smooth minimum is written with: k, 2k, 1/(2k) and the saturation threshold as text, "<false>" where the
+	 * form without v_div_fixup is proven, and whether the call takes the threshold */
+	struct SminText { std::string k, k2, hrk, ks; const char* fx; bool sat_arith; };
+	int emit_node(const std::vector<Node>& nodes, int ni) {
+		const Node& n = nodes[ni];
+		const lol_op& o = P.ops[n.op];
+		switch (o.op) {
+		case LOL_OP_SPHERE:
+			if (n.fon) {                                       /* sd_sphere_fast_nr: no range tracker (SdfForm::nan_flag) */
+				appendf(s, "\t\tconst float t%d = sd_sphere_fast_nr<%d>(p, %s, %s, %s, %s);\n", t, f.fsqrt,
+				        fbits(o.f[0]).c_str(), fbits(o.f[1]).c_str(), fbits(o.f[2]).c_str(), fbits(o.f[3]).c_str());
+				object_has_nr = true;
+			} else
+				appendf(s, "\t\tconst float t%d = sd_sphere%s(p, %s, %s, %s, %s%s);\n", t, fs.c_str(),
+				        num(n.op, 0).c_str(), num(n.op, 1).c_str(), num(n.op, 2).c_str(), num(n.op, 3).c_str(), f.fsqrt ? ", rg" : "");
+			return t++;
+		case LOL_OP_RBOX:
+			appendf(s, "\t\tconst float t%d = sd_round_box%s(p, %s, %s, %s, %s, %s, %s, %s%s);\n", t, fs.c_str(),
+			        num(n.op, 0).c_str(), num(n.op, 1).c_str(), num(n.op, 2).c_str(), num(n.op, 3).c_str(),
+			        num(n.op, 4).c_str(), num(n.op, 5).c_str(), num(n.op, 6).c_str(), f.fsqrt ? ", rg" : "");
+			return t++;
+		case LOL_OP_PLANE:
+			appendf(s, "\t\tconst float t%d = p.y - %s;\n", t, num(n.op, 0).c_str());
+			return t++;
+		default: break;
+		}
+		/* LOL_OP_SMIN / LOL_OP_SMIN_R */
+		const float ks = smooth_sat_threshold(o.f[0]);
+		const bool proven = fast && fast->has(o.f[0]);
+		/* without v_div_fixup where that is proven too; such an object's value is then voted on for NaN (an infinite
+		 * operand difference — lol_kernel.h, smin_h_fast) like one with spheres that carry no range tracker */
+		const char* fx = proven && fast->has_nf(o.f[0]) ? "<false>" : "";
+		if (fx[0]) object_has_nr = true;
+		/* (sat_arith) the arithmetic shortcut only where the SDF is inlined: in the out-of-line function its four-way branching
+		 * costs more than it saves (504-op chain: 100 -> 42 Mpixels/s) */
+		const SminText m{ num(n.op, 0), fbits(2.0f * o.f[0]), fbits(0.5f * (1.0f / o.f[0])), fbits(ks), fx, !f.out_of_line && ks > 0.f };
+		if (proven && ks > 0.f && f.sat_cull_min_prims > 0 && nodes[n.a].bound.ok && nodes[n.a].prims >= (uint32_t)f.sat_cull_min_prims)
+			return emit_sat_culled_union(nodes, n, m);
+		/* operands in program order (a flattened chain keeps its deep operand first and its operand stack shallow) */
+		const bool a_first = o.op == LOL_OP_SMIN;
+		const int first = emit_node(nodes, a_first ? n.a : n.b), second = emit_node(nodes, a_first ? n.b : n.a);
+		const int a = a_first ? first : second, b = a_first ? second : first;
+		if (proven && m.sat_arith)
+			appendf(s, "\t\tconst float t%d = sminf_fastdiv_sat%s%s(t%d, t%d, %s, %s, %s, %s);\n", t,
+			        nodes[n.a].fon && nodes[n.b].fon ? "2" : "", fx, a, b, m.k.c_str(), m.k2.c_str(), m.hrk.c_str(), m.ks.c_str());
+		else if (proven)
+			appendf(s, "\t\tconst float t%d = sminf_fastdiv%s(t%d, t%d, %s, %s, %s);\n", t, fx, a, b, m.k.c_str(), m.k2.c_str(), m.hrk.c_str());
+		else
+			appendf(s, "\t\tconst float t%d = sminf_(t%d, t%d, %s);\n", t, a, b, m.k.c_str());
+		return t++;
+	}
+	/* Saturation culling inside a smooth union (fast struct only, proven k > 0): sminf(a, b, k) is EXACTLY
+	 * b - dlt*0.f = b + 0.f when dlt = b - a <= -ks (sminf_fastdiv_sat), so operand `a` need not be evaluated
+	 * where it is provably that much greater than b.  b is evaluated first; with sb = fl(b + ks) the bounding-
+	 * sphere test of the top-level culling (best := sb) gives a > sb for the binary32 value of `a`, hence
+	 * dlt = fl(b - a) <= fl(b - sb) =: sw by the monotonicity of rounding, and sw <= -ks is checked directly;
+	 * |p - C|^2 < 2^120 keeps every primitive of `a` (all within R < 10^15 of C) finite, so dlt is finite and
+	 * dlt*0.f = -0.  A NaN or infinite b fails the comparisons.  Per wave, like every other skip. */
+	int emit_sat_culled_union(const std::vector<Node>& nodes, const Node& n, const SminText& m) {
+		const int b = emit_node(nodes, n.b);
+		const CullTest ct = make_test(nodes[n.a].bound);
+		const int r = t++, q = n_tests++;
+		appendf(s,
+		        "\t\tfloat t%d;\n"
+		        "\t\t{ const float sb%d = t%d + %s, sw%d = t%d - sb%d;\n"
+		        "\t\t  const float sx%d = p.x - %s, sy%d = p.y - %s, sz%d = p.z - %s;\n"
+		        "\t\t  const float sl%d = (sx%d * sx%d + sy%d * sy%d) + sz%d * sz%d;\n"
+		        "\t\t  const float su%d = (sb%d + %s) * %s;\n"
+		        "\t\t  if ((vote(!(sl%d > su%d * su%d)) | vote(!(su%d > 0.f)) | vote(!(sw%d <= -%s)) | vote(!(sl%d < 0x1p120f))) != 0) {\n",
+		        r, q, b, m.ks.c_str(), q, b, q,
+		        q, fbits(ct.c[0]).c_str(), q, fbits(ct.c[1]).c_str(), q, fbits(ct.c[2]).c_str(),
+		        q, q, q, q, q, q, q,
+		        q, q, fbits(ct.rm).c_str(), fbits(ct.k).c_str(),
+		        q, q, q, q, q, m.ks.c_str(), q);
+		const int a = emit_node(nodes, n.a);
+		if (m.sat_arith)
+			appendf(s, "\t\t  t%d = sminf_fastdiv_sat%s(t%d, t%d, %s, %s, %s, %s);\n\t\t  } else t%d = t%d + 0.f;\n\t\t}\n",
+			        r, m.fx, a, b, m.k.c_str(), m.k2.c_str(), m.hrk.c_str(), m.ks.c_str(), r, b);
+		else
+			appendf(s, "\t\t  t%d = sminf_fastdiv%s(t%d, t%d, %s, %s, %s);\n\t\t  } else t%d = t%d + 0.f;\n\t\t}\n",
+			        r, m.fx, a, b, m.k.c_str(), m.k2.c_str(), m.hrk.c_str(), r, b);
+		return r;
+	}
+
+	/* ---- how the object's value t<d> joins the running minimum */
+	void join_minimum(Pass pass, const PlanStep& st, int d) {
+		const uint32_t id = st.root->id;
+		if (pass != Pass::Eval)
+			appendf(s, "\t\tbest = vmin_(t%d, best);\n", d);
+		else if (st.tie)                  /* evaluated after an object that follows it in the file: ties go to the lower id */
+			appendf(s, "\t\tif (t%d < best || (t%d == best && best_id > %uu)) { best = t%d; best_id = %uu; }\n", d, d, id, d, id);
+		else
+			appendf(s, "\t\tif (t%d < best) { best = t%d; best_id = %uu; }\n", d, d, id);
+	}
+	/* the value just computed bounds the object further along the ray (value_carry_constants) */
+	void value_carry_update(int d) {
+		appendf(s, "\t\tif (carry) {\n\t\t  const float vg = __builtin_fmaf(rt, %s, __builtin_fmaf(__builtin_fabsf(t%d), -%s, t%d) - %s);\n"
+		        "\t\t  lb = maxf_(__builtin_fmaf(__builtin_fabsf(vg), -0x1p-20f, vg), lb);\n\t\t}\n",
+		        fbits(f.vc.ctt).c_str(), d, fbits(f.vc.dl).c_str(), d, fbits(f.vc.ef).c_str());
+	}
+
+	/* ---- what closes the struct */
+	void epilogue() {
+		if (f.out_of_line) {
+			s += "\t\treturn { best, best_id, rg.lo, rg.hi, nanacc };\n}\n";
+			appendf(s, "struct %s {\n\tstatic constexpr bool ASSUME_SETTLED = %s;\n\tstatic constexpr bool ASK_ID_ONCE = false;\n\tRange rg;\n\tfloat nanacc = 0.f;\n"
+			        "\t__device__ __forceinline__ void loop_done() {}\n"
+			        "\t__device__ __forceinline__ void eval(V3 p, float& best, u32& best_id) {\n"
+			        "\t\tconst SdfOut o = %s_fn(p.x, p.y, p.z, rg.lo, rg.hi);\n"
+			        "\t\tbest = o.best; best_id = o.id; rg.lo = o.lo; rg.hi = o.hi; nanacc += o.nanacc;\n\t}\n"
+			        "\t__device__ __forceinline__ void eval_dist(V3 p, float& best) { u32 unused; eval(p, best, unused); }\n", name, fast ? "true" : "false", name);
+		}
+		/* the arithmetic of the shading around the loops that the device has proven for the fast pipeline (lol_kernel.h, ShadeMath); a
+		 * struct without it — the plain SDF, LOL_GPU_SHADE_MATH=0 — is the text it was */
+		if (fast && fast->shade_root) appendf(s, "\tstruct Shade { static constexpr int ROOT = %d, RCP = %d; };\n", fast->shade_root, fast->shade_rcp);
+		s += "};\n";
+	}
+
+	/* the passes in the order in which they stand in the struct: eval_rec() first where there is one, then eval(), then eval_dist() */
+	void run() {
+		if (f.fsqrt) appendf(fs, "_fast<%d>", f.fsqrt);
+		if (f.out_of_line) head_out_of_line(); else head_inlined();
+		if (f.last_id) emit_pass(Pass::EvalRec);
+		emit_pass(Pass::Eval);
+		if (!f.out_of_line) emit_pass(Pass::EvalDist);
+		epilogue();
+	}
+};
+
 /* Emits one `struct <name>` with eval(): one SSA temporary per op, same operation order WITHIN every top-level object
  * as the post-order program; the objects themselves in the order of `plan` (file order when culling is off).
  * out_of_line: the body becomes ONE real function (`<name>_fn`, __noinline__) that the march, normal and shadow
@@ -500,365 +963,9 @@ bool build_interp_lists(const lol_program& P, const FastPaths& fast, bool cull, 
  * `param` (the structure module, generate_structure_source: fast == nullptr, an empty plan, inlined): every number of the scene is
  * not a literal but a read K[7 i + j] of op i's f[j] through the member pointer K — the source then depends on the structure alone. */
 void emit_sdf(std::string& s, const lol_program& P, const char* name, const FastPaths* fast, bool out_of_line,
-              const std::vector<RootBound>& roots, const CullPlan& plan, const std::string& occupancy, bool param = false) {
-	char line[768];
-	auto num = [&](uint32_t i, int j) -> std::string {
-		if (!param) return fbits(P.ops[i].f[j]);
-		char b[32];
-		snprintf(b, sizeof b, "K[%u]", (unsigned)lol::OP_NUMBERS * i + (unsigned)j);
-		return b;
-	};
-	const int fsqrt = fast ? fast->sqrt_kind : 0;
-	char fs[32] = "";
-	if (fsqrt) snprintf(fs, sizeof fs, "_fast<%d>", fsqrt);
-	/* only the outermost test keeps a cool-down counter (wave-uniform state in the Sdf struct) */
-	char cool_decl[64] = "";
-	if (!plan.intervals.empty()) snprintf(cool_decl, sizeof cool_decl, "\tu32 cool[1] = {};\n");
-	/* ... and, in the inlined fast SDF, the culling bound carried along the ray (carry_constants): `lb` per lane, `rt` the t of the
-	 * point being evaluated, `carry` whether this loop's ray may set lb (ray_begin; lol_kernel.h, march / soft_shadow).  Out of
-	 * line the body keeps today's test: its state would be per call.  By default only where the outermost run is ONE object behind
-	 * its two cluster spheres: measured on one box, six alternating repetitions (profiles/r7_ab_cull_carry.txt), scene4 C3
-	 * +5.5 %, orbit +2.7 %, but scene.lol's group of three objects (C2) -2.7 %: its rays keep failing the group test, and the
-	 * carried check is one fma, a compare and a branch more on every test.  LOL_GPU_CULL_CARRY=0 / 1: off / on wherever inlined. */
-	bool carry = fast && !out_of_line && !plan.intervals.empty();
-	if (const char* e = tuning_env("LOL_GPU_CULL_CARRY")) carry = carry && atoi(e) != 0;
-	else carry = carry && !plan.intervals[0].both.empty();
-	/* ... and the object's own last value folded into the same lb (value_carry_constants), where the carry is on and the outermost run
-	 * is ONE object: a run of several would need every object's bound per step, which is what cost scene.lol's group 2.7 % with the
-	 * cluster carry.  The carried check then comes BEFORE the cool-down counter: the evaluations taken under cool-down refresh lb, and
-	 * the first step at which the object has stopped winning is skipped without waiting for the counter to run out.
-	 * LOL_GPU_CULL_VALUE_CARRY=0 / 1: off / on (still only for a single object behind a carried bound). */
-	bool vcarry = carry && plan.intervals[0].end == plan.intervals[0].begin + 1 && roots[plan.order[plan.intervals[0].begin]].bounded;
-	if (const char* e = tuning_env("LOL_GPU_CULL_VALUE_CARRY")) vcarry = vcarry && atoi(e) != 0;
-	const ValueCarryConsts vc = vcarry ? value_carry_constants(P, roots[plan.order[plan.intervals[0].begin]]) : ValueCarryConsts();
-	/* ID_FROM_LAST, for the inlined fast SDF of a scene of exactly TWO top-level objects — the scenes that keep the id in their march
-	 * (ASK_ID_ONCE below); every other scene keeps its source byte for byte.  The primary march evaluates through eval_rec(): the
-	 * distance alone, like eval_dist(), plus a RECORD — each object's value at this step per lane, +inf for an object the culling
-	 * skipped — and decides the id once, after the loop, from the record of the lane's own last step (lol_kernel.h, march; id_of
-	 * below).  Per step: one v_min_f32 per object instead of the compares and selects of the strict-'<' / lower-id rule.
-	 * What it rests on: an object's value that is NaN or infinite re-shades the wave through the plain pipeline — every value
-	 * recorded goes through nanacc = fma(value, 0, nanacc) (lol_kernel.h, unproven) — so the rules only have to agree for finite
-	 * values, where "the lowest id among the objects at the minimum" IS what the strict '<' and the lower-id tie rule of eval()
-	 * leave, in any evaluation order (-0 == +0 in both).  They differ for t = +inf alone (t < +inf is false: eval() keeps id 0) and
-	 * for NaN.  A skipped object's plain value strictly loses (open_test), which is what its +inf in the record says.
-	 * Measured on one box, six alternating repetitions (profiles/r19_ab_last_step_id.txt): scene4 C3 +0.9 %.
-	 * LOL_GPU_LAST_STEP_ID=0 beside LOL_GPU_TUNING: off.
-	 * Only for scenes of at most 32 ops (the scenes that keep 8 waves per SIMD, generate_source): eval_rec() is a third copy of the
-	 * inlined body, and what it saves per step is a fixed couple of dozen cycles — 6 % of a step of scene4's 12 ops, under 1 % of a
-	 * step of a hundred, for a third more code to fetch. */
-	bool last_id = fast && !out_of_line && !param && P.n_roots == 2 && P.n_ops <= 32;
-	if (const char* e = tuning_env("LOL_GPU_LAST_STEP_ID")) last_id = last_id && atoi(e) != 0;
-	std::string carry_decl;
-	if (carry)
-		carry_decl = "\tfloat lb = -__builtin_inff(), rt = 0.f;\n\tbool carry = false;\n"
-		             "\t__device__ __forceinline__ void ray_begin(V3 rd) { carry = vote(!(len2(rd) <= 0x1.00001p+0f)) == 0; }\n"
-		             "\t__device__ __forceinline__ void ray_at(float t) { rt = t; }\n";
-	if (out_of_line) {
-		/* out of line the cool-down state is per call (always 0: every evaluation tests) */
-		/* (amdgpu_waves_per_eu applies to kernels only: the function is scheduled with the default register budget) */
-		(void)occupancy;
-		snprintf(line, sizeof line, "__device__ __noinline__ SdfOut %s_fn(float px, float py, float pz, u32 rg_lo, u32 rg_hi) {\n"
-		         "\t\tconst V3 p = { px, py, pz };\n\t\tRange rg; rg.lo = rg_lo; rg.hi = rg_hi;\n\t\tfloat nanacc = 0.f;\n\t\tfloat best; u32 best_id;\n\t%s",
-		         name, cool_decl);
-		s += line;
-	} else {
-		/* ASSUME_SETTLED: the fast pipeline only runs under FLAG_SHADOW_SETTLED (generate_source; lol_kernel.h, soft_shadow).
-		 * loop_done(): what the wave-uniform cool-down counter is after a loop that lanes leave one by one (lol_kernel.h, Interp) */
-		/* ASK_ID_ONCE: the primary march evaluates the distance alone and asks for the id of its last step once (lol_kernel.h,
-		 * march) — from three top-level objects on, where a v_min per object and step outweighs the one evaluation more per pixel
-		 * (measured: scene.lol's four objects +3.6 %, scene4's two -0.8 %; profiles/r6_ab_id_asked_once.txt) */
-		snprintf(line, sizeof line, "struct %s {\n\tstatic constexpr bool ASSUME_SETTLED = %s;\n\tstatic constexpr bool ASK_ID_ONCE = %s;\n\tRange rg;\n\tfloat nanacc = 0.f;\n%s%s"
-		         "\t__device__ __forceinline__ void loop_done() { %s%s }\n", name, fast ? "true" : "false", P.n_roots >= 3 ? "true" : "false", cool_decl,
-		         carry_decl.c_str(), plan.intervals.empty() ? "" : "cool[0] = 0u;", carry ? " lb = -__builtin_inff(); carry = false;" : "");
-		s += line;
-		if (param) s += "\tparam_ptr K = nullptr;\n";
-		if (last_id) {
-			/* the record's two slots in the order of the ids: rec0 the object of the lower id, which a tie goes to */
-			const uint32_t ida = roots[0].id, idb = roots[1].id;
-			snprintf(line, sizeof line, "\tstatic constexpr bool ID_FROM_LAST = true;\n"
-			         "\t__device__ __forceinline__ u32 id_of(float rec0, float rec1) const { return rec0 == vmin_(rec0, rec1) ? %uu : %uu; }\n",
-			         ida < idb ? ida : idb, ida < idb ? idb : ida);
-			s += line;
-		}
-	}
-	/* The body twice where it is inlined: eval() — distance and object id — for the primary march and the normal taps, and
-	 * eval_dist() — the distance alone — for the shadow marches, which never look at the id.  There an object joins the running
-	 * minimum with ONE v_min_f32 instead of the compare(s) and selects of the strict-'<' / lower-id-wins rule: the two agree on the
-	 * value except for the sign of a zero (two objects at distance -0 and +0 of the same point), and a shadow march's results —
-	 * its factor maxf(res, 0) and its step count — are the same for s = -0 and s = +0: t + s, 50 s / t compared with 0, and
-	 * maxf(+-0, 0) = +0 all are (lol_kernel.h, soft_shadow).  A NaN value is dropped by either form.
-	 * ... and once more, FIRST, for an ID_FROM_LAST scene: eval_rec(), eval_dist() plus the record of each object's value (last_id above). */
-	auto rec_slot = [&](size_t oi) { return roots[plan.order[oi]].id > roots[plan.order[oi ^ 1]].id ? 1 : 0; };      /* (two objects) */
-	for (int turn = 0; turn < (out_of_line ? 1 : last_id ? 3 : 2); turn++) {
-	const int pass = last_id ? (turn + 2) % 3 : turn;                          /* (eval_rec comes first; eval and eval_dist stay where they were) */
-	const bool rec = pass == 2, dist_only = pass >= 1;
-	if (!out_of_line)
-		s += rec       ? "\t__device__ __forceinline__ void eval_rec(V3 p, float& best, float& rec0, float& rec1) {\n"
-		   : dist_only ? "\t__device__ __forceinline__ void eval_dist(V3 p, float& best) {\n"
-		               : "\t__device__ __forceinline__ void eval(V3 p, float& best, u32& best_id) {\n";
-	s += dist_only ? "\t\tbest = __builtin_inff();\n" : "\t\tbest = __builtin_inff(); best_id = 0u;\n";
-	if (rec)                            /* an object behind a test that lets the wave skip it is recorded as +inf: it strictly loses */
-		for (size_t oi = 0; oi < plan.order.size(); oi++)
-			for (const CullInterval& iv : plan.intervals)
-				if (iv.begin <= oi && oi < iv.end) {
-					snprintf(line, sizeof line, "\t\trec%d = __builtin_inff();\n", rec_slot(oi));
-					s += line;
-					break;
-				}
-	int t = 0, n_tests = 0;
-	/* After a test that did not allow the skip, the next `cooldown` evaluations of this SDF object do not test
-	 * again (a ray that is near the object now is near it on its next steps too): the test costs 11 VALU
-	 * instructions, and where it keeps failing that is pure overhead.  Never testing is always allowed — the
-	 * test only ever permits a skip — so this changes no result.  `cool` lives in the Sdf struct, wave-uniform. */
-	const int cooldown = 3;
-	/* spheres of radius >= 2^-20 carry no range tracker where the device has shown the fast root harmless below its proven domain
-	 * (lol_kernel.h, sd_sphere_fast_nr): a NaN reaches the object's value instead, which is looked at once */
-	const bool nan_flag = fast && fast->sqrt_tiny_ok;
-	bool object_has_nr = false;
-	/* LOL_GPU_SAT_CULL_MIN_PRIMS: `a` operands of a smooth union with at least this many primitives get a saturation-
-	 * culling test (see emit_node below); 0 = none.  Measured (tools/tree_scene_ab.py, balanced trees of spheres at
-	 * 1080p, profiles/r2_tree_scene_ab.jsonl): the 17-instruction test pays from a few dozen primitives — 128 spheres
-	 * 232 -> 405 Mpixels/s, 256 spheres 127 -> 166 at 32 (375 / 157 at 16); with a test on every operand scene4
-	 * loses 14 %, a 32-sphere tree 30 %. */
-	int sat_cull_min_prims = 32;
-	if (const char* e = tuning_env("LOL_GPU_SAT_CULL_MIN_PRIMS")) sat_cull_min_prims = atoi(e);
-	/* one test = one bounding sphere; a run guarded by several (an object's two cluster spheres) is skipped where ALL pass */
-	auto open_test = [&](const CullInterval& iv, bool with_cooldown) {
-		const std::vector<CullTest> one = { iv.test };
-		const std::vector<CullTest>& tests = iv.both.empty() ? one : iv.both;
-		std::string decl, votes;
-		const int k0 = n_tests;
-		for (const CullTest& ct : tests) {
-			const int k = n_tests++;
-			snprintf(line, sizeof line,
-			         "\t\t  const float cx%d = p.x - %s, cy%d = p.y - %s, cz%d = p.z - %s;\n"
-			         "\t\t  const float cl%d = (cx%d * cx%d + cy%d * cy%d) + cz%d * cz%d;\n"
-			         "\t\t  const float cu%d = (best + %s) * %s;\n",
-			         k, fbits(ct.c[0]).c_str(), k, fbits(ct.c[1]).c_str(), k, fbits(ct.c[2]).c_str(),
-			         k, k, k, k, k, k, k, k, fbits(ct.rm).c_str(), fbits(ct.k).c_str());
-			decl += line;
-			snprintf(line, sizeof line, "%svote(!(cl%d > cu%d * cu%d)) | vote(!(cu%d > 0.f))", votes.empty() ? "" : " | ", k, k, k, k);
-			votes += line;
-		}
-		if (with_cooldown && carry) {
-			/* the carried bound first (one fma and one compare); where a lane fails it, the full test — which, passed by the whole
-			 * wave on a ray that may carry, sets lb anew (one v_sqrt per sphere).  A failed full test leaves lb as it is: still a
-			 * bound, only an older one. */
-			const CarryConsts cc = carry_constants(tests);
-			const float ctc = vcarry && vc.ctc > cc.ctc ? vc.ctc : cc.ctc;      /* one left-hand side for both bounds: the more conservative */
-			snprintf(line, sizeof line, vcarry ? "\t\t{ bool need%d = true;\n\t\t  {\n"
-			         "\t\t  if (vote(!(__builtin_fmaf(rt, %s, __builtin_fabsf(best)) < lb)) == 0) need%d = false; else if (cool[0] == 0u) {\n"
-			         : "\t\t{ bool need%d = true;\n\t\t  if (cool[0] == 0u) {\n"
-			         "\t\t  if (vote(!(__builtin_fmaf(rt, %s, __builtin_fabsf(best)) < lb)) == 0) need%d = false; else {\n",
-			         k0, fbits(ctc).c_str(), k0);
-			s += line;
-			s += decl;
-			snprintf(line, sizeof line, "\t\t  need%d = ((", k0);
-			s += line;
-			s += votes;
-			snprintf(line, sizeof line, ")) != 0;\n\t\t  if (need%d) cool[0] = %du;\n\t\t  else if (carry) {\n", k0, cooldown);
-			s += line;
-			for (size_t j = 0; j < tests.size(); j++) {
-				snprintf(line, sizeof line, j ? "\t\t    lm = vmin_(__builtin_fmaf(__builtin_amdgcn_sqrtf(cl%d), %s, %s), lm);\n"
-				                              : "\t\t    float lm = __builtin_fmaf(__builtin_amdgcn_sqrtf(cl%d), %s, %s);\n",
-				         k0 + (int)j, fbits(cc.a[j]).c_str(), fbits(cc.b[j]).c_str());
-				s += line;
-			}
-			snprintf(line, sizeof line, vcarry ? "\t\t    const float lg = __builtin_fmaf(rt, %s, lm);\n\t\t    lb = maxf_(__builtin_fmaf(__builtin_fabsf(lg), -0x1p-20f, lg), lb);\n"
-			         "\t\t  }\n\t\t  } else cool[0]--; }\n\t\t  if (need%d) {\n"
-			         : "\t\t    const float lg = __builtin_fmaf(rt, %s, lm);\n\t\t    lb = __builtin_fmaf(__builtin_fabsf(lg), -0x1p-20f, lg);\n"
-			         "\t\t  }\n\t\t  } } else cool[0]--;\n\t\t  if (need%d) {\n", fbits(cc.ctt).c_str(), k0);
-			s += line;
-		} else if (with_cooldown) {
-			snprintf(line, sizeof line, "\t\t{ bool need%d = true;\n\t\t  if (cool[0] == 0u) {\n", k0);
-			s += line;
-			s += decl;
-			snprintf(line, sizeof line, "\t\t  need%d = ((", k0);
-			s += line;
-			s += votes;
-			snprintf(line, sizeof line, ")) != 0;\n\t\t  if (need%d) cool[0] = %du;\n\t\t  } else cool[0]--;\n\t\t  if (need%d) {\n", k0, cooldown, k0);
-			s += line;
-		} else {
-			s += "\t\t{\n";
-			s += decl;
-			s += "\t\t  if (((";
-			s += votes;
-			s += ")) != 0) {\n";
-		}
-	};
-	uint32_t max_id_seen = 0;
-	size_t next_iv = 0;
-	std::vector<uint32_t> runs_ending(plan.order.size() + 1, 0);          /* how many runs end after object oi - 1 */
-	for (const CullInterval& iv : plan.intervals) runs_ending[iv.end]++;
-	for (size_t oi = 0; oi < plan.order.size(); oi++) {
-		const RootBound& R = roots[plan.order[oi]];
-		while (next_iv < plan.intervals.size() && plan.intervals[next_iv].begin == oi) {      /* outer runs first */
-			open_test(plan.intervals[next_iv], next_iv == 0);
-			next_iv++;
-		}
-		/* the object's expression tree from its post-order ops (child `a` / `b` = the operands of sminf(a, b, k)) */
-		struct Node { uint32_t op; int a, b; Sphere bound; uint32_t prims; bool fon = false; };      /* fon: the fast SDF's value of this node is finite or NaN */
-		std::vector<Node> nodes;
-		{
-			std::vector<int> st;
-			auto sane = [](double v) { return v - v == 0.0 && fabs(v) < 1e15; };
-			for (uint32_t i = R.first; i < R.top; i++) {
-				const lol_op& o = P.ops[i];
-				Node n{ i, -1, -1, { false, { 0, 0, 0 }, 0, 1 }, 1 };
-				if (o.op == LOL_OP_SPHERE) {
-					n.fon = fsqrt && nan_flag && o.f[3] >= 0x1p-20f && std::isfinite(o.f[3]);      /* sd_sphere_fast_nr (emit_node) */
-					n.bound = { sane(o.f[0]) && sane(o.f[1]) && sane(o.f[2]) && sane(o.f[3]), { o.f[0], o.f[1], o.f[2] }, o.f[3] > 0 ? (double)o.f[3] : 0.0, 1 };
-				} else if (o.op == LOL_OP_RBOX) {
-					bool ok = true;
-					for (int j = 0; j < 7; j++) ok = ok && sane(o.f[j]);
-					ok = ok && o.f[3] >= 0 && o.f[4] >= 0 && o.f[5] >= 0 && o.f[6] >= 0;
-					const double hb = sqrt((double)o.f[3] * o.f[3] + (double)o.f[4] * o.f[4] + (double)o.f[5] * o.f[5]);
-					n.bound = { ok, { o.f[0], o.f[1], o.f[2] }, hb * (1.0 + 1e-12) + o.f[6], 1 };
-				} else if (o.op == LOL_OP_SMIN || o.op == LOL_OP_SMIN_R) {
-					const int top = st.back(); st.pop_back();
-					const int under = st.back(); st.pop_back();
-					n.a = o.op == LOL_OP_SMIN ? under : top;
-					n.b = o.op == LOL_OP_SMIN ? top : under;
-					n.bound = enclose(nodes[n.a].bound, nodes[n.b].bound);
-					if (!(sane(o.f[0]) && o.f[0] > 0)) n.bound.ok = false;
-					n.bound.r += 0.25 * (double)o.f[0];
-					n.bound.levels++;
-					if (!sane(n.bound.r)) n.bound.ok = false;
-					n.prims = nodes[n.a].prims + nodes[n.b].prims;
-					n.fon = nodes[n.a].fon && nodes[n.b].fon && fast && fast->has(o.f[0]);
-				}
-				st.push_back((int)nodes.size());
-				nodes.push_back(n);
-			}
-		}
-		/* Saturation culling inside a smooth union (fast struct only, proven k > 0): sminf(a, b, k) is EXACTLY
-		 * b - dlt*0.f = b + 0.f when dlt = b - a <= -ks (sminf_fastdiv_sat), so operand `a` need not be evaluated
-		 * where it is provably that much greater than b.  b is evaluated first; with sb = fl(b + ks) the bounding-
-		 * sphere test of the top-level culling (best := sb) gives a > sb for the binary32 value of `a`, hence
-		 * dlt = fl(b - a) <= fl(b - sb) =: sw by the monotonicity of rounding, and sw <= -ks is checked directly;
-		 * |p - C|^2 < 2^120 keeps every primitive of `a` (all within R < 10^15 of C) finite, so dlt is finite and
-		 * dlt*0.f = -0.  A NaN or infinite b fails the comparisons.  Per wave, like every other skip. */
-		std::function<int(int)> emit_node = [&](int ni) -> int {
-			const Node& n = nodes[ni];
-			const lol_op& o = P.ops[n.op];
-			switch (o.op) {
-			case LOL_OP_SPHERE:
-				if (fsqrt && nan_flag && o.f[3] >= 0x1p-20f && std::isfinite(o.f[3])) {      /* sd_sphere_fast_nr: no range tracker */
-					snprintf(line, sizeof line, "\t\tconst float t%d = sd_sphere_fast_nr<%d>(p, %s, %s, %s, %s);\n", t, fsqrt,
-					         fbits(o.f[0]).c_str(), fbits(o.f[1]).c_str(), fbits(o.f[2]).c_str(), fbits(o.f[3]).c_str());
-					object_has_nr = true;
-				} else
-				snprintf(line, sizeof line, "\t\tconst float t%d = sd_sphere%s(p, %s, %s, %s, %s%s);\n", t, fs,
-				         num(n.op, 0).c_str(), num(n.op, 1).c_str(), num(n.op, 2).c_str(), num(n.op, 3).c_str(),
-				         fsqrt ? ", rg" : "");
-				s += line; return t++;
-			case LOL_OP_RBOX:
-				snprintf(line, sizeof line, "\t\tconst float t%d = sd_round_box%s(p, %s, %s, %s, %s, %s, %s, %s%s);\n", t,
-				         fs,
-				         num(n.op, 0).c_str(), num(n.op, 1).c_str(), num(n.op, 2).c_str(), num(n.op, 3).c_str(),
-				         num(n.op, 4).c_str(), num(n.op, 5).c_str(), num(n.op, 6).c_str(), fsqrt ? ", rg" : "");
-				s += line; return t++;
-			case LOL_OP_PLANE:
-				snprintf(line, sizeof line, "\t\tconst float t%d = p.y - %s;\n", t, num(n.op, 0).c_str());
-				s += line; return t++;
-			default: break;
-			}
-			/* LOL_OP_SMIN / LOL_OP_SMIN_R */
-			const float ks = smooth_sat_threshold(o.f[0]);
-			const bool proven = fast && fast->has(o.f[0]);
-			/* without v_div_fixup where that is proven too; such an object's value is then voted on for NaN (an infinite
-			 * operand difference — lol_kernel.h, smin_h_fast) like one with spheres that carry no range tracker */
-			const char* fx = proven && fast->has_nf(o.f[0]) ? "<false>" : "";
-			if (fx[0]) object_has_nr = true;
-			/* the arithmetic shortcut only where the SDF is inlined: in the out-of-line function its four-way branching
-			 * costs more than it saves (504-op chain: 100 -> 42 Mpixels/s) */
-			const bool sat_arith = !out_of_line && ks > 0.f;
-			const std::string kk = num(n.op, 0), k2 = fbits(2.0f * o.f[0]), hrk = fbits(0.5f * (1.0f / o.f[0])), kss = fbits(ks);
-			if (proven && ks > 0.f && sat_cull_min_prims > 0 && nodes[n.a].bound.ok && nodes[n.a].prims >= (uint32_t)sat_cull_min_prims) {
-				const int b = emit_node(n.b);
-				const CullTest ct = make_test(nodes[n.a].bound);
-				const int r = t++, q = n_tests++;
-				snprintf(line, sizeof line,
-				         "\t\tfloat t%d;\n"
-				         "\t\t{ const float sb%d = t%d + %s, sw%d = t%d - sb%d;\n"
-				         "\t\t  const float sx%d = p.x - %s, sy%d = p.y - %s, sz%d = p.z - %s;\n"
-				         "\t\t  const float sl%d = (sx%d * sx%d + sy%d * sy%d) + sz%d * sz%d;\n"
-				         "\t\t  const float su%d = (sb%d + %s) * %s;\n"
-				         "\t\t  if ((vote(!(sl%d > su%d * su%d)) | vote(!(su%d > 0.f)) | vote(!(sw%d <= -%s)) | vote(!(sl%d < 0x1p120f))) != 0) {\n",
-				         r, q, b, kss.c_str(), q, b, q,
-				         q, fbits(ct.c[0]).c_str(), q, fbits(ct.c[1]).c_str(), q, fbits(ct.c[2]).c_str(),
-				         q, q, q, q, q, q, q,
-				         q, q, fbits(ct.rm).c_str(), fbits(ct.k).c_str(),
-				         q, q, q, q, q, kss.c_str(), q);
-				s += line;
-				const int a = emit_node(n.a);
-				if (sat_arith)
-					snprintf(line, sizeof line, "\t\t  t%d = sminf_fastdiv_sat%s(t%d, t%d, %s, %s, %s, %s);\n\t\t  } else t%d = t%d + 0.f;\n\t\t}\n",
-					         r, fx, a, b, kk.c_str(), k2.c_str(), hrk.c_str(), kss.c_str(), r, b);
-				else
-					snprintf(line, sizeof line, "\t\t  t%d = sminf_fastdiv%s(t%d, t%d, %s, %s, %s);\n\t\t  } else t%d = t%d + 0.f;\n\t\t}\n",
-					         r, fx, a, b, kk.c_str(), k2.c_str(), hrk.c_str(), r, b);
-				s += line;
-				return r;
-			}
-			/* operands in program order (a flattened chain keeps its deep operand first and its operand stack shallow) */
-			const bool a_first = o.op == LOL_OP_SMIN;
-			const int first = emit_node(a_first ? n.a : n.b), second = emit_node(a_first ? n.b : n.a);
-			const int a = a_first ? first : second, b = a_first ? second : first;
-			if (proven && sat_arith)
-				snprintf(line, sizeof line, "\t\tconst float t%d = sminf_fastdiv_sat%s%s(t%d, t%d, %s, %s, %s, %s);\n", t,
-				         nodes[n.a].fon && nodes[n.b].fon ? "2" : "", fx, a, b, kk.c_str(), k2.c_str(), hrk.c_str(), kss.c_str());
-			else if (proven)
-				snprintf(line, sizeof line, "\t\tconst float t%d = sminf_fastdiv%s(t%d, t%d, %s, %s, %s);\n", t, fx, a, b, kk.c_str(), k2.c_str(), hrk.c_str());
-			else
-				snprintf(line, sizeof line, "\t\tconst float t%d = sminf_(t%d, t%d, %s);\n", t, a, b, kk.c_str());
-			s += line; return t++;
-		};
-		object_has_nr = false;
-		const int d = emit_node((int)nodes.size() - 1);
-		if (object_has_nr || rec) {          /* a NaN from a sphere without range tracker reaches the object's value: 0 * NaN (or inf) = NaN */
-			snprintf(line, sizeof line, "\t\tnanacc = __builtin_fmaf(t%d, 0.f, nanacc);\n", d);      /* (... and every value the record takes) */
-			s += line;
-		}
-		if (rec) {
-			snprintf(line, sizeof line, "\t\trec%d = t%d;\n", rec_slot(oi), d);
-			s += line;
-		}
-		if (dist_only)
-			snprintf(line, sizeof line, "\t\tbest = vmin_(t%d, best);\n", d);
-		else if (R.id < max_id_seen)      /* evaluated after an object that follows it in the file: ties go to the lower id */
-			snprintf(line, sizeof line, "\t\tif (t%d < best || (t%d == best && best_id > %uu)) { best = t%d; best_id = %uu; }\n", d, d, R.id, d, R.id);
-		else
-			snprintf(line, sizeof line, "\t\tif (t%d < best) { best = t%d; best_id = %uu; }\n", d, d, R.id);
-		s += line;
-		if (R.id > max_id_seen) max_id_seen = R.id;
-		if (vcarry && oi == plan.intervals[0].begin) {      /* the value just computed bounds the object further along the ray (value_carry_constants) */
-			snprintf(line, sizeof line, "\t\tif (carry) {\n\t\t  const float vg = __builtin_fmaf(rt, %s, __builtin_fmaf(__builtin_fabsf(t%d), -%s, t%d) - %s);\n"
-			         "\t\t  lb = maxf_(__builtin_fmaf(__builtin_fabsf(vg), -0x1p-20f, vg), lb);\n\t\t}\n",
-			         fbits(vc.ctt).c_str(), d, fbits(vc.dl).c_str(), d, fbits(vc.ef).c_str());
-			s += line;
-		}
-		for (uint32_t k = 0; k < runs_ending[oi + 1]; k++) s += "\t\t} }\n";               /* every run that ends here */
-	}
-	if (!out_of_line) s += "\t}\n";
-	}      /* pass */
-	if (out_of_line) {
-		s += "\t\treturn { best, best_id, rg.lo, rg.hi, nanacc };\n}\n";
-		snprintf(line, sizeof line, "struct %s {\n\tstatic constexpr bool ASSUME_SETTLED = %s;\n\tstatic constexpr bool ASK_ID_ONCE = false;\n\tRange rg;\n\tfloat nanacc = 0.f;\n"
-		         "\t__device__ __forceinline__ void loop_done() {}\n"
-		         "\t__device__ __forceinline__ void eval(V3 p, float& best, u32& best_id) {\n"
-		         "\t\tconst SdfOut o = %s_fn(p.x, p.y, p.z, rg.lo, rg.hi);\n"
-		         "\t\tbest = o.best; best_id = o.id; rg.lo = o.lo; rg.hi = o.hi; nanacc += o.nanacc;\n\t}\n"
-		         "\t__device__ __forceinline__ void eval_dist(V3 p, float& best) { u32 unused; eval(p, best, unused); }\n", name, fast ? "true" : "false", name);
-		s += line;
-	}
-	/* the arithmetic of the shading around the loops that the device has proven for the fast pipeline (lol_kernel.h, ShadeMath); a
-	 * struct without it — the plain SDF, LOL_GPU_SHADE_MATH=0 — is the text it was */
-	if (fast && fast->shade_root) {
-		snprintf(line, sizeof line, "\tstruct Shade { static constexpr int ROOT = %d, RCP = %d; };\n", fast->shade_root, fast->shade_rcp);
-		s += line;
-	}
-	s += "};\n";
+              const std::vector<RootBound>& roots, const CullPlan& plan, bool param = false) {
+	SdfEmitter em{ s, P, name, fast, roots, plan, decide_form(P, fast, out_of_line, param, roots, plan), walk_plan(roots, plan) };
+	em.run();
 }
 bool spec_out_of_line(const lol_program& P, int form) {
 	if (form == SPEC_OUT_OF_LINE) return true;
@@ -866,6 +973,17 @@ bool spec_out_of_line(const lol_program& P, int form) {
 	uint32_t limit = LOL_SPEC_INLINE_MAX_OPS;
 	if (const char* e = tuning_env("LOL_GPU_SPEC_INLINE_MAX")) limit = (uint32_t)strtoul(e, nullptr, 10);
 	return P.n_ops > limit;
+}
+
+/* Register budget, as the attribute of every kernel of a scene's modules.  The SDF of one object is a long dependent chain (every
+ * smooth min waits for the one below it) fed by independent primitives, and the kernel is compiled with the max-ILP scheduling
+ * strategy (compile_source): the more registers a wave may use, the more primitives it keeps in flight.  Measured on
+ * MI355X (profiles/r2_large_scene_ab.jsonl): with max-ILP, scene4 (12 ops) is fastest when 8 waves per SIMD are
+ * kept (64 VGPRs: 4640 vs 4530 Mpixels/s unconstrained), a 44-op chain at >= 6, chains of 142+ ops at >= 4
+ * (128 VGPRs: 427 vs 400 Mpixels/s at 8). */
+static std::string register_budget(const lol_program& P) {
+	const int waves_lo = P.n_ops <= 32 ? 8 : P.n_ops <= 96 ? 6 : 4, waves_hi = 8;
+	return " __attribute__((amdgpu_waves_per_eu(" + std::to_string(waves_lo) + ", " + std::to_string(waves_hi) + ")))";
 }
 
 std::string generate_source(const lol_program& P, const FastPaths* fast, bool cull, int form = SPEC_BY_SIZE, ModuleKernels carries = {}) {
@@ -878,18 +996,11 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 	auto include = [](ModuleSwitch sw) { return std::string("#include \"") + MODULE_SWITCHES[sw].header + "\"\n"; };
 	s += include(SWITCH_NONE);
 	s += "namespace lol {\n";
-	/* Register budget.  The SDF of one object is a long dependent chain (every smooth min waits for the one below
-	 * it) fed by independent primitives, and the kernel is compiled with the max-ILP scheduling strategy
-	 * (compile_spec): the more registers a wave may use, the more primitives it keeps in flight.  Measured on
-	 * MI355X (profiles/r2_large_scene_ab.jsonl): with max-ILP, scene4 (12 ops) is fastest when 8 waves per SIMD are
-	 * kept (64 VGPRs: 4640 vs 4530 Mpixels/s unconstrained), a 44-op chain at >= 6, chains of 142+ ops at >= 4
-	 * (128 VGPRs: 427 vs 400 Mpixels/s at 8). */
-	const int waves_lo = P.n_ops <= 32 ? 8 : P.n_ops <= 96 ? 6 : 4, waves_hi = 8;
-	const std::string occupancy = " __attribute__((amdgpu_waves_per_eu(" + std::to_string(waves_lo) + ", " + std::to_string(waves_hi) + ")))";
+	const std::string occupancy = register_budget(P);
 	if (ool) s += "struct SdfOut { float best; u32 id; u32 lo, hi; float nanacc; };\n";
-	emit_sdf(s, P, "SpecSdfExact", nullptr, ool, roots, plan, occupancy);
+	emit_sdf(s, P, "SpecSdfExact", nullptr, ool, roots, plan);
 	const bool any_fast = fast && (fast->sqrt_kind || !fast->div_ok.empty());
-	if (any_fast) emit_sdf(s, P, "SpecSdfFast", fast, ool, roots, plan, occupancy);
+	if (any_fast) emit_sdf(s, P, "SpecSdfFast", fast, ool, roots, plan);
 	s += "}  // namespace lol\n";
 	/* where lights / materials are read from is a property of the scene too (lol_kernel.h, TABLES_LDS_MAX_DWORDS) */
 	const bool tables_global = !lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots);
@@ -1046,8 +1157,8 @@ std::string generate_source(const lol_program& P, const FastPaths* fast, bool cu
 
 using lol_key::fnv64;
 static std::string hex16(unsigned long long h) {
-	char b[20];
-	snprintf(b, sizeof b, "%016llx", h);
+	std::string b;
+	appendf(b, "%016llx", h);
 	return b;
 }
 std::string fnv_hex(const void* data, size_t n) { return hex16(fnv64(data, n)); }
@@ -1075,9 +1186,8 @@ std::string disk_cache_path(const std::string& key) {
 		if (i == dir.size() || dir[i] == '/') (void)mkdir(dir.substr(0, i).c_str(), 0700);
 	unsigned long long h = 0xcbf29ce484222325ull;         /* FNV-1a of the key names the file */
 	for (unsigned char c : key) { h ^= c; h *= 0x100000001b3ull; }
-	char name[40];
-	snprintf(name, sizeof name, "/%016llx.co", h);
-	return dir + name;
+	appendf(dir, "/%016llx.co", h);
+	return dir;
 }
 
 /* GPU code is only ever loaded from a file this user wrote: the file and its directory must belong to the effective
@@ -1109,9 +1219,8 @@ bool disk_cache_load(const std::string& key, std::vector<char>& code) {
 void disk_cache_store(const std::string& key, const std::vector<char>& code) {
 	const std::string path = disk_cache_path(key);
 	if (path.empty()) return;
-	char tmp[64];
-	snprintf(tmp, sizeof tmp, ".%ld.tmp", (long)getpid());
-	const std::string t = path + tmp;
+	std::string t = path;
+	appendf(t, ".%ld.tmp", (long)getpid());
 	FILE* f = fopen(t.c_str(), "wb");
 	if (!f) return;
 	(void)fchmod(fileno(f), 0600);
@@ -1326,9 +1435,8 @@ std::string generate_structure_source(const lol_program& P, bool samples) {
 	std::string s = samples ? "#include \"lol_kernel_scenes_aa.h\"\nnamespace lol {\n" : "#include \"lol_kernel_scenes.h\"\nnamespace lol {\n";
 	const std::vector<RootBound> roots = analyse_roots(P);
 	const CullPlan plan = plan_culling(roots, false);        /* file order, no test */
-	const int waves_lo = P.n_ops <= 32 ? 8 : P.n_ops <= 96 ? 6 : 4, waves_hi = 8;      /* (generate_source: the register budget) */
-	const std::string occupancy = " __attribute__((amdgpu_waves_per_eu(" + std::to_string(waves_lo) + ", " + std::to_string(waves_hi) + ")))";
-	emit_sdf(s, P, "ParamSdf", nullptr, false, roots, plan, occupancy, true);
+	const std::string occupancy = register_budget(P);
+	emit_sdf(s, P, "ParamSdf", nullptr, false, roots, plan, true);
 	s += "}  // namespace lol\n";
 	const bool tables_global = !lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots);
 	const std::string tg = tables_global ? "true" : "false";
@@ -1361,6 +1469,33 @@ bool compile_structure(const lol_program& P, const std::string& arch, std::vecto
 	const std::string src = generate_structure_source(P, samples);
 	if (src_out) *src_out = src;
 	return compile_source(src, false, samples ? 2 : 1, arch, code, log);
+}
+
+/* What the offline entry points share: `compile(code, log, src)` runs under g_rtc_mutex on the large-stack thread, like every run of
+ * the scene compiler (BigStackThread); the log is copied out; `<out_base>.hip` is written whether or not the compile succeeded,
+ * `<out_base>.co` when it did. */
+template <class Compile>
+static int compile_offline(const char* out_base, char* log, size_t logcap, Compile compile) {
+	std::vector<char> code;
+	std::string lg, src;
+	bool ok = false;
+	{
+		BigStackThread th;
+		auto work = [&]() {
+			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile(code, lg, src); }
+			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
+		};
+		bool started = false;
+		try { started = th.start(work); } catch (...) { started = false; }
+		if (started) th.join(); else work();
+	}
+	if (log && logcap) snprintf(log, logcap, "%s", lg.c_str());
+	if (out_base && out_base[0]) {
+		std::string base = out_base;
+		if (FILE* f = fopen((base + ".hip").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
+		if (ok) if (FILE* f = fopen((base + ".co").c_str(), "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
+	}
+	return ok ? LOL_GPU_OK : LOL_GPU_ERR_UNSUPPORTED;
 }
 
 #pragma GCC visibility pop
@@ -1414,8 +1549,6 @@ int lol_gpu_compile_offline_module(const lol_program* prog, const char* arch, co
 	if (!prog || !arch || switches > ALL_SWITCHES) return LOL_GPU_ERR_ARG;
 	if (form != SPEC_BY_SIZE && form != SPEC_OUT_OF_LINE && form != SPEC_INLINE) return LOL_GPU_ERR_ARG;
 	const ModuleKernels carries = { switches };
-	std::vector<char> code;
-	std::string lg, src;
 	FastPaths fast;
 	if (assume_fast) {                 /* ISA inspection only: pretend every shortcut was proven */
 		fast.sqrt_kind = assume_fast >= 1 && assume_fast <= 3 ? 4 - assume_fast : 3;   /* 1 → sqrt_r2, 2 → sqrt_gs, 3 → sqrt_pm */
@@ -1426,51 +1559,18 @@ int lol_gpu_compile_offline_module(const lol_program* prog, const char* arch, co
 			if ((prog->ops[i].op == LOL_OP_SMIN || prog->ops[i].op == LOL_OP_SMIN_R) && !fast.has(prog->ops[i].f[0]))
 				{ fast.div_ok.push_back(prog->ops[i].f[0]); fast.div_nf_ok.push_back(prog->ops[i].f[0]); }
 	}
-	bool ok = false;
-	{
-		/* on the large-stack thread, like every run of the scene compiler (BigStackThread) */
-		BigStackThread th;
-		auto work = [&]() {
-			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), form, carries); }
-			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
-		};
-		bool started = false;
-		try { started = th.start(work); } catch (...) { started = false; }
-		if (started) th.join(); else work();
-	}
-	if (log && logcap) snprintf(log, logcap, "%s", lg.c_str());
-	if (out_base && out_base[0]) {
-		std::string base = out_base;
-		if (FILE* f = fopen((base + ".hip").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
-		if (ok) if (FILE* f = fopen((base + ".co").c_str(), "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
-	}
-	return ok ? LOL_GPU_OK : LOL_GPU_ERR_UNSUPPORTED;
+	return compile_offline(out_base, log, logcap, [&](std::vector<char>& code, std::string& lg, std::string& src) {
+		return compile_spec(*prog, &fast, arch, code, lg, &src, culling_enabled(1), form, carries);
+	});
 }
 
 /* ... and the structure module of `prog` (lol_gpu_set_scene_views; `samples`: lol_gpu_set_scene_view_samples): `<out_base>.hip` and
  * `<out_base>.co`; lol_gpu_diag.h */
 static int compile_offline_structure(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap, bool samples) {
 	if (!prog || !arch || prog->n_ops > LOL_MAX_OPS || (prog->n_ops && !prog->ops)) return LOL_GPU_ERR_ARG;
-	std::vector<char> code;
-	std::string lg, src;
-	bool ok = false;
-	{
-		BigStackThread th;
-		auto work = [&]() {
-			try { std::lock_guard<std::mutex> rtc(g_rtc_mutex); ok = compile_structure(*prog, arch, code, lg, &src, samples); }
-			catch (...) { ok = false; lg = "the scene compiler ran out of memory"; }
-		};
-		bool started = false;
-		try { started = th.start(work); } catch (...) { started = false; }
-		if (started) th.join(); else work();
-	}
-	if (log && logcap) snprintf(log, logcap, "%s", lg.c_str());
-	if (out_base && out_base[0]) {
-		std::string base = out_base;
-		if (FILE* f = fopen((base + ".hip").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
-		if (ok) if (FILE* f = fopen((base + ".co").c_str(), "wb")) { fwrite(code.data(), 1, code.size(), f); fclose(f); }
-	}
-	return ok ? LOL_GPU_OK : LOL_GPU_ERR_UNSUPPORTED;
+	return compile_offline(out_base, log, logcap, [&](std::vector<char>& code, std::string& lg, std::string& src) {
+		return compile_structure(*prog, arch, code, lg, &src, samples);
+	});
 }
 int lol_gpu_compile_offline_scene_views(const lol_program* prog, const char* arch, const char* out_base, char* log, size_t logcap) {
 	return compile_offline_structure(prog, arch, out_base, log, logcap, false);
