@@ -39,6 +39,13 @@ int lol_gpu_multi_testing_force_copier_threads(lol_gpu_multi* m, int enable);
  * s_setpc_b64 s[30:31], LLVM's long-branch register bug: a function that never returns — 0 when not.  No device needed. */
 int lol_gpu_testing_has_return_clobbering_branch(const void* code, size_t n_bytes);
 
+/* What the pixels of a repeated view are dealt to waves by (lol_gpu_set_tile_order, LOL_GPU_TILES_LPT): the table its recording
+ * frame — the second frame under one camera — wrote, one entry per pixel, `w` per local row of the part: the march steps plus the
+ * shadow steps the pixel's lane RAN (saturating at 65535).  lol_gpu_debug reports the reference's counts, which also hold the turns
+ * a stationary shadow ray left out; this is the only place the two can be told apart.  Waits for the device.  n_pixels must be that
+ * frame's w x rows; LOL_GPU_ERR_ARG when the last frame went through no table or the size is another. */
+int lol_gpu_testing_pixel_cost(lol_gpu* ctx, unsigned short* out, size_t n_pixels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -460,6 +460,7 @@ struct lol_gpu {
 		uint32_t* d_lanes = nullptr;         /* the pixel table: 64 entries per wave slot ("pixels dealt by cost") */
 		unsigned short* d_pixel_cost = nullptr;   /* what every pixel of the view's first frame cost */
 		size_t   lanes_cap = 0, pixels_cap = 0;
+		size_t   pixels = 0;                 /* pixels of the frame that last recorded into d_pixel_cost (lol_gpu_testing_pixel_cost) */
 		size_t   cap = 0;                    /* tiles the buffers hold */
 		int      cur = 0;
 		unsigned frames = 0, sorts = 0;      /* frames launched with this key; sorts done */

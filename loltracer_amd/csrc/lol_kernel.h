@@ -108,7 +108,8 @@ struct Launch {
 	/* FLAG_TILE_TABLE: tile_order[b] = the wave slot the b-th block of the launch shades; tile_cost[b] (may be NULL) receives
 	 * what that block's wave cost: how long it ran (store_pixel).  lane_pixels[64 * slot + lane] = that lane's pixel: column |
 	 * local row << 16 (| LANE_PADDING for a lane that only fills up its wave: it shades the pixel it names and stores nothing).
-	 * pixel_cost (may be NULL) receives every pixel's step count, w per local row: what the pixels are dealt by. */
+	 * pixel_cost (may be NULL) receives the steps every pixel's lane RAN (march + shadow turns, without the turns a stationary
+	 * shadow ray skipped: soft_shadow), w per local row: what the pixels are dealt by. */
 	const u32* tile_order;
 	u32*   tile_cost;
 	u32    tile_stride;          /* both tables are indexed by tile_slot(block): ceil(blocks / 8) */
@@ -972,8 +973,19 @@ __device__ __forceinline__ Marched march(Sdf& sdf, V3 ro, V3 rd, int max_steps, 
  * `t == 0` names the case afterwards (a t that RETURNED to 0 did so on a step with 50 s / t = -50: the factor is 0 as well).
  * Round 6: +0.5 % (profiles/r6_ab1.txt).
  */
+/*
+ * The stationary exit (every Sdf, `settled` or not).  A turn reads (t, res) and writes (fl(t + s), min(res, 50 s / t)) with
+ * s = sdf(fl(ro + dir t)): a function of (t, res) alone.  Once fl(t + s) == t bit for bit (s below half an ulp of t: a ray that
+ * converges onto a surface from outside; s == +-0) the next turn reads the t it read before and a res' = min(res, v) for which
+ * min(res', v) == res' again, so it writes (t, res') once more, and so does every turn up to the 128th: the reference's result is
+ * (t, res) as they stand now, and the lane leaves.  The compare is made on the very value the next turn would read; a NaN s makes
+ * the sum NaN, which equals nothing: such a lane goes on as before.  An Sdf that carries bounds along the ray returns the plain
+ * value or NaN with a re-shade, so its s is a function of q as well.  The turns not taken are counted apart (`skipped`, COUNT
+ * only): what a kernel REPORTS is steps + skipped, the reference's count; what the pixels are dealt by is what they cost, steps
+ * alone (store_pixel).  tests/test_shadow_fixed_point.py replays the argument on recorded rays.
+ */
 template <bool COUNT, class Sdf>
-__device__ __forceinline__ float soft_shadow(Sdf& sdf, V3 p, V3 dir, float max_dist, u32& steps, bool needed, bool settled) {
+__device__ __forceinline__ float soft_shadow(Sdf& sdf, V3 p, V3 dir, float max_dist, u32& steps, u32& skipped, bool needed, bool settled) {
 	constexpr bool VMIN = Sdf::ASSUME_SETTLED;
 	V3 ro = add(p, dir);
 	float res = 1.f, t = 0.f;
@@ -1004,9 +1016,15 @@ __device__ __forceinline__ float soft_shadow(Sdf& sdf, V3 p, V3 dir, float max_d
 				const float v = a / t;
 				res = VMIN ? vmin_(res, v) : minf_(res, v);
 			}
-			t += s;
-			if (COUNT) steps++;
-			if (res <= stop || t > max_dist) break;
+			const float tn = t + s;
+			const bool done = res <= stop || tn > max_dist;
+			const bool still = tn == t;                      /* the next turn would read what this one read: see above */
+			if (COUNT) {
+				steps++;
+				if (still && !done) skipped += 127u - (u32)i;
+			}
+			t = tn;
+			if (done | still) break;
 		}
 		if (VMIN && t == 0.f) res = 0.f;
 	}
@@ -1120,7 +1138,13 @@ __host__ __device__ inline u32 common_lds_dwords(u32 n_lights, u32 n_materials, 
 	return (tables_in_lds(n_lights, n_materials, n_roots) ? table_dwords(n_lights, n_materials, n_roots) : 0u) + TILE_W * TILE_H;
 }
 
-struct Pixel { V3 rgb; Hit hit; u32 shadow_steps; };      /* rgb: the clamped colour BEFORE gamma; store_pixel applies gamma and packs it into the surface's format */
+/* rgb: the clamped colour BEFORE gamma; store_pixel applies gamma and packs it into the surface's format.  shadow_steps: the shadow
+ * turns this pixel's lane ran; shadow_skipped: the turns a stationary ray left out (soft_shadow) — what is REPORTED is their sum,
+ * the reference's count; what a pixel costs is the first alone. */
+struct Pixel {
+	V3 rgb; Hit hit; u32 shadow_steps, shadow_skipped;
+	__device__ __forceinline__ u32 reported_steps() const { return (hit.steps & 0xFFFFu) | ((shadow_steps + shadow_skipped) << 16); }
+};
 
 /* frame row of local row r of this launch's part (the inverse: lol_gpu_part_frame_row) */
 __device__ __forceinline__ int frame_row(const Launch& L, int r) {
@@ -1201,7 +1225,7 @@ __device__ __forceinline__ Pixel shade_pixel(const Launch& L, Sdf& sdf, const u3
 
 	/* get_light, naive_renderer.c:129-175 */
 	V3 total = { 0.f, 0.f, 0.f };
-	u32 shadow_steps = 0;
+	u32 shadow_steps = 0, shadow_skipped = 0;
 	if (lit) {
 		const V3 camera_dir = sm.normalize(sub(ro, p));
 		for (u32 li = 0; li < L.n_lights; li++) {
@@ -1221,7 +1245,7 @@ __device__ __forceinline__ Pixel shade_pixel(const Launch& L, Sdf& sdf, const u3
 			bool needed = true;
 			if (L.flags & FLAG_DARK_SKIP) needed = di > 0.f;
 			if ((L.flags & FLAG_MISS_SKIP) && hit.id == 0u) needed = false;
-			float shadow = soft_shadow<COUNT>(sdf, p, light_dir, light_dist, shadow_steps, needed, (L.flags & FLAG_SHADOW_SETTLED) != 0u);
+			float shadow = soft_shadow<COUNT>(sdf, p, light_dir, light_dist, shadow_steps, shadow_skipped, needed, (L.flags & FLAG_SHADOW_SETTLED) != 0u);
 
 			V3 refl = sub(scale(n, 2.f * dot(light_dir, n)), light_dir);
 			V3 Id = mul(scale(lds_v3(lp + 3), shadow * di), m_diff);
@@ -1242,7 +1266,7 @@ __device__ __forceinline__ Pixel shade_pixel(const Launch& L, Sdf& sdf, const u3
 	/* v3clamp: max(min(v, 1), 0) — NaN → 1 (vec.h:63-65) */
 	V3 c = { maxf_(minf_(total.x, 1.f), 0.f), maxf_(minf_(total.y, 1.f), 0.f), maxf_(minf_(total.z, 1.f), 0.f) };
 
-	return { c, hit, shadow_steps };      /* gamma + colorf_to_pixfmt: store_pixel */
+	return { c, hit, shadow_steps, shadow_skipped };      /* gamma + colorf_to_pixfmt: store_pixel */
 }
 
 /* Gamma + packing of a clamped linear colour, for the kernels that do not store through store_pixel (supersampled frames, batches
@@ -1314,9 +1338,11 @@ __device__ __forceinline__ void store_pixel(const Launch& L, const Pixel& P, u32
 			if (T.dbg_rgb) { T.dbg_rgb[o * 3 + 0] = post.x; T.dbg_rgb[o * 3 + 1] = post.y; T.dbg_rgb[o * 3 + 2] = post.z; }
 			if (T.dbg_hit_dist) T.dbg_hit_dist[o] = P.hit.dist;
 			if (T.dbg_hit_id) T.dbg_hit_id[o] = P.hit.id;
-			if (T.dbg_steps) T.dbg_steps[o] = (P.hit.steps & 0xFFFFu) | (P.shadow_steps << 16);
+			if (T.dbg_steps) T.dbg_steps[o] = P.reported_steps();
 			T.dst[(unsigned long long)gr * T.pitch_px + gx] = px;
 			if (pixel_cost) {                                   /* what the pixels are dealt to waves by: the evaluations this one needed */
+				/* (the turns it RAN, not those a stationary shadow ray left out: lanes grouped by the reference's count would wait
+				 * for the ones that creep to turn 128) */
 				const u32 c = P.hit.steps + P.shadow_steps;
 				pixel_cost[o] = (unsigned short)(c < 0xFFFFu ? c : 0xFFFFu);
 			}
@@ -1342,7 +1368,7 @@ __device__ __forceinline__ void store_pixel(const Launch& L, const Pixel& P, u32
 		if (T.dbg_rgb) { T.dbg_rgb[o * 3 + 0] = post.x; T.dbg_rgb[o * 3 + 1] = post.y; T.dbg_rgb[o * 3 + 2] = post.z; }
 		if (T.dbg_hit_dist) T.dbg_hit_dist[o] = P.hit.dist;
 		if (T.dbg_hit_id) T.dbg_hit_id[o] = P.hit.id;
-		if (T.dbg_steps) T.dbg_steps[o] = (P.hit.steps & 0xFFFFu) | (P.shadow_steps << 16);
+		if (T.dbg_steps) T.dbg_steps[o] = P.reported_steps();
 	}
 	/* through LDS so the block stores whole row segments (64 bytes each with the default 16x4 patch) */
 	l_tile[ty * TILE_W + tx] = px;

@@ -86,7 +86,7 @@ __device__ __forceinline__ void store_pixel_view(const Launch& L, const BatchTai
 		if (T.dbg_rgb) { T.dbg_rgb[o * 3 + 0] = post.x; T.dbg_rgb[o * 3 + 1] = post.y; T.dbg_rgb[o * 3 + 2] = post.z; }
 		if (T.dbg_hit_dist) T.dbg_hit_dist[o] = P.hit.dist;
 		if (T.dbg_hit_id) T.dbg_hit_id[o] = P.hit.id;
-		if (T.dbg_steps) T.dbg_steps[o] = (P.hit.steps & 0xFFFFu) | (P.shadow_steps << 16);
+		if (T.dbg_steps) T.dbg_steps[o] = P.reported_steps();
 		T.dst[v * view_stride_px(B) + (unsigned long long)gr * T.pitch_px + (unsigned long long)gx] = px;
 	}
 }

@@ -84,12 +84,12 @@ __device__ __forceinline__ Hit light_ray(const Launch& L, const LightQuery& Q, S
 		float light_dist = len(to_light);
 		V3 light_dir = scale(to_light, 1.0f / light_dist);      /* == v3normalize(light - p) */
 		const float di = clampf_(dot(n, light_dir), 0.f, 1.f);
-		u32 steps = 0;
-		const float shadow = soft_shadow<true>(sdf, p, light_dir, light_dist, steps, true, settled);
+		u32 steps = 0, skipped = 0;                             /* (turns run, turns a stationary ray left out: reported together) */
+		const float shadow = soft_shadow<true>(sdf, p, light_dir, light_dist, steps, skipped, true, settled);
 		V3 refl = sub(scale(n, 2.f * dot(light_dir, n)), light_dir);
 		const float si = di * powf_glibc(clampf_(dot(refl, camera_dir), 0.f, 1.f), shininess);
 		if (store) {
-			const LightFactor f = { shadow, di, si, steps };
+			const LightFactor f = { shadow, di, si, steps + skipped };
 			light_out(Q).factors[(u64)li * Q.stride + i] = f;
 		}
 	}

@@ -93,15 +93,15 @@ __device__ __forceinline__ void light_update_ray(const Launch& L, const LightUpd
 		float light_dist = len(to_light);
 		V3 light_dir = scale(to_light, 1.0f / light_dist);      /* == v3normalize(light - p) */
 		const float di = clampf_(dot(n, light_dir), 0.f, 1.f);
-		u32 steps = 0;
-		const float shadow = soft_shadow<true>(sdf, p, light_dir, light_dist, steps, whole, settled);      /* (specular alone: no march) */
+		u32 steps = 0, skipped = 0;                             /* (turns run, turns a stationary ray left out: reported together) */
+		const float shadow = soft_shadow<true>(sdf, p, light_dir, light_dist, steps, skipped, whole, settled);      /* (specular alone: no march) */
 		V3 refl = sub(scale(n, 2.f * dot(light_dir, n)), light_dir);
 		const float si = di * powf_glibc(clampf_(dot(refl, camera_dir), 0.f, 1.f), shininess);
 		const LightUpdateLate B = light_update_late(Q);
 		if (i < B.n) {                                          /* (this lane owns an element: asked again here, not kept as a mask) */
 			LightFactor* at = B.factors + ((u64)li * B.stride + i);
 			if ((B.march_lights >> li & 1u) != 0u) {
-				const LightFactor f = { shadow, di, si, steps };
+				const LightFactor f = { shadow, di, si, steps + skipped };
 				*at = f;
 			} else {
 				at->si = si;

@@ -90,7 +90,7 @@ __device__ __forceinline__ Pixel shade_ray(const Launch& L, Sdf& sdf, const u32*
 
 	/* get_light, naive_renderer.c:129-175; the skips as in shade_pixel */
 	V3 total = { 0.f, 0.f, 0.f };
-	u32 shadow_steps = 0;
+	u32 shadow_steps = 0, shadow_skipped = 0;
 	if (lit) {
 		const V3 camera_dir = normalize(sub(ro, p));
 		for (u32 li = 0; li < L.n_lights; li++) {
@@ -102,7 +102,7 @@ __device__ __forceinline__ Pixel shade_ray(const Launch& L, Sdf& sdf, const u32*
 			bool needed = true;
 			if (L.flags & FLAG_DARK_SKIP) needed = di > 0.f;
 			if ((L.flags & FLAG_MISS_SKIP) && hit.id == 0u) needed = false;
-			float shadow = soft_shadow<true>(sdf, p, light_dir, light_dist, shadow_steps, needed, settled);
+			float shadow = soft_shadow<true>(sdf, p, light_dir, light_dist, shadow_steps, shadow_skipped, needed, settled);
 
 			V3 refl = sub(scale(n, 2.f * dot(light_dir, n)), light_dir);
 			V3 Id = mul(scale(lds_v3(lp + 3), shadow * di), m_diff);
@@ -117,7 +117,7 @@ __device__ __forceinline__ Pixel shade_ray(const Launch& L, Sdf& sdf, const u32*
 	total = add(total, mul(v3(L.ambient), m_amb));
 	/* v3clamp: max(min(v, 1), 0) — NaN → 1 (vec.h:63-65) */
 	V3 c = { maxf_(minf_(total.x, 1.f), 0.f), maxf_(minf_(total.y, 1.f), 0.f), maxf_(minf_(total.z, 1.f), 0.f) };
-	return { c, hit, shadow_steps };
+	return { c, hit, shadow_steps, shadow_skipped };
 }
 
 /* Ray i of the query (a lane beyond n: ray n - 1), read or built where a pipeline begins.  A wave that shades again through the exact
@@ -206,7 +206,7 @@ __device__ __forceinline__ void shade_rays(SdfFast& fast, SdfExact& exact, bool 
 		if (O.pixel) O.pixel[i] = px;
 		if (O.hit_dist) O.hit_dist[i] = P.hit.dist;
 		if (O.hit_id) O.hit_id[i] = P.hit.id;
-		if (O.steps) O.steps[i] = (P.hit.steps & 0xFFFFu) | (P.shadow_steps << 16);
+		if (O.steps) O.steps[i] = P.reported_steps();
 	}
 }
 

@@ -165,7 +165,7 @@ static void lpt_release_set(lol_gpu::TileLpt& T) {
 	for (uint32_t** p : { &T.d_order[0], &T.d_order[1], &T.d_cost, &T.d_keys, &T.d_hist, &T.d_lanes })
 		if (*p) { (void)hipFree(*p); *p = nullptr; }
 	if (T.d_pixel_cost) { (void)hipFree(T.d_pixel_cost); T.d_pixel_cost = nullptr; }
-	T.cap = 0; T.lanes_cap = 0; T.pixels_cap = 0; T.n_tiles = 0; T.key[0] = 0;
+	T.cap = 0; T.lanes_cap = 0; T.pixels_cap = 0; T.pixels = 0; T.n_tiles = 0; T.key[0] = 0;
 }
 /* The frame that lpt_table_for_frame has just handed tables to has been queued on `s`: an event of the set's own marks the point
  * up to which its tables are in use.  What later has to wait for a set — another stream taking it over, a handle that may belong
@@ -280,6 +280,7 @@ bool lpt_table_for_frame(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h
 		                   T.d_lanes, (uint32_t)n_lanes, (uint32_t)w, (uint32_t)n_rows, regions_x, REGION_W, REGION_H);
 		if (!ok(hipGetLastError()) || !ok(hipMemsetAsync(T.d_cost, 0, ((size_t)n + 8) * 4, s))) { T.key[0] = 0; return false; }
 		record_pixels = true;
+		T.pixels = n_pixels;
 	} else if (T.frames == 1) {
 		/* the second frame of the view: its pixels dealt to the waves of their region by what they cost (exact: nothing moved);
 		 * the waves are new ones, so they go out in region order once more and report how long THEY run */
@@ -420,5 +421,17 @@ extern "C" int lol_gpu_tile_order(lol_gpu* ctx, lol_gpu_tile_order_info* out) {
 		else *out = { T.mode, T.chosen, (T.deciding || ctx->lpt_sorts == 0) ? 1 : 0, (int32_t)ctx->lpt_sorts, T.typical[0], T.typical[1] };
 	} else
 		*out = { T.mode, T.chosen, T.deciding ? 1 : 0, T.decisions, T.typical[0], T.typical[1] };
+	return LOL_GPU_OK;
+}
+
+/* include/lol_gpu_testing.h: what the recording frame of the view the last frame belongs to wrote for every pixel */
+extern "C" int lol_gpu_testing_pixel_cost(lol_gpu* ctx, unsigned short* out, size_t n_pixels) {
+	if (!ctx || !out) return LOL_GPU_ERR_ARG;
+	if (ctx->lpt_last_set < 0) return LOL_GPU_ERR_ARG;           /* the last frame went out in a fixed order: no table */
+	const lol_gpu::TileLpt& T = ctx->lpt[ctx->lpt_last_set];
+	if (!T.d_pixel_cost || T.pixels == 0 || T.pixels != n_pixels) return LOL_GPU_ERR_ARG;
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	LOL_HIP(ctx, hipDeviceSynchronize());                        /* (the set's stream may be a caller's: every frame queued so far) */
+	LOL_HIP(ctx, hipMemcpy(out, T.d_pixel_cost, n_pixels * sizeof(unsigned short), hipMemcpyDeviceToHost));
 	return LOL_GPU_OK;
 }

@@ -449,7 +449,7 @@ def gpu_lib() -> C.CDLL:
 
 
 TESTING_SYMBOLS = ["lol_gpu_testing_fail_uploads", "lol_gpu_testing_fail_first_tier", "lol_gpu_testing_has_return_clobbering_branch", "lol_gpu_multi_testing_root_stride",
-                   "lol_gpu_multi_testing_force_copier_threads", "lol_gpu_testing_fail_view_scratch"]      # include/lol_gpu_testing.h
+                   "lol_gpu_multi_testing_force_copier_threads", "lol_gpu_testing_fail_view_scratch", "lol_gpu_testing_pixel_cost"]      # include/lol_gpu_testing.h
 
 EXPORTED_SYMBOLS = [                                                    # include/lol_gpu.h
     "lol_gpu_abi_version", "lol_gpu_device_count", "lol_gpu_create", "lol_gpu_destroy", "lol_gpu_error",
@@ -962,6 +962,16 @@ class Renderer:
     def testing_fail_first_tier(self, n: int):
         """lol_gpu_testing_fail_first_tier: the next n out-of-line first runs of the scene compiler count as failed."""
         self._check(self._lib.lol_gpu_testing_fail_first_tier(self._ctx, n))
+
+    def testing_pixel_cost(self, w: int, n_rows: int):
+        """lol_gpu_testing_pixel_cost: the steps every pixel of the repeated view's recording frame ran, (n_rows, w) uint16."""
+        import numpy as np
+        out = np.zeros((n_rows, w), dtype=np.uint16)
+        # (bound here, not in gpu_lib(): a library given by LOL_GPU_LIB for an A/B may be a build from before this symbol)
+        fn = self._lib.lol_gpu_testing_pixel_cost
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_size_t], C.c_int
+        self._check(fn(self._ctx, out.ctypes.data, out.size))
+        return out
 
     def testing_fail_uploads(self, n: int):
         """include/lol_gpu_testing.h: the next n uploads fail at their copy step."""
