@@ -546,6 +546,7 @@ struct SdfForm {
 	bool carry = false;             /* the culling bound of the outermost run is carried along the ray (carry_constants) */
 	bool vcarry = false;            /* ... and the object's own last value is folded into it, with the constants `vc` */
 	ValueCarryConsts vc;
+	bool vgate = false;             /* ... only at evaluations where some lane's value of the object is not the minimum (decide_form) */
 	bool last_id = false;           /* ID_FROM_LAST: a third body, eval_rec(), and the id decided once after the march */
 	int  sat_cull_min_prims = 32;   /* operands of a smooth union from this many primitives on get a saturation test; 0: none */
 	int  cooldown = 3;              /* evaluations that do not test again after a test that did not allow the skip */
@@ -577,6 +578,27 @@ SdfForm decide_form(const lol_program& P, const FastPaths* fast, bool out_of_lin
 	f.vcarry = f.carry && plan.intervals[0].end == plan.intervals[0].begin + 1 && roots[plan.order[plan.intervals[0].begin]].bounded;
 	if (const char* e = tuning_env("LOL_GPU_CULL_VALUE_CARRY")) f.vcarry = f.vcarry && atoi(e) != 0;
 	if (f.vcarry) f.vc = value_carry_constants(P, roots[plan.order[plan.intervals[0].begin]]);
+	/* ... and that fold only at evaluations where it can matter.  In a lane where the object's value V is the minimum of the
+	 * evaluation at T, V is the step the loop takes (march: dist += d; soft_shadow: t + s), so every later point of this ray has
+	 * t >= fl(T + V) >= (T + V)(1 - 2^-24) — or V < 0 and the loop ends.  What the fold would leave is lb' <= ctt T + V (1 - dl) - Ef,
+	 * and a later check fl(fma(t, ctc, |best|)) < lb' needs ctc t (1 - 2^-24) < lb': impossible once ctc (1 - 2^-24)^2 >= ctt and
+	 * >= 1 - dl (scene4: 0.9999924 against 0.9999903 and 0.9999806).  So the fold is dead in that lane for good, and it is left
+	 * out where EVERY lane in EXEC has V <= the minimum of the other objects: one compare and a scalar branch instead of four
+	 * full-rate and two half-rate instructions after most evaluations (tests/tools/bound_upkeep_model.py: 71 % of the march's and
+	 * 81 % of the shadow loops' evaluations of scene4's blob, none of the skips lost).  Leaving a fold out is always allowed — lb stays
+	 * a bound, only an older one — so nothing here is needed for exactness: the two inequalities only say that nothing is lost.
+	 * Where: the carried object is the LAST of the plan, so that `best` before its join is the minimum of all the others, and the
+	 * inequalities hold for the constants written; anywhere else the fold stays unconditional.
+	 * (`lhs` below: the product is taken in double, and the factor 1 - 2^-40 stands for the roundings of its three multiplications,
+	 * so that the comparison errs to the side of the unconditional fold.)
+	 * LOL_GPU_CULL_UPDATE_GATED=0 / 1 beside LOL_GPU_TUNING: off / on (still only where eligible). */
+	if (f.vcarry) {
+		const CullInterval& iv = plan.intervals[0];
+		const double ctc = fmax((double)f.vc.ctc, (double)carry_constants(iv.both.empty() ? std::vector<CullTest>{ iv.test } : iv.both).ctc);
+		const double lhs = ctc * (1.0 - 0x1p-24) * (1.0 - 0x1p-24) * (1.0 - 0x1p-40);
+		f.vgate = iv.begin + 1 == plan.order.size() && lhs >= (double)f.vc.ctt && lhs >= 1.0 - (double)f.vc.dl;
+	}
+	if (const char* e = tuning_env("LOL_GPU_CULL_UPDATE_GATED")) f.vgate = f.vgate && atoi(e) != 0;
 	/* ID_FROM_LAST, for the inlined fast SDF of a scene of exactly TWO top-level objects — the scenes that keep the id in their march
 	 * (ASK_ID_ONCE, SdfEmitter::head_inlined); every other scene keeps its source byte for byte.  The primary march evaluates through
 	 * eval_rec(): the distance alone, like eval_dist(), plus a RECORD — each object's value at this step per lane, +inf for an object
@@ -750,8 +772,10 @@ struct SdfEmitter {
 		/* a NaN from a sphere without range tracker reaches the object's value: 0 * NaN (or inf) = NaN (... and every value the record takes) */
 		if (object_has_nr || rec) appendf(s, "\t\tnanacc = __builtin_fmaf(t%d, 0.f, nanacc);\n", d);
 		if (rec) appendf(s, "\t\trec%d = t%d;\n", rec_slot(oi), d);
+		const bool folds = f.vcarry && oi == plan.intervals[0].begin;
+		if (folds && f.vgate) value_carry_gate(d);
 		join_minimum(pass, st, d);
-		if (f.vcarry && oi == plan.intervals[0].begin) value_carry_update(d);
+		if (folds) value_carry_update(d);
 		for (uint32_t n = 0; n < st.n_close; n++) s += "\t\t} }\n";           /* every run that ends here */
 	}
 
@@ -920,11 +944,18 @@ struct SdfEmitter {
 		else
 			appendf(s, "\t\tif (t%d < best) { best = t%d; best_id = %uu; }\n", d, d, id);
 	}
+	/* (SdfForm::vgate) before the join, where `best` is still the minimum of the other objects: from here to the end of the run's block
+	 * `carry` is a local that shadows the member — "this ray may carry AND some lane's value of the object is not its minimum" —
+	 * and the fold below, the only thing in that block that reads it, is written as it always was */
+	void value_carry_gate(int d) {
+		appendf(s, "\t\tconst bool carry = this->carry && vote(t%d > best) != 0;\n", d);
+	}
 	/* the value just computed bounds the object further along the ray (value_carry_constants) */
 	void value_carry_update(int d) {
 		appendf(s, "\t\tif (carry) {\n\t\t  const float vg = __builtin_fmaf(rt, %s, __builtin_fmaf(__builtin_fabsf(t%d), -%s, t%d) - %s);\n"
-		        "\t\t  lb = maxf_(__builtin_fmaf(__builtin_fabsf(vg), -0x1p-20f, vg), lb);\n\t\t}\n",
-		        fbits(f.vc.ctt).c_str(), d, fbits(f.vc.dl).c_str(), d, fbits(f.vc.ef).c_str());
+		        "\t\t  lb = maxf_(__builtin_fmaf(__builtin_fabsf(vg), -0x1p-20f, vg), lb);\n%s\t\t}\n",
+		        fbits(f.vc.ctt).c_str(), d, fbits(f.vc.dl).c_str(), d, fbits(f.vc.ef).c_str(),
+		        f.vgate ? "\t\t  asm volatile(\"\");\n" : "");      /* (gated: keep the branch, or the fold comes back as a select) */
 	}
 
 	/* ---- what closes the struct */
