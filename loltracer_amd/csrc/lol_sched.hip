@@ -114,14 +114,20 @@ __global__ __launch_bounds__(LPT_THREADS) void deal_by_cost_kernel(const unsigne
 		lane_pixels[(size_t)region * REGION_PIXELS + j] = x | r << 16 | pad;
 	}
 }
-/* pass 1: snapshot every block's cost as a bucket number (bucket 0 = the most expensive), count the buckets */
-__global__ __launch_bounds__(LPT_THREADS) void lpt_hist_kernel(const uint32_t* cost, uint32_t* keys, uint32_t* hist, uint32_t n, uint32_t stride) {
+/* pass 1: snapshot every block's cost as a bucket number (bucket 0 = the most expensive), count the buckets.
+ * A wave whose lanes are all padding leaves before it writes a cost (lol_kernel.h, start_tile_clock), and the costs are zeroed in
+ * the recording frame alone: once a sort has moved such a wave, what lies at its launch position is the run time of the tile that
+ * went out there before.  It costs nothing, so it counts 0 whatever lies there — `lanes` (may be NULL: no wave is empty) is the
+ * DEALT table, whose padding comes first in a region: a wave is empty exactly when its lane 63 is padding. */
+__global__ __launch_bounds__(LPT_THREADS) void lpt_hist_kernel(const uint32_t* cost, const uint32_t* order, const uint32_t* lanes, uint32_t* keys, uint32_t* hist,
+                                                               uint32_t n, uint32_t stride) {
 	__shared__ uint32_t h[LPT_BUCKETS];
 	for (uint32_t b = threadIdx.x; b < LPT_BUCKETS; b += LPT_THREADS) h[b] = 0;
 	__syncthreads();
 	const uint32_t i = blockIdx.x * LPT_THREADS + threadIdx.x;
 	if (i < n) {
 		uint32_t k = cost[lol::tile_slot(i, stride)];          /* <= 703 (lol_kernel.h, store_pixel); clamped all the same */
+		if (lanes && (lanes[(size_t)order[lol::tile_slot(i, stride)] * 64u + 63u] & lol::LANE_PADDING)) k = 0;
 		k = LPT_BUCKETS - 1 - (k < LPT_BUCKETS ? k : LPT_BUCKETS - 1);
 		keys[i] = k;
 		atomicAdd(&h[k], 1u);
@@ -160,6 +166,49 @@ __global__ __launch_bounds__(LPT_THREADS) void lpt_scatter_kernel(const uint32_t
 }
 
 static unsigned lpt_resort_period() { return LPT_RESORT; }
+
+/* How a frame of w x n_rows pixels is cut into regions and wave slots, and how its tables are launched: one place for the frames
+ * (lpt_table_for_frame) and for the suite's scratch runs (lol_gpu_testing_deal, lol_gpu_testing_sort_tiles). */
+struct ScheduleGeometry {
+	uint32_t region_w, region_h, regions_x, regions_y;
+	uint32_t n;                 /* wave slots = blocks of the launch */
+	size_t   n_lanes, n_pixels;
+	bool     fits;              /* (an entry is column | row << 16 | flag) */
+};
+static ScheduleGeometry schedule_geometry(int w, int n_rows) {
+	ScheduleGeometry G{};
+	G.region_w = region_shape().w; G.region_h = region_shape().h;
+	G.regions_x = ((uint32_t)w + G.region_w - 1) / G.region_w; G.regions_y = ((uint32_t)n_rows + G.region_h - 1) / G.region_h;
+	G.n = G.regions_x * G.regions_y * (G.region_w * G.region_h / 64);
+	G.n_lanes = (size_t)G.n * 64; G.n_pixels = (size_t)w * (size_t)n_rows;
+	G.fits = w > 0 && n_rows > 0 && w <= 0xFFFF && n_rows <= 0x7FFF && G.n_lanes <= 0xFFFFFFFFull;
+	return G;
+}
+static dim3 tiles_grid(uint32_t n) { return dim3((n + LPT_THREADS - 1) / LPT_THREADS); }
+static uint32_t tiles_stride(uint32_t n) { return (n + 7u) >> 3; }      /* (lol_kernel.h, tile_slot: reaches 8 * stride - 1 < n + 8) */
+static size_t tiles_capacity(uint32_t n) { return (size_t)n + n / 4 + 1024; }      /* entries a table of n tiles is allocated with */
+/* the lane table: rectangles without costs, else dealt by them */
+static void launch_deal(hipStream_t s, const ScheduleGeometry& G, const unsigned short* pixel_cost, uint32_t* lanes, int w, int n_rows) {
+	if (!pixel_cost)
+		hipLaunchKernelGGL(deal_rectangles_kernel, dim3((unsigned)((G.n_lanes + LPT_THREADS - 1) / LPT_THREADS)), dim3(LPT_THREADS), 0, s,
+		                   lanes, (uint32_t)G.n_lanes, (uint32_t)w, (uint32_t)n_rows, G.regions_x, G.region_w, G.region_h);
+	else
+		hipLaunchKernelGGL(deal_by_cost_kernel, dim3(G.regions_x * G.regions_y), dim3(LPT_THREADS), 0, s, pixel_cost, lanes, (uint32_t)w, (uint32_t)n_rows,
+		                   G.regions_x, G.region_w, G.region_h);
+}
+/* the order table: order_out = order_in sorted by cost, longest first.  starts_out (device, may be NULL) receives where every
+ * bucket starts, taken between the scan and the scatter, which moves those cursors on */
+static bool launch_sort(hipStream_t s, const uint32_t* cost, const uint32_t* order_in, const uint32_t* lanes, uint32_t* keys, uint32_t* hist, uint32_t* order_out,
+                        uint32_t n, uint32_t* starts_out = nullptr) {
+	const uint32_t stride = tiles_stride(n);
+	if (hipMemsetAsync(hist, 0, 2 * LPT_BUCKETS * 4, s) != hipSuccess) { (void)hipGetLastError(); return false; }
+	hipLaunchKernelGGL(lpt_hist_kernel, tiles_grid(n), dim3(LPT_THREADS), 0, s, cost, order_in, lanes, keys, hist, n, stride);
+	hipLaunchKernelGGL(lpt_scan_kernel, dim3(1), dim3(LPT_BUCKETS), 0, s, hist);
+	if (starts_out && hipMemcpyAsync(starts_out, hist + LPT_BUCKETS, LPT_BUCKETS * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) { (void)hipGetLastError(); return false; }
+	hipLaunchKernelGGL(lpt_scatter_kernel, tiles_grid(n), dim3(LPT_THREADS), 0, s, keys, order_in, order_out, hist, n, stride);
+	if (hipGetLastError() != hipSuccess) { (void)hipGetLastError(); return false; }
+	return true;
+}
 
 static void lpt_release_set(lol_gpu::TileLpt& T) {
 	for (uint32_t** p : { &T.d_order[0], &T.d_order[1], &T.d_cost, &T.d_keys, &T.d_hist, &T.d_lanes })
@@ -205,12 +254,11 @@ void lpt_release(lol_gpu* ctx) {
 
 bool lpt_table_for_frame(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps, const lol_gpu_rows* R, int n_rows,
                                 int block, hipStream_t s, FrameTables* out) {
-	const uint32_t REGION_W = region_shape().w, REGION_H = region_shape().h, REGION_WAVES = REGION_W * REGION_H / 64;
-	const uint32_t regions_x = ((uint32_t)w + REGION_W - 1) / REGION_W, regions_y = ((uint32_t)n_rows + REGION_H - 1) / REGION_H;
-	const uint32_t n = regions_x * regions_y * REGION_WAVES;            /* wave slots = blocks of the launch */
-	const size_t n_lanes = (size_t)n * 64, n_pixels = (size_t)w * (size_t)n_rows;
+	const ScheduleGeometry G = schedule_geometry(w, n_rows);
+	const uint32_t n = G.n;
+	const size_t n_lanes = G.n_lanes, n_pixels = G.n_pixels;
 	ctx->lpt_last_set = -1;
-	if (block != 64 || w > 0xFFFF || n_rows > 0x7FFF || n_lanes > 0xFFFFFFFFull) return false;      /* (an entry is column | row << 16 | flag; one-wave blocks) */
+	if (block != 64 || !G.fits) return false;      /* (one-wave blocks) */
 	const int key[7] = { w, h, max_steps, R->band_rows, R->cycle_rows, R->offset_rows, ctx->kernel_epoch };
 	/* what the frame before this one was (on whatever stream): the same view of the same frame? */
 	const bool still = ctx->lpt_have_last && memcmp(key, ctx->lpt_last_key, sizeof key) == 0 && memcmp(cam, &ctx->lpt_last_cam, sizeof *cam) == 0;
@@ -254,7 +302,7 @@ bool lpt_table_for_frame(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h
 			if (T.launched && !ok(hipStreamSynchronize(s))) return false;
 			T.launched = false;
 			lpt_release_set(T);
-			const size_t cap = (size_t)n + n / 4 + 1024;      /* (tile_slot reaches 8 * ceil(n / 8) - 1 < n + 8) */
+			const size_t cap = tiles_capacity(n);
 			const bool good = ok(hipMalloc(reinterpret_cast<void**>(&T.d_order[0]), cap * 4)) && ok(hipMalloc(reinterpret_cast<void**>(&T.d_order[1]), cap * 4)) &&
 			                  ok(hipMalloc(reinterpret_cast<void**>(&T.d_cost), cap * 4)) && ok(hipMalloc(reinterpret_cast<void**>(&T.d_keys), cap * 4)) &&
 			                  ok(hipMalloc(reinterpret_cast<void**>(&T.d_hist), 2 * LPT_BUCKETS * 4)) &&
@@ -266,8 +314,6 @@ bool lpt_table_for_frame(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h
 		memcpy(T.key, key, sizeof key);
 		T.n_tiles = n;
 	}
-	const dim3 grid((n + LPT_THREADS - 1) / LPT_THREADS);
-	const uint32_t stride = (n + 7u) >> 3;
 	bool record_pixels = false;
 	T.launched = true;                                   /* (from here on something of this set is queued on s) */
 	if (new_key || memcmp(cam, &T.cam_epoch, sizeof *cam) != 0) {
@@ -275,26 +321,20 @@ bool lpt_table_for_frame(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h
 		 * pixel and every wave cost */
 		T.cam_epoch = *cam;
 		T.cur = 0; T.frames = 0;
-		hipLaunchKernelGGL(lpt_identity_kernel, grid, dim3(LPT_THREADS), 0, s, T.d_order[0], n, stride);
-		hipLaunchKernelGGL(deal_rectangles_kernel, dim3((unsigned)((n_lanes + LPT_THREADS - 1) / LPT_THREADS)), dim3(LPT_THREADS), 0, s,
-		                   T.d_lanes, (uint32_t)n_lanes, (uint32_t)w, (uint32_t)n_rows, regions_x, REGION_W, REGION_H);
+		hipLaunchKernelGGL(lpt_identity_kernel, tiles_grid(n), dim3(LPT_THREADS), 0, s, T.d_order[0], n, tiles_stride(n));
+		launch_deal(s, G, nullptr, T.d_lanes, w, n_rows);
 		if (!ok(hipGetLastError()) || !ok(hipMemsetAsync(T.d_cost, 0, ((size_t)n + 8) * 4, s))) { T.key[0] = 0; return false; }
 		record_pixels = true;
 		T.pixels = n_pixels;
 	} else if (T.frames == 1) {
 		/* the second frame of the view: its pixels dealt to the waves of their region by what they cost (exact: nothing moved);
 		 * the waves are new ones, so they go out in region order once more and report how long THEY run */
-		hipLaunchKernelGGL(deal_by_cost_kernel, dim3(regions_x * regions_y), dim3(LPT_THREADS), 0, s, T.d_pixel_cost, T.d_lanes, (uint32_t)w, (uint32_t)n_rows, regions_x, REGION_W, REGION_H);
+		launch_deal(s, G, T.d_pixel_cost, T.d_lanes, w, n_rows);
 		if (!ok(hipGetLastError())) { T.key[0] = 0; return false; }
 	} else if (T.frames == 2 || T.frames % lpt_resort_period() == 0) {
 		/* the run times of the frame before are in (same stream): three small kernels, then the other table is the current
 		 * one.  (Again every LPT_RESORT frames: the run times drift a little with what runs beside a wave.) */
-		if (ok(hipMemsetAsync(T.d_hist, 0, 2 * LPT_BUCKETS * 4, s))) {
-			hipLaunchKernelGGL(lpt_hist_kernel, grid, dim3(LPT_THREADS), 0, s, T.d_cost, T.d_keys, T.d_hist, n, stride);
-			hipLaunchKernelGGL(lpt_scan_kernel, dim3(1), dim3(LPT_BUCKETS), 0, s, T.d_hist);
-			hipLaunchKernelGGL(lpt_scatter_kernel, grid, dim3(LPT_THREADS), 0, s, T.d_keys, T.d_order[T.cur], T.d_order[T.cur ^ 1], T.d_hist, n, stride);
-			if (ok(hipGetLastError())) { T.cur ^= 1; T.sorts++; ctx->lpt_sorts++; }
-		}
+		if (launch_sort(s, T.d_cost, T.d_order[T.cur], T.d_lanes, T.d_keys, T.d_hist, T.d_order[T.cur ^ 1], n)) { T.cur ^= 1; T.sorts++; ctx->lpt_sorts++; }
 	}
 	T.frames++;
 	ctx->lpt_last_set = (int)(Tp - ctx->lpt);
@@ -433,5 +473,125 @@ extern "C" int lol_gpu_testing_pixel_cost(lol_gpu* ctx, unsigned short* out, siz
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
 	LOL_HIP(ctx, hipDeviceSynchronize());                        /* (the set's stream may be a caller's: every frame queued so far) */
 	LOL_HIP(ctx, hipMemcpy(out, T.d_pixel_cost, n_pixels * sizeof(unsigned short), hipMemcpyDeviceToHost));
+	return LOL_GPU_OK;
+}
+
+/* ---- include/lol_gpu_testing.h: the schedule's tables, for tests/test_gpu_schedule.py.  Scratch runs of the table kernels with the
+ * geometry and launches the frames use, and a read-only view of the set the last frame went through. ---- */
+#pragma GCC visibility push(hidden)
+/* launch position <-> where the tables keep it (lol_kernel.h, tile_slot), so that no caller restates the layout */
+__global__ __launch_bounds__(LPT_THREADS) void lpt_from_slots_kernel(const uint32_t* slotted, uint32_t* by_position, uint32_t n, uint32_t stride) {
+	const uint32_t i = blockIdx.x * LPT_THREADS + threadIdx.x;
+	if (i < n) by_position[i] = slotted[lol::tile_slot(i, stride)];
+}
+__global__ __launch_bounds__(LPT_THREADS) void lpt_to_slots_kernel(const uint32_t* by_position, uint32_t* slotted, uint32_t n, uint32_t stride) {
+	const uint32_t i = blockIdx.x * LPT_THREADS + threadIdx.x;
+	if (i < n) slotted[lol::tile_slot(i, stride)] = by_position[i];
+}
+namespace {
+/* device scratch that goes when the call returns, however it returns */
+struct TestScratch {
+	void* p[8] = {};
+	int n = 0;
+	~TestScratch() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
+	template <class T> hipError_t get(T** out, size_t count) {
+		*out = nullptr;
+		if (n >= 8) return hipErrorOutOfMemory;
+		void* q = nullptr;
+		const hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
+		if (e == hipSuccess) { p[n++] = q; *out = static_cast<T*>(q); }
+		return e;
+	}
+};
+constexpr size_t TEST_TILES_MAX = 1u << 24;
+/* a table stored by tile_slot, copied out by launch position through `tmp` (n entries of device scratch) */
+int copy_out_by_position(lol_gpu* ctx, const uint32_t* slotted, uint32_t* tmp, uint32_t* out, uint32_t n) {
+	hipLaunchKernelGGL(lpt_from_slots_kernel, tiles_grid(n), dim3(LPT_THREADS), 0, nullptr, slotted, tmp, n, tiles_stride(n));
+	LOL_HIP(ctx, hipGetLastError());
+	LOL_HIP(ctx, hipMemcpy(out, tmp, (size_t)n * 4, hipMemcpyDeviceToHost));
+	return LOL_GPU_OK;
+}
+}
+#pragma GCC visibility pop
+
+extern "C" int lol_gpu_testing_deal(lol_gpu* ctx, const unsigned short* cost, int w, int n_rows, uint32_t* lanes_out, size_t n_lanes) {
+	if (!ctx || !lanes_out) return LOL_GPU_ERR_ARG;
+	const ScheduleGeometry G = schedule_geometry(w, n_rows);
+	if (!G.fits || n_lanes != G.n_lanes) return LOL_GPU_ERR_ARG;
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	TestScratch S;
+	unsigned short* d_cost = nullptr;
+	uint32_t* d_lanes = nullptr;
+	LOL_HIP(ctx, S.get(&d_lanes, G.n_lanes));
+	LOL_HIP(ctx, hipMemset(d_lanes, 0xFF, G.n_lanes * 4));             /* (an entry no kernel wrote names no pixel of any frame) */
+	if (cost) {
+		LOL_HIP(ctx, S.get(&d_cost, G.n_pixels));
+		LOL_HIP(ctx, hipMemcpy(d_cost, cost, G.n_pixels * sizeof(unsigned short), hipMemcpyHostToDevice));
+	}
+	launch_deal(nullptr, G, d_cost, d_lanes, w, n_rows);
+	LOL_HIP(ctx, hipGetLastError());
+	LOL_HIP(ctx, hipMemcpy(lanes_out, d_lanes, G.n_lanes * 4, hipMemcpyDeviceToHost));
+	return LOL_GPU_OK;
+}
+
+extern "C" int lol_gpu_testing_sort_tiles(lol_gpu* ctx, const uint32_t* cost, const uint32_t* order_in, const uint32_t* lanes, size_t n_tiles,
+                                          uint32_t* order_out, uint32_t* keys_out, uint32_t* starts_out) {
+	if (!ctx || !cost || !order_in || !order_out || !keys_out || !starts_out || n_tiles == 0 || n_tiles > TEST_TILES_MAX) return LOL_GPU_ERR_ARG;
+	const uint32_t n = (uint32_t)n_tiles, stride = tiles_stride(n);
+	const size_t slots = tiles_capacity(n);                               /* (as the frames' tables are allocated) */
+	for (size_t i = 0; i < n_tiles; i++) if (order_in[i] >= n) return LOL_GPU_ERR_ARG;      /* (the sort reads lanes[64 * order_in + 63]) */
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	TestScratch S;
+	uint32_t *d_tmp, *d_cost, *d_in, *d_out, *d_keys, *d_hist, *d_starts, *d_lanes = nullptr;
+	LOL_HIP(ctx, S.get(&d_tmp, n_tiles));
+	LOL_HIP(ctx, S.get(&d_cost, slots));
+	LOL_HIP(ctx, S.get(&d_in, slots));
+	LOL_HIP(ctx, S.get(&d_out, slots));
+	LOL_HIP(ctx, S.get(&d_keys, n_tiles));
+	LOL_HIP(ctx, S.get(&d_hist, 2 * LPT_BUCKETS));
+	LOL_HIP(ctx, S.get(&d_starts, LPT_BUCKETS));
+	if (lanes) {
+		LOL_HIP(ctx, S.get(&d_lanes, n_tiles * 64));
+		LOL_HIP(ctx, hipMemcpy(d_lanes, lanes, n_tiles * 64 * 4, hipMemcpyHostToDevice));
+	}
+	LOL_HIP(ctx, hipMemset(d_cost, 0, slots * 4));
+	LOL_HIP(ctx, hipMemset(d_in, 0, slots * 4));
+	LOL_HIP(ctx, hipMemset(d_out, 0xFF, slots * 4));                     /* (a position the scatter left out holds no tile) */
+	LOL_HIP(ctx, hipMemset(d_keys, 0xFF, n_tiles * 4));
+	for (int pass = 0; pass < 2; pass++) {
+		LOL_HIP(ctx, hipMemcpy(d_tmp, pass ? order_in : cost, n_tiles * 4, hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(lpt_to_slots_kernel, tiles_grid(n), dim3(LPT_THREADS), 0, nullptr, d_tmp, pass ? d_in : d_cost, n, stride);
+		LOL_HIP(ctx, hipGetLastError());
+		LOL_HIP(ctx, hipDeviceSynchronize());                            /* (d_tmp is filled again) */
+	}
+	if (!launch_sort(nullptr, d_cost, d_in, d_lanes, d_keys, d_hist, d_out, n, d_starts)) return LOL_GPU_ERR_HIP;
+	LOL_HIP(ctx, hipDeviceSynchronize());
+	if (const int rc = copy_out_by_position(ctx, d_out, d_tmp, order_out, n)) return rc;
+	LOL_HIP(ctx, hipMemcpy(keys_out, d_keys, n_tiles * 4, hipMemcpyDeviceToHost));
+	LOL_HIP(ctx, hipMemcpy(starts_out, d_starts, LPT_BUCKETS * 4, hipMemcpyDeviceToHost));
+	return LOL_GPU_OK;
+}
+
+extern "C" int lol_gpu_testing_schedule(lol_gpu* ctx, lol_gpu_testing_schedule_info* info, uint32_t* order, uint32_t* order_before, uint32_t* keys,
+                                        uint32_t* cost, size_t n_tiles, uint32_t* lanes, size_t n_lanes) {
+	if (!ctx || !info) return LOL_GPU_ERR_ARG;
+	if (ctx->lpt_last_set < 0) return LOL_GPU_ERR_ARG;           /* the last frame went out in a fixed order: no table */
+	const lol_gpu::TileLpt& T = ctx->lpt[ctx->lpt_last_set];
+	if (!T.d_lanes || T.n_tiles == 0 || T.key[0] <= 0 || T.pixels == 0) return LOL_GPU_ERR_ARG;
+	const uint32_t n = T.n_tiles;
+	*info = { n, T.frames, T.sorts, region_shape().w, region_shape().h, (uint32_t)T.key[0], (uint32_t)(T.pixels / (size_t)T.key[0]) };
+	const bool tiles = order || order_before || keys || cost;
+	if ((tiles && n_tiles != n) || (lanes && n_lanes != (size_t)n * 64)) return LOL_GPU_ERR_ARG;
+	if (!tiles && !lanes) return LOL_GPU_OK;
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	LOL_HIP(ctx, hipDeviceSynchronize());                        /* (the set's stream may be a caller's: every frame queued so far) */
+	TestScratch S;
+	uint32_t* d_tmp = nullptr;
+	if (tiles) LOL_HIP(ctx, S.get(&d_tmp, n));
+	if (order) if (const int rc = copy_out_by_position(ctx, T.d_order[T.cur], d_tmp, order, n)) return rc;
+	if (order_before) if (const int rc = copy_out_by_position(ctx, T.d_order[T.cur ^ 1], d_tmp, order_before, n)) return rc;
+	if (cost) if (const int rc = copy_out_by_position(ctx, T.d_cost, d_tmp, cost, n)) return rc;
+	if (keys) LOL_HIP(ctx, hipMemcpy(keys, T.d_keys, (size_t)n * 4, hipMemcpyDeviceToHost));
+	if (lanes) LOL_HIP(ctx, hipMemcpy(lanes, T.d_lanes, (size_t)n * 64 * 4, hipMemcpyDeviceToHost));
 	return LOL_GPU_OK;
 }

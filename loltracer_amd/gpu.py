@@ -449,7 +449,8 @@ def gpu_lib() -> C.CDLL:
 
 
 TESTING_SYMBOLS = ["lol_gpu_testing_fail_uploads", "lol_gpu_testing_fail_first_tier", "lol_gpu_testing_has_return_clobbering_branch", "lol_gpu_multi_testing_root_stride",
-                   "lol_gpu_multi_testing_force_copier_threads", "lol_gpu_testing_fail_view_scratch", "lol_gpu_testing_pixel_cost"]      # include/lol_gpu_testing.h
+                   "lol_gpu_multi_testing_force_copier_threads", "lol_gpu_testing_fail_view_scratch", "lol_gpu_testing_pixel_cost",
+                   "lol_gpu_testing_deal", "lol_gpu_testing_sort_tiles", "lol_gpu_testing_schedule"]      # include/lol_gpu_testing.h
 
 EXPORTED_SYMBOLS = [                                                    # include/lol_gpu.h
     "lol_gpu_abi_version", "lol_gpu_device_count", "lol_gpu_create", "lol_gpu_destroy", "lol_gpu_error",
@@ -972,6 +973,57 @@ class Renderer:
         fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_size_t], C.c_int
         self._check(fn(self._ctx, out.ctypes.data, out.size))
         return out
+
+    def testing_deal(self, cost, w: int, n_rows: int):
+        """lol_gpu_testing_deal: the lane table of a w x n_rows frame — rectangles (cost None) or dealt by cost (n_rows, w) uint16 —
+        made by the library's own kernels on scratch; flat uint32, 64 entries per wave slot."""
+        import numpy as np
+        rw, rh = 64, 16                                             # (only to size the buffer: the library checks it against its own)
+        out = np.zeros(((w + rw - 1) // rw) * ((n_rows + rh - 1) // rh) * rw * rh, dtype=np.uint32)
+        if cost is not None:
+            cost = np.ascontiguousarray(cost, dtype=np.uint16)
+            assert cost.shape == (n_rows, w)
+        fn = self._lib.lol_gpu_testing_deal                         # (bound here, like testing_pixel_cost)
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t], C.c_int
+        self._check(fn(self._ctx, cost.ctypes.data if cost is not None else None, w, n_rows, out.ctypes.data, out.size))
+        return out
+
+    def testing_sort_tiles(self, cost, order_in, lanes=None):
+        """lol_gpu_testing_sort_tiles: one longest-first sort on scratch, everything by launch position.  Returns (order_out,
+        keys, starts)."""
+        import numpy as np
+        cost = np.ascontiguousarray(cost, dtype=np.uint32)
+        order_in = np.ascontiguousarray(order_in, dtype=np.uint32)
+        n = cost.size
+        assert order_in.shape == cost.shape == (n,)
+        if lanes is not None:
+            lanes = np.ascontiguousarray(lanes, dtype=np.uint32)
+            assert lanes.shape == (n * 64,)
+        order_out, keys, starts = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(1024, dtype=np.uint32)
+        fn = self._lib.lol_gpu_testing_sort_tiles
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int
+        self._check(fn(self._ctx, cost.ctypes.data, order_in.ctypes.data, lanes.ctypes.data if lanes is not None else None, n,
+                       order_out.ctypes.data, keys.ctypes.data, starts.ctypes.data))
+        return order_out, keys, starts
+
+    def testing_schedule(self):
+        """lol_gpu_testing_schedule: the tables of the repeated view the last frame belongs to, by launch position, or None when that
+        frame went out in a fixed order.  Waits for the device; changes nothing."""
+        import numpy as np
+        fn = self._lib.lol_gpu_testing_schedule
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, C.c_size_t], C.c_int
+        info = (C.c_uint32 * 7)()
+        rc = fn(self._ctx, info, None, None, None, None, 0, None, 0)
+        if rc == -3:                                                # LOL_GPU_ERR_ARG: no table
+            return None
+        self._check(rc)
+        n = int(info[0])
+        t = {k: np.zeros(n, dtype=np.uint32) for k in ("order", "order_before", "keys", "cost")}
+        lanes = np.zeros(n * 64, dtype=np.uint32)
+        self._check(fn(self._ctx, info, t["order"].ctypes.data, t["order_before"].ctypes.data, t["keys"].ctypes.data, t["cost"].ctypes.data, n,
+                       lanes.ctypes.data, lanes.size))
+        names = ("n_tiles", "frames", "sorts", "region_w", "region_h", "w", "n_rows")
+        return dict({k: int(v) for k, v in zip(names, info)}, lanes=lanes, **t)
 
     def testing_fail_uploads(self, n: int):
         """include/lol_gpu_testing.h: the next n uploads fail at their copy step."""
