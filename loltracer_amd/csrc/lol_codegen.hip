@@ -296,6 +296,57 @@ ValueCarryConsts value_carry_constants(const lol_program& P, const RootBound& r)
 	return c;
 }
 
+/* The carried bound kept past the march (fast SDF, SdfForm::keep; DESIGN 3.3 "The bound kept past the march").  When the march's
+ * loop ends, lb bounds the object along the march's ray from some T <= rt, rt the t of the lane's last evaluation: lb <= L, and
+ * L - ct t > |best| at a point p(t), t >= T, is what either proof above asks for (ct = rho gam with gam = 1 - et for the value bound,
+ * 1 / k_j for a cluster sphere).  The march ends at p(dist), dist = rt + (its last step), which may lie BEHIND rt; with
+ * t* = rt + |dist - rt| one has t* >= |dist| and t* - T >= |dist - T| for every 0 <= T <= rt, and for ANY binary32 point q with
+ * |q - p(dist)| <= d0 + nu e |q|  (|q| <= D(q) + R + |C| as above) the triangle inequality through p(dist) gives, for nu <= 3,
+ *   plain value at q > |best|   where   |best| < (1 - nu e)(L - ct t*) - gam d0 - nu e B,
+ * B >= (Rm + |C|)(1 + 2 et) and >= rm_j + |C_j| for every cluster sphere.  The kernel keeps, per lane,
+ *   kb = fl(K1 - Ek),  K1 = fma(|K|, -2^-20, K),  K = fma(ts, -ctc, lb),  ts = fl(rt + |fl(dist - rt)|) >= t* (1 - 2 e)
+ * (ctc >= ct (1 + 2^-20) makes ctc ts >= ct t*; K1 <= (L - ct t*)(1 - 2^-21); Ek >= 3 e B + 2^-100, the last for results below the
+ * normal range), and the existing check fl(fma(rt, ctc, |best|)) < lb then serves the normal taps q_j = fl(p_j +- h):
+ *   d0 = sqrt(3) |h|, nu = 1:      lb = fma(|h|, -c_tap, kb), rt = 0      (fma(0, ctc, |best|) is |best| exactly).
+ * Each of the two roundings after K1 raises a positive result by a factor 1 + e at most, and (1 - 2^-21)(1 + e)^2 <= 1 - 2^-22 <=
+ * 1 - 3 e; a result that is not positive passes no check.  -inf stays -inf and NaN stays NaN through all of it.
+ * (A shadow ray q(t) = fl(ro' + fl(dir t)), ro' = fl(p + dir), has d0 = rho + rho (1 + 3 e) t + 2 sqrt(3) eta and nu = 2 + e, within
+ * the same Ek and — asserted below — the same ctc; a hook that started the shadow marches from fl(kb - rho) was built on that and
+ * measured: it did not separate from the taps alone and was taken out again)
+ * tests/test_cull_kept_bound.py re-derives the constants in rational arithmetic and checks the implication there. */
+struct KeepConsts { float ctc = 0.f, ek = 0.f, c_tap = 0.f; bool ok = false; };
+KeepConsts keep_constants(const ValueCarryConsts& vc, const std::vector<CullTest>& tests, const lol_program& P, const RootBound& r) {
+	const double e = 0x1p-24, rho = 1.0 + 0x1p-20, et = 40.0 * 0x1p-24 * (double)r.levels;
+	const CarryConsts cc = carry_constants(tests);
+	KeepConsts c;
+	c.ctc = vc.ctc > cc.ctc ? vc.ctc : cc.ctc;                           /* the check's own (open_test_carried) */
+	double B = 0.0, gam = 1.0 - et;
+	{	/* Rm as value_carry_constants takes it */
+		const double cn = sqrt(r.c[0] * r.c[0] + r.c[1] * r.c[1] + r.c[2] * r.c[2]) * (1.0 + 0x1p-40);
+		double R = r.r;
+		for (uint32_t i = r.first; i < r.top; i++) {
+			const lol_op& o = P.ops[i];
+			if (o.op != LOL_OP_SPHERE && o.op != LOL_OP_RBOX) continue;
+			const double dx = o.f[0] - r.c[0], dy = o.f[1] - r.c[1], dz = o.f[2] - r.c[2];
+			const double m = o.op == LOL_OP_SPHERE ? fabs((double)o.f[3])
+			                                       : sqrt((double)o.f[3] * o.f[3] + (double)o.f[4] * o.f[4] + (double)o.f[5] * o.f[5]) + fabs((double)o.f[6]);
+			R = fmax(R, (sqrt(dx * dx + dy * dy + dz * dz) + m) * (1.0 + 0x1p-40));
+		}
+		B = (R * (1.0 + 0x1p-40) + cn) * (1.0 + 2.0 * et);
+	}
+	for (const CullTest& t : tests) {
+		const double cn = sqrt((double)t.c[0] * t.c[0] + (double)t.c[1] * t.c[1] + (double)t.c[2] * t.c[2]) * (1.0 + 0x1p-40);
+		B = fmax(B, (double)t.rm + cn);
+		gam = fmax(gam, 1.0 / (double)t.k);
+	}
+	c.ek = f_up(3.0 * e * B + 0x1p-100);
+	c.c_tap = f_up(sqrt(3.0) * (1.0 + 0x1p-40));
+	/* the preconditions of the argument above */
+	c.ok = !tests.empty() && et < 0x1p-8 && gam <= 1.0 && (double)c.ctc >= rho * gam * (1.0 + 0x1p-21) * (1.0 + 0x1p-40)
+	    && std::isfinite(c.ek) && c.ek > 0.f && (double)c.ek >= 3.0 * e * B + 0x1p-100 && (double)c.c_tap * (double)c.c_tap >= 3.0;
+	return c;
+}
+
 std::vector<CullTest> cluster_tests(const RootBound& r) {
 	std::vector<CullTest> t;
 	for (const Sphere& c : r.clusters) t.push_back(make_test(c));
@@ -547,6 +598,8 @@ struct SdfForm {
 	bool vcarry = false;            /* ... and the object's own last value is folded into it, with the constants `vc` */
 	ValueCarryConsts vc;
 	bool vgate = false;             /* ... only at evaluations where some lane's value of the object is not the minimum (decide_form) */
+	int  keep = 0;                  /* ... and what the march leaves in lb is kept past loop_done(), a mask: 1 for the normal taps */
+	KeepConsts kc;                  /*     (keep_constants) */
 	bool last_id = false;           /* ID_FROM_LAST: a third body, eval_rec(), and the id decided once after the march */
 	int  sat_cull_min_prims = 32;   /* operands of a smooth union from this many primitives on get a saturation test; 0: none */
 	int  cooldown = 3;              /* evaluations that do not test again after a test that did not allow the skip */
@@ -599,6 +652,19 @@ SdfForm decide_form(const lol_program& P, const FastPaths* fast, bool out_of_lin
 		f.vgate = iv.begin + 1 == plan.order.size() && lhs >= (double)f.vc.ctt && lhs >= 1.0 - (double)f.vc.dl;
 	}
 	if (const char* e = tuning_env("LOL_GPU_CULL_UPDATE_GATED")) f.vgate = f.vgate && atoi(e) != 0;
+	/* ... and the bound the march ends with kept for the points the pixel evaluates next (keep_constants): loop_done() forgets lb, and
+	 * the four normal taps then run the two-sphere test again — and the blob itself where the loose spheres fail — for points that lie
+	 * within sqrt(3) h of the march's end.  The struct gets hooks beside ray_begin / ray_at (lol_kernel.h: bound_keep, taps_begin /
+	 * taps_done) which set lb and rt so that the ONE carried check of the bodies decides; eval() and eval_dist() are the text they
+	 * were.  Where the value carry is on and keep_constants' preconditions hold.  LOL_GPU_CULL_KEEP=<mask> beside LOL_GPU_TUNING: bit 1
+	 * the taps; with the bit clear the source is what it was.  (Bit 2 was the start of the shadow marches while that was measured; it
+	 * names nothing now and is ignored.) */
+	if (f.vcarry) {
+		const CullInterval& iv = plan.intervals[0];
+		f.kc = keep_constants(f.vc, iv.both.empty() ? std::vector<CullTest>{ iv.test } : iv.both, P, roots[plan.order[iv.begin]]);
+		f.keep = f.kc.ok ? 1 : 0;
+	}
+	if (const char* e = tuning_env("LOL_GPU_CULL_KEEP")) f.keep = f.keep & atoi(e);
 	/* ID_FROM_LAST, for the inlined fast SDF of a scene of exactly TWO top-level objects — the scenes that keep the id in their march
 	 * (ASK_ID_ONCE, SdfEmitter::head_inlined); every other scene keeps its source byte for byte.  The primary march evaluates through
 	 * eval_rec(): the distance alone, like eval_dist(), plus a RECORD — each object's value at this step per lane, +inf for an object
@@ -724,6 +790,7 @@ struct SdfEmitter {
 		appendf(s, "struct %s {\n\tstatic constexpr bool ASSUME_SETTLED = %s;\n\tstatic constexpr bool ASK_ID_ONCE = %s;\n\tRange rg;\n\tfloat nanacc = 0.f;\n%s%s"
 		        "\t__device__ __forceinline__ void loop_done() { %s%s }\n", name, fast ? "true" : "false", P.n_roots >= 3 ? "true" : "false", cool_decl(),
 		        carry_decl, plan.intervals.empty() ? "" : "cool[0] = 0u;", f.carry ? " lb = -__builtin_inff(); carry = false;" : "");
+		if (f.keep) keep_hooks();
 		if (f.param) s += "\tparam_ptr K = nullptr;\n";
 		if (f.last_id) {
 			/* the record's two slots in the order of the ids: rec0 the object of the lower id, which a tie goes to */
@@ -732,6 +799,17 @@ struct SdfEmitter {
 			        "\t__device__ __forceinline__ u32 id_of(float rec0, float rec1) const { return rec0 == vmin_(rec0, rec1) ? %uu : %uu; }\n",
 			        ida < idb ? ida : idb, ida < idb ? idb : ida);
 		}
+	}
+
+	/* what the march leaves in lb, kept for the normal taps and the shadow rays (SdfForm::keep, keep_constants): bound_keep() is
+	 * called with the march's dist before loop_done() and returns kb, -inf where nothing was carried; taps_begin() turns the carried
+	 * check into |best| < kb - c_tap |h| (rt = 0; carry = false: a passed full test sets nothing, no fold runs), taps_done() forgets it */
+	void keep_hooks() {
+		appendf(s, "\t__device__ __forceinline__ float bound_keep(float dist) const {\n"
+		        "\t\tconst float ts = rt + __builtin_fabsf(dist - rt);\n\t\tconst float kg = __builtin_fmaf(ts, -%s, lb);\n"
+		        "\t\treturn __builtin_fmaf(__builtin_fabsf(kg), -0x1p-20f, kg) - %s;\n\t}\n", fbits(f.kc.ctc).c_str(), fbits(f.kc.ek).c_str());
+		appendf(s, "\t__device__ __forceinline__ void taps_begin(float h, float kb) { lb = __builtin_fmaf(__builtin_fabsf(h), -%s, kb); rt = 0.f; carry = false; }\n"
+		        "\t__device__ __forceinline__ void taps_done() { lb = -__builtin_inff(); }\n", fbits(f.kc.c_tap).c_str());
 	}
 
 	/* ---- one pass */

@@ -860,12 +860,25 @@ template <class S> __device__ __forceinline__ auto ray_begin(S& s, V3 rd, int) -
 template <class S> __device__ __forceinline__ void ray_begin(S&, V3, long) {}
 template <class S> __device__ __forceinline__ auto ray_at(S& s, float t, int) -> decltype(s.ray_at(t)) { s.ray_at(t); }
 template <class S> __device__ __forceinline__ void ray_at(S&, float, long) {}
+/* ... and such an Sdf may KEEP what the march's loop leaves in its bound for the points the pixel evaluates next (lol_codegen.hip,
+ * keep_constants): bound_keep() — called with the march's dist BEFORE loop_done() — returns the bound at the march's end, p(dist), in
+ * a form that is valid at any point q once |q - p(dist)| is taken off, and -inf where nothing was carried; it travels in Marched::kb.
+ * taps_begin() arms the Sdf's check for the four normal taps (within sqrt(3) |h| of p(dist)), taps_done() forgets it again, so the
+ * shadow marches start without a bound as they always did (starting them from kb - |dir| was built and measured too: it did not
+ * separate from the taps alone, LABNOTES 8).  A Marched that no march of this Sdf made (lol_kernel_light_update.h) carries -inf.
+ * Every other Sdf ignores all of it, and its kernels are what they were. */
+template <class S> __device__ __forceinline__ auto bound_keep(const S& s, float dist, int) -> decltype(s.bound_keep(dist)) { return s.bound_keep(dist); }
+template <class S> __device__ __forceinline__ float bound_keep(const S&, float, long) { return -__builtin_inff(); }
+template <class S> __device__ __forceinline__ auto taps_begin(S& s, float h, float kb, int) -> decltype(s.taps_begin(h, kb)) { s.taps_begin(h, kb); }
+template <class S> __device__ __forceinline__ void taps_begin(S&, float, float, long) {}
+template <class S> __device__ __forceinline__ auto taps_done(S& s, int) -> decltype(s.taps_done()) { s.taps_done(); }
+template <class S> __device__ __forceinline__ void taps_done(S&, long) {}
 
 struct Hit { float dist; u32 id; u32 steps; };
 /* what march() hands on: the distance marched, the distance BEFORE its last step (the point that step evaluated), the step count,
  * and the object id as far as it is known without asking — `ask`: this lane's id is that of the object nearest to the point of
  * its last step, which normal_and_id() asks for (Sdf::ASK_ID_ONCE) */
-struct Marched { float dist, prev; u32 steps; u32 id; bool ask; };
+struct Marched { float dist, prev; u32 steps; u32 id; bool ask; float kb = -__builtin_inff(); };      /* kb: bound_keep() above */
 
 /* get_intersection, naive_renderer.c:48-69.
  *
@@ -937,6 +950,7 @@ __device__ __forceinline__ Marched march(Sdf& sdf, V3 ro, V3 rd, int max_steps, 
 		if (COUNT) steps++;
 		if (d < EPSILON || dist > MAX_DIST) break;
 	}
+	const float kb = bound_keep(sdf, dist, 0);       /* (written by every march: a capture, or -inf) */
 	sdf.loop_done();
 	if constexpr (id_from_last<Sdf>(0)) {
 		if (first_turn < max_steps) id = sdf.id_of(rec0, rec1);      /* (wave-uniform: every lane takes the first turn of a loop that runs) */
@@ -946,9 +960,9 @@ __device__ __forceinline__ Marched march(Sdf& sdf, V3 ro, V3 rd, int max_steps, 
 	if constexpr (Sdf::ASK_ID_ONCE) {
 		const bool ran = first_turn < max_steps;
 		if (ran) id = 0;                                 /* (asked for below, unless the ray escaped) */
-		return { dist, prev, steps, id, ran && !far };
+		return { dist, prev, steps, id, ran && !far, kb };
 	}
-	return { dist, prev, steps, id, false };
+	return { dist, prev, steps, id, false, kb };
 }
 
 /* in_shadow + softshadow, naive_renderer.c:73-100.  dir/light_dist come from the caller,
@@ -1089,6 +1103,7 @@ __device__ __forceinline__ V3 normal_and_id(Sdf& sdf, V3 ro, V3 rd, const Marche
 	id = hit.id;
 	lit = true;
 	if (!any_ask && miss_skip && vote(id != 0u) == 0) { lit = false; return acc; }
+	if (!any_ask) taps_begin(sdf, h, hit.kb, 0);         /* (the turn that asks evaluates a point on the ray: it runs without the bound) */
 #pragma unroll 1      /* (unrolled — four independent evaluations in flight — it is 0.8 % slower within the 64-VGPR budget) */
 	for (int k = any_ask ? 4 : 3; k >= 0; k--) {
 		/* sign pattern of tap k, wave-uniform: x is + for k0,k3; y is + for k2,k3; z is + for k1,k3 */
@@ -1100,12 +1115,14 @@ __device__ __forceinline__ V3 normal_and_id(Sdf& sdf, V3 ro, V3 rd, const Marche
 		if (ask) {
 			if (hit.ask) id = did;
 			if (miss_skip && vote(id != 0u) == 0) { lit = false; break; }
+			taps_begin(sdf, h, hit.kb, 0);
 			continue;
 		}
 		const float ns = -s;          /* -1.f * s */
 		V3 term = { px ? s : ns, py ? s : ns, pz ? s : ns };
 		acc = k == 3 ? term : add(term, acc);
 	}
+	taps_done(sdf, 0);
 	return lit ? sm.normalize(acc) : acc;
 }
 /* ... in plain arithmetic, whatever the Sdf (ray and light queries) */

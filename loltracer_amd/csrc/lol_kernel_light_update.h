@@ -59,7 +59,8 @@ __device__ __forceinline__ LightUpdateLate light_update_late(const LightUpdateQu
  * The per-ray body: light_ray's with the march read back — `dist0`, `id0`: what the capture wrote for the element, the id held to
  * n_roots (light_update_rays).  `i` = the ray's element (a lane beyond n works on a copy of element n - 1 and stores
  * nothing).  normal_and_id reads dist, id and `ask` of a Marched alone where ask is false (the interpreter keeps the id
- * in its march: Sdf::ASK_ID_ONCE is false), so prev and steps are left 0.
+ * in its march: Sdf::ASK_ID_ONCE is false), so prev and steps are left 0 — and kb, the bound a march keeps for its taps (lol_kernel.h,
+ * bound_keep), stays at its default of -inf: no march of this Sdf object produced `p`.
  */
 template <class Sdf, bool TABLES_GLOBAL>
 __device__ __forceinline__ void light_update_ray(const Launch& L, const LightUpdateQuery& Q, Sdf& sdf, const u32* lds, V3 ro, V3 rd,

@@ -54,7 +54,7 @@ def configurations():
          ("form 1 (out of line)", but("--form", "1"), {}),
          ("form 2 (inlined)", but("--form", "2"), {}),
          ("module switches: all", but("--switches", "127"), {})]
-    for var, values in (("LOL_GPU_CULL_CARRY", "01"), ("LOL_GPU_CULL_VALUE_CARRY", "0"), ("LOL_GPU_CULL_UPDATE_GATED", "0"),
+    for var, values in (("LOL_GPU_CULL_CARRY", "01"), ("LOL_GPU_CULL_VALUE_CARRY", "0"), ("LOL_GPU_CULL_UPDATE_GATED", "0"), ("LOL_GPU_CULL_KEEP", "0"),
                         ("LOL_GPU_LAST_STEP_ID", "0"),
                         ("LOL_GPU_SAT_CULL_MIN_PRIMS", "02"), ("LOL_GPU_CULL_CLUSTERS", "02"), ("LOL_GPU_INTERP_FUSE_POPS", "0"),
                         ("LOL_GPU_SPEC_INLINE_MAX", ["16"])):
