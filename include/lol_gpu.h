@@ -774,8 +774,8 @@ int  lol_gpu_shade_queries(const lol_gpu* ctx);
  * (lol_gpu_scene_views_kernel_name, lol_gpu_scene_views_state: lol_gpu_diag.h).  Opt-in, and not the default for a reason: on the one scene
  * measured (scene4) the interpreter with the upload's proven fast paths was the faster of the two (README.md quotes the numbers).
  * Out of scope: an adaptive form (of the supersampled and adaptive forms that batches of views have, the supersampled one is
- * lol_gpu_render_scene_views_samples below), ray and shading queries over per-record scenes, row partitions, lol_gpu_multi_*
- * forms, host surfaces and the renderer.h protocol; and the structure module is not kept across uploads of the same structure
+ * lol_gpu_render_scene_views_samples below; ray and shading queries over per-record scenes are lol_gpu_trace_scene_rays' and its
+ * siblings', further below), row partitions, lol_gpu_multi_* forms, host surfaces and the renderer.h protocol; and the structure module is not kept across uploads of the same structure
  * (each upload loads it anew, from the cache).
  */
 int  lol_gpu_render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views, int cams_per_view,
@@ -821,14 +821,65 @@ int  lol_gpu_scene_views(const lol_gpu* ctx);
  * what it is without this call's existence.  Without the setter, until the module is loaded, or if it failed, the interpreter's
  * render_interp_scene_batch_aa / render_interp_scene_batch_aa_lin render on each record's own lists — same bits either way
  * (lol_gpu_scene_view_samples_kernel_name: lol_gpu_diag.h).
- * Out of scope: an adaptive form, ray and shading queries over per-record scenes, row partitions, lol_gpu_multi_* forms,
- * host surfaces and the renderer.h protocol.
+ * Out of scope: an adaptive form, row partitions, lol_gpu_multi_* forms, host surfaces and the renderer.h protocol
+ * (ray and shading queries over per-record scenes are built: "Scene queries", below).
  */
 int  lol_gpu_render_scene_views_samples(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views,
                                         int cams_per_view, int w, int h, int max_steps, int samples, void* dst, size_t pitch_bytes,
                                         size_t view_stride_bytes, const lol_gpu_debug* dbg, void* stream);
 int  lol_gpu_set_scene_view_samples(lol_gpu* ctx, int enable);   /* before lol_gpu_upload_program */
 int  lol_gpu_scene_view_samples(const lol_gpu* ctx);
+
+/*
+ * Scene queries: ray and shading queries under each record's own SCENE — what is under the cursor in frame t of an animation, how far
+ * away the moving object is in each frame (a lens that follows it), whether the camera path walks through it as it moves, the colour
+ * of a probe pixel over the exposure — without an upload per frame and without rendering frames to read one pixel.
+ * `scenes` (and `cams`, for the *_pixels forms) are HOST memory and hold n_scenes entries, 1 <= n_scenes <= LOL_GPU_MAX_VIEWS; both, and
+ * the tables the programs point to, are copied before the call returns.  Record r is one scene and, in the pixel forms, one camera.
+ * Each record answers n rays: the rays of a list in device memory (n x {ox, oy, oz, dx, dy, dz}, used as given) or the primary rays
+ * of n pixels {x, y} of the w x h frame under cams[r].  list_stride == 0: one list of n elements serves every record; otherwise
+ * list_stride >= n, and record r's list begins list_stride ELEMENTS (rays, or {x, y} pairs) behind record r - 1's.  The outputs are
+ * dense: element (r, i) lies at index r * n + i of every output (three floats each for normal, rgb_linear and rgb); all addressing
+ * is 64-bit.
+ * Contract: element (r, i) is EXACTLY what lol_gpu_trace_rays, lol_gpu_trace_pixels, lol_gpu_shade_rays or lol_gpu_shade_pixels answers
+ * for that ray on another context with this context's settings (lol_gpu_set_exact_skips, lol_gpu_set_cull, the pixel format) that called
+ * lol_gpu_upload_program(&scenes[r]) and, for the pixel forms, asks under cams[r] — bit for bit: dist, id, normal, rgb_linear, rgb,
+ * pixel, hit_dist, hit_id, and the march step count.  So each element is the reference's arithmetic on record r's own numbers, for NaN,
+ * infinite, zero and unnormalised rays too, whatever the other rays and the other records hold.
+ * One latitude, the one light updates have: for a LIST OF RAYS with the settled-shadow exit on (bit 2 of lol_gpu_set_exact_skips), the
+ * high 16 bits of lol_gpu_shades.steps (shadow steps) are "the steps really marched", and are held equal to that other context's only
+ * after lol_gpu_set_exact_skips(ctx, 0).  For pixel sources all 32 bits are equal.
+ * Every scene must have the uploaded program's STRUCTURE; the test, the refusal and its text are lol_gpu_render_scene_views'.  Every
+ * number may differ, and a NaN centre in one record is that record's business alone.
+ * Decided per record, on the host, from that record's own scene and camera — everything an upload or a query decides: the three exact
+ * skips (shading); whether the scene is finite, i.e. the scene's side of what the fast SDF and the settled exit rest on; which of the
+ * record's two macro-op lists runs (lists of rays: the one every camera may use; pixels: what that record's camera allows); and, for
+ * the pixel forms, the first march step sdf(cams[r].origin) on that record's scene.  No proof runs on the device: a smoothness
+ * constant the upload did not prove takes the plain sminf — same bits.
+ * Asynchronous on `stream` (NULL = the context's own stream; LOL_GPU_STREAM_DEFAULT as elsewhere): one copy of the records and their
+ * data through scene views' ring of 8 sets, under its rules (HIP's special stream handles included), and ONE launch; no scratch, no
+ * host wait.  The context's scene, kernels, lol_gpu_kernel_key, tile-order state, sample settings and other rings are neither read
+ * nor changed: a frame after the call is the frame it would have been.
+ * Refused, with nothing launched and nothing written, in this order:
+ *  1. what the single-scene query refuses, in its order: no context, a NULL list with n > 0, NULL out or every output NULL,
+ *     max_steps < 0, n > 2^32 - 1 — LOL_GPU_ERR_ARG; no program — LOL_GPU_ERR_NO_PROGRAM; w < 1 or h < 1 — LOL_GPU_ERR_ARG;
+ *  2. LOL_GPU_ERR_ARG for NULL scenes, n_scenes < 1 or > LOL_GPU_MAX_VIEWS, NULL cams in a pixel form, a list_stride that is neither 0
+ *     nor >= n, n_scenes * n > 2^32 - 1;
+ *  3. the scene refusals of lol_gpu_render_scene_views: a missing table, another structure, a root_material out of range.
+ * n == 0 returns LOL_GPU_OK with nothing launched.  An allocation that fails returns LOL_GPU_ERR_HIP, and the context stays usable.
+ * Which kernel: the interpreter's trace_interp_scenes / shade_interp_scenes, always.  lol_gpu_set_scene_views, lol_gpu_set_ray_queries
+ * and lol_gpu_set_shade_queries have no effect on these calls.
+ * Out of scope: a structure-module form, light passes over records, lists in host memory, lol_gpu_multi_* forms, and a C pick over
+ * records (the Python mirror has the convenience: Renderer.pick_scenes).
+ */
+int  lol_gpu_trace_scene_rays(lol_gpu* ctx, const lol_program* scenes, int n_scenes, const float* rays_dev, size_t n, size_t list_stride,
+                              int max_steps, const lol_gpu_hits* out, void* stream);
+int  lol_gpu_trace_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, int w, int h,
+                                int max_steps, const uint32_t* xy_dev, size_t n, size_t list_stride, const lol_gpu_hits* out, void* stream);
+int  lol_gpu_shade_scene_rays(lol_gpu* ctx, const lol_program* scenes, int n_scenes, const float* rays_dev, size_t n, size_t list_stride,
+                              int max_steps, const lol_gpu_shades* out, void* stream);
+int  lol_gpu_shade_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, int w, int h,
+                                int max_steps, const uint32_t* xy_dev, size_t n, size_t list_stride, const lol_gpu_shades* out, void* stream);
 
 /*
  * Light passes and relighting: a new LOOK without a march.  The look of a scene is what a host changes most often once the rays are

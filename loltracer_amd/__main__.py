@@ -2,6 +2,7 @@
                           [--adaptive T] [--orbit K -o DIR [--orbit-samples N [--orbit-adaptive T]] [--orbit-shutter K]]
                           [--lens R (--focus D | --focus-at X,Y) --lens-samples K] [--pick X,Y] [--panorama WxH -o FILE.ppm]
                           [--tween B.lol --frames N [--tween-samples S] [--tween-shutter K] -o DIR]
+                          [--tween B.lol --frames N --pick X,Y] [--tween B.lol --frames N --lens R --focus-at X,Y [--lens-samples K] -o DIR]
                           [--relight LOOK.lol [LOOK2.lol ...] [--samples S] [--lens R --focus D --lens-samples K] [--move-lights] -o DIR]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
@@ -21,7 +22,11 @@ the N frames of an animation from scene A to scene B (same structure, other numb
 scene of its own (Renderer.render_scene_views_into), and writes DIR/frame_0000.ppm ...; with --tween-shutter K each frame is the mean
 in linear light of K scenes spread over its exposure (scene.shutter_times): objects that move are blurred; with --tween-samples S
 every one of those scenes is supersampled S x S (the samples= of that call; --samples stays refused beside --tween: it is the frame
-setting of a context, which that call does not read).  The camera is A's.  SCENE.lol --relight LOOK.lol [LOOK2.lol ...] -o DIR
+setting of a context, which that call does not read).  The camera is A's.  --pick X,Y beside --tween prints one pick line per
+frame, in --pick's format, from ONE scene query over the frames' scenes (Renderer.pick_scenes; no -o needed), and --lens R --focus-at
+X,Y [--lens-samples K] beside --tween pulls focus: frame f is the mean over the K lens cameras focused at what pixel (X, Y) shows IN
+FRAME f (its pick times the cosine to the camera's axis), K records of that frame's scene in the same one launch; a frame whose ray
+hits nothing is an error that names the frame; not with --tween-shutter.  SCENE.lol --relight LOOK.lol [LOOK2.lol ...] -o DIR
 captures the light passes of every pixel of the --size frame ONCE (Renderer.light_pixels_into) and makes one frame per look from them
 without marching again (Renderer.relight_into): DIR/look_0000.ppm ... are the frames of the looks' scenes, byte for byte.  A look is
 the scene with other light intensities, material colours or ambient colour (scene.same_geometry); one that differs in anything else
@@ -101,16 +106,41 @@ def tween_frames(sc, args, w, h) -> int:
         return 1
     n, k = args.frames, args.tween_shutter
     scenes = [S.tween(sc, other, t) for f in range(n) for t in S.shutter_times(f, n, k)]
+    cams = [sc.camera] * len(scenes)
     r = gpu.Renderer(args.device)
     try:
         # (no set_scene_views: the interpreter's kernels with the upload's proven fast paths were the faster route where both were
         # measured; a host whose scenes gain from the structure module sets it before prepare())
-        r.prepare(sc)
+        queries = bool(args.pick or args.focus_at)
+        r.prepare(sc, wait=not queries)      # (scene queries and the frames behind them run on the interpreter: nothing waits)
+        if queries:
+            # what pixel (X, Y) shows in every frame (k = 1 here): ONE scene query over the frames' scenes
+            x, y = pixel_arg(args.pick or args.focus_at, w, h)
+            picks = r.pick_scenes(scenes, x, y, w, h, cameras=cams, max_steps=args.max_steps)
+        if args.pick:
+            for p in picks:
+                print(pick_line(x, y, p))
+            if not args.out:
+                return 0
+        if args.lens:
+            # a lens that follows what (X, Y) shows: frame f is the mean over the K lens cameras focused at ITS pick, K records of its scene
+            k = args.lens_samples
+            focus = [args.focus] * n
+            if args.focus_at:
+                cosine = axis_cosine(sc, w, h, x, y)
+                for f, p in enumerate(picks):
+                    if p["id"] == 0 or not p["dist"] > 0:
+                        print(f"--focus-at {x},{y}: in frame {f} the ray of that pixel hits nothing to focus on", file=sys.stderr)
+                        return 1
+                    focus[f] = p["dist"] * cosine
+                    print(f"frame {f}: focus at {x},{y}: object {p['id']} at {p['dist']:.6g} along its ray, {focus[f]:.6g} along the camera's axis")
+            cams = [c for f in range(n) for c in S.lens_cameras(sc.camera, focus[f], args.lens, k)]
+            scenes = [scenes[f] for f in range(n) for _ in range(k)]
         frames = np.zeros((n, h, w), dtype=np.uint32)
         dev = r.malloc(frames.nbytes)
         try:
             t0 = time.perf_counter()
-            r.render_scene_views_into(dev, [sc.camera] * len(scenes), scenes, w, h, k, args.max_steps, samples=args.tween_samples)
+            r.render_scene_views_into(dev, cams, scenes, w, h, k, args.max_steps, samples=args.tween_samples)
             r.sync()
             dt = (time.perf_counter() - t0) * 1e3
             r.memcpy_d2h(frames.ctypes.data, dev, frames.nbytes)
@@ -359,10 +389,18 @@ def main(argv=None) -> int:
             return 1
         return relight_frames(sc, args, w, h)
     if args.tween:
-        if (args.panorama or args.orbit or args.lens or args.pick or args.samples != 1 or args.adaptive != -1 or not args.out
-                or args.frames < 1 or args.frames * args.tween_shutter > gpu.MAX_VIEWS):
-            print(f"--tween B.lol takes --frames N (N K <= {gpu.MAX_VIEWS} scenes with --tween-shutter K) and -o DIR; not with "
-                  "--panorama, --orbit, --lens, --pick, --samples or --adaptive", file=sys.stderr)
+        per_frame = args.lens_samples if args.lens else args.tween_shutter
+        if (args.panorama or args.orbit or args.samples != 1 or args.adaptive != -1 or not (args.out or (args.pick and not args.lens))
+                or args.frames < 1 or args.frames * per_frame > gpu.MAX_VIEWS):
+            print(f"--tween B.lol takes --frames N (N K <= {gpu.MAX_VIEWS} scenes with --tween-shutter K or --lens R --lens-samples K) and "
+                  "-o DIR (--pick X,Y alone needs no -o); not with --panorama, --orbit, --samples or --adaptive", file=sys.stderr)
+            return 1
+        if args.lens and (args.lens < 0 or not (args.focus > 0 or args.focus_at) or args.pick or args.tween_shutter != 1):
+            print("--tween with --lens R takes a radius > 0 and --focus-at X,Y (or --focus D > 0); not with --pick or --tween-shutter",
+                  file=sys.stderr)
+            return 1
+        if args.pick and args.tween_shutter != 1:
+            print("--tween with --pick X,Y prints one line per frame: not with --tween-shutter", file=sys.stderr)
             return 1
         return tween_frames(sc, args, w, h)
     if args.panorama:

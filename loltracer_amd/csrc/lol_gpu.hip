@@ -2037,7 +2037,8 @@ static hipError_t launch_scene_views(const lol_gpu* ctx, bool lin, bool aa, void
 }
 
 /* the records of a call and their data, on the host: SceneView r and, in `data`, what its offsets point to (each part on a multiple
- * of four dwords: the macro-op records want 16 bytes).  `lists`: the interpreter renders, so every record needs its pair of lists. */
+ * of four dwords: the macro-op records want 16 bytes).  `lists`: the interpreter renders, so every record needs its pair of lists.
+ * `cams` == nullptr: the records of a query over lists of RAYS — no camera, no first step, and the list every camera may use. */
 static int build_scene_records(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n, int max_steps, bool lists,
                                std::vector<lol::SceneView>& views, std::vector<uint32_t>& data) {
 	views.resize((size_t)n);
@@ -2048,16 +2049,25 @@ static int build_scene_records(lol_gpu* ctx, const lol_frame_camera* cams, const
 	const bool cull = culling_enabled(ctx->want_cull);
 	for (int r = 0; r < n; r++) {
 		const lol_program& P = scenes[r];
-		const lol_frame_camera& cam = cams[r];
 		lol::SceneView& V = views[(size_t)r];
 		memset(&V, 0, sizeof V);
-		memcpy(&V.cam, &cam, sizeof V.cam);
 		const bool finite = shadow_settle_ok(P);
 		const unsigned want = ctx->want_skips;
 		V.flags = ((want & 1u) && miss_skip_ok(P) ? lol::FLAG_MISS_SKIP : 0u) | ((want & 2u) && dark_skip_ok(P) ? lol::FLAG_DARK_SKIP : 0u);
-		float d = 0.f; uint32_t id = 0;
-		const bool first = program_first_step(P, cam, max_steps, stack, &d, &id);      /* (on this record's scene: nothing is kept) */
-		const bool second_list = camera_fields(V, cam, finite, (want & 4u) && finite, first, d, id);
+		bool second_list = false;
+		if (cams) {
+			const lol_frame_camera& cam = cams[r];
+			memcpy(&V.cam, &cam, sizeof V.cam);
+			float d = 0.f; uint32_t id = 0;
+			const bool first = program_first_step(P, cam, max_steps, stack, &d, &id);      /* (on this record's scene: nothing is kept) */
+			second_list = camera_fields(V, cam, finite, (want & 4u) && finite, first, d, id);
+		} else if ((want & 4u) && finite) {
+			V.flags |= lol::FLAG_SHADOW_SETTLED;      /* the scene's side of it; the rays' side is the kernel's ballot, as for any list of rays */
+		}
+		/* a query's two bits (lol_kernel_scene_queries.h): what ray_query and launch_scene_query decide from the uploaded scene and the
+		 * call's camera, from this record's.  None of SCENE_VIEW_FLAGS: the frames' kernels mask them out. */
+		if (finite) V.flags |= lol::SCENE_VIEW_FINITE;
+		if (finite && (!cams || camera_sane(cams[r]))) V.flags |= lol::SCENE_VIEW_SANE;
 		V.ambient[0] = P.ambient_color.x; V.ambient[1] = P.ambient_color.y; V.ambient[2] = P.ambient_color.z;
 		if (lists) {
 			uint32_t n_mops = 0;
@@ -2101,6 +2111,22 @@ static int queue_scene_records(lol_gpu* ctx, const std::vector<lol::SceneView>& 
 	return e == hipSuccess ? LOL_GPU_OK : ring_done(ctx, S, s, e, "copy of the records of a batch of scene views");
 }
 
+/* what the scenes of the records are refused for, once the program is known to be there: a missing table, another structure, a
+ * material that is not there */
+static int scenes_refused(lol_gpu* ctx, const lol_program* scenes, int n) {
+	const lol_program& U = ctx->h_prog;
+	for (int r = 0; r < n; r++) {
+		const lol_program& P = scenes[r];
+		if ((P.n_ops && !P.ops) || (P.n_lights && !P.lights) || !P.materials || (P.n_roots && !P.root_material))
+			return fail(ctx, LOL_GPU_ERR_ARG, "malformed scene of a view: a table is missing");
+		if (P.n_ops != U.n_ops || !same_structure(U, P))
+			return fail(ctx, LOL_GPU_ERR_ARG, "a view's scene has not the uploaded program's structure (counts, opcodes, ids)");
+		for (uint32_t i = 0; i < P.n_roots; i++)
+			if (P.root_material[i] >= P.n_materials) return fail(ctx, LOL_GPU_ERR_ARG, "material index out of range in a view's scene");
+	}
+	return LOL_GPU_OK;
+}
+
 /* `samples` x `samples` samples per pixel (lol_gpu_render_scene_views_samples; 1: lol_gpu_render_scene_views).  Nothing in the records
  * depends on it: with samples > 1 the launch is the one of lol_gpu_render_views_samples — counted in samples, the sample grid's size
  * in fw / fh, the sample bits in the flags — and the kernels are the supersampled ones, which reduce a pixel's samples in registers:
@@ -2112,16 +2138,7 @@ static int render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const 
 	if (samples != 1 && samples != 2 && samples != 4) return fail(ctx, LOL_GPU_ERR_ARG, "samples per axis must be 1, 2 or 4");
 	LOL_TRY(blend_refused(ctx, cams, n_views, K, w, h, max_steps, dst, pitch_bytes, view_stride_bytes));
 	const int n = n_views * K;
-	const lol_program& U = ctx->h_prog;
-	for (int r = 0; r < n; r++) {
-		const lol_program& P = scenes[r];
-		if ((P.n_ops && !P.ops) || (P.n_lights && !P.lights) || !P.materials || (P.n_roots && !P.root_material))
-			return fail(ctx, LOL_GPU_ERR_ARG, "malformed scene of a view: a table is missing");
-		if (P.n_ops != U.n_ops || !same_structure(U, P))
-			return fail(ctx, LOL_GPU_ERR_ARG, "a view's scene has not the uploaded program's structure (counts, opcodes, ids)");
-		for (uint32_t i = 0; i < P.n_roots; i++)
-			if (P.root_material[i] >= P.n_materials) return fail(ctx, LOL_GPU_ERR_ARG, "material index out of range in a view's scene");
-	}
+	LOL_TRY(scenes_refused(ctx, scenes, n));
 	const bool aa = samples > 1;
 	if (aa && !lol::samples_fit_wave(samples))
 		return fail(ctx, LOL_GPU_ERR_UNSUPPORTED, "this build's wave patch (LOL_WAVE_W x LOL_WAVE_H) does not divide into that many samples per axis");
@@ -2574,5 +2591,138 @@ int lol_gpu_relight_views_held(lol_gpu* ctx, const lol_program* look, const lol_
 	LOL_TRY(held_look_refused(ctx, look, *held, in, N));
 	if (cams_per_view == 1 && samples == 1) return relight_launch(ctx, look, in, N, out, stream);       /* a pixel is its one leaf */
 	return relight_views_launch(ctx, look, in, N, n_views, cams_per_view, w, h, samples, out, stream);
+}
+}  // extern "C"
+
+/*
+ * Scene queries (include/lol_gpu.h, "Scene queries"; the kernels: lol_kernel_scene_queries.h): a list query (QuerySource,
+ * source_refused) answered under each record's own scene — scene views' records (build_scene_records, with the record's two query
+ * bits), scene views' ring (queue_scene_records) and ONE launch of the interpreter's kernel with the record in the grid's y.  What
+ * ray_query and launch_scene_query decide from the uploaded scene and the call's camera is decided per record, from that record's own.
+ * The context's scene, kernels, keys, cached first step, tile-order state, sample settings and other rings are neither read nor
+ * changed, and no scene kernel takes over here: the interpreter answers, whatever the module switches say.
+ * Last in this file: its kernels are instantiated behind all others (lol_gpu_internal.h).
+ */
+static int scene_query(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, QuerySource src, size_t list_stride,
+                       const lol_gpu_hits* hits, const lol_gpu_shades* shades, bool no_output) {
+	/* 1. the list query's own refusals; a NULL `cams` is 2.'s, so the camera source_refused looks at is there */
+	static const lol_frame_camera no_cam = {};
+	if (src.pixels && !cams) src.cam = &no_cam;
+	LOL_TRY(source_refused(ctx, src, no_output));
+	/* 2. the records and their lists */
+	auto refuse = [&](const char* why) {
+		char text[128];
+		snprintf(text, sizeof text, "%s: %s", src.who, why);
+		return fail(ctx, LOL_GPU_ERR_ARG, text);
+	};
+	if (!scenes) return refuse("no scenes");
+	if (n_scenes < 1 || n_scenes > LOL_GPU_MAX_VIEWS) return refuse("the number of scenes is not in 1 ... LOL_GPU_MAX_VIEWS");
+	if (src.pixels && !cams) return refuse("no cameras");
+	if (list_stride != 0 && list_stride < src.n) return refuse("list_stride is neither 0 nor at least n");
+	if ((unsigned long long)n_scenes * (unsigned long long)src.n > 0xFFFFFFFFull) return refuse("more than 2^32 - 1 rays over all scenes");
+	/* 3. the scenes, as lol_gpu_render_scene_views refuses them */
+	LOL_TRY(scenes_refused(ctx, scenes, n_scenes));
+	if (src.n == 0) return LOL_GPU_OK;
+
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = src.stream ? static_cast<hipStream_t>(src.stream) : ctx->stream;
+	std::vector<lol::SceneView> views;
+	std::vector<uint32_t> data;
+	LOL_TRY(build_scene_records(ctx, src.pixels ? cams : nullptr, scenes, n_scenes, src.max_steps, true, views, data));
+	RingSet* S = nullptr;
+	LOL_TRY(queue_scene_records(ctx, views, data, s, &S));
+	lol::SceneList R = { reinterpret_cast<const lol::SceneView*>(S->d_buf), S->d_buf + views.size() * lol::SCENE_VIEW_DWORDS,
+	                     (unsigned long long)list_stride };
+	const lol_program& P = ctx->h_prog;
+	const int kind = ctx->interp_sqrt_kind;
+	hipError_t e;
+	if (hits) {
+		/* ray_query's RayQuery, without what the record brings: camera, first step, list, RAYS_SCENE_SANE */
+		lol::RayQuery Q;
+		memset(&Q, 0, sizeof Q);
+		Q.rays = src.rays;
+		Q.xy = src.xy;
+		Q.n = (uint32_t)src.n;
+		Q.max_steps = src.max_steps;
+		if (src.pixels) { Q.flags = lol::RAYS_FROM_PIXELS; Q.fw = (float)src.w; Q.fh = (float)src.h; }
+		if (hits->id) Q.flags |= lol::RAYS_WANT_ID;
+		if (hits->normal) Q.flags |= lol::RAYS_WANT_NORMAL;
+		Q.out = { hits->dist, hits->id, hits->steps, hits->normal };
+		const dim3 grid((unsigned)(((unsigned long long)Q.n + 63u) / 64u), (unsigned)n_scenes);
+		void* args[] = { &Q, &R };
+		e = stack_class_dispatch(interp_stack_class(P.max_stack), [&](auto v) {
+			constexpr int ssize = decltype(v)::ssize;
+			const void* k = kind == 3 ? reinterpret_cast<const void*>(&lol::trace_interp_scenes<ssize, 3>)
+			                          : reinterpret_cast<const void*>(&lol::trace_interp_scenes<ssize, 0>);
+			return hipLaunchKernel(k, grid, dim3(64), args, 0, s);
+		});
+	} else {
+		/* launch_scene_query's Launch, without what the record brings: camera, first step, lists, tables, ambient colour, the skips */
+		lol::Launch L;
+		memset(&L, 0, sizeof L);
+		L.max_steps = src.max_steps;
+		L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
+		if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+		L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
+		lol::ShadeQuery Q = {};
+		Q.rays = src.rays;
+		Q.xy = src.xy;
+		Q.n = (uint32_t)src.n;
+		if (src.pixels) {
+			Q.flags |= lol::SHADE_FROM_PIXELS;
+			L.fw = (float)src.w; L.fh = (float)src.h;
+			L.w = src.w; L.h = src.h;
+		}
+		Q.out = { shades->rgb_linear, shades->rgb, shades->pixel, shades->hit_dist, shades->hit_id, shades->steps };
+		const unsigned lds = tables_lds_bytes(P);
+		const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK), (unsigned)n_scenes);
+		void* args[] = { &L, &Q, &R };
+		e = interp_dispatch(ctx, [&](auto v) {
+			constexpr int ssize = decltype(v)::ssize;
+			constexpr bool tables_global = decltype(v)::tables_global;
+			const void* k = kind == 3 ? reinterpret_cast<const void*>(&lol::shade_interp_scenes<ssize, 3, tables_global>)
+			                          : reinterpret_cast<const void*>(&lol::shade_interp_scenes<ssize, 0, tables_global>);
+			return hipLaunchKernel(k, grid, dim3(lol::BLOCK), args, lds, s);
+		});
+	}
+	return ring_done(ctx, *S, s, e, hits ? "scene ray query launch" : "scene shading query launch");
+}
+
+/* no exception crosses the C boundary (the records are built in host memory) */
+static int scene_query_guarded(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, const QuerySource& src,
+                               size_t list_stride, const lol_gpu_hits* hits, const lol_gpu_shades* shades) {
+	const bool no_output = hits ? (!hits->dist && !hits->id && !hits->steps && !hits->normal)
+	                     : shades ? (!shades->rgb_linear && !shades->rgb && !shades->pixel && !shades->hit_dist && !shades->hit_id && !shades->steps) : true;
+	try { return scene_query(ctx, cams, scenes, n_scenes, src, list_stride, hits, shades, no_output); }
+	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a query"); }
+	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a query"); }
+}
+
+extern "C" {
+
+int lol_gpu_trace_scene_rays(lol_gpu* ctx, const lol_program* scenes, int n_scenes, const float* rays_dev, size_t n, size_t list_stride,
+                             int max_steps, const lol_gpu_hits* out, void* stream) {
+	static const lol_gpu_hits none = {};
+	return scene_query_guarded(ctx, nullptr, scenes, n_scenes, rays_source("scene ray query", rays_dev, n, max_steps, stream), list_stride,
+	                           out ? out : &none, nullptr);
+}
+
+int lol_gpu_trace_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, int w, int h, int max_steps,
+                               const uint32_t* xy_dev, size_t n, size_t list_stride, const lol_gpu_hits* out, void* stream) {
+	static const lol_gpu_hits none = {};
+	return scene_query_guarded(ctx, cams, scenes, n_scenes, pixels_source("scene ray query", cams, w, h, xy_dev, n, max_steps, stream), list_stride,
+	                           out ? out : &none, nullptr);
+}
+
+int lol_gpu_shade_scene_rays(lol_gpu* ctx, const lol_program* scenes, int n_scenes, const float* rays_dev, size_t n, size_t list_stride,
+                             int max_steps, const lol_gpu_shades* out, void* stream) {
+	return scene_query_guarded(ctx, nullptr, scenes, n_scenes, rays_source("scene shading query", rays_dev, n, max_steps, stream), list_stride,
+	                           nullptr, out);
+}
+
+int lol_gpu_shade_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, int w, int h, int max_steps,
+                               const uint32_t* xy_dev, size_t n, size_t list_stride, const lol_gpu_shades* out, void* stream) {
+	return scene_query_guarded(ctx, cams, scenes, n_scenes, pixels_source("scene shading query", cams, w, h, xy_dev, n, max_steps, stream), list_stride,
+	                           nullptr, out);
 }
 }  // extern "C"

@@ -33,6 +33,7 @@
 #include "lol_kernel_light.h"      /* last, and its kernels are instantiated last in lol_gpu.hip: the code objects of the others stay what they are */
 #include "lol_kernel_light_views.h"      /* ... and this one behind it, its kernels behind those, for the same reason */
 #include "lol_kernel_light_update.h"     /* ... and the light updates' behind both */
+#include "lol_kernel_scene_queries.h"    /* ... and the scene queries' behind all three */
 
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>

@@ -324,6 +324,16 @@ def gpu_lib() -> C.CDLL:
         lib.lol_gpu_render_scene_views.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
                                                    C.c_size_t, C.c_size_t, P(Debug), vp]
         lib.lol_gpu_render_scene_views.restype = C.c_int
+        lib.lol_gpu_trace_scene_rays.argtypes = [vp, P(S.Program), C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, P(Hits), vp]
+        lib.lol_gpu_trace_scene_rays.restype = C.c_int
+        lib.lol_gpu_trace_scene_pixels.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
+                                                   C.c_size_t, P(Hits), vp]
+        lib.lol_gpu_trace_scene_pixels.restype = C.c_int
+        lib.lol_gpu_shade_scene_rays.argtypes = [vp, P(S.Program), C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, P(Shades), vp]
+        lib.lol_gpu_shade_scene_rays.restype = C.c_int
+        lib.lol_gpu_shade_scene_pixels.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
+                                                   C.c_size_t, P(Shades), vp]
+        lib.lol_gpu_shade_scene_pixels.restype = C.c_int
         lib.lol_gpu_set_scene_views.argtypes = [vp, C.c_int]
         lib.lol_gpu_set_scene_views.restype = C.c_int
         lib.lol_gpu_scene_views.argtypes = [vp]
@@ -476,6 +486,7 @@ EXPORTED_SYMBOLS = [                                                    # includ
     "lol_gpu_shade_rays", "lol_gpu_shade_pixels", "lol_gpu_set_shade_queries", "lol_gpu_shade_queries", "lol_gpu_memcpy_h2d",
     "lol_gpu_render_scene_views", "lol_gpu_set_scene_views", "lol_gpu_scene_views",
     "lol_gpu_render_scene_views_samples", "lol_gpu_set_scene_view_samples", "lol_gpu_scene_view_samples",
+    "lol_gpu_trace_scene_rays", "lol_gpu_trace_scene_pixels", "lol_gpu_shade_scene_rays", "lol_gpu_shade_scene_pixels",
     "lol_gpu_light_rays", "lol_gpu_light_pixels", "lol_gpu_relight", "lol_gpu_light_views", "lol_gpu_relight_views",
     "lol_gpu_light_update_rays", "lol_gpu_light_update_pixels", "lol_gpu_relight_held", "lol_gpu_relight_views_held",
 ]
@@ -921,6 +932,107 @@ class Renderer:
                 self._ctx, arr, progs, len(items) // k, k, w, h, max_steps, int(samples), C.c_void_p(dst_ptr), pitch, stride, dbg,
                 _stream_arg(stream)))
         del keep
+
+    # ---- scene queries (include/lol_gpu.h, "Scene queries")
+    def _scene_records(self, who: str, scenes, cameras=None, size=None):
+        """(keep, programs, frame cameras or None) of a scene query: scenes as render_scene_views_into takes them; size = (w, h):
+        one camera per scene as there (None: every scene's own)."""
+        items = list(scenes)
+        keep = []                                    # the flattened programs live until the call has copied them
+        progs = (S.Program * max(1, len(items)))()
+        for i, sc in enumerate(items):
+            prog = sc if isinstance(sc, S.Program) else sc.flatten()
+            keep.append(prog)
+            C.memmove(C.byref(progs, i * C.sizeof(S.Program)), C.byref(prog), C.sizeof(S.Program))
+        if size is None:
+            return keep, progs, None
+        w, h = size
+        cams = list(cameras) if cameras is not None else [None] * len(items)
+        if len(cams) != len(items):
+            raise ValueError(who + ": one camera per scene")
+        arr = (S.FrameCamera * max(1, len(items)))()
+        for i, (sc, c) in enumerate(zip(items, cams)):
+            if isinstance(c, S.FrameCamera):
+                fc = c
+            elif isinstance(sc, S.Program):
+                if c is None:
+                    raise ValueError(who + ": a Program has no camera of its own")
+                fc = self.scene.frame_camera(w, h, c)
+            else:
+                fc = sc.frame_camera(w, h, c)
+            C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
+        return keep, progs, arr
+
+    def trace_scene_rays_into(self, scenes, rays_ptr: int, n: int, list_stride: int = 0, max_steps: int = 256, dist_ptr: int = 0,
+                              id_ptr: int = 0, steps_ptr: int = 0, normal_ptr: int = 0, stream: int | None = None):
+        """Asynchronously trace n rays under EACH of len(scenes) scenes of the prepared scene's structure (lol_gpu_trace_scene_rays):
+        element (r, i), at index r n + i of every output, is what trace_rays_into answers for ray i of record r after
+        prepare(scenes[r]).  list_stride = 0: one list of n rays (device memory) serves every record; else record r's list begins
+        list_stride rays behind record r - 1's.  scenes: scene.Scene or scene.Program objects, copied before the call returns."""
+        items = list(scenes)
+        keep, progs, _ = self._scene_records("trace_scene_rays_into", items)
+        hits = Hits(dist_ptr or None, id_ptr or None, steps_ptr or None, normal_ptr or None)
+        self._check(self._lib.lol_gpu_trace_scene_rays(self._ctx, progs, len(items), C.c_void_p(rays_ptr), n, list_stride, max_steps,
+                                                       C.byref(hits), _stream_arg(stream)))
+        del keep
+
+    def trace_scene_pixels_into(self, scenes, xy_ptr: int, n: int, w: int, h: int, list_stride: int = 0, max_steps: int = 256,
+                                dist_ptr: int = 0, id_ptr: int = 0, steps_ptr: int = 0, normal_ptr: int = 0,
+                                stream: int | None = None, cameras=None):
+        """... the primary rays of n pixels (device memory, n x {x, y} uint32) of the w x h frame under each record's own camera
+        (lol_gpu_trace_scene_pixels).  cameras: as render_scene_views_into takes them; None: every scene's own."""
+        items = list(scenes)
+        keep, progs, arr = self._scene_records("trace_scene_pixels_into", items, cameras, (w, h))
+        hits = Hits(dist_ptr or None, id_ptr or None, steps_ptr or None, normal_ptr or None)
+        self._check(self._lib.lol_gpu_trace_scene_pixels(self._ctx, arr, progs, len(items), w, h, max_steps, C.c_void_p(xy_ptr), n,
+                                                         list_stride, C.byref(hits), _stream_arg(stream)))
+        del keep
+
+    def shade_scene_rays_into(self, scenes, rays_ptr: int, n: int, list_stride: int = 0, max_steps: int = 256, rgb_linear_ptr: int = 0,
+                              rgb_ptr: int = 0, pixel_ptr: int = 0, dist_ptr: int = 0, id_ptr: int = 0, steps_ptr: int = 0,
+                              stream: int | None = None):
+        """shade_rays_into under each of len(scenes) scenes (lol_gpu_shade_scene_rays); records, lists and outputs as
+        trace_scene_rays_into."""
+        items = list(scenes)
+        keep, progs, _ = self._scene_records("shade_scene_rays_into", items)
+        out = Shades(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None, dist_ptr or None, id_ptr or None, steps_ptr or None)
+        self._check(self._lib.lol_gpu_shade_scene_rays(self._ctx, progs, len(items), C.c_void_p(rays_ptr), n, list_stride, max_steps,
+                                                       C.byref(out), _stream_arg(stream)))
+        del keep
+
+    def shade_scene_pixels_into(self, scenes, xy_ptr: int, n: int, w: int, h: int, list_stride: int = 0, max_steps: int = 256,
+                                rgb_linear_ptr: int = 0, rgb_ptr: int = 0, pixel_ptr: int = 0, dist_ptr: int = 0, id_ptr: int = 0,
+                                steps_ptr: int = 0, stream: int | None = None, cameras=None):
+        """shade_pixels_into under each record's own scene and camera (lol_gpu_shade_scene_pixels); records as
+        trace_scene_pixels_into."""
+        items = list(scenes)
+        keep, progs, arr = self._scene_records("shade_scene_pixels_into", items, cameras, (w, h))
+        out = Shades(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None, dist_ptr or None, id_ptr or None, steps_ptr or None)
+        self._check(self._lib.lol_gpu_shade_scene_pixels(self._ctx, arr, progs, len(items), w, h, max_steps, C.c_void_p(xy_ptr), n,
+                                                         list_stride, C.byref(out), _stream_arg(stream)))
+        del keep
+
+    def pick_scenes(self, scenes, x: int, y: int, w: int, h: int, cameras=None, max_steps: int = 256) -> list:
+        """What is under pixel (x, y) of the w x h frame in EACH scene: a list of pick()'s dicts in host memory, from one
+        trace_scene_pixels_into call on the context's own stream (waits)."""
+        items = list(scenes)
+        if not (0 <= int(x) < w and 0 <= int(y) < h):
+            raise ValueError("pick_scenes: the pixel lies outside the frame")
+        r = len(items)
+        host = (C.c_uint32 * (2 + 6 * max(1, r)))(int(x), int(y))      # xy | dist [r] | id [r] | steps [r] | normal [3 r]
+        dev = self.malloc(C.sizeof(host))
+        try:
+            self.memcpy_h2d(dev, C.addressof(host), 8)
+            at = lambda k: dev + 4 * (2 + k * r)      # noqa: E731
+            self.trace_scene_pixels_into(items, dev, 1, w, h, 0, max_steps, dist_ptr=at(0), id_ptr=at(1), steps_ptr=at(2),
+                                         normal_ptr=at(3), cameras=cameras)
+            self.sync()
+            self.memcpy_d2h(C.addressof(host), dev, C.sizeof(host))
+        finally:
+            self.free(dev)
+        f = C.cast(host, C.POINTER(C.c_float))
+        return [{"id": int(host[2 + r + i]), "dist": float(f[2 + i]), "steps": int(host[2 + 2 * r + i]),
+                 "normal": tuple(float(f[2 + 3 * r + 3 * i + k]) for k in range(3))} for i in range(r)]
 
     def render_host(self, host_ptr: int, w: int, h: int, max_steps: int = 256, camera: S.Camera | None = None,
                     pitch_bytes: int | None = None):
