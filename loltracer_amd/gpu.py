@@ -114,11 +114,198 @@ def _stream_arg(stream):
     return C.c_void_p(STREAM_DEFAULT if stream == 0 else stream)
 
 
+def _ref(obj):
+    """byref(obj), or NULL for None"""
+    return C.byref(obj) if obj is not None else None
+
+
 class GpuError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"lol_gpu: {_STATUS.get(status, status)}: {message}")
         self.status = status
 
+
+class _ScheduleInfo(C.Structure):    # lol_gpu_testing_schedule_info (include/lol_gpu_testing.h)
+    _fields_ = [("n_tiles", C.c_uint32), ("frames", C.c_uint32), ("sorts", C.c_uint32), ("region_w", C.c_uint32),
+                ("region_h", C.c_uint32), ("w", C.c_uint32), ("n_rows", C.c_uint32)]
+
+
+# The C prototypes, one table per header: function -> (restype, argtypes), in the order the symbol lists below have always had.  A new
+# entry point is declared here and nowhere else; tests/test_cabi_prototypes.py holds every entry, and the struct mirrors above, to the
+# headers' text.  Lists in device memory (rays_dev, xy_dev, the buffers of the two *_batch probes) are c_void_p where the header says
+# float* / uint32_t*: callers pass integer addresses.
+_P, _vp, _int, _size, _str = C.POINTER, C.c_void_p, C.c_int, C.c_size_t, C.c_char_p
+_prog, _cam, _u16p, _u32p = _P(S.Program), _P(S.FrameCamera), _P(C.c_ushort), _P(C.c_uint32)
+
+_LOL_GPU_H = {                                                          # include/lol_gpu.h
+    "lol_gpu_abi_version": (_int, []),
+    "lol_gpu_device_count": (_int, []),
+    "lol_gpu_create": (_int, [_int, _P(_vp)]),
+    "lol_gpu_destroy": (None, [_vp]),
+    "lol_gpu_error": (_str, [_vp]),
+    "lol_gpu_upload_program": (_int, [_vp, _prog]),
+    "lol_gpu_part_rows": (_int, [_int, _P(Rows)]),
+    "lol_gpu_render_device": (_int, [_vp, _cam, _int, _int, _int, _P(Rows), _vp, _size, _P(Debug), _vp]),
+    "lol_gpu_render_host": (_int, [_vp, _cam, _int, _int, _int, _vp, _size]),
+    "lol_gpu_sync": (_int, [_vp]),
+    "lol_gpu_malloc": (_int, [_vp, _size, _P(_vp)]),
+    "lol_gpu_free": (_int, [_vp, _vp]),
+    "lol_gpu_memcpy_d2h": (_int, [_vp, _vp, _vp, _size]),
+    "lol_gpu_kernel_name": (_str, [_vp]),
+    "lol_gpu_set_specialize": (_int, [_vp, _int]),
+    "lol_gpu_specialize_log": (_str, [_vp]),
+    "lol_gpu_specialize_wait": (_int, [_vp]),
+    "lol_gpu_specialize_state": (_int, [_vp, _P(C.c_double)]),
+    "lol_gpu_multi_specialize_wait": (_int, [_vp]),
+    "lol_gpu_compile_offline": (_int, [_prog, _str, _str, _int, _str, _size]),
+    "lol_gpu_set_miss_skip": (_int, [_vp, _int]),
+    "lol_gpu_miss_skip_active": (_int, [_vp]),
+    "lol_gpu_set_exact_skips": (_int, [_vp, C.c_uint]),
+    "lol_gpu_device": (_int, [_vp]),
+    "lol_gpu_set_cull": (_int, [_vp, _int]),
+    "lol_gpu_set_tile_order": (_int, [_vp, _int]),
+    "lol_gpu_tile_order": (_int, [_vp, _P(TileOrderInfo)]),
+    "lol_gpu_render_host_begin": (_int, [_vp, _cam, _int, _int, _int]),
+    "lol_gpu_render_host_end": (_int, [_vp, _vp, _size, _int, _int]),
+    "lol_gpu_render_host_pending": (_int, [_vp]),
+    # several devices (include/lol_gpu.h, "Several devices behind the same boundary")
+    "lol_gpu_multi_create": (_int, [_P(_int), _int, _P(_vp)]),
+    "lol_gpu_multi_destroy": (None, [_vp]),
+    "lol_gpu_multi_error": (_str, [_vp]),
+    "lol_gpu_multi_device_count": (_int, [_vp]),
+    "lol_gpu_multi_context": (_vp, [_vp, _int]),
+    "lol_gpu_multi_upload_program": (_int, [_vp, _prog]),
+    "lol_gpu_choose_band_rows": (_int, [_int, _int]),
+    "lol_gpu_multi_set_band_rows": (_int, [_vp, _int]),
+    "lol_gpu_part_frame_row": (_int, [_int, _P(Rows), _int]),
+    "lol_gpu_multi_render_device": (_int, [_vp, _cam, _int, _int, _int, _vp, _size]),
+    "lol_gpu_multi_render_host": (_int, [_vp, _cam, _int, _int, _int, _vp, _size]),
+    "lol_gpu_multi_sync": (_int, [_vp]),
+    "lol_gpu_multi_malloc": (_int, [_vp, _size, _P(_vp)]),
+    "lol_gpu_multi_free": (_int, [_vp, _vp]),
+    "lol_gpu_multi_memcpy_d2h": (_int, [_vp, _vp, _vp, _size]),
+    "lol_gpu_assemble_parts": (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _size, _vp]),
+    "lol_gpu_multi_set_parts_per_device": (_int, [_vp, _int]),
+    "lol_gpu_multi_set_host_via_root": (_int, [_vp, _int]),
+    "lol_gpu_set_pixel_format": (_int, [_vp, _P(PixelFormat)]),
+    "lol_gpu_render_host_pending_size": (_int, [_vp, _P(_int), _P(_int)]),
+    "lol_gpu_render_host_discard": (_int, [_vp]),
+    "lol_gpu_kernel_key": (_str, [_vp]),
+    "lol_gpu_assemble_parts_at": (_int, [_vp, _vp, _P(Rows), _u32p, _int, _int, _int, _vp, _size, _vp]),
+    "lol_gpu_split_rows": (_int, [_int, _int, _int, _int, _P(Rows)]),
+    "lol_gpu_multi_set_root_band_rows": (_int, [_vp, _int]),
+    "lol_gpu_multi_set_pixel_format": (_int, [_vp, _P(PixelFormat)]),
+    "lol_gpu_multi_set_tile_order": (_int, [_vp, _int]),
+    "lol_gpu_set_frames_in_flight": (_int, [_vp, _int]),
+    "lol_gpu_frames_in_flight": (_int, [_vp]),
+    "lol_gpu_next_stream": (_vp, [_vp]),
+    "lol_gpu_set_specialize_max_ops": (_int, [_vp, C.c_uint]),
+    # supersampling, batches of views and blends
+    "lol_gpu_set_samples": (_int, [_vp, _int]),
+    "lol_gpu_samples": (_int, [_vp]),
+    "lol_gpu_multi_set_samples": (_int, [_vp, _int]),
+    "lol_gpu_set_adaptive_samples": (_int, [_vp, _int]),
+    "lol_gpu_adaptive_samples": (_int, [_vp]),
+    "lol_gpu_render_views": (_int, [_vp, _cam, _int, _int, _int, _int, _vp, _size, _size, _P(Debug), _vp]),
+    "lol_gpu_set_view_batches": (_int, [_vp, _int]),
+    "lol_gpu_view_batches": (_int, [_vp]),
+    "lol_gpu_render_views_samples": (_int, [_vp, _cam, _int, _int, _int, _int, _int, _int, _vp, _size, _size, _P(Debug), _vp]),
+    "lol_gpu_set_view_samples": (_int, [_vp, _int]),
+    "lol_gpu_view_samples": (_int, [_vp]),
+    "lol_gpu_render_views_blend": (_int, [_vp, _cam, _int, _int, _int, _int, _int, _vp, _size, _size, _P(Debug), _vp]),
+    "lol_gpu_set_view_blends": (_int, [_vp, _int]),
+    "lol_gpu_view_blends": (_int, [_vp]),
+    "lol_gpu_render_views_blend_samples": (_int, [_vp, _cam, _int, _int, _int, _int, _int, _int, _vp, _size, _size, _P(Debug), _vp]),
+    "lol_gpu_set_view_blend_samples": (_int, [_vp, _int]),
+    "lol_gpu_view_blend_samples": (_int, [_vp]),
+    # ray queries (include/lol_gpu.h, "Ray queries")
+    "lol_gpu_trace_rays": (_int, [_vp, _vp, _size, _int, _P(Hits), _vp]),
+    "lol_gpu_trace_pixels": (_int, [_vp, _cam, _int, _int, _int, _vp, _size, _P(Hits), _vp]),
+    "lol_gpu_pick": (_int, [_vp, _cam, _int, _int, _int, _int, _int, _P(Hit)]),
+    "lol_gpu_set_ray_queries": (_int, [_vp, _int]),
+    "lol_gpu_ray_queries": (_int, [_vp]),
+    # shading queries (include/lol_gpu.h, "Shading queries")
+    "lol_gpu_shade_rays": (_int, [_vp, _vp, _size, _int, _P(Shades), _vp]),
+    "lol_gpu_shade_pixels": (_int, [_vp, _cam, _int, _int, _int, _vp, _size, _P(Shades), _vp]),
+    "lol_gpu_set_shade_queries": (_int, [_vp, _int]),
+    "lol_gpu_shade_queries": (_int, [_vp]),
+    "lol_gpu_memcpy_h2d": (_int, [_vp, _vp, _vp, _size]),
+    # scene views and scene queries (include/lol_gpu.h, "Scene views", "Scene queries")
+    "lol_gpu_render_scene_views": (_int, [_vp, _cam, _prog, _int, _int, _int, _int, _int, _vp, _size, _size, _P(Debug), _vp]),
+    "lol_gpu_set_scene_views": (_int, [_vp, _int]),
+    "lol_gpu_scene_views": (_int, [_vp]),
+    "lol_gpu_render_scene_views_samples": (_int, [_vp, _cam, _prog, _int, _int, _int, _int, _int, _int, _vp, _size, _size, _P(Debug), _vp]),
+    "lol_gpu_set_scene_view_samples": (_int, [_vp, _int]),
+    "lol_gpu_scene_view_samples": (_int, [_vp]),
+    "lol_gpu_trace_scene_rays": (_int, [_vp, _prog, _int, _vp, _size, _size, _int, _P(Hits), _vp]),
+    "lol_gpu_trace_scene_pixels": (_int, [_vp, _cam, _prog, _int, _int, _int, _int, _vp, _size, _size, _P(Hits), _vp]),
+    "lol_gpu_shade_scene_rays": (_int, [_vp, _prog, _int, _vp, _size, _size, _int, _P(Shades), _vp]),
+    "lol_gpu_shade_scene_pixels": (_int, [_vp, _cam, _prog, _int, _int, _int, _int, _vp, _size, _size, _P(Shades), _vp]),
+    # light passes and relighting (include/lol_gpu.h, "Light passes and relighting")
+    "lol_gpu_light_rays": (_int, [_vp, _vp, _size, _int, _P(LightPasses), _vp]),
+    "lol_gpu_light_pixels": (_int, [_vp, _cam, _int, _int, _int, _vp, _size, _P(LightPasses), _vp]),
+    "lol_gpu_relight": (_int, [_vp, _prog, _P(LightPasses), _size, _P(Relit), _vp]),
+    # relit views (include/lol_gpu.h, "Relit views")
+    "lol_gpu_light_views": (_int, [_vp, _cam, _int, _int, _int, _int, _int, _int, _P(LightPasses), _vp]),
+    "lol_gpu_relight_views": (_int, [_vp, _prog, _P(LightPasses), _int, _int, _int, _int, _int, _P(Relit), _vp]),
+    # light updates (include/lol_gpu.h, "Light updates")
+    "lol_gpu_light_update_rays": (_int, [_vp, _prog, _vp, _size, C.c_uint64, C.c_uint64, _P(LightPasses), _vp]),
+    "lol_gpu_light_update_pixels": (_int, [_vp, _prog, _cam, _int, _int, _vp, _size, C.c_uint64, C.c_uint64, _P(LightPasses), _vp]),
+    "lol_gpu_relight_held": (_int, [_vp, _prog, _prog, _P(LightPasses), _size, _P(Relit), _vp]),
+    "lol_gpu_relight_views_held": (_int, [_vp, _prog, _prog, _P(LightPasses), _int, _int, _int, _int, _int, _P(Relit), _vp]),
+}
+
+_LOL_GPU_DIAG_H = {                                                     # include/lol_gpu_diag.h
+    "lol_gpu_tuning_switches": (_str, []),
+    "lol_gpu_roctx_ranges": (C.c_long, []),
+    "lol_gpu_verify_fast_paths": (_int, [_vp, C.c_float, _P(C.c_ulonglong), _P(C.c_ulonglong)]),
+    "lol_gpu_verify_smin_no_fixup": (_int, [_vp, C.c_float, _P(C.c_ulonglong)]),
+    "lol_gpu_verify_gamma_table": (_int, [_vp, _P(C.c_ulonglong), _P(C.c_float)]),
+    "lol_gpu_cull_bounds": (_int, [_prog, C.c_uint32, _P(C.c_float), _P(C.c_float)]),
+    "lol_gpu_cull_bounds_clusters": (_int, [_prog, C.c_uint32, _P(C.c_float * 4)]),
+    "lol_gpu_powf_batch": (_int, [_vp, _vp, _vp, _vp, _size, _vp]),
+    "lol_gpu_sdf_batch": (_int, [_vp, _vp, _vp, _vp, _size, _vp]),
+    "lol_gpu_compile_offline_samples": (_int, [_prog, _str, _str, _int, _int, _str, _size]),
+    "lol_gpu_adaptive_refined": (_int, [_vp, _P(C.c_int64)]),
+    "lol_gpu_adaptive_pass_ms": (_int, [_vp, _P(C.c_float)]),
+    "lol_gpu_compile_offline_views": (_int, [_prog, _str, _str, _int, _int, _int, _str, _size]),
+    "lol_gpu_compile_offline_view_samples": (_int, [_prog, _str, _str, _int, _int, _int, _str, _size]),
+    "lol_gpu_view_samples_kernel_name": (_str, [_vp, _int, _int]),
+    "lol_gpu_views_refined": (_int, [_vp, _P(C.c_int64)]),
+    "lol_gpu_interp_variant": (_int, [_vp, _P(_int), _P(_int)]),
+    "lol_gpu_compile_offline_view_blends": (_int, [_prog, _str, _str, _int, _int, _int, _str, _size]),
+    "lol_gpu_view_blend_kernel_name": (_str, [_vp, _int]),
+    "lol_gpu_compile_offline_view_blend_samples": (_int, [_prog, _str, _str, _int, _int, _int, _int, _str, _size]),
+    "lol_gpu_view_blend_samples_kernel_name": (_str, [_vp, _int, _int]),
+    "lol_gpu_trace_kernel_name": (_str, [_vp]),
+    "lol_gpu_compile_offline_rays": (_int, [_prog, _str, _str, _int, _int, _int, _int, _str, _size]),
+    "lol_gpu_code_key": (None, [_str, _size, _str]),
+    "lol_gpu_shade_kernel_name": (_str, [_vp]),
+    "lol_gpu_compile_offline_shade": (_int, [_prog, _str, _str, _int, _int, _int, _int, _str, _size]),
+    "lol_gpu_compile_offline_module": (_int, [_prog, _str, _str, _int, C.c_uint, _int, _str, _size]),
+    "lol_gpu_scene_views_kernel_name": (_str, [_vp, _int]),
+    "lol_gpu_scene_views_state": (_int, [_vp]),
+    "lol_gpu_compile_offline_scene_views": (_int, [_prog, _str, _str, _str, _size]),
+    "lol_gpu_interp_fast_paths": (_int, [_vp, _P(_int), _P(C.c_uint), _P(C.c_uint)]),
+    "lol_gpu_shade_math": (_int, [_vp, _P(ShadeMathInfo)]),
+    "lol_gpu_scene_view_samples_kernel_name": (_str, [_vp, _int, _int]),
+    "lol_gpu_compile_offline_scene_view_samples": (_int, [_prog, _str, _str, _str, _size]),
+}
+
+_LOL_GPU_TESTING_H = {                                                  # include/lol_gpu_testing.h
+    "lol_gpu_testing_fail_uploads": (_int, [_vp, _int]),
+    "lol_gpu_testing_fail_first_tier": (_int, [_vp, _int]),
+    "lol_gpu_testing_has_return_clobbering_branch": (_int, [_str, _size]),
+    "lol_gpu_multi_testing_root_stride": (_int, [_vp, _int]),
+    "lol_gpu_multi_testing_force_copier_threads": (_int, [_vp, _int]),
+    "lol_gpu_testing_fail_view_scratch": (_int, [_vp, _int]),
+    "lol_gpu_testing_pixel_cost": (_int, [_vp, _u16p, _size]),
+    "lol_gpu_testing_deal": (_int, [_vp, _u16p, _int, _int, _u32p, _size]),
+    "lol_gpu_testing_sort_tiles": (_int, [_vp, _u32p, _u32p, _u32p, _size, _u32p, _u32p, _u32p]),
+    "lol_gpu_testing_schedule": (_int, [_vp, _P(_ScheduleInfo), _u32p, _u32p, _u32p, _u32p, _size, _u32p, _size]),
+}
+
+EXPORTED_SYMBOLS, DIAG_SYMBOLS, TESTING_SYMBOLS = list(_LOL_GPU_H), list(_LOL_GPU_DIAG_H), list(_LOL_GPU_TESTING_H)
 
 _lib = None
 
@@ -131,379 +318,13 @@ def gpu_lib() -> C.CDLL:
             raise RuntimeError(f"{path} is missing: the HIP extension was not built "
                                "(run __graft_entry__.build()); there is no CPU fallback")
         lib = C.CDLL(path)
-        P = C.POINTER
-        vp = C.c_void_p
-        lib.lol_gpu_abi_version.argtypes = []
-        lib.lol_gpu_abi_version.restype = C.c_int
+        S._bind_prototypes(lib, {"lol_gpu_abi_version": _LOL_GPU_H["lol_gpu_abi_version"]})
         if lib.lol_gpu_abi_version() != LOL_GPU_ABI_VERSION:
             raise RuntimeError(f"{path} speaks ABI version {lib.lol_gpu_abi_version()}, this mirror {LOL_GPU_ABI_VERSION}: "
                                "rebuild (__graft_entry__.build())")
-        lib.lol_gpu_device_count.argtypes = []
-        lib.lol_gpu_device_count.restype = C.c_int
-        lib.lol_gpu_create.argtypes = [C.c_int, P(vp)]
-        lib.lol_gpu_create.restype = C.c_int
-        lib.lol_gpu_destroy.argtypes = [vp]
-        lib.lol_gpu_destroy.restype = None
-        lib.lol_gpu_error.argtypes = [vp]
-        lib.lol_gpu_error.restype = C.c_char_p
-        lib.lol_gpu_upload_program.argtypes = [vp, P(S.Program)]
-        lib.lol_gpu_upload_program.restype = C.c_int
-        lib.lol_gpu_part_rows.argtypes = [C.c_int, P(Rows)]
-        lib.lol_gpu_part_rows.restype = C.c_int
-        lib.lol_gpu_render_device.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, P(Rows),
-                                              vp, C.c_size_t, P(Debug), vp]
-        lib.lol_gpu_render_device.restype = C.c_int
-        lib.lol_gpu_render_host.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
-        lib.lol_gpu_render_host.restype = C.c_int
-        lib.lol_gpu_render_host_begin.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int]
-        lib.lol_gpu_render_host_begin.restype = C.c_int
-        lib.lol_gpu_render_host_end.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int]
-        lib.lol_gpu_render_host_end.restype = C.c_int
-        lib.lol_gpu_render_host_pending.argtypes = [vp]
-        lib.lol_gpu_render_host_pending.restype = C.c_int
-        lib.lol_gpu_render_host_pending_size.argtypes = [vp, P(C.c_int), P(C.c_int)]
-        lib.lol_gpu_render_host_pending_size.restype = C.c_int
-        lib.lol_gpu_render_host_discard.argtypes = [vp]
-        lib.lol_gpu_render_host_discard.restype = C.c_int
-        lib.lol_gpu_set_pixel_format.argtypes = [vp, P(PixelFormat)]
-        lib.lol_gpu_set_pixel_format.restype = C.c_int
-        lib.lol_gpu_kernel_key.argtypes = [vp]
-        lib.lol_gpu_kernel_key.restype = C.c_char_p
-        lib.lol_gpu_code_key.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
-        lib.lol_gpu_code_key.restype = None
-        lib.lol_gpu_roctx_ranges.argtypes = []
-        lib.lol_gpu_roctx_ranges.restype = C.c_long
-        lib.lol_gpu_sync.argtypes = [vp]
-        lib.lol_gpu_sync.restype = C.c_int
-        lib.lol_gpu_set_frames_in_flight.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_frames_in_flight.restype = C.c_int
-        lib.lol_gpu_frames_in_flight.argtypes = [vp]
-        lib.lol_gpu_frames_in_flight.restype = C.c_int
-        lib.lol_gpu_next_stream.argtypes = [vp]
-        lib.lol_gpu_next_stream.restype = vp
-        lib.lol_gpu_tuning_switches.argtypes = []
-        lib.lol_gpu_tuning_switches.restype = C.c_char_p
-        lib.lol_gpu_malloc.argtypes = [vp, C.c_size_t, P(vp)]
-        lib.lol_gpu_malloc.restype = C.c_int
-        lib.lol_gpu_free.argtypes = [vp, vp]
-        lib.lol_gpu_free.restype = C.c_int
-        lib.lol_gpu_memcpy_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-        lib.lol_gpu_memcpy_d2h.restype = C.c_int
-        lib.lol_gpu_memcpy_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-        lib.lol_gpu_memcpy_h2d.restype = C.c_int
-        lib.lol_gpu_kernel_name.argtypes = [vp]
-        lib.lol_gpu_kernel_name.restype = C.c_char_p
-        lib.lol_gpu_set_specialize.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_specialize.restype = C.c_int
-        lib.lol_gpu_set_specialize_max_ops.argtypes = [vp, C.c_uint]
-        lib.lol_gpu_set_specialize_max_ops.restype = C.c_int
-        lib.lol_gpu_specialize_log.argtypes = [vp]
-        lib.lol_gpu_specialize_log.restype = C.c_char_p
-        lib.lol_gpu_specialize_wait.argtypes = [vp]
-        lib.lol_gpu_specialize_wait.restype = C.c_int
-        lib.lol_gpu_specialize_state.argtypes = [vp, P(C.c_double)]
-        lib.lol_gpu_specialize_state.restype = C.c_int
-        lib.lol_gpu_multi_specialize_wait.argtypes = [vp]
-        lib.lol_gpu_multi_specialize_wait.restype = C.c_int
-        lib.lol_gpu_compile_offline.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
-        lib.lol_gpu_compile_offline.restype = C.c_int
-        lib.lol_gpu_compile_offline_samples.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
-        lib.lol_gpu_compile_offline_samples.restype = C.c_int
-        lib.lol_gpu_compile_offline_module.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_uint, C.c_int, C.c_char_p, C.c_size_t]
-        lib.lol_gpu_compile_offline_module.restype = C.c_int
-        lib.lol_gpu_set_samples.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_samples.restype = C.c_int
-        lib.lol_gpu_samples.argtypes = [vp]
-        lib.lol_gpu_samples.restype = C.c_int
-        lib.lol_gpu_set_adaptive_samples.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_adaptive_samples.restype = C.c_int
-        lib.lol_gpu_adaptive_samples.argtypes = [vp]
-        lib.lol_gpu_adaptive_samples.restype = C.c_int
-        lib.lol_gpu_adaptive_refined.argtypes = [vp, P(C.c_int64)]
-        lib.lol_gpu_adaptive_refined.restype = C.c_int
-        lib.lol_gpu_adaptive_pass_ms.argtypes = [vp, P(C.c_float)]
-        lib.lol_gpu_adaptive_pass_ms.restype = C.c_int
-        lib.lol_gpu_render_views.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_size_t,
-                                             P(Debug), vp]
-        lib.lol_gpu_render_views.restype = C.c_int
-        lib.lol_gpu_set_view_batches.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_view_batches.restype = C.c_int
-        lib.lol_gpu_view_batches.argtypes = [vp]
-        lib.lol_gpu_view_batches.restype = C.c_int
-        lib.lol_gpu_compile_offline_views.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
-        lib.lol_gpu_compile_offline_views.restype = C.c_int
-        lib.lol_gpu_render_views_samples.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
-                                                     C.c_size_t, C.c_size_t, P(Debug), vp]
-        lib.lol_gpu_render_views_samples.restype = C.c_int
-        lib.lol_gpu_set_view_samples.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_view_samples.restype = C.c_int
-        lib.lol_gpu_view_samples.argtypes = [vp]
-        lib.lol_gpu_view_samples.restype = C.c_int
-        lib.lol_gpu_compile_offline_view_samples.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p,
-                                                             C.c_size_t]
-        lib.lol_gpu_compile_offline_view_samples.restype = C.c_int
-        lib.lol_gpu_view_samples_kernel_name.argtypes = [vp, C.c_int, C.c_int]
-        lib.lol_gpu_view_samples_kernel_name.restype = C.c_char_p
-        lib.lol_gpu_render_views_blend.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
-                                                   C.c_size_t, P(Debug), vp]
-        lib.lol_gpu_render_views_blend.restype = C.c_int
-        lib.lol_gpu_set_view_blends.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_view_blends.restype = C.c_int
-        lib.lol_gpu_view_blends.argtypes = [vp]
-        lib.lol_gpu_view_blends.restype = C.c_int
-        lib.lol_gpu_compile_offline_view_blends.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p,
-                                                            C.c_size_t]
-        lib.lol_gpu_compile_offline_view_blends.restype = C.c_int
-        lib.lol_gpu_view_blend_kernel_name.argtypes = [vp, C.c_int]
-        lib.lol_gpu_view_blend_kernel_name.restype = C.c_char_p
-        lib.lol_gpu_render_views_blend_samples.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
-                                                           C.c_size_t, C.c_size_t, P(Debug), vp]
-        lib.lol_gpu_render_views_blend_samples.restype = C.c_int
-        lib.lol_gpu_set_view_blend_samples.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_view_blend_samples.restype = C.c_int
-        lib.lol_gpu_view_blend_samples.argtypes = [vp]
-        lib.lol_gpu_view_blend_samples.restype = C.c_int
-        lib.lol_gpu_compile_offline_view_blend_samples.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                                   C.c_char_p, C.c_size_t]
-        lib.lol_gpu_compile_offline_view_blend_samples.restype = C.c_int
-        lib.lol_gpu_view_blend_samples_kernel_name.argtypes = [vp, C.c_int, C.c_int]
-        lib.lol_gpu_view_blend_samples_kernel_name.restype = C.c_char_p
-        # ray queries (include/lol_gpu.h, "Ray queries")
-        lib.lol_gpu_trace_rays.argtypes = [vp, vp, C.c_size_t, C.c_int, P(Hits), vp]
-        lib.lol_gpu_trace_rays.restype = C.c_int
-        lib.lol_gpu_trace_pixels.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, vp, C.c_size_t, P(Hits), vp]
-        lib.lol_gpu_trace_pixels.restype = C.c_int
-        lib.lol_gpu_pick.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(Hit)]
-        lib.lol_gpu_pick.restype = C.c_int
-        lib.lol_gpu_set_ray_queries.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_ray_queries.restype = C.c_int
-        lib.lol_gpu_ray_queries.argtypes = [vp]
-        lib.lol_gpu_ray_queries.restype = C.c_int
-        lib.lol_gpu_trace_kernel_name.argtypes = [vp]
-        lib.lol_gpu_trace_kernel_name.restype = C.c_char_p
-        lib.lol_gpu_compile_offline_rays.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                     C.c_char_p, C.c_size_t]
-        lib.lol_gpu_compile_offline_rays.restype = C.c_int
-        # shading queries (include/lol_gpu.h, "Shading queries")
-        lib.lol_gpu_shade_rays.argtypes = [vp, vp, C.c_size_t, C.c_int, P(Shades), vp]
-        lib.lol_gpu_shade_rays.restype = C.c_int
-        lib.lol_gpu_shade_pixels.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, vp, C.c_size_t, P(Shades), vp]
-        lib.lol_gpu_shade_pixels.restype = C.c_int
-        lib.lol_gpu_set_shade_queries.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_shade_queries.restype = C.c_int
-        lib.lol_gpu_shade_queries.argtypes = [vp]
-        lib.lol_gpu_shade_queries.restype = C.c_int
-        lib.lol_gpu_shade_kernel_name.argtypes = [vp]
-        lib.lol_gpu_shade_kernel_name.restype = C.c_char_p
-        lib.lol_gpu_compile_offline_shade.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                      C.c_char_p, C.c_size_t]
-        lib.lol_gpu_compile_offline_shade.restype = C.c_int
-        # light passes and relighting (include/lol_gpu.h, "Light passes and relighting")
-        lib.lol_gpu_light_rays.argtypes = [vp, vp, C.c_size_t, C.c_int, P(LightPasses), vp]
-        lib.lol_gpu_light_rays.restype = C.c_int
-        lib.lol_gpu_light_pixels.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, vp, C.c_size_t, P(LightPasses), vp]
-        lib.lol_gpu_light_pixels.restype = C.c_int
-        lib.lol_gpu_relight.argtypes = [vp, P(S.Program), P(LightPasses), C.c_size_t, P(Relit), vp]
-        lib.lol_gpu_relight.restype = C.c_int
-        # relit views (include/lol_gpu.h, "Relit views")
-        lib.lol_gpu_light_views.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(LightPasses), vp]
-        lib.lol_gpu_light_views.restype = C.c_int
-        lib.lol_gpu_relight_views.argtypes = [vp, P(S.Program), P(LightPasses), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(Relit), vp]
-        lib.lol_gpu_relight_views.restype = C.c_int
-        # light updates (include/lol_gpu.h, "Light updates")
-        lib.lol_gpu_light_update_rays.argtypes = [vp, P(S.Program), vp, C.c_size_t, C.c_uint64, C.c_uint64, P(LightPasses), vp]
-        lib.lol_gpu_light_update_rays.restype = C.c_int
-        lib.lol_gpu_light_update_pixels.argtypes = [vp, P(S.Program), P(S.FrameCamera), C.c_int, C.c_int, vp, C.c_size_t, C.c_uint64,
-                                                    C.c_uint64, P(LightPasses), vp]
-        lib.lol_gpu_light_update_pixels.restype = C.c_int
-        lib.lol_gpu_relight_held.argtypes = [vp, P(S.Program), P(S.Program), P(LightPasses), C.c_size_t, P(Relit), vp]
-        lib.lol_gpu_relight_held.restype = C.c_int
-        lib.lol_gpu_relight_views_held.argtypes = [vp, P(S.Program), P(S.Program), P(LightPasses), C.c_int, C.c_int, C.c_int, C.c_int,
-                                                   C.c_int, P(Relit), vp]
-        lib.lol_gpu_relight_views_held.restype = C.c_int
-        lib.lol_gpu_render_scene_views.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
-                                                   C.c_size_t, C.c_size_t, P(Debug), vp]
-        lib.lol_gpu_render_scene_views.restype = C.c_int
-        lib.lol_gpu_trace_scene_rays.argtypes = [vp, P(S.Program), C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, P(Hits), vp]
-        lib.lol_gpu_trace_scene_rays.restype = C.c_int
-        lib.lol_gpu_trace_scene_pixels.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
-                                                   C.c_size_t, P(Hits), vp]
-        lib.lol_gpu_trace_scene_pixels.restype = C.c_int
-        lib.lol_gpu_shade_scene_rays.argtypes = [vp, P(S.Program), C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, P(Shades), vp]
-        lib.lol_gpu_shade_scene_rays.restype = C.c_int
-        lib.lol_gpu_shade_scene_pixels.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
-                                                   C.c_size_t, P(Shades), vp]
-        lib.lol_gpu_shade_scene_pixels.restype = C.c_int
-        lib.lol_gpu_set_scene_views.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_scene_views.restype = C.c_int
-        lib.lol_gpu_scene_views.argtypes = [vp]
-        lib.lol_gpu_scene_views.restype = C.c_int
-        lib.lol_gpu_scene_views_kernel_name.argtypes = [vp, C.c_int]
-        lib.lol_gpu_scene_views_kernel_name.restype = C.c_char_p
-        lib.lol_gpu_scene_views_state.argtypes = [vp]
-        lib.lol_gpu_scene_views_state.restype = C.c_int
-        lib.lol_gpu_interp_fast_paths.argtypes = [vp, P(C.c_int), P(C.c_uint), P(C.c_uint)]
-        lib.lol_gpu_interp_fast_paths.restype = C.c_int
-        if hasattr(lib, "lol_gpu_shade_math"):       # (a library named by LOL_GPU_LIB for an A/B run may be the parent commit's)
-            lib.lol_gpu_shade_math.argtypes = [vp, P(ShadeMathInfo)]
-            lib.lol_gpu_shade_math.restype = C.c_int
-        lib.lol_gpu_compile_offline_scene_views.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
-        lib.lol_gpu_compile_offline_scene_views.restype = C.c_int
-        lib.lol_gpu_render_scene_views_samples.argtypes = [vp, P(S.FrameCamera), P(S.Program), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                           C.c_int, vp, C.c_size_t, C.c_size_t, P(Debug), vp]
-        lib.lol_gpu_render_scene_views_samples.restype = C.c_int
-        lib.lol_gpu_set_scene_view_samples.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_scene_view_samples.restype = C.c_int
-        lib.lol_gpu_scene_view_samples.argtypes = [vp]
-        lib.lol_gpu_scene_view_samples.restype = C.c_int
-        lib.lol_gpu_scene_view_samples_kernel_name.argtypes = [vp, C.c_int, C.c_int]
-        lib.lol_gpu_scene_view_samples_kernel_name.restype = C.c_char_p
-        lib.lol_gpu_compile_offline_scene_view_samples.argtypes = [P(S.Program), C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
-        lib.lol_gpu_compile_offline_scene_view_samples.restype = C.c_int
-        lib.lol_gpu_views_refined.argtypes = [vp, P(C.c_int64)]
-        lib.lol_gpu_views_refined.restype = C.c_int
-        lib.lol_gpu_interp_variant.argtypes = [vp, P(C.c_int), P(C.c_int)]
-        lib.lol_gpu_interp_variant.restype = C.c_int
-        lib.lol_gpu_testing_fail_view_scratch.argtypes = [vp, C.c_int]
-        lib.lol_gpu_testing_fail_view_scratch.restype = C.c_int
-        lib.lol_gpu_multi_set_samples.argtypes = [vp, C.c_int]
-        lib.lol_gpu_multi_set_samples.restype = C.c_int
-        lib.lol_gpu_verify_fast_paths.argtypes = [vp, C.c_float, P(C.c_ulonglong), P(C.c_ulonglong)]
-        lib.lol_gpu_verify_fast_paths.restype = C.c_int
-        lib.lol_gpu_verify_smin_no_fixup.argtypes = [vp, C.c_float, P(C.c_ulonglong)]
-        lib.lol_gpu_verify_smin_no_fixup.restype = C.c_int
-        lib.lol_gpu_verify_gamma_table.argtypes = [vp, P(C.c_ulonglong), P(C.c_float)]
-        lib.lol_gpu_verify_gamma_table.restype = C.c_int
-        lib.lol_gpu_powf_batch.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
-        lib.lol_gpu_powf_batch.restype = C.c_int
-        lib.lol_gpu_set_miss_skip.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_miss_skip.restype = C.c_int
-        lib.lol_gpu_set_exact_skips.argtypes = [vp, C.c_uint]
-        lib.lol_gpu_set_exact_skips.restype = C.c_int
-        lib.lol_gpu_miss_skip_active.argtypes = [vp]
-        lib.lol_gpu_miss_skip_active.restype = C.c_int
-        lib.lol_gpu_sdf_batch.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
-        lib.lol_gpu_sdf_batch.restype = C.c_int
-        lib.lol_gpu_cull_bounds.argtypes = [P(S.Program), C.c_uint32, P(C.c_float), P(C.c_float)]
-        lib.lol_gpu_cull_bounds.restype = C.c_int
-        lib.lol_gpu_cull_bounds_clusters.argtypes = [P(S.Program), C.c_uint32, P(C.c_float * 4)]
-        lib.lol_gpu_cull_bounds_clusters.restype = C.c_int
-        lib.lol_gpu_set_cull.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_cull.restype = C.c_int
-        lib.lol_gpu_set_tile_order.argtypes = [vp, C.c_int]
-        lib.lol_gpu_set_tile_order.restype = C.c_int
-        lib.lol_gpu_tile_order.argtypes = [vp, P(TileOrderInfo)]
-        lib.lol_gpu_tile_order.restype = C.c_int
-        lib.lol_gpu_device.argtypes = [vp]
-        lib.lol_gpu_device.restype = C.c_int
-        # several devices (include/lol_gpu.h, "Several devices behind the same boundary")
-        lib.lol_gpu_multi_create.argtypes = [P(C.c_int), C.c_int, P(vp)]
-        lib.lol_gpu_multi_create.restype = C.c_int
-        lib.lol_gpu_multi_destroy.argtypes = [vp]
-        lib.lol_gpu_multi_destroy.restype = None
-        lib.lol_gpu_multi_error.argtypes = [vp]
-        lib.lol_gpu_multi_error.restype = C.c_char_p
-        lib.lol_gpu_multi_device_count.argtypes = [vp]
-        lib.lol_gpu_multi_device_count.restype = C.c_int
-        lib.lol_gpu_multi_context.argtypes = [vp, C.c_int]
-        lib.lol_gpu_multi_context.restype = vp
-        lib.lol_gpu_multi_upload_program.argtypes = [vp, P(S.Program)]
-        lib.lol_gpu_multi_upload_program.restype = C.c_int
-        lib.lol_gpu_choose_band_rows.argtypes = [C.c_int, C.c_int]
-        lib.lol_gpu_choose_band_rows.restype = C.c_int
-        lib.lol_gpu_multi_set_band_rows.argtypes = [vp, C.c_int]
-        lib.lol_gpu_multi_set_band_rows.restype = C.c_int
-        lib.lol_gpu_part_frame_row.argtypes = [C.c_int, P(Rows), C.c_int]
-        lib.lol_gpu_part_frame_row.restype = C.c_int
-        lib.lol_gpu_multi_render_device.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
-        lib.lol_gpu_multi_render_device.restype = C.c_int
-        lib.lol_gpu_multi_render_host.argtypes = [vp, P(S.FrameCamera), C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
-        lib.lol_gpu_multi_render_host.restype = C.c_int
-        lib.lol_gpu_multi_set_parts_per_device.argtypes = [vp, C.c_int]
-        lib.lol_gpu_multi_set_parts_per_device.restype = C.c_int
-        lib.lol_gpu_multi_set_host_via_root.argtypes = [vp, C.c_int]
-        lib.lol_gpu_multi_set_host_via_root.restype = C.c_int
-        lib.lol_gpu_multi_sync.argtypes = [vp]
-        lib.lol_gpu_multi_sync.restype = C.c_int
-        lib.lol_gpu_multi_malloc.argtypes = [vp, C.c_size_t, P(vp)]
-        lib.lol_gpu_multi_malloc.restype = C.c_int
-        lib.lol_gpu_multi_free.argtypes = [vp, vp]
-        lib.lol_gpu_multi_free.restype = C.c_int
-        lib.lol_gpu_multi_memcpy_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-        lib.lol_gpu_multi_memcpy_d2h.restype = C.c_int
-        lib.lol_gpu_assemble_parts.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]
-        lib.lol_gpu_assemble_parts.restype = C.c_int
-        lib.lol_gpu_assemble_parts_at.argtypes = [vp, vp, P(Rows), P(C.c_uint32), C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]
-        lib.lol_gpu_assemble_parts_at.restype = C.c_int
-        lib.lol_gpu_split_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, P(Rows)]
-        lib.lol_gpu_split_rows.restype = C.c_int
-        lib.lol_gpu_multi_set_root_band_rows.argtypes = [vp, C.c_int]
-        lib.lol_gpu_multi_set_root_band_rows.restype = C.c_int
-        lib.lol_gpu_multi_set_pixel_format.argtypes = [vp, P(PixelFormat)]
-        lib.lol_gpu_multi_set_pixel_format.restype = C.c_int
-        lib.lol_gpu_multi_set_tile_order.argtypes = [vp, C.c_int]
-        lib.lol_gpu_multi_set_tile_order.restype = C.c_int
-        # include/lol_gpu_testing.h
-        lib.lol_gpu_testing_fail_uploads.argtypes = [vp, C.c_int]
-        lib.lol_gpu_testing_fail_uploads.restype = C.c_int
-        lib.lol_gpu_testing_fail_first_tier.argtypes = [vp, C.c_int]
-        lib.lol_gpu_testing_fail_first_tier.restype = C.c_int
-        lib.lol_gpu_testing_has_return_clobbering_branch.argtypes = [C.c_char_p, C.c_size_t]
-        lib.lol_gpu_testing_has_return_clobbering_branch.restype = C.c_int
-        lib.lol_gpu_multi_testing_root_stride.argtypes = [vp, C.c_int]
-        lib.lol_gpu_multi_testing_root_stride.restype = C.c_int
-        lib.lol_gpu_multi_testing_force_copier_threads.argtypes = [vp, C.c_int]
-        lib.lol_gpu_multi_testing_force_copier_threads.restype = C.c_int
+        S._bind_prototypes(lib, _LOL_GPU_H, _LOL_GPU_DIAG_H, _LOL_GPU_TESTING_H)
         _lib = lib
     return _lib
-
-
-TESTING_SYMBOLS = ["lol_gpu_testing_fail_uploads", "lol_gpu_testing_fail_first_tier", "lol_gpu_testing_has_return_clobbering_branch", "lol_gpu_multi_testing_root_stride",
-                   "lol_gpu_multi_testing_force_copier_threads", "lol_gpu_testing_fail_view_scratch", "lol_gpu_testing_pixel_cost",
-                   "lol_gpu_testing_deal", "lol_gpu_testing_sort_tiles", "lol_gpu_testing_schedule"]      # include/lol_gpu_testing.h
-
-EXPORTED_SYMBOLS = [                                                    # include/lol_gpu.h
-    "lol_gpu_abi_version", "lol_gpu_device_count", "lol_gpu_create", "lol_gpu_destroy", "lol_gpu_error",
-    "lol_gpu_upload_program", "lol_gpu_part_rows", "lol_gpu_render_device", "lol_gpu_render_host", "lol_gpu_sync",
-    "lol_gpu_malloc", "lol_gpu_free", "lol_gpu_memcpy_d2h", "lol_gpu_kernel_name", "lol_gpu_set_specialize",
-    "lol_gpu_specialize_log", "lol_gpu_specialize_wait", "lol_gpu_specialize_state", "lol_gpu_multi_specialize_wait",
-    "lol_gpu_compile_offline", "lol_gpu_set_miss_skip", "lol_gpu_miss_skip_active", "lol_gpu_set_exact_skips", "lol_gpu_device",
-    "lol_gpu_set_cull", "lol_gpu_set_tile_order", "lol_gpu_tile_order", "lol_gpu_render_host_begin", "lol_gpu_render_host_end",
-    "lol_gpu_render_host_pending", "lol_gpu_multi_create", "lol_gpu_multi_destroy", "lol_gpu_multi_error",
-    "lol_gpu_multi_device_count", "lol_gpu_multi_context", "lol_gpu_multi_upload_program", "lol_gpu_choose_band_rows",
-    "lol_gpu_multi_set_band_rows", "lol_gpu_part_frame_row", "lol_gpu_multi_render_device", "lol_gpu_multi_render_host",
-    "lol_gpu_multi_sync", "lol_gpu_multi_malloc", "lol_gpu_multi_free", "lol_gpu_multi_memcpy_d2h", "lol_gpu_assemble_parts",
-    "lol_gpu_multi_set_parts_per_device", "lol_gpu_multi_set_host_via_root", "lol_gpu_set_pixel_format",
-    "lol_gpu_render_host_pending_size", "lol_gpu_render_host_discard", "lol_gpu_kernel_key", "lol_gpu_assemble_parts_at",
-    "lol_gpu_split_rows", "lol_gpu_multi_set_root_band_rows", "lol_gpu_multi_set_pixel_format", "lol_gpu_multi_set_tile_order",
-    "lol_gpu_set_frames_in_flight", "lol_gpu_frames_in_flight", "lol_gpu_next_stream", "lol_gpu_set_specialize_max_ops",
-    "lol_gpu_set_samples", "lol_gpu_samples", "lol_gpu_multi_set_samples", "lol_gpu_set_adaptive_samples",
-    "lol_gpu_adaptive_samples", "lol_gpu_render_views", "lol_gpu_set_view_batches", "lol_gpu_view_batches",
-    "lol_gpu_render_views_samples", "lol_gpu_set_view_samples", "lol_gpu_view_samples",
-    "lol_gpu_render_views_blend", "lol_gpu_set_view_blends", "lol_gpu_view_blends",
-    "lol_gpu_render_views_blend_samples", "lol_gpu_set_view_blend_samples", "lol_gpu_view_blend_samples",
-    "lol_gpu_trace_rays", "lol_gpu_trace_pixels", "lol_gpu_pick", "lol_gpu_set_ray_queries", "lol_gpu_ray_queries",
-    "lol_gpu_shade_rays", "lol_gpu_shade_pixels", "lol_gpu_set_shade_queries", "lol_gpu_shade_queries", "lol_gpu_memcpy_h2d",
-    "lol_gpu_render_scene_views", "lol_gpu_set_scene_views", "lol_gpu_scene_views",
-    "lol_gpu_render_scene_views_samples", "lol_gpu_set_scene_view_samples", "lol_gpu_scene_view_samples",
-    "lol_gpu_trace_scene_rays", "lol_gpu_trace_scene_pixels", "lol_gpu_shade_scene_rays", "lol_gpu_shade_scene_pixels",
-    "lol_gpu_light_rays", "lol_gpu_light_pixels", "lol_gpu_relight", "lol_gpu_light_views", "lol_gpu_relight_views",
-    "lol_gpu_light_update_rays", "lol_gpu_light_update_pixels", "lol_gpu_relight_held", "lol_gpu_relight_views_held",
-]
-
-DIAG_SYMBOLS = [                                                        # include/lol_gpu_diag.h
-    "lol_gpu_tuning_switches", "lol_gpu_roctx_ranges", "lol_gpu_verify_fast_paths", "lol_gpu_verify_smin_no_fixup",
-    "lol_gpu_verify_gamma_table", "lol_gpu_cull_bounds", "lol_gpu_cull_bounds_clusters", "lol_gpu_powf_batch",
-    "lol_gpu_sdf_batch", "lol_gpu_compile_offline_samples", "lol_gpu_adaptive_refined", "lol_gpu_adaptive_pass_ms",
-    "lol_gpu_compile_offline_views", "lol_gpu_compile_offline_view_samples", "lol_gpu_view_samples_kernel_name",
-    "lol_gpu_views_refined", "lol_gpu_interp_variant", "lol_gpu_compile_offline_view_blends", "lol_gpu_view_blend_kernel_name",
-    "lol_gpu_compile_offline_view_blend_samples", "lol_gpu_view_blend_samples_kernel_name",
-    "lol_gpu_trace_kernel_name", "lol_gpu_compile_offline_rays", "lol_gpu_code_key",
-    "lol_gpu_shade_kernel_name", "lol_gpu_compile_offline_shade", "lol_gpu_compile_offline_module",
-    "lol_gpu_scene_views_kernel_name", "lol_gpu_scene_views_state", "lol_gpu_compile_offline_scene_views",
-    "lol_gpu_interp_fast_paths", "lol_gpu_shade_math",
-    "lol_gpu_scene_view_samples_kernel_name", "lol_gpu_compile_offline_scene_view_samples",
-]
 
 
 def tuning_switches() -> str:
@@ -593,26 +414,26 @@ def compile_offline_shade(program: S.Program, out_base: str, enable: bool = True
                     view_batches=view_batches, view_samples=view_samples, view_blend_samples=view_blend_samples, ray_queries=ray_queries)
 
 
+def _offline_structure(compile_fn, program, out_base, arch) -> str:
+    log = C.create_string_buffer(1 << 16)
+    st = compile_fn(C.byref(program), arch.encode(), os.fsencode(out_base), log, len(log))
+    if st != LOL_GPU_OK:
+        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
+    return log.value.decode(errors="replace")
+
+
 def compile_offline_scene_views(program: S.Program, out_base: str, arch: str = "gfx950") -> str:
     """hipRTC-compile the STRUCTURE module of `program` (Renderer.set_scene_views) without a device: writes out_base.hip and
     out_base.co and returns the compiler log.  The source depends on the program's structure alone — opcodes, ids and counts — so
     two programs of one structure give the same two files, byte for byte."""
-    log = C.create_string_buffer(1 << 16)
-    st = gpu_lib().lol_gpu_compile_offline_scene_views(C.byref(program), arch.encode(), os.fsencode(out_base), log, len(log))
-    if st != LOL_GPU_OK:
-        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
-    return log.value.decode(errors="replace")
+    return _offline_structure(gpu_lib().lol_gpu_compile_offline_scene_views, program, out_base, arch)
 
 
 def compile_offline_scene_view_samples(program: S.Program, out_base: str, arch: str = "gfx950") -> str:
     """compile_offline_scene_views for the structure module that Renderer.set_scene_view_samples asks for: the same SDF and the two
     kernels of that module, and lol_render_param_batch_aa / lol_render_param_batch_aa_lin behind them.  Another source than
     compile_offline_scene_views writes, hence another code object; it too depends on the program's structure alone."""
-    log = C.create_string_buffer(1 << 16)
-    st = gpu_lib().lol_gpu_compile_offline_scene_view_samples(C.byref(program), arch.encode(), os.fsencode(out_base), log, len(log))
-    if st != LOL_GPU_OK:
-        raise GpuError(st, "hipRTC compile failed:\n" + log.value.decode(errors="replace"))
-    return log.value.decode(errors="replace")
+    return _offline_structure(gpu_lib().lol_gpu_compile_offline_scene_view_samples, program, out_base, arch)
 
 
 MAX_VIEWS = 4096                     # LOL_GPU_MAX_VIEWS
@@ -620,7 +441,7 @@ MAX_BLEND = 16                       # LOL_GPU_MAX_BLEND
 
 
 def part_rows(h: int, rows: Rows | None) -> int:
-    return gpu_lib().lol_gpu_part_rows(h, C.byref(rows) if rows is not None else None)
+    return gpu_lib().lol_gpu_part_rows(h, _ref(rows))
 
 
 def split_rows(n_parts: int, band_rows: int, root_band_rows: int = 0, root_stride: int = 1) -> list:
@@ -661,6 +482,30 @@ class Renderer:
         if st != LOL_GPU_OK:
             raise GpuError(st, self._lib.lol_gpu_error(self._ctx).decode())
 
+    def _frame_camera(self, frame_camera, w: int, h: int, camera):
+        """frame_camera, or the prepared scene's for a w x h frame under `camera` (None: the scene's own)"""
+        return frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+
+    def _camera_array(self, cameras, w: int, h: int):
+        """scene.Camera or ready scene.FrameCamera objects as one ctypes array of FrameCamera for w x h frames (never of length 0)"""
+        arr = (S.FrameCamera * max(1, len(cameras)))()
+        for i, c in enumerate(cameras):
+            fc = c if isinstance(c, S.FrameCamera) else self.scene.frame_camera(w, h, c)
+            C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
+        return arr
+
+    @staticmethod
+    def _look_program(look):
+        """A `look` or `held` argument — a scene.Scene (flattened here), a ready scene.Program or None — as a Program or None.  The
+        caller keeps the result until its C call has returned: a flattened program's tables go when the object does."""
+        return look if look is None or isinstance(look, S.Program) else look.flatten()
+
+    @staticmethod
+    def _pitch_and_stride(w: int, h: int, pitch_bytes, view_stride_bytes):
+        """the batch methods' defaults: dense rows, dense views"""
+        pitch = pitch_bytes if pitch_bytes is not None else w * 4
+        return pitch, view_stride_bytes if view_stride_bytes is not None else h * pitch
+
     # render_prepare (renderer.h:25): flatten + upload the scene
     def prepare(self, scene: S.Scene, wait: bool = True):
         """wait=True (tests, benchmarks): also wait for the scene's own kernel, so that the frames that follow all run it.
@@ -695,13 +540,10 @@ class Renderer:
                     rows: Rows | None = None, pitch_bytes: int | None = None, debug: Debug | None = None,
                     stream: int | None = None, frame_camera: S.FrameCamera | None = None):
         """Asynchronously render (a part of) a frame into device memory at dst_ptr."""
-        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        fc = self._frame_camera(frame_camera, w, h, camera)
         self._check(self._lib.lol_gpu_render_device(
-            self._ctx, C.byref(fc), w, h, max_steps,
-            C.byref(rows) if rows is not None else None,
-            C.c_void_p(dst_ptr), pitch_bytes if pitch_bytes is not None else w * 4,
-            C.byref(debug) if debug is not None else None,
-            _stream_arg(stream)))
+            self._ctx, C.byref(fc), w, h, max_steps, _ref(rows), C.c_void_p(dst_ptr), pitch_bytes if pitch_bytes is not None else w * 4,
+            _ref(debug), _stream_arg(stream)))
 
     def set_view_batches(self, enable: bool):
         """Before prepare(): the scene's own module also carries the batch kernel (lol_render_spec_batch); without it — and until
@@ -753,13 +595,9 @@ class Renderer:
         samples = 2 or 4 (and adaptive = a contrast 0 ... 255): the supersampled batch of lol_gpu_render_views_samples — view v is the
         frame of set_samples(samples) / set_adaptive_samples(adaptive), whatever this renderer's own set_samples says."""
         cams = list(cameras)
-        arr = (S.FrameCamera * max(1, len(cams)))()
-        for i, c in enumerate(cams):
-            fc = c if isinstance(c, S.FrameCamera) else self.scene.frame_camera(w, h, c)
-            C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
-        pitch = pitch_bytes if pitch_bytes is not None else w * 4
-        stride = view_stride_bytes if view_stride_bytes is not None else h * pitch
-        dbg = C.byref(debug) if debug is not None else None
+        arr = self._camera_array(cams, w, h)
+        pitch, stride = self._pitch_and_stride(w, h, pitch_bytes, view_stride_bytes)
+        dbg = _ref(debug)
         if samples == 1 and adaptive == -1:
             self._check(self._lib.lol_gpu_render_views(
                 self._ctx, arr, len(cams), w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride, dbg, _stream_arg(stream)))
@@ -811,13 +649,9 @@ class Renderer:
         k = int(cameras_per_view)
         if k < 1 or len(cams) % k:
             raise ValueError("render_blended_views_into: len(cameras) must be a multiple of cameras_per_view")
-        arr = (S.FrameCamera * max(1, len(cams)))()
-        for i, c in enumerate(cams):
-            fc = c if isinstance(c, S.FrameCamera) else self.scene.frame_camera(w, h, c)
-            C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
-        pitch = pitch_bytes if pitch_bytes is not None else w * 4
-        stride = view_stride_bytes if view_stride_bytes is not None else h * pitch
-        dbg = C.byref(debug) if debug is not None else None
+        arr = self._camera_array(cams, w, h)
+        pitch, stride = self._pitch_and_stride(w, h, pitch_bytes, view_stride_bytes)
+        dbg = _ref(debug)
         if samples == 1:
             self._check(self._lib.lol_gpu_render_views_blend(
                 self._ctx, arr, len(cams) // k, k, w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride, dbg, _stream_arg(stream)))
@@ -902,28 +736,9 @@ class Renderer:
         k = int(cameras_per_view)
         if k < 1 or len(items) % k:
             raise ValueError("render_scene_views_into: len(scenes) must be a multiple of cameras_per_view")
-        cams = list(cameras) if cameras is not None else [None] * len(items)
-        if len(cams) != len(items):
-            raise ValueError("render_scene_views_into: one camera per scene")
-        keep = []                                    # the flattened programs live until the call has copied them
-        progs = (S.Program * max(1, len(items)))()
-        arr = (S.FrameCamera * max(1, len(items)))()
-        for i, (sc, c) in enumerate(zip(items, cams)):
-            prog = sc if isinstance(sc, S.Program) else sc.flatten()
-            keep.append(prog)
-            C.memmove(C.byref(progs, i * C.sizeof(S.Program)), C.byref(prog), C.sizeof(S.Program))
-            if isinstance(c, S.FrameCamera):
-                fc = c
-            elif isinstance(sc, S.Program):
-                if c is None:
-                    raise ValueError("render_scene_views_into: a Program has no camera of its own")
-                fc = self.scene.frame_camera(w, h, c)
-            else:
-                fc = sc.frame_camera(w, h, c)
-            C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
-        pitch = pitch_bytes if pitch_bytes is not None else w * 4
-        stride = view_stride_bytes if view_stride_bytes is not None else h * pitch
-        dbg = C.byref(debug) if debug is not None else None
+        keep, progs, arr = self._scene_records("render_scene_views_into", items, cameras, (w, h))
+        pitch, stride = self._pitch_and_stride(w, h, pitch_bytes, view_stride_bytes)
+        dbg = _ref(debug)
         if int(samples) == 1:
             self._check(self._lib.lol_gpu_render_scene_views(
                 self._ctx, arr, progs, len(items) // k, k, w, h, max_steps, C.c_void_p(dst_ptr), pitch, stride, dbg, _stream_arg(stream)))
@@ -935,9 +750,12 @@ class Renderer:
 
     # ---- scene queries (include/lol_gpu.h, "Scene queries")
     def _scene_records(self, who: str, scenes, cameras=None, size=None):
-        """(keep, programs, frame cameras or None) of a scene query: scenes as render_scene_views_into takes them; size = (w, h):
-        one camera per scene as there (None: every scene's own)."""
+        """(keep, programs, frame cameras or None) of the records of render_scene_views_into (`who`, for its errors) or of a scene
+        query: scenes as render_scene_views_into takes them; size = (w, h): one camera per scene as there (None: every scene's own)."""
         items = list(scenes)
+        cams = list(cameras) if cameras is not None else [None] * len(items)
+        if size is not None and len(cams) != len(items):
+            raise ValueError(who + ": one camera per scene")
         keep = []                                    # the flattened programs live until the call has copied them
         progs = (S.Program * max(1, len(items)))()
         for i, sc in enumerate(items):
@@ -947,9 +765,6 @@ class Renderer:
         if size is None:
             return keep, progs, None
         w, h = size
-        cams = list(cameras) if cameras is not None else [None] * len(items)
-        if len(cams) != len(items):
-            raise ValueError(who + ": one camera per scene")
         arr = (S.FrameCamera * max(1, len(items)))()
         for i, (sc, c) in enumerate(zip(items, cams)):
             if isinstance(c, S.FrameCamera):
@@ -1066,7 +881,7 @@ class Renderer:
         """The surface's SDL_PixelFormat (None = XRGB8888); raises for palettised / non-32-bit formats."""
         if isinstance(fmt, str):
             fmt = PIXEL_FORMATS[fmt]
-        self._check(self._lib.lol_gpu_set_pixel_format(self._ctx, C.byref(fmt) if fmt is not None else None))
+        self._check(self._lib.lol_gpu_set_pixel_format(self._ctx, _ref(fmt)))
 
 
     def kernel_key(self) -> str:
@@ -1080,10 +895,7 @@ class Renderer:
         """lol_gpu_testing_pixel_cost: the steps every pixel of the repeated view's recording frame ran, (n_rows, w) uint16."""
         import numpy as np
         out = np.zeros((n_rows, w), dtype=np.uint16)
-        # (bound here, not in gpu_lib(): a library given by LOL_GPU_LIB for an A/B may be a build from before this symbol)
-        fn = self._lib.lol_gpu_testing_pixel_cost
-        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_size_t], C.c_int
-        self._check(fn(self._ctx, out.ctypes.data, out.size))
+        self._check(self._lib.lol_gpu_testing_pixel_cost(self._ctx, out.ctypes.data_as(_u16p), out.size))
         return out
 
     def testing_deal(self, cost, w: int, n_rows: int):
@@ -1095,9 +907,8 @@ class Renderer:
         if cost is not None:
             cost = np.ascontiguousarray(cost, dtype=np.uint16)
             assert cost.shape == (n_rows, w)
-        fn = self._lib.lol_gpu_testing_deal                         # (bound here, like testing_pixel_cost)
-        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t], C.c_int
-        self._check(fn(self._ctx, cost.ctypes.data if cost is not None else None, w, n_rows, out.ctypes.data, out.size))
+        self._check(self._lib.lol_gpu_testing_deal(self._ctx, cost.ctypes.data_as(_u16p) if cost is not None else None, w, n_rows,
+                                                   out.ctypes.data_as(_u32p), out.size))
         return out
 
     def testing_sort_tiles(self, cost, order_in, lanes=None):
@@ -1112,10 +923,9 @@ class Renderer:
             lanes = np.ascontiguousarray(lanes, dtype=np.uint32)
             assert lanes.shape == (n * 64,)
         order_out, keys, starts = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros(1024, dtype=np.uint32)
-        fn = self._lib.lol_gpu_testing_sort_tiles
-        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int
-        self._check(fn(self._ctx, cost.ctypes.data, order_in.ctypes.data, lanes.ctypes.data if lanes is not None else None, n,
-                       order_out.ctypes.data, keys.ctypes.data, starts.ctypes.data))
+        u32 = lambda a: a.ctypes.data_as(_u32p) if a is not None else None      # noqa: E731
+        self._check(self._lib.lol_gpu_testing_sort_tiles(self._ctx, u32(cost), u32(order_in), u32(lanes), n, u32(order_out), u32(keys),
+                                                         u32(starts)))
         return order_out, keys, starts
 
     def testing_schedule(self):
@@ -1123,19 +933,18 @@ class Renderer:
         frame went out in a fixed order.  Waits for the device; changes nothing."""
         import numpy as np
         fn = self._lib.lol_gpu_testing_schedule
-        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p, C.c_size_t], C.c_int
-        info = (C.c_uint32 * 7)()
-        rc = fn(self._ctx, info, None, None, None, None, 0, None, 0)
+        info = _ScheduleInfo()
+        rc = fn(self._ctx, C.byref(info), None, None, None, None, 0, None, 0)
         if rc == -3:                                                # LOL_GPU_ERR_ARG: no table
             return None
         self._check(rc)
-        n = int(info[0])
+        n = int(info.n_tiles)
         t = {k: np.zeros(n, dtype=np.uint32) for k in ("order", "order_before", "keys", "cost")}
         lanes = np.zeros(n * 64, dtype=np.uint32)
-        self._check(fn(self._ctx, info, t["order"].ctypes.data, t["order_before"].ctypes.data, t["keys"].ctypes.data, t["cost"].ctypes.data, n,
-                       lanes.ctypes.data, lanes.size))
-        names = ("n_tiles", "frames", "sorts", "region_w", "region_h", "w", "n_rows")
-        return dict({k: int(v) for k, v in zip(names, info)}, lanes=lanes, **t)
+        u32 = lambda a: a.ctypes.data_as(_u32p)                     # noqa: E731
+        self._check(fn(self._ctx, C.byref(info), u32(t["order"]), u32(t["order_before"]), u32(t["keys"]), u32(t["cost"]), n, u32(lanes),
+                       lanes.size))
+        return dict({k: int(getattr(info, k)) for k, _ in _ScheduleInfo._fields_}, lanes=lanes, **t)
 
     def testing_fail_uploads(self, n: int):
         """include/lol_gpu_testing.h: the next n uploads fail at their copy step."""
@@ -1265,7 +1074,7 @@ class Renderer:
                           frame_camera: S.FrameCamera | None = None):
         """Asynchronously trace the primary rays of n pixels (device memory, n x {x, y} uint32) of the w x h frame under the
         camera: what a frame's lol_gpu_debug planes hold for those pixels, and the normal."""
-        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        fc = self._frame_camera(frame_camera, w, h, camera)
         hits = Hits(dist_ptr or None, id_ptr or None, steps_ptr or None, normal_ptr or None)
         self._check(self._lib.lol_gpu_trace_pixels(self._ctx, C.byref(fc), w, h, max_steps, C.c_void_p(xy_ptr), n, C.byref(hits),
                                                    _stream_arg(stream)))
@@ -1273,7 +1082,7 @@ class Renderer:
     def pick(self, x: int, y: int, w: int, h: int, max_steps: int = 256, camera: S.Camera | None = None,
              frame_camera: S.FrameCamera | None = None) -> dict:
         """What is under pixel (x, y) of the w x h frame: {"id", "dist", "steps", "normal"} in host memory (waits)."""
-        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        fc = self._frame_camera(frame_camera, w, h, camera)
         hit = Hit()
         self._check(self._lib.lol_gpu_pick(self._ctx, C.byref(fc), w, h, max_steps, int(x), int(y), C.byref(hit)))
         return {"id": int(hit.id), "dist": float(hit.dist), "steps": int(hit.steps), "normal": tuple(float(v) for v in hit.normal)}
@@ -1305,7 +1114,7 @@ class Renderer:
                           camera: S.Camera | None = None, frame_camera: S.FrameCamera | None = None):
         """Asynchronously shade the primary rays of n pixels (device memory, n x {x, y} uint32) of the w x h frame under the
         camera: what a frame and its lol_gpu_debug planes hold for those pixels, and the linear colour."""
-        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        fc = self._frame_camera(frame_camera, w, h, camera)
         out = Shades(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None, dist_ptr or None, id_ptr or None, steps_ptr or None)
         self._check(self._lib.lol_gpu_shade_pixels(self._ctx, C.byref(fc), w, h, max_steps, C.c_void_p(xy_ptr), n, C.byref(out),
                                                    _stream_arg(stream)))
@@ -1325,7 +1134,7 @@ class Renderer:
                           camera: S.Camera | None = None, frame_camera: S.FrameCamera | None = None):
         """light_rays_into for the primary rays of n pixels (device memory, n x {x, y} uint32) of the w x h frame under the camera;
         xy_ptr = 0: every pixel of the frame, element i = y w + x, and n must be w h."""
-        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
+        fc = self._frame_camera(frame_camera, w, h, camera)
         out = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, steps_ptr or None)
         self._check(self._lib.lol_gpu_light_pixels(self._ctx, C.byref(fc), w, h, max_steps, C.c_void_p(xy_ptr) if xy_ptr else None, n,
                                                    C.byref(out), _stream_arg(stream)))
@@ -1339,16 +1148,15 @@ class Renderer:
         three).  The look's tables are copied before the call returns.  held (a Scene or a Program; None: the prepared scene): what
         the planes hold after light_update_*_into brought them to another look — the look must then stand where `held` stands
         (lol_gpu_relight_held)."""
-        prog = None if look is None else look if isinstance(look, S.Program) else look.flatten()
+        prog = self._look_program(look)
         planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
         if held is not None:
-            hp = held if isinstance(held, S.Program) else held.flatten()
-            self._check(self._lib.lol_gpu_relight_held(self._ctx, C.byref(prog) if prog is not None else None, C.byref(hp), C.byref(planes),
-                                                       n, C.byref(out), _stream_arg(stream)))
+            hp = self._look_program(held)
+            self._check(self._lib.lol_gpu_relight_held(self._ctx, _ref(prog), C.byref(hp), C.byref(planes), n, C.byref(out),
+                                                       _stream_arg(stream)))
             return
-        self._check(self._lib.lol_gpu_relight(self._ctx, C.byref(prog) if prog is not None else None, C.byref(planes), n, C.byref(out),
-                                              _stream_arg(stream)))
+        self._check(self._lib.lol_gpu_relight(self._ctx, _ref(prog), C.byref(planes), n, C.byref(out), _stream_arg(stream)))
 
     def light_update_rays_into(self, look, rays_ptr: int, n: int, march_lights: int = 0, specular_lights: int = 0, factors_ptr: int = 0,
                                id_ptr: int = 0, dist_ptr: int = 0, light_stride: int = 0, stream: int | None = None):
@@ -1357,21 +1165,20 @@ class Renderer:
         shininesses (scene.Scene.with_lighting) — without the primary march (lol_gpu_light_update_rays).  Bit l of march_lights:
         light l's whole factor is computed again; bit l of specular_lights (and not of march_lights): its specular incidence alone,
         with no shadow march.  scene.light_changes gives both masks.  Resolve with relight_into(..., held=look)."""
-        prog = look if isinstance(look, S.Program) else look.flatten() if look is not None else None
+        prog = self._look_program(look)
         planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, None)
-        self._check(self._lib.lol_gpu_light_update_rays(self._ctx, C.byref(prog) if prog is not None else None, C.c_void_p(rays_ptr), n,
-                                                        int(march_lights), int(specular_lights), C.byref(planes), _stream_arg(stream)))
+        self._check(self._lib.lol_gpu_light_update_rays(self._ctx, _ref(prog), C.c_void_p(rays_ptr), n, int(march_lights),
+                                                        int(specular_lights), C.byref(planes), _stream_arg(stream)))
 
     def light_update_pixels_into(self, look, n: int, w: int, h: int, march_lights: int = 0, specular_lights: int = 0, xy_ptr: int = 0,
                                  factors_ptr: int = 0, id_ptr: int = 0, dist_ptr: int = 0, light_stride: int = 0,
                                  stream: int | None = None, camera: S.Camera | None = None, frame_camera: S.FrameCamera | None = None):
         """light_update_rays_into for the planes of light_pixels_into: the same n, w, h, camera and xy_ptr (0: every pixel)."""
-        fc = frame_camera if frame_camera is not None else self.scene.frame_camera(w, h, camera)
-        prog = look if isinstance(look, S.Program) else look.flatten() if look is not None else None
+        fc = self._frame_camera(frame_camera, w, h, camera)
+        prog = self._look_program(look)
         planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, None)
-        self._check(self._lib.lol_gpu_light_update_pixels(self._ctx, C.byref(prog) if prog is not None else None, C.byref(fc), w, h,
-                                                          C.c_void_p(xy_ptr) if xy_ptr else None, n, int(march_lights),
-                                                          int(specular_lights), C.byref(planes), _stream_arg(stream)))
+        self._check(self._lib.lol_gpu_light_update_pixels(self._ctx, _ref(prog), C.byref(fc), w, h, C.c_void_p(xy_ptr) if xy_ptr else None,
+                                                          n, int(march_lights), int(specular_lights), C.byref(planes), _stream_arg(stream)))
 
     def light_views_into(self, cameras, cameras_per_view: int, w: int, h: int, samples: int = 1, max_steps: int = 256,
                          factors_ptr: int = 0, id_ptr: int = 0, dist_ptr: int = 0, steps_ptr: int = 0, light_stride: int = 0,
@@ -1386,10 +1193,7 @@ class Renderer:
         k = int(cameras_per_view)
         if k < 1 or len(cams) % k:
             raise ValueError("light_views_into: len(cameras) must be a multiple of cameras_per_view")
-        arr = (S.FrameCamera * max(1, len(cams)))()
-        for i, c in enumerate(cams):
-            fc = c if isinstance(c, S.FrameCamera) else self.scene.frame_camera(w, h, c)
-            C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
+        arr = self._camera_array(cams, w, h)
         out = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, steps_ptr or None)
         self._check(self._lib.lol_gpu_light_views(self._ctx, arr, len(cams) // k, k, w, h, int(samples), max_steps, C.byref(out),
                                                   _stream_arg(stream)))
@@ -1403,12 +1207,11 @@ class Renderer:
         and this renderer's pixel format — the supersampled frame, the blend, or the supersampled blend of a renderer that prepared
         the look, bit for bit, in one copy and one launch.  rgb_linear / rgb: 3 floats per pixel, pixel: one element, dense over
         [view, y, x]; 0 = not wanted (not all three).  Planes that a light update brought to another look: relight_views_held_into."""
-        prog = None if look is None else look if isinstance(look, S.Program) else look.flatten()
+        prog = self._look_program(look)
         planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
-        self._check(self._lib.lol_gpu_relight_views(self._ctx, C.byref(prog) if prog is not None else None, C.byref(planes),
-                                                    int(n_views), int(cameras_per_view), w, h, int(samples), C.byref(out),
-                                                    _stream_arg(stream)))
+        self._check(self._lib.lol_gpu_relight_views(self._ctx, _ref(prog), C.byref(planes), int(n_views), int(cameras_per_view), w, h,
+                                                    int(samples), C.byref(out), _stream_arg(stream)))
 
     def relight_views_held_into(self, look, held, n_views: int, cameras_per_view: int, w: int, h: int, samples: int = 1,
                                 factors_ptr: int = 0, id_ptr: int = 0, rgb_linear_ptr: int = 0, rgb_ptr: int = 0, pixel_ptr: int = 0,
@@ -1416,12 +1219,11 @@ class Renderer:
         """relight_views_into for planes that hold `held` (a Scene or a Program; None: the prepared scene, which is
         relight_views_into itself) after light_update_pixels_into brought them there record by record: the look must stand where
         `held` stands (lol_gpu_relight_views_held).  What relight_into's held= is to relight_into."""
-        prog = None if look is None else look if isinstance(look, S.Program) else look.flatten()
-        hp = None if held is None else held if isinstance(held, S.Program) else held.flatten()
+        prog = self._look_program(look)
+        hp = self._look_program(held)
         planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
-        self._check(self._lib.lol_gpu_relight_views_held(self._ctx, C.byref(prog) if prog is not None else None,
-                                                         C.byref(hp) if hp is not None else None, C.byref(planes), int(n_views),
+        self._check(self._lib.lol_gpu_relight_views_held(self._ctx, _ref(prog), _ref(hp), C.byref(planes), int(n_views),
                                                          int(cameras_per_view), w, h, int(samples), C.byref(out), _stream_arg(stream)))
 
     def set_cull(self, enable: bool):
@@ -1521,7 +1323,7 @@ class MultiRenderer:
     def set_pixel_format(self, fmt):
         if isinstance(fmt, str):
             fmt = PIXEL_FORMATS[fmt]
-        self._check(self._lib.lol_gpu_multi_set_pixel_format(self._m, C.byref(fmt) if fmt is not None else None))
+        self._check(self._lib.lol_gpu_multi_set_pixel_format(self._m, _ref(fmt)))
 
     def set_tile_order(self, order):
         self._check(self._lib.lol_gpu_multi_set_tile_order(self._m, _tile_order_arg(order)))

@@ -104,6 +104,32 @@ class SceneError(Exception):
         self.message = message
 
 
+def _bind_prototypes(lib, *tables):
+    """Declare to ctypes every function of `tables` (name -> (restype, argtypes)) that `lib` has.  One it lacks — an older build of
+    the library — stays as it is: calling it raises ctypes' AttributeError."""
+    for table in tables:
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
+
+
+# The C prototypes of include/lol_scene.h: function -> (restype, argtypes).  tests/test_cabi_prototypes.py holds them, and the
+# struct mirrors above, to the header's text.
+_P = C.POINTER
+_LOL_SCENE_H = {
+    "lol_scene_parse_file": (C.c_int, [C.c_char_p, _P(_P(SceneStruct)), C.c_char_p, C.c_size_t]),
+    "lol_scene_parse_string": (C.c_int, [C.c_char_p, C.c_size_t, _P(_P(SceneStruct)), C.c_char_p, C.c_size_t]),
+    "lol_scene_free": (None, [_P(SceneStruct)]),
+    "lol_scene_clone": (C.c_int, [_P(SceneStruct), _P(_P(SceneStruct))]),
+    "lol_scene_new": (_P(SceneStruct), []),
+    "lol_scene_validate_materials": (C.c_int, [_P(SceneStruct)]),
+    "lol_scene_flatten": (C.c_int, [_P(SceneStruct), _P(Program)]),
+    "lol_program_free": (None, [_P(Program)]),
+    "lol_frame_camera_init": (None, [_P(FrameCamera), _P(Camera), C.c_int, C.c_int]),
+    "lol_status_str": (C.c_char_p, [C.c_int]),
+}
+
 _lib = None
 
 
@@ -115,27 +141,7 @@ def host_lib() -> C.CDLL:
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: run __graft_entry__.build() (or make -C loltracer_amd/csrc)")
         lib = C.CDLL(path)
-        P = C.POINTER
-        lib.lol_scene_parse_file.argtypes = [C.c_char_p, P(P(SceneStruct)), C.c_char_p, C.c_size_t]
-        lib.lol_scene_parse_file.restype = C.c_int
-        lib.lol_scene_parse_string.argtypes = [C.c_char_p, C.c_size_t, P(P(SceneStruct)), C.c_char_p, C.c_size_t]
-        lib.lol_scene_parse_string.restype = C.c_int
-        lib.lol_scene_free.argtypes = [P(SceneStruct)]
-        lib.lol_scene_free.restype = None
-        lib.lol_scene_clone.argtypes = [P(SceneStruct), P(P(SceneStruct))]
-        lib.lol_scene_clone.restype = C.c_int
-        lib.lol_scene_new.argtypes = []
-        lib.lol_scene_new.restype = P(SceneStruct)
-        lib.lol_scene_validate_materials.argtypes = [P(SceneStruct)]
-        lib.lol_scene_validate_materials.restype = C.c_int
-        lib.lol_scene_flatten.argtypes = [P(SceneStruct), P(Program)]
-        lib.lol_scene_flatten.restype = C.c_int
-        lib.lol_program_free.argtypes = [P(Program)]
-        lib.lol_program_free.restype = None
-        lib.lol_frame_camera_init.argtypes = [P(FrameCamera), P(Camera), C.c_int, C.c_int]
-        lib.lol_frame_camera_init.restype = None
-        lib.lol_status_str.argtypes = [C.c_int]
-        lib.lol_status_str.restype = C.c_char_p
+        _bind_prototypes(lib, _LOL_SCENE_H)
         _lib = lib
     return _lib
 

@@ -104,11 +104,10 @@ def test_pixels_dealt_by_scene4s_cost_are_the_models(torch_cuda, ctx, scenes):
 
 def test_the_scratch_runs_refuse_a_table_of_another_size(ctx):
     out = np.zeros(1024, dtype=np.uint32)
-    fn = gpu.gpu_lib().lol_gpu_testing_deal
-    fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t], C.c_int
-    assert fn(ctx._ctx, None, 65, 16, out.ctypes.data, 1024) == -3       # two regions
-    assert fn(ctx._ctx, None, 0, 16, out.ctypes.data, 1024) == -3
-    assert fn(ctx._ctx, None, 64, 16, out.ctypes.data, 1024) == 0
+    fn, lanes = gpu.gpu_lib().lol_gpu_testing_deal, out.ctypes.data_as(C.POINTER(C.c_uint32))
+    assert fn(ctx._ctx, None, 65, 16, lanes, 1024) == -3                 # two regions
+    assert fn(ctx._ctx, None, 0, 16, lanes, 1024) == -3
+    assert fn(ctx._ctx, None, 64, 16, lanes, 1024) == 0
     with pytest.raises(gpu.GpuError):
         ctx.testing_sort_tiles(np.zeros(4, np.uint32), np.array([0, 1, 2, 4], np.uint32))      # names a wave slot beyond the table
     assert ctx.testing_schedule() is None                                # no frame yet
