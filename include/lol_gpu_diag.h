@@ -54,6 +54,17 @@ int         lol_gpu_cull_bounds(const lol_program* prog, uint32_t root, float c_
  * written (0: the object is tested with its single sphere only; else 2); the specialised kernel skips such an object where
  * the tests of BOTH spheres pass. */
 int         lol_gpu_cull_bounds_clusters(const lol_program* prog, uint32_t root, float out[3][4]);
+/* The interpreter list of `prog` as the scene-record calls build it per record
+ * (analyse_roots, plan_culling(cull), build_mops with nothing proven):
+ * *n_mops, *n_tests (constants records), *n_unbounded, and for up to `cap`
+ * objects in evaluation order their root id (order[]) and whether the macro-op
+ * that finishes them carries MOP_TIE (tie[]).  Returns the number of objects.  No device needed; the three counts may be NULL,
+ * order and tie may be NULL only with cap = 0.  LOL_GPU_ERR_ARG for no program or one beyond LOL_MAX_OPS.
+ * The plan — order, tie flags, tests, unbounded objects — is the one a call builds for that record on any context.  *n_mops is the
+ * length with NOTHING proven: a context whose upload proved a smoothness constant lets a smooth min of two finished sub-unions ride
+ * on the record before it (MOPB_POST), so its list of the same record can be shorter than *n_mops, never longer. */
+int         lol_gpu_interp_list_info(const lol_program* prog, int cull, uint32_t* n_mops, uint32_t* n_tests,
+                                     uint32_t* n_unbounded, uint32_t* order, uint32_t* tie, size_t cap);
 /*
  * Diagnostic: out[i] = the renderer's powf(x[i], y[i]) (device pointers, asynchronous on `stream`, NULL = the
  * context's stream).  The kernel's powf restates the algorithm of the CPU libm's powf so that colours round

@@ -1641,6 +1641,31 @@ int lol_gpu_cull_bounds_clusters(const lol_program* prog, uint32_t root, float o
 	return n;
 }
 
+/* Host-only view of the interpreter list the scene-record calls build for `prog` (build_interp_lists with no proven fast path):
+ * its length, its test records, the objects without a bound, and per object in evaluation order its id and whether the record that
+ * finishes it carries MOP_TIE — read back from the list itself, not from the plan.  Returns the number of objects. */
+int lol_gpu_interp_list_info(const lol_program* prog, int cull, uint32_t* n_mops, uint32_t* n_tests, uint32_t* n_unbounded,
+                             uint32_t* order, uint32_t* tie, size_t cap) {
+	if (!prog || prog->n_ops > LOL_MAX_OPS || (cap && (!order || !tie))) return LOL_GPU_ERR_ARG;
+	const std::vector<RootBound> roots = analyse_roots(*prog);
+	const CullPlan plan = plan_culling(roots, cull != 0);
+	const std::vector<uint32_t> list = build_mops(*prog, nullptr, roots, plan, false);
+	if (n_mops) *n_mops = (uint32_t)(list.size() / lol::MOP_DWORDS);
+	if (n_tests) *n_tests = (uint32_t)plan.intervals.size();
+	if (n_unbounded) *n_unbounded = (uint32_t)plan.n_unbounded;
+	const std::vector<PlanStep> steps = walk_plan(roots, plan);
+	size_t at = 0, n = 0;
+	for (const PlanStep& st : steps) {
+		at += (size_t)st.n_open * lol::MOP_DWORDS;                       /* the constants records in front of the object */
+		while (at < list.size() && !(list[at] & lol::MOP_TOP)) at += lol::MOP_DWORDS;
+		if (at >= list.size()) return LOL_GPU_ERR_UNSUPPORTED;
+		if (n < cap) { order[n] = list[at + 1]; tie[n] = (list[at] & lol::MOP_TIE) ? 1u : 0u; }
+		n++;
+		at += lol::MOP_DWORDS;
+	}
+	return (int)n;
+}
+
 void lol_gpu_code_key(const void* code, size_t n, char out[17]) {
 	if (!out) return;
 	snprintf(out, 17, "%s", code ? code_key_hex(code, n).c_str() : "");

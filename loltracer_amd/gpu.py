@@ -290,6 +290,7 @@ _LOL_GPU_DIAG_H = {                                                     # includ
     "lol_gpu_shade_math": (_int, [_vp, _P(ShadeMathInfo)]),
     "lol_gpu_scene_view_samples_kernel_name": (_str, [_vp, _int, _int]),
     "lol_gpu_compile_offline_scene_view_samples": (_int, [_prog, _str, _str, _str, _size]),
+    "lol_gpu_interp_list_info": (_int, [_prog, _int, _u32p, _u32p, _u32p, _u32p, _u32p, _size]),
 }
 
 _LOL_GPU_TESTING_H = {                                                  # include/lol_gpu_testing.h
@@ -337,6 +338,20 @@ def code_key(code: bytes) -> str:
     out = C.create_string_buffer(17)
     gpu_lib().lol_gpu_code_key(code, len(code), out)
     return out.value.decode()
+
+
+def interp_list_info(program: S.Program, cull: bool = True) -> dict:
+    """lol_gpu_interp_list_info: the interpreter list the scene-record calls build for `program` — n_mops, n_tests, n_unbounded and,
+    per object in evaluation order, its root id (order) and whether the record that finishes it carries MOP_TIE (tie).  No device."""
+    cap = int(program.n_roots)
+    n_mops, n_tests, n_unbounded = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    order, tie = (C.c_uint32 * max(cap, 1))(), (C.c_uint32 * max(cap, 1))()
+    n = gpu_lib().lol_gpu_interp_list_info(C.byref(program), int(bool(cull)), C.byref(n_mops), C.byref(n_tests), C.byref(n_unbounded),
+                                           order, tie, cap)
+    if n < 0 or n > cap:
+        raise GpuError(n, "lol_gpu_interp_list_info failed")
+    return {"n_mops": n_mops.value, "n_tests": n_tests.value, "n_unbounded": n_unbounded.value,
+            "order": tuple(order[:n]), "tie": tuple(tie[:n])}
 
 
 # the module switches, by their setters' names: bit i of lol_gpu_compile_offline_module's mask (include/lol_gpu_diag.h)

@@ -17,6 +17,10 @@ kernels' bound carried along each ray are least protected by coherence.  The par
   (h) unbounded  for an object WITHOUT a bound (a plane, a union with k <= 0): two rays straight down (-y) from seeded points 1 and
              30 above the scene's camera.
 
+bound_rays(sc, seed) makes (f) - (h) for ANY scene — tests/test_gpu_scene_records.py builds the list of every record from that
+record's own bounds with it; for the entries of HOSTILE the lists are byte for byte what they were before it was factored out
+(tests/test_hostile_rays.py holds their digests).
+
 The list comes in two orders.  Object-major: the kinds one behind the other, (f) - (h) grouped by object, so that whole waves may skip
 the same runs.  A seeded permutation of it: the lanes of a wave disagree, and the cool-down is exercised.  A ray's answer must not
 depend on the order.  The length is no multiple of 64 (a trailing ray is dropped if it is): the last wave is ragged.
@@ -129,14 +133,11 @@ def hostile_look(sc):
 _lists = {}
 
 
-def _build(e):
-    sc = SH.hostile_scene(e)
-    rng = np.random.default_rng([SEED, SH.HOSTILE.index(e)])
-    base = R.ray_set(sc, SEED, "abcde")
-    if e.name in THINNED:
-        keep = specials_among(sc, base) | (np.arange(len(base)) % THINNED[e.name] == 0)
-        base = base[keep]
-    rays, kind, obj = [base], ["a"] * len(base), [-1] * len(base)
+def bound_rays(sc, seed):
+    """parts (f) - (h) for `sc` under `seed` (anything numpy's default_rng takes), object-major: (rays [n, 6] f32, kind [n], obj [n]) —
+    aimed and grazing rays made from the scene's OWN culling bounds, and the rays straight down for its objects without one"""
+    rng = np.random.default_rng(seed)
+    rays, kind, obj = [], [], []
     prog = sc.flatten()
     cam = np.array(sc.camera.point.tuple(), np.float64)
     for i in range(prog.n_roots):
@@ -151,6 +152,17 @@ def _build(e):
         rays.append(np.array([q for _, q in new], np.float32).reshape(-1, 6))
         kind += [k for k, _ in new]
         obj += [i] * len(new)
+    return rays, kind, obj
+
+
+def _build(e):
+    sc = SH.hostile_scene(e)
+    base = R.ray_set(sc, SEED, "abcde")
+    if e.name in THINNED:
+        keep = specials_among(sc, base) | (np.arange(len(base)) % THINNED[e.name] == 0)
+        base = base[keep]
+    more, more_kind, more_obj = bound_rays(sc, [SEED, SH.HOSTILE.index(e)])
+    rays, kind, obj = [base] + more, ["a"] * len(base) + more_kind, [-1] * len(base) + more_obj
     rays = np.ascontiguousarray(np.concatenate(rays), dtype=np.float32)
     if len(rays) % 64 == 0:
         rays, kind, obj = rays[:-1], kind[:-1], obj[:-1]

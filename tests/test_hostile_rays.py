@@ -7,6 +7,7 @@ rays never see, and exact ties go to the first object in file order.  Then the r
 (light_reference, light_update_reference; ray_reference and shade_reference have tests/golden/hostile in their own tests) are held to
 lol_oracle_probe_pixel and to one another on the hostile scenes' own camera rays, bit for bit.
 """
+import hashlib
 import time
 
 import numpy as np
@@ -30,6 +31,31 @@ UPDATE_SIZE = (16, 8)                    # the frame whose pixels the GPU tests 
 
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
+
+
+def test_the_lists_are_what_they_have_always_been():
+    """Every ray, kind, object and permutation of all 22 lists, as the builder made them before bound_rays was factored out of it
+    for tests/test_gpu_scene_records.py: one digest over them in the catalogue's order — and bound_rays is that part of the list.
+    The digest was taken with the builder of commit 8126f6e, before the refactoring, and is the refactored builder's too.  It rests on
+    numpy's Generator stream and on the bounds lol_gpu_cull_bounds / _clusters return: a change that legitimately moves a culling
+    bound moves the lists with it, and the digest is then taken anew — it pins the builder, not the bounds."""
+    h, n = hashlib.sha256(), 0
+    for e in SH.HOSTILE:
+        p = HR.hostile_ray_parts(e)
+        for k in ("rays", "permuted"):
+            h.update(p[k].tobytes())
+        h.update("".join(p["kind"].tolist()).encode())
+        h.update(p["obj"].tobytes())
+        h.update(p["perm"].astype("int64").tobytes())
+        n += len(p["rays"])
+    assert n == 6300
+    assert h.hexdigest() == "448a5652fa175656248046da3e0b57bf3875439ab08c4572f1e72774c250d3ee"
+    e = SH.HOSTILE_BY_NAME["tie-crowd"]
+    parts, kind, obj = HR.bound_rays(SH.hostile_scene(e), [HR.SEED, SH.HOSTILE.index(e)])
+    p = HR.hostile_ray_parts(e)
+    own = p["kind"] != "a"
+    assert np.array_equal(bits(np.concatenate(parts)[:own.sum()]), bits(p["rays"][own])) and kind[:own.sum()] == p["kind"][own].tolist()
+    assert obj[:own.sum()] == p["obj"][own].tolist() and len(kind) - own.sum() in (0, 1)
 
 
 @pytest.mark.parametrize("e", SH.HOSTILE, ids=names)
