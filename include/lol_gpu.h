@@ -871,6 +871,7 @@ int  lol_gpu_scene_view_samples(const lol_gpu* ctx);
  * and lol_gpu_set_shade_queries have no effect on these calls.
  * Out of scope: a structure-module form, light passes over records, lists in host memory, lol_gpu_multi_* forms, and a C pick over
  * records (the Python mirror has the convenience: Renderer.pick_scenes).
+ * (Light passes over records are built since: "Scene light passes", below.)
  */
 int  lol_gpu_trace_scene_rays(lol_gpu* ctx, const lol_program* scenes, int n_scenes, const float* rays_dev, size_t n, size_t list_stride,
                               int max_steps, const lol_gpu_hits* out, void* stream);
@@ -953,6 +954,8 @@ typedef struct lol_gpu_relit { float* rgb_linear; float* rgb; uint32_t* pixel; }
  * speed); capture in ONE launch over batches, blends or samples (lol_gpu_light_views, below, covers them with one capture launch
  * per camera, and lol_gpu_relight_views resolves them); per-record scenes; moving a light or changing a shininess (they change the
  * factors: capture again, or update the planes — "Light updates", below); lol_gpu_multi_* forms; planes in host memory; and the renderer.h protocol.
+ * (Per-record scenes, and their capture in one launch, are built since: lol_gpu_light_scene_rays, lol_gpu_light_scene_pixels and
+ * lol_gpu_relight_scenes, "Scene light passes", below.)
  */
 int  lol_gpu_light_rays(lol_gpu* ctx, const float* rays_dev, size_t n, int max_steps, const lol_gpu_light_passes* out, void* stream);
 int  lol_gpu_light_pixels(lol_gpu* ctx, const lol_frame_camera* cam, int w, int h, int max_steps,
@@ -1002,6 +1005,8 @@ int  lol_gpu_relight(lol_gpu* ctx, const lol_program* look /* HOST; NULL = the u
  *
  * Out of scope: a scene-module capture kernel (as above); edge-adaptive relit supersampling; per-record scenes; lol_gpu_multi_*
  * forms; planes in host memory; pitch or stride addressing of the outputs.
+ * (Per-record scenes are built since for the capture and for the resolve of single leaves: "Scene light passes", below; with equal
+ * scenes that capture writes this section's planes in one launch.)
  */
 int  lol_gpu_light_views(lol_gpu* ctx, const lol_frame_camera* cams /* HOST */, int n_views, int cams_per_view,
                          int w, int h, int samples, int max_steps, const lol_gpu_light_passes* out, void* stream);
@@ -1070,6 +1075,67 @@ int  lol_gpu_relight_held(lol_gpu* ctx, const lol_program* look /* HOST; NULL = 
                           const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream);
 int  lol_gpu_relight_views_held(lol_gpu* ctx, const lol_program* look, const lol_program* held, const lol_gpu_light_passes* in,
                                 int n_views, int cams_per_view, int w, int h, int samples, const lol_gpu_relit* out, void* stream);
+
+/*
+ * Scene light passes: light passes captured and relit under each record's own SCENE — an animation's capture in one call, and every
+ * frame of it under a new look in one more, without an upload per frame.
+ * Records and layout.  `scenes`, `looks` and `cams` are HOST memory and hold n_scenes entries, 1 <= n_scenes <= LOL_GPU_MAX_VIEWS; they
+ * and the tables the programs point to are copied before the call returns.  Records, list_stride (0: one list of n elements serves
+ * every record; otherwise list_stride >= n elements between the lists of two records) and the structure test are exactly those of
+ * scene queries ("Scene queries", above).  Element (r, i) — ray i of record r — is element e = r * n + i of N = n_scenes * n.  The factor
+ * planes are light-major over all N elements: light l of element e at factors[l * light_stride + e], light_stride 0 (= N) or >= N;
+ * hit_id, hit_dist and march_steps are dense over e.  All addressing is 64-bit.  With xy_dev == NULL ray i of record r is pixel
+ * (i % w, i / w) under cams[r], and n must be w * h: the leaf layout of relit views, whose record is r = v K + k and whose n is s^2 w h.
+ * Capture.  Element (r, i) of lol_gpu_light_scene_rays / lol_gpu_light_scene_pixels is, bit for bit, EXACTLY what lol_gpu_light_rays /
+ * lol_gpu_light_pixels writes for that ray on another context with this context's settings (lol_gpu_set_exact_skips, lol_gpu_set_cull)
+ * that called lol_gpu_upload_program(&scenes[r]) and, for pixels, captures under cams[r]: all 16 bytes of every factor, hit_id,
+ * hit_dist and march_steps.  So every element is the reference's arithmetic on record r's own numbers, for NaN, infinite, zero
+ * and unnormalised rays too, whatever the other rays and the other records hold; a NaN centre in one record is that record's business
+ * alone.  The escaped-wave skip and the zero-incidence skip are OFF for every record, as for every capture.  Decided per record, on the
+ * host, from that record's own scene and camera, as for scene queries: the settled-shadow exit, whether the scene is finite, which of
+ * the record's two macro-op lists runs, and the first march step.  No proof runs on the device.
+ * One latitude, the one scene queries and light updates have: for a LIST OF RAYS with the settled-shadow exit on (bit 2 of
+ * lol_gpu_set_exact_skips), shadow_steps is "the steps really marched", and is held equal to that other context's only after
+ * lol_gpu_set_exact_skips(ctx, 0).  For pixel sources all 16 bytes are equal.
+ * Relight.  looks[r] must be a look of scenes[r] in exactly lol_gpu_relight's sense, with scenes[r] in the place of the uploaded
+ * program: equal counts, every ops[i].op, .id and .f[], every lights[l].point, every materials[m].shininess as bits, every
+ * root_material[].  looks == NULL: the scenes' own look.  Element (r, i) of lol_gpu_relight_scenes is lol_gpu_relight's element on a
+ * context that uploaded scenes[r], given looks[r] and record r's planes — rgb_linear, rgb and pixel, NaN and infinite looks included;
+ * an id beyond n_roots is taken for 0; the context's gamma table and pixel format apply.  Over planes captured by the two calls above
+ * it is therefore lol_gpu_shade_scene_rays / lol_gpu_shade_scene_pixels on `looks`, and over all pixels frame r of
+ * lol_gpu_render_scene_views on `looks`.
+ * Refused, with nothing launched and nothing written, in this order:
+ *  1. what the single-scene call refuses, in its order — lol_gpu_light_rays / lol_gpu_light_pixels with n elements, lol_gpu_relight
+ *     with a NULL look and n elements: no context, a NULL list of rays with n > 0, NULL out / in, max_steps < 0, n > 2^32 - 1, no
+ *     program (LOL_GPU_ERR_NO_PROGRAM), the planes against n, NULL cam or bad frame geometry, xy_dev == NULL with n != w * h;
+ *  2. LOL_GPU_ERR_ARG for NULL scenes, n_scenes < 1 or > LOL_GPU_MAX_VIEWS, NULL cams in the pixel form, a list_stride that is neither 0
+ *     nor >= n, N > 2^32 - 1, a light_stride that is neither 0 nor >= N;
+ *  3. the scene refusals of lol_gpu_render_scene_views: a missing table, another structure, a root_material out of range;
+ *  4. for the relight, the first looks[r] that is not a look of scenes[r], with lol_gpu_relight's reason behind "record r" in
+ *     lol_gpu_error's text.
+ * n == 0 returns LOL_GPU_OK with nothing launched.  An allocation that fails returns LOL_GPU_ERR_HIP, and the context stays usable.
+ * Consequence.  With scenes[r] the uploaded program for every r and `cams` the cameras of lol_gpu_light_views(n_views, K, w, h, s),
+ * lol_gpu_light_scene_pixels(ctx, cams, scenes, n_views * K, s * w, s * h, max_steps, NULL, s^2 w h, 0, out, stream) writes byte for byte
+ * the planes lol_gpu_light_views writes — n_views * K capture launches there, one here —, and lol_gpu_relight_views /
+ * lol_gpu_relight_views_held resolve them unchanged.
+ * Asynchronous on `stream` (NULL = the context's own stream; LOL_GPU_STREAM_DEFAULT as elsewhere).  A capture is one copy of the
+ * records and their data through scene views' ring of 8 sets, under its rules, and ONE launch; a relight is one copy of the looks'
+ * tables through lol_gpu_relight's ring of 8 sets, under its rules (HIP's special stream handles included), and ONE launch.  No scratch,
+ * no host wait.  The context's scene, kernels, lol_gpu_kernel_key, tile-order state, sample settings and other rings are neither
+ * read nor changed: a frame after the call is the frame it would have been.
+ * Which kernel: the interpreter's light_interp_scenes and relight_rays_scenes, always.  No module switch has an effect on these calls.
+ * Out of scope: an averaged resolve over records (K records per view, or s x s samples: capture here, resolve with
+ * lol_gpu_relight_views where the scenes are equal); light updates over records; a structure-module or scene-module form;
+ * lol_gpu_multi_* forms; planes or lists in host memory; and lol_gpu_light_views made of this call.
+ */
+int  lol_gpu_light_scene_rays(lol_gpu* ctx, const lol_program* scenes /* HOST */, int n_scenes, const float* rays_dev, size_t n,
+                              size_t list_stride, int max_steps, const lol_gpu_light_passes* out, void* stream);
+int  lol_gpu_light_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams /* HOST */, const lol_program* scenes, int n_scenes, int w, int h,
+                                int max_steps, const uint32_t* xy_dev /* NULL: every pixel, n must be w*h */, size_t n, size_t list_stride,
+                                const lol_gpu_light_passes* out, void* stream);
+int  lol_gpu_relight_scenes(lol_gpu* ctx, const lol_program* scenes /* HOST: what the planes hold */,
+                            const lol_program* looks /* HOST; NULL = the scenes themselves */, int n_scenes,
+                            const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream);
 
 #ifdef __cplusplus
 }

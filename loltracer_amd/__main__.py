@@ -4,6 +4,7 @@
                           [--tween B.lol --frames N [--tween-samples S] [--tween-shutter K] -o DIR]
                           [--tween B.lol --frames N --pick X,Y] [--tween B.lol --frames N --lens R --focus-at X,Y [--lens-samples K] -o DIR]
                           [--relight LOOK.lol [LOOK2.lol ...] [--samples S] [--lens R --focus D --lens-samples K] [--move-lights] -o DIR]
+                          [--tween B.lol --frames N --relight LOOK.lol [LOOK2.lol ...] -o DIR]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
@@ -37,6 +38,11 @@ the same flags and without --relight writes, byte for byte.  Not with --adaptive
 the looks may also MOVE LIGHTS or change a shininess: each look is reached from the one before by scene.light_changes, one light update
 (Renderer.light_update_pixels_into: no primary march, a shadow march only towards lights that moved) and relight_into(held=look);
 the files are again what LOOK.lol alone writes, byte for byte.  Not with --samples, --lens, --adaptive or --focus-at.
+A.lol --tween B.lol --frames N --relight LOOK.lol [LOOK2.lol ...] -o DIR relights an ANIMATION: ONE capture over the N tweened scenes
+(Renderer.light_scene_pixels_into: every frame under its own scene, one launch) and per look ONE Renderer.relight_scenes_into, frame
+f under its own scene with the look's intensities and colours (look_of: scene.Scene.with_look from the look's file), into
+DIR/look_LLLL_frame_FFFF.ppm — the frames those scenes render, byte for byte.  Not with --tween-shutter, --tween-samples, --samples,
+--lens or --move-lights.
 There is no CPU rendering path."""
 from __future__ import annotations
 
@@ -221,6 +227,64 @@ def relight_frames(sc, args, w, h) -> int:
     return 0
 
 
+def look_of(sc, look):
+    """`sc` with the look of the scene `look`: its lights' intensities, its materials' colours and its ambient colour, nothing else"""
+    return sc.with_look(lights=[(l.diffuse_intensity.tuple(), l.specular_intensity.tuple()) for l in look.lights()],
+                        materials=[(m.diffuse.tuple(), m.specular.tuple(), m.ambient.tuple()) for m in look.materials()],
+                        ambient=look.c.ambient_color.tuple())
+
+
+def tween_relight_frames(sc, args, w, h) -> int:
+    """N tweened scenes captured in one launch, one relight over all of them per look, one PPM per look and frame"""
+    try:
+        other = S.Scene.parse_file(args.tween)
+        look_files = [S.Scene.parse_file(path) for path in args.relight]
+    except S.SceneError as e:
+        print(e.message, file=sys.stderr)
+        return 1
+    if not S.same_structure(sc, other):
+        print("--tween: the two scenes differ in structure (objects, their nesting, lights or materials)", file=sys.stderr)
+        return 1
+    for path, look in zip(args.relight, look_files):
+        why = S.geometry_difference(sc, look)
+        if why is not None:
+            print(f"--relight {path}: not a look of {args.scene}: {why}", file=sys.stderr)
+            return 1
+    n, px, nl = args.frames, w * h, len(sc.lights())
+    scenes = [S.tween(sc, other, t) for f in range(n) for t in S.shutter_times(f, n, 1)]
+    cams = [sc.camera] * n
+    r = gpu.Renderer(args.device)
+    try:
+        r.prepare(sc, wait=False)            # (capture and relight run on the interpreter: nothing waits for the scene compiler)
+        frames = np.zeros((len(look_files), n, h, w), dtype=np.uint32)
+        d_factors = r.malloc(16 * n * px * nl) if nl else 0
+        d_id, d_px = r.malloc(4 * n * px), r.malloc(4 * n * px)
+        try:
+            t0 = time.perf_counter()
+            r.light_scene_pixels_into(scenes, px, w, h, 0, args.max_steps, factors_ptr=d_factors, id_ptr=d_id, cameras=cams)
+            r.sync()
+            capture_ms = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            for i, look in enumerate(look_files):
+                r.relight_scenes_into(scenes, [look_of(s_, look) for s_ in scenes], px, factors_ptr=d_factors, id_ptr=d_id, pixel_ptr=d_px)
+                r.sync()
+                r.memcpy_d2h(frames[i].ctypes.data, d_px, 4 * n * px)
+            dt = (time.perf_counter() - t0) * 1e3
+        finally:
+            for d in (d_factors, d_id, d_px):
+                if d:
+                    r.free(d)
+    finally:
+        r.close()
+    print(f"{len(look_files)} look(s) of {n} frames of {w}x{h}: capture {capture_ms:.3f}ms, relights and copies {dt:.3f}ms  "
+          "[light_interp_scenes, relight_rays_scenes]")
+    os.makedirs(args.out, exist_ok=True)
+    for i in range(len(look_files)):
+        for f in range(n):
+            write_ppm(os.path.join(args.out, f"look_{i:04d}_frame_{f:04d}.ppm"), frames[i, f])
+    return 0
+
+
 def pixel_arg(text, w, h):
     """"X,Y" -> (x, y) inside the w x h frame, or None"""
     try:
@@ -378,6 +442,22 @@ def main(argv=None) -> int:
     if args.move_lights and (not args.relight or args.samples != 1 or args.lens or args.adaptive != -1 or args.focus_at):
         print("--move-lights goes with --relight LOOK.lol ... -o DIR; not with --samples, --lens, --adaptive or --focus-at", file=sys.stderr)
         return 1
+    if args.relight and args.tween:
+        for flag, given, why in (
+                ("--tween-shutter", args.tween_shutter != 1, "a frame's blur is an averaged resolve over records, which relight_scenes_into does not make"),
+                ("--tween-samples", args.tween_samples != 1, "supersampled frames are an averaged resolve over records, which relight_scenes_into does not make"),
+                ("--samples", args.samples != 1, "it is the frame setting of a context, which the capture over scenes does not read"),
+                ("--lens", bool(args.lens), "a lens is an averaged resolve over records, which relight_scenes_into does not make"),
+                ("--move-lights", args.move_lights, "there is no light update over records: every look keeps its frame's light points and shininess")):
+            if given:
+                print(f"--tween B.lol --relight LOOK.lol ... does not go with {flag}: {why}", file=sys.stderr)
+                return 1
+        if (args.panorama or args.orbit or args.pick or args.focus_at or args.adaptive != -1 or not args.out or args.frames < 1
+                or args.frames > gpu.MAX_VIEWS):
+            print(f"--tween B.lol --relight LOOK.lol ... takes --frames N (N <= {gpu.MAX_VIEWS}) and -o DIR; not with --panorama, --orbit, "
+                  "--pick, --focus-at or --adaptive", file=sys.stderr)
+            return 1
+        return tween_relight_frames(sc, args, w, h)
     if args.relight:
         if (args.tween or args.panorama or args.orbit or args.pick or args.focus_at or args.adaptive != -1 or args.frames != 1
                 or not args.out):

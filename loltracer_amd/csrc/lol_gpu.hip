@@ -2726,3 +2726,178 @@ int lol_gpu_shade_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const
 	                           nullptr, out);
 }
 }  // extern "C"
+
+/*
+ * Scene light passes (include/lol_gpu.h, "Scene light passes"; the kernels: lol_kernel_scene_light.h): a capture and a resolve whose
+ * records are scenes of the uploaded program's structure.  A capture is a scene query (above) with a capture's planes: scene views'
+ * records with the two skips that rest on a look cleared on EVERY record, scene views' ring and ONE launch of light_interp_scenes with
+ * the record in the grid's y.  A resolve checks look r against scenes[r] as lol_gpu_relight checks a look against the uploaded
+ * program, copies the looks' tables — a LookRecord each and, behind the records, lights | materials | root_material — through
+ * lol_gpu::looks and launches relight_rays_scenes behind the copy.  The context's scene, kernels, keys, cached first step, tile-order
+ * state, sample settings and other rings are neither read nor changed; no scene kernel takes over, and nothing waits for one.
+ * Last in this file, its header included here: the kernels are instantiated behind all others (lol_gpu_internal.h).
+ */
+#include "lol_kernel_scene_light.h"
+
+static int scene_light_query(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, QuerySource src, size_t list_stride,
+                             const lol_gpu_light_passes* out) {
+	/* 1. the capture's own refusals; a NULL `cams` is 2.'s, so the camera source_refused looks at is there */
+	static const lol_frame_camera no_cam = {};
+	if (src.pixels && !cams) src.cam = &no_cam;
+	LOL_TRY(source_refused(ctx, src, !out, out));
+	/* 2. the records, their lists and the planes of all of them */
+	auto refuse = [&](const char* why) {
+		char text[128];
+		snprintf(text, sizeof text, "%s: %s", src.who, why);
+		return fail(ctx, LOL_GPU_ERR_ARG, text);
+	};
+	if (!scenes) return refuse("no scenes");
+	if (n_scenes < 1 || n_scenes > LOL_GPU_MAX_VIEWS) return refuse("the number of scenes is not in 1 ... LOL_GPU_MAX_VIEWS");
+	if (src.pixels && !cams) return refuse("no cameras");
+	if (list_stride != 0 && list_stride < src.n) return refuse("list_stride is neither 0 nor at least n");
+	const unsigned long long N = (unsigned long long)n_scenes * (unsigned long long)src.n;
+	if (N > 0xFFFFFFFFull) return refuse("more than 2^32 - 1 rays over all scenes");
+	if (out->light_stride != 0 && out->light_stride < N) return refuse("light_stride is neither 0 nor at least n_scenes * n");
+	/* 3. the scenes, as lol_gpu_render_scene_views refuses them */
+	LOL_TRY(scenes_refused(ctx, scenes, n_scenes));
+	if (src.n == 0) return LOL_GPU_OK;
+
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = src.stream ? static_cast<hipStream_t>(src.stream) : ctx->stream;
+	std::vector<lol::SceneView> views;
+	std::vector<uint32_t> data;
+	LOL_TRY(build_scene_records(ctx, src.pixels ? cams : nullptr, scenes, n_scenes, src.max_steps, true, views, data));
+	/* every factor of every ray, as at every capture: a look may differ from the record in exactly what the two skips rest on */
+	for (lol::SceneView& V : views) V.flags &= ~(lol::FLAG_MISS_SKIP | lol::FLAG_DARK_SKIP);
+	RingSet* S = nullptr;
+	LOL_TRY(queue_scene_records(ctx, views, data, s, &S));
+	lol::SceneList R = { reinterpret_cast<const lol::SceneView*>(S->d_buf), S->d_buf + views.size() * lol::SCENE_VIEW_DWORDS,
+	                     (unsigned long long)list_stride };
+	const lol_program& P = ctx->h_prog;
+	/* launch_scene_query's Launch, without what the record brings: camera, first step, lists, tables, ambient colour, the skips */
+	lol::Launch L;
+	memset(&L, 0, sizeof L);
+	L.max_steps = src.max_steps;
+	L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
+	lol::LightQuery Q = {};
+	Q.rays = src.rays;
+	Q.xy = src.xy;
+	Q.n = (uint32_t)src.n;
+	if (src.pixels) {
+		Q.flags |= lol::SHADE_FROM_PIXELS | (src.xy ? 0u : lol::LIGHT_ALL_PIXELS);
+		L.fw = (float)src.w; L.fh = (float)src.h;
+		L.w = src.w; L.h = src.h;
+	}
+	Q.stride = out->light_stride ? out->light_stride : N;
+	Q.out = { reinterpret_cast<lol::LightFactor*>(out->factors), out->hit_id, out->hit_dist, out->march_steps };
+	const unsigned lds = tables_lds_bytes(P);
+	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK), (unsigned)n_scenes);
+	void* args[] = { &L, &Q, &R };
+	const int kind = ctx->interp_sqrt_kind;
+	const hipError_t e = interp_dispatch(ctx, [&](auto v) {
+		constexpr int ssize = decltype(v)::ssize;
+		constexpr bool tables_global = decltype(v)::tables_global;
+		const void* k = kind == 3 ? reinterpret_cast<const void*>(&lol::light_interp_scenes<ssize, 3, tables_global>)
+		                          : reinterpret_cast<const void*>(&lol::light_interp_scenes<ssize, 0, tables_global>);
+		return hipLaunchKernel(k, grid, dim3(lol::BLOCK), args, lds, s);
+	});
+	return ring_done(ctx, *S, s, e, "scene light pass launch");
+}
+
+static int relight_scenes(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, int n_scenes, const lol_gpu_light_passes* in,
+                          size_t n, const lol_gpu_relit* out, void* stream) {
+	/* 1. what lol_gpu_relight refuses before it looks at its look */
+	LOL_TRY(relit_refused(ctx, in, out));
+	if (n > 0xFFFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight: more than 2^32 - 1 elements");
+	LOL_TRY(look_refused(ctx, nullptr, in, n));
+	/* 2. the records and the planes of all of them */
+	if (!scenes) return fail(ctx, LOL_GPU_ERR_ARG, "relight scenes: no scenes");
+	if (n_scenes < 1 || n_scenes > LOL_GPU_MAX_VIEWS) return fail(ctx, LOL_GPU_ERR_ARG, "relight scenes: the number of scenes is not in 1 ... LOL_GPU_MAX_VIEWS");
+	const unsigned long long N = (unsigned long long)n_scenes * (unsigned long long)n;
+	if (N > 0xFFFFFFFFull) return fail(ctx, LOL_GPU_ERR_ARG, "relight scenes: more than 2^32 - 1 elements over all scenes");
+	if (in->light_stride != 0 && in->light_stride < N) return fail(ctx, LOL_GPU_ERR_ARG, "relight scenes: light_stride is neither 0 nor at least n_scenes * n");
+	/* 3. the scenes: what the planes hold */
+	LOL_TRY(scenes_refused(ctx, scenes, n_scenes));
+	/* 4. the looks, each against its own scene: the first that is no look of it, by its record */
+	if (looks)
+		for (int r = 0; r < n_scenes; r++)
+			if (const char* why = look_differs(scenes[r], looks[r])) {
+				char text[200];
+				if (strncmp(why, "relight: ", 9) == 0) why += 9;
+				snprintf(text, sizeof text, "relight scenes: record %d: %s", r, why);
+				return fail(ctx, LOL_GPU_ERR_ARG, text);
+			}
+	if (n == 0) return LOL_GPU_OK;
+
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	const lol_program& U = ctx->h_prog;
+	/* a LookRecord per record and, behind them, each look's tables as an upload lays them out, on multiples of four dwords */
+	const size_t nt = lol::table_dwords(U.n_lights, U.n_materials, U.n_roots), nt4 = (nt + 3u) & ~(size_t)3u;
+	const size_t head = (size_t)n_scenes * lol::LOOK_RECORD_DWORDS, need = head + (size_t)n_scenes * nt4;
+	if (need > 0x7FFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight scenes: the looks of one call hold more than 2^31 dwords: fewer scenes per call");
+	RingSet& S = ctx->looks.next();
+	LOL_TRY(ring_take(ctx, S, need * 4, std::max<size_t>(1024, need + need / 2) * 4, RING_PINNED, s, nullptr, "tables of the looks of a relight over scenes"));
+	memset(S.h_buf, 0, need * 4);
+	for (int r = 0; r < n_scenes; r++) {
+		const lol_program& K = looks ? looks[r] : scenes[r];
+		lol::LookRecord rec;
+		rec.tables_offset = (uint32_t)((size_t)r * nt4);
+		rec.ambient[0] = K.ambient_color.x; rec.ambient[1] = K.ambient_color.y; rec.ambient[2] = K.ambient_color.z;
+		memcpy(S.h_buf + (size_t)r * lol::LOOK_RECORD_DWORDS, &rec, sizeof rec);
+		uint32_t* t = S.h_buf + head + rec.tables_offset;
+		if (U.n_lights) memcpy(t, K.lights, (size_t)U.n_lights * sizeof(lol_light));
+		t += (size_t)U.n_lights * lol::LIGHT_DWORDS;
+		memcpy(t, K.materials, (size_t)U.n_materials * sizeof(lol_material));
+		t += (size_t)U.n_materials * lol::MATERIAL_DWORDS;
+		if (U.n_roots) memcpy(t, K.root_material, (size_t)U.n_roots * 4);
+	}
+	const hipError_t ce = ring_copy(S, need * 4, s);
+	if (ce != hipSuccess) return ring_done(ctx, S, s, ce, "copy of the tables of the looks of a relight over scenes");
+	lol::LookList R = { reinterpret_cast<const lol::LookRecord*>(S.d_buf), S.d_buf + head };
+	/* relight_launch_fields' Launch without the context's tables and ambient colour: counts, gamma table, pixel format */
+	lol::Launch L;
+	memset(&L, 0, sizeof L);
+	L.n_lights = U.n_lights; L.n_materials = U.n_materials; L.n_roots = U.n_roots;
+	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
+	lol::RelightQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
+	Q.stride = in->light_stride ? in->light_stride : N;
+	Q.hit_id = in->hit_id;
+	Q.n = (uint32_t)n;
+	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
+	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK), (unsigned)n_scenes);
+	void* args[] = { &L, &Q, &R };
+	const void* fn = lol::tables_in_lds(U.n_lights, U.n_materials, U.n_roots) ? reinterpret_cast<const void*>(&lol::relight_rays_scenes<false>)
+	                                                                          : reinterpret_cast<const void*>(&lol::relight_rays_scenes<true>);
+	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, tables_lds_bytes(U), s);
+	return ring_done(ctx, S, s, e, "relight scenes launch");
+}
+
+extern "C" {
+
+/* no exception crosses the C boundary (the records are built in host memory) */
+int lol_gpu_light_scene_rays(lol_gpu* ctx, const lol_program* scenes, int n_scenes, const float* rays_dev, size_t n, size_t list_stride,
+                             int max_steps, const lol_gpu_light_passes* out, void* stream) {
+	try { return scene_light_query(ctx, nullptr, scenes, n_scenes, rays_source("scene light passes", rays_dev, n, max_steps, stream), list_stride, out); }
+	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a capture"); }
+	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a capture"); }
+}
+
+int lol_gpu_light_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, int w, int h, int max_steps,
+                               const uint32_t* xy_dev, size_t n, size_t list_stride, const lol_gpu_light_passes* out, void* stream) {
+	try {
+		return scene_light_query(ctx, cams, scenes, n_scenes, pixels_source("scene light passes", cams, w, h, xy_dev, n, max_steps, stream, true),
+		                         list_stride, out);
+	}
+	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a capture"); }
+	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a capture"); }
+}
+
+int lol_gpu_relight_scenes(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, int n_scenes, const lol_gpu_light_passes* in,
+                           size_t n, const lol_gpu_relit* out, void* stream) {
+	return relight_scenes(ctx, scenes, looks, n_scenes, in, n, out, stream);
+}
+}  // extern "C"

@@ -253,6 +253,10 @@ _LOL_GPU_H = {                                                          # includ
     "lol_gpu_light_update_pixels": (_int, [_vp, _prog, _cam, _int, _int, _vp, _size, C.c_uint64, C.c_uint64, _P(LightPasses), _vp]),
     "lol_gpu_relight_held": (_int, [_vp, _prog, _prog, _P(LightPasses), _size, _P(Relit), _vp]),
     "lol_gpu_relight_views_held": (_int, [_vp, _prog, _prog, _P(LightPasses), _int, _int, _int, _int, _int, _P(Relit), _vp]),
+    # scene light passes (include/lol_gpu.h, "Scene light passes"); their device lists are typed as the header types them
+    "lol_gpu_light_scene_rays": (_int, [_vp, _prog, _int, _P(C.c_float), _size, _size, _int, _P(LightPasses), _vp]),
+    "lol_gpu_light_scene_pixels": (_int, [_vp, _cam, _prog, _int, _int, _int, _int, _u32p, _size, _size, _P(LightPasses), _vp]),
+    "lol_gpu_relight_scenes": (_int, [_vp, _prog, _prog, _int, _P(LightPasses), _size, _P(Relit), _vp]),
 }
 
 _LOL_GPU_DIAG_H = {                                                     # include/lol_gpu_diag.h
@@ -1240,6 +1244,56 @@ class Renderer:
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
         self._check(self._lib.lol_gpu_relight_views_held(self._ctx, _ref(prog), _ref(hp), C.byref(planes), int(n_views),
                                                          int(cameras_per_view), w, h, int(samples), C.byref(out), _stream_arg(stream)))
+
+    # ---- scene light passes (include/lol_gpu.h, "Scene light passes")
+    def light_scene_rays_into(self, scenes, rays_ptr: int, n: int, list_stride: int = 0, max_steps: int = 256, factors_ptr: int = 0,
+                              id_ptr: int = 0, dist_ptr: int = 0, steps_ptr: int = 0, light_stride: int = 0, stream: int | None = None):
+        """Asynchronously capture the light passes of n rays under EACH of len(scenes) scenes of the prepared scene's structure
+        (lol_gpu_light_scene_rays), in one launch: element (r, i), at index e = r n + i of id / dist / steps and at
+        factors[l * light_stride + e] (light_stride = 0: len(scenes) n), is what light_rays_into writes for ray i of record r after
+        prepare(scenes[r]).  scenes and list_stride as trace_scene_rays_into takes them."""
+        items = list(scenes)
+        keep, progs, _ = self._scene_records("light_scene_rays_into", items)
+        out = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, steps_ptr or None)
+        rays = C.cast(C.c_void_p(rays_ptr), _P(C.c_float)) if rays_ptr else None
+        self._check(self._lib.lol_gpu_light_scene_rays(self._ctx, progs, len(items), rays, n, list_stride, max_steps, C.byref(out),
+                                                       _stream_arg(stream)))
+        del keep
+
+    def light_scene_pixels_into(self, scenes, n: int, w: int, h: int, list_stride: int = 0, max_steps: int = 256, xy_ptr: int = 0,
+                                factors_ptr: int = 0, id_ptr: int = 0, dist_ptr: int = 0, steps_ptr: int = 0, light_stride: int = 0,
+                                stream: int | None = None, cameras=None):
+        """light_scene_rays_into for the primary rays of n pixels of the w x h frame under each record's own scene and camera
+        (lol_gpu_light_scene_pixels); xy_ptr = 0: every pixel of the frame, element (r, y w + x), and n must be w h — with equal
+        scenes the planes of light_views_into.  cameras: as render_scene_views_into takes them; None: every scene's own."""
+        items = list(scenes)
+        keep, progs, arr = self._scene_records("light_scene_pixels_into", items, cameras, (w, h))
+        out = LightPasses(factors_ptr or None, light_stride, id_ptr or None, dist_ptr or None, steps_ptr or None)
+        xy = C.cast(C.c_void_p(xy_ptr), _u32p) if xy_ptr else None
+        self._check(self._lib.lol_gpu_light_scene_pixels(self._ctx, arr, progs, len(items), w, h, max_steps, xy, n, list_stride,
+                                                         C.byref(out), _stream_arg(stream)))
+        del keep
+
+    def relight_scenes_into(self, scenes, looks=None, n: int = 0, factors_ptr: int = 0, id_ptr: int = 0, rgb_linear_ptr: int = 0,
+                            rgb_ptr: int = 0, pixel_ptr: int = 0, light_stride: int = 0, stream: int | None = None):
+        """Asynchronously make the len(scenes) n elements of the planes of light_scene_*_into into colours, record r under looks[r]
+        (lol_gpu_relight_scenes): scenes says what the planes hold, looks[r] (a scene.Scene or scene.Program with scenes[r]'s geometry,
+        light points and shininess: scene.Scene.with_look) the look of record r; looks = None: the scenes' own.  Element (r, i) is
+        relight_into's on a renderer that prepared scenes[r]; outputs dense over r n + i, as relight_into's."""
+        items = list(scenes)
+        keep, progs, _ = self._scene_records("relight_scenes_into", items)
+        look_progs = None
+        if looks is not None:
+            look_items = list(looks)
+            if len(look_items) != len(items):
+                raise ValueError("relight_scenes_into: one look per scene")
+            keep_looks, look_progs, _ = self._scene_records("relight_scenes_into", look_items)
+            keep += keep_looks
+        planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
+        out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
+        self._check(self._lib.lol_gpu_relight_scenes(self._ctx, progs, look_progs, len(items), C.byref(planes), n, C.byref(out),
+                                                     _stream_arg(stream)))
+        del keep
 
     def set_cull(self, enable: bool):
         """Exact bounding-sphere culling of top-level objects in the specialised kernel; takes effect at the next prepare()."""
