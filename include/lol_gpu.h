@@ -1007,6 +1007,7 @@ int  lol_gpu_relight(lol_gpu* ctx, const lol_program* look /* HOST; NULL = the u
  * forms; planes in host memory; pitch or stride addressing of the outputs.
  * (Per-record scenes are built since for the capture and for the resolve of single leaves: "Scene light passes", below; with equal
  * scenes that capture writes this section's planes in one launch.)
+ * (Per-record scenes are built since for the averaged resolve too: "Relit scene views", below.)
  */
 int  lol_gpu_light_views(lol_gpu* ctx, const lol_frame_camera* cams /* HOST */, int n_views, int cams_per_view,
                          int w, int h, int samples, int max_steps, const lol_gpu_light_passes* out, void* stream);
@@ -1127,6 +1128,7 @@ int  lol_gpu_relight_views_held(lol_gpu* ctx, const lol_program* look, const lol
  * Out of scope: an averaged resolve over records (K records per view, or s x s samples: capture here, resolve with
  * lol_gpu_relight_views where the scenes are equal); light updates over records; a structure-module or scene-module form;
  * lol_gpu_multi_* forms; planes or lists in host memory; and lol_gpu_light_views made of this call.
+ * (An averaged resolve over records is built since: "Relit scene views", below.)
  */
 int  lol_gpu_light_scene_rays(lol_gpu* ctx, const lol_program* scenes /* HOST */, int n_scenes, const float* rays_dev, size_t n,
                               size_t list_stride, int max_steps, const lol_gpu_light_passes* out, void* stream);
@@ -1136,6 +1138,54 @@ int  lol_gpu_light_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams /* HO
 int  lol_gpu_relight_scenes(lol_gpu* ctx, const lol_program* scenes /* HOST: what the planes hold */,
                             const lol_program* looks /* HOST; NULL = the scenes themselves */, int n_scenes,
                             const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream);
+
+/*
+ * Relit scene views: the AVERAGED pictures of an animation under new looks without a march — s x s samples per pixel and K records
+ * per view, every record under a scene and a look of its own.  What "Relit views" is to lol_gpu_relight, for planes that
+ * lol_gpu_light_scene_pixels captured: lol_gpu_light_scene_pixels(ctx, cams, scenes, n_views * K, s * w, s * h, max_steps, NULL,
+ * s^2 w h, 0, out, stream) writes the leaves of an antialiased or motion-blurred animation in one launch, and this call makes them
+ * the frames of `looks`.
+ * Layout.  K = cams_per_view in {1, 2, 4, 8, 16}, s = samples in {1, 2, 4}.  Record r = v K + k; `scenes` and `looks` are HOST memory
+ * and hold n_views * K entries, copied before the call returns.  LEAF (v, k, Y, X) — sample column X < s w, sample row Y < s h of
+ * record r — is element e = (r s h + Y) s w + X of N = n_views K s^2 w h: relit views' layout, and what the capture above writes.
+ * The factor planes are light-major over all N elements (light l of element e at factors[l * light_stride + e]; light_stride 0 = N,
+ * else >= N); hit_id is dense over e.  The outputs are dense over pixels, at index (v h + y) w + x; any subset, not none.
+ * Contract.  Pixel (x, y) of view v, bracketed and rounded exactly so:
+ *   1. per leaf, c = the rgb_linear of lol_gpu_relight_scenes for its element under looks[r] (an id beyond n_roots is taken for 0);
+ *   2. per record k, m_k = the balanced binary32 tree over its s^2 leaves (s x + i, s y + j) in order j s + i, times 1 / s^2
+ *      (s = 1: the leaf itself, unscaled);
+ *   3. the balanced tree over m_0 ... m_{K-1} in order of k, times 1 / K (K = 1: m_0 itself);
+ *   4. gamma and the context's pixel format, exactly as for one sample's colour.
+ * Each record's scale first, then the tree over the records: the order lol_gpu_render_views_blend_samples fixes.
+ * So, bit for bit: pixel and rgb are the `pixel` and `rgb` of lol_gpu_render_scene_views_samples(cams, looks, n_views, K, w, h,
+ * max_steps, s), and with s = 1 those of lol_gpu_render_scene_views; with K = 1 and s = 1 the call is lol_gpu_relight_scenes with
+ * n = w * h (it forwards to it, and that call's words are then the refusals' words); with every scene the uploaded program and every
+ * look one look L it is lol_gpu_relight_views(L); rgb_linear is the mean before gamma, which the render calls do not expose; NaN and
+ * infinite looks are included.
+ * Looks.  looks[r] must be a look of scenes[r] in look_differs' sense — exactly as for lol_gpu_relight_scenes: equal counts, ops,
+ * light points, shininess and root_material.  looks == NULL: the scenes' own look.  The K records of one view may carry K different
+ * looks and K different scenes.
+ * Refused, with nothing launched and nothing written, in this order:
+ *  1. everything lol_gpu_relight_views refuses before it looks at its look: no context, NULL in / out, no output, n_views < 1 or bad
+ *     frame geometry, K outside {1, 2, 4, 8, 16}, s outside {1, 2, 4}, N > 2^32 - 1, no program (LOL_GPU_ERR_NO_PROGRAM), the
+ *     planes against N;
+ *  2. LOL_GPU_ERR_ARG for NULL scenes or n_views * K > LOL_GPU_MAX_VIEWS;
+ *  3. the scene refusals of lol_gpu_render_scene_views: a missing table, another structure, a root_material out of range;
+ *  4. the first looks[r] that is no look of scenes[r], with "relight scene views: record r: " and lol_gpu_relight's reason behind it
+ *     in lol_gpu_error's text.
+ * Asynchronous on `stream` (NULL = the context's own stream; LOL_GPU_STREAM_DEFAULT as elsewhere).  One copy of the looks' tables
+ * through lol_gpu_relight's ring of 8 sets, under its rules (HIP's special stream handles included), and ONE launch
+ * (relight_views_scenes: the view in the grid's y, the look read per record).  No scratch, no host wait.  The context's scene,
+ * kernels, lol_gpu_kernel_key, tile-order state, sample settings and other rings are neither read nor changed: a frame after the call
+ * is the frame it would have been.  No module switch has an effect on this call.
+ * Out of scope: light updates over records; an edge-adaptive relit form; a structure-module or scene-module form; lol_gpu_multi_*
+ * forms; planes in host memory; pitch or stride addressing of the outputs; lol_gpu_light_views made of the scene capture; and lifting
+ * the CLI's --tween-shutter refusal beside --relight (the blurred form is reached from Python: cameras_per_view = K).
+ */
+int  lol_gpu_relight_scene_views(lol_gpu* ctx, const lol_program* scenes /* HOST: what the planes hold; n_views * K entries */,
+                                 const lol_program* looks /* HOST; NULL = the scenes themselves; n_views * K entries */,
+                                 const lol_gpu_light_passes* in, int n_views, int cams_per_view, int w, int h, int samples,
+                                 const lol_gpu_relit* out, void* stream);
 
 #ifdef __cplusplus
 }

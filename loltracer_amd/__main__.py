@@ -4,7 +4,7 @@
                           [--tween B.lol --frames N [--tween-samples S] [--tween-shutter K] -o DIR]
                           [--tween B.lol --frames N --pick X,Y] [--tween B.lol --frames N --lens R --focus-at X,Y [--lens-samples K] -o DIR]
                           [--relight LOOK.lol [LOOK2.lol ...] [--samples S] [--lens R --focus D --lens-samples K] [--move-lights] -o DIR]
-                          [--tween B.lol --frames N --relight LOOK.lol [LOOK2.lol ...] -o DIR]
+                          [--tween B.lol --frames N --relight LOOK.lol [LOOK2.lol ...] [--tween-samples S] -o DIR]
 
 Renders a `.lol` scene on the GPU through the C ABI (liblol_gpu.so) and writes a binary PPM — the Python spelling of
 `loltracer_amd/lib/lol_headless`.  With --orbit K it renders K views from a circle round the scene (scene.orbit_cameras) as ONE batch
@@ -41,7 +41,10 @@ the files are again what LOOK.lol alone writes, byte for byte.  Not with --sampl
 A.lol --tween B.lol --frames N --relight LOOK.lol [LOOK2.lol ...] -o DIR relights an ANIMATION: ONE capture over the N tweened scenes
 (Renderer.light_scene_pixels_into: every frame under its own scene, one launch) and per look ONE Renderer.relight_scenes_into, frame
 f under its own scene with the look's intensities and colours (look_of: scene.Scene.with_look from the look's file), into
-DIR/look_LLLL_frame_FFFF.ppm — the frames those scenes render, byte for byte.  Not with --tween-shutter, --tween-samples, --samples,
+DIR/look_LLLL_frame_FFFF.ppm — the frames those scenes render, byte for byte.  With --tween-samples S beside it the frames are
+SUPERSAMPLED: the one capture takes every sample of every frame (the S w x S h grid of each scene) and each look is ONE
+Renderer.relight_scene_views_into, averaged in linear light before gamma — the files --tween B.lol --tween-samples S writes of the
+look's scenes, byte for byte.  Not with --tween-shutter (the blurred form is reached from Python: cameras_per_view=K), --samples,
 --lens or --move-lights.
 There is no CPU rendering path."""
 from __future__ import annotations
@@ -235,7 +238,8 @@ def look_of(sc, look):
 
 
 def tween_relight_frames(sc, args, w, h) -> int:
-    """N tweened scenes captured in one launch, one relight over all of them per look, one PPM per look and frame"""
+    """N tweened scenes captured in one launch — every sample of every frame —, one relight over all of them per look, one PPM per look
+    and frame"""
     try:
         other = S.Scene.parse_file(args.tween)
         look_files = [S.Scene.parse_file(path) for path in args.relight]
@@ -250,23 +254,26 @@ def tween_relight_frames(sc, args, w, h) -> int:
         if why is not None:
             print(f"--relight {path}: not a look of {args.scene}: {why}", file=sys.stderr)
             return 1
-    n, px, nl = args.frames, w * h, len(sc.lights())
+    n, px, nl, ss = args.frames, w * h, len(sc.lights()), args.tween_samples
+    leaves = ss * ss * px                    # of one frame: the ss w x ss h grid under its scene
     scenes = [S.tween(sc, other, t) for f in range(n) for t in S.shutter_times(f, n, 1)]
     cams = [sc.camera] * n
     r = gpu.Renderer(args.device)
     try:
         r.prepare(sc, wait=False)            # (capture and relight run on the interpreter: nothing waits for the scene compiler)
         frames = np.zeros((len(look_files), n, h, w), dtype=np.uint32)
-        d_factors = r.malloc(16 * n * px * nl) if nl else 0
-        d_id, d_px = r.malloc(4 * n * px), r.malloc(4 * n * px)
+        d_factors = r.malloc(16 * n * leaves * nl) if nl else 0
+        d_id, d_px = r.malloc(4 * n * leaves), r.malloc(4 * n * px)
         try:
             t0 = time.perf_counter()
-            r.light_scene_pixels_into(scenes, px, w, h, 0, args.max_steps, factors_ptr=d_factors, id_ptr=d_id, cameras=cams)
+            r.light_scene_pixels_into(scenes, leaves, ss * w, ss * h, 0, args.max_steps, factors_ptr=d_factors, id_ptr=d_id, cameras=cams)
             r.sync()
             capture_ms = (time.perf_counter() - t0) * 1e3
             t0 = time.perf_counter()
             for i, look in enumerate(look_files):
-                r.relight_scenes_into(scenes, [look_of(s_, look) for s_ in scenes], px, factors_ptr=d_factors, id_ptr=d_id, pixel_ptr=d_px)
+                # (one sample per pixel: the call forwards to relight_scenes_into's)
+                r.relight_scene_views_into(scenes, [look_of(s_, look) for s_ in scenes], n, 1, w, h, ss, factors_ptr=d_factors, id_ptr=d_id,
+                                           pixel_ptr=d_px)
                 r.sync()
                 r.memcpy_d2h(frames[i].ctypes.data, d_px, 4 * n * px)
             dt = (time.perf_counter() - t0) * 1e3
@@ -276,8 +283,8 @@ def tween_relight_frames(sc, args, w, h) -> int:
                     r.free(d)
     finally:
         r.close()
-    print(f"{len(look_files)} look(s) of {n} frames of {w}x{h}: capture {capture_ms:.3f}ms, relights and copies {dt:.3f}ms  "
-          "[light_interp_scenes, relight_rays_scenes]")
+    print(f"{len(look_files)} look(s) of {n} frames of {w}x{h}{f', {ss}x{ss} samples per pixel' if ss > 1 else ''}: capture {capture_ms:.3f}ms, "
+          f"relights and copies {dt:.3f}ms  [light_interp_scenes, {'relight_views_scenes' if ss > 1 else 'relight_rays_scenes'}]")
     os.makedirs(args.out, exist_ok=True)
     for i in range(len(look_files)):
         for f in range(n):
@@ -444,8 +451,7 @@ def main(argv=None) -> int:
         return 1
     if args.relight and args.tween:
         for flag, given, why in (
-                ("--tween-shutter", args.tween_shutter != 1, "a frame's blur is an averaged resolve over records, which relight_scenes_into does not make"),
-                ("--tween-samples", args.tween_samples != 1, "supersampled frames are an averaged resolve over records, which relight_scenes_into does not make"),
+                ("--tween-shutter", args.tween_shutter != 1, "the blurred form is reached from Python (relight_scene_views_into, cameras_per_view=K)"),
                 ("--samples", args.samples != 1, "it is the frame setting of a context, which the capture over scenes does not read"),
                 ("--lens", bool(args.lens), "a lens is an averaged resolve over records, which relight_scenes_into does not make"),
                 ("--move-lights", args.move_lights, "there is no light update over records: every look keeps its frame's light points and shininess")):

@@ -2804,6 +2804,60 @@ static int scene_light_query(lol_gpu* ctx, const lol_frame_camera* cams, const l
 	return ring_done(ctx, *S, s, e, "scene light pass launch");
 }
 
+/* 4. of both resolves over records: the first looks[r] that is no look of scenes[r], by its record, behind `who` */
+static int record_looks_refused(lol_gpu* ctx, const char* who, const lol_program* scenes, const lol_program* looks, int n_records) {
+	if (looks)
+		for (int r = 0; r < n_records; r++)
+			if (const char* why = look_differs(scenes[r], looks[r])) {
+				char text[200];
+				if (strncmp(why, "relight: ", 9) == 0) why += 9;
+				snprintf(text, sizeof text, "%s: record %d: %s", who, r, why);
+				return fail(ctx, LOL_GPU_ERR_ARG, text);
+			}
+	return LOL_GPU_OK;
+}
+
+/* The looks of a resolve over records onto the device behind what `s` holds, through lol_gpu::looks: a LookRecord per record and,
+ * behind them, each look's tables as an upload lays them out, on multiples of four dwords — look r's at r nt4
+ * dwords (lol::look_stride, lol_kernel_scene_light_views.h, is this nt4).  `S` is then the ring's set, which the caller hands to ring_done with its launch. */
+static int queue_record_looks(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, int n_records, hipStream_t s, RingSet*& S,
+                              lol::LookList& R) {
+	const lol_program& U = ctx->h_prog;
+	const size_t nt = lol::table_dwords(U.n_lights, U.n_materials, U.n_roots), nt4 = (nt + 3u) & ~(size_t)3u;
+	const size_t head = (size_t)n_records * lol::LOOK_RECORD_DWORDS, need = head + (size_t)n_records * nt4;
+	if (need > 0x7FFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight scenes: the looks of one call hold more than 2^31 dwords: fewer scenes per call");
+	S = &ctx->looks.next();
+	LOL_TRY(ring_take(ctx, *S, need * 4, std::max<size_t>(1024, need + need / 2) * 4, RING_PINNED, s, nullptr, "tables of the looks of a relight over scenes"));
+	memset(S->h_buf, 0, need * 4);
+	for (int r = 0; r < n_records; r++) {
+		const lol_program& K = looks ? looks[r] : scenes[r];
+		lol::LookRecord rec;
+		rec.tables_offset = (uint32_t)((size_t)r * nt4);
+		rec.ambient[0] = K.ambient_color.x; rec.ambient[1] = K.ambient_color.y; rec.ambient[2] = K.ambient_color.z;
+		memcpy(S->h_buf + (size_t)r * lol::LOOK_RECORD_DWORDS, &rec, sizeof rec);
+		uint32_t* t = S->h_buf + head + rec.tables_offset;
+		if (U.n_lights) memcpy(t, K.lights, (size_t)U.n_lights * sizeof(lol_light));
+		t += (size_t)U.n_lights * lol::LIGHT_DWORDS;
+		memcpy(t, K.materials, (size_t)U.n_materials * sizeof(lol_material));
+		t += (size_t)U.n_materials * lol::MATERIAL_DWORDS;
+		if (U.n_roots) memcpy(t, K.root_material, (size_t)U.n_roots * 4);
+	}
+	const hipError_t ce = ring_copy(*S, need * 4, s);
+	if (ce != hipSuccess) return ring_done(ctx, *S, s, ce, "copy of the tables of the looks of a relight over scenes");
+	R = { reinterpret_cast<const lol::LookRecord*>(S->d_buf), S->d_buf + head };
+	return LOL_GPU_OK;
+}
+
+/* relight_launch_fields' Launch without the context's tables and ambient colour, which the records bring: counts, gamma table, pixel
+ * format */
+static void record_resolve_launch_fields(lol_gpu* ctx, lol::Launch& L) {
+	const lol_program& U = ctx->h_prog;
+	memset(&L, 0, sizeof L);
+	L.n_lights = U.n_lights; L.n_materials = U.n_materials; L.n_roots = U.n_roots;
+	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
+}
+
 static int relight_scenes(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, int n_scenes, const lol_gpu_light_passes* in,
                           size_t n, const lol_gpu_relit* out, void* stream) {
 	/* 1. what lol_gpu_relight refuses before it looks at its look */
@@ -2819,48 +2873,17 @@ static int relight_scenes(lol_gpu* ctx, const lol_program* scenes, const lol_pro
 	/* 3. the scenes: what the planes hold */
 	LOL_TRY(scenes_refused(ctx, scenes, n_scenes));
 	/* 4. the looks, each against its own scene: the first that is no look of it, by its record */
-	if (looks)
-		for (int r = 0; r < n_scenes; r++)
-			if (const char* why = look_differs(scenes[r], looks[r])) {
-				char text[200];
-				if (strncmp(why, "relight: ", 9) == 0) why += 9;
-				snprintf(text, sizeof text, "relight scenes: record %d: %s", r, why);
-				return fail(ctx, LOL_GPU_ERR_ARG, text);
-			}
+	LOL_TRY(record_looks_refused(ctx, "relight scenes", scenes, looks, n_scenes));
 	if (n == 0) return LOL_GPU_OK;
 
 	LOL_HIP(ctx, hipSetDevice(ctx->device));
 	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
 	const lol_program& U = ctx->h_prog;
-	/* a LookRecord per record and, behind them, each look's tables as an upload lays them out, on multiples of four dwords */
-	const size_t nt = lol::table_dwords(U.n_lights, U.n_materials, U.n_roots), nt4 = (nt + 3u) & ~(size_t)3u;
-	const size_t head = (size_t)n_scenes * lol::LOOK_RECORD_DWORDS, need = head + (size_t)n_scenes * nt4;
-	if (need > 0x7FFFFFFFu) return fail(ctx, LOL_GPU_ERR_ARG, "relight scenes: the looks of one call hold more than 2^31 dwords: fewer scenes per call");
-	RingSet& S = ctx->looks.next();
-	LOL_TRY(ring_take(ctx, S, need * 4, std::max<size_t>(1024, need + need / 2) * 4, RING_PINNED, s, nullptr, "tables of the looks of a relight over scenes"));
-	memset(S.h_buf, 0, need * 4);
-	for (int r = 0; r < n_scenes; r++) {
-		const lol_program& K = looks ? looks[r] : scenes[r];
-		lol::LookRecord rec;
-		rec.tables_offset = (uint32_t)((size_t)r * nt4);
-		rec.ambient[0] = K.ambient_color.x; rec.ambient[1] = K.ambient_color.y; rec.ambient[2] = K.ambient_color.z;
-		memcpy(S.h_buf + (size_t)r * lol::LOOK_RECORD_DWORDS, &rec, sizeof rec);
-		uint32_t* t = S.h_buf + head + rec.tables_offset;
-		if (U.n_lights) memcpy(t, K.lights, (size_t)U.n_lights * sizeof(lol_light));
-		t += (size_t)U.n_lights * lol::LIGHT_DWORDS;
-		memcpy(t, K.materials, (size_t)U.n_materials * sizeof(lol_material));
-		t += (size_t)U.n_materials * lol::MATERIAL_DWORDS;
-		if (U.n_roots) memcpy(t, K.root_material, (size_t)U.n_roots * 4);
-	}
-	const hipError_t ce = ring_copy(S, need * 4, s);
-	if (ce != hipSuccess) return ring_done(ctx, S, s, ce, "copy of the tables of the looks of a relight over scenes");
-	lol::LookList R = { reinterpret_cast<const lol::LookRecord*>(S.d_buf), S.d_buf + head };
-	/* relight_launch_fields' Launch without the context's tables and ambient colour: counts, gamma table, pixel format */
+	RingSet* S = nullptr;
+	lol::LookList R;
+	LOL_TRY(queue_record_looks(ctx, scenes, looks, n_scenes, s, S, R));
 	lol::Launch L;
-	memset(&L, 0, sizeof L);
-	L.n_lights = U.n_lights; L.n_materials = U.n_materials; L.n_roots = U.n_roots;
-	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
-	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
+	record_resolve_launch_fields(ctx, L);
 	lol::RelightQuery Q;
 	memset(&Q, 0, sizeof Q);
 	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
@@ -2873,7 +2896,7 @@ static int relight_scenes(lol_gpu* ctx, const lol_program* scenes, const lol_pro
 	const void* fn = lol::tables_in_lds(U.n_lights, U.n_materials, U.n_roots) ? reinterpret_cast<const void*>(&lol::relight_rays_scenes<false>)
 	                                                                          : reinterpret_cast<const void*>(&lol::relight_rays_scenes<true>);
 	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, tables_lds_bytes(U), s);
-	return ring_done(ctx, S, s, e, "relight scenes launch");
+	return ring_done(ctx, *S, s, e, "relight scenes launch");
 }
 
 extern "C" {
@@ -2899,5 +2922,72 @@ int lol_gpu_light_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const
 int lol_gpu_relight_scenes(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, int n_scenes, const lol_gpu_light_passes* in,
                            size_t n, const lol_gpu_relit* out, void* stream) {
 	return relight_scenes(ctx, scenes, looks, n_scenes, in, n, out, stream);
+}
+}  // extern "C"
+
+/*
+ * Relit scene views (include/lol_gpu.h, "Relit scene views"; the kernel: lol_kernel_scene_light_views.h): the averaged resolve of
+ * relit views over planes whose every record holds a scene of its own, under a look per record.  The refusals of relit views up to
+ * its look, then those of the resolve over records (above); the looks' LookRecords and tables go through lol_gpu::looks as
+ * relight_scenes lays them out (queue_record_looks), and ONE launch of relight_views_scenes follows the copy, the view in the grid's
+ * y.  Nothing is allocated on the host, so nothing throws.  The context's scene, kernels, keys, tile-order state, sample settings and
+ * other rings are neither read nor changed.
+ * Last in this file, its header included here: the kernels are instantiated behind all others (lol_gpu_internal.h).
+ */
+#include "lol_kernel_scene_light_views.h"
+
+static int relight_scene_views(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, const lol_gpu_light_passes* in, int n_views,
+                               int cams_per_view, int w, int h, int samples, const lol_gpu_relit* out, void* stream) {
+	/* 1. what lol_gpu_relight_views refuses before it looks at its look */
+	LOL_TRY(relit_refused(ctx, in, out));
+	size_t N = 0;
+	LOL_TRY(views_shape_refused(ctx, n_views, cams_per_view, w, h, samples, &N));
+	LOL_TRY(look_refused(ctx, nullptr, in, N));
+	/* 2. the records */
+	if (!scenes) return fail(ctx, LOL_GPU_ERR_ARG, "relight scene views: no scenes");
+	const long long records = (long long)n_views * cams_per_view;
+	if (records > LOL_GPU_MAX_VIEWS) return fail(ctx, LOL_GPU_ERR_ARG, "relight scene views: more than LOL_GPU_MAX_VIEWS records (n_views * cams_per_view)");
+	/* a pixel that is its one leaf: the resolve of single leaves, which refuses 3. and 4. in its own words */
+	if (cams_per_view == 1 && samples == 1) return lol_gpu_relight_scenes(ctx, scenes, looks, n_views, in, (size_t)w * (size_t)h, out, stream);
+	/* 3. the scenes: what the planes hold */
+	LOL_TRY(scenes_refused(ctx, scenes, (int)records));
+	/* 4. the looks, each against its own scene: the first that is no look of it, by its record */
+	LOL_TRY(record_looks_refused(ctx, "relight scene views", scenes, looks, (int)records));
+
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	const lol_program& U = ctx->h_prog;
+	RingSet* S = nullptr;
+	lol::LookList R;
+	LOL_TRY(queue_record_looks(ctx, scenes, looks, (int)records, s, S, R));
+	lol::Launch L;
+	record_resolve_launch_fields(ctx, L);
+	lol::RelightSceneViewsQuery Q;
+	memset(&Q, 0, sizeof Q);
+	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
+	Q.stride = in->light_stride ? in->light_stride : N;
+	Q.hit_id = in->hit_id;
+	Q.w = (uint32_t)w; Q.h = (uint32_t)h;
+	Q.s_log2 = samples == 4 ? 2u : samples == 2 ? 1u : 0u;
+	Q.cams = (uint32_t)cams_per_view;
+	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
+	/* a wave per 64 pixels of ONE view, whatever s and K: it takes them in s^2 rounds of 64 / s^2 */
+	const unsigned long long lanes = ((unsigned long long)w * (unsigned long long)h + 63u) / 64u * 64u;
+	const dim3 grid((unsigned)((lanes + lol::BLOCK - 1) / lol::BLOCK), (unsigned)n_views);
+	/* the K looks of a view staged as one run where they fit, read where they lie where they do not: the kernel's rule */
+	const bool staged = lol::views_looks_in_lds(Q.cams, U.n_lights, U.n_materials, U.n_roots);
+	const unsigned lds = staged ? Q.cams * lol::look_stride(U.n_lights, U.n_materials, U.n_roots) * 4u : 0u;
+	void* args[] = { &L, &Q, &R };
+	const void* fn = staged ? reinterpret_cast<const void*>(&lol::relight_views_scenes<false>)
+	                        : reinterpret_cast<const void*>(&lol::relight_views_scenes<true>);
+	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	return ring_done(ctx, *S, s, e, "relight scene views launch");
+}
+
+extern "C" {
+
+int lol_gpu_relight_scene_views(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, const lol_gpu_light_passes* in, int n_views,
+                                int cams_per_view, int w, int h, int samples, const lol_gpu_relit* out, void* stream) {
+	return relight_scene_views(ctx, scenes, looks, in, n_views, cams_per_view, w, h, samples, out, stream);
 }
 }  // extern "C"

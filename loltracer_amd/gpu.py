@@ -257,6 +257,8 @@ _LOL_GPU_H = {                                                          # includ
     "lol_gpu_light_scene_rays": (_int, [_vp, _prog, _int, _P(C.c_float), _size, _size, _int, _P(LightPasses), _vp]),
     "lol_gpu_light_scene_pixels": (_int, [_vp, _cam, _prog, _int, _int, _int, _int, _u32p, _size, _size, _P(LightPasses), _vp]),
     "lol_gpu_relight_scenes": (_int, [_vp, _prog, _prog, _int, _P(LightPasses), _size, _P(Relit), _vp]),
+    # relit scene views (include/lol_gpu.h, "Relit scene views")
+    "lol_gpu_relight_scene_views": (_int, [_vp, _prog, _prog, _P(LightPasses), _int, _int, _int, _int, _int, _P(Relit), _vp]),
 }
 
 _LOL_GPU_DIAG_H = {                                                     # include/lol_gpu_diag.h
@@ -1293,6 +1295,35 @@ class Renderer:
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
         self._check(self._lib.lol_gpu_relight_scenes(self._ctx, progs, look_progs, len(items), C.byref(planes), n, C.byref(out),
                                                      _stream_arg(stream)))
+        del keep
+
+    # ---- relit scene views (include/lol_gpu.h, "Relit scene views")
+    def relight_scene_views_into(self, scenes, looks=None, n_views: int = 0, cameras_per_view: int = 1, w: int = 0, h: int = 0,
+                                 samples: int = 1, factors_ptr: int = 0, id_ptr: int = 0, rgb_linear_ptr: int = 0, rgb_ptr: int = 0,
+                                 pixel_ptr: int = 0, light_stride: int = 0, stream: int | None = None):
+        """Asynchronously make the n_views averaged views of w x h from the leaves light_scene_pixels_into captured over
+        len(scenes) = n_views cameras_per_view records of the samples w x samples h grid (lol_gpu_relight_scene_views): per leaf
+        relight_scenes_into's linear colour under looks[r], per record the tree mean over its samples x samples leaves, then the tree
+        mean over the view's cameras_per_view records, then gamma and this renderer's pixel format — the pixel and rgb of
+        render_scene_views_into(cameras, looks, ..., cameras_per_view, samples=samples), bit for bit, in one copy and one launch.
+        scenes says what the planes hold; looks as relight_scenes_into takes them (None: the scenes' own).  rgb_linear / rgb: 3 floats
+        per pixel, pixel: one element, dense over [view, y, x]; 0 = not wanted (not all three)."""
+        items = list(scenes)
+        k = int(cameras_per_view)
+        if len(items) != int(n_views) * k:
+            raise ValueError("relight_scene_views_into: len(scenes) must be n_views * cameras_per_view")
+        keep, progs, _ = self._scene_records("relight_scene_views_into", items)
+        look_progs = None
+        if looks is not None:
+            look_items = list(looks)
+            if len(look_items) != len(items):
+                raise ValueError("relight_scene_views_into: one look per scene")
+            keep_looks, look_progs, _ = self._scene_records("relight_scene_views_into", look_items)
+            keep += keep_looks
+        planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
+        out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
+        self._check(self._lib.lol_gpu_relight_scene_views(self._ctx, progs, look_progs, C.byref(planes), int(n_views), k, w, h,
+                                                          int(samples), C.byref(out), _stream_arg(stream)))
         del keep
 
     def set_cull(self, enable: bool):
