@@ -78,6 +78,20 @@ std::mutex g_rtc_mutex;
 
 namespace {
 
+/* No exception crosses the C boundary: `body()`, or — where it throws — the failure of a call that was preparing `what` in host memory
+ * (the analysis of a scene, the records of a call: whatever the body had queued or committed before stays as it is) */
+template <class Body>
+int guarded(lol_gpu* ctx, const char* what, Body&& body) {
+	auto failed = [&](const char* how) {
+		char text[128];
+		snprintf(text, sizeof text, "%s while preparing %s", how, what);
+		return fail(ctx, LOL_GPU_ERR_HIP, text);           /* (fail copies the text) */
+	};
+	try { return body(); }
+	catch (const std::bad_alloc&) { return failed("out of host memory"); }
+	catch (...) { return failed("unexpected failure"); }
+}
+
 /* the interpreter's kernel of a family (lol_gpu_internal.h, KERNEL_FAMILIES) for one stack class, sqrt kind and table placement: its
  * address, for hipLaunchKernel */
 template <int SSIZE, int KIND, bool TABLES_GLOBAL>
@@ -338,6 +352,17 @@ hipError_t interp_dispatch(const lol_gpu* ctx, Launcher&& launch) {
 	}
 	return hipErrorInvalidValue;           /* a rung without an instantiation: never a silent substitute */
 }
+/* ... and THE launch of an interpreter's kernel that reads the tables: the instantiation for the program's rung and the root kind the
+ * upload proved, a block of lol::BLOCK lanes.  `kernel_of(variant, kind)`: the address of the caller's kernel for an InterpVariant and
+ * a std::integral_constant of the kind — the caller names the kernel, so its instantiations stand where the caller stands. */
+template <class KernelOf>
+hipError_t launch_interp(const lol_gpu* ctx, dim3 grid, void** args, unsigned lds, hipStream_t s, KernelOf&& kernel_of) {
+	const int kind = ctx->interp_sqrt_kind;
+	return interp_dispatch(ctx, [&](auto v) {
+		const void* k = kind == 3 ? kernel_of(v, std::integral_constant<int, 3>()) : kernel_of(v, std::integral_constant<int, 0>());
+		return hipLaunchKernel(k, grid, dim3(lol::BLOCK), args, lds, s);
+	});
+}
 
 /* ONE launch of a kernel of family `f`: the scene module's where the module carries the family, else the interpreter's instantiation
  * for the program's rung (interp_dispatch: a rung without one is an error, never a substitute).  `args`: the addresses of the
@@ -350,13 +375,25 @@ hipError_t launch_family(const lol_gpu* ctx, KernelFamily f, bool counts, void**
 	const unsigned lds = lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u;
 	if (const SceneKernel* k = family_kernel(ctx, f))
 		return hipModuleLaunchKernel(counts ? k->counting[f] : k->fn[f], grid.x, grid.y, grid.z, lol::BLOCK, 1, 1, lds, s, args, nullptr);
-	const int kind = ctx->interp_sqrt_kind;
-	return interp_dispatch(ctx, [&](auto v) {
-		constexpr int ssize = decltype(v)::ssize;
-		constexpr bool tables_global = decltype(v)::tables_global;
-		const void* fn = kind == 3 ? interp_kernel<ssize, 3, tables_global>(f) : interp_kernel<ssize, 0, tables_global>(f);
-		return hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	return launch_interp(ctx, grid, args, lds, s, [f](auto v, auto kind) {
+		return interp_kernel<decltype(v)::ssize, decltype(kind)::value, decltype(v)::tables_global>(f);
 	});
+}
+
+/* lights | materials | root_material of `P` as one run of lol::table_dwords dwords at `dst`: how an upload lays a program's tables
+ * out, and what every copy of a scene's or a look's tables to the device holds */
+void pack_tables(uint32_t* dst, const lol_program& P) {
+	if (P.n_lights) memcpy(dst, P.lights, (size_t)P.n_lights * sizeof(lol_light));
+	dst += (size_t)P.n_lights * lol::LIGHT_DWORDS;
+	memcpy(dst, P.materials, (size_t)P.n_materials * sizeof(lol_material));
+	dst += (size_t)P.n_materials * lol::MATERIAL_DWORDS;
+	if (P.n_roots) memcpy(dst, P.root_material, (size_t)P.n_roots * 4);
+}
+/* ... and its inverse: the three tables of a launch whose counts are set, from such a run on the device */
+void launch_tables(lol::Launch& L, const uint32_t* packed) {
+	L.lights        = packed;
+	L.materials     = L.lights + (size_t)L.n_lights * lol::LIGHT_DWORDS;
+	L.root_material = L.materials + (size_t)L.n_materials * lol::MATERIAL_DWORDS;
 }
 
 /*
@@ -676,9 +713,7 @@ static int upload_program(lol_gpu* ctx, const lol_program* prog);
  * lists, the tables) allocates as it goes — a std::bad_alloc anywhere in it is an upload that failed, with the scene the
  * context had still rendering (every step before the commit works on the side). */
 int lol_gpu_upload_program(lol_gpu* ctx, const lol_program* prog) {
-	try { return upload_program(ctx, prog); }
-	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scene"); }
-	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scene"); }
+	return guarded(ctx, "the scene", [&] { return upload_program(ctx, prog); });
 }
 
 static int upload_program(lol_gpu* ctx, const lol_program* prog) {
@@ -733,14 +768,7 @@ static int upload_program(lol_gpu* ctx, const lol_program* prog) {
 	if (injected) ctx->fail_uploads--;
 	/* lights | materials | root_material as one array of dwords, in the set no frame reads; grown when this scene needs more */
 	std::vector<uint32_t> tables(lol::table_dwords(prog->n_lights, prog->n_materials, prog->n_roots));
-	{
-		uint32_t* t = tables.data();
-		if (prog->n_lights) memcpy(t, prog->lights, (size_t)prog->n_lights * sizeof(lol_light));
-		t += (size_t)prog->n_lights * lol::LIGHT_DWORDS;
-		memcpy(t, prog->materials, (size_t)prog->n_materials * sizeof(lol_material));
-		t += (size_t)prog->n_materials * lol::MATERIAL_DWORDS;
-		if (prog->n_roots) memcpy(t, prog->root_material, (size_t)prog->n_roots * 4);
-	}
+	pack_tables(tables.data(), *prog);
 	auto fit = [&](uint32_t*& buf, size_t& cap, size_t need) -> hipError_t {
 		if (need <= cap) return hipSuccess;
 		uint32_t* nb = nullptr;
@@ -820,20 +848,29 @@ static int ensure_refine_grid(lol_gpu* ctx) {
 	return LOL_GPU_OK;
 }
 
+/* The part of a launch that is the context's whoever brings the scene — the uploaded program, or the records of a call, which have
+ * its structure: the tables' counts (alone: a capture over records, which packs no pixel), the gamma table, the surface's pixel format */
+static void launch_counts(const lol_gpu* ctx, lol::Launch& L) {
+	const lol_program& P = ctx->h_prog;
+	L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
+}
+static void context_launch_fields(const lol_gpu* ctx, lol::Launch& L) {
+	launch_counts(ctx, L);
+	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
+	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
+}
+
 /* The part of a launch that is the uploaded scene's and the context's: program and tables, ambient, the exact skips that hold for
- * every camera, the gamma table, the surface's pixel format, the diagnostics' buffers.  What depends on the camera (which copy of the
+ * every camera, context_launch_fields' part, the diagnostics' buffers.  What depends on the camera (which copy of the
  * macro-op list, FLAG_SHADOW_SETTLED, the first step) is the caller's: per frame, or per view of a batch. */
 static void scene_launch_fields(const lol_gpu* ctx, const lol_gpu_debug* dbg, lol::Launch& L) {
 	const lol_program& P = ctx->h_prog;
-	L.n_ops = ctx->n_mops; L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
-	L.ops           = ctx->d_mops[ctx->cur];
-	L.lights        = ctx->d_tables[ctx->cur];
-	L.materials     = L.lights + (size_t)P.n_lights * lol::LIGHT_DWORDS;
-	L.root_material = L.materials + (size_t)P.n_materials * lol::MATERIAL_DWORDS;
-	L.ambient[0] = P.ambient_color.x; L.ambient[1] = P.ambient_color.y; L.ambient[2] = P.ambient_color.z;
 	L.flags = (ctx->miss_skip ? lol::FLAG_MISS_SKIP : 0u) | (ctx->dark_skip ? lol::FLAG_DARK_SKIP : 0u);
-	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
-	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
+	context_launch_fields(ctx, L);
+	L.n_ops = ctx->n_mops;
+	L.ops   = ctx->d_mops[ctx->cur];
+	launch_tables(L, ctx->d_tables[ctx->cur]);
+	L.ambient[0] = P.ambient_color.x; L.ambient[1] = P.ambient_color.y; L.ambient[2] = P.ambient_color.z;
 	if (dbg) {
 		L.dbg_rgb = dbg->rgb; L.dbg_hit_dist = dbg->hit_dist;
 		L.dbg_hit_id = dbg->hit_id; L.dbg_steps = dbg->steps;
@@ -1749,7 +1786,16 @@ int lol_gpu_sdf_batch(lol_gpu* ctx, const float* pts_dev, float* dist_dev, uint3
  *   QuerySource         where a call's elements come from, and the name its family's refusals carry
  *   source_refused      every refusal of a *_rays or *_pixels call, in the order a host sees them
  *   launch_on_stream    the call's device, its stream, the launch and the launch's error
+ *   source_fields       the source's half of a Launch and a query: the list, its length, a frame's size
  *   launch_scene_query  the scene's half of a shading query's or a capture's launch: the Launch, what rests on the camera, the tables' LDS
+ *   record_query        a list query under each record's own scene: the trace, shade and capture forms are its three callers, further down
+ * and, further up and further down, what they share with the frames and with the families whose records bring their own scene:
+ *   guarded               the C boundary's guard against exceptions, for the calls that prepare something in host memory
+ *   launch_interp         the interpreter's instantiation for the program's rung and root kind, launched
+ *   pack_tables           a program's three tables as an upload lays them out (launch_tables: a Launch's three pointers into them)
+ *   context_launch_fields the context's part of every Launch: the tables' counts, the gamma table, the pixel format
+ *   look_differs          the walk over a program that says what a look, or a held program, may not differ in
+ *   record_resolve        a resolve under each record's own look: both resolves over records are its callers
  */
 struct QuerySource {
 	const char*     who;             /* "ray query", "shading query", "light passes": what the family's refusals begin with */
@@ -1780,16 +1826,18 @@ static int passes_refused(lol_gpu* ctx, const lol_gpu_light_passes* p, size_t n)
 	return LOL_GPU_OK;
 }
 
+/* LOL_GPU_ERR_ARG in the family's words: "<who>: <why>" */
+static int source_refuse(lol_gpu* ctx, const QuerySource& src, const char* why) {
+	char text[128];
+	snprintf(text, sizeof text, "%s: %s", src.who, why);
+	return fail(ctx, LOL_GPU_ERR_ARG, text);           /* (fail copies the text) */
+}
 /* The refusals of a list query, in THE order (tests/test_gpu_rays.py, test_refusals, and its three siblings pin it): a bad argument
  * beats a missing program, and a missing program the camera and the frame's geometry — which are asked for with n = 0 too.
  * `no_output`: the family's own test of its outputs; `planes`: a capture's, held to passes_refused where the parent held them. */
 static int source_refused(lol_gpu* ctx, const QuerySource& src, bool no_output, const lol_gpu_light_passes* planes = nullptr) {
 	if (!ctx) return LOL_GPU_ERR_ARG;
-	auto refuse = [&](const char* why) {
-		char text[128];
-		snprintf(text, sizeof text, "%s: %s", src.who, why);
-		return fail(ctx, LOL_GPU_ERR_ARG, text);           /* (fail copies the text) */
-	};
+	auto refuse = [&](const char* why) { return source_refuse(ctx, src, why); };
 	if (!(src.pixels ? (const void*)src.xy : (const void*)src.rays) && !src.list_optional && src.n > 0) return refuse("no list");
 	if (no_output) return refuse("no output");
 	if (src.max_steps < 0 || src.n > 0xFFFFFFFFu) return refuse("max_steps < 0 or more than 2^32 - 1 rays");
@@ -1814,6 +1862,21 @@ static int launch_on_stream(lol_gpu* ctx, void* stream, const char* what, Launch
 /* dynamic LDS of the kernels that stage the scene's tables and nothing else (lol_kernel.h, tables_in_lds): no output tile */
 static unsigned tables_lds_bytes(const lol_program& P) {
 	return lol::tables_in_lds(P.n_lights, P.n_materials, P.n_roots) ? lol::table_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u : 0u;
+}
+
+/* The source's half of a shading query, a capture or an update — `Q` a ShadeQuery, LightQuery or LightUpdateQuery — and of its Launch:
+ * the list and its length; for pixels the frame's size and SHADE_FROM_PIXELS, with LIGHT_ALL_PIXELS where there is no list (only a
+ * capture or an update gets here without one: source_refused).  The camera is not set here: it is the call's, or each record's own. */
+template <class Query>
+static void source_fields(const QuerySource& src, lol::Launch& L, Query& Q) {
+	Q.rays = src.rays;
+	Q.xy = src.xy;
+	Q.n = (uint32_t)src.n;
+	if (src.pixels) {
+		Q.flags |= lol::SHADE_FROM_PIXELS | (src.xy ? 0u : lol::LIGHT_ALL_PIXELS);
+		L.fw = (float)src.w; L.fh = (float)src.h;
+		L.w = src.w; L.h = src.h;
+	}
 }
 
 /* ---- ray queries.  A RayQuery carries its own camera: no Launch, no tables, a wave per block. */
@@ -1898,29 +1961,66 @@ static int launch_scene_query(lol_gpu* ctx, const QuerySource& src, Query& Q, bo
 	const bool sane = !src.pixels || camera_sane(*src.cam);
 	if (ctx->finite_scene && sane) Q.flags |= lol::SHADE_SCENE_SANE;
 	if (ctx->shadow_settle && sane) L.flags |= lol::FLAG_SHADOW_SETTLED;
+	source_fields(src, L, Q);
 	if (src.pixels) {
-		Q.flags |= lol::SHADE_FROM_PIXELS;
 		memcpy(&L.cam, src.cam, sizeof L.cam);
-		L.fw = (float)src.w; L.fh = (float)src.h;
-		L.w = src.w; L.h = src.h;
 		if (first_step(ctx, *src.cam, src.max_steps)) { L.flags |= lol::FLAG_FIRST_STEP; L.first_dist = ctx->first_dist; L.first_id = ctx->first_id; }
 	}
-	Q.rays = src.rays;
-	Q.xy = src.xy;
-	Q.n = (uint32_t)src.n;
 	return launch_on_stream(ctx, src.stream, what, [&](hipStream_t s) {
 		const hipFunction_t fn = module_fn ? module_fn(ctx) : nullptr;
 		const unsigned lds = tables_lds_bytes(ctx->h_prog);
 		const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
 		void* args[] = { &L, &Q };
 		if (fn) return hipModuleLaunchKernel(fn, grid.x, 1, 1, lol::BLOCK, 1, 1, lds, s, args, nullptr);
-		const int kind = ctx->interp_sqrt_kind;
-		return interp_dispatch(ctx, [&](auto v) {
-			const void* k = kind == 3 ? interp_kernel(v, std::integral_constant<int, 3>()) : interp_kernel(v, std::integral_constant<int, 0>());
-			return hipLaunchKernel(k, grid, dim3(lol::BLOCK), args, lds, s);
-		});
+		return launch_interp(ctx, grid, args, lds, s, interp_kernel);
 	});
 }
+
+/* (scene views' records, their ring and the refusal of their scenes stand with scene views, further down) */
+static int build_scene_records(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n, int max_steps, bool lists,
+                               std::vector<lol::SceneView>& views, std::vector<uint32_t>& data);
+static int queue_scene_records(lol_gpu* ctx, const std::vector<lol::SceneView>& views, const std::vector<uint32_t>& data, hipStream_t s, RingSet** out);
+static int scenes_refused(lol_gpu* ctx, const lol_program* scenes, int n);
+
+/* THE host path of a list query under each record's own scene, for its three forms — trace, shade, capture (`planes`: its planes, and
+ * what makes it one).  In the order a host sees (include/lol_gpu.h numbers the refusals the same way):
+ *  1. the single-scene query's refusals (source_refused); a NULL `cams` is 2.'s, so the camera source_refused looks at is there;
+ *  2. the records and their lists, and a capture's planes over all of them;
+ *  3. the scenes, as lol_gpu_render_scene_views refuses them; then nothing for n = 0.
+ * Then the call's device and stream, scene views' records (every factor of every ray at a capture, as at every capture: a look may
+ * differ from the record in exactly what the two skips rest on, so they are cleared on EVERY record) through scene views' ring, the
+ * family's `launch(R, s)` — its query, its grid with the record in y, its kernel — and the ring's event behind it, `what` its name. */
+template <class Launcher>
+static int record_query(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, QuerySource src, size_t list_stride,
+                        bool no_output, const lol_gpu_light_passes* planes, const char* what, Launcher&& launch) {
+	static const lol_frame_camera no_cam = {};
+	if (src.pixels && !cams) src.cam = &no_cam;
+	LOL_TRY(source_refused(ctx, src, no_output, planes));
+	auto refuse = [&](const char* why) { return source_refuse(ctx, src, why); };
+	if (!scenes) return refuse("no scenes");
+	if (n_scenes < 1 || n_scenes > LOL_GPU_MAX_VIEWS) return refuse("the number of scenes is not in 1 ... LOL_GPU_MAX_VIEWS");
+	if (src.pixels && !cams) return refuse("no cameras");
+	if (list_stride != 0 && list_stride < src.n) return refuse("list_stride is neither 0 nor at least n");
+	const unsigned long long N = (unsigned long long)n_scenes * (unsigned long long)src.n;
+	if (N > 0xFFFFFFFFull) return refuse("more than 2^32 - 1 rays over all scenes");
+	if (planes && planes->light_stride != 0 && planes->light_stride < N) return refuse("light_stride is neither 0 nor at least n_scenes * n");
+	LOL_TRY(scenes_refused(ctx, scenes, n_scenes));
+	if (src.n == 0) return LOL_GPU_OK;
+
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = src.stream ? static_cast<hipStream_t>(src.stream) : ctx->stream;
+	std::vector<lol::SceneView> views;
+	std::vector<uint32_t> data;
+	LOL_TRY(build_scene_records(ctx, src.pixels ? cams : nullptr, scenes, n_scenes, src.max_steps, true, views, data));
+	if (planes) for (lol::SceneView& V : views) V.flags &= ~(lol::FLAG_MISS_SKIP | lol::FLAG_DARK_SKIP);
+	RingSet* S = nullptr;
+	LOL_TRY(queue_scene_records(ctx, views, data, s, &S));
+	lol::SceneList R = { reinterpret_cast<const lol::SceneView*>(S->d_buf), S->d_buf + views.size() * lol::SCENE_VIEW_DWORDS,
+	                     (unsigned long long)list_stride };
+	return ring_done(ctx, *S, s, launch(R, s), what);
+}
+/* the grid of such a launch: a block per `block` elements of the list in x, the record in y */
+static dim3 record_grid(size_t n, unsigned block, int n_scenes) { return dim3((unsigned)((n + block - 1) / block), (unsigned)n_scenes); }
 
 static int shade_query(lol_gpu* ctx, const QuerySource& src, const lol_gpu_shades* out) {
 	LOL_TRY(source_refused(ctx, src, !out || (!out->rgb_linear && !out->rgb && !out->pixel && !out->hit_dist && !out->hit_id && !out->steps)));
@@ -2027,12 +2127,8 @@ static hipError_t launch_scene_views(const lol_gpu* ctx, bool lin, bool aa, void
 	const unsigned lds = lol::common_lds_dwords(P.n_lights, P.n_materials, P.n_roots) * 4u;
 	if (const hipFunction_t f = structure_kernel(ctx, lin, aa))
 		return hipModuleLaunchKernel(f, grid.x, grid.y, grid.z, lol::BLOCK, 1, 1, lds, s, args, nullptr);
-	const int kind = ctx->interp_sqrt_kind;
-	return interp_dispatch(ctx, [&](auto v) {
-		constexpr int ssize = decltype(v)::ssize;
-		constexpr bool tables_global = decltype(v)::tables_global;
-		const void* fn = kind == 3 ? scene_interp_kernel<ssize, 3, tables_global>(lin, aa) : scene_interp_kernel<ssize, 0, tables_global>(lin, aa);
-		return hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
+	return launch_interp(ctx, grid, args, lds, s, [lin, aa](auto v, auto kind) {
+		return scene_interp_kernel<decltype(v)::ssize, decltype(kind)::value, decltype(v)::tables_global>(lin, aa);
 	});
 }
 
@@ -2079,16 +2175,8 @@ static int build_scene_records(lol_gpu* ctx, const lol_frame_camera* cams, const
 		}
 		align();
 		V.tables_offset = (uint32_t)data.size();
-		const size_t nt = lol::table_dwords(P.n_lights, P.n_materials, P.n_roots);
-		data.resize(data.size() + nt);
-		{
-			uint32_t* t = data.data() + V.tables_offset;
-			if (P.n_lights) memcpy(t, P.lights, (size_t)P.n_lights * sizeof(lol_light));
-			t += (size_t)P.n_lights * lol::LIGHT_DWORDS;
-			memcpy(t, P.materials, (size_t)P.n_materials * sizeof(lol_material));
-			t += (size_t)P.n_materials * lol::MATERIAL_DWORDS;
-			if (P.n_roots) memcpy(t, P.root_material, (size_t)P.n_roots * 4);
-		}
+		data.resize(data.size() + lol::table_dwords(P.n_lights, P.n_materials, P.n_roots));
+		pack_tables(data.data() + V.tables_offset, P);
 		align();
 		V.nums_offset = (uint32_t)data.size();
 		data.resize(data.size() + (size_t)P.n_ops * lol::OP_NUMBERS);
@@ -2188,9 +2276,9 @@ extern "C" {
 int lol_gpu_render_scene_views(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_views, int cams_per_view,
                                int w, int h, int max_steps, void* dst, size_t pitch_bytes, size_t view_stride_bytes,
                                const lol_gpu_debug* dbg, void* stream) {
-	try { return render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, 1, dst, pitch_bytes, view_stride_bytes, dbg, stream); }
-	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a batch"); }
-	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a batch"); }
+	return guarded(ctx, "the scenes of a batch", [&] {
+		return render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, 1, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+	});
 }
 
 /* s = 1 IS lol_gpu_render_scene_views: the call forwards to it behind the one refusal that comes first */
@@ -2201,9 +2289,9 @@ int lol_gpu_render_scene_views_samples(lol_gpu* ctx, const lol_frame_camera* cam
 	if (samples != 1 && samples != 2 && samples != 4) return fail(ctx, LOL_GPU_ERR_ARG, "samples per axis must be 1, 2 or 4");
 	if (samples == 1)
 		return lol_gpu_render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, dst, pitch_bytes, view_stride_bytes, dbg, stream);
-	try { return render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, samples, dst, pitch_bytes, view_stride_bytes, dbg, stream); }
-	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a batch"); }
-	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a batch"); }
+	return guarded(ctx, "the scenes of a batch", [&] {
+		return render_scene_views(ctx, cams, scenes, n_views, cams_per_view, w, h, max_steps, samples, dst, pitch_bytes, view_stride_bytes, dbg, stream);
+	});
 }
 
 int lol_gpu_set_scene_view_samples(lol_gpu* ctx, int enable) {
@@ -2270,7 +2358,6 @@ int lol_gpu_scene_views_state(const lol_gpu* ctx) { return ctx ? ctx->tiers.stru
 static int light_query(lol_gpu* ctx, const QuerySource& src, const lol_gpu_light_passes* out) {
 	LOL_TRY(source_refused(ctx, src, !out, out));
 	lol::LightQuery Q = {};
-	if (src.pixels && !src.xy) Q.flags = lol::LIGHT_ALL_PIXELS;
 	Q.stride = out->light_stride ? out->light_stride : src.n;
 	Q.out = { reinterpret_cast<lol::LightFactor*>(out->factors), out->hit_id, out->hit_dist, out->march_steps };
 	return launch_scene_query(ctx, src, Q, true, nullptr, "light pass launch", [](auto v, auto kind) {
@@ -2278,52 +2365,53 @@ static int light_query(lol_gpu* ctx, const QuerySource& src, const lol_gpu_light
 	});
 }
 
-/* What a look may not differ from the uploaded program in, or nullptr: the first difference, for the context's error */
-static const char* look_differs(const lol_program& U, const lol_program& K) {
+/* What `K` — the `noun` of the refusal: a look, or the program planes are said to hold — may not differ from `U` in, or nullptr: the
+ * first difference, written to `text` behind `who` (and, for the look of record `record` >= 0, "record <r>"), for the context's error.
+ * `look_only`: with the two tests that hold a look to what was captured and that a program which is merely to have U's geometry need
+ * not pass — a moved light, a changed shininess. */
+static const char* look_differs(const lol_program& U, const lol_program& K, const char* who, int record, const char* noun, bool look_only,
+                                char (&text)[200]) {
+	auto say = [&](const char* fmt) {
+		char of_record[64];
+		if (record >= 0) { snprintf(of_record, sizeof of_record, "%s: record %d", who, record); who = of_record; }
+		snprintf(text, sizeof text, fmt, who, noun);
+		return text;
+	};
 	if (K.n_ops != U.n_ops || K.n_lights != U.n_lights || K.n_materials != U.n_materials || K.n_roots != U.n_roots || K.max_stack != U.max_stack)
-		return "relight: the look differs from the uploaded program in a count (ops, lights, materials, roots, max_stack)";
+		return say("%s: the %s differs from the uploaded program in a count (ops, lights, materials, roots, max_stack)");
 	if ((K.n_ops && !K.ops) || (K.n_lights && !K.lights) || !K.materials || (K.n_roots && !K.root_material))
-		return "relight: malformed look: a table is missing";
+		return say("%s: malformed %s: a table is missing");
 	for (uint32_t i = 0; i < K.n_ops; i++)
 		if (K.ops[i].op != U.ops[i].op || K.ops[i].id != U.ops[i].id || memcmp(K.ops[i].f, U.ops[i].f, sizeof K.ops[i].f) != 0)
-			return "relight: the look differs from the uploaded program in an op (opcode, id or a number): capture again";
-	for (uint32_t l = 0; l < K.n_lights; l++)
+			return say("%s: the %s differs from the uploaded program in an op (opcode, id or a number): capture again");
+	for (uint32_t l = 0; look_only && l < K.n_lights; l++)
 		if (memcmp(&K.lights[l].point, &U.lights[l].point, sizeof K.lights[l].point) != 0)
-			return "relight: the look moves a light: capture again";
-	for (uint32_t m = 0; m < K.n_materials; m++)
+			return say("%s: the %s moves a light: capture again");
+	for (uint32_t m = 0; look_only && m < K.n_materials; m++)
 		if (memcmp(&K.materials[m].shininess, &U.materials[m].shininess, 4) != 0)
-			return "relight: the look changes a shininess: capture again";
+			return say("%s: the %s changes a shininess: capture again");
 	for (uint32_t i = 0; i < K.n_roots; i++) {
-		if (K.root_material[i] >= K.n_materials) return "relight: material index out of range in the look";
-		if (K.root_material[i] != U.root_material[i]) return "relight: the look gives an object another material: capture again";
+		if (K.root_material[i] >= K.n_materials) return say("%s: material index out of range in the %s");
+		if (K.root_material[i] != U.root_material[i]) return say("%s: the %s gives an object another material: capture again");
 	}
 	return nullptr;
 }
 
 /* The Launch of a resolve under `look` (nullptr: the context's own tables, nothing copied): counts, gamma table and pixel format the
- * context's; a look's lights | materials | root_material go through lol_gpu::looks onto the device behind what `s` holds, and `S` is
- * then the ring's set, which the caller hands to ring_done with its launch. */
+ * context's; a look's tables (pack_tables: its counts are the program's, the refusals have seen to it) go through lol_gpu::looks onto
+ * the device behind what `s` holds, and `S` is then the ring's set, which the caller hands to ring_done with its launch. */
 static int relight_launch_fields(lol_gpu* ctx, const lol_program* look, hipStream_t s, lol::Launch& L, RingSet*& S) {
 	memset(&L, 0, sizeof L);
 	scene_launch_fields(ctx, nullptr, L);       /* counts, the context's own tables and ambient colour, gamma table, pixel format */
-	const lol_program& P = ctx->h_prog;
 	S = nullptr;
 	if (look) {
-		/* lights | materials | root_material of the look, as an upload lays them out */
-		const size_t need = lol::table_dwords(P.n_lights, P.n_materials, P.n_roots);
+		const size_t need = lol::table_dwords(look->n_lights, look->n_materials, look->n_roots);
 		S = &ctx->looks.next();
 		LOL_TRY(ring_take(ctx, *S, need * 4, std::max<size_t>(1024, need + need / 2) * 4, RING_PINNED, s, nullptr, "tables of a look"));
-		uint32_t* t = S->h_buf;
-		if (P.n_lights) memcpy(t, look->lights, (size_t)P.n_lights * sizeof(lol_light));
-		t += (size_t)P.n_lights * lol::LIGHT_DWORDS;
-		memcpy(t, look->materials, (size_t)P.n_materials * sizeof(lol_material));
-		t += (size_t)P.n_materials * lol::MATERIAL_DWORDS;
-		if (P.n_roots) memcpy(t, look->root_material, (size_t)P.n_roots * 4);
+		pack_tables(S->h_buf, *look);
 		const hipError_t ce = ring_copy(*S, need * 4, s);
 		if (ce != hipSuccess) return ring_done(ctx, *S, s, ce, "copy of the tables of a look");
-		L.lights        = S->d_buf;
-		L.materials     = L.lights + (size_t)P.n_lights * lol::LIGHT_DWORDS;
-		L.root_material = L.materials + (size_t)P.n_materials * lol::MATERIAL_DWORDS;
+		launch_tables(L, S->d_buf);
 		L.ambient[0] = look->ambient_color.x; L.ambient[1] = look->ambient_color.y; L.ambient[2] = look->ambient_color.z;
 	}
 	return LOL_GPU_OK;
@@ -2341,7 +2429,8 @@ static int relit_refused(lol_gpu* ctx, const lol_gpu_light_passes* in, const lol
 static int look_refused(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t n) {
 	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
 	LOL_TRY(passes_refused(ctx, in, n));
-	if (look) if (const char* why = look_differs(ctx->h_prog, *look)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	char text[200];
+	if (look) if (const char* why = look_differs(ctx->h_prog, *look, "relight", -1, "look", true, text)) return fail(ctx, LOL_GPU_ERR_ARG, why);
 	return LOL_GPU_OK;
 }
 
@@ -2381,16 +2470,23 @@ static int views_shape_refused(lol_gpu* ctx, int n_views, int cams_per_view, int
 	return LOL_GPU_OK;
 }
 
+/* The planes' half of a resolve's query — a RelightQuery, RelightViewsQuery or RelightSceneViewsQuery, zeroed here —: the planes,
+ * over `n_all` elements in all, and the three outputs */
+template <class Query>
+static void resolve_planes(Query& Q, const lol_gpu_light_passes* in, size_t n_all, const lol_gpu_relit* out) {
+	memset(&Q, 0, sizeof Q);
+	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
+	Q.stride = in->light_stride ? in->light_stride : n_all;
+	Q.hit_id = in->hit_id;
+	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
+}
+
 /* a resolve of n elements whose every refusal has passed */
 static int relight_launch(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t n, const lol_gpu_relit* out, void* stream) {
 	if (n == 0) return LOL_GPU_OK;
 	lol::RelightQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
-	Q.stride = in->light_stride ? in->light_stride : n;
-	Q.hit_id = in->hit_id;
+	resolve_planes(Q, in, n, out);
 	Q.n = (uint32_t)n;
-	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
 	return launch_resolve(ctx, look, stream, Q, Q.n, reinterpret_cast<const void*>(&lol::relight_rays<false>), reinterpret_cast<const void*>(&lol::relight_rays<true>));
 }
 
@@ -2398,16 +2494,12 @@ static int relight_launch(lol_gpu* ctx, const lol_program* look, const lol_gpu_l
 static int relight_views_launch(lol_gpu* ctx, const lol_program* look, const lol_gpu_light_passes* in, size_t N, int n_views, int cams_per_view,
                                 int w, int h, int samples, const lol_gpu_relit* out, void* stream) {
 	lol::RelightViewsQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
-	Q.stride = in->light_stride ? in->light_stride : N;
-	Q.hit_id = in->hit_id;
+	resolve_planes(Q, in, N, out);
 	Q.n_pixels = (uint32_t)((size_t)n_views * (size_t)w * (size_t)h);
 	Q.w = (uint32_t)w; Q.h = (uint32_t)h;
 	Q.s_log2 = samples == 4 ? 2u : samples == 2 ? 1u : 0u;
 	Q.cams = (uint32_t)cams_per_view;
 	Q.last_view = (uint32_t)n_views - 1u;
-	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
 	/* a wave per 64 pixels, whatever s and K: it takes them in s^2 rounds of 64 / s^2 */
 	const unsigned long long lanes = ((unsigned long long)Q.n_pixels + 63u) / 64u * 64u;
 	return launch_resolve(ctx, look, stream, Q, lanes, reinterpret_cast<const void*>(&lol::relight_views<false>), reinterpret_cast<const void*>(&lol::relight_views<true>));
@@ -2477,24 +2569,6 @@ int lol_gpu_relight_views(lol_gpu* ctx, const lol_program* look, const lol_gpu_l
  * (shadow_settle_ok: its light points are part of the test) — what a context that uploaded the look would have cached.  Nothing of the
  * frames' state is read or written, the cached first step included: nothing marches from the eye.
  */
-/* What `K` (a look of an update, or what planes are said to hold) may not differ from the uploaded program in: look_differs' tests
- * without the two for light points and shininess, in its order and wording.  nullptr, or the first difference written to `text`. */
-static const char* geometry_differs(const lol_program& U, const lol_program& K, const char* who, const char* noun, char (&text)[160]) {
-	auto say = [&](const char* fmt) { snprintf(text, sizeof text, fmt, who, noun); return text; };
-	if (K.n_ops != U.n_ops || K.n_lights != U.n_lights || K.n_materials != U.n_materials || K.n_roots != U.n_roots || K.max_stack != U.max_stack)
-		return say("%s: the %s differs from the uploaded program in a count (ops, lights, materials, roots, max_stack)");
-	if ((K.n_ops && !K.ops) || (K.n_lights && !K.lights) || !K.materials || (K.n_roots && !K.root_material))
-		return say("%s: malformed %s: a table is missing");
-	for (uint32_t i = 0; i < K.n_ops; i++)
-		if (K.ops[i].op != U.ops[i].op || K.ops[i].id != U.ops[i].id || memcmp(K.ops[i].f, U.ops[i].f, sizeof K.ops[i].f) != 0)
-			return say("%s: the %s differs from the uploaded program in an op (opcode, id or a number): capture again");
-	for (uint32_t i = 0; i < K.n_roots; i++) {
-		if (K.root_material[i] >= K.n_materials) return say("%s: material index out of range in the %s");
-		if (K.root_material[i] != U.root_material[i]) return say("%s: the %s gives an object another material: capture again");
-	}
-	return nullptr;
-}
-
 static int light_update(lol_gpu* ctx, const lol_program* look, const QuerySource& src, uint64_t march_lights, uint64_t specular_lights,
                         const lol_gpu_light_passes* planes) {
 	if (!ctx) return LOL_GPU_ERR_ARG;
@@ -2505,14 +2579,11 @@ static int light_update(lol_gpu* ctx, const lol_program* look, const QuerySource
 	const uint64_t masks = march_lights | specular_lights;
 	if (P.n_lights < 64u && (masks >> P.n_lights) != 0)
 		return fail(ctx, LOL_GPU_ERR_ARG, "light update: a mask names a light the program has not (lights from the 64th on: capture again)");
-	char text[160];
-	if (const char* why = geometry_differs(P, *look, "light update", "look", text)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	char text[200];
+	if (const char* why = look_differs(P, *look, "light update", -1, "look", false, text)) return fail(ctx, LOL_GPU_ERR_ARG, why);
 	if (src.n == 0 || masks == 0) return LOL_GPU_OK;
 
 	lol::LightUpdateQuery Q = {};
-	Q.rays = src.rays;
-	Q.xy = src.xy;
-	Q.n = (uint32_t)src.n;
 	Q.march_lights = march_lights;
 	Q.specular_lights = specular_lights;
 	Q.stride = planes->light_stride ? planes->light_stride : src.n;
@@ -2530,22 +2601,12 @@ static int light_update(lol_gpu* ctx, const lol_program* look, const QuerySource
 	const bool finite = shadow_settle_ok(*look), sane = !src.pixels || camera_sane(*src.cam);
 	if (finite && sane) Q.flags |= lol::SHADE_SCENE_SANE;
 	if ((ctx->want_skips & 4u) && finite && sane) L.flags |= lol::FLAG_SHADOW_SETTLED;
-	if (src.pixels) {
-		Q.flags |= lol::SHADE_FROM_PIXELS | (src.xy ? 0u : lol::LIGHT_ALL_PIXELS);
-		memcpy(&L.cam, src.cam, sizeof L.cam);
-		L.fw = (float)src.w; L.fh = (float)src.h;
-		L.w = src.w; L.h = src.h;
-	}
-	const unsigned lds = tables_lds_bytes(P);
+	source_fields(src, L, Q);
+	if (src.pixels) memcpy(&L.cam, src.cam, sizeof L.cam);
 	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK));
 	void* args[] = { &L, &Q };
-	const int kind = ctx->interp_sqrt_kind;
-	const hipError_t e = interp_dispatch(ctx, [&](auto v) {
-		constexpr int ssize = decltype(v)::ssize;
-		constexpr bool tables_global = decltype(v)::tables_global;
-		const void* k = kind == 3 ? reinterpret_cast<const void*>(&lol::light_update_interp<ssize, 3, tables_global>)
-		                          : reinterpret_cast<const void*>(&lol::light_update_interp<ssize, 0, tables_global>);
-		return hipLaunchKernel(k, grid, dim3(lol::BLOCK), args, lds, s);
+	const hipError_t e = launch_interp(ctx, grid, args, tables_lds_bytes(P), s, [](auto v, auto kind) {
+		return reinterpret_cast<const void*>(&lol::light_update_interp<decltype(v)::ssize, decltype(kind)::value, decltype(v)::tables_global>);
 	});
 	return ring_done(ctx, *S, s, e, "light update launch");
 }
@@ -2555,9 +2616,9 @@ static int light_update(lol_gpu* ctx, const lol_program* look, const QuerySource
 static int held_look_refused(lol_gpu* ctx, const lol_program* look, const lol_program& held, const lol_gpu_light_passes* in, size_t n) {
 	if (!ctx->have_prog) return fail(ctx, LOL_GPU_ERR_NO_PROGRAM, "no scene program uploaded");
 	LOL_TRY(passes_refused(ctx, in, n));
-	char text[160];
-	if (const char* why = geometry_differs(ctx->h_prog, held, "relight", "held program", text)) return fail(ctx, LOL_GPU_ERR_ARG, why);
-	if (const char* why = look_differs(held, look ? *look : ctx->h_prog)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	char text[200];
+	if (const char* why = look_differs(ctx->h_prog, held, "relight", -1, "held program", false, text)) return fail(ctx, LOL_GPU_ERR_ARG, why);
+	if (const char* why = look_differs(held, look ? *look : ctx->h_prog, "relight", -1, "look", true, text)) return fail(ctx, LOL_GPU_ERR_ARG, why);
 	return LOL_GPU_OK;
 }
 
@@ -2596,224 +2657,125 @@ int lol_gpu_relight_views_held(lol_gpu* ctx, const lol_program* look, const lol_
 
 /*
  * Scene queries (include/lol_gpu.h, "Scene queries"; the kernels: lol_kernel_scene_queries.h): a list query (QuerySource,
- * source_refused) answered under each record's own scene — scene views' records (build_scene_records, with the record's two query
- * bits), scene views' ring (queue_scene_records) and ONE launch of the interpreter's kernel with the record in the grid's y.  What
+ * source_refused) answered under each record's own scene — record_query (with the list queries, above), whose callers here fill their
+ * query and name their kernel: ONE launch of the interpreter's, the record in the grid's y.  What
  * ray_query and launch_scene_query decide from the uploaded scene and the call's camera is decided per record, from that record's own.
  * The context's scene, kernels, keys, cached first step, tile-order state, sample settings and other rings are neither read nor
  * changed, and no scene kernel takes over here: the interpreter answers, whatever the module switches say.
  * Last in this file: its kernels are instantiated behind all others (lol_gpu_internal.h).
  */
-static int scene_query(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, QuerySource src, size_t list_stride,
-                       const lol_gpu_hits* hits, const lol_gpu_shades* shades, bool no_output) {
-	/* 1. the list query's own refusals; a NULL `cams` is 2.'s, so the camera source_refused looks at is there */
-	static const lol_frame_camera no_cam = {};
-	if (src.pixels && !cams) src.cam = &no_cam;
-	LOL_TRY(source_refused(ctx, src, no_output));
-	/* 2. the records and their lists */
-	auto refuse = [&](const char* why) {
-		char text[128];
-		snprintf(text, sizeof text, "%s: %s", src.who, why);
-		return fail(ctx, LOL_GPU_ERR_ARG, text);
-	};
-	if (!scenes) return refuse("no scenes");
-	if (n_scenes < 1 || n_scenes > LOL_GPU_MAX_VIEWS) return refuse("the number of scenes is not in 1 ... LOL_GPU_MAX_VIEWS");
-	if (src.pixels && !cams) return refuse("no cameras");
-	if (list_stride != 0 && list_stride < src.n) return refuse("list_stride is neither 0 nor at least n");
-	if ((unsigned long long)n_scenes * (unsigned long long)src.n > 0xFFFFFFFFull) return refuse("more than 2^32 - 1 rays over all scenes");
-	/* 3. the scenes, as lol_gpu_render_scene_views refuses them */
-	LOL_TRY(scenes_refused(ctx, scenes, n_scenes));
-	if (src.n == 0) return LOL_GPU_OK;
-
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t s = src.stream ? static_cast<hipStream_t>(src.stream) : ctx->stream;
-	std::vector<lol::SceneView> views;
-	std::vector<uint32_t> data;
-	LOL_TRY(build_scene_records(ctx, src.pixels ? cams : nullptr, scenes, n_scenes, src.max_steps, true, views, data));
-	RingSet* S = nullptr;
-	LOL_TRY(queue_scene_records(ctx, views, data, s, &S));
-	lol::SceneList R = { reinterpret_cast<const lol::SceneView*>(S->d_buf), S->d_buf + views.size() * lol::SCENE_VIEW_DWORDS,
-	                     (unsigned long long)list_stride };
-	const lol_program& P = ctx->h_prog;
-	const int kind = ctx->interp_sqrt_kind;
-	hipError_t e;
-	if (hits) {
-		/* ray_query's RayQuery, without what the record brings: camera, first step, list, RAYS_SCENE_SANE */
-		lol::RayQuery Q;
-		memset(&Q, 0, sizeof Q);
-		Q.rays = src.rays;
-		Q.xy = src.xy;
-		Q.n = (uint32_t)src.n;
-		Q.max_steps = src.max_steps;
-		if (src.pixels) { Q.flags = lol::RAYS_FROM_PIXELS; Q.fw = (float)src.w; Q.fh = (float)src.h; }
-		if (hits->id) Q.flags |= lol::RAYS_WANT_ID;
-		if (hits->normal) Q.flags |= lol::RAYS_WANT_NORMAL;
-		Q.out = { hits->dist, hits->id, hits->steps, hits->normal };
-		const dim3 grid((unsigned)(((unsigned long long)Q.n + 63u) / 64u), (unsigned)n_scenes);
-		void* args[] = { &Q, &R };
-		e = stack_class_dispatch(interp_stack_class(P.max_stack), [&](auto v) {
-			constexpr int ssize = decltype(v)::ssize;
-			const void* k = kind == 3 ? reinterpret_cast<const void*>(&lol::trace_interp_scenes<ssize, 3>)
-			                          : reinterpret_cast<const void*>(&lol::trace_interp_scenes<ssize, 0>);
-			return hipLaunchKernel(k, grid, dim3(64), args, 0, s);
+static int scene_ray_query(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, const QuerySource& src,
+                           size_t list_stride, const lol_gpu_hits* out) {
+	const bool no_output = !out || (!out->dist && !out->id && !out->steps && !out->normal);
+	return guarded(ctx, "the scenes of a query", [&] {
+		return record_query(ctx, cams, scenes, n_scenes, src, list_stride, no_output, nullptr, "scene ray query launch", [&](lol::SceneList& R, hipStream_t s) {
+			/* ray_query's RayQuery, without what the record brings: camera, first step, list, RAYS_SCENE_SANE */
+			lol::RayQuery Q;
+			memset(&Q, 0, sizeof Q);
+			Q.rays = src.rays;
+			Q.xy = src.xy;
+			Q.n = (uint32_t)src.n;
+			Q.max_steps = src.max_steps;
+			if (src.pixels) { Q.flags = lol::RAYS_FROM_PIXELS; Q.fw = (float)src.w; Q.fh = (float)src.h; }
+			if (out->id) Q.flags |= lol::RAYS_WANT_ID;
+			if (out->normal) Q.flags |= lol::RAYS_WANT_NORMAL;
+			Q.out = { out->dist, out->id, out->steps, out->normal };
+			const dim3 grid = record_grid(src.n, 64u, n_scenes);
+			void* args[] = { &Q, &R };
+			const int kind = ctx->interp_sqrt_kind;
+			return stack_class_dispatch(interp_stack_class(ctx->h_prog.max_stack), [&](auto v) {
+				constexpr int ssize = decltype(v)::ssize;
+				const void* k = kind == 3 ? reinterpret_cast<const void*>(&lol::trace_interp_scenes<ssize, 3>)
+				                          : reinterpret_cast<const void*>(&lol::trace_interp_scenes<ssize, 0>);
+				return hipLaunchKernel(k, grid, dim3(64), args, 0, s);
+			});
 		});
-	} else {
-		/* launch_scene_query's Launch, without what the record brings: camera, first step, lists, tables, ambient colour, the skips */
-		lol::Launch L;
-		memset(&L, 0, sizeof L);
-		L.max_steps = src.max_steps;
-		L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
-		if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
-		L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
-		lol::ShadeQuery Q = {};
-		Q.rays = src.rays;
-		Q.xy = src.xy;
-		Q.n = (uint32_t)src.n;
-		if (src.pixels) {
-			Q.flags |= lol::SHADE_FROM_PIXELS;
-			L.fw = (float)src.w; L.fh = (float)src.h;
-			L.w = src.w; L.h = src.h;
-		}
-		Q.out = { shades->rgb_linear, shades->rgb, shades->pixel, shades->hit_dist, shades->hit_id, shades->steps };
-		const unsigned lds = tables_lds_bytes(P);
-		const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK), (unsigned)n_scenes);
-		void* args[] = { &L, &Q, &R };
-		e = interp_dispatch(ctx, [&](auto v) {
-			constexpr int ssize = decltype(v)::ssize;
-			constexpr bool tables_global = decltype(v)::tables_global;
-			const void* k = kind == 3 ? reinterpret_cast<const void*>(&lol::shade_interp_scenes<ssize, 3, tables_global>)
-			                          : reinterpret_cast<const void*>(&lol::shade_interp_scenes<ssize, 0, tables_global>);
-			return hipLaunchKernel(k, grid, dim3(lol::BLOCK), args, lds, s);
-		});
-	}
-	return ring_done(ctx, *S, s, e, hits ? "scene ray query launch" : "scene shading query launch");
+	});
 }
 
-/* no exception crosses the C boundary (the records are built in host memory) */
-static int scene_query_guarded(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, const QuerySource& src,
-                               size_t list_stride, const lol_gpu_hits* hits, const lol_gpu_shades* shades) {
-	const bool no_output = hits ? (!hits->dist && !hits->id && !hits->steps && !hits->normal)
-	                     : shades ? (!shades->rgb_linear && !shades->rgb && !shades->pixel && !shades->hit_dist && !shades->hit_id && !shades->steps) : true;
-	try { return scene_query(ctx, cams, scenes, n_scenes, src, list_stride, hits, shades, no_output); }
-	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a query"); }
-	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a query"); }
+static int scene_shade_query(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, const QuerySource& src,
+                             size_t list_stride, const lol_gpu_shades* out) {
+	const bool no_output = !out || (!out->rgb_linear && !out->rgb && !out->pixel && !out->hit_dist && !out->hit_id && !out->steps);
+	return guarded(ctx, "the scenes of a query", [&] {
+		return record_query(ctx, cams, scenes, n_scenes, src, list_stride, no_output, nullptr, "scene shading query launch", [&](lol::SceneList& R, hipStream_t s) {
+			/* launch_scene_query's Launch, without what the record brings: camera, first step, lists, tables, ambient colour, the skips */
+			lol::Launch L;
+			memset(&L, 0, sizeof L);
+			L.max_steps = src.max_steps;
+			context_launch_fields(ctx, L);
+			lol::ShadeQuery Q = {};
+			source_fields(src, L, Q);
+			Q.out = { out->rgb_linear, out->rgb, out->pixel, out->hit_dist, out->hit_id, out->steps };
+			void* args[] = { &L, &Q, &R };
+			return launch_interp(ctx, record_grid(src.n, lol::BLOCK, n_scenes), args, tables_lds_bytes(ctx->h_prog), s, [](auto v, auto kind) {
+				return reinterpret_cast<const void*>(&lol::shade_interp_scenes<decltype(v)::ssize, decltype(kind)::value, decltype(v)::tables_global>);
+			});
+		});
+	});
 }
 
 extern "C" {
 
 int lol_gpu_trace_scene_rays(lol_gpu* ctx, const lol_program* scenes, int n_scenes, const float* rays_dev, size_t n, size_t list_stride,
                              int max_steps, const lol_gpu_hits* out, void* stream) {
-	static const lol_gpu_hits none = {};
-	return scene_query_guarded(ctx, nullptr, scenes, n_scenes, rays_source("scene ray query", rays_dev, n, max_steps, stream), list_stride,
-	                           out ? out : &none, nullptr);
+	return scene_ray_query(ctx, nullptr, scenes, n_scenes, rays_source("scene ray query", rays_dev, n, max_steps, stream), list_stride, out);
 }
 
 int lol_gpu_trace_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, int w, int h, int max_steps,
                                const uint32_t* xy_dev, size_t n, size_t list_stride, const lol_gpu_hits* out, void* stream) {
-	static const lol_gpu_hits none = {};
-	return scene_query_guarded(ctx, cams, scenes, n_scenes, pixels_source("scene ray query", cams, w, h, xy_dev, n, max_steps, stream), list_stride,
-	                           out ? out : &none, nullptr);
+	return scene_ray_query(ctx, cams, scenes, n_scenes, pixels_source("scene ray query", cams, w, h, xy_dev, n, max_steps, stream), list_stride, out);
 }
 
 int lol_gpu_shade_scene_rays(lol_gpu* ctx, const lol_program* scenes, int n_scenes, const float* rays_dev, size_t n, size_t list_stride,
                              int max_steps, const lol_gpu_shades* out, void* stream) {
-	return scene_query_guarded(ctx, nullptr, scenes, n_scenes, rays_source("scene shading query", rays_dev, n, max_steps, stream), list_stride,
-	                           nullptr, out);
+	return scene_shade_query(ctx, nullptr, scenes, n_scenes, rays_source("scene shading query", rays_dev, n, max_steps, stream), list_stride, out);
 }
 
 int lol_gpu_shade_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, int w, int h, int max_steps,
                                const uint32_t* xy_dev, size_t n, size_t list_stride, const lol_gpu_shades* out, void* stream) {
-	return scene_query_guarded(ctx, cams, scenes, n_scenes, pixels_source("scene shading query", cams, w, h, xy_dev, n, max_steps, stream), list_stride,
-	                           nullptr, out);
+	return scene_shade_query(ctx, cams, scenes, n_scenes, pixels_source("scene shading query", cams, w, h, xy_dev, n, max_steps, stream), list_stride, out);
 }
 }  // extern "C"
 
 /*
  * Scene light passes (include/lol_gpu.h, "Scene light passes"; the kernels: lol_kernel_scene_light.h): a capture and a resolve whose
- * records are scenes of the uploaded program's structure.  A capture is a scene query (above) with a capture's planes: scene views'
- * records with the two skips that rest on a look cleared on EVERY record, scene views' ring and ONE launch of light_interp_scenes with
- * the record in the grid's y.  A resolve checks look r against scenes[r] as lol_gpu_relight checks a look against the uploaded
- * program, copies the looks' tables — a LookRecord each and, behind the records, lights | materials | root_material — through
- * lol_gpu::looks and launches relight_rays_scenes behind the copy.  The context's scene, kernels, keys, cached first step, tile-order
+ * records are scenes of the uploaded program's structure.  A capture is a scene query (record_query, above) with a capture's planes:
+ * scene views' records with the two skips that rest on a look cleared on EVERY record, scene views' ring and ONE launch of
+ * light_interp_scenes with the record in the grid's y.  A resolve checks look r against scenes[r] as lol_gpu_relight checks a look
+ * against the uploaded program and goes through record_resolve, as the averaged resolve below does: the looks' tables — a LookRecord
+ * each and, behind the records, lights | materials | root_material — through lol_gpu::looks and its kernel behind the copy.  The context's scene, kernels, keys, cached first step, tile-order
  * state, sample settings and other rings are neither read nor changed; no scene kernel takes over, and nothing waits for one.
  * Last in this file, its header included here: the kernels are instantiated behind all others (lol_gpu_internal.h).
  */
 #include "lol_kernel_scene_light.h"
 
-static int scene_light_query(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, QuerySource src, size_t list_stride,
-                             const lol_gpu_light_passes* out) {
-	/* 1. the capture's own refusals; a NULL `cams` is 2.'s, so the camera source_refused looks at is there */
-	static const lol_frame_camera no_cam = {};
-	if (src.pixels && !cams) src.cam = &no_cam;
-	LOL_TRY(source_refused(ctx, src, !out, out));
-	/* 2. the records, their lists and the planes of all of them */
-	auto refuse = [&](const char* why) {
-		char text[128];
-		snprintf(text, sizeof text, "%s: %s", src.who, why);
-		return fail(ctx, LOL_GPU_ERR_ARG, text);
-	};
-	if (!scenes) return refuse("no scenes");
-	if (n_scenes < 1 || n_scenes > LOL_GPU_MAX_VIEWS) return refuse("the number of scenes is not in 1 ... LOL_GPU_MAX_VIEWS");
-	if (src.pixels && !cams) return refuse("no cameras");
-	if (list_stride != 0 && list_stride < src.n) return refuse("list_stride is neither 0 nor at least n");
-	const unsigned long long N = (unsigned long long)n_scenes * (unsigned long long)src.n;
-	if (N > 0xFFFFFFFFull) return refuse("more than 2^32 - 1 rays over all scenes");
-	if (out->light_stride != 0 && out->light_stride < N) return refuse("light_stride is neither 0 nor at least n_scenes * n");
-	/* 3. the scenes, as lol_gpu_render_scene_views refuses them */
-	LOL_TRY(scenes_refused(ctx, scenes, n_scenes));
-	if (src.n == 0) return LOL_GPU_OK;
-
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t s = src.stream ? static_cast<hipStream_t>(src.stream) : ctx->stream;
-	std::vector<lol::SceneView> views;
-	std::vector<uint32_t> data;
-	LOL_TRY(build_scene_records(ctx, src.pixels ? cams : nullptr, scenes, n_scenes, src.max_steps, true, views, data));
-	/* every factor of every ray, as at every capture: a look may differ from the record in exactly what the two skips rest on */
-	for (lol::SceneView& V : views) V.flags &= ~(lol::FLAG_MISS_SKIP | lol::FLAG_DARK_SKIP);
-	RingSet* S = nullptr;
-	LOL_TRY(queue_scene_records(ctx, views, data, s, &S));
-	lol::SceneList R = { reinterpret_cast<const lol::SceneView*>(S->d_buf), S->d_buf + views.size() * lol::SCENE_VIEW_DWORDS,
-	                     (unsigned long long)list_stride };
-	const lol_program& P = ctx->h_prog;
-	/* launch_scene_query's Launch, without what the record brings: camera, first step, lists, tables, ambient colour, the skips */
-	lol::Launch L;
-	memset(&L, 0, sizeof L);
-	L.max_steps = src.max_steps;
-	L.n_lights = P.n_lights; L.n_materials = P.n_materials; L.n_roots = P.n_roots;
-	lol::LightQuery Q = {};
-	Q.rays = src.rays;
-	Q.xy = src.xy;
-	Q.n = (uint32_t)src.n;
-	if (src.pixels) {
-		Q.flags |= lol::SHADE_FROM_PIXELS | (src.xy ? 0u : lol::LIGHT_ALL_PIXELS);
-		L.fw = (float)src.w; L.fh = (float)src.h;
-		L.w = src.w; L.h = src.h;
-	}
-	Q.stride = out->light_stride ? out->light_stride : N;
-	Q.out = { reinterpret_cast<lol::LightFactor*>(out->factors), out->hit_id, out->hit_dist, out->march_steps };
-	const unsigned lds = tables_lds_bytes(P);
-	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK), (unsigned)n_scenes);
-	void* args[] = { &L, &Q, &R };
-	const int kind = ctx->interp_sqrt_kind;
-	const hipError_t e = interp_dispatch(ctx, [&](auto v) {
-		constexpr int ssize = decltype(v)::ssize;
-		constexpr bool tables_global = decltype(v)::tables_global;
-		const void* k = kind == 3 ? reinterpret_cast<const void*>(&lol::light_interp_scenes<ssize, 3, tables_global>)
-		                          : reinterpret_cast<const void*>(&lol::light_interp_scenes<ssize, 0, tables_global>);
-		return hipLaunchKernel(k, grid, dim3(lol::BLOCK), args, lds, s);
+static int scene_light_query(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, const QuerySource& src,
+                             size_t list_stride, const lol_gpu_light_passes* out) {
+	return guarded(ctx, "the scenes of a capture", [&] {
+		return record_query(ctx, cams, scenes, n_scenes, src, list_stride, !out, out, "scene light pass launch", [&](lol::SceneList& R, hipStream_t s) {
+			/* launch_scene_query's Launch, without what the record brings: camera, first step, lists, tables, ambient colour, the skips —
+			 * and without gamma table and pixel format: a capture packs no pixel */
+			lol::Launch L;
+			memset(&L, 0, sizeof L);
+			L.max_steps = src.max_steps;
+			launch_counts(ctx, L);
+			lol::LightQuery Q = {};
+			source_fields(src, L, Q);
+			Q.stride = out->light_stride ? out->light_stride : (unsigned long long)n_scenes * (unsigned long long)src.n;
+			Q.out = { reinterpret_cast<lol::LightFactor*>(out->factors), out->hit_id, out->hit_dist, out->march_steps };
+			void* args[] = { &L, &Q, &R };
+			return launch_interp(ctx, record_grid(src.n, lol::BLOCK, n_scenes), args, tables_lds_bytes(ctx->h_prog), s, [](auto v, auto kind) {
+				return reinterpret_cast<const void*>(&lol::light_interp_scenes<decltype(v)::ssize, decltype(kind)::value, decltype(v)::tables_global>);
+			});
+		});
 	});
-	return ring_done(ctx, *S, s, e, "scene light pass launch");
 }
 
 /* 4. of both resolves over records: the first looks[r] that is no look of scenes[r], by its record, behind `who` */
 static int record_looks_refused(lol_gpu* ctx, const char* who, const lol_program* scenes, const lol_program* looks, int n_records) {
-	if (looks)
-		for (int r = 0; r < n_records; r++)
-			if (const char* why = look_differs(scenes[r], looks[r])) {
-				char text[200];
-				if (strncmp(why, "relight: ", 9) == 0) why += 9;
-				snprintf(text, sizeof text, "%s: record %d: %s", who, r, why);
-				return fail(ctx, LOL_GPU_ERR_ARG, text);
-			}
+	char text[200];
+	for (int r = 0; looks && r < n_records; r++)
+		if (const char* why = look_differs(scenes[r], looks[r], who, r, "look", true, text)) return fail(ctx, LOL_GPU_ERR_ARG, why);
 	return LOL_GPU_OK;
 }
 
@@ -2835,12 +2797,7 @@ static int queue_record_looks(lol_gpu* ctx, const lol_program* scenes, const lol
 		rec.tables_offset = (uint32_t)((size_t)r * nt4);
 		rec.ambient[0] = K.ambient_color.x; rec.ambient[1] = K.ambient_color.y; rec.ambient[2] = K.ambient_color.z;
 		memcpy(S->h_buf + (size_t)r * lol::LOOK_RECORD_DWORDS, &rec, sizeof rec);
-		uint32_t* t = S->h_buf + head + rec.tables_offset;
-		if (U.n_lights) memcpy(t, K.lights, (size_t)U.n_lights * sizeof(lol_light));
-		t += (size_t)U.n_lights * lol::LIGHT_DWORDS;
-		memcpy(t, K.materials, (size_t)U.n_materials * sizeof(lol_material));
-		t += (size_t)U.n_materials * lol::MATERIAL_DWORDS;
-		if (U.n_roots) memcpy(t, K.root_material, (size_t)U.n_roots * 4);
+		pack_tables(S->h_buf + head + rec.tables_offset, K);      /* (its counts are U's: scenes_refused and record_looks_refused have run) */
 	}
 	const hipError_t ce = ring_copy(*S, need * 4, s);
 	if (ce != hipSuccess) return ring_done(ctx, *S, s, ce, "copy of the tables of the looks of a relight over scenes");
@@ -2848,14 +2805,22 @@ static int queue_record_looks(lol_gpu* ctx, const lol_program* scenes, const lol
 	return LOL_GPU_OK;
 }
 
-/* relight_launch_fields' Launch without the context's tables and ambient colour, which the records bring: counts, gamma table, pixel
- * format */
-static void record_resolve_launch_fields(lol_gpu* ctx, lol::Launch& L) {
-	const lol_program& U = ctx->h_prog;
+/* Everything behind a filled query of a resolve over records: the call's device and stream, the looks through their ring, the Launch —
+ * relight_launch_fields' without the context's tables and ambient colour, which the records bring: context_launch_fields alone —, the
+ * launch of `fn` on `grid` with `lds` bytes behind the copy, and the ring's event behind it, `what` its name */
+template <class Query>
+static int record_resolve(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, int n_records, void* stream, Query& Q, dim3 grid,
+                          unsigned lds, const void* fn, const char* what) {
+	LOL_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+	RingSet* S = nullptr;
+	lol::LookList R;
+	LOL_TRY(queue_record_looks(ctx, scenes, looks, n_records, s, S, R));
+	lol::Launch L;
 	memset(&L, 0, sizeof L);
-	L.n_lights = U.n_lights; L.n_materials = U.n_materials; L.n_roots = U.n_roots;
-	if (ctx->gamma_table) { L.flags |= lol::FLAG_GAMMA_TABLE; L.gamma_table = ctx->d_gamma; }
-	L.fmt_shift = ctx->fmt_shift; L.fmt_loss = ctx->fmt_loss; L.fmt_amask = ctx->fmt_amask;
+	context_launch_fields(ctx, L);
+	void* args[] = { &L, &Q, &R };
+	return ring_done(ctx, *S, s, hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s), what);
 }
 
 static int relight_scenes(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, int n_scenes, const lol_gpu_light_passes* in,
@@ -2876,47 +2841,26 @@ static int relight_scenes(lol_gpu* ctx, const lol_program* scenes, const lol_pro
 	LOL_TRY(record_looks_refused(ctx, "relight scenes", scenes, looks, n_scenes));
 	if (n == 0) return LOL_GPU_OK;
 
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
 	const lol_program& U = ctx->h_prog;
-	RingSet* S = nullptr;
-	lol::LookList R;
-	LOL_TRY(queue_record_looks(ctx, scenes, looks, n_scenes, s, S, R));
-	lol::Launch L;
-	record_resolve_launch_fields(ctx, L);
 	lol::RelightQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
-	Q.stride = in->light_stride ? in->light_stride : N;
-	Q.hit_id = in->hit_id;
+	resolve_planes(Q, in, N, out);
 	Q.n = (uint32_t)n;
-	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
-	const dim3 grid((unsigned)(((unsigned long long)Q.n + lol::BLOCK - 1) / lol::BLOCK), (unsigned)n_scenes);
-	void* args[] = { &L, &Q, &R };
 	const void* fn = lol::tables_in_lds(U.n_lights, U.n_materials, U.n_roots) ? reinterpret_cast<const void*>(&lol::relight_rays_scenes<false>)
 	                                                                          : reinterpret_cast<const void*>(&lol::relight_rays_scenes<true>);
-	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, tables_lds_bytes(U), s);
-	return ring_done(ctx, *S, s, e, "relight scenes launch");
+	return record_resolve(ctx, scenes, looks, n_scenes, stream, Q, record_grid(n, lol::BLOCK, n_scenes), tables_lds_bytes(U), fn, "relight scenes launch");
 }
 
 extern "C" {
 
-/* no exception crosses the C boundary (the records are built in host memory) */
 int lol_gpu_light_scene_rays(lol_gpu* ctx, const lol_program* scenes, int n_scenes, const float* rays_dev, size_t n, size_t list_stride,
                              int max_steps, const lol_gpu_light_passes* out, void* stream) {
-	try { return scene_light_query(ctx, nullptr, scenes, n_scenes, rays_source("scene light passes", rays_dev, n, max_steps, stream), list_stride, out); }
-	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a capture"); }
-	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a capture"); }
+	return scene_light_query(ctx, nullptr, scenes, n_scenes, rays_source("scene light passes", rays_dev, n, max_steps, stream), list_stride, out);
 }
 
 int lol_gpu_light_scene_pixels(lol_gpu* ctx, const lol_frame_camera* cams, const lol_program* scenes, int n_scenes, int w, int h, int max_steps,
                                const uint32_t* xy_dev, size_t n, size_t list_stride, const lol_gpu_light_passes* out, void* stream) {
-	try {
-		return scene_light_query(ctx, cams, scenes, n_scenes, pixels_source("scene light passes", cams, w, h, xy_dev, n, max_steps, stream, true),
-		                         list_stride, out);
-	}
-	catch (const std::bad_alloc&) { return fail(ctx, LOL_GPU_ERR_HIP, "out of host memory while preparing the scenes of a capture"); }
-	catch (...) { return fail(ctx, LOL_GPU_ERR_HIP, "unexpected failure while preparing the scenes of a capture"); }
+	return scene_light_query(ctx, cams, scenes, n_scenes, pixels_source("scene light passes", cams, w, h, xy_dev, n, max_steps, stream, true),
+	                         list_stride, out);
 }
 
 int lol_gpu_relight_scenes(lol_gpu* ctx, const lol_program* scenes, const lol_program* looks, int n_scenes, const lol_gpu_light_passes* in,
@@ -2954,34 +2898,20 @@ static int relight_scene_views(lol_gpu* ctx, const lol_program* scenes, const lo
 	/* 4. the looks, each against its own scene: the first that is no look of it, by its record */
 	LOL_TRY(record_looks_refused(ctx, "relight scene views", scenes, looks, (int)records));
 
-	LOL_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
 	const lol_program& U = ctx->h_prog;
-	RingSet* S = nullptr;
-	lol::LookList R;
-	LOL_TRY(queue_record_looks(ctx, scenes, looks, (int)records, s, S, R));
-	lol::Launch L;
-	record_resolve_launch_fields(ctx, L);
 	lol::RelightSceneViewsQuery Q;
-	memset(&Q, 0, sizeof Q);
-	Q.factors = reinterpret_cast<const lol::LightFactor*>(in->factors);
-	Q.stride = in->light_stride ? in->light_stride : N;
-	Q.hit_id = in->hit_id;
+	resolve_planes(Q, in, N, out);
 	Q.w = (uint32_t)w; Q.h = (uint32_t)h;
 	Q.s_log2 = samples == 4 ? 2u : samples == 2 ? 1u : 0u;
 	Q.cams = (uint32_t)cams_per_view;
-	Q.rgb_linear = out->rgb_linear; Q.rgb = out->rgb; Q.pixel = out->pixel;
 	/* a wave per 64 pixels of ONE view, whatever s and K: it takes them in s^2 rounds of 64 / s^2 */
 	const unsigned long long lanes = ((unsigned long long)w * (unsigned long long)h + 63u) / 64u * 64u;
-	const dim3 grid((unsigned)((lanes + lol::BLOCK - 1) / lol::BLOCK), (unsigned)n_views);
 	/* the K looks of a view staged as one run where they fit, read where they lie where they do not: the kernel's rule */
 	const bool staged = lol::views_looks_in_lds(Q.cams, U.n_lights, U.n_materials, U.n_roots);
 	const unsigned lds = staged ? Q.cams * lol::look_stride(U.n_lights, U.n_materials, U.n_roots) * 4u : 0u;
-	void* args[] = { &L, &Q, &R };
 	const void* fn = staged ? reinterpret_cast<const void*>(&lol::relight_views_scenes<false>)
 	                        : reinterpret_cast<const void*>(&lol::relight_views_scenes<true>);
-	const hipError_t e = hipLaunchKernel(fn, grid, dim3(lol::BLOCK), args, lds, s);
-	return ring_done(ctx, *S, s, e, "relight scene views launch");
+	return record_resolve(ctx, scenes, looks, (int)records, stream, Q, record_grid(lanes, lol::BLOCK, n_views), lds, fn, "relight scene views launch");
 }
 
 extern "C" {

@@ -799,6 +799,17 @@ class Renderer:
             C.memmove(C.byref(arr, i * C.sizeof(S.FrameCamera)), C.byref(fc), C.sizeof(S.FrameCamera))
         return keep, progs, arr
 
+    def _record_looks(self, who: str, looks, n_records: int):
+        """(keep, programs or None) of the looks of a resolve over n_records records (`who`, for its error): one per record as
+        _scene_records takes scenes, or None: the scenes' own"""
+        if looks is None:
+            return [], None
+        look_items = list(looks)
+        if len(look_items) != n_records:
+            raise ValueError(who + ": one look per scene")
+        keep, look_progs, _ = self._scene_records(who, look_items)
+        return keep, look_progs
+
     def trace_scene_rays_into(self, scenes, rays_ptr: int, n: int, list_stride: int = 0, max_steps: int = 256, dist_ptr: int = 0,
                               id_ptr: int = 0, steps_ptr: int = 0, normal_ptr: int = 0, stream: int | None = None):
         """Asynchronously trace n rays under EACH of len(scenes) scenes of the prepared scene's structure (lol_gpu_trace_scene_rays):
@@ -1284,18 +1295,12 @@ class Renderer:
         relight_into's on a renderer that prepared scenes[r]; outputs dense over r n + i, as relight_into's."""
         items = list(scenes)
         keep, progs, _ = self._scene_records("relight_scenes_into", items)
-        look_progs = None
-        if looks is not None:
-            look_items = list(looks)
-            if len(look_items) != len(items):
-                raise ValueError("relight_scenes_into: one look per scene")
-            keep_looks, look_progs, _ = self._scene_records("relight_scenes_into", look_items)
-            keep += keep_looks
+        keep_looks, look_progs = self._record_looks("relight_scenes_into", looks, len(items))
         planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
         self._check(self._lib.lol_gpu_relight_scenes(self._ctx, progs, look_progs, len(items), C.byref(planes), n, C.byref(out),
                                                      _stream_arg(stream)))
-        del keep
+        del keep, keep_looks
 
     # ---- relit scene views (include/lol_gpu.h, "Relit scene views")
     def relight_scene_views_into(self, scenes, looks=None, n_views: int = 0, cameras_per_view: int = 1, w: int = 0, h: int = 0,
@@ -1313,18 +1318,12 @@ class Renderer:
         if len(items) != int(n_views) * k:
             raise ValueError("relight_scene_views_into: len(scenes) must be n_views * cameras_per_view")
         keep, progs, _ = self._scene_records("relight_scene_views_into", items)
-        look_progs = None
-        if looks is not None:
-            look_items = list(looks)
-            if len(look_items) != len(items):
-                raise ValueError("relight_scene_views_into: one look per scene")
-            keep_looks, look_progs, _ = self._scene_records("relight_scene_views_into", look_items)
-            keep += keep_looks
+        keep_looks, look_progs = self._record_looks("relight_scene_views_into", looks, len(items))
         planes = LightPasses(factors_ptr or None, light_stride, id_ptr or None, None, None)
         out = Relit(rgb_linear_ptr or None, rgb_ptr or None, pixel_ptr or None)
         self._check(self._lib.lol_gpu_relight_scene_views(self._ctx, progs, look_progs, C.byref(planes), int(n_views), k, w, h,
                                                           int(samples), C.byref(out), _stream_arg(stream)))
-        del keep
+        del keep, keep_looks
 
     def set_cull(self, enable: bool):
         """Exact bounding-sphere culling of top-level objects in the specialised kernel; takes effect at the next prepare()."""
